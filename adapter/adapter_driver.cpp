@@ -2,12 +2,15 @@
 // drives the adapter exactly like laserMapping::performSLAMOptimization does (src/LaserMapping/laserMapping.cpp:703-741):
 // first frame with initialization == false (map seeding), then Localization() per frame, reading back the public fields.
 //
-//   adapter_driver <in.bin> <out.bin>
+//   adapter_driver <in.bin> <out.bin> [--sequence]
 // in.bin : int32 n_frames, float32 plane_res, int32 max_iterations, int32 max_surface_features; per frame: int32 n,
 //          float64 guess[7], float64 time, float32 xyz[n][3]  (sensor frame, as the node passes it)
 // out.bin: per frame: int32 status, int32 startupCount, int32 pos_in_localmap[3], float64 T_w_lidar[7] (tx ty tz qx qy qz qw),
 //          int32 n_iterations, int32 surf_from_map, float64 total_translation, float64 uncertainty[6],
 //          int32 num_surf of the last iteration, uint32 flags;  then: uint64 map size, float32 map xyz (5x5 neighbourhood)
+// --sequence: a replay (LidarSLAM::LocalizationSequence): frame 0 seeds the map, frames 1.. run as ONE sequence from guess 1 with the
+//          motion predictions guess_(k-1)^-1 * guess_k; prints one line per frame (index and pose, %.17g) and writes
+//          out.bin: int32 status, int32 n_done, float64 T_w_lidar[n_done][7]
 #include <cstdint>
 #include <cstdio>
 #include <cstring>
@@ -20,6 +23,24 @@ using namespace super_odometry_soicp;
 
 template <typename T> static T rd(FILE* f) { T v; if (fread(&v, sizeof(T), 1, f) != 1) throw std::runtime_error("short input"); return v; }
 template <typename T> static void wr(FILE* f, const T& v) { fwrite(&v, sizeof(T), 1, f); }
+
+// a^-1 * b (Twist.h:172-185): the motion prediction that takes pose a to pose b, in a's frame
+static Transformd between(const Transformd& a, const Transformd& b) {
+  const Quaterniond& q = a.rot;
+  const double ax = -q.x(), ay = -q.y(), az = -q.z(), aw = q.w();  // conj(q)
+  const double vx = b.pos.x() - a.pos.x(), vy = b.pos.y() - a.pos.y(), vz = b.pos.z() - a.pos.z();
+  // t = conj(q) v conj(q)^-1 = v + 2 w (u x v) + 2 u x (u x v), u = (ax, ay, az)
+  const double cx = ay * vz - az * vy, cy = az * vx - ax * vz, cz = ax * vy - ay * vx;
+  const double tx = vx + 2 * (aw * cx + ay * cz - az * cy), ty = vy + 2 * (aw * cy + az * cx - ax * cz), tz = vz + 2 * (aw * cz + ax * cy - ay * cx);
+  const Quaterniond& r = b.rot;
+  const double w = aw * r.w() - ax * r.x() - ay * r.y() - az * r.z();
+  const double x = aw * r.x() + ax * r.w() + ay * r.z() - az * r.y();
+  const double y = aw * r.y() - ax * r.z() + ay * r.w() + az * r.x();
+  const double z = aw * r.z() + ax * r.y() - ay * r.x() + az * r.w();
+  Transformd d;
+  d.pos = Vector3d(tx, ty, tz); d.rot = Quaterniond(w, x, y, z);
+  return d;
+}
 
 int main(int argc, char** argv) {
   if (argc < 3) { fprintf(stderr, "usage: %s in.bin out.bin\n", argv[0]); return 2; }
@@ -50,6 +71,27 @@ int main(int argc, char** argv) {
       guesses.push_back(T);
     }
     auto edge = std::make_shared<PointCloud<Point>>();  // dead path: the node still passes it
+    if (argc > 3 && std::strcmp(argv[3], "--sequence") == 0) {
+      if (n_frames < 2) throw std::runtime_error("--sequence needs at least two frames");
+      slam.Localization(false, LidarSLAM::PredictionSource::LIO_ODOM, guesses[0], edge, clouds[0], times[0]);  // seeds the map
+      std::vector<PointCloud<Point>::Ptr> run(clouds.begin() + 1, clouds.end());
+      std::vector<double> run_times(times.begin() + 1, times.end());
+      std::vector<Transformd> predictions(run.size());
+      for (size_t k = 1; k < run.size(); ++k) predictions[k] = between(guesses[k], guesses[k + 1]);
+      std::vector<Transformd> poses;
+      const int n_done = slam.LocalizationSequence(guesses[1], run, predictions, run_times, &poses);
+      wr<int32_t>(out, slam.last_status); wr<int32_t>(out, n_done);
+      for (int k = 0; k < n_done; ++k) {
+        const Transformd& T = poses[(size_t)k];
+        const double p[7] = {T.pos.x(), T.pos.y(), T.pos.z(), T.rot.x(), T.rot.y(), T.rot.z(), T.rot.w()};
+        for (double v : p) wr<double>(out, v);
+        printf("frame %d: %.17g %.17g %.17g %.17g %.17g %.17g %.17g\n", k + 1, p[0], p[1], p[2], p[3], p[4], p[5], p[6]);
+      }
+      printf("status %d, %d of %d frames registered and inserted, map %zu points\n", slam.last_status, n_done, (int)run.size(),
+             slam.localMap.getAllLocalMap().points.size());
+      fclose(in); fclose(out);
+      return 0;
+    }
     bool initialization = false;                        // laserMapping.cpp: first frame seeds the map
     for (int f = 0; f < n_frames; ++f) {
       if (f + 1 < n_frames && f >= 1) slam.StageNextScan(clouds[f + 1]);  // what the feature callback would do

@@ -3,6 +3,7 @@
 // on this path (process() catches std::exception, logs and continues: src/LaserMapping/laserMapping.cpp:788-790).
 #include "lidar_slam_soicp.h"
 
+#include <algorithm>
 #include <stdexcept>
 
 namespace super_odometry_soicp {
@@ -115,6 +116,51 @@ void LidarSLAM::Localization(bool initialization, PredictionSource /*predictodom
   last_status = so_icp_localization(gpu_, initialization ? 1 : 0, T_in, xyz, n, sizeof(Point), timeLaserOdometry, T_out, &last_raw);
   if (last_status < 0) throw std::runtime_error(std::string("so_icp_localization: ") + so_icp_last_error(gpu_));
   read_back(edge_point ? (int32_t)edge_point->points.size() : 0, T_out, timeLaserOdometry);
+}
+
+int LidarSLAM::LocalizationSequence(Transformd position, const std::vector<PointCloud<Point>::Ptr>& planner_points,
+                                    const std::vector<Transformd>& predictions, const std::vector<double>& times,
+                                    std::vector<Transformd>* poses_out, std::vector<so_icp_stats>* stats_out) {
+  const size_t count = planner_points.size();
+  if (predictions.size() != count || times.size() != count) throw std::invalid_argument("LocalizationSequence: one prediction and one stamp per cloud");
+  ensure_context();
+  push_knobs();
+  if (count == 0) return 0;
+  auto to7 = [](const Transformd& T, double* o) {
+    o[0] = T.pos.x(); o[1] = T.pos.y(); o[2] = T.pos.z(); o[3] = T.rot.x(); o[4] = T.rot.y(); o[5] = T.rot.z(); o[6] = T.rot.w();
+  };
+  std::vector<const void*> scans(count);
+  std::vector<size_t> n(count);
+  std::vector<double> deltas(7 * count), poses(7 * count);
+  std::vector<so_icp_stats> st(count);
+  for (size_t k = 0; k < count; ++k) {
+    const PointCloud<Point>* cl = planner_points[k].get();
+    n[k] = cl ? cl->points.size() : 0;
+    scans[k] = n[k] ? static_cast<const void*>(cl->points.data()) : nullptr;
+    to7(predictions[k], &deltas[7 * k]);
+  }
+  double T_in[7];
+  to7(position, T_in);
+  int n_done = 0;
+  last_status = so_icp_localization_sequence(gpu_, (int)count, scans.data(), n.data(), sizeof(Point), 0, T_in, deltas.data(), times.data(),
+                                             poses.data(), nullptr, st.data(), &n_done);
+  if (last_status < 0) throw std::runtime_error(std::string("so_icp_localization_sequence: ") + so_icp_last_error(gpu_));
+  if (poses_out) {
+    poses_out->clear();
+    for (int k = 0; k < n_done; ++k) {
+      Transformd T;
+      T.pos = Vector3d(poses[7 * k], poses[7 * k + 1], poses[7 * k + 2]);
+      T.rot = Quaterniond(poses[7 * k + 6], poses[7 * k + 3], poses[7 * k + 4], poses[7 * k + 5]);
+      poses_out->push_back(T);
+    }
+  }
+  if (stats_out) stats_out->assign(st.begin(), st.begin() + n_done);
+  // the public fields: those of the last frame the run reached (the one that stopped it, if any)
+  // (a frame stopped by SO_ICP_NOT_ENOUGH_MAP_FEATURES reports its guess as its pose, like so_icp_localization)
+  const size_t last = std::min((size_t)n_done, count - 1);
+  last_raw = st[last];
+  read_back(0, &poses[7 * last], times[last]);
+  return n_done;
 }
 
 void LidarSLAM::AnnounceSurf(const float* xyz, size_t n, size_t stride_bytes) {

@@ -73,6 +73,15 @@ class LidarSLAM {
   // LidarSlam.h:292-293
   void Localization(bool initialization, PredictionSource predictodom, Transformd T_w_lidar_in, PointCloud<Point>::Ptr edge_point,
                     PointCloud<Point>::Ptr planner_point, double timeLaserOdometry);
+  // A replayed run (a recorded log, a map built offline): Localization(true, ...) for every cloud, the guess of frame k being
+  // poses[k-1] * predictions[k] (laserMapping.cpp:345-372, T_w_lidar = T_w_lidar * prediction; predictions[0] unused, the first
+  // frame starts from T_w_lidar_in) -- one so_icp_localization_sequence call, the same poses, statistics and map as that loop.  The map
+  // must be seeded.  Returns the number of frames registered and inserted (fewer when a frame had too little map: last_status says
+  // so); the public fields afterwards describe the last frame run.  Not the live node's path: the node drops a backlog
+  // (clearSensorData, laserMapping.cpp:689-699).
+  int LocalizationSequence(Transformd T_w_lidar_in, const std::vector<PointCloud<Point>::Ptr>& planner_points,
+                           const std::vector<Transformd>& predictions, const std::vector<double>& timesLaserOdometry,
+                           std::vector<Transformd>* poses_out = nullptr, std::vector<so_icp_stats>* stats_out = nullptr);
   // optional: announce the planar cloud of the NEXT frame (the feature callback has it before process() reaches it)
   void StageNextScan(const PointCloud<Point>::Ptr& planner_point);
   // laserMapping::adjustVoxelSize (laserMapping.cpp:600-651) for the surf cloud on the device: cloud statistic (auto voxel size),

@@ -245,7 +245,9 @@ int so_icp_register(so_icp_ctx *ctx, const float *scan_xyz, size_t n, size_t str
  * the device --, so the device does not idle for the host's turn-around between two calls (~11 us of a 140 us registration), and
  * scan k+1 is copied and binned beside registration k under the predicted guess.  A registration that turns out to need more outer
  * iterations than were enqueued ahead is finished the ordinary way and the one behind it starts again (so_icp_timing::seq_chain_breaks).
- * The map is NOT updated in between (localization mode, LS.cpp:60-80 `if (!localization_mode)`): use so_icp_localization per scan when it must be.
+ * The map is NOT updated in between: the whole run is registered against a fixed (prior) map -- an extension for replay, not the reference's
+ * loop, which inserts every registered frame (LidarSlam.cpp:154-167; `localization_mode` only chooses the prior map and the start pose,
+ * laserMapping.cpp:163-173, 306).  so_icp_localization_sequence below runs the reference's register-then-insert order.
  * scans[k]: host pointers (packed or strided xyz; memory from so_icp_host_alloc / so_icp_host_register is copied by DMA) or, with
  * scans_on_device, device pointers to packed xyz.  deltas: count x 7 {dx, dy, dz, qx, qy, qz, qw}, row 0 unused.  poses_out: count x 7;
  * guesses_out (count x 7, nullable): the guess each registration started from; stats (count, nullable); n_done (nullable): registrations
@@ -256,6 +258,23 @@ int so_icp_register(so_icp_ctx *ctx, const float *scan_xyz, size_t n, size_t str
 int so_icp_register_sequence(so_icp_ctx *ctx, int count, const void *const *scans, const size_t *n_points, size_t stride_bytes,
                              int scans_on_device, const double pose0[7], const double *deltas, double *poses_out, double *guesses_out,
                              so_icp_stats *stats, int *n_done);
+/* A run of frames in the reference's per-frame order (LidarSlam.cpp:30-51, 107-167): for k = 0..count-1
+ *   guess_k = (k == 0 ? pose0 : pose_out_(k-1) o delta_k); register scan k from guess_k (as so_icp_localization);
+ *   checkMotionThresholds bookkeeping with times[k]; insert T_k * scan_k into the map (transformAndAddToMap).
+ * Equivalent, bit for bit, to `count` so_icp_localization(_dev) calls (initialization = 1) from guesses_out[k],
+ * including the map after every frame.  The map must already be seeded.  Returns like so_icp_register_sequence
+ * (first error / SO_ICP_NOT_ENOUGH_MAP_FEATURES stops the run at that frame; *n_done frames were registered AND inserted).
+ * Unlike so_icp_register_sequence the chain continues from pose_out_(k-1), the pose AFTER MannualYawCorrection (LidarSlam.cpp:891-913),
+ * as the node does (`T_w_lidar = T_w_lidar * prediction`, laserMapping.cpp:345-372); so_icp_register_sequence continues from the
+ * optimised pose before it.  An extension for replaying a log or building a map offline: the reference node drops a backlog
+ * (clearSensorData, laserMapping.cpp:689-699).  times: count stamps (time_laser_odometry of each frame); the other arguments as for
+ * so_icp_register_sequence.  A convenience entry: the frames run one after the other through the per-frame entry points (registration
+ * k + 1 is NOT enqueued before the host has read frame k's report: the insert of k needs the host's pose_out_k), so it takes as long
+ * as the caller's own loop.
+ * A host-only context fails with SO_ICP_E_HIP before touching its map; count == 0 does nothing. */
+int so_icp_localization_sequence(so_icp_ctx *ctx, int count, const void *const *scans, const size_t *n_points,
+                                 size_t stride_bytes, int scans_on_device, const double pose0[7], const double *deltas,
+                                 const double *times, double *poses_out, double *guesses_out, so_icp_stats *stats, int *n_done);
 /* A backlog worked off in several calls: name the scan that will START the next so_icp_register_sequence call (packed xyz in host memory,
  * n points) and the motion prediction from the LAST scan of the coming call to it.  That call then copies and bins it beside its last
  * registration, and the call after it -- whose scans[0] is this very buffer -- starts with its first sweep instead of a copy and a binning

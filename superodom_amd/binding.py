@@ -95,7 +95,8 @@ EXPORTED = ["so_icp_default_config", "so_icp_create", "so_icp_destroy", "so_icp_
             "so_icp_localization_dev", "so_icp_download_scan", "so_icp_prefilter_scan", "so_icp_stage_scan", "so_icp_debug_match_status", "so_icp_comm_init_inprocess", "so_icp_peer_export", "so_icp_peer_connect", "so_icp_peer_enable",
             "so_icp_deskew_scan", "so_icp_deskew_scan_dev", "so_icp_transform_cloud", "so_icp_shard_histogram",
             "so_icp_host_register", "so_icp_host_unregister", "so_icp_host_alloc", "so_icp_host_free", "so_icp_device_count", "so_icp_stage_cancel",
-            "so_icp_map_insert_stats", "so_icp_register_sequence", "so_icp_map_export_records", "so_icp_sequence_announce_next", "so_icp_debug_neighbours", "so_icp_prefilter_announce"]
+            "so_icp_map_insert_stats", "so_icp_register_sequence", "so_icp_map_export_records", "so_icp_sequence_announce_next", "so_icp_debug_neighbours", "so_icp_prefilter_announce",
+            "so_icp_localization_sequence"]
 
 _lib = None
 
@@ -133,6 +134,8 @@ def load():
     L.so_icp_register_dev.argtypes = [vp, vp, C.c_size_t, f64p, f64p, C.POINTER(Stats)]
     L.so_icp_sequence_announce_next.argtypes = [vp, f32p, C.c_size_t, f64p]
     L.so_icp_register_sequence.argtypes = [vp, C.c_int, C.POINTER(vp), C.POINTER(C.c_size_t), C.c_size_t, C.c_int, f64p, f64p, f64p, f64p, C.POINTER(Stats), i32p]
+    L.so_icp_localization_sequence.argtypes = [vp, C.c_int, C.POINTER(vp), C.POINTER(C.c_size_t), C.c_size_t, C.c_int, f64p, f64p, f64p, f64p, f64p,
+                                               C.POINTER(Stats), i32p]
     L.so_icp_upload_scan.argtypes = [vp, f32p, C.c_size_t, C.c_size_t, C.POINTER(vp)]
     L.so_icp_free_scan.argtypes = [vp, vp]
     L.so_icp_localization.argtypes = [vp, C.c_int, f64p, f32p, C.c_size_t, C.c_size_t, C.c_double, f64p, C.POINTER(Stats)]
@@ -407,6 +410,37 @@ class LidarSlamGpu:
                                                      deltas.ctypes.data_as(_F64P), out.ctypes.data_as(_F64P), guesses.ctypes.data_as(_F64P), st, C.byref(n_done))
         keep = (ptrs, ns, pose0, deltas, scans)
         return (lambda: fn(*args)), out, guesses, st, n_done, keep
+
+    def prepare_localization_sequence(self, scans, pose0, deltas, times, on_device=False):
+        """so_icp_localization_sequence with pre-built arguments (register + insert per frame, the reference's order).  scans: contiguous
+        float32 (n, 3) host arrays, or (device pointer, n) pairs with on_device.  deltas: (count, 7), row 0 unused; times: count stamps.
+        Returns (call, poses_out, guesses_out, stats array, n_done, keep-alive): call() performs the C call and returns its code."""
+        count = len(scans)
+        ptrs = (C.c_void_p * max(count, 1))(); ns = (C.c_size_t * max(count, 1))()
+        for k, sc in enumerate(scans):
+            if on_device:
+                ptrs[k], ns[k] = sc[0], sc[1]
+            else:
+                assert isinstance(sc, np.ndarray) and sc.dtype == np.float32 and sc.flags.c_contiguous
+                ptrs[k], ns[k] = sc.ctypes.data, len(sc)
+        pose0 = np.ascontiguousarray(pose0, dtype=np.float64)
+        deltas = np.ascontiguousarray(deltas, dtype=np.float64).reshape(count, 7) if count else np.zeros((1, 7))
+        times = np.ascontiguousarray(times, dtype=np.float64).reshape(count) if count else np.zeros(1)
+        out = np.zeros((count, 7)); guesses = np.zeros((count, 7)); st = (Stats * max(count, 1))(); n_done = C.c_int32(0)
+        fn, args = self.L.so_icp_localization_sequence, (self.h, count, ptrs, ns, 12, 1 if on_device else 0, pose0.ctypes.data_as(_F64P),
+                                                         deltas.ctypes.data_as(_F64P), times.ctypes.data_as(_F64P), out.ctypes.data_as(_F64P),
+                                                         guesses.ctypes.data_as(_F64P), st, C.byref(n_done))
+        keep = (ptrs, ns, pose0, deltas, times, scans)
+        return (lambda: fn(*args)), out, guesses, st, n_done, keep
+
+    def localization_sequence(self, scans, pose0, deltas, times, on_device=False):
+        """so_icp_localization_sequence: `count` so_icp_localization calls in one, each frame registered and then inserted into the map,
+        guess_k = pose_out[k-1] o deltas[k].  Returns (rc, poses_out, guesses_out, stats list, n_done); rc < 0 raises."""
+        call, out, guesses, st, n_done, _keep = self.prepare_localization_sequence(scans, pose0, deltas, times, on_device)
+        rc = call()
+        if rc < 0:
+            self._check(rc)
+        return rc, out, guesses, list(st)[:len(scans)], n_done.value
 
     def sequence_announce_next(self, scan, delta):
         """so_icp_sequence_announce_next: the scan that will start the NEXT register_sequence call (None withdraws)"""

@@ -32,6 +32,7 @@
 #include "device_map.h"
 #include "local_map.h"
 #include "so_math.h"
+#include "ctx_access.h"
 
 using namespace soicp;
 
@@ -3206,3 +3207,9 @@ int so_icp_debug_neighbours(so_icp_ctx* c, uint32_t* out, size_t n) {
 int so_icp_synchronize(so_icp_ctx* c) { if (!c) return SO_ICP_E_INVALID; NEED_DEVICE(c); HIP_TRY(c, hipStreamSynchronize(c->stream)); return SO_ICP_OK; }
 
 }  // extern "C"
+
+// ---- ctx_access.h: the context as the entry points in other translation units see it --------------------------------
+namespace soicp {
+CtxView ctx_view(const so_icp_ctx* c) { return CtxView{c->host_only}; }
+int ctx_note(so_icp_ctx* c, int code, const std::string& msg) { c->err = msg; return code; }
+}  // namespace soicp
