@@ -121,6 +121,57 @@ inline NodeConfig node_config_from_params(const ParamMap& p) {
   return c;
 }
 
+// feature_extraction_node's parameter surface (featureExtraction::readParameters, src/FeatureExtraction/featureExtraction.cpp:119-170,
+// the declared defaults included; the sensor and the frames from readGlobalparam, parameter.cpp:289-311).  The blind box, the
+// dynamic mask, max_range and the IMU limits are read by the reference and used by nothing on its path (featureExtraction.h:54-69);
+// only max_range is kept here, for the record.
+enum class SensorType { VELODYNE, OUSTER, LIVOX };  // parameter.h:41
+struct FeatureConfig {
+  int N_SCANS = 4;             // feature_extraction_node.scan_line
+  int skipFrame = 1;           // feature_extraction_node.mapping_skip_frame
+  float min_range = 0.2f;      // feature_extraction_node.min_range (declared as float)
+  float max_range = 130.0f;
+  int filter_point_size = 3;
+  int provide_point_time = 1;
+  bool debug_view_enabled = false;
+  std::string sensor_name = "livox";  // the top-level `sensor`
+  SensorType sensor = SensorType::LIVOX;
+  std::string WORLD_FRAME = "sensor_init", SENSOR_FRAME = "sensor", ProjectName;
+  // calibration (OpenCV FileStorage, parameter.cpp:123-216, not read here): set by the caller
+  double T_i_l[7] = {0, 0, 0, 0, 0, 0, 1};                   // tx ty tz qx qy qz qw
+  double T_ouster_sensor[7] = {0, 0, 0.036180, 0, 0, 1, 0};  // parameter.cpp:270-277: R = diag(-1, -1, 1), t = (0, 0, 0.036180)
+};
+
+inline FeatureConfig feature_config_from_params(const ParamMap& p) {
+  using namespace detail;
+  const std::string n = "feature_extraction_node.";
+  FeatureConfig c;
+  c.N_SCANS = (int)num(p, n + "scan_line", 4);
+  c.skipFrame = (int)num(p, n + "mapping_skip_frame", 1);
+  c.min_range = (float)num(p, n + "min_range", 0.2);
+  c.max_range = (float)num(p, n + "max_range", 130.0);
+  c.filter_point_size = (int)num(p, n + "filter_point_size", 3);
+  c.provide_point_time = (int)num(p, n + "provide_point_time", 1);
+  c.debug_view_enabled = flag(p, n + "debug_view", false);
+  c.sensor_name = str(p, "sensor", "livox");
+  if (c.sensor_name == "livox") c.sensor = SensorType::LIVOX;            // readParameters :160-166
+  else if (c.sensor_name == "velodyne") c.sensor = SensorType::VELODYNE;
+  else if (c.sensor_name == "ouster") c.sensor = SensorType::OUSTER;
+  else throw std::runtime_error("parameter sensor: '" + c.sensor_name + "' is not livox, velodyne or ouster");  // parameter.cpp:323-327
+  c.WORLD_FRAME = str(p, "world_frame", "sensor_init");
+  c.SENSOR_FRAME = str(p, "sensor_frame", "sensor");
+  c.ProjectName = str(p, "PROJECT_NAME", "");
+  return c;
+}
+
+inline FeatureConfig load_feature_config(const std::string& path) {
+  std::ifstream f(path);
+  if (!f) throw std::runtime_error("cannot open parameter file " + path);
+  std::stringstream ss;
+  ss << f.rdbuf();
+  return feature_config_from_params(parse_ros_params_yaml(ss.str()));
+}
+
 inline NodeConfig load_node_config(const std::string& path) {
   std::ifstream f(path);
   if (!f) throw std::runtime_error("cannot open parameter file " + path);

@@ -3,6 +3,7 @@
 //   wire_selftest roundtrip <Type> <in.cdr> <out.cdr>   deserialise a message of <Type>, serialise it again
 //   wire_selftest emit <Type> <out.cdr>                 serialise a message with fixed field values (the test knows them)
 //   wire_selftest params <file.yaml>                    node_config.h: ROS 2 parameter file -> NodeConfig, printed
+//   wire_selftest feature-params <file.yaml>            node_config.h: the same file -> FeatureConfig, printed
 // Types: String Float32 Header PointCloud2 Odometry Path IterationStats OptimizationStats LaserFeature
 #include <cstdio>
 #include <cstring>
@@ -154,6 +155,14 @@ int main(int argc, char** argv) {
              c.WORLD_FRAME.c_str(), c.SENSOR_FRAME.c_str(), c.ProjectName.c_str());
       return 0;
     }
+    if (argc == 3 && !strcmp(argv[1], "feature-params")) {  // feature_extraction_node's parameter surface: file -> FeatureConfig, printed
+      const super_odometry_soicp::FeatureConfig c = super_odometry_soicp::load_feature_config(argv[2]);
+      printf("scan_line=%d\nmapping_skip_frame=%d\nmin_range=%.9g\nmax_range=%.9g\nfilter_point_size=%d\nprovide_point_time=%d\ndebug_view=%d\n",
+             c.N_SCANS, c.skipFrame, c.min_range, c.max_range, c.filter_point_size, c.provide_point_time, (int)c.debug_view_enabled);
+      printf("sensor=%s\nsensor_type=%d\nworld_frame=%s\nsensor_frame=%s\nPROJECT_NAME=%s\n", c.sensor_name.c_str(), (int)c.sensor,
+             c.WORLD_FRAME.c_str(), c.SENSOR_FRAME.c_str(), c.ProjectName.c_str());
+      return 0;
+    }
     if (argc == 4 && !strcmp(argv[1], "pcd")) {  // the prior-map reader (pcd_io.h): file -> packed float32 {x, y, z, intensity}
       std::vector<float> xyzi;
       std::string err;
@@ -162,7 +171,7 @@ int main(int argc, char** argv) {
       printf("points=%zu\n", xyzi.size() / 4);
       return 0;
     }
-    fprintf(stderr, "usage: %s roundtrip <Type> in out | emit <Type> out | params <file.yaml> | pcd <file.pcd> out.f32\n", argv[0]);
+    fprintf(stderr, "usage: %s roundtrip <Type> in out | emit <Type> out | params <file.yaml> | feature-params <file.yaml> | pcd <file.pcd> out.f32\n", argv[0]);
     return 2;
   } catch (const std::exception& e) {
     fprintf(stderr, "wire_selftest: %s\n", e.what());

@@ -422,6 +422,55 @@ int so_icp_deskew_scan_dev(so_icp_ctx *ctx, void *d_points, size_t n, size_t str
                            double lidar_start_time, const so_icp_stamped_pose *poses, size_t n_poses, int poses_are_imu,
                            const double T_i_l[7], so_icp_deskew_info *info);
 
+/* -------- the front end of featureExtraction (src/FeatureExtraction/featureExtraction.cpp) on the device: one pass from the
+ * driver's sensor_msgs::PointCloud2 payload to the two clouds of a LaserFeature, in the reference's order.
+ *  1. ingest (laserCloudHandler, :710-766): n = width * height points, row-major, rows row_step bytes apart, points point_step
+ *     bytes apart (pcl::fromROSMsg).  Velodyne: float x y z intensity time and uint16 ring as they are.  Ouster: rot * (x, y, z)
+ *     + pos of T_ouster_sensor in fp64 rounded to float (utils::transformOusterPoints), intensity, time = (float)t * 1e-9f from
+ *     the uint32 t in ns, ring 0.  A field the caller found absent (offset -1; PCL matches name, datatype and count) reads 0.
+ *  2. de-skew (removePointDistortion, :223-314) when n_poses > 0, exactly so_icp_deskew_scan on the ingested records;
+ *     n_poses == 0 is the reference's "no IMU" branch (no de-skew).
+ *  3. uniform surf sampling (uniformFeatureExtraction, :504-525): candidates i = 1, 1 + s, ... < n (s = filter_point_size),
+ *     each against record i - 1, kept when |dx| > 1e-7 || |dy| > 1e-7 || (|dz| > 1e-7 && x*x + y*y + z*z > min_range^2).
+ * Outputs, 32-byte records each: cloud_nodistortion as point_os::PointcloudXYZITR (x y z at 0 4 8, 0 at 12, intensity 16,
+ * time 20, uint16 ring 24, zero padding), cloud_surface as pcl::PointXYZI (x y z, 1.0f at 12, intensity = the point's time at
+ * 16, zero padding) in ascending i.  Little-endian payloads only. */
+#define SO_ICP_SENSOR_VELODYNE 0 /* SensorType::VELODYNE */
+#define SO_ICP_SENSOR_OUSTER 1   /* SensorType::OUSTER */
+typedef struct {
+  int32_t sensor;       /* SO_ICP_SENSOR_* */
+  int32_t is_bigendian; /* PointCloud2::is_bigendian: 1 is refused */
+  uint32_t point_step, row_step;
+  /* byte offsets inside a point; -1 = absent or not matching (x y z intensity FLOAT32 count 1; time FLOAT32 (velodyne) or t
+   * UINT32 (ouster); ring UINT16 (velodyne)) */
+  int32_t off_x, off_y, off_z, off_intensity, off_time, off_ring;
+  int32_t filter_point_size; /* feature_extraction_node.filter_point_size, >= 1 */
+  float min_range;           /* feature_extraction_node.min_range */
+  double T_ouster_sensor[7]; /* tx ty tz qx qy qz qw (parameter.cpp:270-277: R = diag(-1, -1, 1), t = (0, 0, 0.036180)) */
+} so_icp_sweep_layout;
+typedef struct {
+  double q_w_original_l[4]; /* x y z w: so_icp_deskew_info's; identity without de-skew */
+  double t_w_original_l[3]; /* zero without de-skew (the node then publishes its member from the sweep before) */
+  uint32_t n_clamped;       /* so_icp_deskew_info's */
+  int32_t deskewed;         /* 1: n_poses > 0 */
+  uint64_t n_points;        /* width * height: records of cloud_nodistortion */
+  uint64_t n_surface;       /* records of cloud_surface */
+} so_icp_feature_info;
+/* raw: host payload (row_step * height bytes).  nodistortion_out (n_points * 32 bytes) and surface_out (room for
+ * n_points > 1 ? (n_points - 2) / filter_point_size + 1 : 0 records; n_points records always suffice) are host buffers, each
+ * optional.  One copy of the payload in, one enqueue, one read-back of the counts, then the outputs. */
+int so_icp_extract_features(so_icp_ctx *ctx, const void *raw, uint32_t width, uint32_t height, const so_icp_sweep_layout *layout,
+                            double lidar_start_time, const so_icp_stamped_pose *poses, size_t n_poses, int poses_are_imu,
+                            const double T_i_l[7], void *nodistortion_out, void *surface_out, so_icp_feature_info *info);
+/* same, payload already in HBM; *d_nodistortion_out and *d_surface_out (nullable) are device buffers owned by the context, valid
+ * until its next so_icp_extract_features(_dev) call.  The call returns when both are complete. */
+int so_icp_extract_features_dev(so_icp_ctx *ctx, const void *d_raw, uint32_t width, uint32_t height, const so_icp_sweep_layout *layout,
+                                double lidar_start_time, const so_icp_stamped_pose *poses, size_t n_poses, int poses_are_imu,
+                                const double T_i_l[7], void **d_nodistortion_out, void **d_surface_out, so_icp_feature_info *info);
+/* so_icp_prefilter_scan on a cloud already in HBM and complete (e.g. *d_surface_out above, stride 32): same results, bit for bit */
+int so_icp_prefilter_scan_dev(so_icp_ctx *ctx, const void *d_surf, size_t n, size_t stride_bytes, int auto_voxel_size, float line_res,
+                              float plane_res, void **d_filtered_out, size_t *n_out, so_icp_prefilter_info *info);
+
 /* -------- one step after Seam A: the registered scan laserMapping::publishTopic builds
  * (src/LaserMapping/laserMapping.cpp:464-493 with utils::pointAssociateToMap, src/utils/superodom_utils.cpp:148-158).
  * Records with float x y z at byte 0 4 8, rewritten in place: a point within 0.1 m of the sensor (x*x + y*y + z*z < 0.01 in

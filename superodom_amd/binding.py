@@ -65,6 +65,50 @@ class DeskewInfo(C.Structure):
     _fields_ = [("q_w_original_l", C.c_double * 4), ("t_w_original_l", C.c_double * 3), ("n_clamped", C.c_uint32), ("reserved", C.c_uint32)]
 
 
+class SweepLayout(C.Structure):
+    _fields_ = [("sensor", C.c_int32), ("is_bigendian", C.c_int32), ("point_step", C.c_uint32), ("row_step", C.c_uint32),
+                ("off_x", C.c_int32), ("off_y", C.c_int32), ("off_z", C.c_int32), ("off_intensity", C.c_int32), ("off_time", C.c_int32),
+                ("off_ring", C.c_int32), ("filter_point_size", C.c_int32), ("min_range", C.c_float), ("T_ouster_sensor", C.c_double * 7)]
+
+
+class FeatureInfo(C.Structure):
+    _fields_ = [("q_w_original_l", C.c_double * 4), ("t_w_original_l", C.c_double * 3), ("n_clamped", C.c_uint32), ("deskewed", C.c_int32),
+                ("n_points", C.c_uint64), ("n_surface", C.c_uint64)]
+
+
+SENSOR_VELODYNE, SENSOR_OUSTER = 0, 1
+# sensor_msgs::msg::PointField datatypes
+INT8, UINT8, INT16, UINT16, INT32, UINT32, FLOAT32, FLOAT64 = range(1, 9)
+# parameter.cpp:270-277: R = diag(-1, -1, 1) (the quaternion (0, 0, 1, 0)), t = (0, 0, 0.036180)
+T_OUSTER_SENSOR = (0.0, 0.0, 0.036180, 0.0, 0.0, 1.0, 0.0)
+# the fields pcl::fromROSMsg copies into the reference's point types: name -> (datatype, count)
+_VELODYNE_FIELDS = {"x": FLOAT32, "y": FLOAT32, "z": FLOAT32, "intensity": FLOAT32, "time": FLOAT32, "ring": UINT16}   # PointcloudXYZITR
+_OUSTER_FIELDS = {"x": FLOAT32, "y": FLOAT32, "z": FLOAT32, "intensity": FLOAT32, "t": UINT32}                          # OusterPointXYZIRT
+
+
+def sweep_layout(fields, point_step, row_step, sensor, filter_point_size, min_range, is_bigendian=False, T_ouster_sensor=T_OUSTER_SENSOR):
+    """so_icp_sweep_layout from a PointCloud2's PointField list [(name, offset, datatype, count), ...].  A field of the target point
+    type is taken from the first PointField with its name, datatype and count (count 0 also matches a single value), as
+    pcl::detail::FieldMatches does; a field with no match is absent (offset -1) and reads 0."""
+    want = _OUSTER_FIELDS if sensor == SENSOR_OUSTER else _VELODYNE_FIELDS
+    off = {}
+    for name, dtype in want.items():
+        for fname, foff, fdt, fcount in fields:
+            if fname == name and fdt == dtype and (fcount == 1 or fcount == 0):
+                off[name] = int(foff)
+                break
+    L = SweepLayout()
+    L.sensor, L.is_bigendian, L.point_step, L.row_step = int(sensor), int(bool(is_bigendian)), int(point_step), int(row_step)
+    L.off_x, L.off_y, L.off_z = off.get("x", -1), off.get("y", -1), off.get("z", -1)
+    L.off_intensity = off.get("intensity", -1)
+    L.off_time = off.get("t" if sensor == SENSOR_OUSTER else "time", -1)
+    L.off_ring = -1 if sensor == SENSOR_OUSTER else off.get("ring", -1)
+    L.filter_point_size, L.min_range = int(filter_point_size), float(min_range)
+    for k in range(7):
+        L.T_ouster_sensor[k] = float(T_ouster_sensor[k])
+    return L
+
+
 class Timing(C.Structure):
     _fields_ = [("knn_ms_total", C.c_double), ("knn_launches", C.c_int64), ("knn_queries", C.c_int64), ("knn_map_points", C.c_int64),
                 ("eval_ms_total", C.c_double), ("eval_launches", C.c_int64), ("eval_points", C.c_int64),
@@ -96,7 +140,7 @@ EXPORTED = ["so_icp_default_config", "so_icp_create", "so_icp_destroy", "so_icp_
             "so_icp_deskew_scan", "so_icp_deskew_scan_dev", "so_icp_transform_cloud", "so_icp_shard_histogram",
             "so_icp_host_register", "so_icp_host_unregister", "so_icp_host_alloc", "so_icp_host_free", "so_icp_device_count", "so_icp_stage_cancel",
             "so_icp_map_insert_stats", "so_icp_register_sequence", "so_icp_map_export_records", "so_icp_sequence_announce_next", "so_icp_debug_neighbours", "so_icp_prefilter_announce",
-            "so_icp_localization_sequence"]
+            "so_icp_localization_sequence", "so_icp_extract_features", "so_icp_extract_features_dev", "so_icp_prefilter_scan_dev"]
 
 _lib = None
 
@@ -162,6 +206,12 @@ def load():
     L.so_icp_prefilter_announce.argtypes = [vp, f32p, C.c_size_t, C.c_size_t]
     L.so_icp_prefilter_scan.argtypes = [vp, f32p, C.c_size_t, C.c_size_t, C.c_int, C.c_float, C.c_float, C.POINTER(vp),
                                         C.POINTER(C.c_size_t), C.POINTER(PrefilterInfo)]
+    L.so_icp_prefilter_scan_dev.argtypes = [vp, vp, C.c_size_t, C.c_size_t, C.c_int, C.c_float, C.c_float, C.POINTER(vp),
+                                            C.POINTER(C.c_size_t), C.POINTER(PrefilterInfo)]
+    L.so_icp_extract_features.argtypes = [vp, vp, C.c_uint32, C.c_uint32, C.POINTER(SweepLayout), C.c_double, C.POINTER(C.c_double), C.c_size_t,
+                                          C.c_int, C.POINTER(C.c_double), vp, vp, C.POINTER(FeatureInfo)]
+    L.so_icp_extract_features_dev.argtypes = [vp, vp, C.c_uint32, C.c_uint32, C.POINTER(SweepLayout), C.c_double, C.POINTER(C.c_double),
+                                              C.c_size_t, C.c_int, C.POINTER(C.c_double), C.POINTER(vp), C.POINTER(vp), C.POINTER(FeatureInfo)]
     L.so_icp_debug_knn_stamps.argtypes = [vp, C.POINTER(C.c_uint64), C.c_size_t, C.POINTER(C.c_size_t)]
     L.so_icp_set_time_kernels.argtypes = [vp, C.c_int]
     L.so_icp_stage_scan.argtypes = [vp, f32p, C.c_size_t, C.c_size_t]
@@ -503,6 +553,44 @@ class LidarSlamGpu:
         self._check(self.L.so_icp_prefilter_scan(self.h, _p(pts, C.c_float), len(pts), 12, int(bool(auto_voxel_size)), float(line_res),
                                                  float(plane_res), C.byref(d), C.byref(n), C.byref(info)))
         return d.value, n.value, info
+
+    def prefilter_scan_dev(self, d_surf, n, stride_bytes, auto_voxel_size, line_res, plane_res):
+        """so_icp_prefilter_scan on a cloud resident in HBM (d_surf: device address); returns (d_scan, n, PrefilterInfo)."""
+        d = C.c_void_p(); no = C.c_size_t(0); info = PrefilterInfo()
+        self._check(self.L.so_icp_prefilter_scan_dev(self.h, C.c_void_p(d_surf), int(n), int(stride_bytes), int(bool(auto_voxel_size)),
+                                                     float(line_res), float(plane_res), C.byref(d), C.byref(no), C.byref(info)))
+        return d.value, no.value, info
+
+    @staticmethod
+    def _feature_args(poses, T_i_l):
+        poses = np.zeros((0, 8)) if poses is None else np.ascontiguousarray(poses, np.float64).reshape(-1, 8)
+        til = None if T_i_l is None else np.ascontiguousarray(T_i_l, np.float64)
+        return poses, (_p(poses, C.c_double) if len(poses) else None), len(poses), (None if til is None else _p(til, C.c_double)), til
+
+    def extract_features(self, payload, width, height, layout, lidar_start_time, poses=None, poses_are_imu=False, T_i_l=None):
+        """featureExtraction's sweep -> LaserFeature clouds on the device.  payload: the PointCloud2 data (uint8); poses: [m, 8]
+        (time, position, quaternion x y z w) or None (no de-skew).  Returns (cloud_nodistortion uint8 [n, 32], cloud_surface
+        uint8 [n_surface, 32], FeatureInfo)."""
+        raw = np.ascontiguousarray(payload, np.uint8).reshape(-1)
+        poses, pp, npo, tp, _keep = self._feature_args(poses, T_i_l)
+        n = int(width) * int(height)
+        rec = np.zeros((n, 32), np.uint8)
+        surf = np.zeros((max(n, 1), 32), np.uint8)
+        info = FeatureInfo()
+        self._check(self.L.so_icp_extract_features(self.h, raw.ctypes.data_as(C.c_void_p), int(width), int(height), C.byref(layout),
+                                                   float(lidar_start_time), pp, npo, int(bool(poses_are_imu)), tp, rec.ctypes.data_as(C.c_void_p),
+                                                   surf.ctypes.data_as(C.c_void_p), C.byref(info)))
+        return rec, surf[:info.n_surface].copy(), info
+
+    def extract_features_dev(self, d_payload, width, height, layout, lidar_start_time, poses=None, poses_are_imu=False, T_i_l=None):
+        """the same on a payload resident in HBM; returns (d_nodistortion, d_surface, FeatureInfo): context-owned device buffers,
+        valid until the next call"""
+        poses, pp, npo, tp, _keep = self._feature_args(poses, T_i_l)
+        d_rec = C.c_void_p(); d_surf = C.c_void_p(); info = FeatureInfo()
+        self._check(self.L.so_icp_extract_features_dev(self.h, C.c_void_p(d_payload), int(width), int(height), C.byref(layout),
+                                                       float(lidar_start_time), pp, npo, int(bool(poses_are_imu)), tp, C.byref(d_rec),
+                                                       C.byref(d_surf), C.byref(info)))
+        return d_rec.value, d_surf.value, info
 
     def deskew_scan(self, records, time_off, lidar_start_time, poses, poses_are_imu, T_i_l=None):
         """featureExtraction::removePointDistortion on the device.  records: uint8 [n, stride] (float x y z at 0 4 8, float time

@@ -3,6 +3,9 @@
 // the HIP kernel.  Transformd products follow include/super_odometry/utils/Twist.h:165-187 through Eigen 3.4's
 // quaternion <-> matrix conversions [UPSTREAM Eigen, written out]; slerp is Eigen::QuaternionBase::slerp.
 #pragma once
+#include <cstddef>
+#include <vector>
+
 #include "so_math.h"
 
 namespace soicp {
@@ -130,6 +133,44 @@ SO_HD Rigid deskew_transform(const Table& tab, uint32_t n, double ts, const Desk
   const Rigid original_current = rigid_mul(f.w_original_inv, w_current);
   if (!f.imu) return original_current;
   return rigid_mul(rigid_mul(f.l_i, original_current), f.i_l);
+}
+
+// one point of removePointDistortion (:293-306): a finite point measured at t0 + time is moved by deskew_transform (fp64, rounded
+// to float); a non-finite one stays.  Used by deskew_kernel and ingest_deskew_kernel alike.  Returns whether the point was clamped.
+template <typename Table>
+SO_HD bool deskew_point(const Table& tab, uint32_t n, double t0, float time, const DeskewFrames& f, float& x, float& y, float& z) {
+  bool clamped = false;
+  if (isfinite(x) && isfinite(y) && isfinite(z)) {
+    const double ts = (double)time + t0;
+    const Rigid T = deskew_transform(tab, n, ts, f, &clamped);
+    double ox, oy, oz;
+    quat_rotate<double>(T.q, (double)x, (double)y, (double)z, ox, oy, oz);  // Twist::operator*(Tangent3): rot * p + pos
+    x = (float)(ox + T.t[0]); y = (float)(oy + T.t[1]); z = (float)(oz + T.t[2]);
+  }
+  return clamped;
+}
+
+// Host side of one de-skew (featureExtraction.cpp:279-290), shared by so_icp_deskew_scan(_dev) and so_icp_extract_features(_dev):
+// the per-scan constants, the sensor frame at the sweep start and the pose table the kernels read (positions zeroed for the
+// IMU's buffer, extractPose :231-235).  false: the times do not increase strictly (the reference keeps them in a std::map).
+inline bool deskew_setup(const double* tab, size_t n_poses, double t0, int imu, const double T_i_l[7], DeskewFrames& f,
+                         std::vector<double>& dev_tab, double q_sensor[4], double t_sensor[3]) {
+  for (size_t k = 0; k + 1 < n_poses; ++k)
+    if (!(tab[k * kStampedPoseDoubles] < tab[(k + 1) * kStampedPoseDoubles])) return false;
+  f.imu = imu ? 1 : 0;
+  if (T_i_l) { for (int k = 0; k < 3; ++k) f.i_l.t[k] = T_i_l[k]; for (int k = 0; k < 4; ++k) f.i_l.q[k] = T_i_l[3 + k]; }
+  else { f.i_l.t[0] = f.i_l.t[1] = f.i_l.t[2] = 0; f.i_l.q[0] = f.i_l.q[1] = f.i_l.q[2] = 0; f.i_l.q[3] = 1; }
+  f.l_i = rigid_inverse(f.i_l);  // parameter.cpp:193
+  bool clamped_start = false;
+  Rigid start = interpolated_pose(tab, (uint32_t)n_poses, t0, &clamped_start);  // :279
+  if (imu) start.t[0] = start.t[1] = start.t[2] = 0;                             // extractPose, :231-235
+  f.w_original_inv = rigid_inverse(start);
+  const Rigid sensor = imu ? rigid_mul(start, f.i_l) : start;                    // :284-290
+  for (int k = 0; k < 4; ++k) q_sensor[k] = sensor.q[k];
+  for (int k = 0; k < 3; ++k) t_sensor[k] = sensor.t[k];
+  dev_tab.assign(tab, tab + n_poses * kStampedPoseDoubles);
+  if (imu) for (size_t k = 0; k < n_poses; ++k) dev_tab[k * 8 + 1] = dev_tab[k * 8 + 2] = dev_tab[k * 8 + 3] = 0.0;
+  return true;
 }
 
 }  // namespace soicp

@@ -1,0 +1,35 @@
+// feature_kernels.h -- launchers of feature_kernels.hip: featureExtraction's per-sweep point work on the device
+// (laserCloudHandler's ingest, removePointDistortion, uniformFeatureExtraction).
+#pragma once
+#include <hip/hip_runtime_api.h>
+#include <stdint.h>
+
+namespace soicp {
+
+struct DeskewFrames;
+
+// where the fields of one sensor_msgs::PointCloud2 point are (pcl::fromROSMsg's field match, done by the caller); -1: absent
+struct SweepFields {
+  uint32_t point_step, row_step, width;
+  int32_t x, y, z, intensity, time, ring;
+  int32_t ouster;        // 0: velodyne (float time, uint16 ring copied), 1: ouster (T_ouster_sensor, uint32 t in ns, ring 0)
+  double ouster_q[4];    // T_ouster_sensor: x y z w
+  double ouster_t[3];
+};
+
+// bytes of one record of either output cloud: point_os::PointcloudXYZITR and pcl::PointXYZI are both 32 bytes
+constexpr uint32_t kFeatureRecordBytes = 32;
+// surf-sampling candidates per workgroup of the compaction, and the look-back words it needs
+constexpr uint32_t kSurfItems = 2048;
+inline uint32_t surf_candidates(uint32_t n, uint32_t s) { return n > 1u ? (n - 2u) / s + 1u : 0u; }
+inline uint32_t surf_workgroups(uint32_t n, uint32_t s) { return (surf_candidates(n, s) + kSurfItems - 1u) / kSurfItems; }
+
+// payload -> PointcloudXYZITR records (d_rec, 32 B each), de-skewed when n_poses > 0 (d_n_clamped zeroed by the caller)
+void launch_ingest_deskew(const uint8_t* d_raw, uint32_t n, const SweepFields& sf, uint8_t* d_rec, double t0, const double* d_poses,
+                          uint32_t n_poses, const DeskewFrames& f, uint32_t* d_n_clamped, hipStream_t s);
+// uniformFeatureExtraction over the records: pcl::PointXYZI records into d_surf, their number into *d_n_surf.
+// d_state (surf_workgroups words) and d_ticket zeroed by the caller.
+void launch_surf_sample(const uint8_t* d_rec, uint32_t n, uint32_t step, float min_range, uint8_t* d_surf, uint32_t* d_n_surf,
+                        unsigned long long* d_state, uint32_t* d_ticket, hipStream_t s);
+
+}  // namespace soicp

@@ -1,0 +1,189 @@
+// feature_kernels.hip -- featureExtraction's per-sweep point work (src/FeatureExtraction/featureExtraction.cpp) on the device:
+//   ingest_deskew_kernel  laserCloudHandler's pcl::fromROSMsg (+ utils::transformOusterPoints and the ns -> s time for the Ouster,
+//                         :710-766, superodom_utils.cpp:202-209) fused with removePointDistortion (:223-314): payload in,
+//                         point_os::PointcloudXYZITR records out (the LaserFeature's cloud_nodistortion)
+//   surf_sample_kernel    uniformFeatureExtraction (:504-525): an order-preserving compaction into pcl::PointXYZI records
+//                         (cloud_surface), one launch with a decoupled look-back across workgroups
+// The de-skew arithmetic is deskew_math.h's, as in map_kernels.hip deskew_kernel: the same header functions in the same order,
+// so the records equal that kernel's run on the ingested sweep bit for bit.
+#include <hip/hip_runtime.h>
+
+#include "deskew_math.h"
+#include "feature_kernels.h"
+#include "so_math.h"
+
+namespace soicp {
+
+// PointCloud2 fields sit at any byte offset (velodyne_pointcloud's time is at 18 of a 22-byte point); A4: every offset, step
+// and the base are multiples of 4, so the fields load as dwords
+template <bool A4, typename T>
+__device__ __forceinline__ T load_field(const uint8_t* p) {
+  if (A4) return *reinterpret_cast<const T*>(p);
+  T v;
+  __builtin_memcpy(&v, p, sizeof(T));
+  return v;
+}
+
+constexpr uint32_t kIngestLdsPoses = 512;  // (deskew_kernel's kDeskewLdsPoses: beyond it the pose table is read from global memory)
+
+template <bool A4, bool DESKEW, bool LDS>
+__global__ __launch_bounds__(256) void ingest_deskew_kernel(const uint8_t* __restrict__ raw, uint32_t n, SweepFields sf, uint8_t* __restrict__ out,
+                                                            double t0, const double* __restrict__ poses, uint32_t n_poses, DeskewFrames f,
+                                                            uint32_t* __restrict__ n_clamped) {
+  __shared__ double tab_lds[(DESKEW && LDS) ? kIngestLdsPoses * kStampedPoseDoubles : 1];
+  if (DESKEW && LDS) {
+    for (uint32_t k = threadIdx.x; k < n_poses * kStampedPoseDoubles; k += blockDim.x) tab_lds[k] = poses[k];
+    __syncthreads();
+  }
+  const double* tab = (DESKEW && LDS) ? tab_lds : poses;
+  const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+  bool clamped = false;
+  if (i < n) {
+    const uint32_t row = i / sf.width, col = i - row * sf.width;  // row-major, rows row_step apart (pcl::fromROSMsg)
+    const uint8_t* p = raw + (size_t)row * sf.row_step + (size_t)col * sf.point_step;
+    // a field PCL does not match keeps the value-initialised point's 0
+    float x = sf.x >= 0 ? load_field<A4, float>(p + sf.x) : 0.0f;
+    float y = sf.y >= 0 ? load_field<A4, float>(p + sf.y) : 0.0f;
+    float z = sf.z >= 0 ? load_field<A4, float>(p + sf.z) : 0.0f;
+    const float intensity = sf.intensity >= 0 ? load_field<A4, float>(p + sf.intensity) : 0.0f;
+    float time;
+    uint32_t ring;
+    if (sf.ouster) {
+      // transformOusterPoints: Vector3d(x, y, z), rot * p + pos in fp64 (Eigen's _transformVector), rounded to float
+      double ox, oy, oz;
+      quat_rotate<double>(sf.ouster_q, (double)x, (double)y, (double)z, ox, oy, oz);
+      x = (float)(ox + sf.ouster_t[0]); y = (float)(oy + sf.ouster_t[1]); z = (float)(oz + sf.ouster_t[2]);
+      const uint32_t t = sf.time >= 0 ? load_field<A4, uint32_t>(p + sf.time) : 0u;
+      time = (float)t * 1e-9f;  // dst.time = src.t * 1e-9f
+      ring = 0u;
+    } else {
+      time = sf.time >= 0 ? load_field<A4, float>(p + sf.time) : 0.0f;
+      ring = sf.ring >= 0 ? (uint32_t)load_field<A4, uint16_t>(p + sf.ring) : 0u;
+    }
+    if (DESKEW) clamped = deskew_point(tab, n_poses, t0, time, f, x, y, z);  // removePointDistortion, :293-306 (as deskew_kernel)
+    // PointcloudXYZITR: x y z, data[3] = 0, intensity, time, ring (uint16) and zero padding
+    uint4* o = reinterpret_cast<uint4*>(out + (size_t)i * kFeatureRecordBytes);
+    o[0] = make_uint4(__float_as_uint(x), __float_as_uint(y), __float_as_uint(z), 0u);
+    o[1] = make_uint4(__float_as_uint(intensity), __float_as_uint(time), ring, 0u);
+  }
+  if (DESKEW) {
+    const unsigned long long m = __ballot(clamped);
+    if (m && (threadIdx.x & 63) == (uint32_t)__builtin_ctzll(m)) atomicAdd(n_clamped, (uint32_t)__popcll(m));
+  }
+}
+
+template <bool A4>
+static void launch_ingest_a(const uint8_t* d_raw, uint32_t n, const SweepFields& sf, uint8_t* d_rec, double t0, const double* d_poses,
+                            uint32_t n_poses, const DeskewFrames& f, uint32_t* d_n_clamped, hipStream_t s) {
+  const uint32_t blocks = (n + 255u) / 256u;
+  if (!n_poses) ingest_deskew_kernel<A4, false, false><<<blocks, 256, 0, s>>>(d_raw, n, sf, d_rec, t0, d_poses, 0u, f, d_n_clamped);
+  else if (n_poses <= kIngestLdsPoses) ingest_deskew_kernel<A4, true, true><<<blocks, 256, 0, s>>>(d_raw, n, sf, d_rec, t0, d_poses, n_poses, f, d_n_clamped);
+  else ingest_deskew_kernel<A4, true, false><<<blocks, 256, 0, s>>>(d_raw, n, sf, d_rec, t0, d_poses, n_poses, f, d_n_clamped);
+}
+
+void launch_ingest_deskew(const uint8_t* d_raw, uint32_t n, const SweepFields& sf, uint8_t* d_rec, double t0, const double* d_poses,
+                          uint32_t n_poses, const DeskewFrames& f, uint32_t* d_n_clamped, hipStream_t s) {
+  if (!n) return;
+  bool a4 = (reinterpret_cast<uintptr_t>(d_raw) % 4u) == 0 && sf.point_step % 4u == 0 && sf.row_step % 4u == 0;
+  for (int32_t off : {sf.x, sf.y, sf.z, sf.intensity, sf.time, sf.ring}) a4 = a4 && (off < 0 || off % 4 == 0);
+  if (a4) launch_ingest_a<true>(d_raw, n, sf, d_rec, t0, d_poses, n_poses, f, d_n_clamped, s);
+  else launch_ingest_a<false>(d_raw, n, sf, d_rec, t0, d_poses, n_poses, f, d_n_clamped, s);
+}
+
+// uniformFeatureExtraction, featureExtraction.cpp:507-522: candidates i = 1, 1 + s, 1 + 2s, ... < n, each against the RAW record
+// i - 1, kept when  |dx| > 1e-7 || |dy| > 1e-7 || (|dz| > 1e-7 && x*x + y*y + z*z > r*r)  -- C++ precedence: the range gate only
+// goes with the z test.  The differences and abs are float (the float overload), compared in double; the squared norm and r*r are
+// float, left to right, unfused (-ffp-contract=off).  A NaN neighbour makes every term false.
+__device__ __forceinline__ bool surf_keep(const float4 a, const float4 b, float min_range) {
+  const float dx = fabsf(a.x - b.x), dy = fabsf(a.y - b.y), dz = fabsf(a.z - b.z);
+  const float r2 = min_range * min_range;
+  return ((double)dx > 1e-7) || ((double)dy > 1e-7) || (((double)dz > 1e-7) && (a.x * a.x + a.y * a.y + a.z * a.z > r2));
+}
+
+// One launch: each workgroup takes kSurfItems candidates in ticket order (kPer rounds of 256 consecutive candidates: the loads of a
+// wavefront are 64 neighbouring records), ranks its kept ones with a ballot + mbcnt per round and an LDS prefix over (round,
+// wavefront), and finds the number kept in front of it with a decoupled look-back (records = flag << 62 | value, all zero
+// before the launch, vector atomics at agent scope; see leaf_heads_scan_kernel).  Output pcl::PointXYZI in ascending i: x y z,
+// data[3] = 1 (PCL's constructor), intensity = the record's time, zero padding.  The last workgroup writes the count.
+__global__ __launch_bounds__(256) void surf_sample_kernel(const uint8_t* __restrict__ rec, uint32_t n_cand, uint32_t step, float min_range,
+                                                          uint8_t* __restrict__ surf, uint32_t* __restrict__ n_surf,
+                                                          unsigned long long* __restrict__ state, uint32_t* __restrict__ ticket, uint32_t nblk) {
+  constexpr int kPer = (int)(kSurfItems / 256u);
+  __shared__ uint32_t s_bid, s_pre[kPer * 4], s_agg, s_excl;
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  if (tid == 0) s_bid = atomicAdd(ticket, 1u);
+  __syncthreads();
+  const uint32_t bid = s_bid;
+  const float4* r4 = reinterpret_cast<const float4*>(rec);
+  unsigned long long bal[kPer];
+  float4 pt[kPer];
+  float tm[kPer];
+#pragma unroll
+  for (int q = 0; q < kPer; ++q) {
+    const uint32_t k = bid * kSurfItems + (uint32_t)q * 256u + (uint32_t)tid;
+    bool keep = false;
+    pt[q] = make_float4(0.0f, 0.0f, 0.0f, 0.0f); tm[q] = 0.0f;
+    if (k < n_cand) {
+      const size_t i = 1u + (size_t)k * step;
+      pt[q] = r4[2 * i];
+      tm[q] = r4[2 * i + 1].y;
+      keep = surf_keep(pt[q], r4[2 * (i - 1)], min_range);
+    }
+    bal[q] = __ballot(keep);
+    if (lane == 0) s_pre[q * 4 + wave] = (uint32_t)__popcll(bal[q]);
+  }
+  __syncthreads();
+  if (tid == 0) {  // exclusive prefix in candidate order: round-major, then wavefront
+    uint32_t acc = 0;
+    for (int k = 0; k < kPer * 4; ++k) { const uint32_t v = s_pre[k]; s_pre[k] = acc; acc += v; }
+    s_agg = acc;
+  }
+  __syncthreads();
+  const uint32_t agg = s_agg;
+  if (wave == 0) {
+    if (lane == 0) __hip_atomic_store(&state[bid], ((bid == 0u ? 2ull : 1ull) << 62) | (unsigned long long)agg, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    uint32_t excl = 0;
+    int base = (int)bid - 1;
+    while (base >= 0) {
+      const int j = base - lane;
+      unsigned long long r = 2ull << 62;
+      if (j >= 0) {
+        do { r = __hip_atomic_load(&state[j], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); } while ((r >> 62) == 0ull);
+      }
+      const unsigned long long mi = __ballot((r >> 62) == 2ull);
+      const int first = mi ? __ffsll((long long)mi) - 1 : 64;
+      uint32_t contrib = lane <= first ? (uint32_t)(r & 0xFFFFFFFFull) : 0u;
+#pragma unroll
+      for (int d = 32; d >= 1; d >>= 1) contrib += (uint32_t)__shfl_xor((int)contrib, d, 64);
+      excl += contrib;
+      if (mi) break;
+      base -= 64;
+    }
+    if (lane == 0) {
+      if (bid != 0u) __hip_atomic_store(&state[bid], (2ull << 62) | (unsigned long long)(excl + agg), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+      if (bid == nblk - 1u) *n_surf = excl + agg;
+      s_excl = excl;
+    }
+  }
+  __syncthreads();
+  const uint32_t excl = s_excl;
+  uint4* o4 = reinterpret_cast<uint4*>(surf);
+#pragma unroll
+  for (int q = 0; q < kPer; ++q) {
+    if ((bal[q] >> lane) & 1ull) {
+      const uint32_t below = __builtin_amdgcn_mbcnt_hi((uint32_t)(bal[q] >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)bal[q], 0u));
+      const size_t at = (size_t)excl + s_pre[q * 4 + wave] + below;
+      o4[2 * at] = make_uint4(__float_as_uint(pt[q].x), __float_as_uint(pt[q].y), __float_as_uint(pt[q].z), __float_as_uint(1.0f));
+      o4[2 * at + 1] = make_uint4(__float_as_uint(tm[q]), 0u, 0u, 0u);
+    }
+  }
+}
+
+void launch_surf_sample(const uint8_t* d_rec, uint32_t n, uint32_t step, float min_range, uint8_t* d_surf, uint32_t* d_n_surf,
+                        unsigned long long* d_state, uint32_t* d_ticket, hipStream_t s) {
+  const uint32_t nblk = surf_workgroups(n, step);
+  if (!nblk) return;
+  surf_sample_kernel<<<nblk, 256, 0, s>>>(d_rec, surf_candidates(n, step), step, min_range, d_surf, d_n_surf, d_state, d_ticket, nblk);
+}
+
+}  // namespace soicp

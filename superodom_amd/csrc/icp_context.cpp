@@ -207,6 +207,7 @@ struct so_icp_ctx {
   size_t pf_temp_for = 0, pf_temp_need = 0;  // map_sort_temp_bytes(pf_temp_for) == pf_temp_need (the query costs two library calls)
   bool pf_fast = true;                // SOICP_PREFILTER_FAST=0: statistics read back, decided on the host, then the filter (rounds 1-3)
   hipEvent_t ev_upload = nullptr;     // a scan uploaded through the auxiliary queue: the context's queue waits for it
+  std::shared_ptr<void> fe_state;     // so_icp_extract_features(_dev) (feature_extraction.cpp)
   hipStream_t pf_stream = nullptr;    // the pre-filter's own queue: the next frame's upload + VoxelGrid run BESIDE the map insert the previous
   // Seam B scratch
   DevBuf d_q, d_nbr, d_d2, d_idx, d_found, d_fblist;
@@ -1482,6 +1483,7 @@ so_icp_ctx::~so_icp_ctx() {
   }
   if (copy_stream) (void)hipStreamSynchronize(copy_stream);
   if (seq_stream) (void)hipStreamSynchronize(seq_stream);
+  if (fe_state) { if (pf_stream) (void)hipStreamSynchronize(pf_stream); if (stream) (void)hipStreamSynchronize(stream); fe_state.reset(); }
   for (StageSlot& sl : seq_slot) { sl.dev.release(); for (DevBuf* b : {&sl.pb_keys, &sl.pb_vals, &sl.pb_chunks, &sl.pb_binned, &sl.pb_ctr}) b->release(); if (sl.ev) (void)hipEventDestroy(sl.ev); }
   for (DevBuf* b : {&d_sbin_key, &d_sbin_cnt, &d_sbin_off}) b->release();
   if (seq_stream) (void)hipStreamDestroy(seq_stream);
@@ -2636,27 +2638,17 @@ int so_icp_localization(so_icp_ctx* c, int initialization, const double T_in[7],
 static int deskew_core(so_icp_ctx* c, hipStream_t s, void* d_points, size_t n, size_t stride, size_t time_off, double t0, const so_icp_stamped_pose* poses,
                        size_t n_poses, int imu, const double T_i_l[7], so_icp_deskew_info* info) {
   static_assert(sizeof(so_icp_stamped_pose) == kStampedPoseDoubles * sizeof(double), "stamped pose = 8 doubles");
-  const double* tab = reinterpret_cast<const double*>(poses);
-  for (size_t k = 0; k + 1 < n_poses; ++k)
-    if (!(poses[k].time < poses[k + 1].time)) return fail(c, SO_ICP_E_INVALID, "pose buffer times must increase strictly (the reference keeps them in a std::map)");
   DeskewFrames f;
-  f.imu = imu ? 1 : 0;
-  if (T_i_l) { for (int k = 0; k < 3; ++k) f.i_l.t[k] = T_i_l[k]; for (int k = 0; k < 4; ++k) f.i_l.q[k] = T_i_l[3 + k]; }
-  else { f.i_l.t[0] = f.i_l.t[1] = f.i_l.t[2] = 0; f.i_l.q[0] = f.i_l.q[1] = f.i_l.q[2] = 0; f.i_l.q[3] = 1; }
-  f.l_i = rigid_inverse(f.i_l);  // parameter.cpp:193
-  bool clamped_start = false;
-  Rigid start = interpolated_pose(tab, (uint32_t)n_poses, t0, &clamped_start);  // :279
-  if (imu) start.t[0] = start.t[1] = start.t[2] = 0;                             // extractPose, :231-235
-  f.w_original_inv = rigid_inverse(start);
-  const Rigid sensor = imu ? rigid_mul(start, f.i_l) : start;                    // :284-290
+  std::vector<double> host_tab;
+  double q_sensor[4], t_sensor[3];
+  if (!deskew_setup(reinterpret_cast<const double*>(poses), n_poses, t0, imu, T_i_l, f, host_tab, q_sensor, t_sensor))
+    return fail(c, SO_ICP_E_INVALID, "pose buffer times must increase strictly (the reference keeps them in a std::map)");
   if (info) {
     std::memset(info, 0, sizeof(*info));
-    for (int k = 0; k < 4; ++k) info->q_w_original_l[k] = sensor.q[k];
-    for (int k = 0; k < 3; ++k) info->t_w_original_l[k] = sensor.t[k];
+    for (int k = 0; k < 4; ++k) info->q_w_original_l[k] = q_sensor[k];
+    for (int k = 0; k < 3; ++k) info->t_w_original_l[k] = t_sensor[k];
   }
   if (!n) return SO_ICP_OK;
-  std::vector<double> host_tab(tab, tab + n_poses * kStampedPoseDoubles);
-  if (imu) for (size_t k = 0; k < n_poses; ++k) host_tab[k * 8 + 1] = host_tab[k * 8 + 2] = host_tab[k * 8 + 3] = 0.0;
   HIP_TRY(c, c->pf_small.reserve(host_tab.size() * sizeof(double) + 64));
   HIP_TRY(c, hipMemcpyAsync(c->pf_small.p, host_tab.data(), host_tab.size() * sizeof(double), hipMemcpyHostToDevice, s));
   uint32_t* d_cnt = reinterpret_cast<uint32_t*>(c->pf_small.as<uint8_t>() + host_tab.size() * sizeof(double));
@@ -2870,8 +2862,10 @@ int so_icp_prefilter_announce(so_icp_ctx* c, const float* xyz, size_t n, size_t 
   return SO_ICP_OK;
 }
 
-int so_icp_prefilter_scan(so_icp_ctx* c, const float* xyz, size_t n, size_t stride_bytes, int auto_voxel_size, float line_res,
-                          float plane_res, void** d_out, size_t* n_out, so_icp_prefilter_info* info) {
+// xyz_on_device: the cloud is already in HBM (so_icp_prefilter_scan_dev) -- one copy on the device into pf_in, and from there the
+// host entry's path, so both entries give the same bits
+static int prefilter_scan_impl(so_icp_ctx* c, const float* xyz, bool xyz_on_device, size_t n, size_t stride_bytes, int auto_voxel_size,
+                               float line_res, float plane_res, void** d_out, size_t* n_out, so_icp_prefilter_info* info) {
   if (!c || (!xyz && n) || !d_out || !n_out) return SO_ICP_E_INVALID;
   NEED_DEVICE(c);
   HIP_TRY(c, hipSetDevice(c->cfg.device_id));
@@ -2891,7 +2885,7 @@ int so_icp_prefilter_scan(so_icp_ctx* c, const float* xyz, size_t n, size_t stri
   // raw cloud -> device (with its stride) -- unless it was announced (so_icp_prefilter_announce): then its copy went into the queue long
   // ago (34 us for a 131 072-point sweep, beside the registration of the frame before) and the two buffers change places
   bool announced = false;
-  {
+  if (!xyz_on_device) {
     std::lock_guard<std::mutex> lk(c->pf_mu);
     announced = c->pf_announced.on && c->pf_announced.ptr == (const void*)xyz && c->pf_announced.n == n && c->pf_announced.stride == stride_bytes &&
                 c->pf_stage.p != nullptr;
@@ -2900,7 +2894,7 @@ int so_icp_prefilter_scan(so_icp_ctx* c, const float* xyz, size_t n, size_t stri
   }
   if (!announced) {
     HIP_TRY(c, c->pf_in.reserve(n * stride_bytes + 64));
-    HIP_TRY(c, hipMemcpyAsync(c->pf_in.p, xyz, n * stride_bytes, hipMemcpyHostToDevice, s));
+    HIP_TRY(c, hipMemcpyAsync(c->pf_in.p, xyz, n * stride_bytes, xyz_on_device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, s));
   }
   if (c->pf_fast) {
     const int frc = prefilter_fast(c, s, n, sf, auto_voxel_size, line_res, plane_res, li, d_out, n_out);
@@ -2988,6 +2982,16 @@ int so_icp_prefilter_scan(so_icp_ctx* c, const float* xyz, size_t n, size_t stri
   li.reserved = announced ? 1 : 0;
   if (info) *info = li;
   return SO_ICP_OK;
+}
+
+int so_icp_prefilter_scan(so_icp_ctx* c, const float* xyz, size_t n, size_t stride_bytes, int auto_voxel_size, float line_res,
+                          float plane_res, void** d_out, size_t* n_out, so_icp_prefilter_info* info) {
+  return prefilter_scan_impl(c, xyz, false, n, stride_bytes, auto_voxel_size, line_res, plane_res, d_out, n_out, info);
+}
+
+int so_icp_prefilter_scan_dev(so_icp_ctx* c, const void* d_xyz, size_t n, size_t stride_bytes, int auto_voxel_size, float line_res,
+                              float plane_res, void** d_out, size_t* n_out, so_icp_prefilter_info* info) {
+  return prefilter_scan_impl(c, static_cast<const float*>(d_xyz), true, n, stride_bytes, auto_voxel_size, line_res, plane_res, d_out, n_out, info);
 }
 
 int so_icp_comm_unique_id(uint8_t id[SO_ICP_UNIQUE_ID_BYTES]) {
@@ -3211,5 +3215,9 @@ int so_icp_synchronize(so_icp_ctx* c) { if (!c) return SO_ICP_E_INVALID; NEED_DE
 // ---- ctx_access.h: the context as the entry points in other translation units see it --------------------------------
 namespace soicp {
 CtxView ctx_view(const so_icp_ctx* c) { return CtxView{c->host_only}; }
+CtxDevice ctx_device(so_icp_ctx* c) {
+  (void)hipSetDevice(c->cfg.device_id);  // (the auxiliary queue is created on first use: on the context's device)
+  return CtxDevice{c->cfg.device_id, c->stream, aux_stream(c), &c->fe_state};
+}
 int ctx_note(so_icp_ctx* c, int code, const std::string& msg) { c->err = msg; return code; }
 }  // namespace soicp

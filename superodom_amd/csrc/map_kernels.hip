@@ -1793,13 +1793,10 @@ __global__ __launch_bounds__(256) void deskew_kernel(uint8_t* __restrict__ pts, 
   if (i < n) {
     uint8_t* rec = pts + (size_t)i * stride;
     float* xyz = reinterpret_cast<float*>(rec);
-    const float x = xyz[0], y = xyz[1], z = xyz[2];
-    if (isfinite(x) && isfinite(y) && isfinite(z)) {  // :293-295
-      const double ts = (double)*reinterpret_cast<const float*>(rec + time_off) + t0;  // :297
-      const Rigid T = deskew_transform(tab, n_poses, ts, f, &clamped);
-      double ox, oy, oz;
-      quat_rotate<double>(T.q, (double)x, (double)y, (double)z, ox, oy, oz);  // Twist::operator*(Tangent3): rot * p + pos
-      xyz[0] = (float)(ox + T.t[0]); xyz[1] = (float)(oy + T.t[1]); xyz[2] = (float)(oz + T.t[2]);
+    float x = xyz[0], y = xyz[1], z = xyz[2];
+    if (isfinite(x) && isfinite(y) && isfinite(z)) {  // :293-295 (deskew_math.h deskew_point)
+      clamped = deskew_point(tab, n_poses, t0, *reinterpret_cast<const float*>(rec + time_off), f, x, y, z);
+      xyz[0] = x; xyz[1] = y; xyz[2] = z;
     }
   }
   const unsigned long long m = __ballot(clamped);

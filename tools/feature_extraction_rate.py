@@ -1,0 +1,127 @@
+"""Rates of so_icp_extract_features on the GPU box (results in profiles/feature_extraction/), for the 131 072-point Ouster sweep
+(os1_128-like, 1024 x 128) and the 28 800-point VLP-16 sweep, each de-skewed against an IMU buffer, filter_point_size 3:
+  * host payload in, both clouds out (so_icp_extract_features)
+  * payload resident in HBM, clouds left there (so_icp_extract_features_dev)
+  * the resident chain sweep -> features -> so_icp_prefilter_scan_dev -> so_icp_localization_dev against the same chain through
+    host buffers (so_icp_extract_features -> so_icp_prefilter_scan -> so_icp_localization), ms per frame
+  * the CPU restatement (numpy ingest and sampling + the C oracle's de-skew, one core), labelled as such
+    python tools/feature_extraction_rate.py [--reps N] [--kernels-only]
+--kernels-only: only the resident entry, for a rocprofv3 --kernel-trace --stats run."""
+import ctypes as C
+import os
+import sys
+import time
+
+import numpy as np
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path[:0] = [ROOT, os.path.join(ROOT, "oracle"), os.path.join(ROOT, "tests")]
+import deskew_data as dd  # noqa: E402
+import feature_extraction_ref as fr  # noqa: E402
+from superodom_amd import binding  # noqa: E402
+
+T0 = 1.7e9 + 0.25
+
+
+def _hip():
+    h = C.CDLL("libamdhip64.so")
+    h.hipMalloc.argtypes = [C.POINTER(C.c_void_p), C.c_size_t]
+    h.hipMemcpy.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_int]
+    h.hipFree.argtypes = [C.c_void_p]
+    return h
+
+
+def _best_ms(fn, reps, rounds=3):
+    fn()
+    best = float("inf")
+    for _ in range(rounds):
+        t = time.perf_counter()
+        for _ in range(reps):
+            fn()
+        best = min(best, 1e3 * (time.perf_counter() - t) / reps)
+    return best
+
+
+def rates(name, buf, w, h, rs, sensor, reps, kernels_only):
+    hip = _hip()
+    layout = fr.layout_for(sensor, 3, 0.2, row_step=rs)
+    poses = dd.pose_buffer(T0, seed=22, translate=False)
+    pp = np.ascontiguousarray(poses)
+    ppp = pp.ctypes.data_as(C.POINTER(C.c_double))
+    n = w * h
+    slam = binding.LidarSlamGpu(plane_res=0.2, max_iterations=4)
+    L = slam.L
+    info = binding.FeatureInfo()
+    d_raw = C.c_void_p()
+    assert hip.hipMalloc(C.byref(d_raw), buf.nbytes) == 0
+    assert hip.hipMemcpy(d_raw, buf.ctypes.data_as(C.c_void_p), buf.nbytes, 1) == 0
+    d_rec, d_surf = C.c_void_p(), C.c_void_p()
+
+    def dev():
+        rc = L.so_icp_extract_features_dev(slam.h, d_raw, w, h, C.byref(layout), T0, ppp, len(pp), 1, None, C.byref(d_rec), C.byref(d_surf),
+                                           C.byref(info))
+        assert rc == 0, rc
+    if kernels_only:
+        for _ in range(reps):
+            dev()
+        hip.hipFree(d_raw)
+        return
+    rec_out = np.empty((n, 32), np.uint8)
+    surf_out = np.empty((n, 32), np.uint8)
+
+    def host():
+        rc = L.so_icp_extract_features(slam.h, buf.ctypes.data_as(C.c_void_p), w, h, C.byref(layout), T0, ppp, len(pp), 1, None,
+                                       rec_out.ctypes.data_as(C.c_void_p), surf_out.ctypes.data_as(C.c_void_p), C.byref(info))
+        assert rc == 0, rc
+    host_ms = _best_ms(host, reps)
+    dev_ms = _best_ms(dev, reps)
+    n_surf = info.n_surface
+
+    # chains: a map seeded with the first frame, then every call registers (and inserts) the same sweep again
+    chain = {}
+    for mode in ("host", "dev"):
+        s = binding.LidarSlamGpu(plane_res=0.2, max_iterations=4)
+        pose = np.array([0, 0, 0, 0, 0, 0, 1.0])
+        k = [0]
+
+        def step(first=False):
+            t = T0 + 0.1 * k[0]
+            k[0] += 1
+            if mode == "dev":
+                _, ds, inf = s.extract_features_dev(d_raw.value, w, h, layout, T0, poses, True, None)
+                dp, nf, _ = s.prefilter_scan_dev(ds, inf.n_surface, 32, 1, 0.2, 0.4)
+                rc, _, _ = s.localization_dev(0 if first else 1, pose, dp, nf, t)
+            else:
+                _, sf, _ = s.extract_features(buf, w, h, layout, T0, poses, True, None)
+                dp, nf, _ = s.prefilter_scan(sf.view(np.float32)[:, :3], 1, 0.2, 0.4)
+                rc, _, _ = s.localization(0 if first else 1, pose, s.download_scan(dp, nf), t)
+            assert rc in (0, 2), rc
+        step(first=True)
+        chain[mode] = _best_ms(step, max(reps // 5, 5))
+        s.close()
+    hip.hipFree(d_raw)
+
+    t = time.perf_counter()
+    import oracle_py
+    rec = fr.ingest(buf, w, h, layout)
+    rec, _, _ = oracle_py.deskew(rec, 20, T0, poses, True, None)
+    fr.surf_sample(rec, 3, 0.2)
+    cpu_ms = 1e3 * (time.perf_counter() - t)
+    print(f"{name}: {n} points, {len(poses)} IMU poses, filter_point_size 3 -> {n_surf} surf points")
+    print(f"  host payload in, both clouds out  {host_ms:.3f} ms")
+    print(f"  resident in HBM                   {dev_ms:.3f} ms  (pose table upload + 2 kernels + count read-back)")
+    print(f"  chain features -> prefilter -> localization: resident {chain['dev']:.3f} ms, through host buffers {chain['host']:.3f} ms per frame")
+    print(f"  CPU restatement (numpy ingest + sampling, C oracle de-skew; one core, not the reference's code) {cpu_ms:.1f} ms")
+
+
+def main():
+    reps = int(sys.argv[sys.argv.index("--reps") + 1]) if "--reps" in sys.argv else 50
+    ko = "--kernels-only" in sys.argv
+    buf, w, h, rs, _ = fr.ouster_sweep(1024, 128, seed=1, nan_every=997, zero_every=61)
+    rates("os1_128-like Ouster", buf, w, h, rs, fr.SENSOR_OUSTER, reps, ko)
+    buf, w, h, rs, _ = fr.velodyne_sweep(28800, seed=1, nan_every=499, zero_every=73)
+    rates("VLP-16", buf, w, h, rs, fr.SENSOR_VELODYNE, reps, ko)
+
+
+if __name__ == "__main__":
+    main()
