@@ -1,0 +1,293 @@
+// batch.cpp -- so_icp_register_batch: B hypotheses of one scan in the same launches.
+//
+// One binning launch sequence over (queries x hypotheses), then rounds of { one k-NN launch over the chunks of every
+// hypothesis still iterating, one persistent solve launch in which every such hypothesis owns a group of workgroups
+// and runs its own LM controller (kernels.hip: solve_kernel<BATCH>) , one read-back of the state blocks }.  A hypothesis
+// is an independent registration: it leaves the rounds when its own termination rule fires (LidarSlam.cpp:141), and the
+// workgroups it held go to the others in the next round.  Results are bit-identical to so_icp_register per hypothesis.
+#include <hip/hip_runtime_api.h>
+
+#include <algorithm>
+#include <chrono>
+#include <cstddef>
+#include <cstring>
+#include <string>
+#include <thread>
+#include <vector>
+
+#include "ctx.h"
+
+namespace {
+
+constexpr int kBatchMaxConcurrent = 64;
+int batch_reserve(so_icp_ctx* c, uint32_t B, size_t n, uint32_t lg) {
+  so_icp_ctx::BatchBufs& b = c->batch;
+  const uint32_t bs = (uint32_t)(((n + 256 + 63) / 64) * 64);
+  const size_t T = (size_t)1 << lg;
+  const size_t partial_bytes = (size_t)kFitBlocksMax * kRecordChunksMax * 16;
+  if (B > b.cap_hyp || bs > b.bs || lg != b.table_log2) {
+    const uint32_t cap = std::max(B, b.cap_hyp), nbs = std::max(bs, b.bs);
+    b.release();
+    HIP_TRY(c, b.states.reserve((size_t)cap * sizeof(DevState))); HIP_TRY(c, b.begin.reserve((size_t)cap * sizeof(RegBeginArgs)));
+    HIP_TRY(c, b.active.reserve((size_t)cap * 4));
+    for (DevBuf* d : {&b.qslot, &b.qrank, &b.chunks}) HIP_TRY(c, d->reserve((size_t)cap * nbs * 4));
+    HIP_TRY(c, b.binned.reserve((size_t)cap * nbs * 16));
+    HIP_TRY(c, b.status.reserve((size_t)cap * nbs)); HIP_TRY(c, b.nbr5.reserve((size_t)cap * nbs * 20));
+    HIP_TRY(c, b.nd.reserve((size_t)cap * nbs * 32)); HIP_TRY(c, b.coeff.reserve((size_t)cap * nbs * 8));
+    for (DevBuf* d : {&b.bin_key, &b.bin_cnt, &b.bin_off}) HIP_TRY(c, d->reserve((size_t)cap * T * 4));
+    HIP_TRY(c, b.partials.reserve((size_t)cap * partial_bytes)); HIP_TRY(c, b.sync.reserve((size_t)cap * kSyncBytes));
+    HIP_TRY(c, b.hist.reserve((size_t)cap * kHistReplicas * kHistStride * 4));
+    HIP_TRY(c, hipHostMalloc(reinterpret_cast<void**>(&b.h_states), (size_t)cap * sizeof(DevState)));
+    HIP_TRY(c, hipHostMalloc(reinterpret_cast<void**>(&b.h_begin), (size_t)cap * sizeof(RegBeginArgs)));
+    HIP_TRY(c, hipHostMalloc(reinterpret_cast<void**>(&b.h_active), (size_t)cap * 4));
+    // tags / epochs of the record tables and hand-off blocks count up from zero; the state blocks start cleared
+    HIP_TRY(c, hipMemsetAsync(b.partials.p, 0, (size_t)cap * partial_bytes, c->stream));
+    HIP_TRY(c, hipMemsetAsync(b.sync.p, 0, (size_t)cap * kSyncBytes, c->stream));
+    HIP_TRY(c, hipMemsetAsync(b.states.p, 0, (size_t)cap * sizeof(DevState), c->stream));
+    HIP_TRY(c, hipMemsetAsync(b.hist.p, 0, (size_t)cap * kHistReplicas * kHistStride * 4, c->stream));
+    b.cap_hyp = cap; b.bs = nbs; b.table_log2 = lg; b.tables_clean = false;
+  }
+  if (!b.tables_clean) {  // (bin_offsets leaves the tables empty again)
+    HIP_TRY(c, hipMemsetAsync(b.bin_key.p, 0xFF, (size_t)b.cap_hyp * T * 4, c->stream));
+    HIP_TRY(c, hipMemsetAsync(b.bin_cnt.p, 0, (size_t)b.cap_hyp * T * 4, c->stream));
+  }
+  return SO_ICP_OK;
+}
+
+int register_batch_group(so_icp_ctx* c, const float* d_scan, size_t n, const double* poses_in, int B, double* poses_out, so_icp_stats* stats,
+                         int32_t* hyp_rc, const int pos[3], int count_5x5) {
+  const auto t_begin = std::chrono::steady_clock::now();
+  std::vector<so_icp_stats> local;
+  if (!stats) { local.resize((size_t)B); stats = local.data(); }
+  for (int h = 0; h < B; ++h) {
+    so_icp_stats* st = stats + h;
+    std::memset(st, 0, sizeof(*st));
+    st->flags = (!c->dmap ? SO_ICP_FLAG_HOST_MAP : 0u) | (c->direct_readback ? 0u : SO_ICP_FLAG_COPY_READBACK);
+    std::memcpy(poses_out + 7 * (size_t)h, poses_in + 7 * (size_t)h, 7 * sizeof(double));
+    if (c->have_hist) uncertainty_from_hist(c->prev_obs_hist, st->uncertainty);
+    st->pos_in_localmap[0] = pos[0]; st->pos_in_localmap[1] = pos[1]; st->pos_in_localmap[2] = pos[2];
+    st->laser_cloud_surf_from_map_num = count_5x5; st->laser_cloud_surf_stack_num = (int32_t)n; st->startup_count = c->startup_count;
+    hyp_rc[h] = SO_ICP_OK;
+  }
+  if (!(count_5x5 > 50)) { for (int h = 0; h < B; ++h) hyp_rc[h] = SO_ICP_NOT_ENOUGH_MAP_FEATURES; return SO_ICP_OK; }  // LidarSlam.cpp:113-116
+  if (n >= ((size_t)1 << 21)) return fail(c, SO_ICP_E_UNSUPPORTED, "scan of 2^21 points or more: the work-list counters hold 21 bits each (chunk descriptors 26)");
+  const int max_outer = std::min(c->cfg.max_iterations > 0 ? c->cfg.max_iterations : 4, SO_ICP_MAX_OUTER);
+  const int lm_max = std::min(c->cfg.lm_max_iterations > 0 ? c->cfg.lm_max_iterations : 4, 16);
+  const uint32_t lg = bin_table_log2(n);
+  int rc = batch_reserve(c, (uint32_t)B, n, lg);
+  if (rc) return rc;
+  so_icp_ctx::BatchBufs& b = c->batch;
+  hipStream_t s = c->stream;
+  for (int h = 0; h < B; ++h) {
+    std::memcpy(b.h_begin[h].pose, poses_in + 7 * (size_t)h, 7 * sizeof(double));
+    b.h_begin[h].max_outer = max_outer; b.h_begin[h].lm_max = lm_max; b.h_begin[h].chain_expect = 0; b.h_begin[h].pad = 0;  // (a hypothesis starts from its own guess)
+    b.h_active[h] = (uint32_t)h;
+  }
+  HIP_TRY(c, hipMemcpyAsync(b.begin.p, b.h_begin, (size_t)B * sizeof(RegBeginArgs), hipMemcpyHostToDevice, s));
+  HIP_TRY(c, hipMemcpyAsync(b.active.p, b.h_active, (size_t)B * 4, hipMemcpyHostToDevice, s));
+  const float plane_res_now = map_plane_res(c);
+  MatchParams mp = match_params(plane_res_now, c->ablate);
+  mp.chunk_cap = b.bs;
+  mp.hring[0] = mp.hring[1] = nullptr; mp.seq_base = 0; mp.publish_prev = 0;
+  mp.packed_leftover = &b.states.as<DevState>()->packed_leftover;
+  EvalParams ep = eval_params(plane_res_now, c->cfg.tukey_variant, c->ablate);
+  ep.n_queries = (uint32_t)n; ep.q_stride = 3;
+  ep.timeout_ticks = 20000000ull;  // 200 ms: a pass of one hypothesis on a few workgroups lasts up to a millisecond
+  const uint32_t v_grid = solve_grid((uint32_t)n, (uint32_t)c->n_cus);
+  const uint32_t resident = solve_batch_resident_blocks((uint32_t)c->n_cus, c->batch_degrade >= 1 ? 1 : 0);
+  if (resident < (uint32_t)B) {  // (the driver below sizes its groups by the resident workgroups; this is the second line of defence)
+    c->err = "so_icp_register_batch: fewer resident solve workgroups (" + std::to_string(resident) + ") than hypotheses in the group (" + std::to_string(B) + ")";
+    return kRetryWithoutPersistentSolve;  // degrade (fewer workgroups per hypothesis is not possible: one each) -> concurrent sequential registrations
+  }
+  BatchView bv{b.active.as<uint32_t>(), b.begin.as<RegBeginArgs>(), b.bs, (uint32_t)((size_t)1 << lg),
+               (uint32_t)((size_t)kFitBlocksMax * kRecordChunksMax * 2), (uint32_t)(kSyncBytes / 4), 1u, v_grid};
+  const BinTable bt{b.bin_key.as<uint32_t>(), b.bin_cnt.as<uint32_t>(), b.bin_off.as<uint32_t>(), lg};
+  DevState* ds = b.states.as<DevState>();
+  CorrBuffers corr{b.nd.as<double4>(), b.coeff.as<double>(), b.status.as<uint8_t>()};
+  // ---- binning of the scan under every hypothesis' pose: (queries x hypotheses) in three launches
+  b.tables_clean = false;
+  const double zero_pose[7] = {0, 0, 0, 0, 0, 0, 1};
+  launch_scan_keys(d_scan, (uint32_t)n, ds, zero_pose, max_outer, lm_max, b.hist.as<int32_t>(), c->view, c->cfg.max_surface_features, 0, 1,
+                   b.qslot.as<uint32_t>(), b.qrank.as<uint32_t>(), b.status.as<uint8_t>(), bt, s, false, &bv, (uint32_t)B);
+  launch_bin_offsets(bt, b.chunks.as<uint32_t>(), b.bs, ds, s, &bv, (uint32_t)B);
+  b.tables_clean = true;
+  launch_bin_place(bt, d_scan, (uint32_t)n, b.qslot.as<uint32_t>(), b.qrank.as<uint32_t>(), b.binned.as<float4>(), s, nullptr, &bv, (uint32_t)B);
+  HIP_TRY(c, hipGetLastError());
+  std::vector<uint32_t> act((size_t)B);
+  for (int h = 0; h < B; ++h) act[(size_t)h] = (uint32_t)h;
+  // Rounds are CHAINED -- enqueued on the same list without the host looking at the report in between -- while most of the list is
+  // expected to go on: a hypothesis that has finished makes its workgroups of a later round return at once (reg_done), so a stale
+  // list costs launches, never results.  After round 0 always (one outer iteration cannot meet the convergence test of most
+  // guesses, and a list that shrinks by less than half keeps its workgroups per hypothesis anyway); after a later round when
+  // the previous batch of this context found three quarters of that round's list still active (batch_survivors).  Every
+  // report + synchronisation left out is 35 us in which the device sits idle (measured: 4 per batch of 5.7 ms).
+  for (int it = 0; it < max_outer && !act.empty();) {
+    const uint32_t n_act = (uint32_t)act.size();
+    if (it > 0) {  // (round 0 uses the identity list uploaded with the poses; the stream was synchronised by the last read-back)
+      for (uint32_t k = 0; k < n_act; ++k) b.h_active[k] = act[k];
+      HIP_TRY(c, hipMemcpyAsync(b.active.p, b.h_active, (size_t)n_act * 4, hipMemcpyHostToDevice, s));
+    }
+    // workgroups per hypothesis: the resident grid split evenly (a power of two, never more than the grid they stand in for)
+    uint32_t G = 1;
+    while (2u * G * n_act <= resident && 2u * G <= v_grid) G *= 2u;
+    bv.wg_per_hyp = G;
+    const int first = it;
+    for (;;) {
+      MatchParams mp_it = mp;
+      mp_it.skip_near_pass = it == 0 ? 1 : 0;  // round 0 starts with the full k-NN pass (hypotheses +-0.5 m / +-5 degrees off: the near pass certifies almost nothing)
+      mp_it.pack_light = (c->knn_pack && !mp_it.skip_near_pass) ? 1 : 0;
+      launch_knn_plane(b.binned.as<float4>(), b.chunks.as<uint32_t>(), ds, c->view, mp_it, corr,
+                       b.nbr5.as<uint32_t>(), b.hist.as<int32_t>(), s, nullptr, nullptr, &bv, n_act);
+      EvalParams ep_it = ep;
+      ep_it.epoch_base = (++c->solve_launches) << 5;
+      launch_solve_batch(lm_max, d_scan, d_scan + 1, d_scan + 2, corr, ds, ep_it, b.partials.as<double>(), b.sync.as<uint32_t>(), b.hist.as<int32_t>(),
+                         c->view, b.nbr5.as<uint32_t>(), mp, bv, n_act, s);
+      HIP_TRY(c, hipGetLastError());
+      ++it;
+      const bool chain = c->batch_chain && it < max_outer && it - 1 < so_icp_ctx::kBatchRoundsTracked && (it - 1 == 0 || c->batch_survivors[it - 1] >= 0.75f);
+      if (!chain) break;
+    }
+    // at a synchronisation point the host needs two words per hypothesis (outer_iter, reg_done); the whole state blocks (280 KB
+    // for 64 hypotheses) are read once, after the last round
+    static_assert(offsetof(DevState, reg_done) == offsetof(DevState, outer_iter) + 4, "the round report reads outer_iter and reg_done together");
+    HIP_TRY(c, hipMemcpy2DAsync(reinterpret_cast<char*>(b.h_states) + offsetof(DevState, outer_iter), sizeof(DevState),
+                                reinterpret_cast<const char*>(ds) + offsetof(DevState, outer_iter), sizeof(DevState), 8, (size_t)B,
+                                hipMemcpyDeviceToHost, s));
+    HIP_TRY(c, hipStreamSynchronize(s));
+    std::vector<uint32_t> next;
+    uint32_t alive_after[so_icp_ctx::kBatchRoundsTracked] = {};
+    for (uint32_t h : act) {
+      const DevState& H = b.h_states[h];
+      // a hypothesis of the list ran the rounds first .. it-1 unless it finished on the way (then outer_iter says where)
+      const bool ran_all = H.outer_iter == it, finished_early = H.reg_done && H.outer_iter > first && H.outer_iter < it;
+      if (!ran_all && !finished_early) {  // the hypothesis' solve did not finish (a wait inside the launch gave up)
+        c->err = "so_icp_register_batch: the solve of hypothesis " + std::to_string(h) + " did not complete in round " + std::to_string(H.outer_iter) +
+                 " (workgroups not co-resident: compute units held by another process?)";
+        return kRetryWithoutPersistentSolve;
+      }
+      for (int r = first; r < it && r < so_icp_ctx::kBatchRoundsTracked; ++r)
+        if (!(H.reg_done && H.outer_iter <= r + 1)) ++alive_after[r];
+      if (!H.reg_done && it < max_outer) next.push_back(h);
+    }
+    for (int r = first; r < it && r < so_icp_ctx::kBatchRoundsTracked; ++r) c->batch_survivors[r] = (float)alive_after[r] / (float)n_act;
+    act.swap(next);
+  }
+  HIP_TRY(c, hipMemcpyAsync(b.h_states, ds, (size_t)B * sizeof(DevState), hipMemcpyDeviceToHost, s));
+  HIP_TRY(c, hipStreamSynchronize(s));
+  const double ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_begin).count();
+  if ((c->ablate & 128) && c->h_state)  // profiling: so_icp_debug_stamps shows the phase stamps of hypothesis 0's last solve
+    for (int i = 0; i < 16; ++i) c->h_state->dbg[i] = b.h_states[0].dbg[i];
+  for (int h = 0; h < B; ++h) {
+    fill_result(c, b.h_states[h], poses_in + 7 * (size_t)h, stats + h, poses_out + 7 * (size_t)h, false);
+    stats[h].time_elapsed_ms = ms;  // (of the whole group: the hypotheses advance together)
+  }
+  return SO_ICP_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+
+int so_icp_register_batch(so_icp_ctx* c, const float* xyz, const void* d_scan, size_t n, size_t stride_bytes, const double* poses_in,
+                          int n_hyp, double* poses_out, so_icp_stats* stats, int32_t* rc_out) {
+  if (!c || !poses_in || !poses_out || n_hyp < 0 || (!xyz && !d_scan && n)) return SO_ICP_E_INVALID;
+  NEED_DEVICE(c);
+  HIP_TRY(c, hipSetDevice(c->cfg.device_id));
+  if (c->cfg.world_size != 1)  // (hypotheses are independent: replicate the map and split THEM over the ranks -- bench.py's batch64)
+    return fail(c, SO_ICP_E_UNSUPPORTED, "so_icp_register_batch needs the whole map on one device (world_size == 1)");
+  if (n_hyp == 0) return 0;
+  const float* scan = static_cast<const float*>(d_scan);
+  if (!scan) {
+    const int rc = upload_scan_impl(c, xyz, n, stride_bytes, c->d_scan_own);
+    if (rc) return rc;
+    scan = c->d_scan_own.as<float>();
+  }
+  // the map window is placed once, for hypothesis 0 (LidarSlam.cpp:363); every hypothesis sees that map
+  int pos[3];
+  map_shift(c, poses_in, pos);
+  std::memcpy(c->last_pos, pos, sizeof(pos));
+  int rc = upload_map(c);
+  if (rc) return rc;
+  if (n > 0 && c->batch_degrade < 2) {
+    // batched kernels: groups of up to kBatchMaxConcurrent hypotheses advance together (kernels.hip, BatchView)
+    const int count = map_count_5x5(c, pos);
+    std::vector<int32_t> hrc((size_t)n_hyp, 0);
+    for (int base = 0; base < n_hyp;) {
+      // a group never holds more hypotheses than solve workgroups can be resident together (one workgroup per hypothesis at
+      // least): on a device with few compute units -- SOICP_SOLVE_WORKGROUPS, a partitioned device, one workgroup per unit after
+      // a failed co-residency wait -- the batch goes through in smaller groups instead of failing
+      const int cap = (int)std::min<uint32_t>((uint32_t)kBatchMaxConcurrent, solve_batch_resident_blocks((uint32_t)c->n_cus, c->batch_degrade >= 1 ? 1 : 0));
+      if (cap < 1) { c->batch_degrade = 2; break; }
+      const int B = std::min(cap, n_hyp - base);
+      rc = register_batch_group(c, scan, n, poses_in + 7 * (size_t)base, B, poses_out + 7 * (size_t)base, stats ? stats + base : nullptr,
+                                hrc.data() + base, pos, count);
+      // A batched solve launch needs its workgroups resident together.  If the device could not provide that (shared with another
+      // process), the group is repeated with one workgroup per compute unit; if that fails too the context falls back to
+      // concurrent sequential registrations (below) for the rest of its life.  so_icp_last_error keeps the notice.
+      if (rc == kRetryWithoutPersistentSolve) {
+        HIP_TRY(c, hipStreamSynchronize(c->stream));
+        c->batch.tables_clean = false;
+        if (++c->batch_degrade <= 1) continue;  // (the same group again)
+        break;
+      }
+      if (rc < 0) return rc;
+      base += B;
+    }
+    if (c->batch_degrade < 2) {
+      int ok = 0;
+      for (int h = 0; h < n_hyp; ++h) { if (rc_out) rc_out[h] = hrc[(size_t)h]; if (hrc[(size_t)h] == SO_ICP_OK) ++ok; }
+      return ok;
+    }
+  }
+  // SOICP_BATCH_MODE=lanes, empty scans, and a device that cannot keep the batched solve resident: the hypotheses as concurrent
+  // sequential registrations on worker contexts (own stream / buffers / state each, one launch per evaluation)
+  const int lanes = std::max(1, std::min(16, n_hyp));
+  // worker contexts: own stream / buffers / device state, no map of their own (they borrow this context's resident map)
+  while ((int)c->workers.size() < lanes - 1) {
+    so_icp_config wc = c->cfg;
+    wc.time_kernels = 0;
+    so_icp_ctx* w = so_icp_create(&wc);
+    if (!w) return fail(c, SO_ICP_E_HIP, "so_icp_register_batch: worker context: " + g_create_error);
+    w->dmap.reset();
+    c->workers.push_back(w);
+  }
+  so_icp_ctx::Borrow bw;
+  bw.on = true; bw.view = c->view; bw.plane_res = map_plane_res(c);
+  std::memcpy(bw.pos, pos, sizeof(pos));
+  bw.count_5x5 = map_count_5x5(c, pos);
+  std::vector<so_icp_ctx*> lane_ctx(1, c);
+  for (int l = 1; l < lanes; ++l) lane_ctx.push_back(c->workers[l - 1]);
+  for (so_icp_ctx* w : lane_ctx) {
+    w->borrow = bw; w->batch_mode = true; w->batch_single = (lanes == 1);
+    std::memcpy(w->prev_obs_hist, c->prev_obs_hist, sizeof(c->prev_obs_hist));
+    w->have_hist = c->have_hist; w->startup_count = c->startup_count;
+    w->cfg.max_iterations = c->cfg.max_iterations; w->cfg.lm_max_iterations = c->cfg.lm_max_iterations;
+    w->cfg.max_surface_features = c->cfg.max_surface_features;
+  }
+  std::vector<int> lane_rc(lanes, 0);
+  std::vector<int> hyp_rc((size_t)n_hyp, 0);
+  auto run_lane = [&](int l) {
+    so_icp_ctx* w = lane_ctx[l];
+    if (hipSetDevice(c->cfg.device_id) != hipSuccess) { lane_rc[l] = SO_ICP_E_HIP; return; }
+    for (int h = l; h < n_hyp; h += lanes) {
+      so_icp_stats local;
+      const int r = register_core(w, scan, n, poses_in + 7 * (size_t)h, poses_out + 7 * (size_t)h, stats ? stats + h : &local);
+      hyp_rc[h] = r;
+      if (r < 0) { lane_rc[l] = r; return; }
+    }
+  };
+  std::vector<std::thread> th;
+  for (int l = 1; l < lanes; ++l) th.emplace_back(run_lane, l);
+  run_lane(0);
+  for (std::thread& t : th) t.join();
+  int ok = 0, err = 0;
+  for (int l = 0; l < lanes; ++l) {
+    lane_ctx[l]->borrow.on = false; lane_ctx[l]->batch_mode = false;
+    if (lane_rc[l] < 0 && !err) { err = lane_rc[l]; if (l > 0) c->err = "worker: " + lane_ctx[l]->err; }
+  }
+  for (int h = 0; h < n_hyp; ++h) { if (rc_out) rc_out[h] = hyp_rc[h]; if (hyp_rc[h] == SO_ICP_OK) ++ok; }
+  return err ? err : ok;
+}
+
+}  // extern "C"

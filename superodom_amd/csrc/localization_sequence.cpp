@@ -14,11 +14,7 @@
 #include <cstring>
 #include <string>
 
-#include "../../include/so_icp.h"
-#include "ctx_access.h"
-#include "so_math.h"
-
-using namespace soicp;
+#include "ctx.h"
 
 extern "C" {
 
@@ -28,13 +24,12 @@ int so_icp_localization_sequence(so_icp_ctx* c, int count, const void* const* sc
   if (n_done) *n_done = 0;
   if (!c || count < 0 || (count && (!scans || !n_points || !pose0 || !times || !poses_out)) || (count > 1 && !deltas)) return SO_ICP_E_INVALID;
   if (stride_bytes == 0) stride_bytes = 12;
-  if (stride_bytes % 4 || stride_bytes < 12) return ctx_note(c, SO_ICP_E_INVALID, "so_icp_localization_sequence: stride_bytes must be a multiple of 4, >= 12");
-  if (scans_on_device && stride_bytes != 12) return ctx_note(c, SO_ICP_E_INVALID, "so_icp_localization_sequence: resident scans are packed xyz (stride 12)");
+  if (stride_bytes % 4 || stride_bytes < 12) return fail(c, SO_ICP_E_INVALID, "so_icp_localization_sequence: stride_bytes must be a multiple of 4, >= 12");
+  if (scans_on_device && stride_bytes != 12) return fail(c, SO_ICP_E_INVALID, "so_icp_localization_sequence: resident scans are packed xyz (stride 12)");
   for (int k = 0; k < count; ++k)
-    if (!scans[k] && n_points[k]) return ctx_note(c, SO_ICP_E_INVALID, "so_icp_localization_sequence: scans[" + std::to_string(k) + "] is NULL");
+    if (!scans[k] && n_points[k]) return fail(c, SO_ICP_E_INVALID, "so_icp_localization_sequence: scans[" + std::to_string(k) + "] is NULL");
   if (count == 0) return SO_ICP_OK;
-  if (ctx_view(c).host_only)
-    return ctx_note(c, SO_ICP_E_HIP, "host-only context (device_id < 0): no compute path -- libsoicp has no CPU fallback");
+  NEED_DEVICE(c);
 
   double guess[7];
   std::memcpy(guess, pose0, sizeof(guess));

@@ -1,4 +1,4 @@
-"""-m gpu: scans binned AHEAD of their registration (round 5; icp_context.cpp stage_prebin, kernels.hip scan_keys_kernel with
+"""-m gpu: scans binned AHEAD of their registration (round 5; staging.cpp stage_prebin, kernels.hip scan_keys_kernel with
 prebin_ctr / reg_begin_prebinned_kernel).  A scan announced with so_icp_stage_scan from DMA-able memory is hash-binned on the copy
 queue behind its copy, under the guess of the registration in flight; its own registration starts with the k-NN sweep
 (so_icp_stats::flags & SO_ICP_FLAG_BINNED_AHEAD).  The binning only decides which queries share a wavefront: every result must be
