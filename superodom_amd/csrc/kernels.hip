@@ -7,7 +7,7 @@
 //                       exact 5-NN over the hashed-voxel cell grid (LDS-staged candidate tiles, selection network, exact
 //                       re-rank + certification), distance gate
 //                                                                                  (LocalMap.h:481-525, LidarSlam.cpp:720-747)
-//   solve_kernel        ONE persistent launch per outer iteration: plane fit (PCA gate, 5x3 LS plane, inlier gate,
+//   solve_kernel        ONE persistent launch per outer iteration: plane fit (plane_fit.h: PCA gate, 5x3 LS plane, inlier gate,
 //                       coefficient, observability labels; LidarSlam.cpp:514-693) + every LM evaluation (residual,
 //                       Tukey x coefficient weight, 6-DoF Jacobian, the 21+6+1+1 fp64 normal-equation sums;
 //                       lidarOptimization.cpp:55-80) + the Ceres-equivalent LM controller (lm_solver.h), with
@@ -409,264 +409,6 @@ __device__ __forceinline__ uint32_t knn27(const DevMapView& m, const CellRef& c,
 }
 
 // ------------------------------------------------------------------------------------------------
-// plane fit in registers
-// ------------------------------------------------------------------------------------------------
-// cyclic Jacobi on a symmetric 3x3 (restates the RESULT of Eigen::SelfAdjointEigenSolver<Matrix3d>,
-// utils/superodom_utils.h:150: ascending eigenvalues + eigenvector of the smallest one).
-__device__ __forceinline__ void jacobi_rot(double& app, double& aqq, double& apq, double& arp, double& arq,
-                                           double& v0p, double& v0q, double& v1p, double& v1q, double& v2p, double& v2q) {
-  if (apq == 0.0) return;
-  // t = tan(phi) of the annihilating rotation, smaller root: with d = aqq - app, b = 2 apq,
-  //   t = sgn(d) b / (|d| + sqrt(d^2 + b^2))   (== sgn(theta) / (|theta| + sqrt(theta^2 + 1)), theta = d / b)
-  // one sqrt, one division and one rsqrt per rotation instead of three divisions and two square roots.
-  const double d = aqq - app, b2 = 2.0 * apq;
-  const double t = (d >= 0 ? b2 : -b2) / (fabs(d) + sqrt(d * d + b2 * b2));
-  const double c = rsqrt(t * t + 1.0), s = t * c;
-  app -= t * apq; aqq += t * apq; apq = 0.0;
-  const double rp = c * arp - s * arq, rq = s * arp + c * arq;
-  arp = rp; arq = rq;
-  double a, b;
-  a = c * v0p - s * v0q; b = s * v0p + c * v0q; v0p = a; v0q = b;
-  a = c * v1p - s * v1q; b = s * v1p + c * v1q; v1p = a; v1q = b;
-  a = c * v2p - s * v2q; b = s * v2p + c * v2q; v2p = a; v2q = b;
-}
-
-__device__ __forceinline__ void eig3_sym(double a00, double a01, double a02, double a11, double a12, double a22,
-                                         double ev[3], double nrm[3]) {
-  double v00 = 1, v01 = 0, v02 = 0, v10 = 0, v11 = 1, v12 = 0, v20 = 0, v21 = 0, v22 = 1;  // v[row][col]
-  for (int sweep = 0; sweep < 16; ++sweep) {
-    const double off = a01 * a01 + a02 * a02 + a12 * a12;
-    const double dg = a00 * a00 + a11 * a11 + a22 * a22;
-    if (off <= 1e-30 * dg || off == 0.0) break;  // off-diagonal below 1e-15 of the diagonal: converged in fp64
-    jacobi_rot(a00, a11, a01, a02, a12, v00, v01, v10, v11, v20, v21);  // (p,q)=(0,1), r=2
-    jacobi_rot(a00, a22, a02, a01, a12, v00, v02, v10, v12, v20, v22);  // (0,2), r=1
-    jacobi_rot(a11, a22, a12, a01, a02, v01, v02, v11, v12, v21, v22);  // (1,2), r=0
-  }
-  // ascending sort, keep the eigenvector of the smallest eigenvalue
-  double e0 = a00, e1 = a11, e2 = a22;
-  double n0 = v00, n1 = v10, n2 = v20;  // column 0
-  if (e1 < e0 && e1 <= e2) { n0 = v01; n1 = v11; n2 = v21; }
-  else if (e2 < e0 && e2 < e1) { n0 = v02; n1 = v12; n2 = v22; }
-  double t;
-  if (e0 > e1) { t = e0; e0 = e1; e1 = t; }
-  if (e1 > e2) { t = e1; e1 = e2; e2 = t; }
-  if (e0 > e1) { t = e0; e0 = e1; e1 = t; }
-  ev[0] = e0; ev[1] = e1; ev[2] = e2;
-  nrm[0] = n0; nrm[1] = n1; nrm[2] = n2;
-}
-
-// a / b in ~9 instructions instead of the ~28 of the IEEE sequence: v_rcp_f64, two Newton steps, one residual correction
-// (within 1 ulp of the correctly rounded quotient).  The plane-fit pass executes ~26 divisions per query: a third of
-// its instructions.  Used only there -- never in the LM controller or the k-NN certification.
-__device__ __forceinline__ double fdiv(double a, double b) {
-  double r = __builtin_amdgcn_rcp(b);
-  r = __builtin_fma(__builtin_fma(-b, r, 1.0), r, r);
-  r = __builtin_fma(__builtin_fma(-b, r, 1.0), r, r);
-  const double q = a * r;
-  return __builtin_fma(__builtin_fma(-b, q, a), r, q);
-}
-
-// Same result without iterations (the cyclic Jacobi above costs ~1500 fp64 instructions per query, two thirds of the
-// plane-fit pass): the spectrum of a 5-point scatter matrix is lambda0 << lambda1 <= lambda2 for anything that can pass
-// the gates, so
-//   lambda0    = smallest root of the characteristic cubic by Newton from 0 (monotone from below for a polynomial with
-//                real roots; the matrix is first scaled to unit max-norm),
-//   lambda1,2  = roots of the deflated quadratic,
-//   n          = the largest of the three row cross products of (A - lambda0 I), normalised.
-// Eigenvalues agree with the Jacobi values to ~1e-14 relative, the normal to ~1e-15 when lambda0 is separated; only the
-// gates (LidarSlam.cpp:772) and the float observability labels consume them.
-__device__ __forceinline__ void eig3_sym_direct(double a00, double a01, double a02, double a11, double a12, double a22,
-                                                double ev[3], double nrm[3]) {
-  const double mx = fmax(fmax(fmax(fabs(a00), fabs(a11)), fabs(a22)), fmax(fmax(fabs(a01), fabs(a02)), fabs(a12)));
-  if (!(mx > 0.0)) { ev[0] = ev[1] = ev[2] = 0.0; nrm[0] = 1.0; nrm[1] = 0.0; nrm[2] = 0.0; return; }
-  const double is = fdiv(1.0, mx);
-  a00 *= is; a01 *= is; a02 *= is; a11 *= is; a12 *= is; a22 *= is;
-  // p(l) = -l^3 + c2 l^2 - c1 l + c0
-  const double c2 = a00 + a11 + a22;
-  const double m00 = a11 * a22 - a12 * a12, m11 = a00 * a22 - a02 * a02, m22 = a00 * a11 - a01 * a01;
-  const double c1 = m00 + m11 + m22;
-  const double c0 = a00 * m00 - a01 * (a01 * a22 - a12 * a02) + a02 * (a01 * a12 - a11 * a02);
-  double l = 0.0;
-#pragma unroll 1
-  for (int it = 0; it < 60; ++it) {  // 2-3 iterations when lambda0 is separated; linear convergence only towards a double root
-    const double f = ((-l + c2) * l - c1) * l + c0;      // p(l)
-    const double df = (-3.0 * l + 2.0 * c2) * l - c1;    // p'(l) < 0 left of the smallest root
-    if (!(df < 0.0) || !(f > 0.0)) break;   // at (or, by rounding, just past) the root
-    const double step = fdiv(f, df);         // < 0: the iterate moves right, never beyond the root (p is convex there)
-    l -= step;
-    if (!(-step > 4e-16)) break;             // the matrix has unit max-norm: below the noise of p(l)
-  }
-  if (!(l > 0.0)) l = fmax(l, 0.0);
-  // deflate: l1 + l2 = c2 - l, l1 l2 = c1 - l (c2 - l)
-  const double sm = c2 - l, pr = c1 - l * sm;
-  double disc = sm * sm - 4.0 * pr;
-  disc = disc > 0.0 ? sqrt(disc) : 0.0;
-  const double l2 = 0.5 * (sm + disc);
-  const double l1 = (l2 > 0.0) ? fdiv(pr, l2) : 0.0;  // the smaller root from the product: no cancellation
-  ev[0] = l * mx; ev[1] = l1 * mx; ev[2] = l2 * mx;
-  // null vector of (A - l I): largest cross product of its rows
-  const double r00 = a00 - l, r11 = a11 - l, r22 = a22 - l;
-  const double x0 = a01 * a12 - a02 * r11, x1 = a02 * a01 - r00 * a12, x2 = r00 * r11 - a01 * a01;     // row0 x row1
-  const double y0 = a01 * r22 - a02 * a12, y1 = a02 * a02 - r00 * r22, y2 = r00 * a12 - a01 * a02;     // row0 x row2
-  const double z0 = r11 * r22 - a12 * a12, z1 = a12 * a02 - a01 * r22, z2 = a01 * a12 - r11 * a02;     // row1 x row2
-  const double nx = x0 * x0 + x1 * x1 + x2 * x2, ny = y0 * y0 + y1 * y1 + y2 * y2, nz = z0 * z0 + z1 * z1 + z2 * z2;
-  double v0 = x0, v1 = x1, v2 = x2, nn = nx;
-  if (ny > nn) { v0 = y0; v1 = y1; v2 = y2; nn = ny; }
-  if (nz > nn) { v0 = z0; v1 = z1; v2 = z2; nn = nz; }
-  if (!(nn > 0.0)) { nrm[0] = 1.0; nrm[1] = 0.0; nrm[2] = 0.0; return; }
-  const double inv = rsqrt(nn);
-  nrm[0] = v0 * inv; nrm[1] = v1 * inv; nrm[2] = v2 * inv;
-}
-
-// least squares A x = -1 (A = 5x3 neighbour coordinates) by column-pivoted Householder QR
-// (restates matA0.colPivHouseholderQr().solve(matB0), LidarSlam.cpp:798-806).
-__device__ __forceinline__ bool plane_ls5(const float nb[15], double x[3]) {
-  double A[3][5], b[5];
-  int perm[3] = {0, 1, 2};
-#pragma unroll
-  for (int i = 0; i < 5; ++i) {
-    A[0][i] = (double)nb[3 * i]; A[1][i] = (double)nb[3 * i + 1]; A[2][i] = (double)nb[3 * i + 2];
-    b[i] = -1.0;
-  }
-#pragma unroll
-  for (int k = 0; k < 3; ++k) {
-    double nrm[3] = {0, 0, 0};
-#pragma unroll
-    for (int j = k; j < 3; ++j) {
-      double s = 0;
-#pragma unroll
-      for (int i = k; i < 5; ++i) s += A[j][i] * A[j][i];
-      nrm[j] = s;
-    }
-    int piv = k;
-    double best = nrm[k];
-#pragma unroll
-    for (int j = k + 1; j < 3; ++j)
-      if (nrm[j] > best) { best = nrm[j]; piv = j; }
-#pragma unroll
-    for (int j = k + 1; j < 3; ++j)
-      if (piv == j) {
-#pragma unroll
-        for (int i = 0; i < 5; ++i) { const double t = A[k][i]; A[k][i] = A[j][i]; A[j][i] = t; }
-        const int t = perm[k]; perm[k] = perm[j]; perm[j] = t;
-      }
-    double alpha = sqrt(best);
-    if (alpha != 0.0) {
-      if (A[k][k] > 0) alpha = -alpha;
-      double v[5];
-      double vn2 = 0;
-#pragma unroll
-      for (int i = k; i < 5; ++i) v[i] = A[k][i];
-      v[k] -= alpha;
-#pragma unroll
-      for (int i = k; i < 5; ++i) vn2 += v[i] * v[i];
-      if (vn2 != 0.0) {
-#pragma unroll
-        for (int j = k + 1; j < 3; ++j) {
-          double dot = 0;
-#pragma unroll
-          for (int i = k; i < 5; ++i) dot += v[i] * A[j][i];
-          const double f = fdiv(2.0 * dot, vn2);
-#pragma unroll
-          for (int i = k; i < 5; ++i) A[j][i] -= f * v[i];
-        }
-        double dot = 0;
-#pragma unroll
-        for (int i = k; i < 5; ++i) dot += v[i] * b[i];
-        const double f = fdiv(2.0 * dot, vn2);
-#pragma unroll
-        for (int i = k; i < 5; ++i) b[i] -= f * v[i];
-        A[k][k] = alpha;
-      }
-    }
-  }
-  const double y2 = fdiv(b[2], A[2][2]);
-  const double y1 = fdiv(b[1] - A[2][1] * y2, A[1][1]);
-  const double y0 = fdiv(b[0] - A[1][0] * y1 - A[2][0] * y2, A[0][0]);
-#pragma unroll
-  for (int a = 0; a < 3; ++a) x[a] = (perm[0] == a) ? y0 : ((perm[1] == a) ? y1 : y2);
-  return isfinite(x[0]) && isfinite(x[1]) && isfinite(x[2]);
-}
-
-// FeatureObservabilityAnalysis, LidarSlam.cpp:574-693: float arithmetic on float-cast inputs; returns
-// the three labels the histogram counts (rot#1, rot#2, trans#1; LidarSlam.cpp:336-339).
-__device__ __forceinline__ void observability(const double pw[3], const double ev[3], const double nrm[3], const Pose& pose,
-                                              int& o0, int& o1, int& o2) {
-  const float px = (float)pw[0], py = (float)pw[1], pz = (float)pw[2];
-  const float nx = (float)nrm[0], ny = (float)nrm[1], nz = (float)nrm[2];
-  const double l1 = sqrt(ev[2]), l2 = sqrt(ev[1]), l3 = sqrt(ev[0]);
-  const double planar_2 = fdiv(l2 - l3, l1);
-  const float qf[4] = {(float)pose.q[0], (float)pose.q[1], (float)pose.q[2], (float)pose.q[3]};
-  float ax[3][3];
-  quat_rotate<float>(qf, 1.f, 0.f, 0.f, ax[0][0], ax[0][1], ax[0][2]);
-  quat_rotate<float>(qf, 0.f, 1.f, 0.f, ax[1][0], ax[1][1], ax[1][2]);
-  quat_rotate<float>(qf, 0.f, 0.f, 1.f, ax[2][0], ax[2][1], ax[2][2]);
-  const float cx = py * nz - pz * ny, cy = pz * nx - px * nz, cz = px * ny - py * nx;
-  float rot[6], tr[3];
-  const float psq = (float)(planar_2 * planar_2);
-#pragma unroll
-  for (int a = 0; a < 3; ++a) {
-    const float v = cx * ax[a][0] + cy * ax[a][1] + cz * ax[a][2];
-    rot[2 * a] = v; rot[2 * a + 1] = -v;
-    tr[a] = psq * fabsf(nx * ax[a][0] + ny * ax[a][1] + nz * ax[a][2]);
-  }
-  // descending order, ties keep the lower label (stable insertion sort in libstdc++ for n < 16)
-  int b1 = 0;
-#pragma unroll
-  for (int a = 1; a < 6; ++a) if (rot[a] > rot[b1]) b1 = a;
-  int b2 = -1;
-#pragma unroll
-  for (int a = 0; a < 6; ++a) if (a != b1 && (b2 < 0 || rot[a] > rot[b2])) b2 = a;
-  int t1 = 0;
-#pragma unroll
-  for (int a = 1; a < 3; ++a) if (tr[a] > tr[t1]) t1 = a;
-  o0 = b1; o1 = b2; o2 = 6 + t1;
-}
-
-// ComputePlaneDistanceParameters after the neighbour search (LidarSlam.cpp:533-571) with the reference's own algorithms --
-// column-pivoted Householder for the plane, optionally cyclic Jacobi for the PCA.  Production runs plane_fit5 (plane_fit.h:
-// the closed form of the same least-squares problem); this one is kept behind SOICP_ABLATE = 4096 / 512 (PROF kernels) for A/B
-// runs and for the gate-edge test.
-__device__ __forceinline__ int plane_from_neighbours(const float nb[15], const double pw[3], const Pose& pose,
-                                                     const MatchParams& mp, double nd[4], double& coeff, int obs[3], bool jacobi_eig = false) {
-  // PCA (LidarSlam.cpp:756-775, utils/superodom_utils.h:143-151)
-  double mx = 0, my = 0, mz = 0;
-#pragma unroll
-  for (int j = 0; j < 5; ++j) { mx += (double)nb[3 * j]; my += (double)nb[3 * j + 1]; mz += (double)nb[3 * j + 2]; }
-  mx = fdiv(mx, 5.0); my = fdiv(my, 5.0); mz = fdiv(mz, 5.0);
-  double s00 = 0, s01 = 0, s02 = 0, s11 = 0, s12 = 0, s22 = 0;
-#pragma unroll
-  for (int j = 0; j < 5; ++j) {
-    const double a = (double)nb[3 * j] - mx, b = (double)nb[3 * j + 1] - my, c = (double)nb[3 * j + 2] - mz;
-    s00 += a * a; s01 += a * b; s02 += a * c; s11 += b * b; s12 += b * c; s22 += c * c;
-  }
-  double ev[3], nrm[3];
-  if (jacobi_eig) eig3_sym(s00, s01, s02, s11, s12, s22, ev, nrm);  // test switch (SOICP_ABLATE=512, PROF instantiation): the iterative reference solver
-  else eig3_sym_direct(s00, s01, s02, s11, s12, s22, ev, nrm);
-  if (ev[0] < 1e-6 || fdiv(ev[1], ev[2]) < 0.1) return SO_MATCH_BAD_PCA;  // LidarSlam.cpp:772
-  double x[3];
-  if (!plane_ls5(nb, x)) return SO_MATCH_INVALID;                    // LidarSlam.cpp:809-812
-  const double nn = sqrt(x[0] * x[0] + x[1] * x[1] + x[2] * x[2]);
-  const double d = fdiv(1.0, nn);                                    // LidarSlam.cpp:815
-  const double n0 = fdiv(x[0], nn), n1 = fdiv(x[1], nn), n2 = fdiv(x[2], nn);  // LidarSlam.cpp:816
-  double sum = 0;
-  bool too_far = false;
-#pragma unroll
-  for (int j = 0; j < 5; ++j) {
-    const double dist = fabs(n0 * (double)nb[3 * j] + n1 * (double)nb[3 * j + 1] + n2 * (double)nb[3 * j + 2] + d);
-    too_far |= dist > mp.max_point_dist;                             // LidarSlam.cpp:832
-    sum += dist;
-  }
-  if (too_far) return SO_MATCH_MSE;
-  const double mean_abs = fdiv(sum, 5.0);
-  if (pw[0] * nrm[0] + pw[1] * nrm[1] + pw[2] * nrm[2] < 0) { nrm[0] = -nrm[0]; nrm[1] = -nrm[1]; nrm[2] = -nrm[2]; }  // :553-561
-  observability(pw, ev, nrm, pose, obs[0], obs[1], obs[2]);
-  coeff = 1.0 - sqrt(fdiv(mean_abs, (double)mp.sq_max_dist_f));           // LidarSlam.cpp:568
-  nd[0] = n0; nd[1] = n1; nd[2] = n2; nd[3] = d;
-  return SO_MATCH_SUCCESS;
-}
-
-// ------------------------------------------------------------------------------------------------
 // knn_plane_kernel -- wave-cooperative exact 5-NN (the plane fit follows in eval_kernel<true>).
 //
 // A wavefront owns one CHUNK of the spatially sorted scan: <= 64 queries that shared one half-cell octant of the map
@@ -802,6 +544,53 @@ __device__ __forceinline__ unsigned long long wave_min_u64(unsigned long long v)
   }
   return v;
 }
+// The idioms of knn_plane_kernel / knn_query_wave_kernel that could be named without changing the code they compile to.  (The
+// x-run binary search, the four-candidate push into the selection network and the cooperative 27-cell scan stay written out at
+// their sites: as helpers -- value-in / value-out, forced inline -- each of them gave these two kernels different code.)
+// Inclusive prefix sum over every ROW of 16 lanes (DPP row_shr 1, 2, 4, 8; what would be shifted in from outside the row is 0).
+__device__ __forceinline__ uint32_t row_inclusive_scan_u32(uint32_t v) {
+  v += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x111, 0xF, 0xF, true);
+  v += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x112, 0xF, 0xF, true);
+  v += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x114, 0xF, 0xF, true);
+  v += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x118, 0xF, 0xF, true);
+  return v;
+}
+// maximum of a row-uniform value over the four rows (wave-uniform result)
+__device__ __forceinline__ uint32_t max_over_rows(uint32_t v) {
+  return max(max((uint32_t)__builtin_amdgcn_readlane((int)v, 0), (uint32_t)__builtin_amdgcn_readlane((int)v, 16)),
+             max((uint32_t)__builtin_amdgcn_readlane((int)v, 32), (uint32_t)__builtin_amdgcn_readlane((int)v, 48)));
+}
+// LDS written by some lanes of the wavefront is read by others (and the other way round): orders the accesses in the compiler
+// and in the hardware; no instruction of its own beyond the wait it implies
+__device__ __forceinline__ void wave_lds_fence() {
+  __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
+  __builtin_amdgcn_wave_barrier();
+}
+// Distance from a query (cube-local u) to the nearest face of the scanned cell block [b0, b1] that has cells of the cube behind
+// it (a face on the cube's boundary has nothing behind it), less a margin: cell membership of a map point is decided in fp64 on
+// its own coordinates.  Every point of the cube outside the block is at least that far away.
+__device__ __forceinline__ float block_cover_distance(int bx0, int bx1, int by0, int by1, int bz0, int bz1, int nc, float cell,
+                                                      float ux, float uy, float uz) {
+  float cv = 1e15f;
+  if (bx0 > 0) cv = fminf(cv, ux - (float)bx0 * cell);
+  if (bx1 < nc - 1) cv = fminf(cv, (float)(bx1 + 1) * cell - ux);
+  if (by0 > 0) cv = fminf(cv, uy - (float)by0 * cell);
+  if (by1 < nc - 1) cv = fminf(cv, (float)(by1 + 1) * cell - uy);
+  if (bz0 > 0) cv = fminf(cv, uz - (float)bz0 * cell);
+  if (bz1 < nc - 1) cv = fminf(cv, (float)(bz1 + 1) * cell - uz);
+  return fmaxf(cv - 1e-4f, 0.f);
+}
+// The network's eight survivors -> canonical map indices through the staged tile (tile_canon[position]; n_valid positions hold
+// candidates, tile_cap is the tile's size); 0xFFFFFFFF for an empty key.
+__device__ __forceinline__ void survivors_to_canon(const Net8& net, const uint32_t* tile_canon, uint32_t n_valid, uint32_t tile_cap,
+                                                   uint32_t (&canon)[8]) {
+  const int32_t ks[8] = {net.a0, net.a1, net.a2, net.a3, net.a4, net.a5, net.a6, net.a7};
+#pragma unroll
+  for (int t = 0; t < 8; ++t) {
+    const uint32_t jl = (uint32_t)ks[t] & kKeyIdxMask;
+    canon[t] = (ks[t] == kKeyEmpty || jl >= n_valid) ? 0xFFFFFFFFu : tile_canon[jl < tile_cap ? jl : 0u];
+  }
+}
 #ifndef SO_KNN_PACK
 #define SO_KNN_PACK 1  // four light chunks (<= 16 queries each) per wavefront, one per row of 16 lanes (see knn_plane_kernel)
 #endif
@@ -810,10 +599,10 @@ constexpr uint32_t kPartTile = kTileCand / 4;  // candidates a packed chunk may 
 // PROF : the profiling / test-hook instantiation (per-wavefront stamps, SOICP_ABLATE switches, kernel statistics); the
 //        production instantiation carries none of it (the sweep is instruction-issue bound).
 // BATCH: so_icp_register_batch -- blockIdx.y picks the hypothesis, see BatchView.
-// BEGIN: first launch of a registration whose scan was binned ahead (MatchParams::begin): an instantiation of its own, so that the
-//        others do not carry the prologue's arguments in their scalar registers (the kernel sits at its register budget).
 // BEGIN: 0 = a sweep behind the registration's prologue; 1 = first launch of a registration whose scan was binned ahead (MatchParams::begin);
-//        2 = that, for a CHAINED registration (RegBeginArgs::chain_expect): the guess comes from DevState::T_chain
+//        2 = that, for a CHAINED registration (RegBeginArgs::chain_expect): the guess comes from DevState::T_chain.  Instantiations of
+//        their own, so that the others do not carry the prologue's arguments in their scalar registers (the kernel sits at its
+//        register budget).
 template <bool PROF, bool BATCH, int BEGIN = 0>
 __global__ __launch_bounds__(256, 4) void knn_plane_kernel(const float4* __restrict__ binned /* {x, y, z, query index} per binned position */,
                                                         const uint32_t* __restrict__ chunk_start,
@@ -872,6 +661,8 @@ __global__ __launch_bounds__(256, 4) void knn_plane_kernel(const float4* __restr
   // [packed items: light chunks 4 m .. 4 m + 3][normal chunks].
   // (MatchParams::pack_light = 0 -- the host's choice for a sweep that starts with the full pass, or after sweeps in which the packed
   //  near pass left too many queries to the exact scan -- gives the round-3 list: [half of the light chunks][normal][other half])
+  // (the predicate of `first_pass` below, written out a second time -- keep the two in step: formed once, in either place, it
+  //  changed the code of every instantiation of this kernel)
   const float cell_w = (float)(1.0 / map.inv_cell);
   const bool first_pass_is_near = 0.5f * cell_w < 0.8f * (sqrtf(mp.sq_max_dist_f) * 1.0005f + 1e-4f) && !mp.skip_near_pass && !(PROF && (mp.ablate & 256));
   const bool pack = SO_KNN_PACK && mp.pack_light && first_pass_is_near;
@@ -907,7 +698,7 @@ __global__ __launch_bounds__(256, 4) void knn_plane_kernel(const float4* __restr
   // sqrt(3*planeRes) (LidarSlam.cpp:526,741), where "not found inside the gate ball" is a certain TOO_FAR.
   const float r_gate = sqrtf(mp.sq_max_dist_f) * 1.0005f + 1e-4f;
   const float r_near = 0.5f * cell;
-  const int first_pass = (r_near < 0.8f * r_gate && !(abl & 256) && !mp.skip_near_pass) ? 0 : 1;
+  const int first_pass = (r_near < 0.8f * r_gate && !(abl & 256) && !mp.skip_near_pass) ? 0 : 1;  // (== first_pass_is_near above: keep in step)
   // one wavefront per chunk of the work list (a second / further chunk when the list is longer than the grid)
   // (the body is instantiated twice -- packed light chunks / one chunk per wavefront -- so that neither path carries the other's
   //  live values: the kernel sits at its 128-register budget)
@@ -1026,7 +817,6 @@ __global__ __launch_bounds__(256, 4) void knn_plane_kernel(const float4* __restr
   //      addresses per read, like the split scan).  A row whose block has more than 16 x-runs or keeps more than 64 candidates,
   //      and a lane in another cube than its row's first, is left to the group passes below; so is every lane the near pass
   //      cannot certify (full pass) -- the results are the same exact lists either way.
-  constexpr bool near_done = false;  // (group passes only: every lane takes part in its near pass)
   if constexpr (packed) if (first_pass == 0 && !(abl & 2))
   for (int ppass = 0; ppass < 2; ++ppass) {  // near pass, then -- for the rows that still have uncertified lanes -- the full pass (gate radius)
     const bool pend = !resolved && !need_exact;
@@ -1047,19 +837,9 @@ __global__ __launch_bounds__(256, 4) void knn_plane_kernel(const float4* __restr
     bool part_ok = gslot != 0x7FFFFFFF && nrows >= 1 && nrows <= 16;  // (uniform over the row)
     // squared distance from the query to the faces of the block (a face on the cube's boundary has nothing of the cube behind
     // it), capped by the filter radius: formed here, while the bounds are at hand (six registers less across the scan)
-    float cov2p;
-    {
-      float cv = 1e15f;
-      if (bx0 > 0) cv = fminf(cv, ux - (float)bx0 * cell);
-      if (bx1 < nc - 1) cv = fminf(cv, (float)(bx1 + 1) * cell - ux);
-      if (by0 > 0) cv = fminf(cv, uy - (float)by0 * cell);
-      if (by1 < nc - 1) cv = fminf(cv, (float)(by1 + 1) * cell - uy);
-      if (bz0 > 0) cv = fminf(cv, uz - (float)bz0 * cell);
-      if (bz1 < nc - 1) cv = fminf(cv, (float)(bz1 + 1) * cell - uz);
-      cv = fmaxf(cv - 1e-4f, 0.f);  // cell membership of a map point is decided in fp64 on its own coordinates: keep a margin
-      if (ppass == 1) cv = 1e15f;   // (the full pass's block contains the lane's whole gate ball by construction)
-      cov2p = fminf(cv * cv, r_cover * r_cover);  // (candidates beyond r_cover of every lane of the group are not staged)
-    }
+    float cv = block_cover_distance(bx0, bx1, by0, by1, bz0, bz1, nc, cell, ux, uy, uz);
+    if (ppass == 1) cv = 1e15f;   // (the full pass's block contains the lane's whole gate ball by construction)
+    const float cov2p = fminf(cv * cv, r_cover * r_cover);  // (candidates beyond r_cover of every lane of the group are not staged)
     // row table of the part's block: lane r of the row fetches the bounds of x-run r, inclusive scan over the row
     uint32_t vb = 0, vl = 0;
     if (part_ok && (int)lane16 < nrows) {
@@ -1068,17 +848,12 @@ __global__ __launch_bounds__(256, 4) void knn_plane_kernel(const float4* __restr
       const uint32_t* row = mcell_start + (size_t)gslot * map.ncell1 + ((size_t)z * nc + y) * nc;
       vb = row[bx0]; vl = row[bx1 + 1] - vb;
     }
-    uint32_t inc = vl;
-    inc += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)inc, 0x111, 0xF, 0xF, true);
-    inc += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)inc, 0x112, 0xF, 0xF, true);
-    inc += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)inc, 0x114, 0xF, 0xF, true);
-    inc += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)inc, 0x118, 0xF, 0xF, true);
+    const uint32_t inc = row_inclusive_scan_u32(vl);
     const uint32_t total = (uint32_t)row_max_i32((int)inc);  // (the inclusive scan is monotone: its maximum is the row's total)
     part_ok = part_ok && total <= 1024u;
     uint32_t* prowoff = rowoff + part * 17u;   // [17] exclusive offsets (total from entry nrows on)
     uint32_t* prowbeg = rowbeg + part * 16u;   // [16] first canonical index of the x-run
-    __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
-    __builtin_amdgcn_wave_barrier();
+    wave_lds_fence();
     prowoff[lane16] = ((int)lane16 < nrows) ? inc - vl : total; prowbeg[lane16] = vb;
     if (lane16 == 0) prowoff[16] = total;
     // block-local frame of the part: origin at the centre of the block's middle cell, in the group's cube (the lanes of a group
@@ -1097,10 +872,8 @@ __global__ __launch_bounds__(256, 4) void knn_plane_kernel(const float4* __restr
     const float dk = r_cover + 2e-4f, dk2 = dk * dk;
     const uint32_t tbase = part * kPartTile;
     const uint32_t tot_eff = part_ok ? total : 0u;
-    const uint32_t tmax = max(max((uint32_t)__builtin_amdgcn_readlane((int)tot_eff, 0), (uint32_t)__builtin_amdgcn_readlane((int)tot_eff, 16)),
-                              max((uint32_t)__builtin_amdgcn_readlane((int)tot_eff, 32), (uint32_t)__builtin_amdgcn_readlane((int)tot_eff, 48)));
-    __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
-    __builtin_amdgcn_wave_barrier();
+    const uint32_t tmax = max_over_rows(tot_eff);
+    wave_lds_fence();
     if (PROF) n_scanned += tmax;
     uint32_t w = 0;  // candidates the part has kept so far (uniform over the row)
     // Staging.  A group of lanes -- width 16 = every row for itself (near pass: all four rows are busy), or width 64 = the
@@ -1174,10 +947,8 @@ __global__ __launch_bounds__(256, 4) void knn_plane_kernel(const float4* __restr
     for (uint32_t sl = wk + lane16; sl < kPartTile; sl += 16u) {  // the rest of the part's quarter: entries that lose against every real candidate
       tx[tbase + sl] = 0.f; ty[tbase + sl] = 0.f; tz[tbase + sl] = 0.f; tc[tbase + sl] = 3.0e38f; ti[tbase + sl] = 0xFFFFFFFFu;
     }
-    const uint32_t wmax = (max(max((uint32_t)__builtin_amdgcn_readlane((int)wk, 0), (uint32_t)__builtin_amdgcn_readlane((int)wk, 16)),
-                               max((uint32_t)__builtin_amdgcn_readlane((int)wk, 32), (uint32_t)__builtin_amdgcn_readlane((int)wk, 48))) + 3u) & ~3u;
-    __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
-    __builtin_amdgcn_wave_barrier();
+    const uint32_t wmax = (max_over_rows(wk) + 3u) & ~3u;
+    wave_lds_fence();
     const uint32_t keep = ~kKeyIdxMask;
     const float2v pqx = {m2qx, m2qx}, pqy = {m2qy, m2qy}, pqz = {m2qz, m2qz}, pqq = {qq, qq};
     Net8 net;
@@ -1194,13 +965,8 @@ __global__ __launch_bounds__(256, 4) void knn_plane_kernel(const float4* __restr
       net.push(make_key(d23.x, jl + 2u, keep));
       net.push(make_key(d23.y, jl + 3u, keep));
     }
-    const int32_t ks[8] = {net.a0, net.a1, net.a2, net.a3, net.a4, net.a5, net.a6, net.a7};
     uint32_t gs[8];
-#pragma unroll
-    for (int t = 0; t < 8; ++t) {
-      const uint32_t jl = (uint32_t)ks[t] & kKeyIdxMask;
-      gs[t] = (ks[t] == kKeyEmpty || jl >= wk) ? 0xFFFFFFFFu : ti[tbase + (jl < kPartTile ? jl : 0u)];
-    }
+    survivors_to_canon(net, ti + tbase, wk, kPartTile, gs);
     if (mine && part_ok) {
       if (!(abl & 4)) {
         const int v = certify(ppass, gs, net.a5, net.a7, cov2p, top);
@@ -1228,18 +994,12 @@ __global__ __launch_bounds__(256, 4) void knn_plane_kernel(const float4* __restr
           vb = row[x0]; vl = row[x1 + 1] - vb;
         }
       }
-      uint32_t inc = vl;  // inclusive scan over lanes 0..15 (the nine runs sit in the first row of 16 lanes)
-      inc += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)inc, 0x111, 0xF, 0xF, true);
-      inc += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)inc, 0x112, 0xF, 0xF, true);
-      inc += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)inc, 0x114, 0xF, 0xF, true);
-      inc += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)inc, 0x118, 0xF, 0xF, true);
+      const uint32_t inc = row_inclusive_scan_u32(vl);  // (the nine runs sit in the first row of 16 lanes)
       const uint32_t total = (uint32_t)__builtin_amdgcn_readlane((int)inc, 15);
-      __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
-      __builtin_amdgcn_wave_barrier();
+      wave_lds_fence();
       if (lane < 16) { rowoff[lane] = lane < 9 ? inc - vl : total; rowbeg[lane] = vb; }
       if (lane == 0) rowoff[16] = total;
-      __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
-      __builtin_amdgcn_wave_barrier();
+      wave_lds_fence();
       Top5 loc;
       loc.init();
       for (uint32_t t0 = 0; t0 < total; t0 += 256u) {
@@ -1290,7 +1050,7 @@ __global__ __launch_bounds__(256, 4) void knn_plane_kernel(const float4* __restr
   }
   if constexpr (!packed)
   for (int pass = first_pass; pass < 2; ++pass) {
-  bool pending = !resolved && !need_exact && !(pass == 0 && near_done);
+  bool pending = !resolved && !need_exact;
   unsigned long long todo = __ballot(pending);
   if (abl & 2) todo = 0;
   if (!todo) continue;  // (a packed wavefront may have nothing left for the near pass and still lanes for the full pass)
@@ -1347,11 +1107,7 @@ __global__ __launch_bounds__(256, 4) void knn_plane_kernel(const float4* __restr
         }
         // inclusive scan over lanes 0..31 on the DPP network (row_shr 1,2,4,8 inside the rows of 16, row_bcast:15 carries
         // row 0's total into row 1): no LDS round trips
-        uint32_t inc = vl;
-        inc += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)inc, 0x111, 0xF, 0xF, true);
-        inc += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)inc, 0x112, 0xF, 0xF, true);
-        inc += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)inc, 0x114, 0xF, 0xF, true);
-        inc += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)inc, 0x118, 0xF, 0xF, true);
+        uint32_t inc = row_inclusive_scan_u32(vl);
         inc += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)inc, 0x142, 0xA, 0xF, false);
         total = __builtin_amdgcn_readlane(inc, 31);
         if (lane < 32) { rowoff[lane] = inc - vl; rowbeg[lane] = vb; }
@@ -1403,8 +1159,7 @@ __global__ __launch_bounds__(256, 4) void knn_plane_kernel(const float4* __restr
     if (filt) {
       // the WHOLE enumeration is filtered into the one tile; a group whose kept candidates do not fit it (dense cells in the
       // full pass) falls back to the unfiltered stream of pieces below
-      __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
-      __builtin_amdgcn_wave_barrier();
+      wave_lds_fence();
       uint32_t w = 0;  // kept candidates so far (wave-uniform)
       for (uint32_t t0 = 0; t0 < total; t0 += 64) {
         const uint32_t t = t0 + (uint32_t)lane;
@@ -1442,8 +1197,7 @@ __global__ __launch_bounds__(256, 4) void knn_plane_kernel(const float4* __restr
     for (uint32_t base = 0; base < n_enum; base += kTileCand) {
       const uint32_t cnt = (n_enum - base < kTileCand) ? n_enum - base : kTileCand;
       // stage with coalesced 16-byte loads (position -> row by a 5-step binary search over the row offsets)
-      __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
-      __builtin_amdgcn_wave_barrier();
+      wave_lds_fence();
       if (filt) {
         // (the tile already holds the kept candidates)
       } else
@@ -1463,8 +1217,7 @@ __global__ __launch_bounds__(256, 4) void knn_plane_kernel(const float4* __restr
         }
         tx[t] = lx; ty[t] = ly; tz[t] = lz; tc[t] = lc; ti[t] = canon;
       }
-      __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
-      __builtin_amdgcn_wave_barrier();
+      wave_lds_fence();
       if (!(abl & 8) && split) {
         // two quads per trip, one per half of the wavefront (two LDS addresses per read)
         for (uint32_t jl = 0; jl < cnt; jl += sstep) {
@@ -1512,15 +1265,11 @@ __global__ __launch_bounds__(256, 4) void knn_plane_kernel(const float4* __restr
     if (stamp) { ts[3] = wall_clock64(); acc[2] += ts[3] - ts[2]; }
     // survivors: position in the enumeration -> canonical index (all lanes compute, owners commit).  A single-piece
     // group still has its candidates' indices in LDS; a streamed one goes back through the row table.
-    const int32_t ks[8] = {net.a0, net.a1, net.a2, net.a3, net.a4, net.a5, net.a6, net.a7};
     uint32_t gi[8];
     if (filt || total <= kTileCand) {
-#pragma unroll
-      for (int t = 0; t < 8; ++t) {
-        const uint32_t jl = (uint32_t)ks[t] & kKeyIdxMask;
-        gi[t] = (ks[t] == kKeyEmpty || jl >= total_eff) ? 0xFFFFFFFFu : ti[jl < kTileCand ? jl : 0];
-      }
+      survivors_to_canon(net, ti, total_eff, kTileCand, gi);
     } else {
+      const int32_t ks[8] = {net.a0, net.a1, net.a2, net.a3, net.a4, net.a5, net.a6, net.a7};
 #pragma unroll
       for (int t = 0; t < 8; ++t) {
         const uint32_t jl = (uint32_t)ks[t] & kKeyIdxMask;
@@ -1538,14 +1287,7 @@ __global__ __launch_bounds__(256, 4) void knn_plane_kernel(const float4* __restr
         cov2 = 1e30f;  // the block contains the lane's whole gate ball by construction
       } else {
         // distance to the faces of the scanned block; a face on the cube's boundary has nothing of the cube behind it
-        float cv = 1e15f;
-        if (bx0 > 0) cv = fminf(cv, ux - (float)bx0 * cell);
-        if (bx1 < nc - 1) cv = fminf(cv, (float)(bx1 + 1) * cell - ux);
-        if (by0 > 0) cv = fminf(cv, uy - (float)by0 * cell);
-        if (by1 < nc - 1) cv = fminf(cv, (float)(by1 + 1) * cell - uy);
-        if (bz0 > 0) cv = fminf(cv, uz - (float)bz0 * cell);
-        if (bz1 < nc - 1) cv = fminf(cv, (float)(bz1 + 1) * cell - uz);
-        cv = fmaxf(cv - 1e-4f, 0.f);  // cell membership of a map point is decided in fp64 on its own coordinates: keep a margin
+        const float cv = block_cover_distance(bx0, bx1, by0, by1, bz0, bz1, nc, cell, ux, uy, uz);
         cov2 = cv * cv;
       }
       if (filt) cov2 = fminf(cov2, r_cover * r_cover);  // (candidates beyond r_cover of every lane of the group were not staged)
@@ -1588,7 +1330,7 @@ __global__ __launch_bounds__(256, 4) void knn_plane_kernel(const float4* __restr
       if ((abl & 1) || too_far_certain || top.b4 == ~0ull || (double)d2_4 > (double)mp.sq_max_dist_f) {
         status = SO_MATCH_TOO_FAR;   // LidarSlam.cpp:741-744 (d2[4] stays FLT_MAX with < 5 points)
       } else {
-        status = SO_MATCH_PENDING;   // five neighbours inside the gate: the plane fit runs in plane_eval_kernel
+        status = SO_MATCH_PENDING;   // five neighbours inside the gate: the plane fit runs in the fit pass of the solve
         uint32_t* o = nbr5 + (size_t)5 * oi;  // (streaming stores: read by the next launch only -- nothing to write back at kernel end)
         __builtin_nontemporal_store((uint32_t)top.b0, o); __builtin_nontemporal_store((uint32_t)top.b1, o + 1);
         __builtin_nontemporal_store((uint32_t)top.b2, o + 2); __builtin_nontemporal_store((uint32_t)top.b3, o + 3);
@@ -1722,17 +1464,12 @@ __global__ __launch_bounds__(256) void knn_query_wave_kernel(const float* __rest
           vb = row[x0]; vl = row[x1 + 1] - vb;
         }
       }
-      uint32_t inc = vl;  // inclusive scan over lanes 0..15 (the nine runs sit in the first row of 16 lanes)
-      inc += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)inc, 0x111, 0xF, 0xF, true);
-      inc += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)inc, 0x112, 0xF, 0xF, true);
-      inc += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)inc, 0x114, 0xF, 0xF, true);
-      inc += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)inc, 0x118, 0xF, 0xF, true);
+      const uint32_t inc = row_inclusive_scan_u32(vl);  // (the nine runs sit in the first row of 16 lanes)
       const uint32_t total = (uint32_t)__builtin_amdgcn_readlane((int)inc, 15);
       __builtin_amdgcn_wave_barrier();  // (a second point of the share: the table of the first has been read by every lane)
       if (lane < 16) { rowoff[lane] = lane < 9 ? inc - vl : total; rowbeg[lane] = vb; }
       if (lane == 0) rowoff[16] = total;
-      __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
-      __builtin_amdgcn_wave_barrier();
+      wave_lds_fence();
       Top5 loc;
       loc.init();
       for (uint32_t t0 = 0; t0 < total; t0 += 256u) {  // four loads of a lane in flight: a block of <= 256 points is one round trip
@@ -2414,7 +2151,7 @@ __device__ __forceinline__ int eval_pass(int slot, int fuse_lm, const Pose& pose
         const double pw[3] = {wx, wy, wz};
         // (test switches of the PROF instantiation: 4096 = the reference's column-pivoted Householder factorisation instead of the
         //  closed form of plane_fit.h, 512 = that plus the cyclic Jacobi eigen-solver)
-        if (PROF && (mp.ablate & (512 | 4096))) status = plane_from_neighbours(nb, pw, pose, mp, fnd, fc, obs, (mp.ablate & 512) != 0);
+        if (PROF && (mp.ablate & (512 | 4096))) status = plane_fit5_reference(nb, pw, axes, mp.sq_max_dist_f, mp.max_point_dist, fnd, fc, obs, (mp.ablate & 512) != 0);
         else status = plane_fit5(nb, pw, axes, mp.sq_max_dist_f, mp.max_point_dist, fnd, fc, obs);
       }
       if (status != SO_MATCH_SUCCESS) { fc = 0; fnd[0] = fnd[1] = fnd[2] = fnd[3] = 0; }

@@ -2,7 +2,8 @@
 least-squares plane, LidarSlam.cpp:798-816) compiled for the HOST and checked on the CPU:
 
   * against the oracle (fp64 cyclic Jacobi + column-pivoted Householder, oracle/so_oracle.c: orc_plane_match) on every
-    correspondence of real synthetic registrations: MatchingResult and observability labels equal, plane / coefficient to 1e-10;
+    correspondence of real synthetic registrations: MatchingResult and observability labels equal, plane / coefficient to 1e-10
+    -- the closed form, and the reference-algorithm variant plane_fit5_reference that the test switches of the PROF kernels run;
   * against the 80-bit gate-edge fixture (tests/golden/gate_edge.npz);
   * against an 80-bit evaluation of the same least-squares problem on random clusters far from the origin (accuracy claim
     in the header of plane_fit.h, with column-pivoted QR in fp64 beside it);
@@ -32,15 +33,21 @@ def pf():
     L = C.CDLL(LIB)
     f32p, f64p, i32p = C.POINTER(C.c_float), C.POINTER(C.c_double), C.POINTER(C.c_int)
     L.pf_fit.argtypes = [f32p, f64p, f64p, C.c_float, C.c_double, C.c_int, C.c_int, f64p, f64p, i32p, i32p]
+    L.pf_fit_reference.argtypes = [f32p, f64p, f64p, C.c_float, C.c_double, C.c_int, f64p, f64p, i32p, i32p, C.c_int]
 
-    def fit(nb, pw, pose, plane_res, as_written=False):
+    def fit(nb, pw, pose, plane_res, as_written=False, reference=None):
+        """reference: None = plane_fit5 (the closed form); "qr" / "qr+jacobi" = plane_fit5_reference (the reference's own algorithms)"""
         nb = np.ascontiguousarray(nb, np.float32).reshape(-1, 15); pw = np.ascontiguousarray(pw, np.float64).reshape(-1, 3)
         pose = np.ascontiguousarray(pose, np.float64)
         n = len(nb)
         nd = np.zeros((n, 4)); co = np.zeros(n); st = np.zeros(n, np.int32); ob = np.zeros((n, 3), np.int32)
         pr = np.float32(plane_res)
-        L.pf_fit(nb.ctypes.data_as(f32p), pw.ctypes.data_as(f64p), pose.ctypes.data_as(f64p), np.float32(3) * pr, float(pr) / 2.0, n,
-                 1 if as_written else 0, nd.ctypes.data_as(f64p), co.ctypes.data_as(f64p), st.ctypes.data_as(i32p), ob.ctypes.data_as(i32p))
+        head = (nb.ctypes.data_as(f32p), pw.ctypes.data_as(f64p), pose.ctypes.data_as(f64p), np.float32(3) * pr, float(pr) / 2.0, n)
+        out = (nd.ctypes.data_as(f64p), co.ctypes.data_as(f64p), st.ctypes.data_as(i32p), ob.ctypes.data_as(i32p))
+        if reference is None:
+            L.pf_fit(*head, 1 if as_written else 0, *out)
+        else:
+            L.pf_fit_reference(*head, *out, {"qr": 0, "qr+jacobi": 1}[reference])
         return st, nd, co, ob
     return fit
 
@@ -50,8 +57,7 @@ def _world(pose, p):
     return p @ synth.quat_to_R(pose[3:]).T + pose[:3]
 
 
-@pytest.mark.parametrize("scene,scans", [("tiny", (0, 1, 2)), ("small", (0, 5))])
-def test_host_fit_equals_the_oracle_on_real_correspondences(oracle, pf, scene, scans):
+def _fit_equals_the_oracle_on_real_correspondences(oracle, pf, scene, scans):
     from superodom_amd import synth
     sc = synth.Scene(scene)
     om = oracle.OracleMap(plane_res=sc.plane_res)
@@ -75,6 +81,22 @@ def test_host_fit_equals_the_oracle_on_real_correspondences(oracle, pf, scene, s
         assert np.abs(co[ok] - c["coeff"][ok]).max() < 1e-10
         n_fit += len(c); n_ok += int(ok.sum())
     assert n_fit > 1000 and n_ok > 500
+
+
+SCENES = [("tiny", (0, 1, 2)), ("small", (0, 5))]
+
+
+@pytest.mark.parametrize("scene,scans", SCENES)
+def test_host_fit_equals_the_oracle_on_real_correspondences(oracle, pf, scene, scans):
+    _fit_equals_the_oracle_on_real_correspondences(oracle, pf, scene, scans)
+
+
+@pytest.mark.parametrize("reference", ["qr", "qr+jacobi"])
+@pytest.mark.parametrize("scene,scans", SCENES)
+def test_reference_variant_equals_the_oracle_on_real_correspondences(oracle, pf, scene, scans, reference):
+    """plane_fit5_reference (what the PROF kernels run behind SOICP_ABLATE = 4096 / 512) restates the oracle's algorithms: held to
+    what the closed form is held to above -- equal status and labels, plane and coefficient within 1e-10, on every correspondence."""
+    _fit_equals_the_oracle_on_real_correspondences(oracle, lambda *a: pf(*a, reference=reference), scene, scans)
 
 
 def test_host_fit_at_the_gate_edges(pf):
