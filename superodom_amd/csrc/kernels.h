@@ -35,7 +35,9 @@ struct MatchParams {
   float sq_max_dist_f;    // 3 * planeRes evaluated in float (LidarSlam.cpp:526)
   double max_point_dist;  // planeRes / 2.0 (LidarSlam.cpp:820)
   int32_t ablate;         // profiling / test switches (env SOICP_ABLATE), read only by the PROF instantiations of the kernels,
-                          // which are launched when it is non-zero: bit0 skip plane fit, bit1 skip scan, bit2 skip re-rank, ...
+                          // which are launched when it is non-zero: bit0 skip plane fit, bit1 skip scan, bit2 skip re-rank, ...;
+                          // bit16 (65536) switches nothing off: the instrumented sweep with its statistics alone (group passes, exact-scan
+                          // lanes, packed rows and why they were handed back; so_icp_timing with time_kernels 2) -- tests/test_gpu_knn_edges.py
   unsigned long long* kdbg;  // profiling only (SOICP_ABLATE bit 7): 2 sweeps x 4*kKnnBlocks wavefront records of 16 stamps, else nullptr
   uint32_t* packed_leftover;  // &DevState::packed_leftover of the registration (hypothesis 0 of a batch), passed beside `st` so that the
                               // kernel's loads through its read-only, restrict-qualified `st` stay scalar loads
