@@ -27,6 +27,62 @@ namespace soicp {
 
 static inline int cidx(int i, int j, int k) { return i + kMapW * j + kMapW * kMapH * k; }
 
+// log2 of the leaf table's size for n_new new points: load factor <= 1/2, at least one workgroup's worth of slots for the offsets kernel
+static uint32_t leaf_table_log2(size_t n_new) {
+  uint32_t lg = 12;
+  while (((size_t)1 << lg) < 2 * (n_new + 1)) ++lg;
+  return lg;
+}
+
+// cube t of a round: its slot, world id, min corner and common leaf offset
+void DeviceMap::set_touched(MapTouched& tt, int t, int cube, int slot, float inv_leaf) const {
+  tt.cube[t] = cube;
+  tt.slot[t] = (uint32_t)slot;
+  const int ci = cube % kMapW, cj = (cube / kMapW) % kMapH, ck = cube / (kMapW * kMapH);
+  const int w[3] = {ci - origin_[0], cj - origin_[1], ck - origin_[2]};
+  for (int ax = 0; ax < 3; ++ax) {
+    tt.cube_min[t][ax] = w[ax] * kCube - kHalfCube;
+    tt.leaf_lo[t][ax] = (int)std::floor((float)tt.cube_min[t][ax] * inv_leaf) - 2;
+    tt.wcube[t][ax] = w[ax];
+  }
+}
+// the entries behind the round's tt.n cubes (n_old: the round's old points)
+static void finish_touched(MapTouched& tt, uint32_t n_old) {
+  for (int t = tt.n; t <= kMaxTouched; ++t) tt.old_prefix[t] = n_old;
+  for (int t = tt.n; t < kMaxTouched; ++t) { tt.slot[t] = 0; tt.cube[t] = INT32_MAX; }
+}
+
+// the part of a launch's arguments that is the same for every round: resolution of the index, pool, work buffers, counters
+// (after ensure_work / ensure_grid: they may move the buffers)
+MapInsertArgs DeviceMap::work_args() const {
+  MapInsertArgs a{};
+  a.d_tt = d_tt_;
+  a.nc = nc_; a.ncell1 = ncell1_; a.inv_cell = 1.0 / cell_;
+  a.pool = d_pool_; a.cap = kCapPerSlot; a.cell_start = d_cell_start_;
+  a.wpts = d_wpts_; a.cent = d_cent_; a.spts = d_spts_; a.heads = d_heads_;
+  a.keys0 = d_k0_; a.keys1 = d_k1_; a.vals0 = d_v0_; a.vals1 = d_v1_; a.flags = d_flags_; a.pos = d_pos_;
+  a.d_n_cent = d_small_; a.d_counts = d_small_ + kCntCounts;
+  a.grid = d_grid_; a.grid_scan = d_grid_scan_;
+  a.temp = d_temp_; a.temp_bytes = temp_bytes_;
+  return a;
+}
+void DeviceMap::use_leaf_table(MapInsertArgs& a, size_t n_new) const {
+  a.ht_key = d_ht_key_; a.ht_cnt = d_ht_cnt_; a.ht_off = d_ht_off_;
+  a.ht_log2 = leaf_table_log2(n_new);  // this round's share of the (all-empty) table: the kernels hash into / scan the first 2^ht_log2 slots only
+}
+// a round leaves the cell counters it used at zero again (cell_table_kernel): true when no fill is needed for `need` of them
+bool DeviceMap::grid_clean_upto(size_t need) {
+  const bool clean = need <= grid_zero_upto_;
+  grid_zero_upto_ = std::max(grid_zero_upto_, need);
+  return clean;
+}
+// a round's own counters (and the owned counts of a sharded map) back to zero
+int DeviceMap::clear_round_counters(std::string& err) {
+  DM_TRY(hipMemsetAsync(d_small_, 0, kCntRoundWords * sizeof(uint32_t), stream_));
+  if (world_ > 1) DM_TRY(hipMemsetAsync(d_small_ + kCntOwned, 0, kMaxTouched * sizeof(uint32_t), stream_));
+  return 0;
+}
+
 DeviceMap::~DeviceMap() {
   (void)hipStreamSynchronize(stream_);  // (a deferred insert may still be writing its report)
   for (void* p : {(void*)d_tt_, (void*)d_slot_count_, (void*)d_cube_cnt_, (void*)d_scan_state_})
@@ -152,8 +208,7 @@ int DeviceMap::ensure_pool(int slots_needed, std::string& err) {
 // hash table of the insert's first stage: one slot per distinct leaf of the NEW points, load factor <= 1/2, at least one
 // workgroup's worth of slots for the offsets kernel; empty (keys 0xFFFFFFFF, counts 0) between inserts
 int DeviceMap::ensure_leaf_table(size_t n_new, std::string& err) {
-  uint32_t lg = 12;
-  while (((size_t)1 << lg) < 2 * (n_new + 1)) ++lg;
+  const uint32_t lg = leaf_table_log2(n_new);
   if (lg > 30) { err = "DeviceMap: too many new points for the leaf table"; return -1; }
   if (lg <= ht_log2_ && d_ht_key_) return 0;
   for (void* p : {(void*)d_ht_key_, (void*)d_ht_cnt_, (void*)d_ht_off_}) if (p) (void)hipFree(p);
@@ -166,6 +221,24 @@ int DeviceMap::ensure_leaf_table(size_t n_new, std::string& err) {
   DM_TRY(hipMemsetAsync(d_ht_cnt_, 0, slots * sizeof(uint32_t), stream_));
   ht_log2_ = lg;
   return 0;
+}
+
+// the staging buffer holds `floats` floats / the per-point cube indices hold n entries (grown with some slack, contents dropped)
+hipError_t DeviceMap::ensure_stage(size_t floats) {
+  if (floats <= stage_cap_) return hipSuccess;
+  if (d_stage_) (void)hipFree(d_stage_);
+  d_stage_ = nullptr; stage_cap_ = 0;
+  const hipError_t e = hipMalloc(reinterpret_cast<void**>(&d_stage_), (floats + 1024) * sizeof(float));
+  if (e == hipSuccess) stage_cap_ = floats + 1024;
+  return e;
+}
+hipError_t DeviceMap::ensure_cube_of(size_t n) {
+  if (n <= new_cap_) return hipSuccess;
+  if (d_cube_of_) (void)hipFree(d_cube_of_);
+  d_cube_of_ = nullptr; new_cap_ = 0;
+  const hipError_t e = hipMalloc(reinterpret_cast<void**>(&d_cube_of_), (n + 1024) * sizeof(int32_t));
+  if (e == hipSuccess) new_cap_ = n + 1024;
+  return e;
 }
 
 int DeviceMap::ensure_work(size_t total, std::string& err) {
@@ -249,43 +322,25 @@ int DeviceMap::set_resolution(float line_res, float plane_res, std::string& err)
   const uint32_t lbits = leaf_bits(finest_res_);
   const size_t per_round = max_touched(lbits);
   for (size_t r0 = 0; r0 < occupied.size(); r0 += per_round) {
-    MapInsertArgs a{};
-    MapTouched& tt = a.tt;
+    MapTouched tt{};  // (no kernel of the retable reads cube / wcube)
     tt.lbits = lbits;
     tt.n = (int)std::min<size_t>(per_round, occupied.size() - r0);
     uint32_t n_old = 0;
     for (int t = 0; t < tt.n; ++t) {
-      const int s = occupied[r0 + t], cube = slot_cube_[s];
-      tt.slot[t] = (uint32_t)s;
+      const int s = occupied[r0 + t];
+      set_touched(tt, t, slot_cube_[s], s, inv_leaf);
       tt.old_prefix[t] = n_old;
       n_old += slot_count_[s];
-      const int ci = cube % kMapW, cj = (cube / kMapW) % kMapH, ck = cube / (kMapW * kMapH);
-      const int w[3] = {ci - origin_[0], cj - origin_[1], ck - origin_[2]};
-      for (int ax = 0; ax < 3; ++ax) {
-        tt.cube_min[t][ax] = w[ax] * kCube - kHalfCube;
-        tt.leaf_lo[t][ax] = (int)std::floor((float)tt.cube_min[t][ax] * inv_leaf) - 2;
-      }
     }
-    for (int t = tt.n; t <= kMaxTouched; ++t) tt.old_prefix[t] = n_old;
-    for (int t = tt.n; t < kMaxTouched; ++t) tt.slot[t] = 0;
+    finish_touched(tt, n_old);
     if (ensure_work(n_old, err)) return -2;
     if (ensure_grid((size_t)tt.n * ncell1_ + 1024, err)) return -2;
     block_clean_ = false;
-    DM_TRY(hipMemsetAsync(d_small_, 0, 48 * sizeof(uint32_t), stream_));
+    DM_TRY(hipMemsetAsync(d_small_, 0, kCntRoundWords * sizeof(uint32_t), stream_));
+    MapInsertArgs a = work_args();
+    a.tt = tt;
     a.n_old = n_old; a.inv_leaf = inv_leaf;
-    a.nc = nc_; a.ncell1 = ncell1_; a.inv_cell = 1.0 / cell_;
-    a.pool = d_pool_; a.cap = kCapPerSlot; a.cell_start = d_cell_start_;
-    a.wpts = d_wpts_; a.cent = d_cent_; a.spts = d_spts_; a.heads = d_heads_;
-    a.keys0 = d_k0_; a.keys1 = d_k1_; a.vals0 = d_v0_; a.vals1 = d_v1_; a.flags = d_flags_; a.pos = d_pos_;
-    a.d_n_cent = d_small_; a.d_counts = d_small_ + 8;
-    a.grid = d_grid_; a.grid_scan = d_grid_scan_;
-    a.temp = d_temp_; a.temp_bytes = temp_bytes_;
-    a.d_tt = d_tt_;
-    {
-      const size_t need = (size_t)tt.n * ncell1_ + 1;
-      a.grid_is_clean = need <= grid_zero_upto_;
-      grid_zero_upto_ = std::max(grid_zero_upto_, need);
-    }
+    a.grid_is_clean = grid_clean_upto((size_t)tt.n * ncell1_ + 1);
     launch_map_retable(a, stream_);
     DM_TRY(hipGetLastError());
     DM_TRY(hipStreamSynchronize(stream_));  // `a` travels by value, but the next round reuses the work buffers
@@ -316,12 +371,7 @@ int DeviceMap::add_surf_host(const float* xyz, size_t n, size_t stride_floats, s
   if (const int rs = settle(err); rs < 0) return rs;  // (a deferred insert may still read the staging buffer)
   if (!n) return 0;
   if (stride_floats == 0) stride_floats = 3;
-  if (n * stride_floats > stage_cap_) {
-    if (d_stage_) (void)hipFree(d_stage_);
-    d_stage_ = nullptr; stage_cap_ = 0;
-    DM_TRY(hipMalloc(reinterpret_cast<void**>(&d_stage_), (n * stride_floats + 1024) * sizeof(float)));
-    stage_cap_ = n * stride_floats + 1024;
-  }
+  DM_TRY(ensure_stage(n * stride_floats));
   DM_TRY(hipMemcpyAsync(d_stage_, xyz, n * stride_floats * sizeof(float), hipMemcpyHostToDevice, stream_));
   return add_surf_dev(d_stage_, n, stride_floats, err);
 }
@@ -387,12 +437,7 @@ int DeviceMap::insert_fast(const float* d_in, size_t n, size_t stride_floats, co
   if (ensure_work(n_old_ub + n, err)) return -2;
   if (ensure_fast(err)) return -2;
   if (sync_meta(err)) return -2;
-  if (n > new_cap_) {
-    if (d_cube_of_) (void)hipFree(d_cube_of_);
-    d_cube_of_ = nullptr; new_cap_ = 0;
-    DM_TRY(hipMalloc(reinterpret_cast<void**>(&d_cube_of_), (n + 1024) * sizeof(int32_t)));
-    new_cap_ = n + 1024;
-  }
+  DM_TRY(ensure_cube_of(n));
   if (ensure_grid(per_round * ncell1_ + 1024, err, false)) return -2;
   if (ensure_leaf_table(n, err)) return -2;
   if (!block_clean_) { DM_TRY(hipMemsetAsync(d_small_, 0, kSmallWords * sizeof(uint32_t) + kMapNum, stream_)); block_clean_ = true; }
@@ -405,23 +450,15 @@ int DeviceMap::insert_fast(const float* d_in, size_t n, size_t stride_floats, co
     const size_t need = per_round * ncell1_ + 1;
     if (need > grid_zero_upto_) { DM_TRY(hipMemsetAsync(d_grid_, 0, need * sizeof(uint32_t), stream_)); grid_zero_upto_ = need; }
   }
-  MapInsertArgs a{};
-  a.tt.lbits = lbits; a.d_tt = d_tt_;
+  MapInsertArgs a = work_args();
+  a.tt.lbits = lbits;
   a.d_xyz = T ? d_world : d_in; a.n_new = (uint32_t)n; a.stride_floats = T ? 3u : (uint32_t)stride_floats; a.n_old = (uint32_t)n_old_ub;
   // the launches are sized for what the last device-built round held (+ 25 %), not for the whole map: the kernels stride
   a.n_old_grid = (uint32_t)std::max<size_t>(1, std::min<size_t>(n_old_ub, est_old_ ? est_old_ + est_old_ / 4 + 16384 : n_old_ub));
   a.d_cube_of = d_cube_of_; a.inv_leaf = 1.0f / plane_res_;
-  a.nc = nc_; a.ncell1 = ncell1_; a.inv_cell = 1.0 / cell_;
-  a.pool = d_pool_; a.cap = kCapPerSlot; a.cell_start = d_cell_start_;
-  a.wpts = d_wpts_; a.cent = d_cent_; a.spts = d_spts_; a.heads = d_heads_;
-  a.keys0 = d_k0_; a.keys1 = d_k1_; a.vals0 = d_v0_; a.vals1 = d_v1_; a.flags = d_flags_; a.pos = d_pos_;
-  a.d_n_cent = d_small_; a.d_counts = d_small_ + 8;
   a.rank = 0; a.world = 1; a.d_owned = nullptr;
-  a.grid = d_grid_; a.grid_scan = d_grid_scan_; a.grid_is_clean = true;
-  a.temp = d_temp_; a.temp_bytes = temp_bytes_;
-  a.ht_key = d_ht_key_; a.ht_cnt = d_ht_cnt_; a.ht_off = d_ht_off_;
-  a.ht_log2 = 12;
-  while (((size_t)1 << a.ht_log2) < 2 * (n + 1)) ++a.ht_log2;
+  a.grid_is_clean = true;
+  use_leaf_table(a, n);
   MapFastArgs f{};
   f.d_in = d_in; f.n = (uint32_t)n; f.stride_floats = (uint32_t)stride_floats;
   f.transform = T != nullptr; if (T) f.pose = pose_from_array(T);
@@ -429,7 +466,7 @@ int DeviceMap::insert_fast(const float* d_in, size_t n, size_t stride_floats, co
   f.origin[0] = origin_[0]; f.origin[1] = origin_[1]; f.origin[2] = origin_[2];
   f.d_cube_slot = d_cube_slot_; f.d_slot_count = d_slot_count_; f.d_slot_ok = d_slot_ok_;
   f.d_cube_cnt = d_cube_cnt_; f.d_scan_state = d_scan_state_; f.d_tickets = d_tickets_;
-  f.d_small = d_small_; f.small_words = (uint32_t)kSmallWords;
+  f.d_small = d_small_;
   f.h_report = h_report_; f.seq = ++fast_seq_;
   f.per_round = (int32_t)per_round;
   launch_map_insert_fast(a, f, stream_);
@@ -507,69 +544,40 @@ int DeviceMap::add_surf_legacy(const float* d_xyz, size_t n, size_t stride_float
   meta_dirty_ = true;  // (the host lays the rounds out and changes counts / slots: the device's copies follow before its next round)
   if (nc_ <= 1 && ncell1_ <= 2) { double cell; nc_ = cells_per_cube(plane_res_, &cell); cell_ = cell; ncell1_ = (uint32_t)((size_t)nc_ * nc_ * nc_ + 1); }
   if (ensure_work(n, err)) return -2;
-  if (n > new_cap_) {
-    if (d_cube_of_) (void)hipFree(d_cube_of_);
-    d_cube_of_ = nullptr; new_cap_ = 0;
-    DM_TRY(hipMalloc(reinterpret_cast<void**>(&d_cube_of_), (n + 1024) * sizeof(int32_t)));
-    new_cap_ = n + 1024;
-  }
+  DM_TRY(ensure_cube_of(n));
   // 1. cube of every new point + touched flags (one small read-back)
   // (ONE fill clears the counters of the first round below, the per-rank counts and the flags -- enqueued behind the
   //  PREVIOUS insert, when the host has nothing else to do, see the end of this function)
   if (!block_clean_) DM_TRY(hipMemsetAsync(d_small_, 0, kSmallWords * sizeof(uint32_t) + kMapNum, stream_));
   block_clean_ = false;
-  launch_world_cube(d_xyz, (uint32_t)n, (uint32_t)stride_floats, origin_, d_cube_of_, d_touched_, d_small_ + 48, stream_);
-  DM_TRY(hipMemcpyAsync(h_small_ + 48, d_small_ + 48, (kSmallWords - 48) * sizeof(uint32_t) + kMapNum, hipMemcpyDeviceToHost, stream_));
+  launch_world_cube(d_xyz, (uint32_t)n, (uint32_t)stride_floats, origin_, d_cube_of_, d_touched_, d_small_ + kCntInside, stream_);
+  DM_TRY(hipMemcpyAsync(h_small_ + kCntInside, d_small_ + kCntInside, (kSmallWords - kCntInside) * sizeof(uint32_t) + kMapNum, hipMemcpyDeviceToHost, stream_));
   const float inv_leaf = 1.0f / plane_res_;
   const uint32_t lbits = leaf_bits(plane_res_);
   const size_t per_round = max_touched(lbits);  // at most kMaxTouched cubes (4 when the leaf coordinates need 10 key bits: planeRes < 0.1)
   // 2. one round: the cubes `cubes[0..count)` are re-filtered with the new points that fall into them
   auto run_round = [&](const int* cubes, int count, bool clear_counters) -> int {
-    MapInsertArgs a{};
-    MapTouched& tt = a.tt;
+    MapTouched tt{};
     tt.lbits = lbits;
     tt.n = count;
     uint32_t n_old = 0;
-    for (int t = 0; t < tt.n; ++t) {
-      const int cube = cubes[t];
-      const int s = cube_slot_[cube];
-      tt.cube[t] = cube;  // (ascending: the lists below are built in block order)
-      tt.slot[t] = (uint32_t)s;
+    for (int t = 0; t < tt.n; ++t) {  // (ascending cube index: the lists below are built in block order)
+      const int s = cube_slot_[cubes[t]];
+      set_touched(tt, t, cubes[t], s, inv_leaf);
       tt.old_prefix[t] = n_old;
       n_old += slot_count_[s];
-      const int ci = cube % kMapW, cj = (cube / kMapW) % kMapH, ck = cube / (kMapW * kMapH);
-      const int w[3] = {ci - origin_[0], cj - origin_[1], ck - origin_[2]};
-      for (int ax = 0; ax < 3; ++ax) {
-        tt.cube_min[t][ax] = w[ax] * kCube - kHalfCube;
-        tt.leaf_lo[t][ax] = (int)std::floor((float)tt.cube_min[t][ax] * inv_leaf) - 2;
-        tt.wcube[t][ax] = w[ax];
-      }
     }
-    for (int t = tt.n; t <= kMaxTouched; ++t) tt.old_prefix[t] = n_old;
-    for (int t = tt.n; t < kMaxTouched; ++t) { tt.slot[t] = 0; tt.cube[t] = INT32_MAX; }
+    finish_touched(tt, n_old);
     if (ensure_work((size_t)n_old + n, err)) return -2;
-    tt.inv_leaf_watch = inv_leaf; tt.dirty = d_small_ + 7;  // (cleared with the counters)
-    a.rank = rank_; a.world = world_; a.d_owned = world_ > 1 ? d_small_ + 64 : nullptr;
-    if (clear_counters) {  // (the first round's counters were cleared together with the flags)
-      if (world_ > 1) DM_TRY(hipMemsetAsync(d_small_ + 64, 0, kMaxTouched * sizeof(uint32_t), stream_));
-      DM_TRY(hipMemsetAsync(d_small_, 0, 48 * sizeof(uint32_t), stream_));
-    }
+    tt.inv_leaf_watch = inv_leaf; tt.dirty = d_small_ + kCntDirty;  // (cleared with the counters)
+    if (clear_counters && clear_round_counters(err)) return -2;  // (the first round's counters were cleared together with the flags)
+    if (ensure_grid((size_t)tt.n * ncell1_ + 1024, err)) return -2;
+    MapInsertArgs a = work_args();
+    a.tt = tt;
+    a.rank = rank_; a.world = world_; a.d_owned = world_ > 1 ? d_small_ + kCntOwned : nullptr;
     a.d_xyz = d_xyz; a.n_new = (uint32_t)n; a.stride_floats = (uint32_t)stride_floats; a.n_old = n_old;
     a.d_cube_of = d_cube_of_; a.inv_leaf = inv_leaf;
-    a.nc = nc_; a.ncell1 = ncell1_; a.inv_cell = 1.0 / cell_;
-    a.pool = d_pool_; a.cap = kCapPerSlot; a.cell_start = d_cell_start_;
-    a.wpts = d_wpts_; a.cent = d_cent_; a.spts = d_spts_; a.heads = d_heads_;
-    a.keys0 = d_k0_; a.keys1 = d_k1_; a.vals0 = d_v0_; a.vals1 = d_v1_; a.flags = d_flags_; a.pos = d_pos_;
-    a.d_n_cent = d_small_; a.d_counts = d_small_ + 8;
-    a.d_tt = d_tt_;
-    if (ensure_grid((size_t)tt.n * ncell1_ + 1024, err)) return -2;
-    a.grid = d_grid_; a.grid_scan = d_grid_scan_;
-    {  // the round leaves the counters it used at zero again (cell_table_kernel): fill only what no round has cleared yet
-      const size_t need = (size_t)tt.n * ncell1_ + 1;
-      a.grid_is_clean = need <= grid_zero_upto_;
-      grid_zero_upto_ = std::max(grid_zero_upto_, need);
-    }
-    a.temp = d_temp_; a.temp_bytes = temp_bytes_;
+    a.grid_is_clean = grid_clean_upto((size_t)tt.n * ncell1_ + 1);  // fill only what no round has cleared yet
     // first stage: leaf grouping through a hash table (default) or the stable radix sort of the whole working set
     // (the hash grouping lets an old point that shares its leaf with no NEW point pass through: valid when the cube holds one
     //  point per leaf of the CURRENT grid, i.e. it was last filtered at this planeRes; after a resolution change the first
@@ -586,39 +594,36 @@ int DeviceMap::add_surf_legacy(const float* d_xyz, size_t n, size_t stride_float
     }
     if (hash_grouping_ && one_point_per_leaf) {
       if (ensure_leaf_table(n, err)) return -2;
-      a.ht_key = d_ht_key_; a.ht_cnt = d_ht_cnt_; a.ht_off = d_ht_off_;
-      a.ht_log2 = 12;  // this round's share of the (all-empty) table: the kernels hash into / scan the first 2^ht_log2 slots only
-      while (((size_t)1 << a.ht_log2) < 2 * (n + 1)) ++a.ht_log2;
+      use_leaf_table(a, n);
     }
     launch_map_insert(a, stream_);
     DM_TRY(hipGetLastError());  // a refused launch must not pass for an insert
     DM_TRY(hipMemcpyAsync(h_small_, d_small_, kSmallWords * sizeof(uint32_t), hipMemcpyDeviceToHost, stream_));
     DM_TRY(hipStreamSynchronize(stream_));  // also keeps the staging buffer alive long enough
-    if (a.ht_key && h_small_[5]) {
+    if (a.ht_key && h_small_[kCntHalt]) {
       // a leaf with more members than the grouping kernels sort in LDS: the second stage stood still (nothing of the map was
       // rewritten); the round is repeated with the sort-based first stage
       a.ht_key = a.ht_cnt = a.ht_off = nullptr;
-      DM_TRY(hipMemsetAsync(d_small_, 0, 48 * sizeof(uint32_t), stream_));
-      if (world_ > 1) DM_TRY(hipMemsetAsync(d_small_ + 64, 0, kMaxTouched * sizeof(uint32_t), stream_));
+      if (clear_round_counters(err)) return -2;
       launch_map_insert(a, stream_);
       DM_TRY(hipGetLastError());
-      DM_TRY(hipMemcpyAsync(h_small_, d_small_, 48 * sizeof(uint32_t), hipMemcpyDeviceToHost, stream_));
-      if (world_ > 1) DM_TRY(hipMemcpyAsync(h_small_ + 64, d_small_ + 64, kMaxTouched * sizeof(uint32_t), hipMemcpyDeviceToHost, stream_));
+      DM_TRY(hipMemcpyAsync(h_small_, d_small_, kCntRoundWords * sizeof(uint32_t), hipMemcpyDeviceToHost, stream_));
+      if (world_ > 1) DM_TRY(hipMemcpyAsync(h_small_ + kCntOwned, d_small_ + kCntOwned, kMaxTouched * sizeof(uint32_t), hipMemcpyDeviceToHost, stream_));
       DM_TRY(hipStreamSynchronize(stream_));
     }
     for (int t = 0; t < tt.n; ++t) {
-      const uint32_t cnt = h_small_[8 + t];
+      const uint32_t cnt = h_small_[kCntCounts + t];
       if (cnt > kCapPerSlot) { err = "DeviceMap: a 50 m cube exceeds the per-cube capacity of 1M points"; return -1; }
       slot_count_[tt.slot[t]] = cnt;
       // the whole cube has just been filtered at this leaf size -- unless one of its centroids drifted out of its leaf
       // (MapTouched::dirty): then two points may share a leaf and the next insert must not use the pass-through
-      slot_res_[tt.slot[t]] = ((h_small_[7] >> t) & 1u) ? -plane_res_ : plane_res_;
-      if (world_ > 1) slot_owned_[tt.slot[t]] = h_small_[64 + t];
+      slot_res_[tt.slot[t]] = ((h_small_[kCntDirty] >> t) & 1u) ? -plane_res_ : plane_res_;
+      if (world_ > 1) slot_owned_[tt.slot[t]] = h_small_[kCntOwned + t];
     }
     return 0;
   };
   DM_TRY(hipStreamSynchronize(stream_));
-  const int inserted_total = (int)h_small_[48];  // points inside the 21x21x11 window (LocalMap.h:605)
+  const int inserted_total = (int)h_small_[kCntInside];  // points inside the 21x21x11 window (LocalMap.h:605)
   std::vector<int> touched;
   for (int cube = 0; cube < kMapNum; ++cube) if (h_touched_[cube]) touched.push_back(cube);
   // the next insert's fill, now: the stream is idle and the host is about to return
@@ -650,12 +655,7 @@ int DeviceMap::export_owned(std::vector<uint8_t>& blob, std::string& err) {
     const int s = cube_slot_[cube];
     if (s < 0 || slot_count_[s] == 0) continue;
     const uint32_t cnt = slot_count_[s];
-    if ((size_t)cnt * 3 > stage_cap_) {
-      if (d_stage_) (void)hipFree(d_stage_);
-      d_stage_ = nullptr; stage_cap_ = 0;
-      DM_TRY(hipMalloc(reinterpret_cast<void**>(&d_stage_), ((size_t)cnt * 3 + 1024) * sizeof(float)));
-      stage_cap_ = (size_t)cnt * 3 + 1024;
-    }
+    DM_TRY(ensure_stage((size_t)cnt * 3));
     tmp.resize((size_t)cnt * 3);
     launch_gather_export(d_pool_, kCapPerSlot, (uint32_t)s, cnt, d_stage_, stream_);
     DM_TRY(hipMemcpyAsync(tmp.data(), d_stage_, (size_t)cnt * 12, hipMemcpyDeviceToHost, stream_));
@@ -719,24 +719,19 @@ int DeviceMap::reshard(const std::vector<std::vector<uint8_t>>& blobs, float lin
     if (!n) continue;
     if (n > kCapPerSlot) { err = "DeviceMap: a 50 m cube exceeds the per-cube capacity of 1M points"; return -1; }
     const int s = cube_slot_[cube];
-    if ((size_t)n * 3 > stage_cap_) {
-      if (d_stage_) (void)hipFree(d_stage_);
-      d_stage_ = nullptr; stage_cap_ = 0;
-      DM_TRY(hipMalloc(reinterpret_cast<void**>(&d_stage_), ((size_t)n * 3 + 1024) * sizeof(float)));
-      stage_cap_ = (size_t)n * 3 + 1024;
-    }
+    DM_TRY(ensure_stage((size_t)n * 3));
     MapTouched tt{};
     tt.n = 1;
     const int ci = cube % kMapW, cj = (cube / kMapW) % kMapH, ck = cube / (kMapW * kMapH);
     const int w[3] = {ci - origin_[0], cj - origin_[1], ck - origin_[2]};
     for (int ax = 0; ax < 3; ++ax) { tt.cube_min[0][ax] = w[ax] * kCube - kHalfCube; tt.wcube[0][ax] = w[ax]; }
     DM_TRY(hipMemcpyAsync(d_stage_, cs.xyz.data(), (size_t)n * 12, hipMemcpyHostToDevice, stream_));
-    DM_TRY(hipMemsetAsync(d_small_, 0, 2 * sizeof(uint32_t), stream_));
+    DM_TRY(hipMemsetAsync(d_small_, 0, kShardCounterWords * sizeof(uint32_t), stream_));
     launch_shard_select(d_stage_, n, tt, inv_leaf_new, nc_new, 1.0 / cell_new, rank_, world_, d_pool_ + (size_t)s * kCapPerSlot, kCapPerSlot, d_small_, stream_);
     DM_TRY(hipGetLastError());
-    DM_TRY(hipMemcpyAsync(h_small_, d_small_, 2 * sizeof(uint32_t), hipMemcpyDeviceToHost, stream_));
+    DM_TRY(hipMemcpyAsync(h_small_, d_small_, kShardCounterWords * sizeof(uint32_t), hipMemcpyDeviceToHost, stream_));
     DM_TRY(hipStreamSynchronize(stream_));
-    slot_count_[s] = h_small_[0]; slot_owned_[s] = h_small_[1]; slot_full_[s] = n;  // (n = the cube's count in the full map)
+    slot_count_[s] = h_small_[kShardCntKept]; slot_owned_[s] = h_small_[kShardCntOwned]; slot_full_[s] = n;  // (n = the cube's count in the full map)
     slot_res_[s] = cs.res;
   }
   slot_table_dirty_ = true;
@@ -755,12 +750,7 @@ size_t DeviceMap::export_points(float* xyz, size_t cap, bool only_5x5, const int
     }
     const uint32_t cnt = slot_count_[s];
     if (xyz && n + cnt <= cap) {
-      if ((size_t)cnt * 3 > stage_cap_) {
-        if (d_stage_) (void)hipFree(d_stage_);
-        d_stage_ = nullptr; stage_cap_ = 0;
-        if (hipMalloc(reinterpret_cast<void**>(&d_stage_), ((size_t)cnt * 3 + 1024) * sizeof(float)) != hipSuccess) { err = "DeviceMap: export staging alloc failed"; return n; }
-        stage_cap_ = (size_t)cnt * 3 + 1024;
-      }
+      if (ensure_stage((size_t)cnt * 3) != hipSuccess) { err = "DeviceMap: export staging alloc failed"; return n; }
       launch_gather_export(d_pool_, kCapPerSlot, (uint32_t)s, cnt, d_stage_, stream_);
       if (hipMemcpyAsync(xyz + 3 * n, d_stage_, (size_t)cnt * 12, hipMemcpyDeviceToHost, stream_) != hipSuccess ||
           hipStreamSynchronize(stream_) != hipSuccess) { err = "DeviceMap: export copy failed"; return n; }
@@ -786,12 +776,7 @@ size_t DeviceMap::export_records(void* out, size_t stride, size_t cap, bool only
   }
   if (!out || n > cap || !n) return n;
   const size_t words = n * (stride / 4);
-  if (words > stage_cap_) {  // (the staging buffer of export_points, counted in 32-bit words)
-    if (d_stage_) (void)hipFree(d_stage_);
-    d_stage_ = nullptr; stage_cap_ = 0;
-    if (hipMalloc(reinterpret_cast<void**>(&d_stage_), (words + 1024) * sizeof(float)) != hipSuccess) { err = "DeviceMap: export staging alloc failed"; return 0; }
-    stage_cap_ = words + 1024;
-  }
+  if (ensure_stage(words) != hipSuccess) { err = "DeviceMap: export staging alloc failed"; return 0; }  // (the staging buffer of export_points, counted in 32-bit words)
   size_t at = 0;
   for (const auto& sc : todo) {
     launch_gather_export_records(d_pool_, kCapPerSlot, (uint32_t)sc.first, sc.second, reinterpret_cast<uint32_t*>(d_stage_) + at * (stride / 4), (uint32_t)(stride / 4), stream_);

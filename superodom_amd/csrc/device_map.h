@@ -87,7 +87,15 @@ class DeviceMap {
   int ensure_pool(int slots_needed, std::string& err);
   int ensure_work(size_t total, std::string& err);
   int ensure_grid(size_t gn, std::string& err, bool library_scan = true);
+  hipError_t ensure_stage(size_t floats);
+  hipError_t ensure_cube_of(size_t n);
   int alloc_slot(int cube);
+  // pieces of a round's launch arguments that every path fills the same way (device_map.cpp)
+  void set_touched(MapTouched& tt, int t, int cube, int slot, float inv_leaf) const;
+  MapInsertArgs work_args() const;
+  void use_leaf_table(MapInsertArgs& a, size_t n_new) const;
+  bool grid_clean_upto(size_t need);
+  int clear_round_counters(std::string& err);
   hipStream_t stream_;
   int rank_ = 0, world_ = 1;
   std::vector<uint32_t> slot_owned_, slot_full_;  // sharded map: see owned_counts / set_full_counts
@@ -113,8 +121,7 @@ class DeviceMap {
   void* d_temp_ = nullptr; size_t temp_bytes_ = 0;
   int32_t* d_cube_of_ = nullptr; uint8_t* d_touched_ = nullptr; uint32_t* d_small_ = nullptr;
   float* d_stage_ = nullptr; size_t stage_cap_ = 0;  // host->device staging of new points / export
-  uint8_t* h_touched_ = nullptr; uint32_t* h_small_ = nullptr;  // pinned; {counters[kSmallWords], touched flags[kMapNum]} in one block, like d_small_ / d_touched_
-  static constexpr size_t kSmallWords = 128;
+  uint8_t* h_touched_ = nullptr; uint32_t* h_small_ = nullptr;  // pinned; {counters[kSmallWords] (map_kernels.h: kCnt*), touched flags[kMapNum]} in one block, like d_small_ / d_touched_
   size_t grid_zero_upto_ = 0;          // d_grid_[0 .. this) is all zero between inserts (a round cleans up after itself)
   bool block_clean_ = false;           // d_small_ / d_touched_ were cleared behind the previous insert
   // device-built inserts (insert_fast; map_kernels.hip: insert_front_kernel)

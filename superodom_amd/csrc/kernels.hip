@@ -31,6 +31,7 @@
 #ifdef SO_LM_STAMPS  // profiling build: device clock at the phases of the LM controller (tools/eval_stamps.py prints them)
 #define SO_LM_STAMP(dbg, i) do { if (dbg) (dbg)[i] = wall_clock64(); } while (0)
 #endif
+#include "device_idioms.h"
 #include "kernels.h"
 #include "plane_fit.h"
 
@@ -559,12 +560,6 @@ __device__ __forceinline__ uint32_t row_inclusive_scan_u32(uint32_t v) {
 __device__ __forceinline__ uint32_t max_over_rows(uint32_t v) {
   return max(max((uint32_t)__builtin_amdgcn_readlane((int)v, 0), (uint32_t)__builtin_amdgcn_readlane((int)v, 16)),
              max((uint32_t)__builtin_amdgcn_readlane((int)v, 32), (uint32_t)__builtin_amdgcn_readlane((int)v, 48)));
-}
-// LDS written by some lanes of the wavefront is read by others (and the other way round): orders the accesses in the compiler
-// and in the hardware; no instruction of its own beyond the wait it implies
-__device__ __forceinline__ void wave_lds_fence() {
-  __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
-  __builtin_amdgcn_wave_barrier();
 }
 // Distance from a query (cube-local u) to the nearest face of the scanned cell block [b0, b1] that has cells of the cube behind
 // it (a face on the cube's boundary has nothing behind it), less a margin: cell membership of a map point is decided in fp64 on

@@ -236,7 +236,7 @@ static int prefilter_reserve_work(so_icp_ctx* c, size_t n) {
 static int prefilter_fast(so_icp_ctx* c, hipStream_t s, size_t n, uint32_t sf, int auto_voxel_size, float line_res, float plane_res,
                           so_icp_prefilter_info& li, void** d_out, size_t* n_out) {
   constexpr int kStatBlocks = 256;
-  constexpr size_t kDecOff = 64, kPartOff = 512;
+  constexpr size_t kDecOff = kVgCounterWords * sizeof(uint32_t), kPartOff = 512;  // (the counters, kVgCnt*, come first)
   static_assert(kDecOff + sizeof(VgDecision) <= kPartOff, "layout of pf_dec");
   constexpr uint32_t kScanRecords = 1024;  // look-back records of the filter's fused scan: 2 048 points each
   constexpr size_t kStateOff = kPartOff + kStatBlocks * 10 * sizeof(double);
@@ -407,7 +407,7 @@ static int prefilter_scan_impl(so_icp_ctx* c, const float* xyz, bool xyz_on_devi
   for (DevBuf* b : {&c->pf_k0, &c->pf_k1, &c->pf_v0, &c->pf_v1, &c->pf_flags, &c->pf_pos, &c->pf_heads}) HIP_TRY(c, b->reserve((cap + 1) * 4));
   const size_t tb = map_sort_temp_bytes(cap) + 256;
   HIP_TRY(c, c->pf_temp.reserve(tb));
-  HIP_TRY(c, hipMemsetAsync(c->pf_small.p, 0, 64, s));
+  HIP_TRY(c, hipMemsetAsync(c->pf_small.p, 0, kVgCounterWords * sizeof(uint32_t), s));
   a.d_xyz = c->pf_in.as<float>(); a.n = (uint32_t)n; a.stride_floats = sf; a.inv_leaf = inv;
   a.wpts = c->pf_w.as<float4>(); a.spts = c->pf_s.as<float4>();
   a.keys0 = c->pf_k0.as<uint32_t>(); a.keys1 = c->pf_k1.as<uint32_t>(); a.vals0 = c->pf_v0.as<uint32_t>(); a.vals1 = c->pf_v1.as<uint32_t>();
@@ -416,7 +416,7 @@ static int prefilter_scan_impl(so_icp_ctx* c, const float* xyz, bool xyz_on_devi
   a.temp = c->pf_temp.p; a.temp_bytes = c->pf_temp.cap;
   launch_voxel_filter(a, s);
   uint32_t n_leaves = 0;
-  HIP_TRY(c, hipMemcpyAsync(&n_leaves, c->pf_small.p, 4, hipMemcpyDeviceToHost, s));
+  HIP_TRY(c, hipMemcpyAsync(&n_leaves, c->pf_small.as<uint32_t>() + kVgCntLeaves, sizeof(uint32_t), hipMemcpyDeviceToHost, s));
   HIP_TRY(c, hipStreamSynchronize(s));
   *d_out = c->pf_out.p; *n_out = n_leaves;
   li.reserved = announced ? 1 : 0;

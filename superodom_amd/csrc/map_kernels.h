@@ -11,6 +11,30 @@ namespace soicp {
 
 constexpr int kMaxTouched = 32;  // cubes handled by one insert round (5 key bits above 3 x 9 leaf bits; 4 cubes with 10-bit leaves)
 
+// DeviceMap's counter block (MapInsertArgs::d_n_cent, MapFastArgs::d_small): 32-bit word indices.  All zero between inserts;
+// a round clears [0, kCntRoundWords) -- and the owned counts when the map is sharded --, the words from kCntInside on belong
+// to the whole insert and are cleared (and read back) together with the touched-cube flags behind the block.
+enum : uint32_t {
+  kCntCentroids = 0,     // centroids of the round (what the kernels take as n_cent: the block's first word)
+  kCntLongLeaves = 1,    // sort path: leaves left to leaf_centroid_long_kernel
+  kCntCursor = 2,        // [2..3] one 64-bit word: members in the low half, groups in the high half (leafhash_offsets_kernel)
+  kCntGiantLeaves = 4,   // groups of more than kGiantLeaf members
+  kCntHalt = 5,          // kFastHalt*: the second stage stands still, the host repeats the round / the insert
+  kCntMediumGroups = 6,  // groups of 17..64 members
+  kCntDirty = 7,         // MapTouched::dirty bits (drift watch)
+  kCntCounts = 8,        // [8 + t] new point count of touched cube t (MapInsertArgs::d_counts)
+  kCntRoundWords = 48,   // what a round uses ends here
+  kCntInside = 48,       // new points inside the 21x21x11 window
+  kCntOwned = 64,        // [64 + t] sharded map: points of touched cube t whose own cell this rank owns (MapInsertArgs::d_owned)
+  kSmallWords = 128,     // size of the block
+};
+static_assert(kCntCounts + kMaxTouched <= kCntRoundWords && kCntRoundWords <= kCntInside, "the per-cube counts end before the window counter");
+static_assert(kCntInside < kCntOwned && kCntOwned + kMaxTouched <= kSmallWords, "the owned counts fit inside the block");
+static_assert(kCntCursor % 2 == 0, "the 64-bit cursor is 8-byte aligned");
+// the scan pre-filter's block (VoxelFilterArgs::d_n_cent; launch_vg_decide zeroes all of it) and the shard re-cut's (launch_shard_select)
+enum : uint32_t { kVgCntLeaves = 0, kVgCntLongLeaves = 1, kVgCntTicket = 8 /* leaf_heads_scan_kernel's */, kVgCounterWords = 16 };
+enum : uint32_t { kShardCntKept = 0, kShardCntOwned = 1, kShardCounterWords = 2 };
+
 // the cubes one insert round touches (passed by value to the kernels)
 struct MapTouched {
   int32_t n;
@@ -65,10 +89,9 @@ struct MapFastArgs {
   unsigned long long* d_scan_state;              // [kScanStateWords] (zero between inserts)
   uint32_t* d_tickets;                           // [kFastTicketWords]: [0, kMaxTouched) the scan's, [kMaxTouched] the front kernel's, [kMaxTouched + 1] its
                                                  // count of touched cubes (all zero between inserts), then its list of them (64 entries)
-  uint32_t* d_small;                             // DeviceMap's counter block (zero between inserts)
+  uint32_t* d_small;                             // DeviceMap's counter block (kCnt*; zero between inserts)
   MapFastReport* h_report; unsigned long long seq;
   int32_t per_round;
-  uint32_t small_words;
 };
 
 struct MapInsertArgs {
@@ -83,7 +106,7 @@ struct MapInsertArgs {
   float4* pool; uint32_t cap; uint32_t* cell_start;
   float4* wpts; float4* cent; float4* spts /* working set in leaf-sorted order */; uint32_t* heads /* first index of leaf o; [n_leaves] = end */;
   uint32_t *keys0, *keys1, *vals0, *vals1, *flags, *pos;
-  uint32_t* d_n_cent; uint32_t* d_counts;  // [8] (zeroed by the caller: [0] centroids, [1] long leaves, [2..3] member / group cursor, [4] giant leaves, [5] halt), [kMaxTouched]
+  uint32_t* d_n_cent; uint32_t* d_counts;  // the counter block (kCnt*, zeroed by the caller) and its kCntCounts part
   // first stage by hash grouping (default; nullptr = sort-based first stage): table of 2^ht_log2 >= max(4096, 2 n_new) slots,
   // keys 0xFFFFFFFF and counts 0 between inserts (the offsets kernel leaves it that way)
   uint32_t *ht_key, *ht_cnt, *ht_off; uint32_t ht_log2;
@@ -117,18 +140,18 @@ struct VgDecision {
   uint32_t flags, n_leaves;
 };
 struct VgCandidates { float line_res[3], plane_res[3], inv_leaf[3]; };  // per choice; the reciprocals formed on the host
-// partial sums -> VgDecision; zeroes counters[0..16)
+// partial sums -> VgDecision; zeroes counters[0..kVgCounterWords)
 // (also zeroes the look-back records of the filter's fused scan: d_scan_state[0..n_state))
 void launch_vg_decide(const double* d_part, int blocks, uint32_t n, int auto_voxel_size, const VgCandidates& cand, VgDecision* d_out,
                       uint32_t* d_counters, unsigned long long* d_scan_state, uint32_t n_state, hipStream_t s);
 struct VoxelFilterArgs {
   const float* d_xyz; uint32_t n, stride_floats;
   float inv_leaf; int min_b[3], div_b[3];
-  const VgDecision* d_decision;  // non-null: inv_leaf / min_b / div_b are read from here on the device; d_n_cent[0] is copied to its n_leaves
-  unsigned long long* scan_state; uint32_t n_scan_state;  // non-null (all zero, d_n_cent[8] too): flags + scan + heads in one launch
+  const VgDecision* d_decision;  // non-null: inv_leaf / min_b / div_b are read from here on the device; d_n_cent[kVgCntLeaves] is copied to its n_leaves
+  unsigned long long* scan_state; uint32_t n_scan_state;  // non-null (all zero, d_n_cent[kVgCntTicket] too): flags + scan + heads in one launch
   float4 *wpts, *spts;
   uint32_t *keys0, *keys1, *vals0, *vals1, *flags, *pos, *heads;
-  uint32_t* d_n_cent;  // [0] number of leaves, [1] long-leaf counter (both zeroed by the caller)
+  uint32_t* d_n_cent;  // kVgCnt*: number of leaves, long-leaf counter (zeroed by the caller)
   float* d_out;        // packed xyz centroids in ascending leaf index
   void* temp; size_t temp_bytes;
 };
@@ -146,7 +169,7 @@ void launch_map_insert(const MapInsertArgs& a, hipStream_t s);
 // device), the hashed first stage, the second stage with its own scan, the report into pinned memory
 void launch_map_insert_fast(const MapInsertArgs& a, const MapFastArgs& f, hipStream_t s);
 void launch_map_retable(const MapInsertArgs& a, hipStream_t s);  // resolution change: new cell tables over the resident points
-// re-cut of a shard: keep the candidates whose new-grid leaf this rank keeps; counters[0] = kept, [1] = of all candidates, those whose own cell it owns
+// re-cut of a shard: keep the candidates whose new-grid leaf this rank keeps; counters: kShardCntKept, kShardCntOwned = of all candidates, those whose own cell it owns
 void launch_shard_select(const float* d_xyz, uint32_t n, const MapTouched& tt, float inv_leaf, int nc, double inv_cell, int rank, int world,
                          float4* pool_slot, uint32_t cap, uint32_t* d_counters, hipStream_t s);
 void launch_gather_export(const float4* pool, uint32_t cap, uint32_t slot, uint32_t count, float* d_out, hipStream_t s);

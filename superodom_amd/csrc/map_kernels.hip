@@ -24,11 +24,14 @@
 #include <rocprim/rocprim.hpp>
 
 #include "deskew_math.h"
+#include "device_idioms.h"
 #include "local_map.h"
 #include "map_kernels.h"
 #include "so_math.h"
 
 namespace soicp {
+
+static inline dim3 grid_for(uint32_t n, int block) { return dim3((n + block - 1) / block); }
 
 __device__ __forceinline__ int cube_coord_f(float c, int origin) {  // == int((c + 25.0) / 50.0) (+origin), "--" if negative
   const double s = (double)c + 25.0;                                 // (exact for float inputs, see kernels.hip)
@@ -87,15 +90,51 @@ __device__ __forceinline__ uint32_t leaf_key(float x, float y, float z, float in
   return (tid << (3u * lbits)) | (((uint32_t)l2 & m) << (2u * lbits)) | (((uint32_t)l1 & m) << lbits) | ((uint32_t)l0 & m);
 }
 
+// touched cube t of old-point index e: the last t < tt->n with old_prefix[t] <= e
+// (a pointer, not a reference: a reference parameter is dereferenceable as a whole, which lets the compiler load a table entry
+//  before the bounds check in front of it -- other code than the written-out search these kernels were measured with)
+__device__ __forceinline__ int touched_of_old(const MapTouched* tt, uint32_t e) {
+  static_assert(kMaxTouched == 32, "five halving steps");
+  int t = 0;
+#pragma unroll
+  for (int step = 16; step >= 1; step >>= 1) t = (t + step < tt->n && tt->old_prefix[t + step] <= e) ? t + step : t;
+  return t;
+}
+
+// Cell of the hashed-voxel grid a point of a cube lies in: floor((p - cube_min) * inv_cell) per axis in fp64, clamped to the
+// cube.  The host twin is local_map.cpp: cell_of -- the two must agree bit for bit (the k-NN looks a point up where this put it).
+__device__ __forceinline__ void cell_coords(float x, float y, float z, const double cube_min[3], double inv_cell, int nc, int g[3]) {
+  const float c3[3] = {x, y, z};
+#pragma unroll
+  for (int a = 0; a < 3; ++a) {
+    const int v = (int)floor(((double)c3[a] - cube_min[a]) * inv_cell);
+    g[a] = v < 0 ? 0 : (v >= nc ? nc - 1 : v);
+  }
+}
+// second-stage key of a centroid: touched-cube id above the linear cell index, as in the cube's table (nc <= 64: 18 bits)
+constexpr uint32_t kCellKeyBits = 18;
+__device__ __forceinline__ uint32_t cell_index(const int g[3], int nc) { return (uint32_t)((g[2] * nc + g[1]) * nc + g[0]); }
+__device__ __forceinline__ uint32_t cell_key(int t, uint32_t cell) { return ((uint32_t)t << kCellKeyBits) | cell; }
+__device__ __forceinline__ uint32_t cell_key_cube(uint32_t k) { return k >> kCellKeyBits; }
+// the key's counter in the dense cell grids of the touched cubes (ncell1 entries per cube)
+__device__ __forceinline__ size_t cell_key_grid_index(uint32_t k, uint32_t ncell1) {
+  return (size_t)cell_key_cube(k) * ncell1 + (k & ((1u << kCellKeyBits) - 1u));
+}
+// sharded map: does rank `rank` own brick (bx, by, bz) / the brick of cell g of the cube with world id wcube?
+__device__ __forceinline__ bool rank_owns_brick(const int32_t wcube[3], int bx, int by, int bz, int rank, int world) {
+  return (int)(brick_hash(wcube[0], wcube[1], wcube[2], bx, by, bz) % (uint32_t)world) == rank;
+}
+__device__ __forceinline__ bool rank_owns_cell(const int32_t wcube[3], const int g[3], int rank, int world) {
+  return rank_owns_brick(wcube, g[0] / kBrickCells, g[1] / kBrickCells, g[2] / kBrickCells, rank, world);
+}
+
 __global__ __launch_bounds__(256) void gather_old_kernel(const MapTouched* __restrict__ ttp, const float4* __restrict__ pool, uint32_t cap, float inv_leaf,
                                                          uint32_t n_old, float4* __restrict__ wpts, uint32_t* __restrict__ keys,
                                                          uint32_t* __restrict__ vals) {
   const MapTouched& tt = *ttp;
   const uint32_t e = blockIdx.x * blockDim.x + threadIdx.x;
   if (e >= n_old) return;
-  int t = 0;
-#pragma unroll
-  for (int step = 16; step >= 1; step >>= 1) t = (t + step < tt.n && tt.old_prefix[t + step] <= e) ? t + step : t;
+  const int t = touched_of_old(&tt, e);
   const float4 p = pool[(size_t)tt.slot[t] * cap + (e - tt.old_prefix[t])];
   wpts[e] = p;
   keys[e] = leaf_key(p.x, p.y, p.z, inv_leaf, tt.leaf_lo[t][0], tt.leaf_lo[t][1], tt.leaf_lo[t][2], (uint32_t)t, tt.lbits);
@@ -114,9 +153,7 @@ __global__ __launch_bounds__(256) void old_order_key_kernel(const MapTouched* __
   const MapTouched& tt = *ttp;
   const uint32_t e = blockIdx.x * blockDim.x + threadIdx.x;
   if (e >= n_old) return;
-  int t = 0;
-#pragma unroll
-  for (int step = 16; step >= 1; step >>= 1) t = (t + step < tt.n && tt.old_prefix[t + step] <= e) ? t + step : t;
+  const int t = touched_of_old(&tt, e);
   const float4 p = pool[(size_t)tt.slot[t] * cap + (e - tt.old_prefix[t])];
   const float il = og.inv_leaf[t];
   uint32_t k = 0u;  // (0: a cube whose points keep the pool order -- equal keys, stable sort)
@@ -135,9 +172,7 @@ __global__ __launch_bounds__(256) void gather_old_ordered_kernel(const MapTouche
   const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= n_old) return;
   const uint32_t e = order[i];
-  int t = 0;
-#pragma unroll
-  for (int step = 16; step >= 1; step >>= 1) t = (t + step < tt.n && tt.old_prefix[t + step] <= e) ? t + step : t;
+  const int t = touched_of_old(&tt, e);
   const float4 p = pool[(size_t)tt.slot[t] * cap + (e - tt.old_prefix[t])];
   wpts[i] = p;
   keys[i] = leaf_key(p.x, p.y, p.z, inv_leaf, tt.leaf_lo[t][0], tt.leaf_lo[t][1], tt.leaf_lo[t][2], (uint32_t)t, tt.lbits);
@@ -166,7 +201,7 @@ __device__ __forceinline__ bool shard_keeps_leaf(float x, float y, float z, floa
   for (int bz = blo[2]; bz <= bhi[2]; ++bz)
     for (int by = blo[1]; by <= bhi[1]; ++by)
       for (int bx = blo[0]; bx <= bhi[0]; ++bx)
-        if ((int)(brick_hash(tt.wcube[t][0], tt.wcube[t][1], tt.wcube[t][2], bx, by, bz) % (uint32_t)world) == rank) return true;
+        if (rank_owns_brick(tt.wcube[t], bx, by, bz, rank, world)) return true;
   return false;
 }
 
@@ -210,48 +245,37 @@ __global__ __launch_bounds__(256) void count_owned_kernel(const float4* __restri
   bool mine = false;
   if (i < counts[t] && i < cap) {
     const float4 p = pool[(size_t)tt.slot[t] * cap + i];
-    const float c3[3] = {p.x, p.y, p.z};
     int g[3];
-#pragma unroll
-    for (int a = 0; a < 3; ++a) {
-      const int v = (int)floor(((double)c3[a] - tt.cube_min[t][a]) * inv_cell);
-      g[a] = v < 0 ? 0 : (v >= nc ? nc - 1 : v);
-    }
-    mine = (int)(brick_hash(tt.wcube[t][0], tt.wcube[t][1], tt.wcube[t][2], g[0] / kBrickCells, g[1] / kBrickCells, g[2] / kBrickCells) % (uint32_t)world) == rank;
+    cell_coords(p.x, p.y, p.z, tt.cube_min[t], inv_cell, nc, g);
+    mine = rank_owns_cell(tt.wcube[t], g, rank, world);
   }
   const unsigned long long m = __ballot(mine);
   if ((threadIdx.x & 63) == 0 && m) atomicAdd(&owned[t], (uint32_t)__popcll(m));
 }
 
-static inline dim3 grid_for_n(uint32_t n) { return dim3((n + 255u) / 256u); }
 // Re-cut of a shard after a planeRes change (DeviceMap::reshard).  The candidates are ALL points of one cube -- every
 // rank's owned points, gathered --; this rank keeps those whose leaf ON THE NEW GRID it would keep at an insert
 // (shard_keeps_leaf with the new leaf size, cell size and bricks), so that the next re-filter finds every old point of
 // every leaf it keeps, and nothing of the others.  Order in the pool: arbitrary (the retable that follows sorts).
 __global__ __launch_bounds__(256) void shard_select_kernel(const float* __restrict__ xyz, uint32_t n, MapTouched tt, float inv_leaf, int nc,
                                                            double inv_cell, int rank, int world, float4* __restrict__ pool_slot, uint32_t cap,
-                                                           uint32_t* __restrict__ counters /* [0] kept, [1] owned */) {
+                                                           uint32_t* __restrict__ counters /* kShardCnt* */) {
   const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
   bool keep = false, mine = false;
   float x = 0.f, y = 0.f, z = 0.f;
   if (i < n) {
     x = xyz[3 * (size_t)i]; y = xyz[3 * (size_t)i + 1]; z = xyz[3 * (size_t)i + 2];
     keep = shard_keeps_leaf(x, y, z, inv_leaf, tt, 0, nc, inv_cell, rank, world);
-    const float c3[3] = {x, y, z};
     int g[3];
-#pragma unroll
-    for (int a = 0; a < 3; ++a) {
-      const int v = (int)floor(((double)c3[a] - tt.cube_min[0][a]) * inv_cell);
-      g[a] = v < 0 ? 0 : (v >= nc ? nc - 1 : v);
-    }
-    mine = (int)(brick_hash(tt.wcube[0][0], tt.wcube[0][1], tt.wcube[0][2], g[0] / kBrickCells, g[1] / kBrickCells, g[2] / kBrickCells) % (uint32_t)world) == rank;
+    cell_coords(x, y, z, tt.cube_min[0], inv_cell, nc, g);
+    mine = rank_owns_cell(tt.wcube[0], g, rank, world);
   }
   const int lane = threadIdx.x & 63;
   const unsigned long long mk = __ballot(keep), mo = __ballot(mine);
   uint32_t base = 0;
   if (lane == 0) {
-    if (mk) base = atomicAdd(&counters[0], (uint32_t)__popcll(mk));
-    if (mo) atomicAdd(&counters[1], (uint32_t)__popcll(mo));
+    if (mk) base = atomicAdd(&counters[kShardCntKept], (uint32_t)__popcll(mk));
+    if (mo) atomicAdd(&counters[kShardCntOwned], (uint32_t)__popcll(mo));
   }
   base = (uint32_t)__shfl((int)base, 0, 64);
   if (keep) {
@@ -262,7 +286,7 @@ __global__ __launch_bounds__(256) void shard_select_kernel(const float* __restri
 void launch_shard_select(const float* d_xyz, uint32_t n, const MapTouched& tt, float inv_leaf, int nc, double inv_cell, int rank, int world,
                          float4* pool_slot, uint32_t cap, uint32_t* d_counters, hipStream_t s) {
   if (!n) return;
-  hipLaunchKernelGGL(shard_select_kernel, grid_for_n(n), dim3(256), 0, s, d_xyz, n, tt, inv_leaf, nc, inv_cell, rank, world, pool_slot, cap, d_counters);
+  hipLaunchKernelGGL(shard_select_kernel, grid_for(n, 256), dim3(256), 0, s, d_xyz, n, tt, inv_leaf, nc, inv_cell, rank, world, pool_slot, cap, d_counters);
 }
 
 __global__ __launch_bounds__(256) void leaf_flags_kernel(const uint32_t* __restrict__ keys, uint32_t n, uint32_t* __restrict__ flags) {
@@ -272,6 +296,14 @@ __global__ __launch_bounds__(256) void leaf_flags_kernel(const uint32_t* __restr
 }
 
 constexpr uint32_t kLongLeaf = 64, kMaxLongLeaves = 4096;
+// a leaf of more than kLongLeaf points is left to the kernel that gives it a whole wavefront -- while the list has room
+__device__ __forceinline__ bool defer_long_leaf(uint32_t o, uint32_t len, uint32_t* __restrict__ long_list, uint32_t* __restrict__ long_count) {
+  if (len <= kLongLeaf) return false;
+  const uint32_t at = atomicAdd(long_count, 1u);
+  if (at >= kMaxLongLeaves) return false;
+  long_list[at] = o;
+  return true;
+}
 
 // centroid = float sum / float count, then its cell key for the second sort
 // (cc.grid != nullptr: the centroid is also counted into its cell of the dense grids right away -- the second stage's
@@ -285,14 +317,9 @@ __device__ __forceinline__ uint32_t emit_centroid(uint32_t o, uint32_t key, floa
   cent[o] = make_float4(cx, cy, cz, 0.f);
   const int t = (int)(key >> (3u * tt.lbits));
   int g[3];
-  const float c3[3] = {cx, cy, cz};
-#pragma unroll
-  for (int a = 0; a < 3; ++a) {  // cell of the hashed-voxel grid: floor((p - cube_min) * inv_cell), clamped (local_map.cpp: cell_of)
-    const int v = (int)floor(((double)c3[a] - tt.cube_min[t][a]) * inv_cell);
-    g[a] = v < 0 ? 0 : (v >= nc ? nc - 1 : v);
-  }
-  const uint32_t cell = (uint32_t)((g[2] * nc + g[1]) * nc + g[0]);
-  const uint32_t k2 = ((uint32_t)t << 18) | cell;  // linear cell index, as in the cube's table
+  cell_coords(cx, cy, cz, tt.cube_min[t], inv_cell, nc, g);
+  const uint32_t cell = cell_index(g, nc);
+  const uint32_t k2 = cell_key(t, cell);
   keys2[o] = k2;
   if (vals2) vals2[o] = o;  // (only the sort-based second stage reads it)
   if (cc.grid) cc.rank[o] = atomicAdd(&cc.grid[(size_t)t * cc.ncell1 + cell], 1u);
@@ -318,9 +345,38 @@ __global__ __launch_bounds__(256) void leaf_heads_kernel(const uint32_t* __restr
   if (i == 0 && !valid) *n_cent = 0;
 }
 
+// Single-pass device-wide scan with decoupled look-back, the part between the workgroups.  A workgroup takes a ticket (bid:
+// its predecessors are running), and its first wavefront calls this with the workgroup's aggregate: it publishes the
+// aggregate, sums the 64 records before it at a time until it meets an inclusive one, publishes its own inclusive prefix and
+// leaves the exclusive one in *s_excl (LDS) for the rest of the workgroup.  Records: flag (1 = aggregate, 2 = inclusive) << 62 |
+// value; all zero before the launch.
+__device__ __forceinline__ void lookback_exclusive_prefix(unsigned long long* state, uint32_t bid, uint32_t agg, int lane, uint32_t* s_excl) {
+  if (lane == 0) __hip_atomic_store(&state[bid], ((bid == 0u ? 2ull : 1ull) << 62) | (unsigned long long)agg, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+  uint32_t excl = 0;
+  int base = (int)bid - 1;
+  while (base >= 0) {
+    const int j = base - lane;
+    unsigned long long rec = 2ull << 62;  // before the first workgroup: "inclusive prefix 0"
+    if (j >= 0) {
+      do { rec = __hip_atomic_load(&state[j], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); } while ((rec >> 62) == 0ull);
+    }
+    const unsigned long long mi = __ballot((rec >> 62) == 2ull);
+    const int first = mi ? __ffsll((long long)mi) - 1 : 64;  // the nearest predecessor with an inclusive prefix
+    uint32_t contrib = lane <= first ? (uint32_t)(rec & 0xFFFFFFFFull) : 0u;
+#pragma unroll
+    for (int d = 32; d >= 1; d >>= 1) contrib += (uint32_t)__shfl_xor((int)contrib, d, 64);
+    excl += contrib;
+    if (mi) break;
+    base -= 64;
+  }
+  if (lane == 0) {
+    if (bid != 0u) __hip_atomic_store(&state[bid], (2ull << 62) | (unsigned long long)(excl + agg), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    *s_excl = excl;
+  }
+}
+
 // leaf_flags_kernel + exclusive scan + leaf_heads_kernel in ONE launch (the scan pre-filter; four launches before): a
-// single-pass scan of the "first element of its leaf" flags with decoupled look-back (see cell_scan_table_kernel: ticket for
-// the workgroup order, records = flag << 62 | value, all zero before the launch), 2 048 elements per workgroup.
+// single-pass scan of the "first element of its leaf" flags (lookback_exclusive_prefix), 2 048 elements per workgroup.
 constexpr uint32_t kHeadsItems = 2048;
 __global__ __launch_bounds__(256) void leaf_heads_scan_kernel(const uint32_t* __restrict__ keys, const uint32_t* __restrict__ vals, uint32_t n,
                                                               const float4* __restrict__ wpts, float4* __restrict__ spts, uint32_t* __restrict__ heads,
@@ -357,30 +413,7 @@ __global__ __launch_bounds__(256) void leaf_heads_scan_kernel(const uint32_t* __
   uint32_t wbase = 0;
   for (int w = 0; w < wave; ++w) wbase += s_wsum[w];
   const uint32_t agg = s_wsum[0] + s_wsum[1] + s_wsum[2] + s_wsum[3];
-  if (wave == 0) {
-    if (lane == 0) __hip_atomic_store(&state[bid], ((bid == 0u ? 2ull : 1ull) << 62) | (unsigned long long)agg, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    uint32_t excl = 0;
-    int base = (int)bid - 1;
-    while (base >= 0) {
-      const int j = base - lane;
-      unsigned long long rec = 2ull << 62;
-      if (j >= 0) {
-        do { rec = __hip_atomic_load(&state[j], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); } while ((rec >> 62) == 0ull);
-      }
-      const unsigned long long mi = __ballot((rec >> 62) == 2ull);
-      const int first = mi ? __ffsll((long long)mi) - 1 : 64;
-      uint32_t contrib = lane <= first ? (uint32_t)(rec & 0xFFFFFFFFull) : 0u;
-#pragma unroll
-      for (int d = 32; d >= 1; d >>= 1) contrib += (uint32_t)__shfl_xor((int)contrib, d, 64);
-      excl += contrib;
-      if (mi) break;
-      base -= 64;
-    }
-    if (lane == 0) {
-      if (bid != 0u) __hip_atomic_store(&state[bid], (2ull << 62) | (unsigned long long)(excl + agg), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-      s_excl = excl;
-    }
-  }
+  if (wave == 0) lookback_exclusive_prefix(state, bid, agg, lane, &s_excl);
   __syncthreads();
   uint32_t o = s_excl + wbase + inc - tsum;  // exclusive prefix of the flags in front of the thread's first element
 #pragma unroll
@@ -412,10 +445,7 @@ __global__ __launch_bounds__(256) void leaf_centroid_kernel(const uint32_t* __re
   if (o >= *n_cent) return;
   const uint32_t beg = heads[o], end = heads[o + 1];
   const uint32_t key = keys[beg];
-  if (long_list && end - beg > kLongLeaf) {  // a whole wavefront takes this one (leaf_centroid_long_kernel)
-    const uint32_t at = atomicAdd(long_count, 1u);
-    if (at < kMaxLongLeaves) { long_list[at] = o; return; }
-  }
+  if (defer_long_leaf(o, long_list ? end - beg : 0u, long_list, long_count)) return;  // (no list: no leaf is long; else leaf_centroid_long_kernel takes it)
   float s0 = 0.f, s1 = 0.f, s2 = 0.f;
   constexpr int B = 16;
   float4 cur[B], nxt[B];
@@ -557,9 +587,7 @@ __global__ __launch_bounds__(256) void leafhash_match_old_kernel(const float4* _
     const uint32_t e = first + threadIdx.x;
     uint32_t k2 = kLeafEmpty;  // cell key of a point that passes through (stays empty for a point that joins a group)
     if (e < n_old) {
-      int t = 0;
-#pragma unroll
-      for (int step = 16; step >= 1; step >>= 1) t = (t + step < tt.n && tt.old_prefix[t + step] <= e) ? t + step : t;
+      const int t = touched_of_old(&tt, e);
       const float4 p = pool[(size_t)tt.slot[t] * cap + (e - tt.old_prefix[t])];
       const uint32_t key = leaf_key(p.x, p.y, p.z, inv_leaf, tt.leaf_lo[t][0], tt.leaf_lo[t][1], tt.leaf_lo[t][2], (uint32_t)t, tt.lbits);
       wpts[e] = p; keys[e] = key;
@@ -596,7 +624,7 @@ __global__ __launch_bounds__(256) void leafhash_match_old_kernel(const float4* _
         todo &= ~m;
       }
       uint32_t base = 0;
-      if (kept && lead == lane) base = atomicAdd(&cc.grid[(size_t)(k2 >> 18) * cc.ncell1 + (k2 & 0x3FFFFu)], my_cnt);
+      if (kept && lead == lane) base = atomicAdd(&cc.grid[cell_key_grid_index(k2, cc.ncell1)], my_cnt);
       base = (uint32_t)__shfl((int)base, lead, 64);
       if (kept) cc.rank[e] = base + my_idx;
     }
@@ -957,9 +985,6 @@ __global__ __launch_bounds__(256) void gather_export_records_kernel(const float4
   out_words[t] = v;
 }
 
-// ------------------------------------------------------------------------------------------------------------------
-static inline dim3 grid_for(uint32_t n, int block) { return dim3((n + block - 1) / block); }
-
 // ------------------------------------------------------------------------------------------------
 // Second stage without a sort: the centroids are counted into the dense cell grids of the touched cubes (atomic rank
 // inside a cell), an exclusive scan over the grids IS the cubes' new cell_start tables, the centroids are placed, and
@@ -991,7 +1016,7 @@ __global__ __launch_bounds__(256) void cell_count_kernel(const uint32_t* __restr
       todo &= ~m;
     }
     uint32_t base = 0;
-    if (kept && lead == lane) base = atomicAdd(&grid[(size_t)(k >> 18) * ncell1 + (k & 0x3FFFFu)], my_cnt);
+    if (kept && lead == lane) base = atomicAdd(&grid[cell_key_grid_index(k, ncell1)], my_cnt);
     base = (uint32_t)__shfl((int)base, lead, 64);
     if (kept) rank[o] = base + my_idx;
   }
@@ -1022,10 +1047,10 @@ __global__ __launch_bounds__(256) void cell_place_kernel(const uint32_t* __restr
   if (*halt) return;
   const uint32_t n_c = *n_cent;
   for (uint32_t o = blockIdx.x * blockDim.x + threadIdx.x; o < n_c; o += gridDim.x * blockDim.x) {
-    const uint32_t k = keys2[o], t = k >> 18;
+    const uint32_t k = keys2[o], t = cell_key_cube(k);
     if (k == 0xFFFFFFFFu) continue;
     const float4 v = cent[o];
-    const uint32_t at = grid_scan[(size_t)t * ncell1 + (k & 0x3FFFFu)] + rank[o];  // position over all touched cubes
+    const uint32_t at = grid_scan[cell_key_grid_index(k, ncell1)] + rank[o];  // position over all touched cubes
     tmp[at] = v;
     tmpk[at] = leaf_key(v.x, v.y, v.z, inv_leaf, tt.leaf_lo[t][0], tt.leaf_lo[t][1], tt.leaf_lo[t][2], t, tt.lbits);  // (the ranking pass reads 4 bytes per comparison)
   }
@@ -1045,9 +1070,9 @@ __global__ __launch_bounds__(256) void cell_rank_kernel(const uint32_t* __restri
   if (*halt) return;
   const uint32_t n_c = *n_cent;
   for (uint32_t o = blockIdx.x * blockDim.x + threadIdx.x; o < n_c; o += gridDim.x * blockDim.x) {
-    const uint32_t k = keys2[o], t = k >> 18;
+    const uint32_t k = keys2[o], t = cell_key_cube(k);
     if (k == 0xFFFFFFFFu) continue;
-    const size_t gi = (size_t)t * ncell1 + (k & 0x3FFFFu);
+    const size_t gi = cell_key_grid_index(k, ncell1);
     const uint32_t beg = grid_scan[gi], cnt = grid_scan[gi + 1] - beg;  // (the scan has one entry behind the last cell)
     const float4 v = cent[o];
     const uint32_t kv = leaf_key(v.x, v.y, v.z, inv_leaf, tt.leaf_lo[t][0], tt.leaf_lo[t][1], tt.leaf_lo[t][2], t, tt.lbits);
@@ -1242,9 +1267,8 @@ __global__ __launch_bounds__(1024) void insert_front_kernel(const float* __restr
 // Second stage of a device-built round: exclusive scan of the touched cubes' cell grids, cube by cube (blockIdx.y), each
 // from its own base (MapTouched::region_base) -- so the cube's new cell_start table, its point count and the positions of
 // the scratch arrays all come out of the SAME launch (the host-built round needs a device-wide scan whose length the host
-// knows, and cell_table_kernel behind it).  Single pass with decoupled look-back: a workgroup takes a ticket (so that its
-// predecessors are running), publishes its aggregate, and one wavefront sums the 64 records before it at a time until it
-// meets an inclusive one.  Records: flag (1 = aggregate, 2 = inclusive) << 62 | value; all zero between inserts.
+// knows, and cell_table_kernel behind it).  Single pass with decoupled look-back (lookback_exclusive_prefix; the records
+// are all zero between inserts).
 __global__ __launch_bounds__(256) void cell_scan_table_kernel(uint32_t* __restrict__ grid, uint32_t* __restrict__ grid_scan,
                                                               const MapTouched* __restrict__ ttp, uint32_t cap, uint32_t ncell1,
                                                               uint32_t* __restrict__ cell_start, uint32_t* __restrict__ counts,
@@ -1275,31 +1299,7 @@ __global__ __launch_bounds__(256) void cell_scan_table_kernel(uint32_t* __restri
   for (int w = 0; w < wave; ++w) wbase += s_wsum[w];
   const uint32_t agg = s_wsum[0] + s_wsum[1] + s_wsum[2] + s_wsum[3];
   const uint32_t texcl = wbase + inc - tsum;
-  if (wave == 0) {
-    unsigned long long* st = state + (size_t)t * nblk;
-    if (lane == 0) __hip_atomic_store(&st[bid], ((bid == 0u ? 2ull : 1ull) << 62) | (unsigned long long)agg, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    uint32_t excl = 0;
-    int base = (int)bid - 1;
-    while (base >= 0) {
-      const int j = base - lane;
-      unsigned long long rec = 2ull << 62;  // before the first workgroup: "inclusive prefix 0"
-      if (j >= 0) {
-        do { rec = __hip_atomic_load(&st[j], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); } while ((rec >> 62) == 0ull);
-      }
-      const unsigned long long mi = __ballot((rec >> 62) == 2ull);
-      const int first = mi ? __ffsll((long long)mi) - 1 : 64;  // the nearest predecessor with an inclusive prefix
-      uint32_t contrib = lane <= first ? (uint32_t)(rec & 0xFFFFFFFFull) : 0u;
-#pragma unroll
-      for (int d = 32; d >= 1; d >>= 1) contrib += (uint32_t)__shfl_xor((int)contrib, d, 64);
-      excl += contrib;
-      if (mi) break;
-      base -= 64;
-    }
-    if (lane == 0) {
-      if (bid != 0u) __hip_atomic_store(&st[bid], (2ull << 62) | (unsigned long long)(excl + agg), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-      s_excl = excl;
-    }
-  }
+  if (wave == 0) lookback_exclusive_prefix(state + (size_t)t * nblk, bid, agg, lane, &s_excl);
   __syncthreads();
   const uint32_t slot = ttp->slot[t], rb = ttp->region_base[t];
   uint32_t run = s_excl + texcl;
@@ -1323,13 +1323,13 @@ __global__ __launch_bounds__(256) void insert_report_kernel(const MapTouched* __
                                                             uint32_t* __restrict__ tickets, uint32_t* __restrict__ slot_ok,
                                                             MapFastReport* __restrict__ rep, unsigned long long seq) {
   const int tid = threadIdx.x;
-  const uint32_t halt = small[5], n = (uint32_t)ttp->n, dirty = small[7];
+  const uint32_t halt = small[kCntHalt], n = (uint32_t)ttp->n, dirty = small[kCntDirty];
   if (tid < kMaxTouched) {
     rep->cube[tid] = ttp->cube[tid];
-    rep->count[tid] = small[8 + tid];
+    rep->count[tid] = small[kCntCounts + tid];
     if (!halt && (uint32_t)tid < n) slot_ok[ttp->slot[tid]] = ((dirty >> tid) & 1u) ? 0u : 1u;
   }
-  if (tid == 0) { rep->halt = halt; rep->n = n; rep->n_inside = small[48]; rep->dirty = dirty; rep->n_old = ttp->old_prefix[kMaxTouched]; rep->pad = 0u; }
+  if (tid == 0) { rep->halt = halt; rep->n = n; rep->n_inside = small[kCntInside]; rep->dirty = dirty; rep->n_old = ttp->old_prefix[kMaxTouched]; rep->pad = 0u; }
   __syncthreads();  // (every thread has read the counters)
   for (uint32_t i = (uint32_t)tid; i < small_words; i += 256u) small[i] = 0u;
   for (uint32_t i = (uint32_t)tid; i < (uint32_t)kMapNum; i += 256u) cube_cnt[i] = 0u;
@@ -1399,10 +1399,7 @@ __global__ __launch_bounds__(256) void vg_centroid_kernel(const uint32_t* __rest
   if (o == 0u && dec) dec->n_leaves = *n_cent;  // (read back with the decision)
   if (o >= *n_cent) return;
   const uint32_t beg = heads[o], end = heads[o + 1];
-  if (end - beg > kLongLeaf) {
-    const uint32_t at = atomicAdd(long_count, 1u);
-    if (at < kMaxLongLeaves) { long_list[at] = o; return; }
-  }
+  if (defer_long_leaf(o, end - beg, long_list, long_count)) return;  // (vg_centroid_long_kernel takes it)
   float s0 = 0.f, s1 = 0.f, s2 = 0.f;
   constexpr int B = 16;
   for (uint32_t j = beg; j < end; j += B) {
@@ -1452,9 +1449,7 @@ __global__ __launch_bounds__(256) void vg_centroid_long_kernel(const uint32_t* _
         nxt[k] = idx < end ? src[4 * (size_t)idx] : 0.f;
       }
     }
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+    wave_lds_fence();
     const uint32_t m = end - base < 256u ? end - base : 256u, m4 = (m + 3u) & ~3u;
     for (uint32_t q = 0; q < m4; q += 4) {
       const float4 v = *reinterpret_cast<const float4*>(b + q);
@@ -1474,7 +1469,7 @@ __global__ __launch_bounds__(256) void vg_decide_kernel(const double* __restrict
   __shared__ double acc[10];
   __shared__ double sp[kVgStatBlocksMax * 10];  // (the partials through LDS: 256 dependent round trips to memory per thread took 54 us)
   const int k = threadIdx.x;
-  if (k < 16) counters[k] = 0u;
+  if (k < (int)kVgCounterWords) counters[k] = 0u;
   for (uint32_t i = (uint32_t)k; i < n_state; i += blockDim.x) scan_state[i] = 0ull;
   {  // (all of a thread's loads in flight together: a loop of unknown length made ten round trips of them)
     constexpr int kLoads = kVgStatBlocksMax * 10 / 256;
@@ -1535,15 +1530,14 @@ void launch_vg_decide(const double* d_part, int blocks, uint32_t n, int auto_vox
 }
 // Stable (key, index) sort of the working set: merge sort with 2048-item block sorts and odd-even merges (measured against
 // rocPRIM's own choice, its Onesweep radix sort and two other merge configurations in rounds 1-2: the fastest at these sizes).
-static hipError_t map_sort(void* tmp, size_t& bytes, const uint32_t* ki, uint32_t* ko, const uint32_t* vi, uint32_t* vo, size_t n,
-                           unsigned /*end_bit*/, hipStream_t s) {
+static hipError_t map_sort(void* tmp, size_t& bytes, const uint32_t* ki, uint32_t* ko, const uint32_t* vi, uint32_t* vo, size_t n, hipStream_t s) {
   using M1 = rocprim::merge_sort_config<512, 512, 4, 128, 128, 4, (1u << 30)>;
   return rocprim::merge_sort<M1>(tmp, bytes, ki, ko, vi, vo, n, rocprim::less<uint32_t>(), s);
 }
 
 size_t map_sort_temp_bytes(size_t n) {
   size_t a = 0, b = 0;
-  (void)map_sort(nullptr, a, (const uint32_t*)nullptr, (uint32_t*)nullptr, (const uint32_t*)nullptr, (uint32_t*)nullptr, n, 32, (hipStream_t)0);
+  (void)map_sort(nullptr, a, (const uint32_t*)nullptr, (uint32_t*)nullptr, (const uint32_t*)nullptr, (uint32_t*)nullptr, n, (hipStream_t)0);
   (void)rocprim::exclusive_scan(nullptr, b, (const uint32_t*)nullptr, (uint32_t*)nullptr, 0u, n, rocprim::plus<uint32_t>(), (hipStream_t)0);
   return a > b ? a : b;
 }
@@ -1558,9 +1552,42 @@ void launch_transform_scan(const float* d_scan, uint32_t n, const Pose& pose, fl
   if (!n) return;
   hipLaunchKernelGGL(transform_scan_kernel, grid_for(n, 256), dim3(256), 0, s, d_scan, n, pose, d_out);
 }
+// the halt word of the insert's counter block: raised by leafhash_centroids_kernel (a leaf too large for the grouping kernels) or
+// by the front kernel (a round the device cannot lay out); every kernel of the second stage is a no-op behind it
+static inline uint32_t* halt_word(const MapInsertArgs& a) { return a.d_n_cent + kCntHalt; }
+
+// sorted keys -> working set in leaf-sorted order, first index of every leaf, number of leaves (three launches; the fused
+// form is leaf_heads_scan_kernel)
+static void launch_leaf_heads(const uint32_t* keys, const uint32_t* vals, uint32_t n, uint32_t* flags, uint32_t* pos, const float4* wpts, float4* spts,
+                              uint32_t* heads, uint32_t* n_cent, void* temp, size_t temp_bytes, hipStream_t s) {
+  hipLaunchKernelGGL(leaf_flags_kernel, grid_for(n, 256), dim3(256), 0, s, keys, n, flags);
+  (void)rocprim::exclusive_scan(temp, temp_bytes, flags, pos, 0u, (size_t)n, rocprim::plus<uint32_t>(), s);
+  hipLaunchKernelGGL(leaf_heads_kernel, grid_for(n, 256), dim3(256), 0, s, keys, vals, flags, pos, n, wpts, spts, heads, n_cent);
+}
+
+// tail of the second stage: the centroids into their cells' ranges of the scratch arrays (spts / flags: first-stage scratch,
+// free after the centroids), then into the pool in ascending leaf order
+static void launch_place_rank(const MapInsertArgs& a, const uint32_t* keys2, uint32_t total, hipStream_t s) {
+  hipLaunchKernelGGL(cell_place_kernel, grid_for(total, 256), dim3(256), 0, s, keys2, a.vals1, a.d_n_cent, a.grid_scan, a.cent, a.d_tt, a.ncell1,
+                     a.inv_leaf, a.spts, a.flags, halt_word(a));
+  hipLaunchKernelGGL(cell_rank_kernel, grid_for(total, 256), dim3(256), 0, s, keys2, a.d_n_cent, a.grid_scan, a.cent, a.spts, a.flags, a.d_tt,
+                     a.cap, a.ncell1, a.inv_leaf, a.pool, a.vals1, halt_word(a));
+}
+// second stage of a host-built round, by counting into the cell grids (no sort); keys2: cell key per centroid
+static void launch_second_stage(const MapInsertArgs& a, const uint32_t* keys2, uint32_t total, hipStream_t s) {
+  const size_t gn = (size_t)a.tt.n * a.ncell1;
+  if (!a.grid_is_clean) (void)hipMemsetAsync(a.grid, 0, (gn + 1) * sizeof(uint32_t), s);  // (else: cleaned by the previous round's cell_table_kernel)
+  hipLaunchKernelGGL(cell_count_kernel, grid_for(total, 256), dim3(256), 0, s, keys2, a.d_n_cent, a.ncell1, a.grid, a.vals1, halt_word(a));
+  size_t tb = a.temp_bytes;
+  (void)rocprim::exclusive_scan(a.temp, tb, a.grid, a.grid_scan, 0u, gn + 1, rocprim::plus<uint32_t>(), s);
+  hipLaunchKernelGGL(cell_table_kernel, dim3((a.ncell1 + 255) / 256, a.tt.n), dim3(256), 0, s, a.grid_scan, a.d_tt, a.cap, a.ncell1, a.cell_start,
+                     a.d_counts, halt_word(a), a.grid);
+  launch_place_rank(a, keys2, total, s);
+}
+
 // first stage by hash grouping: mslot = keys1, mrank = vals1, member list = pos, group ranges = heads / flags, cell keys =
 // vals0; lists of the larger groups in spts (first-stage scratch of the sort path, the second stage's scratch later): at
-// most n_new / 16 groups of more than 16 members, n_new / 64 of more than 64; counters in d_n_cent[2..6]
+// most n_new / 16 groups of more than 16 members, n_new / 64 of more than 64; counters: kCntCursor .. kCntMediumGroups
 // (a.n_old: the number of old points, or -- device-built round -- a bound on it: the kernels take the number from d_tt)
 // (count_cells: the centroids are counted into the cell grids as they are produced -- no cell_count_kernel behind this stage;
 //  the ranks go to vals1, where a matched old point and every new point keep their member ranks until the members are placed:
@@ -1568,7 +1595,8 @@ void launch_transform_scan(const float* d_scan, uint32_t n, const Pose& pose, fl
 static uint32_t* launch_first_stage_hashed(const MapInsertArgs& a, hipStream_t s, bool count_cells) {
   const LeafTable ht{a.ht_key, a.ht_cnt, a.ht_off, a.ht_log2};
   const CellCount cc{count_cells ? a.grid : nullptr, a.vals1, a.ncell1};
-  unsigned long long* cursor = reinterpret_cast<unsigned long long*>(a.d_n_cent + 2);
+  uint32_t *medium_count = a.d_n_cent + kCntMediumGroups, *giant_count = a.d_n_cent + kCntGiantLeaves;
+  unsigned long long* cursor = reinterpret_cast<unsigned long long*>(a.d_n_cent + kCntCursor);
   uint32_t* keys2 = a.vals0;
   uint32_t* medium_list = reinterpret_cast<uint32_t*>(a.spts);
   uint32_t* giant_list = medium_list + a.n_new / 16u + 2u;
@@ -1579,8 +1607,8 @@ static uint32_t* launch_first_stage_hashed(const MapInsertArgs& a, hipStream_t s
   if (a.n_old)
     hipLaunchKernelGGL(leafhash_match_old_kernel, grid_for(n_old_grid, 256), dim3(256), 0, s, a.pool, a.cap, a.inv_leaf, a.keys0, a.wpts, ht,
                        a.keys1, a.vals1, a.d_tt, a.nc, a.inv_cell, a.cent, keys2, cc);
-  hipLaunchKernelGGL(leafhash_offsets_kernel, dim3((1u << a.ht_log2) / 4096u), dim3(1024), 0, s, ht, a.heads, a.flags, cursor, medium_list, a.d_n_cent + 6,
-                     giant_list, a.d_n_cent + 4);
+  hipLaunchKernelGGL(leafhash_offsets_kernel, dim3((1u << a.ht_log2) / 4096u), dim3(1024), 0, s, ht, a.heads, a.flags, cursor, medium_list, medium_count,
+                     giant_list, giant_count);
   hipLaunchKernelGGL(leafhash_place_kernel, grid_for(total, 256), dim3(256), 0, s, a.keys1, a.vals1, a.n_new, a.d_tt, a.ht_off, a.pos);
   const uint32_t max_medium = a.n_new / 16u + 1u, max_giant = a.n_new / 64u + 1u;
   const uint32_t small_blocks = (a.n_new ? a.n_new + 255u : 256u) / 256u;  // (256 groups per workgroup, see the kernel)
@@ -1590,8 +1618,8 @@ static uint32_t* launch_first_stage_hashed(const MapInsertArgs& a, hipStream_t s
   // (per launch, not once per process: the attribute belongs to the current device, and one process may drive several)
   (void)hipFuncSetAttribute(reinterpret_cast<const void*>(leafhash_centroids_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)giant_lds);
   hipLaunchKernelGGL(leafhash_centroids_kernel, dim3(giant_blocks + small_blocks + medium_blocks), dim3(kGiantThreads), giant_lds, s, a.heads, a.flags, cursor,
-                     a.pos, a.wpts, a.keys0, a.n_new, nhist, a.d_tt, a.nc, a.inv_cell, a.cent, keys2, a.d_n_cent, medium_list, a.d_n_cent + 6, giant_list,
-                     a.d_n_cent + 4, a.d_n_cent + 5, giant_blocks, small_blocks, cc);
+                     a.pos, a.wpts, a.keys0, a.n_new, nhist, a.d_tt, a.nc, a.inv_cell, a.cent, keys2, a.d_n_cent, medium_list, medium_count, giant_list,
+                     giant_count, halt_word(a), giant_blocks, small_blocks, cc);
   return keys2;
 }
 
@@ -1606,7 +1634,7 @@ void launch_map_insert(const MapInsertArgs& a, hipStream_t s) {
       OldGrids og;
       for (int t = 0; t < kMaxTouched; ++t) og.inv_leaf[t] = a.old_inv_leaf[t];
       hipLaunchKernelGGL(old_order_key_kernel, grid_for(a.n_old, 256), dim3(256), 0, s, a.d_tt, og, a.pool, a.cap, a.n_old, a.keys0, a.vals0);
-      (void)map_sort(a.temp, tb, a.keys0, a.keys1, a.vals0, a.vals1, (size_t)a.n_old, 30, s);  // stable
+      (void)map_sort(a.temp, tb, a.keys0, a.keys1, a.vals0, a.vals1, (size_t)a.n_old, s);  // stable
       tb = a.temp_bytes;
       hipLaunchKernelGGL(gather_old_ordered_kernel, grid_for(a.n_old, 256), dim3(256), 0, s, a.d_tt, a.pool, a.cap, a.inv_leaf, a.n_old, a.vals1, a.wpts,
                          a.keys0, a.vals0);
@@ -1620,43 +1648,25 @@ void launch_map_insert(const MapInsertArgs& a, hipStream_t s) {
   if (hashed) {
     keys2 = launch_first_stage_hashed(a, s, false);  // first stage without a sort (see leafhash_insert_new_kernel)
   } else {
-    (void)map_sort(a.temp, tb, a.keys0, a.keys1, a.vals0, a.vals1, (size_t)total, 32, s);  // stable
-    hipLaunchKernelGGL(leaf_flags_kernel, grid_for(total, 256), dim3(256), 0, s, a.keys1, total, a.flags);
-    tb = a.temp_bytes;
-    (void)rocprim::exclusive_scan(a.temp, tb, a.flags, a.pos, 0u, (size_t)total, rocprim::plus<uint32_t>(), s);
-    hipLaunchKernelGGL(leaf_heads_kernel, grid_for(total, 256), dim3(256), 0, s, a.keys1, a.vals1, a.flags, a.pos, total, a.wpts, a.spts, a.heads,
-                       a.d_n_cent);
-    // d_n_cent + 1 = number of long leaves (cleared with d_small_), list = the flags array (free after the scan)
+    (void)map_sort(a.temp, tb, a.keys0, a.keys1, a.vals0, a.vals1, (size_t)total, s);  // stable
+    launch_leaf_heads(a.keys1, a.vals1, total, a.flags, a.pos, a.wpts, a.spts, a.heads, a.d_n_cent, a.temp, a.temp_bytes, s);
+    // list of the long leaves = the flags array (free after the scan)
     hipLaunchKernelGGL(leaf_centroid_kernel, grid_for(total, 256), dim3(256), 0, s, a.keys1, a.heads, a.d_n_cent, a.spts, a.d_tt, a.nc, a.inv_cell,
-                       a.cent, a.keys0, a.vals0, a.flags, a.d_n_cent + 1);
+                       a.cent, a.keys0, a.vals0, a.flags, a.d_n_cent + kCntLongLeaves);
     hipLaunchKernelGGL(leaf_centroid_long_kernel, dim3(kMaxLongLeaves / 4), dim3(256), 0, s, a.keys1, a.heads, a.spts, a.d_tt, a.nc, a.inv_cell,
-                       a.cent, a.keys0, a.vals0, a.flags, a.d_n_cent + 1);
+                       a.cent, a.keys0, a.vals0, a.flags, a.d_n_cent + kCntLongLeaves);
   }
-  {  // second stage by counting into the cell grids (no sort)
-    const size_t gn = (size_t)a.tt.n * a.ncell1;
-    const uint32_t* halt = a.d_n_cent + 5;  // raised by leafhash_giant_kernel: the round is repeated with the sort-based first stage
-    if (!a.grid_is_clean) (void)hipMemsetAsync(a.grid, 0, (gn + 1) * sizeof(uint32_t), s);  // (else: cleaned by the previous round's cell_table_kernel)
-    hipLaunchKernelGGL(cell_count_kernel, grid_for(total, 256), dim3(256), 0, s, keys2, a.d_n_cent, a.ncell1, a.grid, a.vals1, halt);
-    tb = a.temp_bytes;
-    (void)rocprim::exclusive_scan(a.temp, tb, a.grid, a.grid_scan, 0u, gn + 1, rocprim::plus<uint32_t>(), s);
-    hipLaunchKernelGGL(cell_table_kernel, dim3((a.ncell1 + 255) / 256, a.tt.n), dim3(256), 0, s, a.grid_scan, a.d_tt, a.cap, a.ncell1, a.cell_start,
-                       a.d_counts, halt, a.grid);
-    hipLaunchKernelGGL(cell_place_kernel, grid_for(total, 256), dim3(256), 0, s, keys2, a.vals1, a.d_n_cent, a.grid_scan, a.cent, a.d_tt, a.ncell1,
-                       a.inv_leaf, a.spts, a.flags, halt);  // spts / flags (first-stage scratch) are free after the centroids
-    hipLaunchKernelGGL(cell_rank_kernel, grid_for(total, 256), dim3(256), 0, s, keys2, a.d_n_cent, a.grid_scan, a.cent, a.spts, a.flags, a.d_tt,
-                       a.cap, a.ncell1, a.inv_leaf, a.pool, a.vals1, halt);
-    if (a.world > 1 && a.d_owned)
-      hipLaunchKernelGGL(count_owned_kernel, dim3((total + 255) / 256, a.tt.n), dim3(256), 0, s, a.pool, a.cap, a.d_tt, a.d_counts, a.nc, a.inv_cell,
-                         a.rank, a.world, a.d_owned);
-    return;
-  }
+  launch_second_stage(a, keys2, total, s);
+  if (a.world > 1 && a.d_owned)
+    hipLaunchKernelGGL(count_owned_kernel, dim3((total + 255) / 256, a.tt.n), dim3(256), 0, s, a.pool, a.cap, a.d_tt, a.d_counts, a.nc, a.inv_cell,
+                       a.rank, a.world, a.d_owned);
 }
 
 // The insert as one uninterrupted sequence of launches (DeviceMap::insert_fast): a.n_old is a BOUND on the round's old points
 // (the launches are sized by it), a.tt only carries lbits; everything else of the round is laid out by the front kernel.
 void launch_map_insert_fast(const MapInsertArgs& a, const MapFastArgs& f, hipStream_t s) {
   if (!f.n) return;
-  const FrontBuild b{f.d_cube_slot, f.d_slot_count, f.d_slot_ok, f.d_cube_cnt, f.d_small + 48, f.d_tickets + kMaxTouched, f.d_small + 5, f.d_small + 7,
+  const FrontBuild b{f.d_cube_slot, f.d_slot_count, f.d_slot_ok, f.d_cube_cnt, f.d_small + kCntInside, f.d_tickets + kMaxTouched, f.d_small + kCntHalt, f.d_small + kCntDirty,
                      a.d_tt, a.inv_leaf, a.tt.lbits, f.per_round, f.h_report, f.seq,
                      f.d_tickets + kMaxTouched + 1, reinterpret_cast<int32_t*>(f.d_tickets + kMaxTouched + 2)};
   if (f.transform)
@@ -1667,15 +1677,11 @@ void launch_map_insert_fast(const MapInsertArgs& a, const MapFastArgs& f, hipStr
                        f.origin[1], f.origin[2], const_cast<int32_t*>(a.d_cube_of), b);
   uint32_t* keys2 = launch_first_stage_hashed(a, s, /*count_cells=*/true);  // (cell counting folded into the kernels that produce the centroids)
   const uint32_t total = (a.n_old_grid ? a.n_old_grid : a.n_old) + a.n_new;
-  const uint32_t* halt = a.d_n_cent + 5;
   const uint32_t nblk = (a.ncell1 + kScanItems - 1u) / kScanItems;
   hipLaunchKernelGGL(cell_scan_table_kernel, dim3(nblk, (uint32_t)f.per_round), dim3(256), 0, s, a.grid, a.grid_scan, a.d_tt, a.cap, a.ncell1, a.cell_start,
-                     a.d_counts, f.d_slot_count, halt, f.d_scan_state, f.d_tickets, nblk);
-  hipLaunchKernelGGL(cell_place_kernel, grid_for(total, 256), dim3(256), 0, s, keys2, a.vals1, a.d_n_cent, a.grid_scan, a.cent, a.d_tt, a.ncell1,
-                     a.inv_leaf, a.spts, a.flags, halt);
-  hipLaunchKernelGGL(cell_rank_kernel, grid_for(total, 256), dim3(256), 0, s, keys2, a.d_n_cent, a.grid_scan, a.cent, a.spts, a.flags, a.d_tt,
-                     a.cap, a.ncell1, a.inv_leaf, a.pool, a.vals1, halt);
-  hipLaunchKernelGGL(insert_report_kernel, dim3(1), dim3(256), 0, s, a.d_tt, f.d_small, f.small_words, f.d_cube_cnt, f.d_scan_state, f.d_tickets, f.d_slot_ok,
+                     a.d_counts, f.d_slot_count, halt_word(a), f.d_scan_state, f.d_tickets, nblk);
+  launch_place_rank(a, keys2, total, s);
+  hipLaunchKernelGGL(insert_report_kernel, dim3(1), dim3(256), 0, s, a.d_tt, f.d_small, (uint32_t)kSmallWords, f.d_cube_cnt, f.d_scan_state, f.d_tickets, f.d_slot_ok,
                      f.h_report, f.seq);
 }
 // Resolution change (localMap.planeRes_ is pushed every frame, laserMapping.cpp:648-649): the points of a cube stay as they
@@ -1689,19 +1695,12 @@ __global__ __launch_bounds__(256) void retable_gather_kernel(const MapTouched* _
   const uint32_t e = blockIdx.x * blockDim.x + threadIdx.x;
   if (e == 0) *n_cent = n_old;
   if (e >= n_old) return;
-  int t = 0;
-#pragma unroll
-  for (int step = 16; step >= 1; step >>= 1) t = (t + step < tt.n && tt.old_prefix[t + step] <= e) ? t + step : t;
+  const int t = touched_of_old(&tt, e);
   const float4 p = pool[(size_t)tt.slot[t] * cap + (e - tt.old_prefix[t])];
   cent[e] = make_float4(p.x, p.y, p.z, 0.f);
   int g[3];
-  const float c3[3] = {p.x, p.y, p.z};
-#pragma unroll
-  for (int a = 0; a < 3; ++a) {
-    const int v = (int)floor(((double)c3[a] - tt.cube_min[t][a]) * inv_cell);
-    g[a] = v < 0 ? 0 : (v >= nc ? nc - 1 : v);
-  }
-  keys2[e] = ((uint32_t)t << 18) | (uint32_t)((g[2] * nc + g[1]) * nc + g[0]);
+  cell_coords(p.x, p.y, p.z, tt.cube_min[t], inv_cell, nc, g);
+  keys2[e] = cell_key(t, cell_index(g, nc));
 }
 // a.inv_leaf = 1 / the planeRes the points were last filtered with (their leaf keys are distinct there); a.grid required
 void launch_map_retable(const MapInsertArgs& a, hipStream_t s) {
@@ -1710,17 +1709,7 @@ void launch_map_retable(const MapInsertArgs& a, hipStream_t s) {
   hipLaunchKernelGGL(tt_store_kernel, dim3(1), dim3(64), 0, s, a.tt, a.d_tt);
   hipLaunchKernelGGL(retable_gather_kernel, grid_for(total, 256), dim3(256), 0, s, a.d_tt, a.pool, a.cap, total, a.nc, a.inv_cell, a.cent, a.keys0,
                      a.d_n_cent);
-  const size_t gn = (size_t)a.tt.n * a.ncell1;
-  if (!a.grid_is_clean) (void)hipMemsetAsync(a.grid, 0, (gn + 1) * sizeof(uint32_t), s);
-  hipLaunchKernelGGL(cell_count_kernel, grid_for(total, 256), dim3(256), 0, s, a.keys0, a.d_n_cent, a.ncell1, a.grid, a.vals1, a.d_n_cent + 5);
-  size_t tb = a.temp_bytes;
-  (void)rocprim::exclusive_scan(a.temp, tb, a.grid, a.grid_scan, 0u, gn + 1, rocprim::plus<uint32_t>(), s);
-  hipLaunchKernelGGL(cell_table_kernel, dim3((a.ncell1 + 255) / 256, a.tt.n), dim3(256), 0, s, a.grid_scan, a.d_tt, a.cap, a.ncell1, a.cell_start,
-                     a.d_counts, a.d_n_cent + 5, a.grid);
-  hipLaunchKernelGGL(cell_place_kernel, grid_for(total, 256), dim3(256), 0, s, a.keys0, a.vals1, a.d_n_cent, a.grid_scan, a.cent, a.d_tt, a.ncell1,
-                     a.inv_leaf, a.spts, a.flags, a.d_n_cent + 5);
-  hipLaunchKernelGGL(cell_rank_kernel, grid_for(total, 256), dim3(256), 0, s, a.keys0, a.d_n_cent, a.grid_scan, a.cent, a.spts, a.flags, a.d_tt,
-                     a.cap, a.ncell1, a.inv_leaf, a.pool, a.vals1, a.d_n_cent + 5);
+  launch_second_stage(a, a.keys0, total, s);
 }
 // The reference's own accumulation of the auto-voxel statistic (laserMapping.cpp:604-611): Eigen::Vector3f average, one float
 // addition per point and axis IN INPUT ORDER.  A sequential float sum cannot be re-associated without changing its roundings,
@@ -1738,8 +1727,7 @@ __global__ __launch_bounds__(64) void vg_stats_inorder_kernel(const float* __res
     if (i < n) { const float* p = xyz + (size_t)i * stride_floats; x = p[0]; y = p[1]; z = p[2]; }
     __builtin_amdgcn_wave_barrier();
     buf[0][lane] = fabsf(x); buf[1][lane] = fabsf(y); buf[2][lane] = fabsf(z);
-    __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
-    __builtin_amdgcn_wave_barrier();
+    wave_lds_fence();
     const uint32_t m = n - base < 64u ? n - base : 64u;
     if (lane < 3)
       for (uint32_t k = 0; k < m; ++k) sum += buf[lane][k];  // (-ffp-contract=off: a plain float addition, like the reference's)
@@ -1754,23 +1742,20 @@ void launch_vg_stats(const float* d_xyz, uint32_t n, uint32_t stride_floats, dou
 }
 void launch_voxel_filter(const VoxelFilterArgs& a, hipStream_t s) {
   const uint32_t n = a.n;
+  uint32_t* n_leaves = a.d_n_cent + kVgCntLeaves;
   hipLaunchKernelGGL(vg_keys_kernel, grid_for(n, 256), dim3(256), 0, s, a.d_xyz, n, a.stride_floats, a.inv_leaf, a.min_b[0], a.min_b[1],
                      a.min_b[2], a.div_b[0], a.div_b[0] * a.div_b[1], a.wpts, a.keys0, a.vals0, a.d_decision);
   size_t tb = a.temp_bytes;
-  (void)map_sort(a.temp, tb, a.keys0, a.keys1, a.vals0, a.vals1, (size_t)n, 32, s);  // stable: input order inside a leaf
+  (void)map_sort(a.temp, tb, a.keys0, a.keys1, a.vals0, a.vals1, (size_t)n, s);  // stable: input order inside a leaf
   if (a.scan_state && (n + kHeadsItems - 1u) / kHeadsItems <= a.n_scan_state) {
     hipLaunchKernelGGL(leaf_heads_scan_kernel, dim3((n + kHeadsItems - 1u) / kHeadsItems), dim3(256), 0, s, a.keys1, a.vals1, n, a.wpts, a.spts, a.heads,
-                       a.d_n_cent, a.scan_state, a.d_n_cent + 8);
+                       n_leaves, a.scan_state, a.d_n_cent + kVgCntTicket);
   } else {
-    hipLaunchKernelGGL(leaf_flags_kernel, grid_for(n, 256), dim3(256), 0, s, a.keys1, n, a.flags);
-    tb = a.temp_bytes;
-    (void)rocprim::exclusive_scan(a.temp, tb, a.flags, a.pos, 0u, (size_t)n, rocprim::plus<uint32_t>(), s);
-    hipLaunchKernelGGL(leaf_heads_kernel, grid_for(n, 256), dim3(256), 0, s, a.keys1, a.vals1, a.flags, a.pos, n, a.wpts, a.spts, a.heads,
-                       a.d_n_cent);
+    launch_leaf_heads(a.keys1, a.vals1, n, a.flags, a.pos, a.wpts, a.spts, a.heads, n_leaves, a.temp, a.temp_bytes, s);
   }
-  hipLaunchKernelGGL(vg_centroid_kernel, grid_for(n, 256), dim3(256), 0, s, a.heads, a.d_n_cent, a.spts, a.d_out, a.flags, a.d_n_cent + 1,
+  hipLaunchKernelGGL(vg_centroid_kernel, grid_for(n, 256), dim3(256), 0, s, a.heads, n_leaves, a.spts, a.d_out, a.flags, a.d_n_cent + kVgCntLongLeaves,
                      const_cast<VgDecision*>(a.d_decision));
-  hipLaunchKernelGGL(vg_centroid_long_kernel, dim3(3 * kMaxLongLeaves / 4), dim3(256), 0, s, a.heads, a.spts, a.d_out, a.flags, a.d_n_cent + 1);
+  hipLaunchKernelGGL(vg_centroid_long_kernel, dim3(3 * kMaxLongLeaves / 4), dim3(256), 0, s, a.heads, a.spts, a.d_out, a.flags, a.d_n_cent + kVgCntLongLeaves);
 }
 // ---- featureExtraction::removePointDistortion (featureExtraction.cpp:223-314): SURVEY 8(f) row f4, the step that produces
 // the cloud the feature extraction (and through it this path) consumes.  One thread per point: pose of the stamped-pose
