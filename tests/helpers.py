@@ -16,6 +16,165 @@ def pose_close(a, b, tol_t=1e-4, tol_r=1e-4):
     return dt <= tol_t and dr <= tol_r, dt, dr
 
 
+TOL_T, TOL_R = 1e-4, 1e-4  # north_star: <=1e-4 m translation / <=1e-4 rad rotation
+
+# ------------------------------------------------------------------------------------------------------------------------
+# "The same registration": ONE definition for product against product (to the bit) and one for product against oracle.
+# ------------------------------------------------------------------------------------------------------------------------
+ITER_FIELDS = ("lm_iterations", "num_successful_steps", "termination", "num_surf_from_scan", "reject_hist", "obs_hist",
+               "initial_cost", "final_cost", "pose_after", "translation_norm", "rotation_norm")
+STATS_FIELDS = ("JtJ", "Jtr", "uncertainty", "pos_in_localmap", "laser_cloud_surf_from_map_num", "laser_cloud_corner_from_map_num",
+                "laser_cloud_surf_stack_num", "laser_cloud_corner_stack_num", "startup_count",
+                "total_translation", "total_rotation", "translation_from_last", "rotation_from_last")
+# What is a floating-point sum over the residuals, or follows from one: its bits follow the summation tree.  Runs that change the tree
+# (map or queries sharded over ranks) hold these to a tolerance of their own and pass this as omit=.
+SUMMED_FIELDS = ("initial_cost", "final_cost", "pose_after", "translation_norm", "rotation_norm", "JtJ", "Jtr",
+                 "total_translation", "total_rotation", "translation_from_last", "rotation_from_last")
+# What the context carries over from the call before (so_icp_ctx::prev_obs_hist, ::startup_count): equal only after equal call histories.
+CARRIED_OVER_FIELDS = ("uncertainty", "startup_count")
+
+
+def _bits(v):
+    if isinstance(v, int):
+        return v
+    if isinstance(v, float):
+        return np.float64(v).tobytes()
+    a = np.ctypeslib.as_array(v)
+    return tuple(a.tolist()) if a.dtype.kind in "iu" else a.tobytes()
+
+
+def stats_bits(st, *, omit=()):
+    """Every deterministic field of a product Stats as a tuple of (field, outer iteration or None, value) -- hashable, picklable,
+    floats by their bytes: n_iterations, per outer iteration ITER_FIELDS, then STATS_FIELDS.
+
+    Not in the set, because they describe the path taken and not the registration: time_elapsed_ms (wall clock), flags (which host
+    schedule ran: staged, binned ahead, chained, per-evaluation launches ...) and prediction_source (always written 0,
+    icp_context.cpp fill_result).  total_* and *_from_last ARE in the set: fill_result computes them from the guess and the final
+    pose of this call alone, not from earlier calls.  uncertainty and startup_count are in the set too, but come from the call
+    before (CARRIED_OVER_FIELDS): a site that compares contexts with different call histories omits them.  The reserved words and
+    num_corner_from_scan (never written: no edge features) are left out."""
+    unknown = set(omit) - set(ITER_FIELDS) - set(STATS_FIELDS)
+    assert not unknown, f"omit= names no field of the set: {sorted(unknown)}"
+    out = [("n_iterations", None, st.n_iterations)]
+    for it in range(st.n_iterations):
+        out += [(f, it, _bits(getattr(st.iterations[it], f))) for f in ITER_FIELDS if f not in omit]
+    out += [(f, None, _bits(getattr(st, f))) for f in STATS_FIELDS if f not in omit]
+    return tuple(out)
+
+
+def stats_of(res):
+    """(rc, pose, Stats) of a registration -> (rc, pose as a list, flags, stats_bits): the form a rank process sends to its parent"""
+    rc, pose, st = res
+    return rc, np.asarray(pose).tolist(), st.flags, stats_bits(st)
+
+
+def bits_field(bits, name, it=None):
+    """one field out of a stats_bits() value (floats as their bytes)"""
+    return next(v for f, i, v in bits if f == name and i == it)
+
+
+def assert_same_bits(a, b, tag, *, omit=()):
+    """Two product registrations are the same one, bit for bit.  a, b: Stats, or stats_bits() of one (what a worker process sends)."""
+    assert set(omit) <= set(ITER_FIELDS) | set(STATS_FIELDS), f"omit= names no field of the set: {sorted(set(omit) - set(ITER_FIELDS) - set(STATS_FIELDS))}"
+    a, b = [x if isinstance(x, tuple) else stats_bits(x) for x in (a, b)]
+    a, b = [tuple(e for e in x if e[0] not in omit) for x in (a, b)]
+    if a == b:
+        return
+    assert a[0] == b[0], f"{tag}: n_iterations differs: {a[0][2]} != {b[0][2]}"
+    diff = [(x[0], x[1]) for x, y in zip(a, b) if x != y]
+    f, it = diff[0]
+    x, y = [next(e[2] for e in s if e[:2] == (f, it)) for s in (a, b)]
+    x, y = [np.frombuffer(v, np.float64).tolist() if isinstance(v, bytes) else v for v in (x, y)]
+    where = "" if it is None else f" at iteration {it}"
+    raise AssertionError(f"{tag}: {f} differs{where}: {x} != {y} (every differing field: {diff})")
+
+
+def assert_rank_follows_single(a, ref, tag, *, omit=()):
+    """a, ref: stats_of() of one rank of a sharded run and of the single context.  The ranks add their partial sums in another order
+    than one context adds the whole: the float fields are held to 1e-9 through the pose ("changes the summation tree, not the
+    tolerance"), everything else to the bit."""
+    assert a[0] == ref[0] == 0, (tag, a[0], ref[0])
+    assert_same_bits(a[3], ref[3], tag, omit=SUMMED_FIELDS + tuple(omit))
+    ok, dt, dr = pose_close(np.array(a[1]), np.array(ref[1]), 1e-9, 1e-9)
+    assert ok, (tag, dt, dr)
+
+
+def assert_follows_oracle(st, ost, tag, *, pose=None, opose=None, omit=(), cost_rtol=1e-9, pose_tol=1e-8):
+    """A product Stats (or a second oracle Stats) against the oracle's for the same scan, guess and map: outer iteration count first, then per outer iteration
+    the LM iteration count, accepted steps, termination code, matched points, both histograms and the final cost (relative); with
+    the poses given, the tolerance of record and then near-machine agreement."""
+    known = ("lm_iterations", "num_successful_steps", "termination", "num_surf", "reject_hist", "obs_hist", "final_cost")
+    assert set(omit) <= set(known), f"omit= names no field of the set: {sorted(set(omit) - set(known))}"
+    assert st.n_iterations == ost.n_iterations, f"{tag}: n_iterations differs: {st.n_iterations} != {ost.n_iterations} (outer iteration counts must agree before anything else is compared)"
+    bad = []
+    for it in range(st.n_iterations):
+        a, b = (st.iterations if hasattr(st, "iterations") else st.iters)[it], ost.iters[it]
+        for f in known[:-1]:
+            x, y = getattr(a, "num_surf_from_scan" if f == "num_surf" and hasattr(a, "num_surf_from_scan") else f), getattr(b, f)
+            x, y = (x, y) if isinstance(x, int) else (list(x), list(y))
+            if f not in omit and x != y:
+                bad.append((f, it, x, y))
+        if "final_cost" not in omit and not abs(a.final_cost - b.final_cost) <= cost_rtol * max(1.0, abs(b.final_cost)):
+            bad.append(("final_cost", it, a.final_cost, b.final_cost))
+    if bad:
+        f, it, x, y = bad[0]
+        raise AssertionError(f"{tag}: {f} differs at iteration {it}: {x} != {y} (every differing field: {[e[:2] for e in bad]})")
+    if pose is not None:
+        ok, dt, dr = pose_close(pose, opose, TOL_T, TOL_R)
+        assert ok, f"{tag}: pose parity violated: dt={dt:.3e} m dr={dr:.3e} rad"
+        assert dt < pose_tol and dr < pose_tol, f"{tag}: expected near machine agreement, got {dt:.3e} {dr:.3e}"
+
+
+# ------------------------------------------------------------------------------------------------------------------------
+# Set-up shared by the parity tests.
+# ------------------------------------------------------------------------------------------------------------------------
+def scene_with_oracle(scene, oracle, make, *, oracle_too=True, **cfg):
+    """(scene, product context holding the scene's map, oracle map filled from the context's export_map() -- the canonical order, so
+    that the tie-break "earlier index first" is shared).  scene: a synth.Scene name or a scene object."""
+    sc = synth.Scene(scene) if isinstance(scene, str) else scene
+    oracle_res = {k: cfg[k] for k in ("plane_res", "line_res") if k in cfg} or dict(plane_res=sc.plane_res)  # (the oracle's own default line_res otherwise)
+    for k, v in dict(plane_res=sc.plane_res, line_res=sc.plane_res / 2, max_surface_features=-1).items():
+        cfg.setdefault(k, v)
+    slam = make(**cfg)
+    # default window (origin_ = (10,10,5), LocalMap.h:141-144): world cube 0 sits in the middle of the block array.
+    # (LocalMap::setOrigin puts the sensor's cube at index 0, which drops every negative-side cube until the
+    #  first shiftMap -- exercised in test_localization_sequence_with_map_updates.)
+    n = slam.add_surf_point_cloud(sc.map_points)
+    assert n == len(sc.map_points) == slam.map_size()
+    if not oracle_too:
+        return sc, slam, None
+    exported = slam.export_map()
+    assert len(exported) == slam.map_size()
+    om = oracle.OracleMap(**oracle_res)
+    assert om.add_surf(exported, raw=True) == len(exported)
+    return sc, slam, om
+
+
+def chain_deltas(sc, ids, *, off=None, x_off=None):
+    """Motion predictions that put guess k near sc.guess(ids[k]): gt(k-1)^-1 o guess(k) (the registration of k - 1 ends within
+    millimetres of gt).  off = {k: (dt, dth_deg)}: scan k starts that far from its ground truth instead.  x_off = {k: metres}: the
+    prediction of frame k is that far off along x."""
+    d = np.zeros((len(ids), 7)); d[:, 6] = 1.0
+    for k in range(1, len(ids)):
+        g = sc.guess(ids[k]) if off is None or k not in off else synth.perturb_pose(sc.gt_pose(ids[k]), 77 + k, *off[k])
+        d[k] = synth.pose_between(sc.gt_pose(ids[k - 1]), g)
+        if x_off and k in x_off:
+            d[k, 0] += x_off[k]
+    return d
+
+
+def run_staged_stream(slam, scans, guesses, order, step=None):
+    """The bench / node pattern: announce the next scan, register the current one.  step(k, i) replaces the plain
+    slam.register(scans[i], guesses[i]) of position k in the order."""
+    res = []
+    slam.stage_scan(scans[order[0]])
+    for k, i in enumerate(order):
+        if k + 1 < len(order):
+            slam.stage_scan(scans[order[k + 1]])
+        res.append(slam.register(scans[i], guesses[i]) if step is None else step(k, i))
+    return res
+
+
 def noisy_planes_cloud(n, rng, offset=(0.0, 0.0, 0.0), sigma=0.01):
     """Four noisy planes (floor/ceiling/2 walls) inside one 50 m cube -- the SURVEY App. D probe scene."""
     k = n // 4

@@ -11,6 +11,8 @@ import os
 import numpy as np
 import pytest
 
+from helpers import assert_follows_oracle
+
 HERE = os.path.dirname(os.path.abspath(__file__))
 FIX = np.load(os.path.join(HERE, "golden", "gate_edge.npz"))
 PLANE_RES = float(FIX["plane_res"])
@@ -65,8 +67,7 @@ def test_hip_fit_pass_agrees_with_the_oracle_at_the_gate_edges(oracle, soicp, ab
         assert np.array_equal(status[sure], expect[sure]), (b, kind[sure], margin[sure], status[sure], expect[sure])
         # against the oracle: every cluster, whatever its margin (down to ~1e-14 in this fixture)
         assert np.array_equal(status, ostatus), (b, kind, margin, status, ostatus)
-        assert list(st.iterations[0].reject_hist) == list(ost.iters[0].reject_hist)
-        assert list(st.iterations[0].obs_hist) == list(ost.iters[0].obs_hist)
+        assert_follows_oracle(st, ost, ("batch", b))
         n_tight += int((~sure).sum())
         slam.close()
     assert n_tight >= 20  # the fixture does contain margins below 1e-12

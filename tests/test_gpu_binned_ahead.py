@@ -8,6 +8,7 @@ import os
 import numpy as np
 import pytest
 
+from helpers import assert_follows_oracle, assert_same_bits, run_staged_stream, scene_with_oracle
 from superodom_amd import synth
 
 pytestmark = pytest.mark.gpu
@@ -20,31 +21,9 @@ def _chunked_sweep_for_small_scans(monkeypatch):
     monkeypatch.setenv("SOICP_QUERY_WAVES", "0")
 
 
-def _stats_tuple(st):
-    out = [st.n_iterations]
-    for it in range(st.n_iterations):
-        a = st.iterations[it]
-        out += [a.lm_iterations, a.num_successful_steps, a.termination, a.num_surf_from_scan, tuple(a.reject_hist), tuple(a.obs_hist),
-                np.float64(a.final_cost).tobytes(), np.float64(a.initial_cost).tobytes()]
-    return out
-
-
-def _run_stream(slam, scans, guesses, order):
-    """the bench / node pattern: announce the next scan, register the current one"""
-    res = []
-    slam.stage_scan(scans[order[0]])
-    for k, i in enumerate(order):
-        if k + 1 < len(order):
-            slam.stage_scan(scans[order[k + 1]])
-        res.append(slam.register(scans[i], guesses[i]))
-    return res
-
-
 @pytest.mark.parametrize("max_surface_features", [-1, 3000])
 def test_binned_ahead_bit_identical_to_plain_registration(oracle, soicp, gpu_slam_factory, max_surface_features):
-    sc = synth.Scene("small")
-    slam = gpu_slam_factory(plane_res=sc.plane_res, line_res=sc.plane_res / 2, max_surface_features=max_surface_features, max_iterations=5)
-    slam.add_surf_point_cloud(sc.map_points)
+    sc, slam, om = scene_with_oracle("small", oracle, gpu_slam_factory, max_surface_features=max_surface_features, max_iterations=5)
     n = 8
     scans = [slam.host_alloc_like(np.ascontiguousarray(sc.scan(i), dtype=np.float32)) for i in range(n)]
     guesses = [sc.guess(i) for i in range(n)]
@@ -54,7 +33,7 @@ def test_binned_ahead_bit_identical_to_plain_registration(oracle, soicp, gpu_sla
     # seven frames (1.2 m / 12 degrees: every far chunk straddles cells and cubes it was not binned for)
     n_ahead_total = 0
     for order in (list(range(n)), [0, 7, 1, 6, 2, 5, 3, 4]):
-        got = _run_stream(slam, scans, guesses, order)
+        got = run_staged_stream(slam, scans, guesses, order)
         ahead = [bool(r[2].flags & soicp.FLAG_BINNED_AHEAD) for r in got]
         # nobody was in flight to bin the first one; the others are binned by the registration before them -- unless that one took
         # more than 300 us to reach the point where it enqueues the copy (then the copy thread did, without binning: a loaded host)
@@ -64,8 +43,7 @@ def test_binned_ahead_bit_identical_to_plain_registration(oracle, soicp, gpu_sla
             rc, pose, st = got[k]
             assert rc == 0 and (st.flags & soicp.FLAG_STAGED_SCAN)
             assert np.array_equal(pose, ref[i][1]), (order, k)
-            assert np.array_equal(np.array(st.JtJ), np.array(ref[i][2].JtJ)) and np.array_equal(np.array(st.Jtr), np.array(ref[i][2].Jtr))
-            assert _stats_tuple(st) == _stats_tuple(ref[i][2]), (order, k)
+            assert_same_bits(st, ref[i][2], (order, k), omit=("uncertainty",))  # (carries over from the call before, another one here)
     # (how MANY scans were binned ahead depends on the registration thread reaching the point where it enqueues the next copy within
     #  300 us of the announcement: on a loaded host the copy thread wins and nothing is binned -- no functional bug, but then this
     #  test has not exercised the path it is about; the bit-identity asserts above are strict either way)
@@ -75,20 +53,18 @@ def test_binned_ahead_bit_identical_to_plain_registration(oracle, soicp, gpu_sla
     # outlive the scan it was built for (the slots still hold the lists of the pinned scans above, same sizes)
     pageable = [np.array(s_, dtype=np.float32, copy=True) for s_ in scans]
     order = [3, 1, 4, 0, 2, 6]
-    got = _run_stream(slam, pageable, guesses, order)
+    got = run_staged_stream(slam, pageable, guesses, order)
     for k, i in enumerate(order):
         rc, pose, st = got[k]
         assert rc == 0 and (st.flags & soicp.FLAG_STAGED_SCAN) and not (st.flags & soicp.FLAG_BINNED_AHEAD), (k, hex(st.flags))
-        assert np.array_equal(pose, ref[i][1]) and _stats_tuple(st) == _stats_tuple(ref[i][2]), ("pageable after pinned", k)
+        assert np.array_equal(pose, ref[i][1])
+        assert_same_bits(st, ref[i][2], ("pageable after pinned", k), omit=("uncertainty",))  # (carries over from the call before, another one here)
     # ... and the oracle agrees with what both paths produced
-    om = oracle.OracleMap(plane_res=sc.plane_res)
-    om.add_surf(slam.export_map(), raw=True)
     cfg = oracle.default_config(max_iterations=5, max_surface_features=max_surface_features)
     for i in (1, 6):
         orc, opose, ost, _ = om.register(np.asarray(scans[i]), guesses[i], cfg)
-        assert orc == 0 and ost.n_iterations == ref[i][2].n_iterations
-        dt, dr = synth.pose_error(ref[i][1], opose)
-        assert dt < 1e-8 and dr < 1e-8
+        assert orc == 0
+        assert_follows_oracle(ref[i][2], ost, ("plain registration", i), pose=ref[i][1], opose=opose)
 
 
 def test_binned_ahead_switch_and_pageable_buffers(soicp, gpu_slam_factory):
@@ -108,7 +84,7 @@ def test_binned_ahead_switch_and_pageable_buffers(soicp, gpu_slam_factory):
             os.environ.pop("SOICP_PREBIN", None)
         slam.add_surf_point_cloud(sc.map_points)
         scans = scans_np if mode == "pageable" else [slam.host_alloc_like(s) for s in scans_np]
-        out[mode] = _run_stream(slam, scans, guesses, [0, 1, 2, 3])
+        out[mode] = run_staged_stream(slam, scans, guesses, [0, 1, 2, 3])
         flags = [bool(r[2].flags & soicp.FLAG_BINNED_AHEAD) for r in out[mode]]
         assert (not flags[0]) if mode == "on" else flags == [False] * 4, (mode, flags)
         few_ahead = few_ahead or (mode == "on" and sum(flags) < 2)
@@ -116,7 +92,8 @@ def test_binned_ahead_switch_and_pageable_buffers(soicp, gpu_slam_factory):
     for k in range(4):
         for mode in ("off", "pageable"):
             assert out[mode][k][0] == out["on"][k][0] == 0
-            assert np.array_equal(out[mode][k][1], out["on"][k][1]) and _stats_tuple(out[mode][k][2]) == _stats_tuple(out["on"][k][2])
+            assert np.array_equal(out[mode][k][1], out["on"][k][1])
+            assert_same_bits(out[mode][k][2], out["on"][k][2], (mode, k))
     if few_ahead:
         pytest.xfail("fewer than 2 of 4 scans were binned ahead (loaded host?): the binned path was not exercised enough")
 
@@ -137,19 +114,15 @@ def test_binned_ahead_through_localization_with_map_inserts(soicp, gpu_slam_fact
             os.environ.pop("SOICP_PREBIN", None)
         slam.add_surf_point_cloud(sc.map_points[::2])  # half the map: the frames' inserts add the rest of what they see
         scans = [slam.host_alloc_like(np.ascontiguousarray(sc.scan(i), dtype=np.float32)) for i in range(6)]
-        res = []
-        slam.stage_scan(scans[0])
-        for i in range(6):
-            if i + 1 < 6:
-                slam.stage_scan(scans[i + 1])
-            res.append(slam.localization(True, sc.guess(i), scans[i], 0.1 * (i + 1)))
+        res = run_staged_stream(slam, scans, None, list(range(6)), step=lambda k, i: slam.localization(True, sc.guess(i), scans[i], 0.1 * (i + 1)))
         out[mode] = (res, slam.export_map())
         ahead = [bool(r[2].flags & soicp.FLAG_BINNED_AHEAD) for r in res]
         assert (not ahead[0]) if mode == "on" else ahead == [False] * 6, (mode, ahead)
         few_on = few_on or (mode == "on" and sum(ahead) < 3)
         slam.close()
-    for a, b in zip(out["on"][0], out["off"][0]):
-        assert a[0] == b[0] and np.array_equal(a[1], b[1]) and _stats_tuple(a[2]) == _stats_tuple(b[2])
+    for k, (a, b) in enumerate(zip(out["on"][0], out["off"][0])):
+        assert a[0] == b[0] and np.array_equal(a[1], b[1])
+        assert_same_bits(a[2], b[2], ("frame", k))
     assert np.array_equal(out["on"][1], out["off"][1])
     if few_on:
         pytest.xfail("fewer than 3 of 6 frames were binned ahead (loaded host?): the binned path was not exercised enough")

@@ -11,40 +11,16 @@ import os
 import numpy as np
 import pytest
 
-from helpers import pose_close
+from helpers import (SUMMED_FIELDS, assert_follows_oracle, assert_same_bits, in_threads, pose_close, run_staged_stream, scene_with_oracle)
 from superodom_amd import synth
 
 pytestmark = pytest.mark.gpu
-TOL_T, TOL_R = 1e-4, 1e-4  # north_star
-
-
-def _setup(scene_name, oracle, make, **cfg):
-    sc = synth.Scene(scene_name)
-    slam = make(plane_res=sc.plane_res, line_res=sc.plane_res / 2, max_surface_features=-1, **cfg)
-    assert slam.add_surf_point_cloud(sc.map_points) == len(sc.map_points) == slam.map_size()
-    om = oracle.OracleMap(plane_res=sc.plane_res)
-    assert om.add_surf(slam.export_map(), raw=True) == slam.map_size()
-    return sc, slam, om
-
-
-def _assert_registration_equal(st, ost, pose, opose, tag):
-    assert st.n_iterations == ost.n_iterations, (tag, "outer iteration counts must agree before poses are compared")
-    for it in range(st.n_iterations):
-        a, b = st.iterations[it], ost.iters[it]
-        assert (a.lm_iterations, a.num_successful_steps, a.termination) == (b.lm_iterations, b.num_successful_steps, b.termination), (tag, it)
-        assert a.num_surf_from_scan == b.num_surf, (tag, it)
-        assert list(a.reject_hist) == list(b.reject_hist), (tag, it)
-        assert list(a.obs_hist) == list(b.obs_hist), (tag, it)
-        assert abs(a.final_cost - b.final_cost) <= 1e-9 * max(1.0, abs(b.final_cost)), (tag, it)
-    ok, dt, dr = pose_close(pose, opose, TOL_T, TOL_R)
-    assert ok, f"{tag}: pose parity violated: dt={dt:.3e} m dr={dr:.3e} rad"
-    assert dt < 1e-8 and dr < 1e-8, f"{tag}: expected near machine agreement, got {dt:.3e} {dr:.3e}"
 
 
 def test_config1_seam_b_every_query_bit_exact(oracle, gpu_slam_factory):
     """BASELINE configs[1]: the 16 x 1800 = 28 800 world-frame queries of a scan against the 200 000-point map through
     so_icp_knn_surf -- found flags, neighbour coordinates and d2 bit-identical to the CPU restatement for EVERY query."""
-    sc, slam, om = _setup("vlp16_200k", oracle, gpu_slam_factory)
+    sc, slam, om = scene_with_oracle("vlp16_200k", oracle, gpu_slam_factory)
     assert slam.map_size() == 200_000
     for i in (0, 13):
         gt = sc.gt_pose(i)
@@ -62,7 +38,7 @@ def test_config1_seam_b_every_query_bit_exact(oracle, gpu_slam_factory):
 @pytest.mark.parametrize("scene", ["small", "vlp16_200k"])
 def test_all_32_seeded_scans_of_the_trajectory(oracle, gpu_slam_factory, scene):
     """seeds world=1, map-noise=2, scan-noise=3+i, guess=1000+i for the 32 scans of the trajectory."""
-    sc, slam, om = _setup(scene, oracle, gpu_slam_factory, max_iterations=5)
+    sc, slam, om = scene_with_oracle(scene, oracle, gpu_slam_factory, max_iterations=5)
     cfg = oracle.default_config(max_iterations=5)
     outer = []
     for i in range(32):
@@ -70,7 +46,7 @@ def test_all_32_seeded_scans_of_the_trajectory(oracle, gpu_slam_factory, scene):
         rc, pose, st = slam.register(scan, guess)
         orc, opose, ost, corrs = om.register(scan, guess, cfg, want_corrs=True)
         assert rc == orc == 0, (scene, i)
-        _assert_registration_equal(st, ost, pose, opose, (scene, i))
+        assert_follows_oracle(st, ost, (scene, i), pose=pose, opose=opose)
         # per-query MatchingResult of the last outer iteration: the accepted sets are the SAME set (Jaccard 1), not just equally large
         assert np.array_equal(slam.match_status(len(scan)), corrs["status"].astype(np.uint8)), (scene, i)
         e = synth.pose_error(pose, gt)
@@ -83,7 +59,7 @@ def test_batch64_full_size_with_the_survey_seeds(oracle, gpu_slam_factory):
     """BASELINE configs[4] / SURVEY 8(d) "batched": 64 guesses per scan, dt ~ U(-0.5, 0.5) m, dtheta ~ U(-5, 5) deg per axis,
     seeds 5000 + 64 i + h, at the full size (131 072-point scan, 2M-point map).  Every hypothesis returns; a sample of them
     (the oracle needs ~1 s per full-size hypothesis on all host cores) is compared with the oracle in full."""
-    sc, slam, om = _setup("os1_128_2m", oracle, gpu_slam_factory, max_iterations=5)
+    sc, slam, om = scene_with_oracle("os1_128_2m", oracle, gpu_slam_factory, max_iterations=5)
     i = 1
     scan = sc.scan(i)
     poses = np.stack([synth.perturb_pose(sc.gt_pose(i), 5000 + 64 * i + h, 0.5, 5.0) for h in range(64)])
@@ -97,7 +73,7 @@ def test_batch64_full_size_with_the_survey_seeds(oracle, gpu_slam_factory):
         for h in (0, 21, 42, 63):
             orc, opose, ost, _ = om.register(scan, poses[h], oracle.default_config(max_iterations=5))
             assert orc == 0
-            _assert_registration_equal(sts[h], ost, out[h], opose, ("batch64", h))
+            assert_follows_oracle(sts[h], ost, ("batch64", h), pose=out[h], opose=opose)
     finally:
         oracle.set_num_threads(1)
     # the batch is B independent registrations: EVERY hypothesis alone gives the same bits (pose, final normal equations,
@@ -105,19 +81,7 @@ def test_batch64_full_size_with_the_survey_seeds(oracle, gpu_slam_factory):
     for h in range(64):
         rc, ph, sh = slam.register_dev(d, n, poses[h])
         assert rc == 0 and np.array_equal(ph, out[h]), h
-        _assert_same_bits(sts[h], sh, ("batch64 vs single", h))
-
-
-def _assert_same_bits(a, b, tag):
-    assert a.n_iterations == b.n_iterations, tag
-    assert np.array_equal(np.array(a.JtJ), np.array(b.JtJ)) and np.array_equal(np.array(a.Jtr), np.array(b.Jtr)), tag
-    for it in range(a.n_iterations):
-        x, y = a.iterations[it], b.iterations[it]
-        assert (x.lm_iterations, x.num_successful_steps, x.termination, x.num_surf_from_scan) == \
-               (y.lm_iterations, y.num_successful_steps, y.termination, y.num_surf_from_scan), (tag, it)
-        assert list(x.reject_hist) == list(y.reject_hist) and list(x.obs_hist) == list(y.obs_hist), (tag, it)
-        assert (x.initial_cost, x.final_cost) == (y.initial_cost, y.final_cost), (tag, it)
-        assert np.array_equal(np.array(x.pose_after), np.array(y.pose_after)), (tag, it)
+        assert_same_bits(sts[h], sh, ("batch64 vs single", h), omit=("uncertainty",))  # (from the call before: the single ones advance it)
 
 
 @pytest.mark.parametrize("scene,n_hyp,sub", [("tiny", 5, None), ("tiny", 70, None), ("small", 33, None), ("small", 9, 1500)])
@@ -127,7 +91,7 @@ def test_batched_hypotheses_equal_single_registrations_bit_for_bit(oracle, gpu_s
     (tiny: 16 workgroups), a sub-sampled scan (max_surface_features), hypotheses that converge in different rounds and
     hypotheses that start far away.  Every hypothesis must equal its single registration bit for bit; a sample is compared
     with the oracle in full."""
-    sc, slam, om = _setup(scene, oracle, gpu_slam_factory, max_iterations=5)
+    sc, slam, om = scene_with_oracle(scene, oracle, gpu_slam_factory, max_iterations=5)
     if sub:
         slam.set_max_surface_features(sub)
     i = 2
@@ -140,7 +104,7 @@ def test_batched_hypotheses_equal_single_registrations_bit_for_bit(oracle, gpu_s
     for h in range(n_hyp):
         rc, ph, sh = slam.register_dev(d, n, poses[h])
         assert rc == 0 and np.array_equal(ph, out[h]), (scene, h)
-        _assert_same_bits(sts[h], sh, (scene, h))
+        assert_same_bits(sts[h], sh, (scene, h), omit=("uncertainty",))  # (from the call before: the single ones advance it)
         outer.add(sh.n_iterations)
     if n_hyp >= 33:
         assert len(outer) >= 2, "the hypotheses should leave the rounds at different times"
@@ -148,7 +112,7 @@ def test_batched_hypotheses_equal_single_registrations_bit_for_bit(oracle, gpu_s
     for h in (0, n_hyp // 2, n_hyp - 1):
         orc, opose, ost, _ = om.register(scan, poses[h], cfg)
         assert orc == 0
-        _assert_registration_equal(sts[h], ost, out[h], opose, (scene, "batch", h))
+        assert_follows_oracle(sts[h], ost, (scene, "batch", h), pose=out[h], opose=opose)
     # a host scan buffer instead of a resident one; and a batch of one
     ok2, _, out2, _ = slam.register_batch(scan, poses[:3])
     assert ok2 == 3 and np.array_equal(out2, out[:3])
@@ -162,7 +126,7 @@ def test_batch_with_hypotheses_that_fail_and_degenerate_inputs(oracle, gpu_slam_
     duplicates of one guess, next to ordinary ones -- each must carry the status, the pose and the statistics of its single
     registration.  Then an EMPTY map (every hypothesis SO_ICP_NOT_ENOUGH_MAP_FEATURES, pose = guess, LS.cpp:113-116), a
     batch of zero hypotheses and an empty scan."""
-    sc, slam, _ = _setup("small", oracle, gpu_slam_factory, max_iterations=5)
+    sc, slam, _ = scene_with_oracle("small", oracle, gpu_slam_factory, max_iterations=5)
     i = 4
     scan = sc.scan(i)
     gt = sc.gt_pose(i)
@@ -179,7 +143,7 @@ def test_batch_with_hypotheses_that_fail_and_degenerate_inputs(oracle, gpu_slam_
     assert ok == sum(1 for r in singles if r[0] == 0) >= 4
     for h, (rc, ph, sh) in enumerate(singles):
         assert np.array_equal(out[h], ph), h
-        _assert_same_bits(sts[h], sh, ("mixed batch", h))
+        assert_same_bits(sts[h], sh, ("mixed batch", h), omit=("uncertainty",))  # (from the call before: the single ones advance it)
     assert np.array_equal(out[0], out[4])
     # empty map
     empty = gpu_slam_factory(plane_res=sc.plane_res, line_res=sc.plane_res / 2, max_surface_features=-1, max_iterations=5)
@@ -201,7 +165,7 @@ def test_batch_fallback_paths_give_the_same_bits(oracle, gpu_slam_factory, monke
     poses of the batched kernels bit for bit; so do the rounds with a report + synchronisation after every one of them
     (SOICP_BATCH_CHAIN=0) against the chained rounds, whose lists go stale (second batch of a context: chained by the
     survivor counts of the first)."""
-    sc, slam, _ = _setup("small", oracle, gpu_slam_factory, max_iterations=5)
+    sc, slam, _ = scene_with_oracle("small", oracle, gpu_slam_factory, max_iterations=5)
     scan = sc.scan(6)
     poses = np.stack([synth.perturb_pose(sc.gt_pose(6), 9000 + h, 0.05 + 0.4 * (h % 5) / 4.0, 0.5 + 4.0 * (h % 3) / 2.0) for h in range(19)])
     ok, rcs, out, sts = slam.register_batch(scan, poses)
@@ -209,14 +173,14 @@ def test_batch_fallback_paths_give_the_same_bits(oracle, gpu_slam_factory, monke
     ok1, _, out1, sts1 = slam.register_batch(scan, poses)  # (chained further, by what the first batch saw)
     assert ok1 == 19 and np.array_equal(out1, out)
     for h in range(19):
-        _assert_same_bits(sts[h], sts1[h], ("second batch", h))
+        assert_same_bits(sts[h], sts1[h], ("second batch", h))
     for k, v in env.items():
         monkeypatch.setenv(k, v)  # read by so_icp_create
-    _, alt, _ = _setup("small", oracle, gpu_slam_factory, max_iterations=5)
+    _, alt, _ = scene_with_oracle("small", oracle, gpu_slam_factory, max_iterations=5)
     ok2, rcs2, out2, sts2 = alt.register_batch(scan, poses)
     assert ok2 == 19 and np.array_equal(out2, out)
     for h in range(19):
-        _assert_same_bits(sts[h], sts2[h], (env, h))
+        assert_same_bits(sts[h], sts2[h], (env, h))
 
 
 @pytest.mark.parametrize("buffers", ["pageable", "registered", "pinned"])
@@ -225,7 +189,7 @@ def test_staged_scan_is_the_same_registration(oracle, gpu_slam_factory, soicp, b
     from the caller's buffer (so_icp_host_register / so_icp_host_alloc), enqueued by the registration in flight -- feeds the same
     kernels: bit-identical results, the stats say which path ran; a staged scan that is never consumed and a re-staged one are
     handled; so_icp_stage_cancel withdraws a copy."""
-    sc, slam, om = _setup("small", oracle, gpu_slam_factory, max_iterations=5)
+    sc, slam, om = scene_with_oracle("small", oracle, gpu_slam_factory, max_iterations=5)
     scans = [np.ascontiguousarray(sc.scan(i), dtype=np.float32) for i in range(4)]
     if buffers == "registered":
         for s_ in scans:
@@ -234,13 +198,10 @@ def test_staged_scan_is_the_same_registration(oracle, gpu_slam_factory, soicp, b
         scans = [slam.host_alloc_like(s_) for s_ in scans]
     ref = [slam.register(scans[i], sc.guess(i)) for i in range(4)]
     assert all(not (r[2].flags & soicp.FLAG_STAGED_SCAN) for r in ref)
-    slam.stage_scan(scans[0])
-    for i in range(4):  # the pattern of the bench loop: announce i + 1, register i
-        if i + 1 < 4:
-            slam.stage_scan(scans[i + 1])
-        rc, pose, st = slam.register(scans[i], sc.guess(i))
+    for i, (rc, pose, st) in enumerate(run_staged_stream(slam, scans, [sc.guess(i) for i in range(4)], list(range(4)))):
         assert rc == 0 and (st.flags & soicp.FLAG_STAGED_SCAN)
-        assert np.array_equal(pose, ref[i][1]) and np.array_equal(np.array(st.JtJ), np.array(ref[i][2].JtJ))
+        assert np.array_equal(pose, ref[i][1])
+        assert_same_bits(st, ref[i][2], ("staged", i), omit=("uncertainty",))  # (from the call before: ref[0] had none)
     slam.stage_scan(scans[2])            # staged, then a DIFFERENT scan is registered: plain upload, staged copy ignored
     rc, pose, st = slam.register(scans[3], sc.guess(3))
     assert rc == 0 and not (st.flags & soicp.FLAG_STAGED_SCAN) and np.array_equal(pose, ref[3][1])
@@ -276,7 +237,8 @@ def test_staged_scan_is_the_same_registration(oracle, gpu_slam_factory, soicp, b
     staged = 0
     for k in order:
         rc, pose, st = slam.register(scans[k], sc.guess(k))
-        assert rc == 0 and np.array_equal(pose, ref[k][1]) and np.array_equal(np.array(st.JtJ), np.array(ref[k][2].JtJ)), k
+        assert rc == 0 and np.array_equal(pose, ref[k][1]), k
+        assert_same_bits(st, ref[k][2], ("feeder thread", k), omit=("uncertainty",))  # (from the call before, another one here)
         staged += 1 if (st.flags & soicp.FLAG_STAGED_SCAN) else 0
     th.join(30)
     assert staged >= 1
@@ -293,7 +255,7 @@ def test_staged_scan_is_the_same_registration(oracle, gpu_slam_factory, soicp, b
 
 
 def test_stats_flags_name_the_degraded_modes(oracle, gpu_slam_factory, soicp, monkeypatch):
-    sc, slam, _ = _setup("tiny", oracle, gpu_slam_factory, max_iterations=3)
+    sc, slam, _ = scene_with_oracle("tiny", oracle, gpu_slam_factory, max_iterations=3)
     scan, guess = sc.scan(0), sc.guess(0)
     rc, pose0, st = slam.register(scan, guess)
     QW = soicp.FLAG_QUERY_WAVES  # (a 4 096-point scan: one wavefront per query, no binning -- not a degraded mode, tests/test_gpu_query_waves.py)
@@ -302,15 +264,16 @@ def test_stats_flags_name_the_degraded_modes(oracle, gpu_slam_factory, soicp, mo
                       ({"SOICP_HOST_MAP": "1"}, soicp.FLAG_HOST_MAP), ({"SOICP_READBACK": "copy"}, soicp.FLAG_COPY_READBACK)):
         for k, v in env.items():
             monkeypatch.setenv(k, v)
-        _, alt, _ = _setup("tiny", oracle, gpu_slam_factory, max_iterations=3)
+        _, alt, _ = scene_with_oracle("tiny", oracle, gpu_slam_factory, max_iterations=3)
         rc, pose2, s2 = alt.register(scan, guess)
         assert rc == 0 and s2.flags == (flag | QW), (env, hex(s2.flags))
-        assert np.array_equal(pose2, pose0) and np.array_equal(np.array(s2.JtJ), np.array(st.JtJ)), (env, "a degraded mode is the same registration, bit for bit")
+        assert np.array_equal(pose2, pose0), (env, "a degraded mode is the same registration, bit for bit")
+        assert_same_bits(s2, st, env)
         for k in env:
             monkeypatch.delenv(k)
     # an abandoned persistent solve (test hook): the repeated registration is flagged, later ones carry the degraded mode
     monkeypatch.setenv("SOICP_ABLATE", "8192")
-    _, alt, _ = _setup("tiny", oracle, gpu_slam_factory, max_iterations=3)
+    _, alt, _ = scene_with_oracle("tiny", oracle, gpu_slam_factory, max_iterations=3)
     rc, _, s3 = alt.register(scan, guess)
     assert rc == 0 and s3.flags == (soicp.FLAG_RETRIED | soicp.FLAG_PER_EVAL_LAUNCHES), hex(s3.flags)
     rc, _, s4 = alt.register(scan, guess)
@@ -348,7 +311,7 @@ def test_resolution_change_keeps_the_points_until_their_cube_is_touched(oracle, 
         orc, opose, ost, _ = om2.register(sc.scan(1), sc.guess(1), oracle.default_config(max_iterations=3))
         assert rc == orc
         if rc == 0:
-            _assert_registration_equal(st, ost, pose, opose, ("resolution", res))
+            assert_follows_oracle(st, ost, ("resolution", res), pose=pose, opose=opose)
     # the next insert re-filters the touched cubes at the resolution in effect (0.8): product and oracle agree point for point
     gt = sc.gt_pose(2)
     w = (sc.scan(2) @ synth.quat_to_R(gt[3:]).T + gt[:3]).astype(np.float32)
@@ -383,11 +346,11 @@ def test_plane_res_change_recuts_the_shards(oracle, gpu_slam_factory, soicp):
     for sh in shards:
         sh.comm_init_inprocess(0x4E5)
     one.add_surf_point_cloud(sc.map_points)
-    _in_threads([lambda sh=sh: sh.add_surf_point_cloud(sc.map_points) for sh in shards])
+    in_threads(3, lambda r: shards[r].add_surf_point_cloud(sc.map_points), 180)
     key = lambda a: {tuple(v) for v in a.view(np.uint32).reshape(-1, 3).tolist()}
     for res in (0.4, 0.2, 0.4):
         one.set_resolution(res / 2, res)
-        _in_threads([lambda sh=sh: (sh.set_resolution(res / 2, res), True)[1] for sh in shards])
+        in_threads(3, lambda r: (shards[r].set_resolution(res / 2, res), True)[1], 180)
         full = one.export_map(); kfull = key(full); union = set()
         for sh in shards:
             total, mine = sh.map_size(this_rank=True)
@@ -399,21 +362,17 @@ def test_plane_res_change_recuts_the_shards(oracle, gpu_slam_factory, soicp):
         for i in (2, 9):
             scan, guess = sc.scan(i), sc.guess(i, dt=0.3, dth_deg=2.0)
             rc, pose, st = one.register(scan, guess)
-            out = _in_threads([lambda sh=sh: sh.register(scan, guess) for sh in shards])
+            out = in_threads(3, lambda r: shards[r].register(scan, guess), 180)
             assert all(r[0] == rc == 0 for r in out) and all(np.array_equal(out[0][1], r[1]) for r in out)
             for r in out:
-                assert r[2].n_iterations == st.n_iterations
-                for it in range(st.n_iterations):
-                    a, b = r[2].iterations[it], st.iterations[it]
-                    assert (a.lm_iterations, a.termination, a.num_surf_from_scan) == (b.lm_iterations, b.termination, b.num_surf_from_scan), (res, i, it)
-                    assert list(a.reject_hist) == list(b.reject_hist) and list(a.obs_hist) == list(b.obs_hist)
+                assert_same_bits(r[2], st, (res, i), omit=SUMMED_FIELDS)  # (three shards: another summation tree; the pose to 1e-9 below)
                 ok, dt, dr = pose_close(r[1], pose, 1e-9, 1e-9)
                 assert ok, (res, i, dt, dr)
         # an insert on the new grid: the touched cubes are re-filtered, shard by shard, like the whole map
         gt = sc.gt_pose(4)
         w = (sc.scan(4) @ synth.quat_to_R(gt[3:]).T + gt[:3]).astype(np.float32)
         n1 = one.add_surf_point_cloud(w)
-        assert [r for r in _in_threads([lambda sh=sh: sh.add_surf_point_cloud(w) for sh in shards])] == [n1] * 3
+        assert in_threads(3, lambda r: shards[r].add_surf_point_cloud(w), 180) == [n1] * 3
         full = one.export_map(); kfull = key(full); union = set()
         for sh in shards:
             part = sh.export_map()
@@ -431,8 +390,7 @@ def test_two_shard_ranks_follow_the_queries_across_outer_iterations(oracle, gpu_
     (ADVICE r01, high).  Two shard contexts on this one GPU, each driven from its own thread and joined by an in-process
     group (the sums take the place of the RCCL all-reduce): every iteration's histograms, iteration counts and termination
     codes must equal the single-context registration and the oracle; the poses agree to the last bits."""
-    import threading
-    sc, full, om = _setup("small", oracle, gpu_slam_factory, max_iterations=5)
+    sc, full, om = scene_with_oracle("small", oracle, gpu_slam_factory, max_iterations=5)
     shards = []
     key = 0x5151
     for rank in (0, 1):
@@ -445,45 +403,19 @@ def test_two_shard_ranks_follow_the_queries_across_outer_iterations(oracle, gpu_
         rc, pose, st = full.register(scan, guess)
         orc, opose, ost, _ = om.register(scan, guess, oracle.default_config(max_iterations=5))
         assert rc == orc == 0
-        _assert_registration_equal(st, ost, pose, opose, ("single context", i))
+        assert_follows_oracle(st, ost, ("single context", i), pose=pose, opose=opose)
         if i == 3:
             assert st.n_iterations >= 3, "the test needs several outer iterations"
-        res = [None, None]
-
-        def run(r):
-            res[r] = shards[r].register(scan, guess)
-        th = [threading.Thread(target=run, args=(r,)) for r in (0, 1)]
-        for t in th:
-            t.start()
-        for t in th:
-            t.join(120)
-        assert all(r is not None and r[0] == 0 for r in res), [None if r is None else r[0] for r in res]
+        res = in_threads(2, lambda r: shards[r].register(scan, guess), 120)
+        assert all(r[0] == 0 for r in res), [r[0] for r in res]
         assert np.array_equal(res[0][1], res[1][1]), "both ranks must take identical decisions on identical sums"
         for r in (0, 1):
-            s2 = res[r][2]
-            assert s2.n_iterations == st.n_iterations
-            for it in range(st.n_iterations):
-                a, b = s2.iterations[it], st.iterations[it]
-                assert (a.lm_iterations, a.num_successful_steps, a.termination, a.num_surf_from_scan) == \
-                       (b.lm_iterations, b.num_successful_steps, b.termination, b.num_surf_from_scan), (r, it)
-                assert list(a.reject_hist) == list(b.reject_hist) and list(a.obs_hist) == list(b.obs_hist), (r, it)
+            # (two shards: another summation tree, the pose to 1e-9 below; they were filled before the group existed, so that no
+            #  collective summed the map counts: each rank reports the count of its own shard (seen on the device: 59 985 on rank 0 against the
+            #  single context's 120 000); test_gpu_multi.py adds the ranks' counts up)
+            assert_same_bits(res[r][2], st, ("shard rank", r, i), omit=SUMMED_FIELDS + ("laser_cloud_surf_from_map_num",))
             ok, dt, dr = pose_close(res[r][1], pose, 1e-9, 1e-9)
             assert ok, (r, dt, dr)
-
-
-def _in_threads(fns):
-    import threading
-    res = [None] * len(fns)
-
-    def run(k):
-        res[k] = fns[k]()
-    th = [threading.Thread(target=run, args=(k,)) for k in range(len(fns))]
-    for t in th:
-        t.start()
-    for t in th:
-        t.join(180)
-    assert all(r is not None for r in res), "a shard rank did not return"
-    return res
 
 
 def test_sharded_localization_keeps_the_shard_resident_and_exact(oracle, gpu_slam_factory):
@@ -499,21 +431,18 @@ def test_sharded_localization_keeps_the_shard_resident_and_exact(oracle, gpu_sla
         sh.comm_init_inprocess(0x7A7A)
     T0 = sc.gt_pose(0)
     assert one.localization(False, T0, sc.scan(0), 0.0)[0] == 2
-    assert [r[0] for r in _in_threads([lambda sh=sh: sh.localization(False, T0, sc.scan(0), 0.0) for sh in shards])] == [2, 2]
+    assert [r[0] for r in in_threads(2, lambda r: shards[r].localization(False, T0, sc.scan(0), 0.0), 180)] == [2, 2]
     n_ok = 0
     for i in range(1, 5):
         scan, guess = sc.scan(i), sc.guess(i)
         rc, pose, st = one.localization(True, guess, scan, 0.1 * i)
-        res = _in_threads([lambda sh=sh: sh.localization(True, guess, scan, 0.1 * i) for sh in shards])
+        res = in_threads(2, lambda r: shards[r].localization(True, guess, scan, 0.1 * i), 180)
         assert [r[0] for r in res] == [rc, rc]
         assert np.array_equal(res[0][1], res[1][1])
         if rc == 0:
             n_ok += 1
             for r in res:
-                assert r[2].n_iterations == st.n_iterations and r[2].laser_cloud_surf_from_map_num == st.laser_cloud_surf_from_map_num
-                for it in range(st.n_iterations):
-                    assert list(r[2].iterations[it].reject_hist) == list(st.iterations[it].reject_hist)
-                    assert list(r[2].iterations[it].obs_hist) == list(st.iterations[it].obs_hist)
+                assert_same_bits(r[2], st, ("sharded frame", i), omit=SUMMED_FIELDS)  # (two shards: another summation tree; the pose to 1e-9 below)
                 ok, dt, dr = pose_close(r[1], pose, 1e-9, 1e-9)
                 assert ok, (i, dt, dr)
         full = one.export_map()

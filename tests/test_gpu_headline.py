@@ -9,39 +9,22 @@ closing the gaps VERDICT r02 names under "Parity is partial" (ii)-(iv):
       shared with the checker -- d2 must still be bit-identical and the neighbour sets equal, ties at the k-th distance aside
       [LocalMap.h:481-525, octree.h:93-102]"""
 import os
-import threading
 
 import numpy as np
 import pytest
 
-from helpers import pose_close
+from helpers import SUMMED_FIELDS, assert_follows_oracle, assert_same_bits, in_threads, pose_close, scene_with_oracle
 from superodom_amd import synth
 
 pytestmark = pytest.mark.gpu
-TOL_T, TOL_R = 1e-4, 1e-4  # north_star
 
 
 @pytest.fixture(scope="module")
 def headline(oracle, gpu_slam_factory):
-    sc = synth.Scene("os1_128_2m")
-    slam = gpu_slam_factory(plane_res=sc.plane_res, line_res=sc.plane_res / 2, max_surface_features=-1, max_iterations=5)
-    assert slam.add_surf_point_cloud(sc.map_points) == 2_000_000 == slam.map_size()
-    exported = slam.export_map()
-    om = oracle.OracleMap(plane_res=sc.plane_res)
-    assert om.add_surf(exported, raw=True) == len(exported)
+    sc, slam, om = scene_with_oracle("os1_128_2m", oracle, gpu_slam_factory, max_iterations=5)
+    assert slam.map_size() == 2_000_000
     om.ensure_grids()
-    return sc, slam, om, exported
-
-
-def _equal_stats(st, ost, tag):
-    assert st.n_iterations == ost.n_iterations, (tag, st.n_iterations, ost.n_iterations)
-    for it in range(st.n_iterations):
-        a, b = st.iterations[it], ost.iters[it]
-        assert (a.lm_iterations, a.num_successful_steps, a.termination) == (b.lm_iterations, b.num_successful_steps, b.termination), (tag, it)
-        assert a.num_surf_from_scan == b.num_surf, (tag, it)
-        assert list(a.reject_hist) == list(b.reject_hist), (tag, it)
-        assert list(a.obs_hist) == list(b.obs_hist), (tag, it)
-        assert abs(a.final_cost - b.final_cost) <= 1e-9 * max(1.0, abs(b.final_cost)), (tag, it)
+    return sc, slam, om, slam.export_map()
 
 
 def test_all_32_headline_scans_against_oracle_a(oracle, headline):
@@ -57,15 +40,14 @@ def test_all_32_headline_scans_against_oracle_a(oracle, headline):
             rc, pose, st = slam.register(scan, guess)
             orc, opose, ost, corrs = om.register(scan, guess, cfg, want_corrs=True)
             assert rc == orc == 0, i
-            _equal_stats(st, ost, ("os1_128_2m", i))
+            assert_follows_oracle(st, ost, ("os1_128_2m", i), pose=pose, opose=opose)
             status = slam.match_status(len(scan))
             ostatus = corrs["status"].astype(np.uint8)
             acc, oacc = status == 0, ostatus == 0
             union = int((acc | oacc).sum())
             assert union > 30_000 and int((acc & oacc).sum()) == union, ("accepted-set Jaccard must be 1.0", i)
             assert np.array_equal(status, ostatus), ("per-query MatchingResult", i)
-            ok, dt, dr = pose_close(pose, opose, TOL_T, TOL_R)
-            assert ok and dt < 1e-8 and dr < 1e-8, (i, dt, dr)
+            dt, dr = synth.pose_error(pose, opose)
             worst = [max(worst[0], dt), max(worst[1], dr)]
             e = synth.pose_error(pose, gt)
             assert e[0] < 0.02 and e[1] < 0.004, (i, e)
@@ -94,25 +76,14 @@ def test_two_shard_ranks_on_the_headline_scene(oracle, gpu_slam_factory, headlin
         scan, guess = sc.scan(i), sc.guess(i)
         rc, pose, st = full.register(scan, guess)
         assert rc == 0
-        res = [None, None]
-
-        def run(r):
-            res[r] = shards[r].register(scan, guess)
-        th = [threading.Thread(target=run, args=(r,)) for r in (0, 1)]
-        for t in th:
-            t.start()
-        for t in th:
-            t.join(300)
-        assert all(r is not None and r[0] == 0 for r in res)
+        res = in_threads(2, lambda r: shards[r].register(scan, guess), 300)
+        assert all(r[0] == 0 for r in res)
         assert np.array_equal(res[0][1], res[1][1]), "identical sums, identical decisions, identical bits on both ranks"
         for r in (0, 1):
-            s2 = res[r][2]
-            assert s2.n_iterations == st.n_iterations
-            for it in range(st.n_iterations):
-                a, b = s2.iterations[it], st.iterations[it]
-                assert (a.lm_iterations, a.num_successful_steps, a.termination, a.num_surf_from_scan) == \
-                       (b.lm_iterations, b.num_successful_steps, b.termination, b.num_surf_from_scan), (i, r, it)
-                assert list(a.reject_hist) == list(b.reject_hist) and list(a.obs_hist) == list(b.obs_hist), (i, r, it)
+            # (two shards: another summation tree, the pose to 1e-9 below; the module's context has registered other scans before;
+            #  the shards were filled before the group existed, so that each rank reports the map count of its own shard, as
+            #  seen on the device in test_gpu_configs.py's two-shard test: 59 985 against 120 000)
+            assert_same_bits(res[r][2], st, ("shard rank", r, i), omit=SUMMED_FIELDS + ("uncertainty", "laser_cloud_surf_from_map_num"))
             ok, dt, dr = pose_close(res[r][1], pose, 1e-9, 1e-9)
             assert ok, (i, r, dt, dr)
     for sh in shards:

@@ -9,41 +9,16 @@ import os
 import numpy as np
 import pytest
 
+from helpers import assert_follows_oracle, assert_same_bits, chain_deltas, scene_with_oracle
 from superodom_amd import synth
 
 pytestmark = pytest.mark.gpu
 
 
-def _stats_tuple(st):
-    out = [st.n_iterations]
-    for it in range(st.n_iterations):
-        a = st.iterations[it]
-        out += [a.lm_iterations, a.num_successful_steps, a.termination, a.num_surf_from_scan, tuple(a.reject_hist), tuple(a.obs_hist),
-                np.float64(a.final_cost).tobytes(), np.float64(a.initial_cost).tobytes(), np.array(a.pose_after).tobytes()]
-    out += [np.array(st.JtJ).tobytes(), np.array(st.Jtr).tobytes(), tuple(st.pos_in_localmap), st.laser_cloud_surf_from_map_num,
-            st.laser_cloud_surf_stack_num, np.array(st.uncertainty).tobytes(), st.startup_count]
-    return out
-
-
-def _deltas(sc, ids, off=None):
-    """motion predictions that put guess k near sc.guess(ids[k]); off[k] = (x metres): frame k's prediction is that far off"""
-    d = np.zeros((len(ids), 7)); d[:, 6] = 1.0
-    for k in range(1, len(ids)):
-        d[k] = synth.pose_between(sc.gt_pose(ids[k - 1]), sc.guess(ids[k]))
-        if off and k in off:
-            d[k, 0] += off[k]
-    return d
-
-
 def _contexts(factory, sc, n=2, **kw):
-    mk = dict(plane_res=sc.plane_res, line_res=sc.plane_res / 2, max_surface_features=-1, max_iterations=5)
-    mk.update(kw)
-    out = []
-    for _ in range(n):
-        s = factory(**mk)
-        s.add_surf_point_cloud(sc.map_points)
+    out = [scene_with_oracle(sc, None, factory, oracle_too=False, **dict(dict(max_iterations=5), **kw))[1] for _ in range(n)]
+    for s in out:
         s.shift_map(sc.gt_pose(0)[:3])
-        out.append(s)
     return out
 
 
@@ -74,7 +49,7 @@ def _assert_run_matches(res, ref, pose0, deltas):
         assert np.array_equal(guesses[k], synth.pose_compose(poses[k - 1], deltas[k])), k
     assert np.array_equal(poses[:n_done], rposes), "poses differ from the per-frame loop"
     for k in range(n_done):
-        assert _stats_tuple(stats[k]) == _stats_tuple(rstats[k]), k
+        assert_same_bits(stats[k], rstats[k], ("frame", k))
 
 
 @pytest.mark.parametrize("scene,n_frames,pinned", [("small", 9, True), ("tiny", 9, False), ("os1_128_2m", 8, True)])
@@ -84,7 +59,7 @@ def test_sequence_equals_the_per_frame_loop_including_the_map(gpu_slam_factory, 
     ids = list(range(n_frames))
     host = [np.ascontiguousarray(sc.scan(i), dtype=np.float32) for i in ids]
     scans = [seq.host_alloc_like(h) for h in host] if pinned else host
-    deltas = _deltas(sc, ids); times = 0.1 * np.arange(1, n_frames + 1)
+    deltas = chain_deltas(sc, ids); times = 0.1 * np.arange(1, n_frames + 1)
     pose0 = sc.guess(0)
     # a partial run of 3 frames first: an insert applied late or twice shows in the map here
     res3 = seq.localization_sequence(scans[:3], pose0, deltas[:3], times[:3])
@@ -114,7 +89,7 @@ def test_off_by_metres_prediction_and_resident_scans_give_the_same_bits(gpu_slam
     ids = list(range(8))
     host = [np.ascontiguousarray(sc.scan(i), dtype=np.float32) for i in ids]
     scans = [seq.host_alloc_like(h) for h in host]
-    deltas = _deltas(sc, ids, off={4: 1.5}); times = 0.1 * np.arange(1, 9)
+    deltas = chain_deltas(sc, ids, x_off={4: 1.5}); times = 0.1 * np.arange(1, 9)
     pose0 = sc.guess(0)
     res = seq.localization_sequence(scans, pose0, deltas, times)
     ref = _per_frame(plain, host, res[2], times)
@@ -128,7 +103,8 @@ def test_off_by_metres_prediction_and_resident_scans_give_the_same_bits(gpu_slam
     res_d = resident.localization_sequence(d_scans, pose0, deltas, times, on_device=True)
     assert res_d[0] == 0
     assert np.array_equal(res_d[1], res[1]) and np.array_equal(res_d[2], res[2])
-    assert [_stats_tuple(a) for a in res_d[3]] == [_stats_tuple(a) for a in res[3]]
+    for k, (a, b) in enumerate(zip(res_d[3], res[3])):
+        assert_same_bits(a, b, ("resident scans, frame", k))
     _assert_maps_equal(resident, seq, res[3][-1].pos_in_localmap)
     for s in (seq, plain, resident):
         s.close()
@@ -150,7 +126,7 @@ def test_a_run_across_a_block_boundary_into_a_new_cube(gpu_slam_factory):
     assert not (seq.export_map()[:, 0] >= 25.0).any()
     ids = list(range(10))
     host = [np.ascontiguousarray(sc.scan(i), dtype=np.float32) for i in ids]
-    deltas = _deltas(sc, ids, off={9: -30.0}); times = 0.1 * np.arange(1, 11)
+    deltas = chain_deltas(sc, ids, x_off={9: -30.0}); times = 0.1 * np.arange(1, 11)
     pose0 = sc.guess(0).copy(); pose0[:3] += off
     res = seq.localization_sequence([seq.host_alloc_like(h) for h in host], pose0, deltas, times)
     assert res[0] == 0 and res[4] == len(ids), (res[0], res[4], seq.last_error())
@@ -172,7 +148,7 @@ def test_a_frame_without_map_stops_the_run_like_the_loop(gpu_slam_factory, soicp
     seq, plain = _contexts(gpu_slam_factory, sc)
     ids = list(range(6))
     host = [np.ascontiguousarray(sc.scan(i), dtype=np.float32) for i in ids]
-    deltas = _deltas(sc, ids, off={3: 250.0}); times = 0.1 * np.arange(1, 7)
+    deltas = chain_deltas(sc, ids, x_off={3: 250.0}); times = 0.1 * np.arange(1, 7)
     pose0 = sc.guess(0)
     res = seq.localization_sequence(host, pose0, deltas, times)
     assert res[0] == soicp.NOT_ENOUGH_MAP_FEATURES and res[4] == 3, (res[0], res[4], seq.last_error())
@@ -197,19 +173,15 @@ def test_the_oracle_agrees_from_the_same_guesses(oracle, gpu_slam_factory):
     cfg = oracle.default_config(max_iterations=5)
     ids = list(range(8))
     host = [np.ascontiguousarray(sc.scan(i), dtype=np.float32) for i in ids]
-    deltas = _deltas(sc, ids); times = 0.1 * np.arange(1, 9)
+    deltas = chain_deltas(sc, ids); times = 0.1 * np.arange(1, 9)
     res = seq.localization_sequence([seq.host_alloc_like(h) for h in host], sc.guess(0), deltas, times)
     assert res[0] == 0 and res[4] == len(ids)
     prev_hist = None
     for k in range(len(ids)):
         orc, opose, ost, _ = om.register(host[k], res[2][k], cfg, prev_obs_hist=prev_hist)
         st = res[3][k]
-        assert orc == 0 and ost.n_iterations == st.n_iterations, k
-        for it in range(ost.n_iterations):
-            assert list(st.iterations[it].reject_hist) == list(ost.iters[it].reject_hist), (k, it)
-            assert st.iterations[it].lm_iterations == ost.iters[it].lm_iterations, (k, it)
-        dt, dr = synth.pose_error(res[1][k], opose)
-        assert dt < 1e-8 and dr < 1e-8, (k, dt, dr)
+        assert orc == 0, k
+        assert_follows_oracle(st, ost, ("frame", k), pose=res[1][k], opose=opose)
         prev_hist = np.array(ost.iters[ost.n_iterations - 1].obs_hist, np.int32)
         om.transform_and_add(host[k], res[1][k])  # the oracle's map follows the product's poses
     assert seq.map_size() == om.size(), "the inserts of the run differ from the oracle's VoxelGrid insert"

@@ -18,32 +18,12 @@ import sys
 import numpy as np
 import pytest
 
-from helpers import MAX_RANK_PROCESSES, by_rank, in_threads, pose_close, rank_groups
+from helpers import MAX_RANK_PROCESSES, assert_rank_follows_single, bits_field, by_rank, in_threads, rank_groups, stats_of
 from superodom_amd import synth
 
 pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CASES = ((3, 0.4, 3.0), (9, 0.1, 1.0))  # (scan, guess dt, guess dtheta): the first needs several outer iterations
-
-
-def _summary(res):
-    rc, pose, st = res
-    return (rc, np.asarray(pose).tolist(), st.n_iterations, st.flags,
-            [(st.iterations[it].lm_iterations, st.iterations[it].num_successful_steps, st.iterations[it].termination,
-              st.iterations[it].num_surf_from_scan, list(st.iterations[it].reject_hist), list(st.iterations[it].obs_hist))
-             for it in range(st.n_iterations)], st.laser_cloud_surf_stack_num, st.laser_cloud_surf_from_map_num)
-
-
-def _assert_same(a, ref, tag):
-    assert a[0] == ref[0] == 0, (tag, a[0], ref[0])
-    assert a[2] == ref[2], (tag, "outer iterations", a[2], ref[2])
-    for it in range(ref[2]):
-        assert a[4][it] == ref[4][it], (tag, it, a[4][it], ref[4][it])
-    assert a[5] == ref[5] and a[6] == ref[6], (tag, a[5:], ref[5:])
-    ok, dt, dr = pose_close(np.array(a[1]), np.array(ref[1]), 1e-9, 1e-9)
-    assert ok, (tag, dt, dr)
-
-
 
 
 @pytest.mark.parametrize("world,n_keep,max_sf", [(2, None, -1), (3, 7001, -1), (4, 6000, 2500)])
@@ -64,14 +44,14 @@ def test_query_split_ranks_equal_the_single_context(soicp, world, n_keep, max_sf
         if n_keep:
             scan = np.ascontiguousarray(scan[:n_keep])
         guess = sc.guess(i, dt=dt, dth_deg=dth)
-        ref = _summary(one.register(scan, guess))
+        ref = stats_of(one.register(scan, guess))
         if i == 3 and max_sf < 0:
-            assert ref[2] >= 3, "the test needs several outer iterations"
-        res = in_threads(world, lambda r: _summary(ranks[r].register(scan, guess)))
+            assert bits_field(ref[3], "n_iterations") >= 3, "the test needs several outer iterations"
+        res = in_threads(world, lambda r: stats_of(ranks[r].register(scan, guess)))
         for r in range(world):
             assert res[r][1] == res[0][1], "all ranks hold the same sums: identical decisions, identical bits"
-            assert res[r][3] & soicp.FLAG_QUERY_SPLIT and res[r][3] & soicp.FLAG_SHARDED
-            _assert_same(res[r], ref, ("query split", world, i, r))
+            assert res[r][2] & soicp.FLAG_QUERY_SPLIT and res[r][2] & soicp.FLAG_SHARDED
+            assert_rank_follows_single(res[r], ref, ("query split", world, i, r))
     for sh in ranks + [one]:
         sh.close()
 
@@ -93,12 +73,12 @@ def test_query_split_over_the_peer_exchange_in_one_process(soicp, monkeypatch):
         sh.peer_enable(True)
     for i, dt, dth in CASES:
         scan, guess = sc.scan(i), sc.guess(i, dt=dt, dth_deg=dth)
-        ref = _summary(one.register(scan, guess))
-        res = in_threads(2, lambda r: _summary(ranks[r].register(scan, guess)))
+        ref = stats_of(one.register(scan, guess))
+        res = in_threads(2, lambda r: stats_of(ranks[r].register(scan, guess)))
         for r in range(2):
             assert res[r][1] == res[0][1]
-            assert not (res[r][3] & soicp.FLAG_PER_EVAL_LAUNCHES), "the persistent solve launch must survive N > 1"
-            _assert_same(res[r], ref, ("query split, peer exchange", i, r))
+            assert not (res[r][2] & soicp.FLAG_PER_EVAL_LAUNCHES), "the persistent solve launch must survive N > 1"
+            assert_rank_follows_single(res[r], ref, ("query split, peer exchange", i, r))
     for sh in ranks + [one]:
         sh.close()
 
@@ -139,7 +119,7 @@ def _rank_process(ranks, world, shard_mode, transport, recut, conn):
                 conn.recv()  # barrier
                 scan, guess = sc.scan(i), sc.guess(i, dt=dt, dth_deg=dth)
                 for j, res in enumerate(in_threads(len(shs), lambda j: shs[j].register(scan, guess))):
-                    out[j].append(_summary(res))
+                    out[j].append(stats_of(res))
                 conn.send(True)
         out = [[] for _ in shs]
         register_all(out)
@@ -211,10 +191,11 @@ def _assert_same_over_map_shards(res, ref, k, tag):
     """Map shards joined by the peer exchange only: no communicator sums the per-block counts of the insert, so each rank reports
     the 5x5 count of ITS shard (laser_cloud_surf_from_map_num); the shards partition the map, so the counts add up to the single
     context's.  Everything else equals the single context rank by rank."""
-    assert sum(r_[k][6] for r_ in res) == ref[k][6], (tag, [r_[k][6] for r_ in res], ref[k][6])
+    counts = [bits_field(r_[k][3], "laser_cloud_surf_from_map_num") for r_ in res]
+    whole = bits_field(ref[k][3], "laser_cloud_surf_from_map_num")
+    assert sum(counts) == whole and all(0 < c < whole for c in counts), (tag, counts, whole)
     for r, r_ in enumerate(res):
-        assert 0 < r_[k][6] < ref[k][6], (tag, r, r_[k][6])
-        _assert_same(tuple(r_[k][:6]) + (ref[k][6],), ref[k], tag + (r,))
+        assert_rank_follows_single(r_[k], ref[k], tag + (r,), omit=("laser_cloud_surf_from_map_num",))  # (compared as a sum, just above)
 
 
 def _single_context_reference(soicp, plane_res=None):
@@ -223,7 +204,7 @@ def _single_context_reference(soicp, plane_res=None):
     one.add_surf_point_cloud(sc.map_points)
     if plane_res:
         one.set_resolution(plane_res / 2, plane_res)
-    out = [_summary(one.register(sc.scan(i), sc.guess(i, dt=dt, dth_deg=dth))) for i, dt, dth in CASES]
+    out = [stats_of(one.register(sc.scan(i), sc.guess(i, dt=dt, dth_deg=dth))) for i, dt, dth in CASES]
     one.close()
     return out
 
@@ -242,8 +223,8 @@ def test_rccl_two_ranks_on_two_devices_equal_the_single_context(soicp, shard_mod
     for k in range(len(CASES)):
         assert res[0][k][1] == res[1][k][1], "both ranks all-reduce the same sums: identical poses"
         for r in range(2):
-            assert res[r][k][3] & soicp.FLAG_PER_EVAL_LAUNCHES, "RCCL path: one launch per evaluation"
-            _assert_same(res[r][k], ref[k], ("rccl", shard_mode, k, r))
+            assert res[r][k][2] & soicp.FLAG_PER_EVAL_LAUNCHES, "RCCL path: one launch per evaluation"
+            assert_rank_follows_single(res[r][k], ref[k], ("rccl", shard_mode, k, r))
 
 
 @pytest.mark.parametrize("shard_mode", [0, 1])
@@ -255,9 +236,9 @@ def test_peer_exchange_across_two_devices_equals_the_single_context(soicp, shard
     for k in range(len(CASES)):
         assert res[0][k][1] == res[1][k][1]
         for r in range(2):
-            assert not (res[r][k][3] & soicp.FLAG_PER_EVAL_LAUNCHES), "the persistent solve launch must survive N > 1"
+            assert not (res[r][k][2] & soicp.FLAG_PER_EVAL_LAUNCHES), "the persistent solve launch must survive N > 1"
             if shard_mode == 1:  # (map replicated: every rank counts the whole map)
-                _assert_same(res[r][k], ref[k], ("peer over xGMI", shard_mode, k, r))
+                assert_rank_follows_single(res[r][k], ref[k], ("peer over xGMI", shard_mode, k, r))
         if shard_mode == 0:
             _assert_same_over_map_shards(res, ref, k, ("peer over xGMI", shard_mode, k))
 
@@ -270,11 +251,12 @@ def test_rccl_all_gather_recuts_the_shards_at_a_plane_res_change(soicp):
     n = len(CASES)
     for r in range(2):
         for k in range(n):
-            _assert_same(res[r][k], ref_a[k], ("before the re-cut", k, r))
+            assert_rank_follows_single(res[r][k], ref_a[k], ("before the re-cut", k, r))
         tag, sizes = res[r][n]
         assert tag == "sizes" and sizes[1] < sizes[0], "a shard, not the whole map, after the re-cut"
         for k in range(n):
-            _assert_same(res[r][n + 1 + k], ref_b[k], ("after the re-cut", k, r))
+            # (the ranks have registered these scans once before the re-cut, ref_b has not: another call before this one)
+            assert_rank_follows_single(res[r][n + 1 + k], ref_b[k], ("after the re-cut", k, r), omit=("uncertainty",))
 
 
 def test_eight_ranks_on_eight_devices(soicp):

@@ -13,7 +13,7 @@ import os
 import numpy as np
 import pytest
 
-from helpers import CorridorScene, pose_close
+from helpers import CorridorScene, assert_follows_oracle
 from test_oracle_b_registration import REF_SO, oracle_map_of, run_a_and_b, assert_same_registration
 
 pytestmark = [pytest.mark.gpu, pytest.mark.skipif(not os.path.exists(REF_SO), reason="oracle/_ref/libref_octree.so not built")]
@@ -36,13 +36,8 @@ def test_hip_registration_equals_the_reference_octree_driven_oracle(oracle, gpu_
     rc, pose, st = slam.register(scan, guess)
     assert rc == 0
     for tag, (orc, opose, ost, ocorr) in (("Oracle-A", a), ("Oracle-B (reference octree.h)", b)):
-        assert st.n_iterations == ost.n_iterations, tag
-        for it in range(st.n_iterations):
-            x, y = st.iterations[it], ost.iters[it]
-            assert (x.lm_iterations, x.num_successful_steps, x.termination, x.num_surf_from_scan) == \
-                   (y.lm_iterations, y.num_successful_steps, y.termination, y.num_surf), (tag, it)
-            assert list(x.reject_hist) == list(y.reject_hist) and list(x.obs_hist) == list(y.obs_hist), (tag, it)
+        # (1e-6, and no cost: the two sides fit A x = -1 to neighbours in unrelated orders 1.1 km from the origin -- the docstring's
+        #  conditioning argument; a cost is first order in those planes and was never held to 1e-9 here)
+        assert_follows_oracle(st, ost, tag, pose=pose, opose=opose, pose_tol=1e-6, omit=("final_cost",))
         assert np.array_equal(slam.match_status(len(scan)), ocorr["status"]), tag
-        ok, et, er = pose_close(pose, opose, 1e-6, 1e-6)
-        assert ok, (tag, et, er)
     slam.close()

@@ -13,7 +13,7 @@ import sys
 import numpy as np
 import pytest
 
-from helpers import MAX_RANK_PROCESSES, by_rank, in_threads, pose_close, rank_groups
+from helpers import MAX_RANK_PROCESSES, assert_rank_follows_single, bits_field, by_rank, in_threads, rank_groups, stats_of
 from superodom_amd import synth
 
 pytestmark = pytest.mark.gpu
@@ -24,22 +24,9 @@ CASES = ((3, 0.4, 3.0), (9, 0.1, 1.0), (14, 0.1, 1.0))  # (scan, guess dt, guess
 def _reference(soicp, sc):
     one = soicp.LidarSlamGpu(plane_res=sc.plane_res, line_res=sc.plane_res / 2, max_surface_features=-1, max_iterations=5)
     one.add_surf_point_cloud(sc.map_points)
-    out = [one.register(sc.scan(i), sc.guess(i, dt=dt, dth_deg=dth)) for i, dt, dth in CASES]
+    out = [stats_of(one.register(sc.scan(i), sc.guess(i, dt=dt, dth_deg=dth))) for i, dt, dth in CASES]
     one.close()
     return out
-
-
-def _same(a, b, tag):
-    (rc_a, pose_a, st_a), (rc_b, pose_b, st_b) = a, b
-    assert rc_a == rc_b == 0, (tag, rc_a, rc_b)
-    assert st_a.n_iterations == st_b.n_iterations, tag
-    for it in range(st_b.n_iterations):
-        x, y = st_a.iterations[it], st_b.iterations[it]
-        assert (x.lm_iterations, x.num_successful_steps, x.termination, x.num_surf_from_scan) == \
-               (y.lm_iterations, y.num_successful_steps, y.termination, y.num_surf_from_scan), (tag, it)
-        assert list(x.reject_hist) == list(y.reject_hist) and list(x.obs_hist) == list(y.obs_hist), (tag, it)
-    ok, dt, dr = pose_close(pose_a, pose_b, 1e-9, 1e-9)
-    assert ok, (tag, dt, dr)
 
 
 @pytest.mark.parametrize("world,wgs", [(2, 100)])
@@ -50,7 +37,7 @@ def test_peer_exchange_between_contexts_of_one_process(soicp, monkeypatch, world
     queues, GPU_MAX_HW_QUEUES = 4 by default, and two solve launches on one queue cannot run at the same time.)"""
     sc = synth.Scene("small")
     ref = _reference(soicp, sc)
-    assert ref[0][2].n_iterations >= 3
+    assert bits_field(ref[0][3], "n_iterations") >= 3
     monkeypatch.setenv("SOICP_SOLVE_WORKGROUPS", str(wgs))
     ranks = list(range(world))
     shards = [soicp.LidarSlamGpu(plane_res=sc.plane_res, line_res=sc.plane_res / 2, max_surface_features=-1, max_iterations=5,
@@ -70,8 +57,7 @@ def test_peer_exchange_between_contexts_of_one_process(soicp, monkeypatch, world
         res = in_threads(world, lambda r: shards[r].register(scan, guess), 180)
         for r in ranks:
             assert np.array_equal(res[r][1], res[0][1]), "all ranks hold the same sums: identical decisions, identical bits"
-            _same(res[r], ref[k], ("in-process", world, i, r))
-            assert res[r][2].laser_cloud_surf_from_map_num == ref[k][2].laser_cloud_surf_from_map_num
+            assert_rank_follows_single(stats_of(res[r]), ref[k], ("in-process", world, i, r))
             assert not (res[r][2].flags & soicp.FLAG_PER_EVAL_LAUNCHES), "the persistent solve launch must survive N > 1"
 
 
@@ -109,10 +95,7 @@ def _peer_worker_body(ranks, world, wgs, conn):
         scan, guess = sc.scan(i), sc.guess(i, dt=dt, dth_deg=dth)
         res = in_threads(len(shards), lambda j: shards[j].register(scan, guess))
         for j, (rc, pose, st) in enumerate(res):
-            out[j].append((rc, pose.tolist(), st.n_iterations, st.flags,
-                           [(st.iterations[it].lm_iterations, st.iterations[it].num_successful_steps, st.iterations[it].termination,
-                             st.iterations[it].num_surf_from_scan, list(st.iterations[it].reject_hist), list(st.iterations[it].obs_hist))
-                            for it in range(st.n_iterations)]))
+            out[j].append(stats_of((rc, pose, st)))
         conn.send(True)
     conn.send(out)
     conn.recv()
@@ -169,11 +152,6 @@ def test_peer_exchange_between_processes_over_hip_ipc(soicp, world, wgs):
         a = res[0][k]
         for r in range(1, world):
             assert res[r][k][0] == a[0] == 0 and res[r][k][1] == a[1], "all processes must return identical poses"
-        assert not (a[3] & soicp.FLAG_PER_EVAL_LAUNCHES)
-        rc, pose, st = ref[k]
-        assert a[2] == st.n_iterations
-        for it in range(st.n_iterations):
-            y = st.iterations[it]
-            assert a[4][it] == (y.lm_iterations, y.num_successful_steps, y.termination, y.num_surf_from_scan, list(y.reject_hist), list(y.obs_hist)), (i, it)
-        ok, dt_, dr_ = pose_close(np.array(a[1]), pose, 1e-9, 1e-9)
-        assert ok, (i, dt_, dr_)
+        assert not (a[2] & soicp.FLAG_PER_EVAL_LAUNCHES)
+        # (no communicator between the processes: each rank counts the map points of its own shard; test_gpu_multi.py adds them up)
+        assert_rank_follows_single(a, ref[k], ("processes", world, i), omit=("laser_cloud_surf_from_map_num",))

@@ -9,28 +9,10 @@ import os
 import numpy as np
 import pytest
 
+from helpers import assert_follows_oracle, assert_same_bits, chain_deltas
 from superodom_amd import synth
 
 pytestmark = pytest.mark.gpu
-
-
-def _stats_tuple(st):
-    out = [st.n_iterations]
-    for it in range(st.n_iterations):
-        a = st.iterations[it]
-        out += [a.lm_iterations, a.num_successful_steps, a.termination, a.num_surf_from_scan, tuple(a.reject_hist), tuple(a.obs_hist),
-                np.float64(a.final_cost).tobytes(), np.float64(a.initial_cost).tobytes(), np.array(a.pose_after).tobytes()]
-    out += [np.array(st.JtJ).tobytes(), np.array(st.Jtr).tobytes(), tuple(st.pos_in_localmap), st.laser_cloud_surf_from_map_num,
-            st.laser_cloud_surf_stack_num, np.array(st.uncertainty).tobytes()]
-    return out
-
-
-def _deltas(sc, ids, off=None):
-    """motion predictions that put guess k near sc.guess(ids[k]): gt(k-1)^-1 o guess(k) (the registration of k - 1 ends within millimetres of gt)"""
-    d = np.zeros((len(ids), 7)); d[:, 6] = 1.0
-    for k in range(1, len(ids)):
-        d[k] = synth.pose_between(sc.gt_pose(ids[k - 1]), sc.guess(ids[k]) if off is None or k not in off else synth.perturb_pose(sc.gt_pose(ids[k]), 77 + k, *off[k]))
-    return d
 
 
 def _check_run(slam, plain, scans, pose0, deltas, res, oracle_map=None, oracle=None, cfg=None, on_device_scans=None):
@@ -46,15 +28,11 @@ def _check_run(slam, plain, scans, pose0, deltas, res, oracle_map=None, oracle=N
         prc, ppose, pst = plain.register(scans[k], guesses[k])
         assert prc == 0
         assert np.array_equal(ppose, poses[k]), (k, ppose - poses[k])
-        assert _stats_tuple(pst) == _stats_tuple(stats[k]), k
+        assert_same_bits(pst, stats[k], ("scan", k))
         if oracle_map is not None:
             orc, opose, ost, _ = oracle_map.register(scans[k], guesses[k], cfg)
-            assert orc == 0 and ost.n_iterations == stats[k].n_iterations
-            for it in range(ost.n_iterations):
-                assert list(stats[k].iterations[it].reject_hist) == list(ost.iters[it].reject_hist)
-                assert stats[k].iterations[it].lm_iterations == ost.iters[it].lm_iterations
-            dt, dr = synth.pose_error(poses[k], opose)
-            assert dt < 1e-8 and dr < 1e-8, (k, dt, dr)
+            assert orc == 0
+            assert_follows_oracle(stats[k], ost, ("scan", k), pose=poses[k], opose=opose)
 
 
 @pytest.mark.parametrize("scene,max_feat,ids", [("small", -1, [0, 1, 2, 3, 4, 5, 6]), ("small", 3000, [2, 3, 4, 5]), ("tiny", -1, [0, 1, 2, 3, 4, 5])])
@@ -67,7 +45,7 @@ def test_sequence_equals_single_registrations_and_the_oracle(oracle, soicp, gpu_
     om = oracle.OracleMap(plane_res=sc.plane_res)
     om.add_surf(slam.export_map(), raw=True)
     scans = [slam.host_alloc_like(np.ascontiguousarray(sc.scan(i), dtype=np.float32)) for i in ids]
-    pose0 = sc.guess(ids[0]); deltas = _deltas(sc, ids)
+    pose0 = sc.guess(ids[0]); deltas = chain_deltas(sc, ids)
     res = slam.register_sequence(scans, pose0, deltas)
     _check_run(slam, plain, scans, pose0, deltas, res, om, oracle, oracle.default_config(max_iterations=5, max_surface_features=max_feat))
     flags = [st.flags for st in res[3]]
@@ -83,7 +61,8 @@ def test_sequence_equals_single_registrations_and_the_oracle(oracle, soicp, gpu_
     d_scans = [slam.upload_scan(s_) for s_ in scans]
     res_dev = slam.register_sequence(d_scans, pose0, deltas, on_device=True)
     assert res_dev[0] == 0 and np.array_equal(res_dev[1], res[1]) and np.array_equal(res_dev[2], res[2])
-    assert [_stats_tuple(a)[:-1] for a in res_dev[3]] == [_stats_tuple(a)[:-1] for a in res[3]]  # (all but the uncertainty, which carries over from the call before)
+    for k, (a, b) in enumerate(zip(res_dev[3], res[3])):
+        assert_same_bits(a, b, ("resident scans", k), omit=("uncertainty",))  # (carries over from the call before)
     os.environ["SOICP_SEQ_CHAIN"] = "0"
     try:
         unchained = gpu_slam_factory(**mk)
@@ -92,7 +71,8 @@ def test_sequence_equals_single_registrations_and_the_oracle(oracle, soicp, gpu_
     unchained.add_surf_point_cloud(sc.map_points)
     res_u = unchained.register_sequence(scans, pose0, deltas)
     assert res_u[0] == 0 and np.array_equal(res_u[1], res[1]) and np.array_equal(res_u[2], res[2])
-    assert [_stats_tuple(a) for a in res_u[3]] == [_stats_tuple(a) for a in res[3]]
+    for k, (a, b) in enumerate(zip(res_u[3], res[3])):
+        assert_same_bits(a, b, ("unchained", k))
     assert not any(st.flags & soicp.FLAG_CHAINED for st in res_u[3])
     for s in (slam, plain, unchained):
         s.close()
@@ -108,7 +88,7 @@ def test_a_registration_that_needs_more_iterations_breaks_the_chain_not_the_resu
     scans = [slam.host_alloc_like(np.ascontiguousarray(sc.scan(i), dtype=np.float32)) for i in ids]
     pose0 = sc.guess(0)
     # scans 3 and 6 start 0.45 m / 4 degrees off: they need more outer iterations than the two their neighbours take
-    deltas = _deltas(sc, ids, off={3: (0.45, 4.0), 6: (0.45, 4.0)})
+    deltas = chain_deltas(sc, ids, off={3: (0.45, 4.0), 6: (0.45, 4.0)})
     res = slam.register_sequence(scans, pose0, deltas)
     _check_run(slam, plain, scans, pose0, deltas, res)
     iters = [st.n_iterations for st in res[3]]
@@ -132,7 +112,7 @@ def test_sequence_edge_cases(soicp, gpu_slam_factory):
     assert one[0] == 0 and one[4] == 1 and np.array_equal(one[1][0], ppose)
     ids = [0, 1, 2, 3]
     scans = [np.ascontiguousarray(sc.scan(i), dtype=np.float32) for i in ids]
-    deltas = _deltas(sc, ids)
+    deltas = chain_deltas(sc, ids)
     res = slam.register_sequence(scans, sc.guess(0), deltas)
     _check_run(slam, plain, scans, sc.guess(0), deltas, res)
     # count == 0
@@ -151,7 +131,7 @@ def test_a_run_worked_off_in_two_calls_with_the_next_scan_announced(soicp, gpu_s
         s.add_surf_point_cloud(sc.map_points)
     ids = list(range(8))
     scans = [slam.host_alloc_like(np.ascontiguousarray(sc.scan(i), dtype=np.float32)) for i in ids]
-    pose0 = sc.guess(0); deltas = _deltas(sc, ids)
+    pose0 = sc.guess(0); deltas = chain_deltas(sc, ids)
     whole = plain.register_sequence(scans, pose0, deltas)
     assert whole[0] == 0
     slam.sequence_announce_next(scans[4], deltas[4])
@@ -162,7 +142,8 @@ def test_a_run_worked_off_in_two_calls_with_the_next_scan_announced(soicp, gpu_s
     d2 = deltas[4:].copy(); d2[0] = [0, 0, 0, 0, 0, 0, 1]
     b = slam.register_sequence(scans[4:], g4, d2)
     assert b[0] == 0 and np.array_equal(b[1], whole[1][4:]) and np.array_equal(b[2], whole[2][4:])
-    assert [_stats_tuple(x) for x in list(a[3]) + list(b[3])] == [_stats_tuple(x) for x in whole[3]]
+    for k, (x, y) in enumerate(zip(list(a[3]) + list(b[3]), whole[3])):
+        assert_same_bits(x, y, ("two calls", k))
     assert b[3][0].flags & soicp.FLAG_BINNED_AHEAD and b[3][0].flags & soicp.FLAG_STAGED_SCAN
     # an announcement that is not taken up (another scan starts the next call) and a withdrawn one change nothing
     slam.sequence_announce_next(scans[1], deltas[1])

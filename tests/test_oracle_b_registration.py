@@ -14,7 +14,7 @@ import os
 import numpy as np
 import pytest
 
-from helpers import CorridorScene
+from helpers import CorridorScene, assert_follows_oracle
 
 REF_SO = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "oracle", "_ref", "libref_octree.so")
 pytestmark = pytest.mark.skipif(not os.path.exists(REF_SO), reason="oracle/_ref/libref_octree.so not built (needs /root/reference)")
@@ -46,11 +46,7 @@ def run_a_and_b(oracle, om, scan, guess, max_iterations=5):
 def assert_same_registration(a, b, bits=True):
     (rc_a, pose_a, st_a, co_a), (rc_b, pose_b, st_b, co_b) = a, b
     assert rc_a == rc_b == 0
-    assert st_a.n_iterations == st_b.n_iterations
-    for it in range(st_a.n_iterations):
-        x, y = st_a.iters[it], st_b.iters[it]
-        assert (x.lm_iterations, x.num_successful_steps, x.termination, x.num_surf) == (y.lm_iterations, y.num_successful_steps, y.termination, y.num_surf), it
-        assert list(x.reject_hist) == list(y.reject_hist) and list(x.obs_hist) == list(y.obs_hist), it
+    assert_follows_oracle(st_b, st_a, "Oracle-B against Oracle-A")
     if co_a is not None and co_b is not None:  # correspondences of the LAST outer iteration
         assert np.array_equal(co_a["status"], co_b["status"])
         ok = co_a["status"] == 0
