@@ -7,6 +7,8 @@
 // undistortionAndFeatureExtraction (:440-499), extractFeatures (:422-437), publishTopic / publishCloud (:379-420).
 // Left to the caller: imu_Handler's integration, imuInit and IMU_INIT (the caller passes stamped orientations and the flag),
 // visual_odom_Handler's message parsing (stamped poses), livoxHandler, provide_point_time == 0 (refused here).
+// The library has livoxHandler's ingest (so_icp_extract_features_livox, wire/messages.h CustomMsg); this shell does not route a
+// sensor: livox configuration to it and keeps refusing it.
 #pragma once
 #include <map>
 #include <stdexcept>

@@ -210,6 +210,28 @@ inline void get(CdrReader& r, LaserFeature& m) {
   get(r, m.cloud_nodistortion); get(r, m.cloud_corner); get(r, m.cloud_surface); get(r, m.cloud_realsense);
 }
 
+// CustomPoint[]: every element starts with a uint32, so elements are aligned to 4: 19 bytes of fields 20 bytes apart, and no
+// padding behind the last one (whatever follows aligns itself)
+inline void put(CdrWriter& w, const CustomPoint& m) {
+  w.prim(m.offset_time); w.prim(m.x); w.prim(m.y); w.prim(m.z); w.prim(m.reflectivity); w.prim(m.tag); w.prim(m.line);
+}
+inline void get(CdrReader& r, CustomPoint& m) {
+  m.offset_time = r.prim<uint32_t>(); m.x = r.prim<float>(); m.y = r.prim<float>(); m.z = r.prim<float>();
+  m.reflectivity = r.prim<uint8_t>(); m.tag = r.prim<uint8_t>(); m.line = r.prim<uint8_t>();
+}
+inline void put(CdrWriter& w, const CustomMsg& m) {
+  put(w, m.header); w.prim(m.timebase); w.prim(m.point_num); w.prim(m.lidar_id);
+  for (uint8_t b : m.rsvd) w.prim(b);
+  w.prim<uint32_t>((uint32_t)m.points.size());
+  for (const CustomPoint& p : m.points) put(w, p);
+}
+inline void get(CdrReader& r, CustomMsg& m) {
+  get(r, m.header); m.timebase = r.prim<uint64_t>(); m.point_num = r.prim<uint32_t>(); m.lidar_id = r.prim<uint8_t>();
+  for (uint8_t& b : m.rsvd) b = r.prim<uint8_t>();
+  m.points.resize(r.count(19));
+  for (CustomPoint& p : m.points) get(r, p);
+}
+
 template <typename M> std::vector<uint8_t> serialize(const M& m) { CdrWriter w; put(w, m); return w.take(); }
 // A PointCloud2 whose payload is produced IN PLACE (a device copy lands in the message, no intermediate cloud): the serialised message of
 // `meta` (data empty, width / row_step already those of the final message) up to and including the length word of `data`, for a payload

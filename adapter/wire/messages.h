@@ -11,10 +11,13 @@
 //   sensor_msgs/PointCloud2 (+PointField)           in LaserFeature; out: /registered_scan, /laser_cloud_surround, /laser_cloud_map, /overall_map
 //   std_msgs/String                                 out: /prediction_source (:417-435)
 //   std_msgs/Float32                                out: <ProjectName>uncertainty_{X,Y,Z,roll,pitch,yaw} (LidarSlam.cpp:22-27, 969-974)
+//   livox_ros_driver2/msg/CustomMsg (+CustomPoint)  in : featureExtraction::livoxHandler (featureExtraction.cpp:775-823)
 // The common_interfaces definitions (std_msgs, sensor_msgs, geometry_msgs, nav_msgs, builtin_interfaces) are the ROS 2
 // Humble ones (the reference's Dockerfile pins ros:humble); they are not part of /root/reference.
+// Neither is livox_ros_driver2: CustomMsg and CustomPoint are written from the driver's published .msg files (unpinned).
 #pragma once
 #include <array>
+#include <cstddef>
 #include <cstdint>
 #include <string>
 #include <vector>
@@ -90,5 +93,29 @@ struct LaserFeature {  // super_odometry_msgs/msg/LaserFeature.msg
   int64_t imu_preintegration_reset_id = 0;
   PointCloud2 cloud_nodistortion, cloud_corner, cloud_surface, cloud_realsense;
 };
+
+struct CustomPoint {  // livox_ros_driver2/msg/CustomPoint
+  uint32_t offset_time = 0;  // ns from CustomMsg::timebase
+  float x = 0, y = 0, z = 0;
+  uint8_t reflectivity = 0, tag = 0, line = 0;
+};
+// 19 bytes of fields, elements 4-byte aligned: in CDR and here alike the points are 20 bytes apart, fields at 0 / 4 8 12 / 16 17 18
+static_assert(sizeof(CustomPoint) == 20 && offsetof(CustomPoint, x) == 4 && offsetof(CustomPoint, z) == 12 && offsetof(CustomPoint, reflectivity) == 16 &&
+                  offsetof(CustomPoint, tag) == 17 && offsetof(CustomPoint, line) == 18,
+              "CustomPoint must have the layout so_icp_livox_default_layout describes");
+struct CustomMsg {  // livox_ros_driver2/msg/CustomMsg
+  Header header;
+  uint64_t timebase = 0;
+  uint32_t point_num = 0;
+  uint8_t lidar_id = 0;
+  std::array<uint8_t, 3> rsvd{};
+  std::vector<CustomPoint> points;
+};
+// the points as so_icp_extract_features_livox takes them (point_step 20, so_icp_livox_default_layout's offsets), without repacking:
+// livoxHandler reads points[0 .. point_num), so *n is point_num, held to the points that are there
+inline const uint8_t* points_payload(const CustomMsg& m, uint32_t* n) {
+  *n = m.point_num < m.points.size() ? m.point_num : (uint32_t)m.points.size();
+  return reinterpret_cast<const uint8_t*>(m.points.data());
+}
 
 }  // namespace so_wire

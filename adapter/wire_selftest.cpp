@@ -4,7 +4,9 @@
 //   wire_selftest emit <Type> <out.cdr>                 serialise a message with fixed field values (the test knows them)
 //   wire_selftest params <file.yaml>                    node_config.h: ROS 2 parameter file -> NodeConfig, printed
 //   wire_selftest feature-params <file.yaml>            node_config.h: the same file -> FeatureConfig, printed
-// Types: String Float32 Header PointCloud2 Odometry Path IterationStats OptimizationStats LaserFeature
+// Types: String Float32 Header PointCloud2 Odometry Path IterationStats OptimizationStats LaserFeature CustomMsg
+//   emit CustomMsg takes an optional frame_id (wire_selftest emit CustomMsg <out.cdr> [frame_id]): its length moves the padding
+//   in front of timebase
 #include <cstdio>
 #include <cstring>
 #include <string>
@@ -66,6 +68,7 @@ int main(int argc, char** argv) {
       else if (t == "IterationStats") out = again<IterationStats>(in);
       else if (t == "OptimizationStats") out = again<OptimizationStats>(in);
       else if (t == "LaserFeature") out = again<LaserFeature>(in);
+      else if (t == "CustomMsg") out = again<CustomMsg>(in);
       else throw std::runtime_error("unknown type " + t);
       spit(argv[4], out);
       return 0;
@@ -100,7 +103,7 @@ int main(int argc, char** argv) {
       spit(argv[4], out);
       return 0;
     }
-    if (argc == 4 && !strcmp(argv[1], "emit")) {
+    if ((argc == 4 || (argc == 5 && !strcmp(argv[2], "CustomMsg"))) && !strcmp(argv[1], "emit")) {
       const std::string t = argv[2];
       std::vector<uint8_t> out;
       if (t == "String") { String m; m.data = "hello"; out = serialize(m); }
@@ -140,6 +143,22 @@ int main(int argc, char** argv) {
         m.imu_preintegration_reset_id = -5;
         m.cloud_nodistortion = sample_cloud(4, "sensor"); m.cloud_corner = sample_cloud(1, "sensor"); m.cloud_surface = sample_cloud(3, "sensor"); m.cloud_realsense = sample_cloud(0, "");
         out = serialize(m);
+      } else if (t == "CustomMsg") {
+        CustomMsg m;
+        m.header.stamp = {1700000000, 250000000u}; m.header.frame_id = argc == 5 ? argv[4] : "livox_frame";
+        m.timebase = 1700000000250000000ull; m.lidar_id = 192; m.rsvd = {1, 2, 3};
+        for (uint32_t i = 0; i < 5; ++i) {
+          CustomPoint p;
+          p.offset_time = 20000u * i + 7u; p.x = 1.5f * i; p.y = -0.25f * i; p.z = 0.125f + i;
+          p.reflectivity = (uint8_t)(10 * i); p.tag = (uint8_t)(0x10 * i); p.line = (uint8_t)(i % 4);
+          m.points.push_back(p);
+        }
+        m.point_num = (uint32_t)m.points.size();
+        uint32_t n;
+        const uint8_t* raw = points_payload(m, &n);  // the bytes handed to so_icp_extract_features_livox are those on the wire
+        const std::vector<uint8_t> b = serialize(m);
+        if (n != 5 || std::memcmp(raw, b.data() + b.size() - (20 * n - 1), 20 * n - 1)) throw std::runtime_error("points_payload differs from the wire bytes");
+        out = b;
       } else throw std::runtime_error("unknown type " + t);
       spit(argv[3], out);
       return 0;

@@ -467,6 +467,43 @@ int so_icp_extract_features(so_icp_ctx *ctx, const void *raw, uint32_t width, ui
 int so_icp_extract_features_dev(so_icp_ctx *ctx, const void *d_raw, uint32_t width, uint32_t height, const so_icp_sweep_layout *layout,
                                 double lidar_start_time, const so_icp_stamped_pose *poses, size_t n_poses, int poses_are_imu,
                                 const double T_i_l[7], void **d_nodistortion_out, void **d_surface_out, so_icp_feature_info *info);
+/* -------- the same front end for the Livox sensors: featureExtraction::livoxHandler
+ * (src/FeatureExtraction/featureExtraction.cpp:775-823) in place of laserCloudHandler, then the same removePointDistortion
+ * (:223-314) and uniformFeatureExtraction (:504-525) as above.  raw: the `points` of a livox_ros_driver2/msg/CustomMsg,
+ * n_points records point_step bytes apart (the last one may end with its last field).  Per point i (:794-806):
+ *   accepted iff line < n_scans && ((tag & 0x30) == 0x10 || (tag & 0x30) == 0x00); a rejected point keeps the value-initialised
+ *   record of points.resize(point_num): 32 zero bytes -- which the de-skew and the sampler then treat like any other point;
+ *   x y z = R_imu_laser_gravity * Vector3d(x, y, z) in fp64, each row (R[r][0]*x + R[r][1]*y) + R[r][2]*z unfused, rounded to
+ *   float (always multiplied, the identity too: an infinite x makes y and z NaN, as Eigen's product does);
+ *   intensity = (float)reflectivity; time = (float)offset_time / 1e9f (a correctly rounded division, :803 -- not the Ouster's
+ *   multiplication by 1e-9f); ring = line.
+ * R_imu_laser_gravity is imu_Init->imu_laser_R_Gravity, or the identity while the node's IMU buffer is empty (:788-791): the
+ * caller's, as this library does not build imuInit.  provide_point_time: 0 (:807-810, the node shuts down) has no counterpart.
+ * The offsets are data: so_icp_livox_default_layout gives those of livox_ros_driver2's CustomPoint (uint32 offset_time; float32
+ * x, y, z; uint8 reflectivity, tag, line: 0 / 4 8 12 / 16 17 18, point_step 20 -- as CDR lays the sequence out and as a C++
+ * std::vector<CustomPoint> does); that message definition is not part of the reference tree (unpinned). */
+typedef struct {
+  uint32_t point_step;
+  /* byte offsets inside a point, all >= 0: offset_time UINT32 (ns from the message's timebase), x y z FLOAT32, the rest UINT8 */
+  int32_t off_offset_time, off_x, off_y, off_z, off_reflectivity, off_tag, off_line;
+  int32_t n_scans;           /* feature_extraction_node.scan_line (N_SCANS, default 4); 0 .. 256 */
+  int32_t filter_point_size; /* feature_extraction_node.filter_point_size, >= 1 */
+  float min_range;           /* feature_extraction_node.min_range */
+  int32_t reserved;
+  double R_imu_laser_gravity[9]; /* row-major */
+} so_icp_livox_layout;
+/* CustomPoint's offsets, the node's parameter defaults (:120-130: scan_line 4, filter_point_size 3, min_range 0.2), R = identity */
+void so_icp_livox_default_layout(so_icp_livox_layout *layout);
+/* livoxHandler (:775-823) + removePointDistortion + uniformFeatureExtraction; arguments and outputs as so_icp_extract_features.
+ * raw: host, (n_points - 1) * point_step + the end of the last field bytes are read. */
+int so_icp_extract_features_livox(so_icp_ctx *ctx, const void *raw, uint32_t n_points, const so_icp_livox_layout *layout,
+                                  double lidar_start_time, const so_icp_stamped_pose *poses, size_t n_poses, int poses_are_imu,
+                                  const double T_i_l[7], void *nodistortion_out, void *surface_out, so_icp_feature_info *info);
+/* same (livoxHandler, :775-823), payload already in HBM at any byte alignment; outputs as so_icp_extract_features_dev: device
+ * buffers owned by the context, shared with that entry, valid until the next call of either. */
+int so_icp_extract_features_livox_dev(so_icp_ctx *ctx, const void *d_raw, uint32_t n_points, const so_icp_livox_layout *layout,
+                                      double lidar_start_time, const so_icp_stamped_pose *poses, size_t n_poses, int poses_are_imu,
+                                      const double T_i_l[7], void **d_nodistortion_out, void **d_surface_out, so_icp_feature_info *info);
 /* so_icp_prefilter_scan on a cloud already in HBM and complete (e.g. *d_surface_out above, stride 32): same results, bit for bit */
 int so_icp_prefilter_scan_dev(so_icp_ctx *ctx, const void *d_surf, size_t n, size_t stride_bytes, int auto_voxel_size, float line_res,
                               float plane_res, void **d_filtered_out, size_t *n_out, so_icp_prefilter_info *info);

@@ -76,6 +76,33 @@ class FeatureInfo(C.Structure):
                 ("n_points", C.c_uint64), ("n_surface", C.c_uint64)]
 
 
+class LivoxLayout(C.Structure):
+    """so_icp_livox_layout"""
+    _fields_ = [("point_step", C.c_uint32), ("off_offset_time", C.c_int32), ("off_x", C.c_int32), ("off_y", C.c_int32), ("off_z", C.c_int32),
+                ("off_reflectivity", C.c_int32), ("off_tag", C.c_int32), ("off_line", C.c_int32), ("n_scans", C.c_int32),
+                ("filter_point_size", C.c_int32), ("min_range", C.c_float), ("reserved", C.c_int32), ("R_imu_laser_gravity", C.c_double * 9)]
+
+
+# livox_ros_driver2/msg/CustomPoint (uint32 offset_time; float32 x, y, z; uint8 reflectivity, tag, line): field -> byte offset
+LIVOX_CUSTOM_POINT = {"offset_time": 0, "x": 4, "y": 8, "z": 12, "reflectivity": 16, "tag": 17, "line": 18}
+LIVOX_POINT_STEP = 20  # points 20 bytes apart (CDR and C++ alike); the last field ends at byte 19
+
+
+def livox_layout(filter_point_size=3, min_range=0.2, n_scans=4, R_imu_laser_gravity=None, point_step=LIVOX_POINT_STEP, offsets=None):
+    """so_icp_livox_layout: so_icp_livox_default_layout (CustomPoint's offsets, the node's parameter defaults, R = identity) with
+    the given values; offsets: field -> byte offset for another driver's point; R_imu_laser_gravity: 3 x 3, row-major."""
+    L = LivoxLayout()
+    load().so_icp_livox_default_layout(C.byref(L))
+    L.point_step, L.n_scans, L.filter_point_size, L.min_range = int(point_step), int(n_scans), int(filter_point_size), float(min_range)
+    for name, off in (offsets or {}).items():
+        assert name in LIVOX_CUSTOM_POINT, name
+        setattr(L, "off_" + name, int(off))
+    if R_imu_laser_gravity is not None:
+        for k, v in enumerate(np.asarray(R_imu_laser_gravity, np.float64).reshape(9)):
+            L.R_imu_laser_gravity[k] = float(v)
+    return L
+
+
 SENSOR_VELODYNE, SENSOR_OUSTER = 0, 1
 # sensor_msgs::msg::PointField datatypes
 INT8, UINT8, INT16, UINT16, INT32, UINT32, FLOAT32, FLOAT64 = range(1, 9)
@@ -140,7 +167,8 @@ EXPORTED = ["so_icp_default_config", "so_icp_create", "so_icp_destroy", "so_icp_
             "so_icp_deskew_scan", "so_icp_deskew_scan_dev", "so_icp_transform_cloud", "so_icp_shard_histogram",
             "so_icp_host_register", "so_icp_host_unregister", "so_icp_host_alloc", "so_icp_host_free", "so_icp_device_count", "so_icp_stage_cancel",
             "so_icp_map_insert_stats", "so_icp_register_sequence", "so_icp_map_export_records", "so_icp_sequence_announce_next", "so_icp_debug_neighbours", "so_icp_prefilter_announce",
-            "so_icp_localization_sequence", "so_icp_extract_features", "so_icp_extract_features_dev", "so_icp_prefilter_scan_dev"]
+            "so_icp_localization_sequence", "so_icp_extract_features", "so_icp_extract_features_dev", "so_icp_prefilter_scan_dev",
+            "so_icp_livox_default_layout", "so_icp_extract_features_livox", "so_icp_extract_features_livox_dev"]
 
 _lib = None
 
@@ -212,6 +240,11 @@ def load():
                                           C.c_int, C.POINTER(C.c_double), vp, vp, C.POINTER(FeatureInfo)]
     L.so_icp_extract_features_dev.argtypes = [vp, vp, C.c_uint32, C.c_uint32, C.POINTER(SweepLayout), C.c_double, C.POINTER(C.c_double),
                                               C.c_size_t, C.c_int, C.POINTER(C.c_double), C.POINTER(vp), C.POINTER(vp), C.POINTER(FeatureInfo)]
+    L.so_icp_livox_default_layout.argtypes = [C.POINTER(LivoxLayout)]; L.so_icp_livox_default_layout.restype = None
+    L.so_icp_extract_features_livox.argtypes = [vp, vp, C.c_uint32, C.POINTER(LivoxLayout), C.c_double, C.POINTER(C.c_double), C.c_size_t,
+                                                C.c_int, C.POINTER(C.c_double), vp, vp, C.POINTER(FeatureInfo)]
+    L.so_icp_extract_features_livox_dev.argtypes = [vp, vp, C.c_uint32, C.POINTER(LivoxLayout), C.c_double, C.POINTER(C.c_double), C.c_size_t,
+                                                    C.c_int, C.POINTER(C.c_double), C.POINTER(vp), C.POINTER(vp), C.POINTER(FeatureInfo)]
     L.so_icp_debug_knn_stamps.argtypes = [vp, C.POINTER(C.c_uint64), C.c_size_t, C.POINTER(C.c_size_t)]
     L.so_icp_set_time_kernels.argtypes = [vp, C.c_int]
     L.so_icp_stage_scan.argtypes = [vp, f32p, C.c_size_t, C.c_size_t]
@@ -590,6 +623,29 @@ class LidarSlamGpu:
         self._check(self.L.so_icp_extract_features_dev(self.h, C.c_void_p(d_payload), int(width), int(height), C.byref(layout),
                                                        float(lidar_start_time), pp, npo, int(bool(poses_are_imu)), tp, C.byref(d_rec),
                                                        C.byref(d_surf), C.byref(info)))
+        return d_rec.value, d_surf.value, info
+
+    def extract_features_livox(self, points, n_points, layout, lidar_start_time, poses=None, poses_are_imu=False, T_i_l=None):
+        """livoxHandler's sweep -> LaserFeature clouds on the device.  points: the CustomMsg's points as bytes (uint8), n_points of them
+        layout.point_step apart (the last one may end with its last field); the rest as extract_features."""
+        raw = np.ascontiguousarray(points, np.uint8).reshape(-1)
+        poses, pp, npo, tp, _keep = self._feature_args(poses, T_i_l)
+        n = int(n_points)
+        rec = np.zeros((n, 32), np.uint8)
+        surf = np.zeros((max(n, 1), 32), np.uint8)
+        info = FeatureInfo()
+        self._check(self.L.so_icp_extract_features_livox(self.h, raw.ctypes.data_as(C.c_void_p), n, C.byref(layout), float(lidar_start_time), pp,
+                                                         npo, int(bool(poses_are_imu)), tp, rec.ctypes.data_as(C.c_void_p),
+                                                         surf.ctypes.data_as(C.c_void_p), C.byref(info)))
+        return rec, surf[:info.n_surface].copy(), info
+
+    def extract_features_livox_dev(self, d_points, n_points, layout, lidar_start_time, poses=None, poses_are_imu=False, T_i_l=None):
+        """the same on points resident in HBM (any byte alignment); returns (d_nodistortion, d_surface, FeatureInfo): context-owned
+        device buffers, valid until the next extract_features*_dev call"""
+        poses, pp, npo, tp, _keep = self._feature_args(poses, T_i_l)
+        d_rec = C.c_void_p(); d_surf = C.c_void_p(); info = FeatureInfo()
+        self._check(self.L.so_icp_extract_features_livox_dev(self.h, C.c_void_p(d_points), int(n_points), C.byref(layout), float(lidar_start_time),
+                                                             pp, npo, int(bool(poses_are_imu)), tp, C.byref(d_rec), C.byref(d_surf), C.byref(info)))
         return d_rec.value, d_surf.value, info
 
     def deskew_scan(self, records, time_off, lidar_start_time, poses, poses_are_imu, T_i_l=None):

@@ -1,9 +1,11 @@
-// feature_extraction.cpp -- so_icp_extract_features(_dev): featureExtraction's per-sweep path (laserCloudHandler's ingest,
-// removePointDistortion, uniformFeatureExtraction; src/FeatureExtraction/featureExtraction.cpp) as one enqueue on the device.
+// feature_extraction.cpp -- so_icp_extract_features(_dev) and so_icp_extract_features_livox(_dev): featureExtraction's per-sweep
+// path (laserCloudHandler's or livoxHandler's ingest, removePointDistortion, uniformFeatureExtraction;
+// src/FeatureExtraction/featureExtraction.cpp) as one enqueue on the device.
 //
 // The node's bookkeeping around it (frame skipping, the sweep and pose buffers, the branch choice, the LaserFeature message) stays
 // with the caller; this entry takes one sweep and the pose buffer the branch chose, and returns cloud_nodistortion and
 // cloud_surface.  Kernels: feature_kernels.hip.  The per-scan de-skew constants are deskew_setup's, as for so_icp_deskew_scan.
+#include <algorithm>
 #include <cstring>
 #include <string>
 #include <vector>
@@ -66,9 +68,62 @@ int check_args(so_icp_ctx* c, const char* who, const void* raw, uint32_t width, 
   return SO_ICP_OK;
 }
 
-// the whole pass on queue s: [payload copy], counters cleared, pose table, ingest + de-skew, compaction, counts read back
-int run(so_icp_ctx* c, hipStream_t s, FeatureState& st, const uint8_t* d_raw, uint32_t n, const so_icp_sweep_layout* L, uint32_t width,
-        double t0, const so_icp_stamped_pose* poses, size_t n_poses, int imu, const double T_i_l[7], so_icp_feature_info& info) {
+// the fields of a CustomPoint in so_icp_livox_layout: offset, bytes, name
+struct LivoxField { int32_t off; uint32_t bytes; const char* name; };
+inline void livox_fields(const so_icp_livox_layout* L, LivoxField f[7]) {
+  const LivoxField v[7] = {{L->off_offset_time, 4, "offset_time"}, {L->off_x, 4, "x"}, {L->off_y, 4, "y"}, {L->off_z, 4, "z"},
+                           {L->off_reflectivity, 1, "reflectivity"}, {L->off_tag, 1, "tag"}, {L->off_line, 1, "line"}};
+  for (int k = 0; k < 7; ++k) f[k] = v[k];
+}
+
+int check_livox_layout(so_icp_ctx* c, const char* who, uint32_t n, const so_icp_livox_layout* L) {
+  const std::string w(who);
+  if (L->filter_point_size < 1) return fail(c, SO_ICP_E_INVALID, w + ": filter_point_size must be >= 1");
+  if (L->n_scans < 0 || L->n_scans > 256) return fail(c, SO_ICP_E_INVALID, w + ": n_scans must lie in 0 .. 256 (line is a uint8)");
+  if (L->point_step == 0) return fail(c, SO_ICP_E_INVALID, w + ": point_step must be > 0");
+  LivoxField f[7];
+  livox_fields(L, f);
+  for (const LivoxField& q : f) {
+    if (q.off < 0) return fail(c, SO_ICP_E_INVALID, w + ": offset of " + q.name + " must be >= 0 (a CustomPoint has every field)");
+    if ((uint64_t)q.off + q.bytes > L->point_step) return fail(c, SO_ICP_E_INVALID, w + ": offset of " + q.name + " lies past point_step");
+  }
+  if (n >= ((uint32_t)1 << 31)) return fail(c, SO_ICP_E_UNSUPPORTED, w + ": too many points");
+  return SO_ICP_OK;
+}
+
+LivoxFields livox_fields_of(const so_icp_livox_layout* L) {
+  LivoxFields lf;
+  lf.point_step = L->point_step;
+  lf.offset_time = (uint32_t)L->off_offset_time; lf.x = (uint32_t)L->off_x; lf.y = (uint32_t)L->off_y; lf.z = (uint32_t)L->off_z;
+  lf.reflectivity = (uint32_t)L->off_reflectivity; lf.tag = (uint32_t)L->off_tag; lf.line = (uint32_t)L->off_line;
+  lf.n_scans = (uint32_t)L->n_scans;
+  for (int k = 0; k < 9; ++k) lf.R[k] = L->R_imu_laser_gravity[k];
+  return lf;
+}
+
+// bytes of the payload that are read: the last point ends with its last field (19 of the 20 bytes of a CDR CustomPoint)
+size_t livox_payload_bytes(uint32_t n, const so_icp_livox_layout* L) {
+  LivoxField f[7];
+  livox_fields(L, f);
+  size_t end = 0;
+  for (const LivoxField& q : f) end = std::max(end, (size_t)q.off + q.bytes);
+  return n ? (size_t)(n - 1) * L->point_step + end : 0;
+}
+
+int check_livox_args(so_icp_ctx* c, const char* who, const void* raw, uint32_t n, const so_icp_livox_layout* L, const so_icp_stamped_pose* poses,
+                     size_t n_poses) {
+  if (!c || !L || (!raw && n) || (n_poses && !poses)) return SO_ICP_E_INVALID;
+  if (const int rc = check_livox_layout(c, who, n, L)) return rc;
+  if (n_poses >= ((size_t)1 << 24)) return fail(c, SO_ICP_E_UNSUPPORTED, std::string(who) + ": too many poses");
+  NEED_DEVICE(c);
+  return SO_ICP_OK;
+}
+
+// the whole pass on queue s: [payload copy], counters cleared, pose table, ingest + de-skew, compaction, counts read back.
+// ingest(d_rec, d_pose_table, frames, d_n_clamped): the sensor's launch_*ingest_deskew on queue s; step, min_range: the sampler's.
+template <typename Ingest>
+int run(so_icp_ctx* c, hipStream_t s, FeatureState& st, uint32_t n, uint32_t step, float min_range, double t0, const so_icp_stamped_pose* poses,
+        size_t n_poses, int imu, const double T_i_l[7], so_icp_feature_info& info, Ingest&& ingest) {
   static_assert(sizeof(so_icp_stamped_pose) == kStampedPoseDoubles * sizeof(double), "stamped pose = 8 doubles");
   std::memset(&info, 0, sizeof(info));
   info.q_w_original_l[3] = 1.0;
@@ -81,7 +136,7 @@ int run(so_icp_ctx* c, hipStream_t s, FeatureState& st, const uint8_t* d_raw, ui
     info.deskewed = 1;
   }
   if (!n) return SO_ICP_OK;
-  const uint32_t step = (uint32_t)L->filter_point_size, nblk = surf_workgroups(n, step);
+  const uint32_t nblk = surf_workgroups(n, step);
   const size_t state_off = 16, tab_off = (state_off + (size_t)nblk * 8 + 255) & ~(size_t)255;
   HIP_TRY(c, st.rec.reserve((size_t)n * kFeatureRecordBytes));
   HIP_TRY(c, st.surf.reserve((size_t)(surf_candidates(n, step) + 1) * kFeatureRecordBytes));
@@ -90,15 +145,38 @@ int run(so_icp_ctx* c, hipStream_t s, FeatureState& st, const uint8_t* d_raw, ui
   uint32_t* d_counts = st.small.as<uint32_t>();
   HIP_TRY(c, hipMemsetAsync(st.small.p, 0, tab_off, s));
   if (n_poses) HIP_TRY(c, hipMemcpyAsync(st.small.as<uint8_t>() + tab_off, tab.data(), tab.size() * sizeof(double), hipMemcpyHostToDevice, s));
-  launch_ingest_deskew(d_raw, n, fields_of(L, width), st.rec.as<uint8_t>(), t0, reinterpret_cast<const double*>(st.small.as<uint8_t>() + tab_off),
-                       (uint32_t)n_poses, f, d_counts, s);
-  launch_surf_sample(st.rec.as<uint8_t>(), n, step, L->min_range, st.surf.as<uint8_t>(), d_counts + 1,
+  ingest(st.rec.as<uint8_t>(), reinterpret_cast<const double*>(st.small.as<uint8_t>() + tab_off), f, d_counts);
+  launch_surf_sample(st.rec.as<uint8_t>(), n, step, min_range, st.surf.as<uint8_t>(), d_counts + 1,
                      reinterpret_cast<unsigned long long*>(st.small.as<uint8_t>() + state_off), d_counts + 2, s);
   HIP_TRY(c, hipGetLastError());
   HIP_TRY(c, hipMemcpyAsync(st.h_counts, d_counts, 8, hipMemcpyDeviceToHost, s));
   HIP_TRY(c, hipStreamSynchronize(s));  // (also keeps `tab` alive until its upload has been consumed)
   info.n_clamped = st.h_counts[0];
   info.n_surface = st.h_counts[1];
+  return SO_ICP_OK;
+}
+
+// run() for a PointCloud2 sweep (laserCloudHandler) and for a CustomMsg's points (livoxHandler)
+int run_sweep(so_icp_ctx* c, hipStream_t s, FeatureState& st, const uint8_t* d_raw, uint32_t n, const so_icp_sweep_layout* L, uint32_t width,
+              double t0, const so_icp_stamped_pose* poses, size_t n_poses, int imu, const double T_i_l[7], so_icp_feature_info& info) {
+  return run(c, s, st, n, (uint32_t)L->filter_point_size, L->min_range, t0, poses, n_poses, imu, T_i_l, info,
+             [&](uint8_t* d_rec, const double* d_tab, const DeskewFrames& f, uint32_t* d_n_clamped) {
+               launch_ingest_deskew(d_raw, n, fields_of(L, width), d_rec, t0, d_tab, (uint32_t)n_poses, f, d_n_clamped, s);
+             });
+}
+int run_livox(so_icp_ctx* c, hipStream_t s, FeatureState& st, const uint8_t* d_raw, uint32_t n, const so_icp_livox_layout* L, double t0,
+              const so_icp_stamped_pose* poses, size_t n_poses, int imu, const double T_i_l[7], so_icp_feature_info& info) {
+  return run(c, s, st, n, (uint32_t)L->filter_point_size, L->min_range, t0, poses, n_poses, imu, T_i_l, info,
+             [&](uint8_t* d_rec, const double* d_tab, const DeskewFrames& f, uint32_t* d_n_clamped) {
+               launch_livox_ingest_deskew(d_raw, n, livox_fields_of(L), d_rec, t0, d_tab, (uint32_t)n_poses, f, d_n_clamped, s);
+             });
+}
+
+// the clouds of the host entries: out of the context's buffers into the caller's
+int read_back(so_icp_ctx* c, hipStream_t s, FeatureState& st, const so_icp_feature_info& li, void* nodistortion_out, void* surface_out) {
+  if (li.n_points && nodistortion_out) HIP_TRY(c, hipMemcpyAsync(nodistortion_out, st.rec.p, (size_t)li.n_points * kFeatureRecordBytes, hipMemcpyDeviceToHost, s));
+  if (li.n_surface && surface_out) HIP_TRY(c, hipMemcpyAsync(surface_out, st.surf.p, (size_t)li.n_surface * kFeatureRecordBytes, hipMemcpyDeviceToHost, s));
+  HIP_TRY(c, hipStreamSynchronize(s));
   return SO_ICP_OK;
 }
 
@@ -128,11 +206,8 @@ int so_icp_extract_features(so_icp_ctx* c, const void* raw, uint32_t width, uint
     HIP_TRY(c, hipMemcpyAsync(st.raw.p, raw, bytes, hipMemcpyHostToDevice, s));
   }
   so_icp_feature_info li;
-  const int rc = run(c, s, st, st.raw.as<uint8_t>(), n, L, width, lidar_start_time, poses, n_poses, poses_are_imu, T_i_l, li);
-  if (rc) return rc;
-  if (n && nodistortion_out) HIP_TRY(c, hipMemcpyAsync(nodistortion_out, st.rec.p, (size_t)n * kFeatureRecordBytes, hipMemcpyDeviceToHost, s));
-  if (li.n_surface && surface_out) HIP_TRY(c, hipMemcpyAsync(surface_out, st.surf.p, (size_t)li.n_surface * kFeatureRecordBytes, hipMemcpyDeviceToHost, s));
-  HIP_TRY(c, hipStreamSynchronize(s));
+  if (const int rc = run_sweep(c, s, st, st.raw.as<uint8_t>(), n, L, width, lidar_start_time, poses, n_poses, poses_are_imu, T_i_l, li)) return rc;
+  if (const int rc = read_back(c, s, st, li, nodistortion_out, surface_out)) return rc;
   if (info) *info = li;
   return SO_ICP_OK;
 }
@@ -145,8 +220,52 @@ int so_icp_extract_features_dev(so_icp_ctx* c, const void* d_raw, uint32_t width
   FeatureState& st = *state_of(c);
   so_icp_feature_info li;
   // (the caller's device buffer: the context's queue, as so_icp_deskew_scan_dev)
-  const int rc = run(c, c->stream, st, static_cast<const uint8_t*>(d_raw), width * height, L, width, lidar_start_time, poses, n_poses,
-                     poses_are_imu, T_i_l, li);
+  const int rc = run_sweep(c, c->stream, st, static_cast<const uint8_t*>(d_raw), width * height, L, width, lidar_start_time, poses, n_poses,
+                           poses_are_imu, T_i_l, li);
+  if (rc) return rc;
+  if (d_nodistortion_out) *d_nodistortion_out = st.rec.p;
+  if (d_surface_out) *d_surface_out = st.surf.p;
+  if (info) *info = li;
+  return SO_ICP_OK;
+}
+
+void so_icp_livox_default_layout(so_icp_livox_layout* L) {
+  if (!L) return;
+  std::memset(L, 0, sizeof(*L));
+  // livox_ros_driver2/msg/CustomPoint: uint32 offset_time; float32 x, y, z; uint8 reflectivity, tag, line
+  L->point_step = 20;
+  L->off_offset_time = 0; L->off_x = 4; L->off_y = 8; L->off_z = 12; L->off_reflectivity = 16; L->off_tag = 17; L->off_line = 18;
+  L->n_scans = 4; L->filter_point_size = 3; L->min_range = 0.2f;  // featureExtraction.cpp:120-130
+  L->R_imu_laser_gravity[0] = L->R_imu_laser_gravity[4] = L->R_imu_laser_gravity[8] = 1.0;
+}
+
+int so_icp_extract_features_livox(so_icp_ctx* c, const void* raw, uint32_t n, const so_icp_livox_layout* L, double lidar_start_time,
+                                  const so_icp_stamped_pose* poses, size_t n_poses, int poses_are_imu, const double T_i_l[7],
+                                  void* nodistortion_out, void* surface_out, so_icp_feature_info* info) {
+  if (const int rc = check_livox_args(c, "so_icp_extract_features_livox", raw, n, L, poses, n_poses)) return rc;
+  HIP_TRY(c, hipSetDevice(c->cfg.device_id));
+  FeatureState& st = *state_of(c);
+  hipStream_t s = aux_stream(c);  // (host buffers in and out: as so_icp_extract_features)
+  if (n) {
+    const size_t bytes = livox_payload_bytes(n, L);
+    HIP_TRY(c, st.raw.reserve(bytes + 64));
+    HIP_TRY(c, hipMemcpyAsync(st.raw.p, raw, bytes, hipMemcpyHostToDevice, s));  // (pageable, straight from the message: see above)
+  }
+  so_icp_feature_info li;
+  if (const int rc = run_livox(c, s, st, st.raw.as<uint8_t>(), n, L, lidar_start_time, poses, n_poses, poses_are_imu, T_i_l, li)) return rc;
+  if (const int rc = read_back(c, s, st, li, nodistortion_out, surface_out)) return rc;
+  if (info) *info = li;
+  return SO_ICP_OK;
+}
+
+int so_icp_extract_features_livox_dev(so_icp_ctx* c, const void* d_raw, uint32_t n, const so_icp_livox_layout* L, double lidar_start_time,
+                                      const so_icp_stamped_pose* poses, size_t n_poses, int poses_are_imu, const double T_i_l[7],
+                                      void** d_nodistortion_out, void** d_surface_out, so_icp_feature_info* info) {
+  if (const int rc = check_livox_args(c, "so_icp_extract_features_livox_dev", d_raw, n, L, poses, n_poses)) return rc;
+  HIP_TRY(c, hipSetDevice(c->cfg.device_id));
+  FeatureState& st = *state_of(c);
+  so_icp_feature_info li;
+  const int rc = run_livox(c, c->stream, st, static_cast<const uint8_t*>(d_raw), n, L, lidar_start_time, poses, n_poses, poses_are_imu, T_i_l, li);
   if (rc) return rc;
   if (d_nodistortion_out) *d_nodistortion_out = st.rec.p;
   if (d_surface_out) *d_surface_out = st.surf.p;

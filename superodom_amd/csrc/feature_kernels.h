@@ -17,6 +17,14 @@ struct SweepFields {
   double ouster_t[3];
 };
 
+// where the fields of one livox_ros_driver2 CustomPoint are (all present), livoxHandler's line gate and its rotation
+struct LivoxFields {
+  uint32_t point_step;
+  uint32_t offset_time, x, y, z, reflectivity, tag, line;  // uint32 ns; float; uint8
+  uint32_t n_scans;                                        // config_.N_SCANS
+  double R[9];                                             // imu_laser_R_Gravity (identity while the IMU buffer is empty), row-major
+};
+
 // bytes of one record of either output cloud: point_os::PointcloudXYZITR and pcl::PointXYZI are both 32 bytes
 constexpr uint32_t kFeatureRecordBytes = 32;
 // surf-sampling candidates per workgroup of the compaction, and the look-back words it needs
@@ -27,6 +35,9 @@ inline uint32_t surf_workgroups(uint32_t n, uint32_t s) { return (surf_candidate
 // payload -> PointcloudXYZITR records (d_rec, 32 B each), de-skewed when n_poses > 0 (d_n_clamped zeroed by the caller)
 void launch_ingest_deskew(const uint8_t* d_raw, uint32_t n, const SweepFields& sf, uint8_t* d_rec, double t0, const double* d_poses,
                           uint32_t n_poses, const DeskewFrames& f, uint32_t* d_n_clamped, hipStream_t s);
+// the same for a Livox CustomMsg's points (livoxHandler, :794-806): n points point_step bytes apart, d_raw at any alignment
+void launch_livox_ingest_deskew(const uint8_t* d_raw, uint32_t n, const LivoxFields& lf, uint8_t* d_rec, double t0, const double* d_poses,
+                                uint32_t n_poses, const DeskewFrames& f, uint32_t* d_n_clamped, hipStream_t s);
 // uniformFeatureExtraction over the records: pcl::PointXYZI records into d_surf, their number into *d_n_surf.
 // d_state (surf_workgroups words) and d_ticket zeroed by the caller.
 void launch_surf_sample(const uint8_t* d_rec, uint32_t n, uint32_t step, float min_range, uint8_t* d_surf, uint32_t* d_n_surf,

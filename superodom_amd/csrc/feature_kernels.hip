@@ -90,6 +90,68 @@ void launch_ingest_deskew(const uint8_t* d_raw, uint32_t n, const SweepFields& s
   else launch_ingest_a<false>(d_raw, n, sf, d_rec, t0, d_poses, n_poses, f, d_n_clamped, s);
 }
 
+// livoxHandler's loop (:794-806) fused with removePointDistortion, a kernel of its own beside ingest_deskew_kernel (whose code
+// it leaves as it is): one thread per livox_ros_driver2 CustomPoint, the same records out.  A4: base, point_step and the offsets
+// of the four 4-byte fields are multiples of 4, those load as dwords; the three uint8 fields are byte loads either way, so nothing
+// behind a point's last field is read (the last CustomPoint of a CDR sequence has 19 bytes, not 20).
+template <bool A4, bool DESKEW, bool LDS>
+__global__ __launch_bounds__(256) void livox_ingest_deskew_kernel(const uint8_t* __restrict__ raw, uint32_t n, LivoxFields lf, uint8_t* __restrict__ out,
+                                                                  double t0, const double* __restrict__ poses, uint32_t n_poses, DeskewFrames f,
+                                                                  uint32_t* __restrict__ n_clamped) {
+  __shared__ double tab_lds[(DESKEW && LDS) ? kIngestLdsPoses * kStampedPoseDoubles : 1];
+  if (DESKEW && LDS) {
+    for (uint32_t k = threadIdx.x; k < n_poses * kStampedPoseDoubles; k += blockDim.x) tab_lds[k] = poses[k];
+    __syncthreads();
+  }
+  const double* tab = (DESKEW && LDS) ? tab_lds : poses;
+  const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+  bool clamped = false;
+  if (i < n) {
+    const uint8_t* p = raw + (size_t)i * lf.point_step;
+    const uint32_t line = p[lf.line], tag = p[lf.tag] & 0x30u;
+    // a point the handler skips keeps the value-initialised record of points.resize(point_num)
+    float x = 0.0f, y = 0.0f, z = 0.0f, intensity = 0.0f, time = 0.0f;
+    uint32_t ring = 0u;
+    if (line < lf.n_scans && (tag == 0x10u || tag == 0x00u)) {
+      // rotation_matrix * Vector3d(x, y, z): Eigen's coefficient product, left to right, unfused (-ffp-contract=off); rounded to float
+      const double px = (double)load_field<A4, float>(p + lf.x), py = (double)load_field<A4, float>(p + lf.y),
+                   pz = (double)load_field<A4, float>(p + lf.z);
+      x = (float)((lf.R[0] * px + lf.R[1] * py) + lf.R[2] * pz);
+      y = (float)((lf.R[3] * px + lf.R[4] * py) + lf.R[5] * pz);
+      z = (float)((lf.R[6] * px + lf.R[7] * py) + lf.R[8] * pz);
+      intensity = (float)p[lf.reflectivity];
+      time = __fdiv_rn((float)load_field<A4, uint32_t>(p + lf.offset_time), 1000000000.0f);  // offset_time / float(1000000000), :803
+      ring = line;
+    }
+    if (DESKEW) clamped = deskew_point(tab, n_poses, t0, time, f, x, y, z);  // removePointDistortion, :293-306: the zero records too
+    uint4* o = reinterpret_cast<uint4*>(out + (size_t)i * kFeatureRecordBytes);
+    o[0] = make_uint4(__float_as_uint(x), __float_as_uint(y), __float_as_uint(z), 0u);
+    o[1] = make_uint4(__float_as_uint(intensity), __float_as_uint(time), ring, 0u);
+  }
+  if (DESKEW) {
+    const unsigned long long m = __ballot(clamped);
+    if (m && (threadIdx.x & 63) == (uint32_t)__builtin_ctzll(m)) atomicAdd(n_clamped, (uint32_t)__popcll(m));
+  }
+}
+
+template <bool A4>
+static void launch_livox_a(const uint8_t* d_raw, uint32_t n, const LivoxFields& lf, uint8_t* d_rec, double t0, const double* d_poses,
+                           uint32_t n_poses, const DeskewFrames& f, uint32_t* d_n_clamped, hipStream_t s) {
+  const uint32_t blocks = (n + 255u) / 256u;
+  if (!n_poses) livox_ingest_deskew_kernel<A4, false, false><<<blocks, 256, 0, s>>>(d_raw, n, lf, d_rec, t0, d_poses, 0u, f, d_n_clamped);
+  else if (n_poses <= kIngestLdsPoses) livox_ingest_deskew_kernel<A4, true, true><<<blocks, 256, 0, s>>>(d_raw, n, lf, d_rec, t0, d_poses, n_poses, f, d_n_clamped);
+  else livox_ingest_deskew_kernel<A4, true, false><<<blocks, 256, 0, s>>>(d_raw, n, lf, d_rec, t0, d_poses, n_poses, f, d_n_clamped);
+}
+
+void launch_livox_ingest_deskew(const uint8_t* d_raw, uint32_t n, const LivoxFields& lf, uint8_t* d_rec, double t0, const double* d_poses,
+                                uint32_t n_poses, const DeskewFrames& f, uint32_t* d_n_clamped, hipStream_t s) {
+  if (!n) return;
+  bool a4 = (reinterpret_cast<uintptr_t>(d_raw) % 4u) == 0 && lf.point_step % 4u == 0;
+  for (uint32_t off : {lf.offset_time, lf.x, lf.y, lf.z}) a4 = a4 && off % 4u == 0;
+  if (a4) launch_livox_a<true>(d_raw, n, lf, d_rec, t0, d_poses, n_poses, f, d_n_clamped, s);
+  else launch_livox_a<false>(d_raw, n, lf, d_rec, t0, d_poses, n_poses, f, d_n_clamped, s);
+}
+
 // uniformFeatureExtraction, featureExtraction.cpp:507-522: candidates i = 1, 1 + s, 1 + 2s, ... < n, each against the RAW record
 // i - 1, kept when  |dx| > 1e-7 || |dy| > 1e-7 || (|dz| > 1e-7 && x*x + y*y + z*z > r*r)  -- C++ precedence: the range gate only
 // goes with the z test.  The differences and abs are float (the float overload), compared in double; the squared norm and r*r are

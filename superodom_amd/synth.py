@@ -323,3 +323,56 @@ class Scene:
 
     def guess(self, i, dt=0.10, dth_deg=1.0, seed_base=1000):
         return perturb_pose(self.gt_pose(i), seed_base + i, dt, dth_deg)
+
+
+# --------------------------------------------------------------------------------------------
+# Livox CustomMsg sweeps (livox_ros_driver2/msg/CustomPoint: uint32 offset_time; float32 x, y, z; uint8 reflectivity, tag, line)
+# --------------------------------------------------------------------------------------------
+LIVOX_POINT_STEP = 20  # CustomPoint[] in CDR and in C++: 19 bytes of fields, elements 4-byte aligned
+
+
+def livox_sweep(n=20000, seed=0, reject_share=0.06, sweep_s=0.1, n_lines=4, xyz=None):
+    """A seeded Mid-360-like sweep as CustomPoint field arrays: n points in the order a non-repetitive rosette visits them (azimuth
+    and elevation advance at incommensurate rates, the n_lines laser lines interleaved), offset_time rising over sweep_s with
+    jitter, and about reject_share of the points marked the way livoxHandler rejects them: two thirds by tag ((tag & 0x30) of 0x20
+    or 0x30, partly in runs of two), one third by a line >= n_lines.  xyz: [n, 3] sensor-frame points to carry instead of the built-in
+    box room (e.g. Scene.scan()); they are visited in a seeded shuffled order.  Returns a dict of arrays, ready for livox_points()."""
+    rng = np.random.default_rng(seed)
+    if xyz is None:
+        t = (np.arange(n) + rng.random(n) * 0.5) / n
+        az = 2 * np.pi * 17.0 * t * (np.sqrt(5.0) - 1.0)
+        el = np.deg2rad(22.5 + 29.5 * np.sin(2 * np.pi * 13.0 * np.sqrt(2.0) * t)) + np.deg2rad(1.1) * (np.arange(n) % n_lines)
+        d = np.stack([np.cos(el) * np.cos(az), np.cos(el) * np.sin(az), np.sin(el)], 1)
+        with np.errstate(divide="ignore"):  # a 36 m x 22 m x 4.8 m room around the sensor
+            r = np.min(np.where(d > 0, np.array([18.0, 11.0, 3.2]) / d, np.where(d < 0, np.array([-18.0, -11.0, -1.6]) / d, np.inf)), 1)
+        xyz = d * (r * (1 + rng.normal(0, 0.002, n)))[:, None]
+    else:
+        xyz = np.asarray(xyz, np.float32).reshape(-1, 3)
+        n = len(xyz)
+        xyz = xyz[rng.permutation(n)]
+    xyz = np.ascontiguousarray(xyz, np.float32)
+    step_ns = sweep_s * 1e9 / n
+    offset_time = np.floor(np.arange(n) * step_ns + rng.random(n) * step_ns).astype(np.uint32)
+    line = (np.arange(n) % n_lines).astype(np.uint8)
+    tag = (rng.integers(0, 16, n) | (rng.integers(0, 4, n) << 6) | np.where(rng.random(n) < 0.5, 0x10, 0x00)).astype(np.uint8)
+    k_tag = max(int(n * reject_share * 2 / 3), 1)
+    at = rng.choice(n - 1, k_tag // 2 + 1, replace=False)
+    at = np.unique(np.concatenate([at, at[: len(at) // 2] + 1]))  # half of them followed by a second rejected point
+    tag[at] = (tag[at] & 0xCF) | np.where(rng.random(len(at)) < 0.5, 0x20, 0x30).astype(np.uint8)
+    at_line = rng.choice(n, max(int(n * reject_share / 3), 1), replace=False)
+    line[at_line] = n_lines + rng.integers(0, 4, len(at_line)).astype(np.uint8)
+    return {"offset_time": offset_time, "x": xyz[:, 0].copy(), "y": xyz[:, 1].copy(), "z": xyz[:, 2].copy(),
+            "reflectivity": rng.integers(0, 256, n).astype(np.uint8), "tag": tag, "line": line}
+
+
+def livox_points(vals, point_step=LIVOX_POINT_STEP, trim_last=True, fill=0):
+    """The `points` bytes of a CustomMsg: CustomPoint records point_step (>= 19) bytes apart, fields at 0 / 4 8 12 / 16 17 18; bytes
+    no field covers hold `fill`.  trim_last: the last record ends with its last field, as the CDR sequence does."""
+    n = len(vals["x"])
+    buf = np.full((n, point_step), fill, np.uint8)
+    for name, off, dt in (("offset_time", 0, np.uint32), ("x", 4, np.float32), ("y", 8, np.float32), ("z", 12, np.float32)):
+        buf[:, off:off + 4] = np.ascontiguousarray(vals[name], dt).view(np.uint8).reshape(n, 4)
+    for name, off in (("reflectivity", 16), ("tag", 17), ("line", 18)):
+        buf[:, off] = np.asarray(vals[name], np.uint8)
+    buf = buf.reshape(-1)
+    return buf[:len(buf) - (point_step - 19)].copy() if trim_last and n else buf

@@ -5,8 +5,11 @@
   * the resident chain sweep -> features -> so_icp_prefilter_scan_dev -> so_icp_localization_dev against the same chain through
     host buffers (so_icp_extract_features -> so_icp_prefilter_scan -> so_icp_localization), ms per frame
   * the CPU restatement (numpy ingest and sampling + the C oracle's de-skew, one core), labelled as such
-    python tools/feature_extraction_rate.py [--reps N] [--kernels-only]
---kernels-only: only the resident entry, for a rocprofv3 --kernel-trace --stats run."""
+    python tools/feature_extraction_rate.py [--reps N] [--kernels-only] [--livox]
+--kernels-only: only the resident entry, for a rocprofv3 --kernel-trace --stats run.
+--livox: the same rows for so_icp_extract_features_livox instead (results in profiles/feature_extraction/rate_livox.txt): seeded
+Mid-360-like sweeps (synth.livox_sweep) of 20 000 and of 131 072 CustomPoints, R = a few degrees of roll and pitch, the chain at
+the livox_mid360 operating point (planeRes 0.1, 4 000 surface features)."""
 import ctypes as C
 import os
 import sys
@@ -18,7 +21,8 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path[:0] = [ROOT, os.path.join(ROOT, "oracle"), os.path.join(ROOT, "tests")]
 import deskew_data as dd  # noqa: E402
 import feature_extraction_ref as fr  # noqa: E402
-from superodom_amd import binding  # noqa: E402
+import livox_ref as lr  # noqa: E402
+from superodom_amd import binding, synth  # noqa: E402
 
 T0 = 1.7e9 + 0.25
 
@@ -114,9 +118,75 @@ def rates(name, buf, w, h, rs, sensor, reps, kernels_only):
     print(f"  CPU restatement (numpy ingest + sampling, C oracle de-skew; one core, not the reference's code) {cpu_ms:.1f} ms")
 
 
+def rates_livox(n, reps, kernels_only):
+    hip = _hip()
+    vals = synth.livox_sweep(n=n, seed=1)
+    buf = synth.livox_points(vals)
+    layout = binding.livox_layout(3, 0.2, R_imu_laser_gravity=lr.R_TILT)
+    poses = dd.pose_buffer(T0, seed=22, translate=False)
+    slam = binding.LidarSlamGpu(plane_res=0.1, line_res=0.05, max_surface_features=4000, max_iterations=4)
+    d_raw = C.c_void_p()
+    assert hip.hipMalloc(C.byref(d_raw), buf.nbytes) == 0
+    assert hip.hipMemcpy(d_raw, buf.ctypes.data_as(C.c_void_p), buf.nbytes, 1) == 0
+    info = [None]
+
+    def dev():
+        info[0] = slam.extract_features_livox_dev(d_raw.value, n, layout, T0, poses, True, None)[2]
+    if kernels_only:
+        for _ in range(reps):
+            dev()
+        hip.hipFree(d_raw)
+        return
+
+    def host():
+        slam.extract_features_livox(buf, n, layout, T0, poses, True, None)
+    host_ms = _best_ms(host, reps)
+    dev_ms = _best_ms(dev, reps)
+
+    # chains: a map seeded with the first frame, then every call registers (and inserts) the same sweep again
+    chain = {}
+    for mode in ("host", "dev"):
+        s = binding.LidarSlamGpu(plane_res=0.1, line_res=0.05, max_surface_features=4000, max_iterations=4)
+        pose = np.array([0, 0, 0, 0, 0, 0, 1.0])
+        k = [0]
+
+        def step(first=False):
+            t = T0 + 0.1 * k[0]
+            k[0] += 1
+            if mode == "dev":
+                _, ds, inf = s.extract_features_livox_dev(d_raw.value, n, layout, T0, poses, True, None)
+                dp, nf, _ = s.prefilter_scan_dev(ds, inf.n_surface, 32, 1, 0.05, 0.1)
+                rc, _, _ = s.localization_dev(0 if first else 1, pose, dp, nf, t)
+            else:
+                _, sf, _ = s.extract_features_livox(buf, n, layout, T0, poses, True, None)
+                dp, nf, _ = s.prefilter_scan(sf.view(np.float32)[:, :3], 1, 0.05, 0.1)
+                rc, _, _ = s.localization(0 if first else 1, pose, s.download_scan(dp, nf), t)
+            assert rc in (0, 2), rc
+        step(first=True)
+        chain[mode] = _best_ms(step, max(reps // 5, 5))
+        s.close()
+    hip.hipFree(d_raw)
+
+    t = time.perf_counter()
+    import oracle_py
+    rec = lr.ingest(vals, lr.R_TILT)
+    rec, _, _ = oracle_py.deskew(rec, 20, T0, poses, True, None)
+    fr.surf_sample(rec, 3, 0.2)
+    cpu_ms = 1e3 * (time.perf_counter() - t)
+    print(f"Livox CustomMsg, Mid-360-like: {n} points ({buf.nbytes} bytes), {len(poses)} IMU poses, filter_point_size 3 -> {info[0].n_surface} surf points")
+    print(f"  host payload in, both clouds out  {host_ms:.3f} ms")
+    print(f"  resident in HBM                   {dev_ms:.3f} ms  (pose table upload + 2 kernels + count read-back)")
+    print(f"  chain features -> prefilter -> localization (planeRes 0.1, 4000 features): resident {chain['dev']:.3f} ms, through host buffers {chain['host']:.3f} ms per frame")
+    print(f"  CPU restatement (numpy ingest + sampling, C oracle de-skew; one core, not the reference's code) {cpu_ms:.1f} ms")
+
+
 def main():
     reps = int(sys.argv[sys.argv.index("--reps") + 1]) if "--reps" in sys.argv else 50
     ko = "--kernels-only" in sys.argv
+    if "--livox" in sys.argv:
+        for n in (20000, 131072):
+            rates_livox(n, reps, ko)
+        return
     buf, w, h, rs, _ = fr.ouster_sweep(1024, 128, seed=1, nan_every=997, zero_every=61)
     rates("os1_128-like Ouster", buf, w, h, rs, fr.SENSOR_OUSTER, reps, ko)
     buf, w, h, rs, _ = fr.velodyne_sweep(28800, seed=1, nan_every=499, zero_every=73)
