@@ -391,20 +391,15 @@ void laserMapping::publishTopic() {  // :415-597
     static const size_t device_min = std::getenv("SOICP_NODE_DEVICE_TRANSFORM_MIN") ? (size_t)std::atol(std::getenv("SOICP_NODE_DEVICE_TRANSFORM_MIN")) : 4096;
     if (n >= device_min && n && out_ && fullRes_.point_step == sizeof(Point) && L0.contiguous && L0.off_x == 0 && L0.has_intensity && L0.off_intensity == 16) {
       // the message already holds pcl::PointXYZI records: they go into the payload area of the outgoing message -- assembled in a pinned
-      // buffer, so that both copies of so_icp_transform_cloud are DMA transfers --, are transformed there by the device, and the rare
-      // dropped points are squeezed out in place.  (The serialised prefix has the same length whatever the point count.)
+      // buffer, so that both copies of so_icp_registered_scan are DMA transfers --, and come back there from the device transformed,
+      // with the dropped points already squeezed out.  (The serialised prefix has the same length whatever the point count.)
       so_wire::PointCloud2 meta = to_ros_msg(PointCloud<Point>());
       meta.header.stamp = stamp; meta.header.frame_id = config_.WORLD_FRAME;
       const size_t psize = so_wire::cloud_prefix(meta, 0).size();
       uint8_t* buf = slam.PinnedScratch(1, psize + n * sizeof(Point) + 1);
       std::memcpy(buf + psize, fullRes_.data.data(), n * sizeof(Point));
       Transformd Tw; Tw.rot = q_w_curr; Tw.pos = t_w_curr;
-      std::vector<uint8_t> keep;
-      kept = slam.TransformCloud(buf + psize, n, sizeof(Point), Tw, keep);
-      if (kept != n) {
-        size_t o = 0;
-        for (size_t i = 0; i < n; ++i) if (keep[i]) { if (o != i) std::memcpy(buf + psize + o * sizeof(Point), buf + psize + i * sizeof(Point), sizeof(Point)); ++o; }
-      }
+      kept = slam.RegisteredScan(buf + psize, n, sizeof(Point), Tw, buf + psize);
       meta.width = (uint32_t)kept; meta.row_step = meta.point_step * meta.width;
       const std::vector<uint8_t> prefix = so_wire::cloud_prefix(meta, kept * sizeof(Point));
       std::memcpy(buf, prefix.data(), psize);

@@ -187,6 +187,15 @@ size_t LidarSLAM::TransformCloud(void* points, size_t n, size_t stride_bytes, co
   return kept;
 }
 
+size_t LidarSLAM::RegisteredScan(const void* records, size_t n, size_t stride_bytes, const Transformd& T, void* out) {
+  ensure_context();
+  const double Tw[7] = {T.pos.x(), T.pos.y(), T.pos.z(), T.rot.x(), T.rot.y(), T.rot.z(), T.rot.w()};
+  size_t kept = 0;
+  if (so_icp_registered_scan(gpu_, records, n, stride_bytes, Tw, out, &kept) < 0)
+    throw std::runtime_error(std::string("so_icp_registered_scan: ") + so_icp_last_error(gpu_));
+  return kept;
+}
+
 uint8_t* LidarSLAM::PinnedScratch(int which, size_t bytes) {
   ensure_context();
   if ((size_t)which >= scratch_.size()) scratch_.resize((size_t)which + 1);

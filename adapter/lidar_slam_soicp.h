@@ -95,6 +95,9 @@ class LidarSLAM {
   // utils::pointAssociateToMap over a cloud (the registered scan of laserMapping::publishTopic, laserMapping.cpp:464-493) on the
   // device: records with float x y z at 0 4 8 rewritten in place, keep[i] = the node publishes point i
   size_t TransformCloud(void* points, size_t n, size_t stride_bytes, const Transformd& T, std::vector<uint8_t>& keep);
+  // the same registered scan as it is published (so_icp_registered_scan): the kept records, transformed, in order and packed into
+  // `out` (room for n records; out == records squeezes in place); returns their number
+  size_t RegisteredScan(const void* records, size_t n, size_t stride_bytes, const Transformd& T, void* out);
   // A message buffer of at least `bytes` in pinned host memory (so_icp_host_alloc): copies between it and the device are DMA transfers.
   // One buffer per `which` (0, 1, ...), grown on demand, valid until the next call with the same index or the context's end.
   uint8_t* PinnedScratch(int which, size_t bytes);

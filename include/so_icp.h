@@ -515,6 +515,22 @@ int so_icp_prefilter_scan_dev(so_icp_ctx *ctx, const void *d_surf, size_t n, siz
  * result lies farther than 0.1 m from the world origin -- the node publishes only those; *n_kept (nullable) = their number. */
 int so_icp_transform_cloud(so_icp_ctx *ctx, void *points /* host, rewritten in place */, size_t n, size_t stride_bytes,
                            const double T_w_lidar[7], uint8_t *keep, size_t *n_kept);
+/* The same registered scan (laserMapping.cpp:464-493, utils::pointAssociateToMap, superodom_utils.cpp:148-158) as the node
+ * publishes it, from records already in HBM and complete (e.g. *d_nodistortion_out of so_icp_extract_features(_livox)_dev, stride
+ * 32): n records stride_bytes apart (>= 12, a multiple of 4; d_records 4-byte aligned; 16-byte aligned records with a stride that
+ * is a multiple of 16 take the wide loads), float x y z at byte 0 4 8, not modified.  The arithmetic is so_icp_transform_cloud's;
+ * a record whose result lies farther than 0.1 m from the world origin is kept: all its stride_bytes bytes with the three floats
+ * replaced, in the order of the input, packed at the same stride -- so_icp_transform_cloud followed by the caller's squeeze, bit
+ * for bit.  A NaN coordinate drops the record.  One launch, one copy, one synchronisation, on the auxiliary queue.
+ * out (host, nullable) has room for n records: n * stride_bytes bytes are copied, the bytes behind the first *n_kept records are
+ * unspecified.  *d_out (nullable) = a device buffer owned by the context with the same bytes, valid until the next
+ * so_icp_registered_scan(_dev) call; no other entry writes it, and this entry writes no other entry's buffers.
+ * n == 0: SO_ICP_OK, *n_kept = 0, *d_out = NULL.  SO_ICP_E_UNSUPPORTED for n >= 2^31. */
+int so_icp_registered_scan_dev(so_icp_ctx *ctx, const void *d_records, size_t n, size_t stride_bytes, const double T_w_lidar[7],
+                               void *out, void **d_out, size_t *n_kept);
+/* same from host records (any address; not modified unless out == records, which is allowed: the squeeze in place) */
+int so_icp_registered_scan(so_icp_ctx *ctx, const void *records, size_t n, size_t stride_bytes, const double T_w_lidar[7],
+                           void *out, size_t *n_kept);
 
 /* -------- multi-GPU: one process per GPU; the map is sharded by brick-hash of the voxel grid and the 45 fp64 sums of every
  * evaluation are summed over the ranks: by RCCL (below), by an in-process group, or by the solve launches themselves

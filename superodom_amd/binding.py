@@ -168,7 +168,8 @@ EXPORTED = ["so_icp_default_config", "so_icp_create", "so_icp_destroy", "so_icp_
             "so_icp_host_register", "so_icp_host_unregister", "so_icp_host_alloc", "so_icp_host_free", "so_icp_device_count", "so_icp_stage_cancel",
             "so_icp_map_insert_stats", "so_icp_register_sequence", "so_icp_map_export_records", "so_icp_sequence_announce_next", "so_icp_debug_neighbours", "so_icp_prefilter_announce",
             "so_icp_localization_sequence", "so_icp_extract_features", "so_icp_extract_features_dev", "so_icp_prefilter_scan_dev",
-            "so_icp_livox_default_layout", "so_icp_extract_features_livox", "so_icp_extract_features_livox_dev"]
+            "so_icp_livox_default_layout", "so_icp_extract_features_livox", "so_icp_extract_features_livox_dev",
+            "so_icp_registered_scan", "so_icp_registered_scan_dev"]
 
 _lib = None
 
@@ -231,6 +232,8 @@ def load():
         fn.argtypes = [vp, vp, C.c_size_t, C.c_size_t, C.c_size_t, C.c_double, C.POINTER(C.c_double), C.c_size_t, C.c_int, C.POINTER(C.c_double),
                        C.POINTER(DeskewInfo)]
     L.so_icp_transform_cloud.argtypes = [vp, vp, C.c_size_t, C.c_size_t, C.POINTER(C.c_double), C.POINTER(C.c_uint8), C.POINTER(C.c_size_t)]
+    L.so_icp_registered_scan.argtypes = [vp, vp, C.c_size_t, C.c_size_t, C.POINTER(C.c_double), vp, C.POINTER(C.c_size_t)]
+    L.so_icp_registered_scan_dev.argtypes = [vp, vp, C.c_size_t, C.c_size_t, C.POINTER(C.c_double), vp, C.POINTER(vp), C.POINTER(C.c_size_t)]
     L.so_icp_prefilter_announce.argtypes = [vp, f32p, C.c_size_t, C.c_size_t]
     L.so_icp_prefilter_scan.argtypes = [vp, f32p, C.c_size_t, C.c_size_t, C.c_int, C.c_float, C.c_float, C.POINTER(vp),
                                         C.POINTER(C.c_size_t), C.POINTER(PrefilterInfo)]
@@ -669,6 +672,33 @@ class LidarSlamGpu:
         self._check(self.L.so_icp_transform_cloud(self.h, rec.ctypes.data_as(C.c_void_p), rec.shape[0], rec.shape[1], _p(T, C.c_double),
                                                   _p(keep, C.c_uint8), C.byref(nk)))
         return rec, keep, nk.value
+
+    def registered_scan(self, records, T_w_lidar, in_place=False):
+        """the node's registered scan as it is published (so_icp_registered_scan): records uint8 [n, stride], float x y z at 0 4 8 ->
+        the kept records, transformed, in order: uint8 [n_kept, stride].  in_place: `records` (a contiguous uint8 array) is also the
+        output buffer, and the result is a view of its first n_kept records."""
+        T = np.ascontiguousarray(T_w_lidar, np.float64)
+        if in_place:
+            assert isinstance(records, np.ndarray) and records.dtype == np.uint8 and records.ndim == 2 and records.flags.c_contiguous
+            rec = out = records
+        else:
+            rec = np.ascontiguousarray(records, np.uint8)
+            out = np.empty_like(rec)
+        nk = C.c_size_t(0)
+        self._check(self.L.so_icp_registered_scan(self.h, rec.ctypes.data_as(C.c_void_p), rec.shape[0], rec.shape[1], _p(T, C.c_double),
+                                                  out.ctypes.data_as(C.c_void_p), C.byref(nk)))
+        return out[:nk.value]
+
+    def registered_scan_dev(self, d_records, n, stride, T_w_lidar, want_host=True):
+        """the same from records resident in HBM (d_records: device address, e.g. extract_features_dev's d_nodistortion), which stay as
+        they are.  Returns (kept records uint8 [n_kept, stride] or None, d_out, n_kept): d_out is a context-owned device buffer
+        with the same bytes, valid until the next registered_scan(_dev) call."""
+        T = np.ascontiguousarray(T_w_lidar, np.float64)
+        out = np.empty((int(n), int(stride)), np.uint8) if want_host else None
+        d = C.c_void_p(); nk = C.c_size_t(0)
+        self._check(self.L.so_icp_registered_scan_dev(self.h, C.c_void_p(d_records), int(n), int(stride), _p(T, C.c_double),
+                                                      None if out is None else out.ctypes.data_as(C.c_void_p), C.byref(d), C.byref(nk)))
+        return (None if out is None else out[:nk.value]), d.value, nk.value
 
     def deskew_scan_dev(self, d_records, n, stride, time_off, lidar_start_time, poses, poses_are_imu, T_i_l=None):
         """the same on records resident in HBM (d_records: device address), rewritten there; returns DeskewInfo"""

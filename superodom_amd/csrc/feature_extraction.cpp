@@ -5,6 +5,9 @@
 // The node's bookkeeping around it (frame skipping, the sweep and pose buffers, the branch choice, the LaserFeature message) stays
 // with the caller; this entry takes one sweep and the pose buffer the branch chose, and returns cloud_nodistortion and
 // cloud_surface.  Kernels: feature_kernels.hip.  The per-scan de-skew constants are deskew_setup's, as for so_icp_deskew_scan.
+//
+// so_icp_registered_scan(_dev) closes the resident chain behind them: laserMapping::publishTopic's registered scan
+// (src/LaserMapping/laserMapping.cpp:464-493) from the records that pass left in HBM, transformed and compacted in one launch.
 #include <algorithm>
 #include <cstring>
 #include <string>
@@ -180,6 +183,53 @@ int read_back(so_icp_ctx* c, hipStream_t s, FeatureState& st, const so_icp_featu
   return SO_ICP_OK;
 }
 
+// device state of so_icp_registered_scan(_dev), owned by the context (so_icp_ctx::rs_state): nothing of it is the feature
+// extraction's or the pre-filter's, so those entries leave *d_out alone and this one leaves their clouds alone
+struct RegisteredScanState {
+  DevBuf in;     // the records (host entry)
+  DevBuf out;    // the registered scan
+  DevBuf small;  // counters {n_kept, ticket, -, -} | look-back words of the compaction
+  uint32_t* h_kept = nullptr;  // pinned read-back of n_kept
+  ~RegisteredScanState() {
+    for (DevBuf* b : {&in, &out, &small}) b->release();
+    if (h_kept) (void)hipHostFree(h_kept);
+  }
+};
+
+int check_registered_scan_args(so_icp_ctx* c, const void* records, size_t n, size_t stride, const double T[7], bool on_device) {
+  if (!c || !T || (!records && n)) return SO_ICP_E_INVALID;
+  if (stride < 12 || stride % 4) return fail(c, SO_ICP_E_INVALID, "records: float x y z at 0 4 8, stride a multiple of 4");
+  if (on_device && reinterpret_cast<uintptr_t>(records) % 4u) return fail(c, SO_ICP_E_INVALID, "records: the device address must be 4-byte aligned");
+  if (n >= ((size_t)1 << 31)) return fail(c, SO_ICP_E_UNSUPPORTED, "too many points");
+  NEED_DEVICE(c);
+  return SO_ICP_OK;
+}
+
+// on queue s: counters and look-back words cleared, one launch, [the copy to `out`] and the count enqueued together, one wait
+int run_registered_scan(so_icp_ctx* c, hipStream_t s, RegisteredScanState& st, const uint8_t* d_rec, size_t n, size_t stride, const double T[7],
+                        void* out, size_t* n_kept) {
+  const size_t state_off = 16, small_bytes = state_off + (size_t)registered_scan_workgroups((uint32_t)n) * 8;
+  HIP_TRY(c, st.out.reserve(n * stride + 64));
+  HIP_TRY(c, st.small.reserve(small_bytes));
+  if (!st.h_kept) HIP_TRY(c, hipHostMalloc(reinterpret_cast<void**>(&st.h_kept), 64));
+  uint32_t* d_counts = st.small.as<uint32_t>();
+  HIP_TRY(c, hipMemsetAsync(st.small.p, 0, small_bytes, s));
+  launch_registered_scan(d_rec, (uint32_t)n, (uint32_t)stride, pose_from_array(T), st.out.as<uint8_t>(), d_counts,
+                         reinterpret_cast<unsigned long long*>(st.small.as<uint8_t>() + state_off), d_counts + 1, s);
+  HIP_TRY(c, hipGetLastError());
+  // all n records' room rather than a second wait for the count first; the count through a pinned word, as so_icp_transform_cloud's
+  if (out) HIP_TRY(c, hipMemcpyAsync(out, st.out.p, n * stride, hipMemcpyDeviceToHost, s));
+  HIP_TRY(c, hipMemcpyAsync(st.h_kept, d_counts, 4, hipMemcpyDeviceToHost, s));
+  HIP_TRY(c, hipStreamSynchronize(s));
+  if (n_kept) *n_kept = *st.h_kept;
+  return SO_ICP_OK;
+}
+
+RegisteredScanState* registered_scan_state_of(so_icp_ctx* c) {
+  if (!c->rs_state) c->rs_state = std::make_shared<RegisteredScanState>();
+  return static_cast<RegisteredScanState*>(c->rs_state.get());
+}
+
 FeatureState* state_of(so_icp_ctx* c) {
   if (!c->fe_state) c->fe_state = std::make_shared<FeatureState>();
   return static_cast<FeatureState*>(c->fe_state.get());
@@ -271,6 +321,34 @@ int so_icp_extract_features_livox_dev(so_icp_ctx* c, const void* d_raw, uint32_t
   if (d_surface_out) *d_surface_out = st.surf.p;
   if (info) *info = li;
   return SO_ICP_OK;
+}
+
+// laserMapping::publishTopic's registered scan, laserMapping.cpp:464-493 with utils::pointAssociateToMap, superodom_utils.cpp:148-158
+// (kernel: feature_kernels.hip registered_scan_kernel).  The auxiliary queue, as so_icp_transform_cloud: beside the map insert that
+// so_icp_localization left in the context's queue.
+int so_icp_registered_scan_dev(so_icp_ctx* c, const void* d_records, size_t n, size_t stride, const double T[7], void* out, void** d_out,
+                               size_t* n_kept) {
+  if (const int rc = check_registered_scan_args(c, d_records, n, stride, T, true)) return rc;
+  HIP_TRY(c, hipSetDevice(c->cfg.device_id));
+  if (n_kept) *n_kept = 0;
+  if (d_out) *d_out = nullptr;
+  if (!n) return SO_ICP_OK;
+  RegisteredScanState& st = *registered_scan_state_of(c);
+  if (const int rc = run_registered_scan(c, aux_stream(c), st, static_cast<const uint8_t*>(d_records), n, stride, T, out, n_kept)) return rc;
+  if (d_out) *d_out = st.out.p;
+  return SO_ICP_OK;
+}
+
+int so_icp_registered_scan(so_icp_ctx* c, const void* records, size_t n, size_t stride, const double T[7], void* out, size_t* n_kept) {
+  if (const int rc = check_registered_scan_args(c, records, n, stride, T, false)) return rc;
+  HIP_TRY(c, hipSetDevice(c->cfg.device_id));
+  if (n_kept) *n_kept = 0;
+  if (!n) return SO_ICP_OK;
+  RegisteredScanState& st = *registered_scan_state_of(c);
+  hipStream_t s = aux_stream(c);
+  HIP_TRY(c, st.in.reserve(n * stride + 64));
+  HIP_TRY(c, hipMemcpyAsync(st.in.p, records, n * stride, hipMemcpyHostToDevice, s));
+  return run_registered_scan(c, s, st, st.in.as<uint8_t>(), n, stride, T, out, n_kept);
 }
 
 }  // extern "C"

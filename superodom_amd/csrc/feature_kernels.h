@@ -7,6 +7,7 @@
 namespace soicp {
 
 struct DeskewFrames;
+struct Pose;
 
 // where the fields of one sensor_msgs::PointCloud2 point are (pcl::fromROSMsg's field match, done by the caller); -1: absent
 struct SweepFields {
@@ -42,5 +43,12 @@ void launch_livox_ingest_deskew(const uint8_t* d_raw, uint32_t n, const LivoxFie
 // d_state (surf_workgroups words) and d_ticket zeroed by the caller.
 void launch_surf_sample(const uint8_t* d_rec, uint32_t n, uint32_t step, float min_range, uint8_t* d_surf, uint32_t* d_n_surf,
                         unsigned long long* d_state, uint32_t* d_ticket, hipStream_t s);
+
+// laserMapping::publishTopic's registered scan: n records `stride` bytes apart (float x y z at 0 4 8, stride a multiple of 4, d_rec
+// 4-byte aligned; not modified) -> the kept ones, transformed, in order and packed at the same stride into d_out (room for n, must not
+// overlap d_rec), their number into *d_n_kept.  d_state (registered_scan_workgroups words), d_ticket and *d_n_kept zeroed by the caller.
+inline uint32_t registered_scan_workgroups(uint32_t n) { return (n + kSurfItems - 1u) / kSurfItems; }
+void launch_registered_scan(const uint8_t* d_rec, uint32_t n, uint32_t stride, const Pose& pose, uint8_t* d_out, uint32_t* d_n_kept,
+                            unsigned long long* d_state, uint32_t* d_ticket, hipStream_t s);
 
 }  // namespace soicp

@@ -4,6 +4,8 @@
 //                         point_os::PointcloudXYZITR records out (the LaserFeature's cloud_nodistortion)
 //   surf_sample_kernel    uniformFeatureExtraction (:504-525): an order-preserving compaction into pcl::PointXYZI records
 //                         (cloud_surface), one launch with a decoupled look-back across workgroups
+// and, for the records that pass leaves in HBM, laserMapping::publishTopic's registered scan (src/LaserMapping/laserMapping.cpp:464-493):
+//   registered_scan_kernel  utils::pointAssociateToMap over the cloud and the drop of points at the world origin, compacted
 // The de-skew arithmetic is deskew_math.h's, as in map_kernels.hip deskew_kernel: the same header functions in the same order,
 // so the records equal that kernel's run on the ingested sweep bit for bit.
 #include <hip/hip_runtime.h>
@@ -246,6 +248,129 @@ void launch_surf_sample(const uint8_t* d_rec, uint32_t n, uint32_t step, float m
   const uint32_t nblk = surf_workgroups(n, step);
   if (!nblk) return;
   surf_sample_kernel<<<nblk, 256, 0, s>>>(d_rec, surf_candidates(n, step), step, min_range, d_surf, d_n_surf, d_state, d_ticket, nblk);
+}
+
+// surf_sample_kernel's decoupled look-back as a function, for registered_scan_kernel below: run by the first wavefront of workgroup
+// `bid` (ticket order) once it knows `agg`, the number it keeps.  Records = flag << 62 | value (flag 1: this workgroup's own count,
+// 2: the count up to and including it), all zero before the launch, vector atomics at agent scope.  Publishes agg, walks back 64
+// records at a time until a flag-2 record, publishes the inclusive count and returns the number kept in front of the workgroup
+// (on every lane).  surf_sample_kernel keeps its own copy in line: calling this from it changes its register allocation and
+// instruction order, and that kernel's code stays as measured.
+__device__ __forceinline__ uint32_t lookback_exclusive(unsigned long long* state, uint32_t bid, uint32_t agg, int lane) {
+  if (lane == 0) __hip_atomic_store(&state[bid], ((bid == 0u ? 2ull : 1ull) << 62) | (unsigned long long)agg, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+  uint32_t excl = 0;
+  int base = (int)bid - 1;
+  while (base >= 0) {
+    const int j = base - lane;
+    unsigned long long r = 2ull << 62;
+    if (j >= 0) {
+      do { r = __hip_atomic_load(&state[j], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); } while ((r >> 62) == 0ull);
+    }
+    const unsigned long long mi = __ballot((r >> 62) == 2ull);
+    const int first = mi ? __ffsll((long long)mi) - 1 : 64;
+    uint32_t contrib = lane <= first ? (uint32_t)(r & 0xFFFFFFFFull) : 0u;
+#pragma unroll
+    for (int d = 32; d >= 1; d >>= 1) contrib += (uint32_t)__shfl_xor((int)contrib, d, 64);
+    excl += contrib;
+    if (mi) break;
+    base -= 64;
+  }
+  if (lane == 0 && bid != 0u) __hip_atomic_store(&state[bid], (2ull << 62) | (unsigned long long)(excl + agg), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+  return excl;
+}
+
+// laserMapping::publishTopic's registered scan (laserMapping.cpp:464-493, utils::pointAssociateToMap, superodom_utils.cpp:148-158)
+// from records that stay as they are: transform_cloud_kernel's arithmetic (map_kernels.hip) -- a point within 0.1 m of the sensor
+// keeps its coordinates, every other one becomes q * p + t in fp64, rounded to float; kept when the result lies farther than
+// 0.1 m from the world origin; float products and sums, compared with the double 0.01 -- and surf_sample_kernel's order-preserving
+// compaction: tiles of kSurfItems consecutive records in ticket order, a ballot + mbcnt per round, the LDS prefix over (round,
+// wavefront), lookback_exclusive, the count from the last workgroup.  A kept record goes out as all its `stride` bytes with the
+// three floats replaced.  V16: rec and out 16-byte aligned and stride a multiple of 16 -- 16-byte loads and stores, the first two
+// of a record held in registers from the first pass (all of a 32-byte record); otherwise dwords (stride a multiple of 4).
+template <bool V16>
+__global__ __launch_bounds__(256) void registered_scan_kernel(const uint8_t* __restrict__ rec, uint32_t n, uint32_t stride, Pose pose,
+                                                              uint8_t* __restrict__ out, uint32_t* __restrict__ n_kept,
+                                                              unsigned long long* __restrict__ state, uint32_t* __restrict__ ticket, uint32_t nblk) {
+  constexpr int kPer = (int)(kSurfItems / 256u);
+  __shared__ uint32_t s_bid, s_pre[kPer * 4], s_agg, s_excl;
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  if (tid == 0) s_bid = atomicAdd(ticket, 1u);
+  __syncthreads();
+  const uint32_t bid = s_bid;
+  unsigned long long bal[kPer];
+  uint4 head[kPer];                // x' y' z' and, V16, the record's fourth word
+  uint4 tail[V16 ? kPer : 1];      // V16, stride >= 32: bytes 16 .. 31
+#pragma unroll
+  for (int q = 0; q < kPer; ++q) {
+    const uint32_t i = bid * kSurfItems + (uint32_t)q * 256u + (uint32_t)tid;
+    bool keep = false;
+    head[q] = make_uint4(0u, 0u, 0u, 0u);
+    if (V16) tail[q] = make_uint4(0u, 0u, 0u, 0u);
+    if (i < n) {
+      const uint8_t* p = rec + (size_t)i * stride;
+      if (V16) {
+        head[q] = *reinterpret_cast<const uint4*>(p);
+        if (stride >= 32u) tail[q] = *reinterpret_cast<const uint4*>(p + 16);
+      } else {
+        const uint32_t* w = reinterpret_cast<const uint32_t*>(p);
+        head[q].x = w[0]; head[q].y = w[1]; head[q].z = w[2];
+      }
+      float x = __uint_as_float(head[q].x), y = __uint_as_float(head[q].y), z = __uint_as_float(head[q].z);
+      if (!(x * x + y * y + z * z < 0.01)) {
+        double wx, wy, wz;
+        quat_rotate<double>(pose.q, (double)x, (double)y, (double)z, wx, wy, wz);
+        x = (float)(wx + pose.t[0]); y = (float)(wy + pose.t[1]); z = (float)(wz + pose.t[2]);
+        head[q].x = __float_as_uint(x); head[q].y = __float_as_uint(y); head[q].z = __float_as_uint(z);
+      }
+      keep = x * x + y * y + z * z > 0.01;
+    }
+    bal[q] = __ballot(keep);
+    if (lane == 0) s_pre[q * 4 + wave] = (uint32_t)__popcll(bal[q]);
+  }
+  __syncthreads();
+  if (tid == 0) {  // exclusive prefix in record order: round-major, then wavefront
+    uint32_t acc = 0;
+    for (int k = 0; k < kPer * 4; ++k) { const uint32_t v = s_pre[k]; s_pre[k] = acc; acc += v; }
+    s_agg = acc;
+  }
+  __syncthreads();
+  const uint32_t agg = s_agg;
+  if (wave == 0) {
+    const uint32_t excl = lookback_exclusive(state, bid, agg, lane);
+    if (lane == 0) {
+      if (bid == nblk - 1u) *n_kept = excl + agg;
+      s_excl = excl;
+    }
+  }
+  __syncthreads();
+  const uint32_t excl = s_excl;
+#pragma unroll
+  for (int q = 0; q < kPer; ++q) {
+    if ((bal[q] >> lane) & 1ull) {
+      const uint32_t below = __builtin_amdgcn_mbcnt_hi((uint32_t)(bal[q] >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)bal[q], 0u));
+      const size_t at = (size_t)excl + s_pre[q * 4 + wave] + below;
+      const uint8_t* p = rec + (size_t)(bid * kSurfItems + (uint32_t)q * 256u + (uint32_t)tid) * stride;
+      uint8_t* o = out + at * stride;
+      if (V16) {
+        *reinterpret_cast<uint4*>(o) = head[q];
+        if (stride >= 32u) *reinterpret_cast<uint4*>(o + 16) = tail[q];
+        for (uint32_t b = 32u; b < stride; b += 16u) *reinterpret_cast<uint4*>(o + b) = *reinterpret_cast<const uint4*>(p + b);
+      } else {
+        uint32_t* ow = reinterpret_cast<uint32_t*>(o);
+        ow[0] = head[q].x; ow[1] = head[q].y; ow[2] = head[q].z;
+        for (uint32_t b = 12u; b < stride; b += 4u) *reinterpret_cast<uint32_t*>(o + b) = *reinterpret_cast<const uint32_t*>(p + b);
+      }
+    }
+  }
+}
+
+void launch_registered_scan(const uint8_t* d_rec, uint32_t n, uint32_t stride, const Pose& pose, uint8_t* d_out, uint32_t* d_n_kept,
+                            unsigned long long* d_state, uint32_t* d_ticket, hipStream_t s) {
+  const uint32_t nblk = registered_scan_workgroups(n);
+  if (!nblk) return;
+  const bool v16 = stride % 16u == 0 && (reinterpret_cast<uintptr_t>(d_rec) | reinterpret_cast<uintptr_t>(d_out)) % 16u == 0;
+  if (v16) registered_scan_kernel<true><<<nblk, 256, 0, s>>>(d_rec, n, stride, pose, d_out, d_n_kept, d_state, d_ticket, nblk);
+  else registered_scan_kernel<false><<<nblk, 256, 0, s>>>(d_rec, n, stride, pose, d_out, d_n_kept, d_state, d_ticket, nblk);
 }
 
 }  // namespace soicp
