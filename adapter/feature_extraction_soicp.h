@@ -8,7 +8,9 @@
 // Left to the caller: imu_Handler's integration, imuInit and IMU_INIT (the caller passes stamped orientations and the flag),
 // visual_odom_Handler's message parsing (stamped poses), livoxHandler, provide_point_time == 0 (refused here).
 // The library has livoxHandler's ingest (so_icp_extract_features_livox, wire/messages.h CustomMsg); this shell does not route a
-// sensor: livox configuration to it and keeps refusing it.
+// sensor: livox configuration to it and keeps refusing it.  The same holds for a sweep without per-point time: the library has
+// assignTimeforPointCloud's ingest (so_icp_extract_features_untimed), and this shell keeps refusing provide_point_time: 0 until a
+// later change routes it.
 #pragma once
 #include <map>
 #include <stdexcept>

@@ -504,6 +504,49 @@ int so_icp_extract_features_livox(so_icp_ctx *ctx, const void *raw, uint32_t n_p
 int so_icp_extract_features_livox_dev(so_icp_ctx *ctx, const void *d_raw, uint32_t n_points, const so_icp_livox_layout *layout,
                                       double lidar_start_time, const so_icp_stamped_pose *poses, size_t n_poses, int poses_are_imu,
                                       const double T_i_l[7], void **d_nodistortion_out, void **d_surface_out, so_icp_feature_info *info);
+/* -------- the same front end for a sweep WITHOUT per-point time (feature_extraction_node.provide_point_time: 0; older
+ * velodyne_pointcloud drivers, most recorded VLP-16 / HDL-32 / HDL-64 bags): featureExtraction::assignTimeforPointCloud
+ * (src/FeatureExtraction/featureExtraction.cpp:646-708, called from laserCloudHandler :753-759) in place of step 1, then the same
+ * removePointDistortion and uniformFeatureExtraction on the records it leaves.  pcl::fromROSMsg into pcl::PointXYZI: float
+ * x y z intensity, an absent field reads 0; the sensor type is not looked at.  Per point i of the n = width * height (:655-704):
+ *   angle = atan(z / sqrt(x*x + y*y)) * 180 / M_PI as a float: the sum (unfused), sqrt and the quotient in float, atan as float
+ *   (taken as the correctly rounded value), * 180 a float product, / M_PI in double, rounded to float;
+ *   n_scans 16: ring = int((angle + 15) / 2 + 0.5), sum and quotient in float, + 0.5 in double; dropped when > 15 or < 0
+ *           32: ring = int((angle + 92.0/3.0) * 3.0 / 4.0) in double; dropped when > 31 or < 0
+ *           64: ring = angle >= -8.83 ? int((2 - angle) * 3.0 + 0.5) : 32 + int((-8.83 - angle) * 2.0 + 0.5), 2 - angle in float, the
+ *               rest in double; dropped when angle > 2 || angle < -24.33 || ring > 50 || ring < 0
+ *           4, 128: ring 0, nothing dropped (the "wrong scan number" branch)
+ *   int() truncates toward zero (an angle of -17 degrees is ring 0 of 16).  NaN rule: a NaN angle -- (0, 0, 0), inf / inf, a NaN
+ *   coordinate -- makes int(NaN), undefined in C++; it is pinned to x86-64's INT_MIN, so the point is dropped in the three tables.
+ *   time = (float)(rel * scanPeriod), rel = (float)((columnTime * int(i / n_scans) + laserTime * (i % n_scans)) / scanPeriod) in
+ *   double, with featureExtraction.h:91-93's constants; i is the index in the incoming sweep.
+ * Loop-bound rule: a dropped point does cloud_size--; continue, and cloud_size is the loop's bound, so every drop also cuts one
+ * point off the END of the sweep.  With D(i) = the number of dropped points among [0, i): index i is visited iff i + D(i) < n
+ * (a prefix, as i + D(i) increases strictly); a point becomes a record iff it is visited and not dropped, at position i - D(i).
+ * info->n_points is the number of these records (not width * height); de-skew and sampling see only them.
+ * width * height == 0, or no record left: SO_ICP_OK, zero counts, no de-skew (deskewed 0, the identity; the reference's back() on
+ * the empty cloud is undefined). */
+typedef struct {
+  int32_t is_bigendian; /* PointCloud2::is_bigendian: 1 is refused */
+  uint32_t point_step, row_step;
+  int32_t off_x, off_y, off_z, off_intensity; /* byte offsets inside a point, FLOAT32 count 1; -1 = absent or not matching */
+  int32_t n_scans;                            /* feature_extraction_node.scan_line (N_SCANS): 4, 16, 32, 64 or 128 (:62); any other value is refused */
+  int32_t filter_point_size;                  /* feature_extraction_node.filter_point_size, >= 1 */
+  float min_range;                            /* feature_extraction_node.min_range */
+} so_icp_untimed_layout;
+/* assignTimeforPointCloud (:646-708) + removePointDistortion + uniformFeatureExtraction; arguments, buffer ownership and validity as
+ * so_icp_extract_features, the host output buffers sized for width * height records.  The record count is known only on the
+ * device, and the sampler's launch takes it as an argument: it is read back between the two launches, one synchronisation more
+ * than so_icp_extract_features. */
+int so_icp_extract_features_untimed(so_icp_ctx *ctx, const void *raw, uint32_t width, uint32_t height, const so_icp_untimed_layout *layout,
+                                    double lidar_start_time, const so_icp_stamped_pose *poses, size_t n_poses, int poses_are_imu,
+                                    const double T_i_l[7], void *nodistortion_out, void *surface_out, so_icp_feature_info *info);
+/* same (assignTimeforPointCloud, :646-708), payload already in HBM; outputs as so_icp_extract_features_dev: device buffers owned by
+ * the context, shared with that entry and the Livox one, valid until the next call of any of them. */
+int so_icp_extract_features_untimed_dev(so_icp_ctx *ctx, const void *d_raw, uint32_t width, uint32_t height,
+                                        const so_icp_untimed_layout *layout, double lidar_start_time, const so_icp_stamped_pose *poses,
+                                        size_t n_poses, int poses_are_imu, const double T_i_l[7], void **d_nodistortion_out,
+                                        void **d_surface_out, so_icp_feature_info *info);
 /* so_icp_prefilter_scan on a cloud already in HBM and complete (e.g. *d_surface_out above, stride 32): same results, bit for bit */
 int so_icp_prefilter_scan_dev(so_icp_ctx *ctx, const void *d_surf, size_t n, size_t stride_bytes, int auto_voxel_size, float line_res,
                               float plane_res, void **d_filtered_out, size_t *n_out, so_icp_prefilter_info *info);

@@ -103,6 +103,13 @@ def livox_layout(filter_point_size=3, min_range=0.2, n_scans=4, R_imu_laser_grav
     return L
 
 
+class UntimedLayout(C.Structure):
+    """so_icp_untimed_layout"""
+    _fields_ = [("is_bigendian", C.c_int32), ("point_step", C.c_uint32), ("row_step", C.c_uint32), ("off_x", C.c_int32), ("off_y", C.c_int32),
+                ("off_z", C.c_int32), ("off_intensity", C.c_int32), ("n_scans", C.c_int32), ("filter_point_size", C.c_int32),
+                ("min_range", C.c_float)]
+
+
 SENSOR_VELODYNE, SENSOR_OUSTER = 0, 1
 # sensor_msgs::msg::PointField datatypes
 INT8, UINT8, INT16, UINT16, INT32, UINT32, FLOAT32, FLOAT64 = range(1, 9)
@@ -133,6 +140,23 @@ def sweep_layout(fields, point_step, row_step, sensor, filter_point_size, min_ra
     L.filter_point_size, L.min_range = int(filter_point_size), float(min_range)
     for k in range(7):
         L.T_ouster_sensor[k] = float(T_ouster_sensor[k])
+    return L
+
+
+def untimed_layout(fields, point_step, row_step, n_scans, filter_point_size, min_range, is_bigendian=False):
+    """so_icp_untimed_layout (a sweep without per-point time, assignTimeforPointCloud) from a PointCloud2's PointField list
+    [(name, offset, datatype, count), ...]: pcl::PointXYZI's x y z intensity, matched as in sweep_layout (FLOAT32, count 1 or 0; a
+    field with no match is absent and reads 0)."""
+    off = {}
+    for name in ("x", "y", "z", "intensity"):
+        for fname, foff, fdt, fcount in fields:
+            if fname == name and fdt == FLOAT32 and (fcount == 1 or fcount == 0):
+                off[name] = int(foff)
+                break
+    L = UntimedLayout()
+    L.is_bigendian, L.point_step, L.row_step = int(bool(is_bigendian)), int(point_step), int(row_step)
+    L.off_x, L.off_y, L.off_z, L.off_intensity = off.get("x", -1), off.get("y", -1), off.get("z", -1), off.get("intensity", -1)
+    L.n_scans, L.filter_point_size, L.min_range = int(n_scans), int(filter_point_size), float(min_range)
     return L
 
 
@@ -169,7 +193,7 @@ EXPORTED = ["so_icp_default_config", "so_icp_create", "so_icp_destroy", "so_icp_
             "so_icp_map_insert_stats", "so_icp_register_sequence", "so_icp_map_export_records", "so_icp_sequence_announce_next", "so_icp_debug_neighbours", "so_icp_prefilter_announce",
             "so_icp_localization_sequence", "so_icp_extract_features", "so_icp_extract_features_dev", "so_icp_prefilter_scan_dev",
             "so_icp_livox_default_layout", "so_icp_extract_features_livox", "so_icp_extract_features_livox_dev",
-            "so_icp_registered_scan", "so_icp_registered_scan_dev"]
+            "so_icp_registered_scan", "so_icp_registered_scan_dev", "so_icp_extract_features_untimed", "so_icp_extract_features_untimed_dev"]
 
 _lib = None
 
@@ -248,6 +272,10 @@ def load():
                                                 C.c_int, C.POINTER(C.c_double), vp, vp, C.POINTER(FeatureInfo)]
     L.so_icp_extract_features_livox_dev.argtypes = [vp, vp, C.c_uint32, C.POINTER(LivoxLayout), C.c_double, C.POINTER(C.c_double), C.c_size_t,
                                                     C.c_int, C.POINTER(C.c_double), C.POINTER(vp), C.POINTER(vp), C.POINTER(FeatureInfo)]
+    L.so_icp_extract_features_untimed.argtypes = [vp, vp, C.c_uint32, C.c_uint32, C.POINTER(UntimedLayout), C.c_double, C.POINTER(C.c_double),
+                                                  C.c_size_t, C.c_int, C.POINTER(C.c_double), vp, vp, C.POINTER(FeatureInfo)]
+    L.so_icp_extract_features_untimed_dev.argtypes = [vp, vp, C.c_uint32, C.c_uint32, C.POINTER(UntimedLayout), C.c_double, C.POINTER(C.c_double),
+                                                      C.c_size_t, C.c_int, C.POINTER(C.c_double), C.POINTER(vp), C.POINTER(vp), C.POINTER(FeatureInfo)]
     L.so_icp_debug_knn_stamps.argtypes = [vp, C.POINTER(C.c_uint64), C.c_size_t, C.POINTER(C.c_size_t)]
     L.so_icp_set_time_kernels.argtypes = [vp, C.c_int]
     L.so_icp_stage_scan.argtypes = [vp, f32p, C.c_size_t, C.c_size_t]
@@ -649,6 +677,31 @@ class LidarSlamGpu:
         d_rec = C.c_void_p(); d_surf = C.c_void_p(); info = FeatureInfo()
         self._check(self.L.so_icp_extract_features_livox_dev(self.h, C.c_void_p(d_points), int(n_points), C.byref(layout), float(lidar_start_time),
                                                              pp, npo, int(bool(poses_are_imu)), tp, C.byref(d_rec), C.byref(d_surf), C.byref(info)))
+        return d_rec.value, d_surf.value, info
+
+    def extract_features_untimed(self, payload, width, height, layout, lidar_start_time, poses=None, poses_are_imu=False, T_i_l=None):
+        """a sweep without per-point time (assignTimeforPointCloud) -> LaserFeature clouds on the device.  payload: the PointCloud2 data
+        (uint8), layout: untimed_layout(...); the rest as extract_features.  Returns (cloud_nodistortion uint8 [info.n_points, 32] --
+        the records that remain --, cloud_surface uint8 [n_surface, 32], FeatureInfo)."""
+        raw = np.ascontiguousarray(payload, np.uint8).reshape(-1)
+        poses, pp, npo, tp, _keep = self._feature_args(poses, T_i_l)
+        n = int(width) * int(height)
+        rec = np.zeros((n, 32), np.uint8)
+        surf = np.zeros((max(n, 1), 32), np.uint8)
+        info = FeatureInfo()
+        self._check(self.L.so_icp_extract_features_untimed(self.h, raw.ctypes.data_as(C.c_void_p), int(width), int(height), C.byref(layout),
+                                                           float(lidar_start_time), pp, npo, int(bool(poses_are_imu)), tp,
+                                                           rec.ctypes.data_as(C.c_void_p), surf.ctypes.data_as(C.c_void_p), C.byref(info)))
+        return rec[:info.n_points].copy(), surf[:info.n_surface].copy(), info
+
+    def extract_features_untimed_dev(self, d_payload, width, height, layout, lidar_start_time, poses=None, poses_are_imu=False, T_i_l=None):
+        """the same on a payload resident in HBM; returns (d_nodistortion, d_surface, FeatureInfo): context-owned device buffers
+        holding info.n_points and info.n_surface records, valid until the next extract_features*_dev call"""
+        poses, pp, npo, tp, _keep = self._feature_args(poses, T_i_l)
+        d_rec = C.c_void_p(); d_surf = C.c_void_p(); info = FeatureInfo()
+        self._check(self.L.so_icp_extract_features_untimed_dev(self.h, C.c_void_p(d_payload), int(width), int(height), C.byref(layout),
+                                                               float(lidar_start_time), pp, npo, int(bool(poses_are_imu)), tp, C.byref(d_rec),
+                                                               C.byref(d_surf), C.byref(info)))
         return d_rec.value, d_surf.value, info
 
     def deskew_scan(self, records, time_off, lidar_start_time, poses, poses_are_imu, T_i_l=None):

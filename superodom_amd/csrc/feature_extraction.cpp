@@ -1,5 +1,5 @@
-// feature_extraction.cpp -- so_icp_extract_features(_dev) and so_icp_extract_features_livox(_dev): featureExtraction's per-sweep
-// path (laserCloudHandler's or livoxHandler's ingest, removePointDistortion, uniformFeatureExtraction;
+// feature_extraction.cpp -- so_icp_extract_features(_dev), so_icp_extract_features_livox(_dev) and so_icp_extract_features_untimed(_dev):
+// featureExtraction's per-sweep path (laserCloudHandler's, livoxHandler's or assignTimeforPointCloud's ingest, removePointDistortion, uniformFeatureExtraction;
 // src/FeatureExtraction/featureExtraction.cpp) as one enqueue on the device.
 //
 // The node's bookkeeping around it (frame skipping, the sweep and pose buffers, the branch choice, the LaserFeature message) stays
@@ -175,6 +175,91 @@ int run_livox(so_icp_ctx* c, hipStream_t s, FeatureState& st, const uint8_t* d_r
              });
 }
 
+// ---- so_icp_extract_features_untimed(_dev): a sweep without per-point time (assignTimeforPointCloud, :646-708) ----
+int check_untimed_layout(so_icp_ctx* c, const char* who, uint32_t width, uint32_t height, const so_icp_untimed_layout* L) {
+  const std::string w(who);
+  if (L->is_bigendian) return fail(c, SO_ICP_E_INVALID, w + ": big-endian payloads are not supported");
+  if (L->filter_point_size < 1) return fail(c, SO_ICP_E_INVALID, w + ": filter_point_size must be >= 1");
+  bool scans_ok = false;
+  for (int32_t v : {4, 16, 32, 64, 128}) scans_ok = scans_ok || L->n_scans == v;  // featureExtraction.cpp:62
+  if (!scans_ok) return fail(c, SO_ICP_E_INVALID, w + ": n_scans must be 4, 16, 32, 64 or 128");
+  if (L->point_step == 0) return fail(c, SO_ICP_E_INVALID, w + ": point_step must be > 0");
+  if ((uint64_t)L->row_step < (uint64_t)width * L->point_step) return fail(c, SO_ICP_E_INVALID, w + ": row_step < width * point_step");
+  const struct { int32_t off; const char* name; } f[] = {{L->off_x, "x"}, {L->off_y, "y"}, {L->off_z, "z"}, {L->off_intensity, "intensity"}};
+  for (const auto& q : f)
+    if (q.off < -1 || (q.off >= 0 && (uint64_t)q.off + 4 > L->point_step))
+      return fail(c, SO_ICP_E_INVALID, w + ": offset of " + q.name + " lies past point_step");
+  if ((uint64_t)width * height >= ((uint64_t)1 << 31)) return fail(c, SO_ICP_E_UNSUPPORTED, w + ": too many points");
+  return SO_ICP_OK;
+}
+
+int check_untimed_args(so_icp_ctx* c, const char* who, const void* raw, uint32_t width, uint32_t height, const so_icp_untimed_layout* L,
+                       const so_icp_stamped_pose* poses, size_t n_poses) {
+  if (!c || !L || (!raw && (uint64_t)width * height) || (n_poses && !poses)) return SO_ICP_E_INVALID;
+  if (const int rc = check_untimed_layout(c, who, width, height, L)) return rc;
+  if (n_poses >= ((size_t)1 << 24)) return fail(c, SO_ICP_E_UNSUPPORTED, std::string(who) + ": too many poses");
+  NEED_DEVICE(c);
+  return SO_ICP_OK;
+}
+
+UntimedFields untimed_fields_of(const so_icp_untimed_layout* L, uint32_t width) {
+  UntimedFields uf;
+  uf.point_step = L->point_step; uf.row_step = L->row_step; uf.width = width;
+  uf.x = L->off_x; uf.y = L->off_y; uf.z = L->off_z; uf.intensity = L->off_intensity;
+  uf.n_scans = (uint32_t)L->n_scans;
+  return uf;
+}
+
+// run() for such a sweep.  The number of records is known only on the device and surf_sample_kernel takes it as a launch
+// argument, so it is read back between the two launches: counters cleared, pose table, ingest + compaction + de-skew, the counts
+// read back (wait), the sampler over the n_kept records, its count read back (wait).
+int run_untimed(so_icp_ctx* c, hipStream_t s, FeatureState& st, const uint8_t* d_raw, uint32_t n, const so_icp_untimed_layout* L, uint32_t width,
+                double t0, const so_icp_stamped_pose* poses, size_t n_poses, int imu, const double T_i_l[7], so_icp_feature_info& info) {
+  std::memset(&info, 0, sizeof(info));  // what stays where there is no record: zero counts, no de-skew, the identity
+  info.q_w_original_l[3] = 1.0;
+  DeskewFrames f{};
+  std::vector<double> tab;
+  double q_start[4] = {0.0, 0.0, 0.0, 1.0}, t_start[3] = {0.0, 0.0, 0.0};  // the sweep-start pose, reported once a record exists
+  if (n_poses && !deskew_setup(reinterpret_cast<const double*>(poses), n_poses, t0, imu, T_i_l, f, tab, q_start, t_start))
+    return fail(c, SO_ICP_E_INVALID, "pose buffer times must increase strictly (the reference keeps them in a std::map)");
+  if (!n) return SO_ICP_OK;
+  const uint32_t step = (uint32_t)L->filter_point_size;
+  // counters {n_clamped, n_surface, sampler's ticket, -, n_kept, ingest's ticket, -, -} | the sampler's look-back words (for up to
+  // n records) | the ingest's | pose table
+  const size_t surf_state_off = 32, in_state_off = surf_state_off + (size_t)surf_workgroups(n, step) * 8,
+               tab_off = (in_state_off + (size_t)untimed_workgroups(n) * 8 + 255) & ~(size_t)255;
+  HIP_TRY(c, st.rec.reserve((size_t)n * kFeatureRecordBytes));
+  HIP_TRY(c, st.surf.reserve((size_t)(surf_candidates(n, step) + 1) * kFeatureRecordBytes));
+  HIP_TRY(c, st.small.reserve(tab_off + tab.size() * sizeof(double) + 64));
+  if (!st.h_counts) HIP_TRY(c, hipHostMalloc(reinterpret_cast<void**>(&st.h_counts), 64));
+  uint32_t* d_counts = st.small.as<uint32_t>();
+  HIP_TRY(c, hipMemsetAsync(st.small.p, 0, tab_off, s));
+  if (n_poses) HIP_TRY(c, hipMemcpyAsync(st.small.as<uint8_t>() + tab_off, tab.data(), tab.size() * sizeof(double), hipMemcpyHostToDevice, s));
+  launch_untimed_ingest_deskew(d_raw, n, untimed_fields_of(L, width), st.rec.as<uint8_t>(), t0,
+                               reinterpret_cast<const double*>(st.small.as<uint8_t>() + tab_off), (uint32_t)n_poses, f, d_counts, d_counts + 4,
+                               reinterpret_cast<unsigned long long*>(st.small.as<uint8_t>() + in_state_off), d_counts + 5, s);
+  HIP_TRY(c, hipGetLastError());
+  HIP_TRY(c, hipMemcpyAsync(st.h_counts, d_counts, 32, hipMemcpyDeviceToHost, s));
+  HIP_TRY(c, hipStreamSynchronize(s));  // (also keeps `tab` alive until its upload has been consumed)
+  const uint32_t n_kept = st.h_counts[4];
+  if (!n_kept) return SO_ICP_OK;
+  info.n_points = n_kept;
+  info.n_clamped = st.h_counts[0];
+  if (n_poses) {
+    info.deskewed = 1;
+    std::memcpy(info.q_w_original_l, q_start, sizeof(q_start));
+    std::memcpy(info.t_w_original_l, t_start, sizeof(t_start));
+  }
+  if (!surf_workgroups(n_kept, step)) return SO_ICP_OK;  // one record: no candidate
+  launch_surf_sample(st.rec.as<uint8_t>(), n_kept, step, L->min_range, st.surf.as<uint8_t>(), d_counts + 1,
+                     reinterpret_cast<unsigned long long*>(st.small.as<uint8_t>() + surf_state_off), d_counts + 2, s);
+  HIP_TRY(c, hipGetLastError());
+  HIP_TRY(c, hipMemcpyAsync(st.h_counts + 1, d_counts + 1, 4, hipMemcpyDeviceToHost, s));
+  HIP_TRY(c, hipStreamSynchronize(s));
+  info.n_surface = st.h_counts[1];
+  return SO_ICP_OK;
+}
+
 // the clouds of the host entries: out of the context's buffers into the caller's
 int read_back(so_icp_ctx* c, hipStream_t s, FeatureState& st, const so_icp_feature_info& li, void* nodistortion_out, void* surface_out) {
   if (li.n_points && nodistortion_out) HIP_TRY(c, hipMemcpyAsync(nodistortion_out, st.rec.p, (size_t)li.n_points * kFeatureRecordBytes, hipMemcpyDeviceToHost, s));
@@ -316,6 +401,42 @@ int so_icp_extract_features_livox_dev(so_icp_ctx* c, const void* d_raw, uint32_t
   FeatureState& st = *state_of(c);
   so_icp_feature_info li;
   const int rc = run_livox(c, c->stream, st, static_cast<const uint8_t*>(d_raw), n, L, lidar_start_time, poses, n_poses, poses_are_imu, T_i_l, li);
+  if (rc) return rc;
+  if (d_nodistortion_out) *d_nodistortion_out = st.rec.p;
+  if (d_surface_out) *d_surface_out = st.surf.p;
+  if (info) *info = li;
+  return SO_ICP_OK;
+}
+
+int so_icp_extract_features_untimed(so_icp_ctx* c, const void* raw, uint32_t width, uint32_t height, const so_icp_untimed_layout* L,
+                                    double lidar_start_time, const so_icp_stamped_pose* poses, size_t n_poses, int poses_are_imu,
+                                    const double T_i_l[7], void* nodistortion_out, void* surface_out, so_icp_feature_info* info) {
+  if (const int rc = check_untimed_args(c, "so_icp_extract_features_untimed", raw, width, height, L, poses, n_poses)) return rc;
+  HIP_TRY(c, hipSetDevice(c->cfg.device_id));
+  FeatureState& st = *state_of(c);
+  hipStream_t s = aux_stream(c);  // (host buffers in and out: as so_icp_extract_features)
+  const uint32_t n = width * height;
+  if (n) {
+    const size_t bytes = (size_t)L->row_step * (height - 1) + (size_t)width * L->point_step;  // (the last row's tail is never read)
+    HIP_TRY(c, st.raw.reserve(bytes + 64));
+    HIP_TRY(c, hipMemcpyAsync(st.raw.p, raw, bytes, hipMemcpyHostToDevice, s));  // (pageable, straight from the message: see above)
+  }
+  so_icp_feature_info li;
+  if (const int rc = run_untimed(c, s, st, st.raw.as<uint8_t>(), n, L, width, lidar_start_time, poses, n_poses, poses_are_imu, T_i_l, li)) return rc;
+  if (const int rc = read_back(c, s, st, li, nodistortion_out, surface_out)) return rc;
+  if (info) *info = li;
+  return SO_ICP_OK;
+}
+
+int so_icp_extract_features_untimed_dev(so_icp_ctx* c, const void* d_raw, uint32_t width, uint32_t height, const so_icp_untimed_layout* L,
+                                        double lidar_start_time, const so_icp_stamped_pose* poses, size_t n_poses, int poses_are_imu,
+                                        const double T_i_l[7], void** d_nodistortion_out, void** d_surface_out, so_icp_feature_info* info) {
+  if (const int rc = check_untimed_args(c, "so_icp_extract_features_untimed_dev", d_raw, width, height, L, poses, n_poses)) return rc;
+  HIP_TRY(c, hipSetDevice(c->cfg.device_id));
+  FeatureState& st = *state_of(c);
+  so_icp_feature_info li;
+  const int rc = run_untimed(c, c->stream, st, static_cast<const uint8_t*>(d_raw), width * height, L, width, lidar_start_time, poses, n_poses,
+                             poses_are_imu, T_i_l, li);
   if (rc) return rc;
   if (d_nodistortion_out) *d_nodistortion_out = st.rec.p;
   if (d_surface_out) *d_surface_out = st.surf.p;

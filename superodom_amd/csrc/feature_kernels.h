@@ -26,6 +26,13 @@ struct LivoxFields {
   double R[9];                                             // imu_laser_R_Gravity (identity while the IMU buffer is empty), row-major
 };
 
+// where the four float fields of a sweep without per-point time are (pcl::fromROSMsg into pcl::PointXYZI; -1: absent), and N_SCANS
+struct UntimedFields {
+  uint32_t point_step, row_step, width;
+  int32_t x, y, z, intensity;
+  uint32_t n_scans;  // config_.N_SCANS: 16, 32, 64 take their ring table; 4 and 128 give ring 0 and drop nothing
+};
+
 // bytes of one record of either output cloud: point_os::PointcloudXYZITR and pcl::PointXYZI are both 32 bytes
 constexpr uint32_t kFeatureRecordBytes = 32;
 // surf-sampling candidates per workgroup of the compaction, and the look-back words it needs
@@ -39,6 +46,13 @@ void launch_ingest_deskew(const uint8_t* d_raw, uint32_t n, const SweepFields& s
 // the same for a Livox CustomMsg's points (livoxHandler, :794-806): n points point_step bytes apart, d_raw at any alignment
 void launch_livox_ingest_deskew(const uint8_t* d_raw, uint32_t n, const LivoxFields& lf, uint8_t* d_rec, double t0, const double* d_poses,
                                 uint32_t n_poses, const DeskewFrames& f, uint32_t* d_n_clamped, hipStream_t s);
+// the same for a sweep without per-point time (assignTimeforPointCloud, :646-708): ring and time computed, the points the
+// reference drops or no longer visits left out -- d_rec (room for n) gets the *d_n_kept records that remain, in order.
+// d_state (untimed_workgroups words), d_ticket, *d_n_kept and *d_n_clamped zeroed by the caller.
+inline uint32_t untimed_workgroups(uint32_t n) { return (n + kSurfItems - 1u) / kSurfItems; }
+void launch_untimed_ingest_deskew(const uint8_t* d_raw, uint32_t n, const UntimedFields& uf, uint8_t* d_rec, double t0, const double* d_poses,
+                                  uint32_t n_poses, const DeskewFrames& f, uint32_t* d_n_clamped, uint32_t* d_n_kept, unsigned long long* d_state,
+                                  uint32_t* d_ticket, hipStream_t s);
 // uniformFeatureExtraction over the records: pcl::PointXYZI records into d_surf, their number into *d_n_surf.
 // d_state (surf_workgroups words) and d_ticket zeroed by the caller.
 void launch_surf_sample(const uint8_t* d_rec, uint32_t n, uint32_t step, float min_range, uint8_t* d_surf, uint32_t* d_n_surf,

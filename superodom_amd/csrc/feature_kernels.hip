@@ -13,6 +13,7 @@
 #include "deskew_math.h"
 #include "feature_kernels.h"
 #include "so_math.h"
+#include "untimed_math.h"
 
 namespace soicp {
 
@@ -371,6 +372,122 @@ void launch_registered_scan(const uint8_t* d_rec, uint32_t n, uint32_t stride, c
   const bool v16 = stride % 16u == 0 && (reinterpret_cast<uintptr_t>(d_rec) | reinterpret_cast<uintptr_t>(d_out)) % 16u == 0;
   if (v16) registered_scan_kernel<true><<<nblk, 256, 0, s>>>(d_rec, n, stride, pose, d_out, d_n_kept, d_state, d_ticket, nblk);
   else registered_scan_kernel<false><<<nblk, 256, 0, s>>>(d_rec, n, stride, pose, d_out, d_n_kept, d_state, d_ticket, nblk);
+}
+
+// assignTimeforPointCloud (:646-708) -- the ingest of a sweep whose points carry x y z intensity only (provide_point_time: 0) --
+// fused with removePointDistortion, a kernel of its own beside the two ingests above (whose code it leaves as it is).  The ring,
+// the drop test and the time are untimed_math.h's.  The reference's loop shrinks its own bound with every drop (cloud_size--), so
+// with D(i) = the number of dropped points among [0, i): index i is visited iff i + D(i) < n (i + D(i) increases strictly, so the
+// visited indices are a prefix), a visited point that is not dropped is record i - D(i), and the number of records is
+// F - D(F) for the first unvisited F -- written by the thread of F - 1, the one visited index whose successor is not.
+// registered_scan_kernel's order-preserving compaction over the DROPPED points gives D(i): tiles of kSurfItems consecutive
+// points in ticket order, a ballot per round, the LDS prefix over (round, wavefront), lookback_exclusive, mbcnt.  Pass 1 reads
+// x y z and keeps one byte per round (the ring, 0xFF = dropped); pass 2, behind the look-back, reads the point again, and only a
+// point that becomes a record is de-skewed (deskew_math.h's deskew_point, as the other ingests) and counted in n_clamped: the
+// de-skew chain is in the code once, not once per round, and the eight rounds hold 2 registers instead of 48.
+template <bool A4, bool DESKEW, bool LDS>
+__global__ __launch_bounds__(256) void untimed_ingest_deskew_kernel(const uint8_t* __restrict__ raw, uint32_t n, UntimedFields uf, uint8_t* __restrict__ out,
+                                                                    double t0, const double* __restrict__ poses, uint32_t n_poses, DeskewFrames f,
+                                                                    uint32_t* __restrict__ n_clamped, uint32_t* __restrict__ n_kept,
+                                                                    unsigned long long* __restrict__ state, uint32_t* __restrict__ ticket) {
+  constexpr int kPer = (int)(kSurfItems / 256u);
+  static_assert(kPer <= 8, "rings holds one byte per round in a 64-bit word");
+  __shared__ double tab_lds[(DESKEW && LDS) ? kIngestLdsPoses * kStampedPoseDoubles : 1];
+  __shared__ uint32_t s_bid, s_pre[kPer * 4], s_agg, s_excl;
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  if (tid == 0) s_bid = atomicAdd(ticket, 1u);
+  if (DESKEW && LDS)
+    for (uint32_t k = threadIdx.x; k < n_poses * kStampedPoseDoubles; k += blockDim.x) tab_lds[k] = poses[k];
+  __syncthreads();
+  const double* tab = (DESKEW && LDS) ? tab_lds : poses;
+  const uint32_t bid = s_bid;
+  const bool tabled = uf.n_scans == 16u || uf.n_scans == 32u || uf.n_scans == 64u;  // any other value: ring 0, nothing dropped
+  unsigned long long rings = 0ull;  // byte q: the ring of this thread's point of round q, 0xFF when it is dropped
+#pragma unroll
+  for (int q = 0; q < kPer; ++q) {
+    const uint32_t i = bid * kSurfItems + (uint32_t)q * 256u + (uint32_t)tid;
+    int id = 0;
+    if (tabled && i < n) {
+      const uint32_t row = i / uf.width, col = i - row * uf.width;  // row-major, rows row_step apart (pcl::fromROSMsg)
+      const uint8_t* p = raw + (size_t)row * uf.row_step + (size_t)col * uf.point_step;
+      const float x = uf.x >= 0 ? load_field<A4, float>(p + uf.x) : 0.0f;
+      const float y = uf.y >= 0 ? load_field<A4, float>(p + uf.y) : 0.0f;
+      const float z = uf.z >= 0 ? load_field<A4, float>(p + uf.z) : 0.0f;
+      id = untimed_ring(untimed_angle(x, y, z), (int)uf.n_scans);
+    }
+    rings |= (unsigned long long)((uint32_t)id & 0xFFu) << (8 * q);
+    const unsigned long long dropped = __ballot(id == kUntimedDropped);
+    if (lane == 0) s_pre[q * 4 + wave] = (uint32_t)__popcll(dropped);
+  }
+  __syncthreads();
+  if (tid == 0) {  // exclusive prefix in point order: round-major, then wavefront
+    uint32_t acc = 0;
+    for (int k = 0; k < kPer * 4; ++k) { const uint32_t v = s_pre[k]; s_pre[k] = acc; acc += v; }
+    s_agg = acc;
+  }
+  __syncthreads();
+  const uint32_t agg = s_agg;
+  if (wave == 0) {
+    const uint32_t excl = lookback_exclusive(state, bid, agg, lane);
+    if (lane == 0) s_excl = excl;
+  }
+  __syncthreads();
+  const uint32_t excl = s_excl;
+  uint32_t wave_clamped = 0;
+  constexpr int kUnroll = DESKEW ? 1 : kPer;  // the de-skew chain once in the code
+#pragma unroll kUnroll
+  for (int q = 0; q < kPer; ++q) {
+    const uint32_t i = bid * kSurfItems + (uint32_t)q * 256u + (uint32_t)tid;
+    const uint32_t ring = (uint32_t)(rings >> (8 * q)) & 0xFFu;
+    const bool drop = ring == 0xFFu;
+    const unsigned long long dropped = __ballot(drop);
+    const uint32_t below = __builtin_amdgcn_mbcnt_hi((uint32_t)(dropped >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)dropped, 0u));
+    const uint32_t d = excl + s_pre[q * 4 + wave] + below;  // D(i)
+    bool clamped = false;
+    if (i < n && i + d < n) {  // visited
+      if (!drop) {
+        const uint32_t row = i / uf.width, col = i - row * uf.width;
+        const uint8_t* p = raw + (size_t)row * uf.row_step + (size_t)col * uf.point_step;
+        // a field PCL does not match keeps the value-initialised point's 0
+        float x = uf.x >= 0 ? load_field<A4, float>(p + uf.x) : 0.0f;
+        float y = uf.y >= 0 ? load_field<A4, float>(p + uf.y) : 0.0f;
+        float z = uf.z >= 0 ? load_field<A4, float>(p + uf.z) : 0.0f;
+        const float intensity = uf.intensity >= 0 ? load_field<A4, float>(p + uf.intensity) : 0.0f;
+        const float time = untimed_time(i, uf.n_scans);
+        if (DESKEW) clamped = deskew_point(tab, n_poses, t0, time, f, x, y, z);  // removePointDistortion, :293-306
+        uint4* o = reinterpret_cast<uint4*>(out + (size_t)(i - d) * kFeatureRecordBytes);
+        o[0] = make_uint4(__float_as_uint(x), __float_as_uint(y), __float_as_uint(z), 0u);
+        o[1] = make_uint4(__float_as_uint(intensity), __float_as_uint(time), ring, 0u);
+      }
+      const uint32_t d_next = d + (drop ? 1u : 0u);  // D(i + 1)
+      if (i + 1u + d_next >= n) *n_kept = i + 1u - d_next;  // i + 1 is the first unvisited index
+    }
+    if (DESKEW) {
+      const unsigned long long m = __ballot(clamped);
+      wave_clamped += (uint32_t)__popcll(m);
+    }
+  }
+  if (DESKEW && lane == 0 && wave_clamped) atomicAdd(n_clamped, wave_clamped);
+}
+
+template <bool A4>
+static void launch_untimed_a(const uint8_t* d_raw, uint32_t n, const UntimedFields& uf, uint8_t* d_rec, double t0, const double* d_poses,
+                             uint32_t n_poses, const DeskewFrames& f, uint32_t* d_n_clamped, uint32_t* d_n_kept, unsigned long long* d_state,
+                             uint32_t* d_ticket, hipStream_t s) {
+  const uint32_t blocks = untimed_workgroups(n);
+  if (!n_poses) untimed_ingest_deskew_kernel<A4, false, false><<<blocks, 256, 0, s>>>(d_raw, n, uf, d_rec, t0, d_poses, 0u, f, d_n_clamped, d_n_kept, d_state, d_ticket);
+  else if (n_poses <= kIngestLdsPoses) untimed_ingest_deskew_kernel<A4, true, true><<<blocks, 256, 0, s>>>(d_raw, n, uf, d_rec, t0, d_poses, n_poses, f, d_n_clamped, d_n_kept, d_state, d_ticket);
+  else untimed_ingest_deskew_kernel<A4, true, false><<<blocks, 256, 0, s>>>(d_raw, n, uf, d_rec, t0, d_poses, n_poses, f, d_n_clamped, d_n_kept, d_state, d_ticket);
+}
+
+void launch_untimed_ingest_deskew(const uint8_t* d_raw, uint32_t n, const UntimedFields& uf, uint8_t* d_rec, double t0, const double* d_poses,
+                                  uint32_t n_poses, const DeskewFrames& f, uint32_t* d_n_clamped, uint32_t* d_n_kept, unsigned long long* d_state,
+                                  uint32_t* d_ticket, hipStream_t s) {
+  if (!n) return;
+  bool a4 = (reinterpret_cast<uintptr_t>(d_raw) % 4u) == 0 && uf.point_step % 4u == 0 && uf.row_step % 4u == 0;
+  for (int32_t off : {uf.x, uf.y, uf.z, uf.intensity}) a4 = a4 && (off < 0 || off % 4 == 0);
+  if (a4) launch_untimed_a<true>(d_raw, n, uf, d_rec, t0, d_poses, n_poses, f, d_n_clamped, d_n_kept, d_state, d_ticket, s);
+  else launch_untimed_a<false>(d_raw, n, uf, d_rec, t0, d_poses, n_poses, f, d_n_clamped, d_n_kept, d_state, d_ticket, s);
 }
 
 }  // namespace soicp
