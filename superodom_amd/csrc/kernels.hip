@@ -56,18 +56,7 @@ struct CellRef {
   int cx, cy, cz;  // cell inside the cube
 };
 
-// int((c + 25.0) / 50.0) for a FLOAT-valued c without the fp64 division: c + 25.0 is exact in double and, unless it
-// is an exact multiple of 50, differs from one by at least a float ulp (>= 2^-24 relative), far more than the 2^-53
-// error of multiplying by 0.02; on exact multiples the product rounds to the same integer side.  So the truncation
-// is identical to the reference's division for every float input (LocalMap.h:488-497).
-__device__ __forceinline__ int cube_coord_f(float c, int origin) {
-  const double s = (double)c + 25.0;
-  int i = (int)(s * 0.02) + origin;
-  if (s < 0) i--;
-  return i;
-}
-
-// cube index exactly as LocalMap::nearestKSearchSurf (LocalMap.h:488-507); then the cell of the
+// cube index exactly as LocalMap::nearestKSearchSurf (LocalMap.h:488-507; cube_coord_f: device_idioms.h); then the cell of the
 // hashed-voxel grid inside that cube.
 __device__ __forceinline__ CellRef locate(const DevMapView& m, float qx, float qy, float qz, int* wcube = nullptr) {
   CellRef r;

@@ -33,13 +33,6 @@ namespace soicp {
 
 static inline dim3 grid_for(uint32_t n, int block) { return dim3((n + block - 1) / block); }
 
-__device__ __forceinline__ int cube_coord_f(float c, int origin) {  // == int((c + 25.0) / 50.0) (+origin), "--" if negative
-  const double s = (double)c + 25.0;                                 // (exact for float inputs, see kernels.hip)
-  int i = (int)(s * 0.02) + origin;
-  if (s < 0) i--;
-  return i;
-}
-
 // LocalMap.h:596-610
 __global__ __launch_bounds__(1024) void world_cube_kernel(const float* __restrict__ xyz, uint32_t n, uint32_t stride_floats,
                                                           int o0, int o1, int o2, int32_t* __restrict__ cube_of,
