@@ -640,6 +640,42 @@ int so_icp_debug_match_status(so_icp_ctx *ctx, uint8_t *out, size_t n);
  * like the scan: out[5 * n].  Meaningful where that sweep found five neighbours inside the gate (every query the fit pass then judged: status
  * 0, 3, 4, 5); elsewhere the entries are whatever an earlier sweep left */
 int so_icp_debug_neighbours(so_icp_ctx *ctx, uint32_t *out, size_t n);
+/* test aid: the DEVICE forms of the LM controller on a scripted sequence of sums -- no scan, no map.  The controller is a pure state
+ * machine of (x0, sequence of sums), so a script drives any of its branches deterministically.
+ *   form 0  the lane-parallel controller of the persistent solve (kernels.hip: lm_control_wave), run by one wavefront the way the solve's
+ *           finishing workgroup runs it: sums, state and loop bounds in LDS, the hand-off record stored to global memory
+ *   form 1  the one-thread controller (lm_solver.h through lm_control), by launching the production lm_step_kernel once per entry --
+ *           the very kernel of the sharded path
+ * Everything runs on a scratch state block owned by the call; the context's registration state is not touched.  An entry whose
+ * new_solve is set is the evaluation at the solve's start (slot 0: the start is x0 for the first solve, the pose the solve before
+ * ended with afterwards); the others are evaluations at the pose handed on by the entry before.  An entry is skipped, as the
+ * launches of a registration skip a pass, once the registration is over or while no solve is running.
+ * LIMIT: lm_control_wave is force-inlined, so form 0 is a second compilation of its source, not the instance inside the persistent
+ * solve kernel: this checks the source's semantics and its equality with the one-thread form, not that kernel's machine code. */
+#define SO_ICP_LM_SCRIPT_MAX 64
+typedef struct {
+  so_icp_sums sums;
+  int32_t new_solve, reserved;
+} so_icp_lm_script_entry;
+typedef struct {
+  int32_t more, reserved;   /* the controller's return value (0 for a skipped entry) */
+  double pose[7];           /* the next pose as handed on: form 0 the pose_out copy of the hand-off, form 1 the state block's eval_pose
+                               (which the one-thread form writes only when more == 1) */
+  uint32_t hand[8][4];      /* form 0: the eight 16-byte hand-off chunks {value lo, value hi, tag lo, tag hi}: chunks 0..6 the pose, chunk 7
+                               `more`; all ones where the entry was skipped.  form 1: zero */
+  so_icp_lm_state state;    /* the controller state after the entry */
+} so_icp_lm_script_step;
+typedef struct {
+  so_icp_lm_state state;
+  double T[7], eval_pose[7], T_final[7];
+  double JtJ[36], Jtr[6];
+  int32_t lm_more, outer_iter, n_iterations, reg_done;
+  uint32_t done_count, reserved;
+  so_icp_iter_stats iterations[SO_ICP_MAX_OUTER];  /* the scratch block starts zeroed: records no solve wrote stay zero */
+} so_icp_lm_script_result;
+int so_icp_debug_lm_script(so_icp_ctx *ctx, int form, const double x0[7], int lm_max, int max_outer, int outer_iter,
+                           const so_icp_lm_script_entry *entries, int n_entries /* 1 .. SO_ICP_LM_SCRIPT_MAX */, uint64_t want /* hand-off tag */,
+                           so_icp_lm_script_step *steps /* n_entries */, so_icp_lm_script_result *result);
 /* profiling aid: wall-clock stamps (100 MHz ticks) of the phases of the last fit / evaluation kernels (SOICP_ABLATE=128) */
 int so_icp_debug_stamps(so_icp_ctx *ctx, uint64_t out[16]);
 /* profiling aid: per-workgroup records (16 words each, 2 sweeps x workgroups) of the k-NN kernel's phases (SOICP_ABLATE=128);

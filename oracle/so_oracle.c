@@ -836,7 +836,7 @@ void orc_lm_solve(const orc_corr *c_all, size_t n_all, double pose[7], float pla
     }
     if (!ok || !(model_cost_change > 0.0)) { /* HandleInvalidStep */
       if (++invalid_steps >= 5) { st->termination = 5; break; }
-      radius *= 0.5; reuse_diagonal = 1;
+      radius = radius / decrease_factor; decrease_factor *= 2.0; reuse_diagonal = 1; /* StepIsInvalid == StepRejected(0.0), levenberg_marquardt_strategy.h */
       continue;
     }
     invalid_steps = 0;

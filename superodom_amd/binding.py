@@ -180,6 +180,21 @@ class LmState(C.Structure):
     _fields_ = [("opaque", C.c_double * 96)]
 
 
+class LmScriptEntry(C.Structure):
+    _fields_ = [("sums", Sums), ("new_solve", C.c_int32), ("reserved", C.c_int32)]
+
+
+class LmScriptStep(C.Structure):
+    _fields_ = [("more", C.c_int32), ("reserved", C.c_int32), ("pose", C.c_double * 7), ("hand", (C.c_uint32 * 4) * 8), ("state", LmState)]
+
+
+class LmScriptResult(C.Structure):
+    _fields_ = [("state", LmState), ("T", C.c_double * 7), ("eval_pose", C.c_double * 7), ("T_final", C.c_double * 7),
+                ("JtJ", C.c_double * 36), ("Jtr", C.c_double * 6),
+                ("lm_more", C.c_int32), ("outer_iter", C.c_int32), ("n_iterations", C.c_int32), ("reg_done", C.c_int32),
+                ("done_count", C.c_uint32), ("reserved", C.c_uint32), ("iterations", IterStats * 16)]
+
+
 EXPORTED = ["so_icp_default_config", "so_icp_create", "so_icp_destroy", "so_icp_last_error", "so_icp_abi_version",
             "so_icp_device_available", "so_icp_set_resolution", "so_icp_set_max_surface_features", "so_icp_set_max_iterations",
             "so_icp_map_set_origin", "so_icp_map_shift", "so_icp_map_add_surf", "so_icp_map_count_5x5", "so_icp_map_export",
@@ -193,7 +208,8 @@ EXPORTED = ["so_icp_default_config", "so_icp_create", "so_icp_destroy", "so_icp_
             "so_icp_map_insert_stats", "so_icp_register_sequence", "so_icp_map_export_records", "so_icp_sequence_announce_next", "so_icp_debug_neighbours", "so_icp_prefilter_announce",
             "so_icp_localization_sequence", "so_icp_extract_features", "so_icp_extract_features_dev", "so_icp_prefilter_scan_dev",
             "so_icp_livox_default_layout", "so_icp_extract_features_livox", "so_icp_extract_features_livox_dev",
-            "so_icp_registered_scan", "so_icp_registered_scan_dev", "so_icp_extract_features_untimed", "so_icp_extract_features_untimed_dev"]
+            "so_icp_registered_scan", "so_icp_registered_scan_dev", "so_icp_extract_features_untimed", "so_icp_extract_features_untimed_dev",
+            "so_icp_debug_lm_script"]
 
 _lib = None
 
@@ -286,6 +302,8 @@ def load():
     L.so_icp_host_free.argtypes = [vp, vp]
     L.so_icp_debug_match_status.argtypes = [vp, u8p, C.c_size_t]
     L.so_icp_debug_neighbours.argtypes = [vp, C.POINTER(C.c_uint32), C.c_size_t]
+    L.so_icp_debug_lm_script.argtypes = [vp, C.c_int, f64p, C.c_int, C.c_int, C.c_int, C.POINTER(LmScriptEntry), C.c_int, C.c_uint64,
+                                         C.POINTER(LmScriptStep), C.POINTER(LmScriptResult)]
     L.so_icp_comm_init_inprocess.argtypes = [vp, C.c_uint64]
     L.so_icp_peer_export.argtypes = [vp, u8p]
     L.so_icp_peer_connect.argtypes = [vp, u8p, i32p]
@@ -814,6 +832,17 @@ class LidarSlamGpu:
         out = np.zeros(n.value, np.uint64)
         self._check(self.L.so_icp_debug_knn_stamps(self.h, _p(out, C.c_uint64), n.value, C.byref(n)))
         return out.reshape(2, -1, 16)
+
+    def debug_lm_script(self, form, x0, entries, lm_max=4, max_outer=5, outer_iter=0, want=0):
+        """so_icp_debug_lm_script: entries = [(Sums, new_solve), ...] -> (LmScriptStep array, LmScriptResult)."""
+        x0 = np.ascontiguousarray(x0, dtype=np.float64); n = len(entries)
+        ent = (LmScriptEntry * n)()
+        for i, (sums, new_solve) in enumerate(entries):
+            ent[i].sums = sums; ent[i].new_solve = int(bool(new_solve))
+        steps = (LmScriptStep * n)(); res = LmScriptResult()
+        self._check(self.L.so_icp_debug_lm_script(self.h, int(form), _p(x0, C.c_double), int(lm_max), int(max_outer), int(outer_iter), ent, n,
+                                                  int(want), steps, C.byref(res)))
+        return steps, res
 
     def synchronize(self):
         self._check(self.L.so_icp_synchronize(self.h))

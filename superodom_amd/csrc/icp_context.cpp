@@ -1120,6 +1120,71 @@ int so_icp_debug_neighbours(so_icp_ctx* c, uint32_t* out, size_t n) {
   HIP_TRY(c, hipMemcpy(out, c->d_nbr5.p, n * 20, hipMemcpyDeviceToHost));
   return SO_ICP_OK;
 }
+static_assert(sizeof(so_icp_lm_script_entry) == sizeof(LmScriptEntry) && sizeof(so_icp_lm_script_step) == sizeof(LmScriptStep) &&
+              offsetof(so_icp_lm_script_step, hand) == offsetof(LmScriptStep, hand) && offsetof(so_icp_lm_script_step, state) == offsetof(LmScriptStep, S) &&
+              SO_ICP_LM_SCRIPT_MAX == kLmScriptMaxEntries && SO_ICP_MAX_OUTER == 16, "so_icp_lm_script_* mirror kernels.h");
+int so_icp_debug_lm_script(so_icp_ctx* c, int form, const double x0[7], int lm_max, int max_outer, int outer_iter, const so_icp_lm_script_entry* entries,
+                           int n_entries, uint64_t want, so_icp_lm_script_step* steps, so_icp_lm_script_result* result) {
+  if (!c) return SO_ICP_E_INVALID;
+  if (!x0 || !entries || !steps || !result || (form != 0 && form != 1) || n_entries < 1 || n_entries > SO_ICP_LM_SCRIPT_MAX || lm_max < 0 ||
+      max_outer < 1 || outer_iter < 0)
+    return fail(c, SO_ICP_E_INVALID, "so_icp_debug_lm_script: bad argument");
+  NEED_DEVICE(c);
+  HIP_TRY(c, hipSetDevice(c->cfg.device_id));
+  struct Scratch {  // owned by this call, whatever way it returns
+    DevBuf state, entries, steps, hist;
+    ~Scratch() { state.release(); entries.release(); steps.release(); hist.release(); }
+  } sc;
+  const size_t hist_bytes = (size_t)kHistReplicas * kHistStride * sizeof(int32_t);
+  HIP_TRY(c, sc.state.reserve(sizeof(DevState)));
+  HIP_TRY(c, sc.entries.reserve((size_t)n_entries * sizeof(LmScriptEntry)));
+  HIP_TRY(c, sc.steps.reserve((size_t)n_entries * sizeof(LmScriptStep)));
+  HIP_TRY(c, sc.hist.reserve(hist_bytes));
+  std::vector<unsigned char> init(sizeof(DevState), 0);
+  DevState* h = reinterpret_cast<DevState*>(init.data());
+  for (int i = 0; i < 7; ++i) { h->pose_in[i] = x0[i]; h->T[i] = x0[i]; h->eval_pose[i] = x0[i]; }
+  h->max_outer = max_outer; h->lm_max = lm_max; h->outer_iter = outer_iter; h->n_iterations = outer_iter;
+  hipStream_t s = c->stream;
+  DevState* ds = sc.state.as<DevState>();
+  LmScriptEntry* de = sc.entries.as<LmScriptEntry>();
+  LmScriptStep* dstep = sc.steps.as<LmScriptStep>();
+  HIP_TRY(c, hipMemcpyAsync(ds, h, sizeof(DevState), hipMemcpyHostToDevice, s));
+  HIP_TRY(c, hipMemcpyAsync(de, entries, (size_t)n_entries * sizeof(LmScriptEntry), hipMemcpyHostToDevice, s));
+  HIP_TRY(c, hipMemsetAsync(dstep, 0xFF, (size_t)n_entries * sizeof(LmScriptStep), s));
+  HIP_TRY(c, hipMemsetAsync(sc.hist.p, 0, hist_bytes, s));
+  if (form == 0) {
+    launch_lm_script_wave(ds, de, n_entries, (unsigned long long)want, dstep, s);
+  } else {
+    const EvalParams ep = eval_params(0.2f, 0, 0);  // (hring == nullptr: the step kernel publishes nothing)
+    int slot = 0;
+    for (int e = 0; e < n_entries; ++e) {
+      slot = entries[e].new_solve ? 0 : slot + 1;
+      launch_lm_step(slot, ds, &de[e].sums, sc.hist.as<int32_t>(), ep, s);
+      launch_lm_script_record(ds, dstep + e, s);
+    }
+  }
+  HIP_TRY(c, hipGetLastError());
+  HIP_TRY(c, hipMemcpyAsync(steps, dstep, (size_t)n_entries * sizeof(LmScriptStep), hipMemcpyDeviceToHost, s));
+  HIP_TRY(c, hipMemcpyAsync(h, ds, sizeof(DevState), hipMemcpyDeviceToHost, s));
+  HIP_TRY(c, hipStreamSynchronize(s));
+  std::memset(result, 0, sizeof(*result));
+  std::memcpy(&result->state, &h->S, sizeof(LmState));
+  std::memcpy(result->T, h->T, sizeof(h->T)); std::memcpy(result->eval_pose, h->eval_pose, sizeof(h->eval_pose));
+  std::memcpy(result->T_final, h->T_final, sizeof(h->T_final));
+  std::memcpy(result->JtJ, h->JtJ, sizeof(h->JtJ)); std::memcpy(result->Jtr, h->Jtr, sizeof(h->Jtr));
+  result->lm_more = h->lm_more; result->outer_iter = h->outer_iter; result->n_iterations = h->n_iterations; result->reg_done = h->reg_done;
+  result->done_count = h->done_count;
+  for (int o = 0; o < 16; ++o) {
+    const DevIterStats& d = h->iters[o];
+    so_icp_iter_stats& t = result->iterations[o];
+    t.translation_norm = d.translation_norm; t.rotation_norm = d.rotation_norm; t.num_surf_from_scan = d.num_surf;
+    t.lm_iterations = d.lm_iterations; t.num_successful_steps = d.num_successful; t.termination = d.termination;
+    t.initial_cost = d.initial_cost; t.final_cost = d.final_cost;
+    std::memcpy(t.reject_hist, d.reject_hist, sizeof(d.reject_hist)); std::memcpy(t.obs_hist, d.obs_hist, sizeof(d.obs_hist));
+    std::memcpy(t.pose_after, d.pose_after, sizeof(d.pose_after));
+  }
+  return SO_ICP_OK;
+}
 int so_icp_synchronize(so_icp_ctx* c) { if (!c) return SO_ICP_E_INVALID; NEED_DEVICE(c); HIP_TRY(c, hipStreamSynchronize(c->stream)); return SO_ICP_OK; }
 
 }  // extern "C"

@@ -245,6 +245,17 @@ void launch_solve_batch(int lm_max, const float* spx, const float* spy, const fl
                         const EvalParams& ep, double* d_partials, uint32_t* d_ticket, int32_t* d_hist, const DevMapView& map,
                         const uint32_t* d_nbr5, const MatchParams& mp, const BatchView& bv, uint32_t n_hyp, hipStream_t s);
 void launch_lm_step(int slot, DevState* st, const LmSums* d_sums, int32_t* d_hist, const EvalParams& ep, hipStream_t s);
+// test aid (so_icp_debug_lm_script): a script of sums for the LM controller, and what the controller left after every entry
+// (device mirrors of so_icp_lm_script_entry / so_icp_lm_script_step)
+constexpr int kLmScriptMaxEntries = 64, kLmScriptStateWords = 96;
+struct LmScriptEntry { LmSums sums; int32_t new_solve, pad; };
+struct LmScriptStep { int32_t more, pad; double pose[7]; uint32_t hand[8][4]; double S[kLmScriptStateWords]; };
+static_assert(offsetof(LmScriptStep, hand) % 16 == 0 && sizeof(LmScriptStep) % 16 == 0, "the hand-off chunks are 16-byte stores");
+static_assert(sizeof(LmState) <= kLmScriptStateWords * 8, "LmScriptStep::S too small");
+// form 0: one wavefront runs lm_control_wave over the entries (steps[e].hand receives entry e's hand-off record)
+void launch_lm_script_wave(DevState* st, const LmScriptEntry* entries, int n_entries, unsigned long long want, LmScriptStep* steps, hipStream_t s);
+// form 1: after launch_lm_step on one entry, record lm_more / eval_pose / the state into *step
+void launch_lm_script_record(const DevState* st, LmScriptStep* step, hipStream_t s);
 // peer exchange self-test: every rank writes a tagged chunk into every inbox and waits (<= 2 s) for all of them in its own; *d_ok = 1 on success
 void launch_peer_selftest(void* const inbox[8], int rank, int world, uint32_t tag, int32_t* d_ok, hipStream_t s);
 // Seam B

@@ -1569,7 +1569,7 @@ __device__ __forceinline__ int lm_control_regs(int slot, DevState* st, LmState& 
   const int rd = lm_solve_finished(st, ctl, S.x, S.count, S.lm_iterations, S.num_successful, S.termination, S.initial_cost, S.x_cost, sums);
   if (rd) {
     if (reg_done_out) *reg_done_out = 1;
-    const bool have = S.count > 0;
+    const bool have = S.count >= 1.0;
     for (int i = 0; i < 36; ++i) st->JtJ[i] = have ? S.H[i] : 0.0;
     for (int i = 0; i < 6; ++i) st->Jtr[i] = have ? S.g[i] : 0.0;
   }
@@ -1658,7 +1658,8 @@ __device__ SO_LM_INLINE int lm_control(int slot, DevState* st, LmState& S_lds, c
 // (six pivots through rsqrt), the substitutions, the model cost change, the quaternion update -- stays the code of
 // lm_solver.h, run by every lane on the same (gathered) operands, so every element goes through the operations of the
 // one-thread controller in the same order: identical bits (the batched solve and the per-evaluation launches keep the
-// one-thread form; tests/test_gpu_configs.py compares them bit for bit).  The state's home is the LDS copy; what the next
+// one-thread form; tests/test_gpu_configs.py compares them bit for bit on registrations, tests/test_gpu_lm_scripts.py branch by
+// branch on scripted sums).  The state's home is the LDS copy; what the next
 // lm_feed needs beyond the sums (lm_after_candidate) and the store-back run AFTER the hand-off has been published.
 __device__ __forceinline__ int lm_control_wave(int slot, DevState* st, LmState& S, const LmSums& sums, const LmCtl& ctl, double* gather /* LDS, >= 56 doubles */,
                                                u4v* hand, unsigned long long want, double* pose_out, int* reg_done_out, int lane,
@@ -1683,7 +1684,7 @@ __device__ __forceinline__ int lm_control_wave(int slot, DevState* st, LmState& 
     count = sums.count; x_cost = sums.cost; initial_cost = x_cost; x_norm = 0;
     if (is_mat) Hl = sums.JtJ[tri];
     if (is_vec) gl = sums.Jtr[lj];
-    if (!(count > 0)) { termination = 4; done = 1; }  // no residual blocks: nothing to minimise (scale 1, diag 0 go to the state below)
+    if (!(count >= 1.0)) { termination = 4; done = 1; }  // no residual blocks: nothing to minimise (scale 1, diag 0 go to the state below)
     else {
       // jacobi_scaling, fixed at iteration 0: 1 / (1 + sqrt(H_jj)) on the diagonal lanes, handed to the element lanes through the state
       const double sc = 1.0 / (1.0 + sqrt(Hl));
@@ -1808,7 +1809,7 @@ __device__ __forceinline__ int lm_control_wave(int slot, DevState* st, LmState& 
     __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");  // (the next round of the loop rewrites the gather area)
     if (!ok || !(mcc > 0.0)) {  // HandleInvalidStep
       if (++invalid_steps >= LmConst::kMaxConsecutiveInvalidSteps) { termination = 5; done = 1; break; }
-      inv_radius *= 2.0;
+      inv_radius = inv_radius * decrease_factor; decrease_factor *= 2.0;  // StepIsInvalid == StepRejected(0), see lm_propose
       continue;
     }
     SO_LM_STAMP(dbg, 5);
@@ -1868,7 +1869,7 @@ __device__ __forceinline__ int lm_control_wave(int slot, DevState* st, LmState& 
     }
     rd = __builtin_amdgcn_readfirstlane(rd);
     if (rd) {  // final normal equations: H and g as the state holds them, element by element
-      const bool have = count > 0;
+      const bool have = count >= 1.0;
       if (is_mat) st->JtJ[lane] = have ? Hl : 0.0;
       if (is_vec) st->Jtr[lj] = have ? gl : 0.0;
     }
@@ -2691,6 +2692,61 @@ __global__ __launch_bounds__(64) void lm_step_kernel(int slot, DevState* st, con
   }
 }
 
+// ---- test aid (so_icp_debug_lm_script): the controller on SCRIPTED sums, no scene, no other workgroup.
+// Form 0: ONE wavefront walks the script and calls lm_control_wave the way eval_pass does -- sums, state and LmCtl in LDS, a
+// gather area of 64 doubles, the hand-off record in global memory (entry e's eight chunks are steps[e].hand), pose_out / reg_done_out
+// in LDS; load_ctl at slot 0, the state stored back to st->S when a solve ends.  lm_control_wave is force-inlined: this is a second
+// compilation of its source, not the instance inside solve_kernel.  No wait, no polling; the only loop is the one over the
+// <= 64 entries.  An entry is skipped the way the launches skip a pass (eval_slot_active): after the registration is over, or when it
+// does not start a solve and none is running.
+__global__ __launch_bounds__(64) void lm_script_wave_kernel(DevState* st, const LmScriptEntry* __restrict__ entries, int n_entries,
+                                                            unsigned long long want, LmScriptStep* steps) {
+  __shared__ LmSums sh_sums;
+  __shared__ LmState sh_S;
+  __shared__ LmCtl sh_ctl;
+  __shared__ double sh_gather[64];
+  __shared__ double sh_pose[8];
+  __shared__ int sh_reg_done;
+  const int tid = threadIdx.x;
+  constexpr int kStateWords = (int)(sizeof(LmState) / 8);
+  copy_words(reinterpret_cast<double*>(&sh_S), reinterpret_cast<const double*>(&st->S), kStateWords, tid, 64);
+  if (tid < 7) sh_pose[tid] = st->eval_pose[tid];
+  int reg_done = st->reg_done, running = 0, slot = 0;
+  __syncthreads();
+  for (int e = 0; e < n_entries && e < kLmScriptMaxEntries; ++e) {
+    const int first = entries[e].new_solve != 0;
+    int more = 0;
+    if (!reg_done && (first || running)) {
+      slot = first ? 0 : slot + 1;
+      copy_words(reinterpret_cast<double*>(&sh_sums), reinterpret_cast<const double*>(&entries[e].sums), (int)(sizeof(LmSums) / 8), tid, 64);
+      if (slot == 0) load_ctl(sh_ctl, st, tid, 32);
+      __syncthreads();
+      more = lm_control_wave(slot, st, sh_S, sh_sums, sh_ctl, sh_gather, reinterpret_cast<u4v*>(steps[e].hand), want, sh_pose, &sh_reg_done, tid);
+      __syncthreads();
+      running = more;
+      if (!more) {  // the solve is over: the state goes home, the next solve's load_ctl must see T and outer_iter as just stored
+        copy_words(reinterpret_cast<double*>(&st->S), reinterpret_cast<const double*>(&sh_S), kStateWords, tid, 64);
+        reg_done = sh_reg_done;
+        __threadfence();
+        __syncthreads();
+      }
+    }
+    if (tid == 0) { steps[e].more = more; steps[e].pad = 0; }
+    if (tid < 7) steps[e].pose[tid] = sh_pose[tid];
+    for (int i = tid; i < kLmScriptStateWords; i += 64) steps[e].S[i] = i < kStateWords ? reinterpret_cast<const double*>(&sh_S)[i] : 0.0;
+    __syncthreads();
+  }
+}
+// Form 1 runs the production lm_step_kernel once per entry; this records what it left: lm_more, eval_pose, the state.
+__global__ __launch_bounds__(64) void lm_script_record_kernel(const DevState* st, LmScriptStep* step) {
+  const int tid = threadIdx.x;
+  constexpr int kStateWords = (int)(sizeof(LmState) / 8);
+  if (tid == 0) { step->more = st->lm_more; step->pad = 0; }
+  if (tid < 7) step->pose[tid] = st->eval_pose[tid];
+  if (tid < 32) reinterpret_cast<uint32_t*>(step->hand)[tid] = 0u;
+  for (int i = tid; i < kLmScriptStateWords; i += 64) step->S[i] = i < kStateWords ? reinterpret_cast<const double*>(&st->S)[i] : 0.0;
+}
+
 // ------------------------------------------------------------------------------------------------
 // Seam B kernels
 // ------------------------------------------------------------------------------------------------
@@ -2905,6 +2961,12 @@ void launch_solve_batch(int lm_max, const float* spx, const float* spy, const fl
 }
 void launch_lm_step(int slot, DevState* st, const LmSums* sums, int32_t* hist, const EvalParams& ep, hipStream_t s) {
   hipLaunchKernelGGL(lm_step_kernel, dim3(1), dim3(64), 0, s, slot, st, sums, hist, ep);
+}
+void launch_lm_script_wave(DevState* st, const LmScriptEntry* entries, int n_entries, unsigned long long want, LmScriptStep* steps, hipStream_t s) {
+  hipLaunchKernelGGL(lm_script_wave_kernel, dim3(1), dim3(64), 0, s, st, entries, n_entries, want, steps);
+}
+void launch_lm_script_record(const DevState* st, LmScriptStep* step, hipStream_t s) {
+  hipLaunchKernelGGL(lm_script_record_kernel, dim3(1), dim3(64), 0, s, st, step);
 }
 // peer exchange self-test (so_icp_peer_connect): the same stores and loads as the solve's exchange, one chunk per rank pair
 __global__ __launch_bounds__(64) void peer_selftest_kernel(EvalParams ep, uint32_t tag, int32_t* __restrict__ ok_out) {

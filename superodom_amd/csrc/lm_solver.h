@@ -37,7 +37,7 @@ struct LmSums {      // == so_icp_sums (include/so_icp.h), 45 doubles
 // Round 5: the controller's serial chain carries no division any more.  Ceres keeps the trust-region radius and divides by it
 // (lm_diagonal = sqrt(diagonal / radius)), divides the cost change by the model cost change, and forms two norms when the
 // candidate's cost arrives.  Here the state holds the RECIPROCAL radius -- every update of the radius is a product (x 1/f on an
-// accepted step, x decrease_factor = a power of two on a rejected one, x 2 on an invalid one), so 1/radius is never formed --
+// accepted step, x decrease_factor = a power of two on a rejected or an invalid one), so 1/radius is never formed --
 // and lm_propose, right after it has the candidate, forms 1 / model_cost_change, |x - cand| and |cand| (inputs of the NEXT
 // lm_feed's tolerance tests and step quality): on the device that work runs after the next pose has been handed to the other
 // workgroups, i.e. beside their evaluation pass instead of in front of it.  rel = cost_change x (1 / model_cost_change) differs
@@ -200,7 +200,10 @@ SO_HD int lm_propose(LmState& S, double next_pose[7], unsigned long long* dbg = 
     }
     if (!ok || !(mcc > 0.0)) {  // HandleInvalidStep
       if (++S.invalid_steps >= LmConst::kMaxConsecutiveInvalidSteps) { S.termination = 5; S.done = 1; return 0; }
-      S.inv_radius *= 2.0;  // radius *= 0.5
+      // LevenbergMarquardtStrategy::StepIsInvalid (ceres 2.0.0 levenberg_marquardt_strategy.h) is StepRejected(0): "treat the
+      // current step as a rejected step with no increase in solution quality" -- the radius shrinks by the GROWING factor
+      S.inv_radius = S.inv_radius * S.decrease_factor;
+      S.decrease_factor *= 2.0;
       continue;
     }
     SO_LM_STAMP(dbg, 5);
@@ -229,7 +232,7 @@ SO_HD int lm_begin(LmState& S, const double x0[7], const LmSums& sums, int max_i
   lm_unpack(sums, S.H, S.g);
   SO_UNROLL
   for (int j = 0; j < 6; ++j) { S.scale[j] = 1.0; S.diag[j] = 0; }
-  if (!(sums.count > 0)) { S.termination = 4; S.done = 1; return 0; }  // no residual blocks: nothing to minimise
+  if (!(sums.count >= 1.0)) { S.termination = 4; S.done = 1; return 0; }  // no residual blocks (the count is a whole number; NaN counts as none): nothing to minimise
   SO_UNROLL
   for (int j = 0; j < 6; ++j) S.scale[j] = 1.0 / (1.0 + sqrt(S.H[7 * j]));  // jacobi_scaling, fixed at iteration 0
   double n2 = 0;
