@@ -4,6 +4,7 @@ This is the thin host-side mirror used by tests and bench.py.  The reference's h
 (LidarSLAM, src/LidarProcess/LidarSlam.cpp); its C++ adapter is shown in INTEGRATION.md.  Loading
 fails loudly when the library is missing or when no HIP device is usable -- there is no CPU path."""
 import ctypes as C
+import math
 import os
 
 import numpy as np
@@ -643,84 +644,65 @@ class LidarSlamGpu:
                                                      float(line_res), float(plane_res), C.byref(d), C.byref(no), C.byref(info)))
         return d.value, no.value, info
 
-    @staticmethod
-    def _feature_args(poses, T_i_l):
+    def _extract_host(self, fn, payload, shape, layout, lidar_start_time, poses, poses_are_imu, T_i_l):
+        """a so_icp_extract_features* host entry: fn(ctx, payload, *shape, layout, time, poses..., clouds out, info); shape: (width, height) or
+        (n,).  Returns (records uint8 [n, 32], cloud_surface uint8 [n_surface, 32], FeatureInfo)."""
+        raw = np.ascontiguousarray(payload, np.uint8).reshape(-1)
+        n = math.prod(map(int, shape))
+        rec = np.zeros((n, 32), np.uint8)
+        surf = np.zeros((max(n, 1), 32), np.uint8)
+        out = (rec.ctypes.data_as(C.c_void_p), surf.ctypes.data_as(C.c_void_p))
+        info = self._extract(fn, raw.ctypes.data_as(C.c_void_p), shape, layout, lidar_start_time, poses, poses_are_imu, T_i_l, out)
+        return rec, surf[:info.n_surface].copy(), info
+
+    def _extract_dev(self, fn, d_payload, shape, layout, lidar_start_time, poses, poses_are_imu, T_i_l):
+        """a so_icp_extract_features*_dev entry; returns (d_nodistortion, d_surface, FeatureInfo)"""
+        d_rec = C.c_void_p(); d_surf = C.c_void_p()
+        info = self._extract(fn, C.c_void_p(d_payload), shape, layout, lidar_start_time, poses, poses_are_imu, T_i_l, (C.byref(d_rec), C.byref(d_surf)))
+        return d_rec.value, d_surf.value, info
+
+    def _extract(self, fn, payload, shape, layout, lidar_start_time, poses, poses_are_imu, T_i_l, out):
         poses = np.zeros((0, 8)) if poses is None else np.ascontiguousarray(poses, np.float64).reshape(-1, 8)
         til = None if T_i_l is None else np.ascontiguousarray(T_i_l, np.float64)
-        return poses, (_p(poses, C.c_double) if len(poses) else None), len(poses), (None if til is None else _p(til, C.c_double)), til
+        info = FeatureInfo()
+        self._check(fn(self.h, payload, *map(int, shape), C.byref(layout), float(lidar_start_time), _p(poses, C.c_double) if len(poses) else None,
+                       len(poses), int(bool(poses_are_imu)), None if til is None else _p(til, C.c_double), *out, C.byref(info)))
+        return info
 
     def extract_features(self, payload, width, height, layout, lidar_start_time, poses=None, poses_are_imu=False, T_i_l=None):
         """featureExtraction's sweep -> LaserFeature clouds on the device.  payload: the PointCloud2 data (uint8); poses: [m, 8]
         (time, position, quaternion x y z w) or None (no de-skew).  Returns (cloud_nodistortion uint8 [n, 32], cloud_surface
         uint8 [n_surface, 32], FeatureInfo)."""
-        raw = np.ascontiguousarray(payload, np.uint8).reshape(-1)
-        poses, pp, npo, tp, _keep = self._feature_args(poses, T_i_l)
-        n = int(width) * int(height)
-        rec = np.zeros((n, 32), np.uint8)
-        surf = np.zeros((max(n, 1), 32), np.uint8)
-        info = FeatureInfo()
-        self._check(self.L.so_icp_extract_features(self.h, raw.ctypes.data_as(C.c_void_p), int(width), int(height), C.byref(layout),
-                                                   float(lidar_start_time), pp, npo, int(bool(poses_are_imu)), tp, rec.ctypes.data_as(C.c_void_p),
-                                                   surf.ctypes.data_as(C.c_void_p), C.byref(info)))
-        return rec, surf[:info.n_surface].copy(), info
+        return self._extract_host(self.L.so_icp_extract_features, payload, (width, height), layout, lidar_start_time, poses, poses_are_imu, T_i_l)
 
     def extract_features_dev(self, d_payload, width, height, layout, lidar_start_time, poses=None, poses_are_imu=False, T_i_l=None):
         """the same on a payload resident in HBM; returns (d_nodistortion, d_surface, FeatureInfo): context-owned device buffers,
         valid until the next call"""
-        poses, pp, npo, tp, _keep = self._feature_args(poses, T_i_l)
-        d_rec = C.c_void_p(); d_surf = C.c_void_p(); info = FeatureInfo()
-        self._check(self.L.so_icp_extract_features_dev(self.h, C.c_void_p(d_payload), int(width), int(height), C.byref(layout),
-                                                       float(lidar_start_time), pp, npo, int(bool(poses_are_imu)), tp, C.byref(d_rec),
-                                                       C.byref(d_surf), C.byref(info)))
-        return d_rec.value, d_surf.value, info
+        return self._extract_dev(self.L.so_icp_extract_features_dev, d_payload, (width, height), layout, lidar_start_time, poses, poses_are_imu, T_i_l)
 
     def extract_features_livox(self, points, n_points, layout, lidar_start_time, poses=None, poses_are_imu=False, T_i_l=None):
         """livoxHandler's sweep -> LaserFeature clouds on the device.  points: the CustomMsg's points as bytes (uint8), n_points of them
         layout.point_step apart (the last one may end with its last field); the rest as extract_features."""
-        raw = np.ascontiguousarray(points, np.uint8).reshape(-1)
-        poses, pp, npo, tp, _keep = self._feature_args(poses, T_i_l)
-        n = int(n_points)
-        rec = np.zeros((n, 32), np.uint8)
-        surf = np.zeros((max(n, 1), 32), np.uint8)
-        info = FeatureInfo()
-        self._check(self.L.so_icp_extract_features_livox(self.h, raw.ctypes.data_as(C.c_void_p), n, C.byref(layout), float(lidar_start_time), pp,
-                                                         npo, int(bool(poses_are_imu)), tp, rec.ctypes.data_as(C.c_void_p),
-                                                         surf.ctypes.data_as(C.c_void_p), C.byref(info)))
-        return rec, surf[:info.n_surface].copy(), info
+        return self._extract_host(self.L.so_icp_extract_features_livox, points, (n_points,), layout, lidar_start_time, poses, poses_are_imu, T_i_l)
 
     def extract_features_livox_dev(self, d_points, n_points, layout, lidar_start_time, poses=None, poses_are_imu=False, T_i_l=None):
         """the same on points resident in HBM (any byte alignment); returns (d_nodistortion, d_surface, FeatureInfo): context-owned
         device buffers, valid until the next extract_features*_dev call"""
-        poses, pp, npo, tp, _keep = self._feature_args(poses, T_i_l)
-        d_rec = C.c_void_p(); d_surf = C.c_void_p(); info = FeatureInfo()
-        self._check(self.L.so_icp_extract_features_livox_dev(self.h, C.c_void_p(d_points), int(n_points), C.byref(layout), float(lidar_start_time),
-                                                             pp, npo, int(bool(poses_are_imu)), tp, C.byref(d_rec), C.byref(d_surf), C.byref(info)))
-        return d_rec.value, d_surf.value, info
+        return self._extract_dev(self.L.so_icp_extract_features_livox_dev, d_points, (n_points,), layout, lidar_start_time, poses, poses_are_imu, T_i_l)
 
     def extract_features_untimed(self, payload, width, height, layout, lidar_start_time, poses=None, poses_are_imu=False, T_i_l=None):
         """a sweep without per-point time (assignTimeforPointCloud) -> LaserFeature clouds on the device.  payload: the PointCloud2 data
         (uint8), layout: untimed_layout(...); the rest as extract_features.  Returns (cloud_nodistortion uint8 [info.n_points, 32] --
         the records that remain --, cloud_surface uint8 [n_surface, 32], FeatureInfo)."""
-        raw = np.ascontiguousarray(payload, np.uint8).reshape(-1)
-        poses, pp, npo, tp, _keep = self._feature_args(poses, T_i_l)
-        n = int(width) * int(height)
-        rec = np.zeros((n, 32), np.uint8)
-        surf = np.zeros((max(n, 1), 32), np.uint8)
-        info = FeatureInfo()
-        self._check(self.L.so_icp_extract_features_untimed(self.h, raw.ctypes.data_as(C.c_void_p), int(width), int(height), C.byref(layout),
-                                                           float(lidar_start_time), pp, npo, int(bool(poses_are_imu)), tp,
-                                                           rec.ctypes.data_as(C.c_void_p), surf.ctypes.data_as(C.c_void_p), C.byref(info)))
-        return rec[:info.n_points].copy(), surf[:info.n_surface].copy(), info
+        rec, surf, info = self._extract_host(self.L.so_icp_extract_features_untimed, payload, (width, height), layout, lidar_start_time, poses,
+                                             poses_are_imu, T_i_l)
+        return rec[:info.n_points].copy(), surf, info
 
     def extract_features_untimed_dev(self, d_payload, width, height, layout, lidar_start_time, poses=None, poses_are_imu=False, T_i_l=None):
         """the same on a payload resident in HBM; returns (d_nodistortion, d_surface, FeatureInfo): context-owned device buffers
         holding info.n_points and info.n_surface records, valid until the next extract_features*_dev call"""
-        poses, pp, npo, tp, _keep = self._feature_args(poses, T_i_l)
-        d_rec = C.c_void_p(); d_surf = C.c_void_p(); info = FeatureInfo()
-        self._check(self.L.so_icp_extract_features_untimed_dev(self.h, C.c_void_p(d_payload), int(width), int(height), C.byref(layout),
-                                                               float(lidar_start_time), pp, npo, int(bool(poses_are_imu)), tp, C.byref(d_rec),
-                                                               C.byref(d_surf), C.byref(info)))
-        return d_rec.value, d_surf.value, info
+        return self._extract_dev(self.L.so_icp_extract_features_untimed_dev, d_payload, (width, height), layout, lidar_start_time, poses,
+                                 poses_are_imu, T_i_l)
 
     def deskew_scan(self, records, time_off, lidar_start_time, poses, poses_are_imu, T_i_l=None):
         """featureExtraction::removePointDistortion on the device.  records: uint8 [n, stride] (float x y z at 0 4 8, float time

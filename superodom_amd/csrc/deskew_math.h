@@ -4,6 +4,7 @@
 // quaternion <-> matrix conversions [UPSTREAM Eigen, written out]; slerp is Eigen::QuaternionBase::slerp.
 #pragma once
 #include <cstddef>
+#include <cstdint>
 #include <vector>
 
 #include "so_math.h"
@@ -90,6 +91,9 @@ SO_HD void quat_slerp(const double a[4], const double b[4], double t, double o[4
 
 // one stamped pose of the buffer the scan is de-skewed against: 8 doubles {time, px, py, pz, qx, qy, qz, qw}
 constexpr int kStampedPoseDoubles = 8;
+// a buffer of up to this many poses is copied into LDS by the kernels that de-skew (device_idioms.h copy_pose_table); a longer
+// one is read from global memory
+constexpr uint32_t kDeskewLdsPoses = 512;
 
 // getInterpolatedPoseAtTime (featureExtraction.cpp:257-276): the first entry with time > ts is "after"; before the first
 // entry its pose is returned; otherwise slerp / lerp between the neighbours.  ts at or beyond the last entry has no

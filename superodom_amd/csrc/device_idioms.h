@@ -2,6 +2,8 @@
 #pragma once
 #include <hip/hip_runtime.h>
 
+#include "deskew_math.h"
+
 namespace soicp {
 
 // LDS written by some lanes of the wavefront is read by others (and the other way round): orders the accesses in the compiler
@@ -26,6 +28,19 @@ __device__ __forceinline__ int cube_coord_f(float c, int origin) {
   int i = (int)(s * 0.02) + origin;
   if (s < 0) i--;
   return i;
+}
+
+// Adds the number of lanes of the wavefront whose `flag` is set to *counter with one atomic, from the first such lane.  Every lane
+// of the wavefront calls it (the ballot is over the active lanes).
+__device__ __forceinline__ void wave_count_add(bool flag, uint32_t* counter) {
+  const unsigned long long m = __ballot(flag);
+  if (m && (threadIdx.x & 63) == (uint32_t)__builtin_ctzll(m)) atomicAdd(counter, (uint32_t)__popcll(m));
+}
+
+// The workgroup copies the stamped-pose table (n_poses <= kDeskewLdsPoses entries of kStampedPoseDoubles doubles, deskew_math.h)
+// into LDS; the barrier behind it is the caller's.
+__device__ __forceinline__ void copy_pose_table(double* tab_lds, const double* __restrict__ poses, uint32_t n_poses) {
+  for (uint32_t k = threadIdx.x; k < n_poses * kStampedPoseDoubles; k += blockDim.x) tab_lds[k] = poses[k];
 }
 
 }  // namespace soicp

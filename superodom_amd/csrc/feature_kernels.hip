@@ -10,7 +10,11 @@
 // so the records equal that kernel's run on the ingested sweep bit for bit.
 #include <hip/hip_runtime.h>
 
+#include <initializer_list>
+#include <type_traits>
+
 #include "deskew_math.h"
+#include "device_idioms.h"
 #include "feature_kernels.h"
 #include "so_math.h"
 #include "untimed_math.h"
@@ -27,15 +31,34 @@ __device__ __forceinline__ T load_field(const uint8_t* p) {
   return v;
 }
 
-constexpr uint32_t kIngestLdsPoses = 512;  // (deskew_kernel's kDeskewLdsPoses: beyond it the pose table is read from global memory)
+// A4 of the three ingests: the base, the steps and every present offset (< 0: absent) are multiples of 4
+static bool dword_aligned(const void* base, std::initializer_list<uint32_t> steps, std::initializer_list<int32_t> offsets) {
+  bool a4 = reinterpret_cast<uintptr_t>(base) % 4u == 0;
+  for (uint32_t step : steps) a4 = a4 && step % 4u == 0;
+  for (int32_t off : offsets) a4 = a4 && (off < 0 || off % 4 == 0);
+  return a4;
+}
+
+// The instantiation of an ingest kernel: launch(A4, DESKEW, LDS) with the three as compile-time constants (std::bool_constant).
+// No pose, no de-skew; up to kDeskewLdsPoses poses, the table in LDS; more, the table read from global memory.
+template <typename Launch>
+static void dispatch_ingest(bool a4, uint32_t n_poses, Launch&& launch) {
+  auto with_a4 = [&](auto A4) {
+    if (!n_poses) launch(A4, std::false_type{}, std::false_type{});
+    else if (n_poses <= kDeskewLdsPoses) launch(A4, std::true_type{}, std::true_type{});
+    else launch(A4, std::true_type{}, std::false_type{});
+  };
+  if (a4) with_a4(std::true_type{});
+  else with_a4(std::false_type{});
+}
 
 template <bool A4, bool DESKEW, bool LDS>
 __global__ __launch_bounds__(256) void ingest_deskew_kernel(const uint8_t* __restrict__ raw, uint32_t n, SweepFields sf, uint8_t* __restrict__ out,
                                                             double t0, const double* __restrict__ poses, uint32_t n_poses, DeskewFrames f,
                                                             uint32_t* __restrict__ n_clamped) {
-  __shared__ double tab_lds[(DESKEW && LDS) ? kIngestLdsPoses * kStampedPoseDoubles : 1];
+  __shared__ double tab_lds[(DESKEW && LDS) ? kDeskewLdsPoses * kStampedPoseDoubles : 1];
   if (DESKEW && LDS) {
-    for (uint32_t k = threadIdx.x; k < n_poses * kStampedPoseDoubles; k += blockDim.x) tab_lds[k] = poses[k];
+    copy_pose_table(tab_lds, poses, n_poses);
     __syncthreads();
   }
   const double* tab = (DESKEW && LDS) ? tab_lds : poses;
@@ -69,28 +92,16 @@ __global__ __launch_bounds__(256) void ingest_deskew_kernel(const uint8_t* __res
     o[0] = make_uint4(__float_as_uint(x), __float_as_uint(y), __float_as_uint(z), 0u);
     o[1] = make_uint4(__float_as_uint(intensity), __float_as_uint(time), ring, 0u);
   }
-  if (DESKEW) {
-    const unsigned long long m = __ballot(clamped);
-    if (m && (threadIdx.x & 63) == (uint32_t)__builtin_ctzll(m)) atomicAdd(n_clamped, (uint32_t)__popcll(m));
-  }
-}
-
-template <bool A4>
-static void launch_ingest_a(const uint8_t* d_raw, uint32_t n, const SweepFields& sf, uint8_t* d_rec, double t0, const double* d_poses,
-                            uint32_t n_poses, const DeskewFrames& f, uint32_t* d_n_clamped, hipStream_t s) {
-  const uint32_t blocks = (n + 255u) / 256u;
-  if (!n_poses) ingest_deskew_kernel<A4, false, false><<<blocks, 256, 0, s>>>(d_raw, n, sf, d_rec, t0, d_poses, 0u, f, d_n_clamped);
-  else if (n_poses <= kIngestLdsPoses) ingest_deskew_kernel<A4, true, true><<<blocks, 256, 0, s>>>(d_raw, n, sf, d_rec, t0, d_poses, n_poses, f, d_n_clamped);
-  else ingest_deskew_kernel<A4, true, false><<<blocks, 256, 0, s>>>(d_raw, n, sf, d_rec, t0, d_poses, n_poses, f, d_n_clamped);
+  if (DESKEW) wave_count_add(clamped, n_clamped);
 }
 
 void launch_ingest_deskew(const uint8_t* d_raw, uint32_t n, const SweepFields& sf, uint8_t* d_rec, double t0, const double* d_poses,
                           uint32_t n_poses, const DeskewFrames& f, uint32_t* d_n_clamped, hipStream_t s) {
   if (!n) return;
-  bool a4 = (reinterpret_cast<uintptr_t>(d_raw) % 4u) == 0 && sf.point_step % 4u == 0 && sf.row_step % 4u == 0;
-  for (int32_t off : {sf.x, sf.y, sf.z, sf.intensity, sf.time, sf.ring}) a4 = a4 && (off < 0 || off % 4 == 0);
-  if (a4) launch_ingest_a<true>(d_raw, n, sf, d_rec, t0, d_poses, n_poses, f, d_n_clamped, s);
-  else launch_ingest_a<false>(d_raw, n, sf, d_rec, t0, d_poses, n_poses, f, d_n_clamped, s);
+  const bool a4 = dword_aligned(d_raw, {sf.point_step, sf.row_step}, {sf.x, sf.y, sf.z, sf.intensity, sf.time, sf.ring});
+  dispatch_ingest(a4, n_poses, [&](auto A4, auto DESKEW, auto LDS) {
+    ingest_deskew_kernel<A4(), DESKEW(), LDS()><<<(n + 255u) / 256u, 256, 0, s>>>(d_raw, n, sf, d_rec, t0, d_poses, n_poses, f, d_n_clamped);
+  });
 }
 
 // livoxHandler's loop (:794-806) fused with removePointDistortion, a kernel of its own beside ingest_deskew_kernel (whose code
@@ -101,9 +112,9 @@ template <bool A4, bool DESKEW, bool LDS>
 __global__ __launch_bounds__(256) void livox_ingest_deskew_kernel(const uint8_t* __restrict__ raw, uint32_t n, LivoxFields lf, uint8_t* __restrict__ out,
                                                                   double t0, const double* __restrict__ poses, uint32_t n_poses, DeskewFrames f,
                                                                   uint32_t* __restrict__ n_clamped) {
-  __shared__ double tab_lds[(DESKEW && LDS) ? kIngestLdsPoses * kStampedPoseDoubles : 1];
+  __shared__ double tab_lds[(DESKEW && LDS) ? kDeskewLdsPoses * kStampedPoseDoubles : 1];
   if (DESKEW && LDS) {
-    for (uint32_t k = threadIdx.x; k < n_poses * kStampedPoseDoubles; k += blockDim.x) tab_lds[k] = poses[k];
+    copy_pose_table(tab_lds, poses, n_poses);
     __syncthreads();
   }
   const double* tab = (DESKEW && LDS) ? tab_lds : poses;
@@ -131,28 +142,16 @@ __global__ __launch_bounds__(256) void livox_ingest_deskew_kernel(const uint8_t*
     o[0] = make_uint4(__float_as_uint(x), __float_as_uint(y), __float_as_uint(z), 0u);
     o[1] = make_uint4(__float_as_uint(intensity), __float_as_uint(time), ring, 0u);
   }
-  if (DESKEW) {
-    const unsigned long long m = __ballot(clamped);
-    if (m && (threadIdx.x & 63) == (uint32_t)__builtin_ctzll(m)) atomicAdd(n_clamped, (uint32_t)__popcll(m));
-  }
-}
-
-template <bool A4>
-static void launch_livox_a(const uint8_t* d_raw, uint32_t n, const LivoxFields& lf, uint8_t* d_rec, double t0, const double* d_poses,
-                           uint32_t n_poses, const DeskewFrames& f, uint32_t* d_n_clamped, hipStream_t s) {
-  const uint32_t blocks = (n + 255u) / 256u;
-  if (!n_poses) livox_ingest_deskew_kernel<A4, false, false><<<blocks, 256, 0, s>>>(d_raw, n, lf, d_rec, t0, d_poses, 0u, f, d_n_clamped);
-  else if (n_poses <= kIngestLdsPoses) livox_ingest_deskew_kernel<A4, true, true><<<blocks, 256, 0, s>>>(d_raw, n, lf, d_rec, t0, d_poses, n_poses, f, d_n_clamped);
-  else livox_ingest_deskew_kernel<A4, true, false><<<blocks, 256, 0, s>>>(d_raw, n, lf, d_rec, t0, d_poses, n_poses, f, d_n_clamped);
+  if (DESKEW) wave_count_add(clamped, n_clamped);
 }
 
 void launch_livox_ingest_deskew(const uint8_t* d_raw, uint32_t n, const LivoxFields& lf, uint8_t* d_rec, double t0, const double* d_poses,
                                 uint32_t n_poses, const DeskewFrames& f, uint32_t* d_n_clamped, hipStream_t s) {
   if (!n) return;
-  bool a4 = (reinterpret_cast<uintptr_t>(d_raw) % 4u) == 0 && lf.point_step % 4u == 0;
-  for (uint32_t off : {lf.offset_time, lf.x, lf.y, lf.z}) a4 = a4 && off % 4u == 0;
-  if (a4) launch_livox_a<true>(d_raw, n, lf, d_rec, t0, d_poses, n_poses, f, d_n_clamped, s);
-  else launch_livox_a<false>(d_raw, n, lf, d_rec, t0, d_poses, n_poses, f, d_n_clamped, s);
+  const bool a4 = dword_aligned(d_raw, {lf.point_step}, {(int32_t)lf.offset_time, (int32_t)lf.x, (int32_t)lf.y, (int32_t)lf.z});
+  dispatch_ingest(a4, n_poses, [&](auto A4, auto DESKEW, auto LDS) {
+    livox_ingest_deskew_kernel<A4(), DESKEW(), LDS()><<<(n + 255u) / 256u, 256, 0, s>>>(d_raw, n, lf, d_rec, t0, d_poses, n_poses, f, d_n_clamped);
+  });
 }
 
 // uniformFeatureExtraction, featureExtraction.cpp:507-522: candidates i = 1, 1 + s, 1 + 2s, ... < n, each against the RAW record
@@ -392,12 +391,11 @@ __global__ __launch_bounds__(256) void untimed_ingest_deskew_kernel(const uint8_
                                                                     unsigned long long* __restrict__ state, uint32_t* __restrict__ ticket) {
   constexpr int kPer = (int)(kSurfItems / 256u);
   static_assert(kPer <= 8, "rings holds one byte per round in a 64-bit word");
-  __shared__ double tab_lds[(DESKEW && LDS) ? kIngestLdsPoses * kStampedPoseDoubles : 1];
+  __shared__ double tab_lds[(DESKEW && LDS) ? kDeskewLdsPoses * kStampedPoseDoubles : 1];
   __shared__ uint32_t s_bid, s_pre[kPer * 4], s_agg, s_excl;
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   if (tid == 0) s_bid = atomicAdd(ticket, 1u);
-  if (DESKEW && LDS)
-    for (uint32_t k = threadIdx.x; k < n_poses * kStampedPoseDoubles; k += blockDim.x) tab_lds[k] = poses[k];
+  if (DESKEW && LDS) copy_pose_table(tab_lds, poses, n_poses);
   __syncthreads();
   const double* tab = (DESKEW && LDS) ? tab_lds : poses;
   const uint32_t bid = s_bid;
@@ -470,24 +468,15 @@ __global__ __launch_bounds__(256) void untimed_ingest_deskew_kernel(const uint8_
   if (DESKEW && lane == 0 && wave_clamped) atomicAdd(n_clamped, wave_clamped);
 }
 
-template <bool A4>
-static void launch_untimed_a(const uint8_t* d_raw, uint32_t n, const UntimedFields& uf, uint8_t* d_rec, double t0, const double* d_poses,
-                             uint32_t n_poses, const DeskewFrames& f, uint32_t* d_n_clamped, uint32_t* d_n_kept, unsigned long long* d_state,
-                             uint32_t* d_ticket, hipStream_t s) {
-  const uint32_t blocks = untimed_workgroups(n);
-  if (!n_poses) untimed_ingest_deskew_kernel<A4, false, false><<<blocks, 256, 0, s>>>(d_raw, n, uf, d_rec, t0, d_poses, 0u, f, d_n_clamped, d_n_kept, d_state, d_ticket);
-  else if (n_poses <= kIngestLdsPoses) untimed_ingest_deskew_kernel<A4, true, true><<<blocks, 256, 0, s>>>(d_raw, n, uf, d_rec, t0, d_poses, n_poses, f, d_n_clamped, d_n_kept, d_state, d_ticket);
-  else untimed_ingest_deskew_kernel<A4, true, false><<<blocks, 256, 0, s>>>(d_raw, n, uf, d_rec, t0, d_poses, n_poses, f, d_n_clamped, d_n_kept, d_state, d_ticket);
-}
-
 void launch_untimed_ingest_deskew(const uint8_t* d_raw, uint32_t n, const UntimedFields& uf, uint8_t* d_rec, double t0, const double* d_poses,
                                   uint32_t n_poses, const DeskewFrames& f, uint32_t* d_n_clamped, uint32_t* d_n_kept, unsigned long long* d_state,
                                   uint32_t* d_ticket, hipStream_t s) {
   if (!n) return;
-  bool a4 = (reinterpret_cast<uintptr_t>(d_raw) % 4u) == 0 && uf.point_step % 4u == 0 && uf.row_step % 4u == 0;
-  for (int32_t off : {uf.x, uf.y, uf.z, uf.intensity}) a4 = a4 && (off < 0 || off % 4 == 0);
-  if (a4) launch_untimed_a<true>(d_raw, n, uf, d_rec, t0, d_poses, n_poses, f, d_n_clamped, d_n_kept, d_state, d_ticket, s);
-  else launch_untimed_a<false>(d_raw, n, uf, d_rec, t0, d_poses, n_poses, f, d_n_clamped, d_n_kept, d_state, d_ticket, s);
+  const bool a4 = dword_aligned(d_raw, {uf.point_step, uf.row_step}, {uf.x, uf.y, uf.z, uf.intensity});
+  dispatch_ingest(a4, n_poses, [&](auto A4, auto DESKEW, auto LDS) {
+    untimed_ingest_deskew_kernel<A4(), DESKEW(), LDS()><<<untimed_workgroups(n), 256, 0, s>>>(d_raw, n, uf, d_rec, t0, d_poses, n_poses, f, d_n_clamped,
+                                                                                            d_n_kept, d_state, d_ticket);
+  });
 }
 
 }  // namespace soicp

@@ -1755,14 +1755,13 @@ void launch_voxel_filter(const VoxelFilterArgs& a, hipStream_t s) {
 // buffer interpolated at the point's own time, T_final = [T_l_i] T_w_original^-1 T_w_current [T_i_l], x y z rewritten in
 // place.  The buffer (tens of entries for a 0.1 s sweep against a 200 Hz IMU) sits in LDS; every thread runs its own
 // upper_bound over it.  32 B read + 12 B written per point, ~1.5 k fp64 operations: bound by neither at these sizes.
-constexpr uint32_t kDeskewLdsPoses = 512;
 template <bool LDS>
 __global__ __launch_bounds__(256) void deskew_kernel(uint8_t* __restrict__ pts, uint32_t n, uint32_t stride, uint32_t time_off, double t0,
                                                      const double* __restrict__ poses, uint32_t n_poses, DeskewFrames f,
                                                      uint32_t* __restrict__ n_clamped) {
   __shared__ double tab_lds[LDS ? kDeskewLdsPoses * kStampedPoseDoubles : 1];
   if (LDS) {
-    for (uint32_t k = threadIdx.x; k < n_poses * kStampedPoseDoubles; k += blockDim.x) tab_lds[k] = poses[k];
+    copy_pose_table(tab_lds, poses, n_poses);
     __syncthreads();
   }
   const double* tab = LDS ? tab_lds : poses;
@@ -1777,8 +1776,7 @@ __global__ __launch_bounds__(256) void deskew_kernel(uint8_t* __restrict__ pts, 
       xyz[0] = x; xyz[1] = y; xyz[2] = z;
     }
   }
-  const unsigned long long m = __ballot(clamped);
-  if (m && (threadIdx.x & 63) == (uint32_t)__builtin_ctzll(m)) atomicAdd(n_clamped, (uint32_t)__popcll(m));
+  wave_count_add(clamped, n_clamped);
 }
 
 void launch_deskew(uint8_t* d_pts, uint32_t n, uint32_t stride, uint32_t time_off, double t0, const double* d_poses, uint32_t n_poses,
@@ -1809,8 +1807,7 @@ __global__ __launch_bounds__(256) void transform_cloud_kernel(uint8_t* __restric
     k = x * x + y * y + z * z > 0.01;
     keep[i] = k ? 1 : 0;
   }
-  const unsigned long long m = __ballot(k);
-  if (m && (threadIdx.x & 63) == (uint32_t)__builtin_ctzll(m)) atomicAdd(n_kept, (uint32_t)__popcll(m));
+  wave_count_add(k, n_kept);
 }
 void launch_transform_cloud(uint8_t* d_pts, uint32_t n, uint32_t stride, const Pose& pose, uint8_t* d_keep, uint32_t* d_n_kept, hipStream_t s) {
   if (!n) return;
