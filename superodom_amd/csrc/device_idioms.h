@@ -2,6 +2,8 @@
 #pragma once
 #include <hip/hip_runtime.h>
 
+#include <type_traits>
+
 #include "deskew_math.h"
 
 namespace soicp {
@@ -29,6 +31,65 @@ __device__ __forceinline__ int cube_coord_f(float c, int origin) {
   if (s < 0) i--;
   return i;
 }
+
+// ---- launch entry: fetch what the first statements of a kernel read in one memory trip per batch (arguments, then state)
+// A launch starts cold: its kernel-argument segment was just written by the host side and its state block by the launch in front
+// (the scalar cache is invalidated between kernels).  The compiler sinks every argument load to its first use, and the early
+// returns of a kernel keep its state loads apart, so the entry code touches those lines one after the other, one trip each.  The
+// helpers below load one dword of every 64-byte line of a byte range, together, and drop the values: the code behind them finds its
+// lines in the scalar cache.  The addresses are wave-uniform, so the loads are scalar loads; nothing is stored, nothing stays live.
+
+// Bytes of the explicit arguments of a kernel, laid out as the kernel-argument segment lays them out (each at its natural alignment).
+template <typename... A>
+struct KernargExtent;
+template <>
+struct KernargExtent<> { static constexpr size_t at(size_t off) { return off; } };
+template <typename T, typename... A>
+struct KernargExtent<T, A...> {
+  static constexpr size_t at(size_t off) { return KernargExtent<A...>::at((off + alignof(T) - 1) / alignof(T) * alignof(T) + sizeof(T)); }
+};
+template <typename F>
+struct KernargBytes;
+template <typename... A>
+struct KernargBytes<void (*)(A...)> { static constexpr size_t value = KernargExtent<A...>::at(0); };
+
+// OR of one dword per 64-byte line that the BYTES bytes at p overlap, whatever p's alignment beyond 4: the dwords at 0, 64, 128, ...
+// and the last one (a line that begins inside the range holds one of the former, or begins after the last of them and holds the latter)
+template <size_t BYTES, typename P>
+__device__ __forceinline__ uint32_t touch_lines(P p) {
+  static_assert(BYTES >= 4 && BYTES % 4 == 0, "whole dwords: never a byte beyond the range");
+  uint32_t x = p[BYTES / 4 - 1];
+#pragma unroll
+  for (size_t o = 0; o + 4 <= BYTES; o += 64) x |= p[o / 4];
+  return x;
+}
+// The values are not needed, the loads are.  after_loaded takes them in a scalar register through an empty statement and hands back
+// the pointer the code behind it goes on with, plus a zero the compiler cannot see through: the statement survives because that
+// pointer is used, and the loads of that code cannot be issued before the statement's wait.  Not volatile on purpose -- a volatile
+// statement counts as a possible store, and behind it the uniform loads through every pointer that is not read-only to the kernel
+// become vector loads.  (The pointer itself through the statement would lose its address space: flat loads.)
+template <typename T>
+__device__ __forceinline__ T* after_loaded(T* p, uint32_t x) {
+  uint32_t zero = 0;
+  asm("" : "+s"(zero) : "s"(x));
+  using Byte = std::conditional_t<std::is_const<T>::value, const char, char>;
+  return reinterpret_cast<T*>(reinterpret_cast<Byte*>(p) + zero);
+}
+
+// one dword per line of the explicit arguments of the calling kernel: kernarg_lines<decltype(&this_kernel<...>)>()
+template <typename F>
+__device__ __forceinline__ uint32_t kernarg_lines() {
+  constexpr size_t bytes = KernargBytes<F>::value;
+  static_assert(bytes % 4 == 0 && bytes <= 4096, "explicit kernel arguments: whole dwords, within the segment");
+  typedef const __attribute__((address_space(4))) uint32_t* KernargWords;
+  // (+ the grid size, which the segment holds behind the explicit arguments, possibly on a line of its own: read the way every
+  //  kernel reads it, not by address -- nothing beyond the explicit arguments is addressed here)
+  return touch_lines<bytes>((KernargWords)__builtin_amdgcn_kernarg_segment_ptr()) | gridDim.x;
+}
+// the fields FIRST .. LAST (both included, in declaration order) of the block at st
+#define SO_WARM_FIELDS(st, T, FIRST, LAST)                                                                                    \
+  touch_lines<offsetof(T, LAST) + sizeof(T::LAST) - offsetof(T, FIRST)>(                                                       \
+      reinterpret_cast<const uint32_t*>(reinterpret_cast<const char*>(st) + offsetof(T, FIRST)))
 
 // Adds the number of lanes of the wavefront whose `flag` is set to *counter with one atomic, from the first such lane.  Every lane
 // of the wavefront calls it (the ballot is over the active lanes).

@@ -48,6 +48,20 @@ namespace soicp {
 static_assert(SO_FIT_SUCCESS == SO_MATCH_SUCCESS && SO_FIT_BAD_PCA == SO_MATCH_BAD_PCA && SO_FIT_INVALID == SO_MATCH_INVALID && SO_FIT_MSE == SO_MATCH_MSE,
               "plane_fit.h returns MatchingResult codes");
 
+// Launch entry (device_idioms.h): the lines of the state block that the first statements of the sweep and solve kernels read --
+// loop bounds .. work-list counters .. pose, and the chain fields a registration leaves behind -- requested together.
+#ifndef SO_ENTRY_WARM
+#define SO_ENTRY_WARM 1
+#endif
+// (LOOP / CHAIN: which of the two ranges the launch reads)
+template <bool LOOP = true, bool CHAIN = true>
+__device__ __forceinline__ uint32_t state_lines(const DevState* st) {
+  static_assert(offsetof(DevState, max_outer) < offsetof(DevState, reg_done) && offsetof(DevState, reg_done) < offsetof(DevState, bin_packed) &&
+                offsetof(DevState, bin_packed) < offsetof(DevState, T) && offsetof(DevState, T_chain) < offsetof(DevState, done_count) &&
+                offsetof(DevState, done_count) < offsetof(DevState, peer_seq), "the two field ranges below");
+  return (LOOP ? SO_WARM_FIELDS(st, DevState, max_outer, T) : 0u) | (CHAIN ? SO_WARM_FIELDS(st, DevState, T_chain, peer_seq) : 0u);
+}
+
 // ------------------------------------------------------------------------------------------------
 // map addressing
 // ------------------------------------------------------------------------------------------------
@@ -600,6 +614,9 @@ __global__ __launch_bounds__(256, 4) void knn_plane_kernel(const float4* __restr
   __shared__ uint32_t tcanon[4][kTileCand + 16];  // per wavefront: canonical map index of the staged candidate
   __shared__ uint32_t rowtab[4][2][72];  // per wavefront: exclusive candidate offsets [33] and first canonical index [32] of the block's x-runs
                                          // (packed light chunks: four tables of 17 + 16 entries, one per row of 16 lanes)
+  unsigned long long t_entry = 0;
+  if (PROF) t_entry = wall_clock64();  // (profiling: "kernel entry -> first item begins", with the stamps below)
+  if (SO_ENTRY_WARM) st = after_loaded(st, kernarg_lines<decltype(&knn_plane_kernel<PROF, BATCH, BEGIN>)>());
   if (BATCH) {
     const size_t h = bv.active[blockIdx.y];
     st += h; binned += h * bv.bs; chunk_start += h * bv.bs;
@@ -610,6 +627,8 @@ __global__ __launch_bounds__(256, 4) void knn_plane_kernel(const float4* __restr
   // (MatchParams::begin: first launch of a registration whose scan was binned ahead -- prologue, pose and counters from the arguments)
   constexpr bool begin = BEGIN != 0 && !BATCH;
   constexpr bool chained_begin = BEGIN == 2 && !BATCH;
+  // (a BEGIN launch takes loop state and pose from its arguments: of the state block it reads the chain fields only)
+  if (SO_ENTRY_WARM) st = after_loaded(st, state_lines<!begin, !BATCH>(st));
   if (!begin && st->reg_done) return;  // the registration already converged: this launch is a no-op
   if (!BATCH && mp.chain_expect && st->done_count != mp.chain_expect) return;  // chained registration whose predecessor was not over: no-op
   // BEGIN launch of a chained registration: valid only if the registration in front of it was over, and its guess is what that one's
@@ -670,7 +689,7 @@ __global__ __launch_bounds__(256, 4) void knn_plane_kernel(const float4* __restr
   const bool stamp = PROF && (abl & 128) != 0 && mp.kdbg != nullptr;
   unsigned long long ts[4] = {0, 0, 0, 0}, acc[5] = {0, 0, 0, 0, 0}, t_first = 0, n_mine = 0, t_maxchunk = 0;
   unsigned long long n_cand_total = 0, n_q_total = 0, n_groups_total = 0, n_pass2 = 0, max_info = 0, n_fb_total = 0;
-  unsigned long long c_first = 0;
+  unsigned long long c_first = 0, t_item0 = 0;
   if (stamp) { t_first = wall_clock64(); c_first = clock64(); }
   const int nc = map.nc;
   const float cell = (float)(1.0 / map.inv_cell);
@@ -694,7 +713,7 @@ __global__ __launch_bounds__(256, 4) void knn_plane_kernel(const float4* __restr
   // algorithmic) for values a handful of integer operations rebuild.
   int lane = lane_k;
   asm volatile("" : "+v"(lane));
-  if (stamp) ts[0] = wall_clock64();
+  if (stamp) { ts[0] = wall_clock64(); if (!n_mine) t_item0 = ts[0]; }
   uint32_t j = 0;
   bool valid_q = false;
   // A chunk of at most 32 queries is served by BOTH halves of the wavefront: lanes l and l + 32 hold the same query and
@@ -1340,7 +1359,8 @@ __global__ __launch_bounds__(256, 4) void knn_plane_kernel(const float4* __restr
     d[0] = t_first; d[1] = wall_clock64();
     for (int i = 0; i < 5; ++i) d[2 + i] = acc[i];
     d[15] = clock64() - c_first;  // shader-clock ticks over the wavefront's life (d[1] - d[0] = the same span at 100 MHz)
-    d[7] = n_mine; d[8] = t_maxchunk; d[9] = n_cand_total; d[10] = n_q_total; d[11] = n_groups_total; d[12] = n_pass2; d[13] = max_info;
+    d[7] = n_mine; d[8] = t_maxchunk; d[9] = n_cand_total; d[10] = n_q_total; d[11] = n_groups_total; d[13] = max_info;
+    d[12] = n_pass2 | ((t_item0 ? t_item0 - t_entry : 0ull) << 32);  // + kernel entry -> first item begins (ticks), wavefronts with work
     d[14] = n_fb_total | ((unsigned long long)(__builtin_amdgcn_s_getreg(63492) & 0xFFFFu) << 32) | ((unsigned long long)(__builtin_amdgcn_s_getreg(63508) & 0xFu) << 48);  // + HW_ID[15:0] (wave, simd, cu, se), XCC_ID: where the wavefront ran
   }
   if (PROF) {
@@ -1386,6 +1406,7 @@ __global__ __launch_bounds__(256) void knn_query_wave_kernel(const float* __rest
                                                              const uint32_t* __restrict__ mcell_start, DevMapView map, MatchParams mp, int max_surface_features,
                                                              uint8_t* __restrict__ status, uint32_t* __restrict__ nbr5) {
   __shared__ uint32_t rowtab[4][2][20];  // per wavefront: exclusive candidate offsets [17] and first canonical index [16] of the nine x-runs
+  if (SO_ENTRY_WARM) st = after_loaded(st, kernarg_lines<decltype(&knn_query_wave_kernel<BEGIN>)>());
   const int lane = threadIdx.x & 63;
   const int wv = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
   const uint32_t k = blockIdx.x * 4u + (uint32_t)wv;  // this wavefront's share of the scan
@@ -1394,6 +1415,7 @@ __global__ __launch_bounds__(256) void knn_query_wave_kernel(const float* __rest
   // looked at: one memory round trip for the three instead of two (a sweep is five dependent round trips and little else)
   const uint32_t il0 = i_lo + (uint32_t)lane < n ? i_lo + (uint32_t)lane : n - 1u;
   float sx = scan[3 * il0], sy = scan[3 * il0 + 1], sz = scan[3 * il0 + 2];
+  if (SO_ENTRY_WARM) st = after_loaded(st, state_lines<!BEGIN, true>(st));  // (behind the point's request: the state lines travel beside it)
   double T7[7];
 #pragma unroll
   for (int t = 0; t < 7; ++t) T7[t] = BEGIN ? (a.chain_expect ? st->T_chain[t] : a.pose[t]) : st->T[t];
@@ -2460,7 +2482,8 @@ __device__ __forceinline__ int eval_pass(int slot, int fuse_lm, const Pose& pose
     if (stamp && tid == 0 && (FIT || slot == 1)) {
       t_lm = wall_clock64();
       unsigned long long* d = st->dbg + (FIT ? 0 : 8);
-      d[0] = t_loop - t_begin; d[1] = t_red - t_loop; d[2] = t_ticket - t_red; d[3] = t_loaded - t_ticket; d[4] = t_sums - t_loaded;
+      // (word 3, "load partials", does not exist in this path: the fit record's is solve_kernel's "kernel entry -> first pass begins")
+      d[0] = t_loop - t_begin; d[1] = t_red - t_loop; d[2] = t_ticket - t_red; if (!FIT || BATCH) d[3] = t_loaded - t_ticket; d[4] = t_sums - t_loaded;
       d[5] = t_lm - t_sums; d[6] = t_lm - t_begin; d[7] = t_ctl - t_sums;
     }
     return sh_more ? kPassMore : kPassDone;
@@ -2583,6 +2606,10 @@ __global__ __launch_bounds__(256, SO_SOLVE_BLOCKS / 256) void eval_kernel(int sl
                                                    const float4* __restrict__ mpts, const uint32_t* __restrict__ nbr5,
                                                    MatchParams mp) {
   __shared__ EvalShared sh;
+  if (SO_ENTRY_WARM) {
+    st = after_loaded(st, kernarg_lines<decltype(&eval_kernel<FIT, PROF>)>());
+    st = after_loaded(st, SO_WARM_FIELDS(st, DevState, max_outer, eval_pose));  // reg_done, lm_more, either pose
+  }
   if (!eval_slot_active(st, slot)) return;
   const Pose pose = pose_from_array(slot == 0 ? st->T : st->eval_pose);
   (void)eval_pass<FIT, false, PROF>(slot, fuse_lm, pose, spx, spy, spz, corr, st, ep, partials, ticket, hist, out, mpts, nbr5, mp, sh);
@@ -2608,6 +2635,9 @@ __global__ __launch_bounds__(256, BATCH ? 2 : 1) void solve_kernel(int lm_max, c
                                                     MatchParams mp, BatchView bv) {
   __shared__ EvalShared sh;
   __shared__ CorrCache cache;  // 26 KB next to the 64 KB of EvalShared: gfx950 has 160 KB of LDS per CU, one workgroup each here
+  unsigned long long t_entry = 0;
+  if (PROF && !BATCH) t_entry = wall_clock64();  // (profiling: "kernel entry -> first pass begins", word 3 of the fit record)
+  if (SO_ENTRY_WARM) st = after_loaded(st, kernarg_lines<decltype(&solve_kernel<PROF, BATCH, PEER>)>());
   WgSpan span{0, 0, 0, false};
   if (BATCH) {
     const uint32_t G = bv.wg_per_hyp, hi = blockIdx.x / G, sub = blockIdx.x - hi * G;
@@ -2619,6 +2649,7 @@ __global__ __launch_bounds__(256, BATCH ? 2 : 1) void solve_kernel(int lm_max, c
     span.vb1 = (uint32_t)(((unsigned long long)(sub + 1u) * bv.v_grid) / G);
     span.ctl = sub == 0;
   }
+  if (SO_ENTRY_WARM) st = after_loaded(st, state_lines<true, !BATCH>(st));
   if (st->reg_done) return;
   if (!BATCH && ep.chain_expect && st->done_count != ep.chain_expect) return;  // chained registration whose predecessor was not over: no-op
   const int tid = threadIdx.x;
@@ -2637,6 +2668,7 @@ __global__ __launch_bounds__(256, BATCH ? 2 : 1) void solve_kernel(int lm_max, c
     sh.ctl.lm_max = st->lm_max; sh.ctl.outer_iter = st->outer_iter; sh.ctl.max_outer = st->max_outer;
   }
   const unsigned long long tag0 = (e0 + 1ull) << 5;  // pass tags: unique over launches (every launch advances the epoch) and passes (slot <= 16)
+  if (PROF && !BATCH && (ep.ablate & 128) && tid == 0 && blockIdx.x == 0) st->dbg[3] = wall_clock64() - t_entry;
   int code = eval_pass<true, true, PROF, BATCH, PEER>(0, 1, pose, spx, spy, spz, corr, st, ep, partials, ticket, hist, out, mpts, nbr5, mp, sh, tag0, &cache, hand, e0 + 1ull, span);
   for (int slot = 1; slot <= lm_max; ++slot) {
     __syncthreads();

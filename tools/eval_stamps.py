@@ -18,6 +18,7 @@ os.environ.setdefault("SOICP_ABLATE", "128")
 from superodom_amd import binding, synth  # noqa: E402
 
 NAMES = ["loop", "lds_reduce+store", "ticket", "load_partials", "reduce+sums", "lm", "total", "controller"]
+# persistent solve (solve_kernel): the fit record has no "load_partials" phase, its word 3 is "kernel entry -> first pass begins"
 
 
 def main():
@@ -61,7 +62,8 @@ def main():
                                                     "pose_plus", "store back"], np.round(lm_acc / a.reps, 2))))
     rec = slam.debug_knn_stamps()
     if rec is not None:
-        steals_all = (rec[..., 12].astype(np.uint64) >> np.uint64(32)).astype(np.int64)  # queries a wavefront claimed from the hand-over ring
+        entry_all = (rec[..., 12].astype(np.uint64) >> np.uint64(32)).astype(np.float64) * 0.01  # kernel entry -> first item begins (us), wavefronts with work
+        steals_all = np.zeros(rec.shape[:-1], np.int64)  # (the hand-over ring that used these bits is gone)
         rec = rec.copy(); rec[..., 12] = rec[..., 12].astype(np.uint64) & np.uint64(0xFFFFFFFF)
         rec = rec.astype(np.float64)
         for o in range(2):
@@ -75,6 +77,11 @@ def main():
                       f"those wavefronts end at p50 {np.percentile((r[w_, 1] - t0_) * 0.01, 50):.1f} max {((r[w_, 1] - t0_) * 0.01).max():.1f} us, the others at max {((r[~w_, 1] - t0_) * 0.01).max():.1f} us")
             if not len(r):
                 continue
+            en = entry_all[o][rec[o][:, 0] > 0]
+            en = en[en > 0]
+            if len(en):
+                print(f"knn sweep {o}: kernel entry -> first item begins (us): p50 {np.percentile(en, 50):.2f} p90 {np.percentile(en, 90):.2f} max {en.max():.2f} "
+                      f"mean {en.mean():.2f} ({len(en)} wavefronts)")
             t0 = r[:, 0].min()
             busy = r[r[:, 7] > 0]
             nch = busy[:, 7].sum()
@@ -118,6 +125,7 @@ def main():
             idle = r[r[:, 7] == 0]
             if len(idle):
                 print("   idle workgroups: start offset p50 %.1f max %.1f us" % (np.percentile((idle[:, 0] - t0) * 0.01, 50), ((idle[:, 0] - t0) * 0.01).max()))
+    print("solve: kernel entry -> first pass begins (us): %.2f  (controller's workgroup, thread 0; word 3 of the fit record)" % acc[0][3])
     for k, row in zip(("fit ", "eval"), acc):
         print(k, {n: round(float(v), 2) for n, v in zip(NAMES, row)})
 
