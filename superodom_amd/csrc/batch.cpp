@@ -64,15 +64,12 @@ int register_batch_group(so_icp_ctx* c, const float* d_scan, size_t n, const dou
     std::memset(st, 0, sizeof(*st));
     st->flags = (!c->dmap ? SO_ICP_FLAG_HOST_MAP : 0u) | (c->direct_readback ? 0u : SO_ICP_FLAG_COPY_READBACK);
     std::memcpy(poses_out + 7 * (size_t)h, poses_in + 7 * (size_t)h, 7 * sizeof(double));
-    if (c->have_hist) uncertainty_from_hist(c->prev_obs_hist, st->uncertainty);
-    st->pos_in_localmap[0] = pos[0]; st->pos_in_localmap[1] = pos[1]; st->pos_in_localmap[2] = pos[2];
-    st->laser_cloud_surf_from_map_num = count_5x5; st->laser_cloud_surf_stack_num = (int32_t)n; st->startup_count = c->startup_count;
+    fill_stats_header(c, st, pos, count_5x5, n);
     hyp_rc[h] = SO_ICP_OK;
   }
   if (!(count_5x5 > 50)) { for (int h = 0; h < B; ++h) hyp_rc[h] = SO_ICP_NOT_ENOUGH_MAP_FEATURES; return SO_ICP_OK; }  // LidarSlam.cpp:113-116
-  if (n >= ((size_t)1 << 21)) return fail(c, SO_ICP_E_UNSUPPORTED, "scan of 2^21 points or more: the work-list counters hold 21 bits each (chunk descriptors 26)");
-  const int max_outer = std::min(c->cfg.max_iterations > 0 ? c->cfg.max_iterations : 4, SO_ICP_MAX_OUTER);
-  const int lm_max = std::min(c->cfg.lm_max_iterations > 0 ? c->cfg.lm_max_iterations : 4, 16);
+  if (n >= kMaxScanPoints) return refuse_scan_size(c);
+  const int max_outer = outer_limit(c->cfg.max_iterations), lm_max = lm_limit(c->cfg.lm_max_iterations);
   const uint32_t lg = bin_table_log2(n);
   int rc = batch_reserve(c, (uint32_t)B, n, lg);
   if (rc) return rc;
@@ -187,7 +184,6 @@ int register_batch_group(so_icp_ctx* c, const float* d_scan, size_t n, const dou
 }  // namespace
 
 extern "C" {
-
 
 int so_icp_register_batch(so_icp_ctx* c, const float* xyz, const void* d_scan, size_t n, size_t stride_bytes, const double* poses_in,
                           int n_hyp, double* poses_out, so_icp_stats* stats, int32_t* rc_out) {

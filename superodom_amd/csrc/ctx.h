@@ -4,6 +4,7 @@
 //   staging.cpp           so_icp_stage_scan: slots, copy thread, binning ahead, so_icp_host_register / _alloc
 //   sequence.cpp          so_icp_register_sequence, so_icp_sequence_announce_next
 //   batch.cpp             so_icp_register_batch
+//   reg_plan.h            what all three decide without a device: loop limits, query split, table and work-list sizes, window rule
 //   localization.cpp      so_icp_localization(_dev), de-skew, so_icp_transform_cloud, the pre-filter
 //   multi_gpu.cpp         RCCL, in-process groups, peer exchange, shard helpers
 //   localization_sequence.cpp, feature_extraction.cpp
@@ -26,6 +27,7 @@
 #include "kernels.h"
 #include "local_map.h"
 #include "lm_solver.h"
+#include "reg_plan.h"
 #include "so_math.h"
 
 namespace soicp::host {
@@ -89,12 +91,7 @@ struct BinHashTable {
   BinTable view() const { return BinTable{key.as<uint32_t>(), cnt.as<uint32_t>(), off.as<uint32_t>(), log2}; }
   void release() { key.release(); cnt.release(); off.release(); log2 = 0; }
 };
-// the table for a scan of n points: >= 2 slots per query
-inline uint32_t bin_table_log2(size_t n) {
-  uint32_t lg = 16;
-  while ((1ull << lg) < 2 * (unsigned long long)n) ++lg;
-  return lg;
-}
+static_assert(kOuterCap == SO_ICP_MAX_OUTER, "outer_limit (reg_plan.h) caps at the per-iteration statistics of so_icp_stats");
 
 struct InprocGroup;  // so_icp_comm_init_inprocess (multi_gpu.cpp)
 
@@ -183,7 +180,7 @@ struct so_icp_ctx {
   //  marker packet, and so is what hipStreamQuery enqueues to learn whether the queue has drained: either one landed between the
   //  speculated k-NN sweep and the solve launch enqueued behind it, where the command processor spent ~6 us on it -- the gap
   //  every kernel trace of rounds 3-5 shows in front of the second solve.  The watchdog of that wait is now the clock: the queue
-  //  is queried only after kReportWatchdogMs without a report.)
+  //  is queried only after kReportWatchdogMs without a report -- await_report, icp_context.cpp.)
   bool batch_mode = false;    // no kernel timing, tracker state read-only
   bool batch_single = false;  // batch on ONE lane: nothing runs next to it, the persistent solve launch is safe
   bool no_map_shift = false;  // so_icp_register_batch: hypotheses after the first keep the window of the first
@@ -328,10 +325,32 @@ int reserve_scan_buffers(so_icp_ctx* c, size_t n);
 MatchParams match_params(float plane_res, int ablate);
 EvalParams eval_params(float plane_res, int variant, int ablate);
 unsigned long long registration_params(so_icp_ctx* c, float plane_res, size_t n, uint32_t chunk_cap, int ring, MatchParams& mp, EvalParams& ep);
-void begin_in_sweep(const so_icp_ctx* c, MatchParams& mp, const so_icp_ctx::StageSlot& sl, size_t n, const double pose[7], int max_outer,
-                    int lm_max, uint32_t chain_expect);
-void note_packing(so_icp_ctx* c, const DevState& H, const MatchParams& mp, size_t n);
-void uncertainty_from_hist(const int32_t* H, double u[6]);
+int refuse_scan_size(so_icp_ctx* c);  // a scan of kMaxScanPoints or more: SO_ICP_E_UNSUPPORTED with its text
+// What the sweep and solve launches of one registration read: the scan, its work list, the correspondences, the loop bounds
+// (so_icp_register's RegPlan and so_icp_register_sequence's SeqRun are both one of these and more)
+struct RegWork {
+  const float* d_scan = nullptr; size_t n = 0;
+  bool query_waves = false;                                             // every kept query a wavefront of its own: no work list
+  const float4* d_binned = nullptr; const uint32_t* d_chunks = nullptr;  // the work list of a scan swept in chunks
+  CorrBuffers corr{nullptr, nullptr, nullptr};
+  int max_outer = 0, lm_max = 0;
+};
+// One k-NN sweep.  `mp_it`: the caller's copy of the registration's parameters for this sweep (publish_prev is the caller's policy);
+// `first`: outer iteration 0; `begin_slot`: the registration's prologue rides on this sweep of a scan binned ahead (MatchParams::begin),
+// its counters are in that slot; `pose`, `chain_expect`: the prologue's guess / the chained start's condition
+void launch_sweep(so_icp_ctx* c, const RegWork& w, MatchParams& mp_it, bool first, const so_icp_ctx::StageSlot* begin_slot, const double pose[7],
+                  uint32_t chain_expect, hipEvent_t ev_start, hipEvent_t ev_stop);
+// The whole solve of one outer iteration in one launch; gives `ep_it` (the caller's copy: defer_publish, chain_*) its epoch
+void launch_persistent_solve(so_icp_ctx* c, const RegWork& w, EvalParams& ep_it, const MatchParams& mp);
+// The host's wait for the report `want` in a pinned mirror's seq word; `s`: the queue whose draining ends the wait without one.  The
+// mirrors are polled; the watchdog of that wait is the clock and, once it has run out, the queue (so_icp_ctx::speculate has the
+// measured reason why nothing -- no event, no stream query -- accompanies the wait in the normal case).
+enum class Report { kReported, kDrained /* every launch completed, no report */, kHipError /* c->err is set */ };
+Report await_report(so_icp_ctx* c, const volatile unsigned long long* seq, unsigned long long want, hipStream_t s);
+// the head of so_icp_stats every registration entry fills alike: uncertainty, window position, map and scan counts, startup_count
+void fill_stats_header(const so_icp_ctx* c, so_icp_stats* st, const int pos[3], int count_5x5, size_t n);
+// what a finished registration, reported in `mirror`, leaves in the context: h_state, the packing policy, knn_list_fits, done_count_seen
+void note_registration_done(so_icp_ctx* c, DevState* mirror, const MatchParams& mp, size_t n, bool sets_list_fits, bool sets_done_count);
 void fill_result(so_icp_ctx* c, const DevState& H, const double pose_in[7], so_icp_stats* st, double pose_out[7], bool update_tracker);
 constexpr int kRetryWithoutPersistentSolve = -1000;  // internal: never leaves register_core
 int register_core(so_icp_ctx* c, const float* d_scan, size_t n, const double pose_in[7], double pose_out[7], so_icp_stats* st);

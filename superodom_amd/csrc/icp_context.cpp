@@ -159,25 +159,76 @@ unsigned long long registration_params(so_icp_ctx* c, float plane_res, size_t n,
   mp.hring[0] = ep.hring[0]; mp.hring[1] = ep.hring[1]; mp.seq_base = ep.seq_base; mp.publish_prev = 0;
   return seq_base;
 }
-// The first k-NN sweep of a scan binned ahead starts the registration itself (MatchParams::begin): the prologue's arguments
-void begin_in_sweep(const so_icp_ctx* c, MatchParams& mp, const so_icp_ctx::StageSlot& sl, size_t n, const double pose[7], int max_outer,
-                    int lm_max, uint32_t chain_expect) {
-  mp.begin = 1; mp.begin_args.max_outer = max_outer; mp.begin_args.lm_max = lm_max; mp.begin_max_surface_features = c->cfg.max_surface_features;
-  mp.begin_n = (uint32_t)n; std::memcpy(mp.begin_args.pose, pose, sizeof(mp.begin_args.pose));
-  mp.begin_args.chain_expect = chain_expect; mp.begin_args.pad = 0;
-  mp.begin_ctr = sl.pb_ctr.as<unsigned long long>(); mp.begin_state = c->d_state;
+int refuse_scan_size(so_icp_ctx* c) {  // (kernels.hip: bin_offsets_kernel / knn_plane_kernel)
+  return fail(c, SO_ICP_E_UNSUPPORTED, "scan of 2^21 points or more: the work-list counters hold 21 bits each (chunk descriptors 26)");
 }
-// After a registration's last report: the k-NN packing policy (so_icp_ctx::knn_pack_hold)
-void note_packing(so_icp_ctx* c, const DevState& H, const MatchParams& mp, size_t n) {
+// processPlannerFeatures: every kept query in parallel (LidarSlam.cpp:323-344)
+void launch_sweep(so_icp_ctx* c, const RegWork& w, MatchParams& mp_it, bool first, const so_icp_ctx::StageSlot* begin_slot, const double pose[7],
+                  uint32_t chain_expect, hipEvent_t ev_start, hipEvent_t ev_stop) {
+  if (w.query_waves) {
+    launch_knn_query_waves(w.d_scan, (uint32_t)w.n, c->d_state, pose, w.max_outer, w.lm_max, first, c->d_hist, c->view, mp_it, c->cfg.max_surface_features,
+                           c->d_status.as<uint8_t>(), c->d_nbr5.as<uint32_t>(), c->stream, ev_start, ev_stop, first ? chain_expect : 0u);
+  } else {
+    if (begin_slot) {  // the first sweep of a scan binned ahead starts the registration itself (MatchParams::begin): the prologue's arguments
+      mp_it.begin = 1; mp_it.begin_args.max_outer = w.max_outer; mp_it.begin_args.lm_max = w.lm_max; mp_it.begin_max_surface_features = c->cfg.max_surface_features;
+      mp_it.begin_n = (uint32_t)w.n; std::memcpy(mp_it.begin_args.pose, pose, sizeof(mp_it.begin_args.pose));
+      mp_it.begin_args.chain_expect = chain_expect; mp_it.begin_args.pad = 0;
+      mp_it.begin_ctr = begin_slot->pb_ctr.as<unsigned long long>(); mp_it.begin_state = c->d_state;
+    }
+    launch_knn_plane(w.d_binned, w.d_chunks, c->d_state, c->view, mp_it, w.corr, c->d_nbr5.as<uint32_t>(), c->d_hist, c->stream, ev_start, ev_stop);
+  }
+}
+// setupOptimizationProblem + solveOptimizationProblem (LidarSlam.cpp:213-240) of one outer iteration: the whole solve in one launch
+// (workgroups hand the next pose to each other on the device).  (The span is one of profiling mode, time_kernels 2.)
+void launch_persistent_solve(so_icp_ctx* c, const RegWork& w, EvalParams& ep_it, const MatchParams& mp) {
+  ep_it.epoch_base = (++c->solve_launches) << 5;
+  span_begin(c, 1, (uint32_t)w.n);
+  launch_solve(w.lm_max, w.d_scan, w.d_scan + 1, w.d_scan + 2, w.corr, c->d_state, ep_it, c->d_partials, c->d_ticket, c->d_hist, c->d_sums, c->view,
+               c->d_nbr5.as<uint32_t>(), mp, (uint32_t)w.n, (uint32_t)c->n_cus, c->stream);
+  span_end(c);
+}
+Report await_report(so_icp_ctx* c, const volatile unsigned long long* seq, unsigned long long want, hipStream_t s) {
+  constexpr int kReportWatchdogMs = 5;  // (a registration lasts 0.15 ms; the waits inside a solve launch give up after 50 ms)
+  auto next_check = std::chrono::steady_clock::now() + std::chrono::milliseconds(kReportWatchdogMs);
+  for (unsigned spin = 1;; ++spin) {
+    if (*seq == want) break;
+    if ((spin & 0x3FFu) != 0) continue;
+    const auto now = std::chrono::steady_clock::now();
+    if (now < next_check) continue;
+    next_check = now + std::chrono::milliseconds(1);
+    // watchdog: everything enqueued so far -- the launch that reports this iteration included -- has completed
+    if (hipStreamQuery(s) != hipErrorNotReady) {
+      (void)hipGetLastError();  // (hipErrorNotReady of the earlier polls, or the error the synchronize below reports)
+      // the iteration's launches have all completed: either it was a no-op (converged earlier: cannot happen for the
+      // iteration the host waits on) or a kernel failed -- report instead of spinning forever
+      if (*seq == want) break;
+      const hipError_t e = hipStreamSynchronize(s);
+      if (e != hipSuccess) { c->err = std::string("hipStreamSynchronize(s): ") + hipGetErrorString(e); return Report::kHipError; }
+      if (*seq == want) break;
+      return Report::kDrained;
+    }
+  }
+  std::atomic_thread_fence(std::memory_order_acquire);
+  return Report::kReported;
+}
+void note_registration_done(so_icp_ctx* c, DevState* mirror, const MatchParams& mp, size_t n, bool sets_list_fits, bool sets_done_count) {
+  const DevState& H = *(c->h_state = mirror);
+  // the k-NN packing policy (so_icp_ctx::knn_pack_hold)
   if (mp.pack_light) c->timing.knn_pack_registrations++;
   // (the device's count runs on from registration to registration -- nothing on the device clears it beside the sweeps that add to it)
   const uint32_t packed_left = H.packed_leftover >= c->packed_leftover_seen ? H.packed_leftover - c->packed_leftover_seen : H.packed_leftover;
   c->packed_leftover_seen = H.packed_leftover;
   if (mp.pack_light && (double)packed_left > 0.03 * (double)n * (double)std::max(H.n_iterations, 1)) { c->knn_pack_hold = 32; c->timing.knn_pack_holds++; }
+  // (scans of a stream have one size: the list of this registration decides the packing of the next -- results do not depend on it;
+  //  so_icp_register_sequence leaves it as it is after a registration swept by query waves, which builds no list)
+  if (sets_list_fits) c->knn_list_fits = work_list_fits(H.bin_packed, (unsigned long long)kKnnBlocks * 4ull);
+  // (registrations completed on the context's own state block, so_icp_register_sequence's chain condition: a batch lane or a
+  //  borrowed map leaves the count alone)
+  if (sets_done_count) c->done_count_seen = H.done_count;
 }
 
 // LidarSLAM::EstimateLidarUncertainty, LidarSlam.cpp:915-964
-void uncertainty_from_hist(const int32_t* H, double u[6]) {
+static void uncertainty_from_hist(const int32_t* H, double u[6]) {
   const double tt = (double)H[6] + H[7] + H[8];
   const double tr = (double)H[0] + H[1] + H[2] + H[3] + H[4] + H[5];
   if (tt == 0 || tr == 0) { for (int i = 0; i < 6; ++i) u[i] = 0; return; }
@@ -244,6 +295,258 @@ void fill_result(so_icp_ctx* c, const DevState& H, const double pose_in[7], so_i
   std::memcpy(pose_out, T, sizeof(T));
 }
 
+void fill_stats_header(const so_icp_ctx* c, so_icp_stats* st, const int pos[3], int count_5x5, size_t n) {
+  if (c->have_hist) uncertainty_from_hist(c->prev_obs_hist, st->uncertainty);  // LidarSlam.cpp:47
+  st->pos_in_localmap[0] = pos[0]; st->pos_in_localmap[1] = pos[1]; st->pos_in_localmap[2] = pos[2];
+  st->laser_cloud_surf_from_map_num = count_5x5; st->laser_cloud_surf_stack_num = (int32_t)n; st->startup_count = c->startup_count;  // LidarSlam.cpp:367
+}
+
+namespace {
+
+// One so_icp_register(_dev) registration: every mode of its schedule, resolved once and explained where it is (plan_registration),
+// its buffers (claim_buffers) and the parameters of its launches (begin_registration)
+struct RegPlan : RegWork {
+  const double* pose_in = nullptr;
+  size_t n_total = 0;  // the whole scan; n: what this context registers of it (its share under a query split)
+  QueryShare share{0, false, 0};
+  bool solo = false, qsplit = false, may_prebin = false, begin_in_knn = false, rebin = false, direct_rb = false, timed = false, peer = false,
+       exchange = false, persistent = false, defer_reports = false;
+  so_icp_ctx::StageSlot* pb = nullptr;  // the scan was binned ahead: its work list is in this slot
+  uint32_t flags = 0, chunk_cap = 0;    // (flags: what of the modes goes into so_icp_stats::flags)
+  BinTable bt{nullptr, nullptr, nullptr, 0};
+  MatchParams mp; EvalParams ep;
+  unsigned long long seq_base = 0;
+  std::vector<size_t> knn_span_of_outer, eval_span_first;  // so_icp_ctx::spans index of every outer iteration's sweep / first evaluation span
+};
+
+void plan_registration(const so_icp_ctx* c, RegPlan& p, const float* d_scan, size_t n, const double pose_in[7]) {
+  p.d_scan = d_scan; p.n = p.n_total = n; p.pose_in = pose_in;
+  p.max_outer = outer_limit(c->cfg.max_iterations);
+  p.lm_max = lm_limit(c->cfg.lm_max_iterations);
+  const bool own = !c->batch_mode && !c->borrow.on;  // this context's own registration, on its own map
+  const bool one_device = c->cfg.world_size <= 1;
+  const bool controller = !(c->ablate & 32);         // (ablated controller: per-evaluation launches, read-back by copy)
+  // SO_ICP_SHARD_QUERIES: this rank registers ITS share of the scan -- the 64-point segments rank, rank + world, ... (a 128-ring
+  // sweep in ring-major order gives every rank two 22.5-degree sectors of every ring: spatially compact, so its k-NN chunks are
+  // as full as the whole scan's) -- gathered into one array by a strided device copy; from here on the registration is a
+  // single-device one over n_own points, except that the sums of every evaluation are exchanged with the other ranks.
+  p.qsplit = c->query_split && own;
+  if (p.qsplit) { p.share = query_split_share(n, (size_t)c->cfg.world_size, (size_t)c->cfg.rank); p.n = p.share.n_own; }
+  p.solo = own && !p.qsplit;
+  // A SMALL scan is not binned at all (query_wave_count_ok, reg_plan.h), the prologue rides on the first sweep.  Single device,
+  // single registration; the instrumented build keeps the chunked sweep (its stamps describe that kernel).
+  p.query_waves = c->query_waves && query_wave_count_ok(c->cfg.max_surface_features, p.n, kQueryWaveMaxKept) && one_device && p.solo && c->ablate == 0;
+  // a scan that was binned ahead of this call (so_icp_stage_scan, so_icp_ctx::prebin): its work list is in the slot
+  p.may_prebin = c->prebin && c->dmap && one_device && p.solo;
+  p.pb = (!p.query_waves && p.may_prebin && p.n && c->scan_staged && c->stage_in_use && c->stage_in_use->prebinned && c->stage_in_use->n == p.n &&
+          c->stage_in_use->dev.as<float>() == d_scan) ? c->stage_in_use : nullptr;
+  // (the prologue rides on the first k-NN launch -- MatchParams::begin -- unless that is the instrumented instantiation, whose
+  //  statistics share the histogram block the prologue clears)
+  p.begin_in_knn = p.pb && c->ablate == 0;
+  // sharded map: ownership follows the query's cell under the CURRENT pose, so the scan is re-binned at the start of
+  // every outer iteration (a 1 degree correction at 50 m moves a point by more than the one-cell halo of a shard)
+  p.rebin = !one_device && p.n && !p.qsplit;
+  p.direct_rb = c->direct_readback && controller;
+  // time_kernels == 1 samples every 3rd registration (a period coprime to the scan rotation of typical benchmarks, so
+  // that every scan of the rotation gets timed): even dispatch-attached events cost ~5 us of stream time per
+  // timed launch (completion-signal handling), which would otherwise sit inside every step of a throughput run
+  p.timed = !c->batch_mode && (c->cfg.time_kernels >= 2 || (c->cfg.time_kernels == 1 && (c->timing.registrations % 3) == 0));
+  // (concurrent hypotheses: two persistent launches could each hold part of the CUs and wait for the rest -- one launch per
+  //  evaluation there; only workgroup 0 of a launch ever waits, for workgroups that finish unconditionally)
+  p.peer = c->peer_on && !one_device && c->persistent_solve && !c->batch_mode && controller;
+  p.exchange = !p.peer && (c->comm != nullptr || c->group != nullptr);
+  p.persistent = c->persistent_solve && !p.exchange && (!c->batch_mode || c->batch_single) && controller;
+  // deferred report: possible when the host always has the next k-NN launch in the queue before it waits for a report
+  p.defer_reports = p.persistent && p.direct_rb && c->speculate;
+  p.flags = (p.query_waves ? SO_ICP_FLAG_QUERY_WAVES : 0u) | (p.pb ? SO_ICP_FLAG_BINNED_AHEAD : 0u) | (p.persistent ? 0u : SO_ICP_FLAG_PER_EVAL_LAUNCHES);
+}
+
+// this rank's share of a split scan gathered into d_sub, the scan buffers, and where the sweeps find their work
+int claim_buffers(so_icp_ctx* c, RegPlan& p) {
+  if (p.qsplit) {
+    const size_t W = (size_t)c->cfg.world_size, r = (size_t)c->cfg.rank, own_full = p.share.own_full, s_full = p.n_total / 64, tail = p.n_total % 64;
+    HIP_TRY(c, c->d_sub.reserve((p.n + 64) * 12));
+    if (own_full) HIP_TRY(c, hipMemcpy2DAsync(c->d_sub.p, 768, p.d_scan + r * 192, W * 768, 768, own_full, hipMemcpyDeviceToDevice, c->stream));
+    if (p.share.own_tail) HIP_TRY(c, hipMemcpyAsync(c->d_sub.as<float>() + own_full * 192, p.d_scan + s_full * 192, tail * 12, hipMemcpyDeviceToDevice, c->stream));
+    p.d_scan = c->d_sub.as<float>();
+  }
+  const int rc = reserve_scan_buffers(c, p.n);
+  if (rc) return rc;
+  p.d_binned = p.pb ? p.pb->pb_binned.as<float4>() : c->d_binned.as<float4>();
+  p.d_chunks = p.pb ? p.pb->pb_chunks.as<uint32_t>() : c->d_chunks.as<uint32_t>();
+  p.chunk_cap = p.pb ? p.pb->pb_chunk_cap : (uint32_t)(c->d_chunks.cap / 4);
+  p.corr = CorrBuffers{c->d_nd.as<double4>(), c->d_coeff.as<double>(), c->d_status.as<uint8_t>()};
+  return SO_ICP_OK;
+}
+
+// hash binning: keys + per-key counts (scan_keys), bucket offsets + chunk list (bin_offsets), placement (bin_place).
+// The table has >= 2 slots per query; bin_offsets leaves it empty again.  `rebin`: under the CURRENT device-resident pose, no prologue
+void launch_hash_binning(so_icp_ctx* c, const RegPlan& p, bool rebin) {
+  DevState* ds = c->d_state; hipStream_t s = c->stream;
+  launch_scan_keys(p.d_scan, (uint32_t)p.n, ds, p.pose_in, p.max_outer, p.lm_max, c->d_hist, c->view, c->cfg.max_surface_features, c->cfg.rank,
+                   c->cfg.world_size, c->d_keys0.as<uint32_t>(), c->d_vals0.as<uint32_t>(), c->d_status.as<uint8_t>(), p.bt, s, rebin, nullptr, 0,
+                   p.qsplit, rebin ? 0u : (uint32_t)p.n_total);
+  launch_bin_offsets(p.bt, c->d_chunks.as<uint32_t>(), (uint32_t)(c->d_chunks.cap / 4), ds, s);
+  launch_bin_place(p.bt, p.d_scan, (uint32_t)p.n, c->d_keys0.as<uint32_t>(), c->d_vals0.as<uint32_t>(), c->d_binned.as<float4>(), s, rebin ? ds : nullptr);
+}
+// ---- once per registration: prologue (the guess and the loop bounds travel as kernel arguments, no H2D copy),
+//      sampling rule, spatial sort (locality survives the small pose updates), chunk list + gather
+int begin_registration(so_icp_ctx* c, RegPlan& p) {
+  DevState* ds = c->d_state; hipStream_t s = c->stream; const uint32_t n = (uint32_t)p.n;
+  span_begin(c, 2, n);
+  if (p.query_waves || p.begin_in_knn) {  // (the first sweep starts the registration)
+  } else if (p.pb) {
+    launch_reg_begin_prebinned(ds, p.pose_in, p.max_outer, p.lm_max, c->d_hist, p.pb->pb_ctr.as<unsigned long long>(), c->d_status.as<uint8_t>(), n,
+                               c->cfg.max_surface_features, s);
+  } else if (n) {
+    const uint32_t lg = bin_table_log2(p.n);
+    HIP_TRY(c, c->bin.ensure(lg, s));
+    p.bt = c->bin.view();
+    c->bin.log2 = 0;  // dirty until bin_offsets has been enqueued behind scan_keys
+    launch_hash_binning(c, p, false);
+    c->bin.log2 = lg;
+  } else {
+    launch_scan_keys(p.d_scan, 0, ds, p.pose_in, p.max_outer, p.lm_max, c->d_hist, c->view, c->cfg.max_surface_features, c->cfg.rank,
+                     c->cfg.world_size, nullptr, nullptr, nullptr, p.bt, s);  // (empty scan: the prologue alone)
+  }
+  span_end(c);
+  HIP_TRY(c, hipGetLastError());  // a refused launch would otherwise surface as a 50 ms wait or "state was not published"
+  // the parameters of the sweeps and solves (host work: it follows the first launches into the queue)
+  p.seq_base = registration_params(c, c->borrow.on ? c->borrow.plane_res : map_plane_res(c), p.n, p.chunk_cap, 0, p.mp, p.ep);
+  if (p.mp.ablate & 128) {  // profiling: per-workgroup phase stamps of the k-NN sweeps
+    HIP_TRY(c, c->d_kdbg.reserve((size_t)2 * kKnnBlocks * 4 * 16 * sizeof(unsigned long long)));
+    HIP_TRY(c, hipMemsetAsync(c->d_kdbg.p, 0, (size_t)2 * kKnnBlocks * 4 * 16 * sizeof(unsigned long long), c->stream));
+    p.mp.kdbg = c->d_kdbg.as<unsigned long long>();
+  }
+  if (p.peer) {
+    for (int r = 0; r < 8; ++r) p.ep.peer_inbox[r] = c->peer_inbox[r];
+    p.ep.peer_rank = c->cfg.rank; p.ep.peer_world = c->cfg.world_size; p.ep.timeout_ticks = c->peer_timeout_ticks;
+  }
+  p.mp.publish_prev = p.defer_reports ? 1 : 0;
+  return SO_ICP_OK;
+}
+
+// one evaluation of the per-evaluation schedule: eval(slot) -> (all-reduce -> lm_step)
+int enqueue_eval(so_icp_ctx* c, RegPlan& p, int slot) {
+  DevState* ds = c->d_state; hipStream_t s = c->stream;
+  span_begin(c, 1, (uint32_t)p.n);
+  const bool fuse_lm = !p.exchange;  // single device: the last workgroup of eval runs the LM controller itself
+  launch_eval(slot, fuse_lm, p.d_scan, p.d_scan + 1, p.d_scan + 2, p.corr, ds, p.ep, c->d_partials,
+              c->d_ticket, c->d_hist, c->d_sums, c->view, c->d_nbr5.as<uint32_t>(), p.mp, (uint32_t)p.n, s);
+  span_end(c);
+  if (!fuse_lm && c->group) {  // in-process group: through host memory (every member calls this the same number of times)
+    HIP_TRY(c, hipMemcpyAsync(c->h_sums, c->d_sums, sizeof(LmSums), hipMemcpyDeviceToHost, s));
+    HIP_TRY(c, hipStreamSynchronize(s));
+    if (!group_allreduce(c, c->h_sums))
+      return fail(c, SO_ICP_E_RCCL, "in-process group: the exchange of the normal-equation sums failed (a member returned early or did not arrive)");
+    HIP_TRY(c, hipMemcpyAsync(c->d_sums, c->h_sums, sizeof(LmSums), hipMemcpyHostToDevice, s));
+    launch_lm_step(slot, ds, c->d_sums, c->d_hist, p.ep, s);
+  } else if (!fuse_lm) {  // per-evaluation collective: 45 fp64 summed over the shards (xGMI, latency-bound), then the controller
+    const ncclResult_t nrc = c->rccl.AllReduce(c->d_sums, c->d_sums, sizeof(LmSums) / sizeof(double), ncclDouble, ncclSum, c->comm, s);
+    if (nrc != ncclSuccess) return fail(c, SO_ICP_E_RCCL, std::string("ncclAllReduce: ") + (c->rccl.GetErrorString ? c->rccl.GetErrorString(nrc) : "?"));
+    launch_lm_step(slot, ds, c->d_sums, c->d_hist, p.ep, s);
+  }
+  return SO_ICP_OK;
+}
+
+// One outer iteration = knn_plane -> [ eval(slot) -> (all-reduce -> lm_step) ] x (1 + lm_max) -> state read-back.
+// (The histogram replicas are cleared by reg_begin and again by the controller when a solve ends:
+//  ResetDistanceParameters, LidarSlam.cpp:847-852.)
+// part A: correspondences + plane fit + first evaluation; part B: the remaining evaluations + read-back
+int enqueue_outer_a(so_icp_ctx* c, RegPlan& p, int it) {
+  if (it > 0 && p.rebin) launch_hash_binning(c, p, true);
+  p.knn_span_of_outer.push_back(c->spans.size());
+  hipEvent_t ka = nullptr, kb = nullptr;
+  if (p.timed) {  // the events ride on the dispatch packet (hipExtLaunchKernelGGL), no marker packets
+    ka = next_event(c); kb = next_event(c);
+    if (ka && kb) c->spans.push_back(EventSpan{0, ka, kb, (uint32_t)p.n});
+  }
+  MatchParams mp_it = p.mp;
+  launch_sweep(c, p, mp_it, it == 0, (it == 0 && p.begin_in_knn) ? p.pb : nullptr, p.pose_in, 0, ka, kb);
+  if (c->cfg.time_kernels >= 2)  // kernel statistics of this sweep (profiling mode only)
+    HIP_TRY(c, hipMemcpyAsync(c->h_hist + (size_t)it * kHistReplicas * kHistStride, c->d_hist,
+                              kHistReplicas * kHistStride * sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
+  // setupOptimizationProblem + solveOptimizationProblem (LidarSlam.cpp:213-240): 1 + lm_max fused evaluations
+  p.eval_span_first.push_back(c->spans.size());
+  HIP_TRY(c, hipGetLastError());
+  if (p.persistent) return SO_ICP_OK;  // the solve launch belongs to part B: only the k-NN sweep is speculated
+  return enqueue_eval(c, p, 0);
+}
+int enqueue_outer_b(so_icp_ctx* c, RegPlan& p, int it) {
+  hipStream_t s = c->stream;
+  if (p.persistent) {
+    EvalParams ep_it = p.ep;
+    // (deferred: the k-NN launch of it + 1 will be enqueued before the host waits)
+    ep_it.defer_publish = (p.defer_reports && it + 1 < p.max_outer) ? 1 : 0;
+    launch_persistent_solve(c, p, ep_it, p.mp);
+  } else {
+    for (int slot = 1; slot <= p.lm_max; ++slot) { const int r = enqueue_eval(c, p, slot); if (r) return r; }
+  }
+  // the whole state block (pose, per-iteration statistics, final normal equations) into this iteration's pinned mirror
+  if (!p.direct_rb) HIP_TRY(c, hipMemcpyAsync(c->h_ring[it & 1], c->d_state, sizeof(DevState), hipMemcpyDeviceToHost, s));
+  // (a deferred report is complete only after the NEXT k-NN launch: the event is recorded behind that one, see the loop)
+  // (the pinned mirrors are polled; the event is the watchdog of that wait only where the stream itself cannot serve as one)
+  if (!p.direct_rb) HIP_TRY(c, hipEventRecord(c->ev_outer[it & 1], s));
+  HIP_TRY(c, hipGetLastError());
+  return SO_ICP_OK;
+}
+// wait until outer iteration `it` has been reported
+int await_outer(so_icp_ctx* c, const RegPlan& p, int it) {
+  if (!p.direct_rb) { HIP_TRY(c, hipEventSynchronize(c->ev_outer[it & 1])); return SO_ICP_OK; }
+  const Report rep = await_report(c, &c->h_ring[it & 1]->seq, p.seq_base | (unsigned long long)(it + 1), c->stream);
+  if (rep != Report::kDrained) return rep == Report::kReported ? SO_ICP_OK : SO_ICP_E_HIP;
+  if (p.persistent && p.peer) {
+    // The ranks' pass counters (DevState::peer_seq) and inboxes can no longer be assumed equal: chunks of the failed attempt
+    // still carry tags the next registration would reuse.  The peer path is left until the caller repeats the collective
+    // handshake (so_icp_peer_export clears the inbox and the counter, _connect, _enable).
+    c->peer_on = false; c->peer_connected = false;
+    return fail(c, SO_ICP_E_HIP, "peer exchange: a solve launch was abandoned (a rank's records did not arrive within SOICP_PEER_TIMEOUT_MS, or the "
+                                 "workgroups were not co-resident); the peer exchange is now disabled on this rank until so_icp_peer_export / "
+                                 "_connect / _enable are repeated on every rank");
+  }
+  if (p.persistent) {
+    // The persistent solve launch needs all of its workgroups resident at once.  If the device could not provide that
+    // (compute units held by another process, a partitioned device, ...) its waits gave up after 50 ms: fall back to
+    // one launch per evaluation for the rest of this context's life and run the registration again.
+    c->persistent_solve = false;
+    c->err = "persistent solve launch did not complete (workgroups not co-resident?): using per-evaluation launches from now on";
+    return kRetryWithoutPersistentSolve;
+  }
+  return fail(c, SO_ICP_E_HIP, "registration state was not published by the device");
+}
+// the timing events of a timed registration: keep only the launches that did real work (no-op launches after convergence are excluded)
+int collect_timing(so_icp_ctx* c, const RegPlan& p, const DevState& H) {
+  std::vector<EventSpan> real;
+  for (size_t i = 0; i < c->spans.size(); ++i) {
+    const EventSpan& sp = c->spans[i];
+    bool keep = (sp.kind == 2);
+    for (int it = 0; it < H.n_iterations && !keep; ++it) {
+      if (sp.kind == 0 && it < (int)p.knn_span_of_outer.size() && i == p.knn_span_of_outer[it]) keep = true;
+      // (a persistent solve launch is ONE span per outer iteration, the per-evaluation schedule 1 + #LM iterations)
+      if (sp.kind == 1 && it < (int)p.eval_span_first.size() && i >= p.eval_span_first[it] &&
+          i < p.eval_span_first[it] + (p.persistent ? 1 : 1 + (size_t)std::max(H.iters[it].lm_iterations, 0))) keep = true;
+    }
+    if (keep) { EventSpan r = sp; r.units = work_list_kept(H.bin_packed); real.push_back(r); }
+  }
+  c->spans.swap(real);
+  // profiling mode brackets the solve launches too: the last one has published its result but its stop event may not
+  // have signalled yet (hipEventElapsedTime would refuse it) -- wait for the stream there; the k-NN events of mode 1
+  // completed long ago
+  if (c->cfg.time_kernels >= 2) HIP_TRY(c, hipStreamSynchronize(c->stream));
+  spans_collect(c);
+  for (int it = 0; it < H.n_iterations && c->cfg.time_kernels >= 2; ++it)
+    for (int r = 0; r < kHistReplicas; ++r) {
+      const int32_t* hh = c->h_hist + ((size_t)it * kHistReplicas + r) * kHistStride;
+      c->timing.knn_group_passes += hh[16]; c->timing.knn_fallback_lanes += hh[17];
+      c->timing.knn_packed_rows += hh[20]; c->timing.knn_packed_rows_too_many_runs += hh[21]; c->timing.knn_packed_rows_tile_full += hh[22];
+      c->timing.knn_packed_kept += hh[23];
+      c->timing.knn_candidates_scanned += (int64_t)hh[18] * 16;
+    }
+  return SO_ICP_OK;
+}
+
+}  // namespace
+
 // LidarSLAM::performLocalizationAndMapping (LidarSlam.cpp:107-152) with the loop state resident on the device:
 // the host enqueues, per outer iteration, the STATIC sequence
 //     clear histograms -> knn_plane -> [ eval(slot) -> (all-reduce) -> lm_step(slot) ] x (1 + lm_max)
@@ -255,250 +558,27 @@ static int register_core_once(so_icp_ctx* c, const float* d_scan, size_t n, cons
   so_icp_stats local;
   if (!st) st = &local;
   std::memset(st, 0, sizeof(*st));
-  // (kernels.hip: bin_offsets_kernel / knn_plane_kernel)
-  if (n >= ((size_t)1 << 21)) return fail(c, SO_ICP_E_UNSUPPORTED, "scan of 2^21 points or more: the work-list counters hold 21 bits each (chunk descriptors 26)");
+  if (n >= kMaxScanPoints) return refuse_scan_size(c);
   st->flags = (c->retried ? SO_ICP_FLAG_RETRIED : 0u) | (!c->dmap && !c->borrow.on ? SO_ICP_FLAG_HOST_MAP : 0u) |
               (c->cfg.world_size > 1 ? SO_ICP_FLAG_SHARDED : 0u) | (c->query_split ? SO_ICP_FLAG_QUERY_SPLIT : 0u) |
               (c->scan_staged ? SO_ICP_FLAG_STAGED_SCAN : 0u) | (c->direct_readback ? 0u : SO_ICP_FLAG_COPY_READBACK);
-  double T[7];
-  std::memcpy(T, pose_in, sizeof(T));  // LidarSlam.cpp:53-57 (T_w_initial_guess = last_T_w_lidar = T_w_lidar = the guess)
-  std::memcpy(pose_out, pose_in, sizeof(T));
-  if (c->have_hist) uncertainty_from_hist(c->prev_obs_hist, st->uncertainty);  // LidarSlam.cpp:47
+  std::memcpy(pose_out, pose_in, 7 * sizeof(double));  // LidarSlam.cpp:53-57 (T_w_initial_guess = last_T_w_lidar = T_w_lidar = the guess)
   int pos[3];
   if (c->borrow.on) std::memcpy(pos, c->borrow.pos, sizeof(pos));  // window, count and map view were fixed by the batch driver
-  else if (!c->no_map_shift && !c->no_map_shift_once) { map_shift(c, T, pos); std::memcpy(c->last_pos, pos, sizeof(pos)); }  // LidarSlam.cpp:363
+  else if (!c->no_map_shift && !c->no_map_shift_once) { map_shift(c, pose_in, pos); std::memcpy(c->last_pos, pos, sizeof(pos)); }  // LidarSlam.cpp:363
   else std::memcpy(pos, c->last_pos, sizeof(pos));
   c->no_map_shift_once = false;
-  st->pos_in_localmap[0] = pos[0]; st->pos_in_localmap[1] = pos[1]; st->pos_in_localmap[2] = pos[2];
-  st->laser_cloud_surf_from_map_num = c->borrow.on ? c->borrow.count_5x5 : map_count_5x5(c, pos);  // LidarSlam.cpp:367
-  st->laser_cloud_surf_stack_num = (int32_t)n;
-  st->startup_count = c->startup_count;
+  fill_stats_header(c, st, pos, c->borrow.on ? c->borrow.count_5x5 : map_count_5x5(c, pos), n);
   if (!(st->laser_cloud_surf_from_map_num > 50)) return SO_ICP_NOT_ENOUGH_MAP_FEATURES;  // LidarSlam.cpp:113-116
   int rc = SO_ICP_OK;
   if (c->borrow.on) c->view = c->borrow.view; else rc = upload_map(c);
   if (rc) return rc;
-  // SO_ICP_SHARD_QUERIES: this rank registers ITS share of the scan -- the 64-point segments rank, rank + world, ... (a 128-ring
-  // sweep in ring-major order gives every rank two 22.5-degree sectors of every ring: spatially compact, so its k-NN chunks are
-  // as full as the whole scan's) -- gathered into one array by a strided device copy; from here on the registration is a
-  // single-device one over n_own points, except that the sums of every evaluation are exchanged with the other ranks.
-  const bool qsplit = c->query_split && !c->batch_mode && !c->borrow.on;
-  const size_t n_total = n;
-  if (qsplit) {
-    const size_t W = (size_t)c->cfg.world_size, r = (size_t)c->cfg.rank, s_full = n / 64, tail = n % 64;
-    const size_t own_full = s_full > r ? (s_full - r + W - 1) / W : 0;
-    const bool own_tail = tail != 0 && (s_full % W) == r;  // (the partial last segment is segment number s_full)
-    const size_t n_own = own_full * 64 + (own_tail ? tail : 0);
-    HIP_TRY(c, c->d_sub.reserve((n_own + 64) * 12));
-    if (own_full) HIP_TRY(c, hipMemcpy2DAsync(c->d_sub.p, 768, d_scan + r * 192, W * 768, 768, own_full, hipMemcpyDeviceToDevice, c->stream));
-    if (own_tail) HIP_TRY(c, hipMemcpyAsync(c->d_sub.as<float>() + own_full * 192, d_scan + s_full * 192, tail * 12, hipMemcpyDeviceToDevice, c->stream));
-    d_scan = c->d_sub.as<float>();
-    n = n_own;
-  }
-  rc = reserve_scan_buffers(c, n);
-  if (rc) return rc;
+  RegPlan p;
+  plan_registration(c, p, d_scan, n, pose_in);
+  if ((rc = claim_buffers(c, p))) return rc;
   const auto t_icp = std::chrono::steady_clock::now();  // TicToc t_opt, LidarSlam.cpp:118
-
-  const int max_outer = std::min(c->cfg.max_iterations > 0 ? c->cfg.max_iterations : 4, SO_ICP_MAX_OUTER);
-  const int lm_max = std::min(c->cfg.lm_max_iterations > 0 ? c->cfg.lm_max_iterations : 4, 16);
-  DevState* ds = c->d_state;
-  hipStream_t s = c->stream;
-  // ---- once per registration: prologue (the guess and the loop bounds travel as kernel arguments, no H2D copy),
-  //      sampling rule, spatial sort (locality survives the small pose updates), chunk list + gather
-  span_begin(c, 2, (uint32_t)n);
-  BinTable bt{nullptr, nullptr, nullptr, 0};
-  // a scan that was binned ahead of this call (so_icp_stage_scan, so_icp_ctx::prebin): its work list is in the slot
-  const bool may_prebin = c->prebin && c->dmap && c->cfg.world_size <= 1 && !c->batch_mode && !c->borrow.on && !qsplit;
-  so_icp_ctx::StageSlot* pb = (may_prebin && n && c->scan_staged && c->stage_in_use && c->stage_in_use->prebinned && c->stage_in_use->n == n &&
-                               c->stage_in_use->dev.as<float>() == d_scan) ? c->stage_in_use : nullptr;
-  const float4* d_binned = c->d_binned.as<float4>();
-  const uint32_t* d_chunks = c->d_chunks.as<uint32_t>();
-  uint32_t chunk_cap = (uint32_t)(c->d_chunks.cap / 4);
-  // (the prologue rides on the first k-NN launch -- MatchParams::begin -- unless that is the instrumented instantiation, whose
-  //  statistics share the histogram block the prologue clears)
-  const bool begin_in_knn = pb && c->ablate == 0;
-  // A SMALL scan -- the stock operating point of the node: max_surface_features 2000 / 4000 of a pre-filtered cloud -- is not binned at all:
-  // every kept query gets a wavefront of its own (knn_query_wave_kernel), the prologue rides on the first sweep.  Single device,
-  // single registration; the instrumented build keeps the chunked sweep (its stamps describe that kernel).
-  const int max_sf_cfg = c->cfg.max_surface_features;
-  const size_t kept_upper = (max_sf_cfg >= 0 && n > (size_t)max_sf_cfg) ? (size_t)max_sf_cfg + 2 : n;  // (the rule keeps ~ rate * n points)
-  const bool query_waves = c->query_waves && n && kept_upper <= kQueryWaveMaxKept && c->cfg.world_size <= 1 && !c->batch_mode && !c->borrow.on &&
-                           !qsplit && c->ablate == 0;
-  if (query_waves) {
-    st->flags |= SO_ICP_FLAG_QUERY_WAVES;
-  } else if (pb) {
-    if (!begin_in_knn)
-      launch_reg_begin_prebinned(ds, pose_in, max_outer, lm_max, c->d_hist, pb->pb_ctr.as<unsigned long long>(), c->d_status.as<uint8_t>(), (uint32_t)n,
-                                 c->cfg.max_surface_features, s);
-    d_binned = pb->pb_binned.as<float4>(); d_chunks = pb->pb_chunks.as<uint32_t>(); chunk_cap = pb->pb_chunk_cap;
-    st->flags |= SO_ICP_FLAG_BINNED_AHEAD;
-  } else if (n) {
-    // hash binning: keys + per-key counts (scan_keys), bucket offsets + chunk list (bin_offsets), placement (bin_place).
-    // The table has >= 2 slots per query; bin_offsets leaves it empty again.
-    const uint32_t lg = bin_table_log2(n);
-    HIP_TRY(c, c->bin.ensure(lg, s));
-    bt = c->bin.view();
-    c->bin.log2 = 0;  // dirty until bin_offsets has been enqueued behind scan_keys
-    launch_scan_keys(d_scan, (uint32_t)n, ds, pose_in, max_outer, lm_max, c->d_hist, c->view, c->cfg.max_surface_features, c->cfg.rank,
-                     c->cfg.world_size, c->d_keys0.as<uint32_t>(), c->d_vals0.as<uint32_t>(), c->d_status.as<uint8_t>(), bt, s, false, nullptr, 0,
-                     qsplit, (uint32_t)n_total);
-    launch_bin_offsets(bt, c->d_chunks.as<uint32_t>(), (uint32_t)(c->d_chunks.cap / 4), ds, s);
-    c->bin.log2 = lg;
-    launch_bin_place(bt, d_scan, (uint32_t)n, c->d_keys0.as<uint32_t>(), c->d_vals0.as<uint32_t>(), c->d_binned.as<float4>(), s);
-  } else {
-    launch_scan_keys(d_scan, 0, ds, pose_in, max_outer, lm_max, c->d_hist, c->view, c->cfg.max_surface_features, c->cfg.rank,
-                     c->cfg.world_size, nullptr, nullptr, nullptr, bt, s);  // (empty scan: the prologue alone)
-  }
-  span_end(c);
-  HIP_TRY(c, hipGetLastError());  // a refused launch would otherwise surface as a 50 ms wait or "state was not published"
-  const float plane_res_now = c->borrow.on ? c->borrow.plane_res : map_plane_res(c);
-  MatchParams mp;
-  EvalParams ep;
-  const unsigned long long seq_base = registration_params(c, plane_res_now, n, chunk_cap, 0, mp, ep);
-  const bool direct_rb = c->direct_readback && !(ep.ablate & 32);  // (the state block is published into the pinned mirrors, polled below)
-  if (mp.ablate & 128) {  // profiling: per-workgroup phase stamps of the k-NN sweeps
-    HIP_TRY(c, c->d_kdbg.reserve((size_t)2 * kKnnBlocks * 4 * 16 * sizeof(unsigned long long)));
-    HIP_TRY(c, hipMemsetAsync(c->d_kdbg.p, 0, (size_t)2 * kKnnBlocks * 4 * 16 * sizeof(unsigned long long), s));
-    mp.kdbg = c->d_kdbg.as<unsigned long long>();
-  }
-  CorrBuffers corr{c->d_nd.as<double4>(), c->d_coeff.as<double>(), c->d_status.as<uint8_t>()};
-  std::vector<size_t> knn_span_of_outer, eval_span_first;
-  // One outer iteration = knn_plane -> [ eval(slot) -> (all-reduce -> lm_step) ] x (1 + lm_max) -> state read-back.
-  // (The histogram replicas are cleared by reg_begin and again by the controller when a solve ends:
-  //  ResetDistanceParameters, LidarSlam.cpp:847-852.)
-  // time_kernels == 1 samples every 3rd registration (a period coprime to the scan rotation of typical benchmarks, so
-  // that every scan of the rotation gets timed): even dispatch-attached events cost ~5 us of stream time per
-  // timed launch (completion-signal handling), which would otherwise sit inside every step of a throughput run
-  const bool timed = !c->batch_mode && (c->cfg.time_kernels >= 2 || (c->cfg.time_kernels == 1 && (c->timing.registrations % 3) == 0));
-  // part A: correspondences + plane fit + first evaluation; part B: the remaining evaluations + read-back
-  // (concurrent hypotheses: two persistent launches could each hold part of the CUs and wait for the rest -- one launch per
-  //  evaluation there; only workgroup 0 of a launch ever waits, for workgroups that finish unconditionally)
-  const bool peer = c->peer_on && c->cfg.world_size > 1 && c->persistent_solve && !c->batch_mode && !(ep.ablate & 32);
-  if (peer) { for (int r = 0; r < 8; ++r) ep.peer_inbox[r] = c->peer_inbox[r]; ep.peer_rank = c->cfg.rank; ep.peer_world = c->cfg.world_size; ep.timeout_ticks = c->peer_timeout_ticks; }
-  // (peer exchange: the ranks' persistent solve launches trade their records themselves, see EvalParams::peer_inbox)
-  const bool exchange = !peer && (c->comm != nullptr || c->group != nullptr);  // the sums pass through a collective between evaluation and controller
-  const bool persistent = c->persistent_solve && !exchange && (!c->batch_mode || c->batch_single) && !(ep.ablate & 32);  // (ablated controller: per-evaluation launches)
-  if (!persistent) st->flags |= SO_ICP_FLAG_PER_EVAL_LAUNCHES;
-  // deferred report (see EvalParams::defer_publish): possible when the host always has the next k-NN launch in the queue
-  // before it waits for a report
-  const bool defer_reports = persistent && direct_rb && c->speculate;
-  mp.publish_prev = defer_reports ? 1 : 0;
-  auto enqueue_eval = [&](int slot) -> int {
-    span_begin(c, 1, (uint32_t)n);
-    const bool fuse_lm = !exchange;  // single device: the last workgroup of eval runs the LM controller itself
-    launch_eval(slot, fuse_lm, d_scan, d_scan + 1, d_scan + 2, corr, ds, ep, c->d_partials,
-                c->d_ticket, c->d_hist, c->d_sums, c->view, c->d_nbr5.as<uint32_t>(), mp, (uint32_t)n, s);
-    span_end(c);
-    if (!fuse_lm && c->group) {  // in-process group: through host memory (every member calls this the same number of times)
-      HIP_TRY(c, hipMemcpyAsync(c->h_sums, c->d_sums, sizeof(LmSums), hipMemcpyDeviceToHost, s));
-      HIP_TRY(c, hipStreamSynchronize(s));
-      if (!group_allreduce(c, c->h_sums))
-        return fail(c, SO_ICP_E_RCCL, "in-process group: the exchange of the normal-equation sums failed (a member returned early or did not arrive)");
-      HIP_TRY(c, hipMemcpyAsync(c->d_sums, c->h_sums, sizeof(LmSums), hipMemcpyHostToDevice, s));
-      launch_lm_step(slot, ds, c->d_sums, c->d_hist, ep, s);
-    } else if (!fuse_lm) {  // per-evaluation collective: 45 fp64 summed over the shards (xGMI, latency-bound), then the controller
-      const ncclResult_t nrc = c->rccl.AllReduce(c->d_sums, c->d_sums, sizeof(LmSums) / sizeof(double), ncclDouble, ncclSum, c->comm, s);
-      if (nrc != ncclSuccess) return fail(c, SO_ICP_E_RCCL, std::string("ncclAllReduce: ") + (c->rccl.GetErrorString ? c->rccl.GetErrorString(nrc) : "?"));
-      launch_lm_step(slot, ds, c->d_sums, c->d_hist, ep, s);
-    }
-    return SO_ICP_OK;
-  };
-  auto enqueue_outer_a = [&](int it) -> int {
-    if (it > 0 && c->cfg.world_size > 1 && n && !qsplit) {
-      // sharded map: ownership follows the query's cell under the CURRENT pose, so the scan is re-binned at the start of
-      // every outer iteration (a 1 degree correction at 50 m moves a point by more than the one-cell halo of a shard)
-      launch_scan_keys(d_scan, (uint32_t)n, ds, pose_in, max_outer, lm_max, c->d_hist, c->view, c->cfg.max_surface_features, c->cfg.rank,
-                       c->cfg.world_size, c->d_keys0.as<uint32_t>(), c->d_vals0.as<uint32_t>(), c->d_status.as<uint8_t>(), bt, s, true);
-      launch_bin_offsets(bt, c->d_chunks.as<uint32_t>(), (uint32_t)(c->d_chunks.cap / 4), ds, s);
-      launch_bin_place(bt, d_scan, (uint32_t)n, c->d_keys0.as<uint32_t>(), c->d_vals0.as<uint32_t>(), c->d_binned.as<float4>(), s, ds);
-    }
-    // processPlannerFeatures: every kept query in parallel (LidarSlam.cpp:323-344)
-    knn_span_of_outer.push_back(c->spans.size());
-    hipEvent_t ka = nullptr, kb = nullptr;
-    if (timed) {  // the events ride on the dispatch packet (hipExtLaunchKernelGGL), no marker packets
-      ka = next_event(c); kb = next_event(c);
-      if (ka && kb) c->spans.push_back(EventSpan{0, ka, kb, (uint32_t)n});
-    }
-    MatchParams mp_it = mp;
-    if (it == 0 && begin_in_knn && !query_waves) begin_in_sweep(c, mp_it, *pb, n, pose_in, max_outer, lm_max, 0);
-    if (query_waves)
-      launch_knn_query_waves(d_scan, (uint32_t)n, ds, pose_in, max_outer, lm_max, it == 0, c->d_hist, c->view, mp, c->cfg.max_surface_features,
-                             c->d_status.as<uint8_t>(), c->d_nbr5.as<uint32_t>(), s, ka, kb);
-    else
-      launch_knn_plane(d_binned, d_chunks, ds, c->view, mp_it, corr, c->d_nbr5.as<uint32_t>(), c->d_hist, s, ka, kb);
-    if (c->cfg.time_kernels >= 2)  // kernel statistics of this sweep (profiling mode only)
-      HIP_TRY(c, hipMemcpyAsync(c->h_hist + (size_t)it * kHistReplicas * kHistStride, c->d_hist,
-                                kHistReplicas * kHistStride * sizeof(int32_t), hipMemcpyDeviceToHost, s));
-    // setupOptimizationProblem + solveOptimizationProblem (LidarSlam.cpp:213-240): 1 + lm_max fused evaluations
-    eval_span_first.push_back(c->spans.size());
-    HIP_TRY(c, hipGetLastError());
-    if (persistent) return SO_ICP_OK;  // the solve launch belongs to part B: only the k-NN sweep is speculated
-    return enqueue_eval(0);
-  };
-  auto enqueue_outer_b = [&](int it) -> int {
-    const bool deferred = defer_reports && it + 1 < max_outer;  // the k-NN launch of it + 1 will be enqueued before the host waits
-    if (persistent) {  // the whole solve in one launch (workgroups hand the next pose to each other on the device)
-      EvalParams ep_it = ep;
-      ep_it.defer_publish = deferred ? 1 : 0;
-      ep_it.epoch_base = (++c->solve_launches) << 5;
-      span_begin(c, 1, (uint32_t)n);
-      launch_solve(lm_max, d_scan, d_scan + 1, d_scan + 2, corr, ds, ep_it, c->d_partials, c->d_ticket,
-                   c->d_hist, c->d_sums, c->view, c->d_nbr5.as<uint32_t>(), mp, (uint32_t)n, (uint32_t)c->n_cus, s);
-      span_end(c);
-    } else {
-      for (int slot = 1; slot <= lm_max; ++slot) { const int r = enqueue_eval(slot); if (r) return r; }
-    }
-    // the whole state block (pose, per-iteration statistics, final normal equations) into this iteration's pinned mirror
-    if (!direct_rb) HIP_TRY(c, hipMemcpyAsync(c->h_ring[it & 1], ds, sizeof(DevState), hipMemcpyDeviceToHost, s));
-    // (a deferred report is complete only after the NEXT k-NN launch: the event is recorded behind that one, see the loop)
-    // (the pinned mirrors are polled; the event is the watchdog of that wait only where the stream itself cannot serve as one)
-    if (!direct_rb) HIP_TRY(c, hipEventRecord(c->ev_outer[it & 1], s));
-    HIP_TRY(c, hipGetLastError());
-    return SO_ICP_OK;
-  };
-  // wait until outer iteration `it` has been reported
-  auto await_outer = [&](int it) -> int {
-    if (!direct_rb) { HIP_TRY(c, hipEventSynchronize(c->ev_outer[it & 1])); return SO_ICP_OK; }
-    volatile unsigned long long* seq = &c->h_ring[it & 1]->seq;
-    const unsigned long long want = seq_base | (unsigned long long)(it + 1);
-    constexpr int kReportWatchdogMs = 5;  // (a registration lasts 0.15 ms; the waits inside a solve launch give up after 50 ms)
-    auto next_check = std::chrono::steady_clock::now() + std::chrono::milliseconds(kReportWatchdogMs);
-    for (unsigned spin = 1;; ++spin) {
-      if (*seq == want) break;
-      if ((spin & 0x3FFu) != 0) continue;
-      const auto now = std::chrono::steady_clock::now();
-      if (now < next_check) continue;
-      next_check = now + std::chrono::milliseconds(1);
-      // watchdog: everything enqueued so far -- the launch that reports this iteration included -- has completed
-      if (hipStreamQuery(s) != hipErrorNotReady) {
-        (void)hipGetLastError();  // (hipErrorNotReady of the earlier polls, or the error the synchronize below reports)
-        // the iteration's launches have all completed: either it was a no-op (converged earlier: cannot happen for the
-        // iteration the host waits on) or a kernel failed -- report instead of spinning forever
-        if (*seq == want) break;
-        HIP_TRY(c, hipStreamSynchronize(s));
-        if (*seq == want) break;
-        if (persistent && peer) {
-          // The ranks' pass counters (DevState::peer_seq) and inboxes can no longer be assumed equal: chunks of the failed attempt
-          // still carry tags the next registration would reuse.  The peer path is left until the caller repeats the collective
-          // handshake (so_icp_peer_export clears the inbox and the counter, _connect, _enable).
-          c->peer_on = false; c->peer_connected = false;
-          return fail(c, SO_ICP_E_HIP, "peer exchange: a solve launch was abandoned (a rank's records did not arrive within SOICP_PEER_TIMEOUT_MS, or the "
-                                       "workgroups were not co-resident); the peer exchange is now disabled on this rank until so_icp_peer_export / "
-                                       "_connect / _enable are repeated on every rank");
-        }
-        if (persistent) {
-          // The persistent solve launch needs all of its workgroups resident at once.  If the device could not provide that
-          // (compute units held by another process, a partitioned device, ...) its waits gave up after 50 ms: fall back to
-          // one launch per evaluation for the rest of this context's life and run the registration again.
-          c->persistent_solve = false;
-          c->err = "persistent solve launch did not complete (workgroups not co-resident?): using per-evaluation launches from now on";
-          return kRetryWithoutPersistentSolve;
-        }
-        return fail(c, SO_ICP_E_HIP, "registration state was not published by the device");
-      }
-    }
-    std::atomic_thread_fence(std::memory_order_acquire);
-    return SO_ICP_OK;
-  };
+  if ((rc = begin_registration(c, p))) return rc;
+  st->flags |= p.flags;
   // The host stays ahead of what it knows: part A of iteration it+1 (the k-NN sweep; with a sharded map also the fit
   // evaluation) is enqueued before the report of iteration it is awaited, so the device never idles on a host round trip;
   // part B (the solve launch / the remaining evaluations) follows as soon as the report says "not converged" -- the device
@@ -506,59 +586,28 @@ static int register_core_once(so_icp_ctx* c, const float* d_scan, size_t n, cons
   // (every kernel consults DevState::reg_done) that drains while the host post-processes.
   // (SOICP_SPECULATE=0 enqueues nothing ahead: every launch of a profiled run is then a real one.)
   int last = 0;
-  if ((rc = enqueue_outer_a(0))) return rc;
+  if ((rc = enqueue_outer_a(c, p, 0))) return rc;
   // the NEXT scan's DMA goes out right behind this registration's first launch (the rest of what the copy queue does for that
   // scan follows below, once the launches that are not urgent -- the first sweep lasts 20 us -- are in the queue as well)
   if (!c->batch_mode) stage_issue_deferred_copy(c);
-  if ((rc = enqueue_outer_b(0))) return rc;
+  if ((rc = enqueue_outer_b(c, p, 0))) return rc;
   for (int it = 0;; ++it) {
-    if (c->speculate && it + 1 < max_outer && (rc = enqueue_outer_a(it + 1))) return rc;
+    if (c->speculate && it + 1 < p.max_outer && (rc = enqueue_outer_a(c, p, it + 1))) return rc;
     // this registration's launches are in the queue and the host is about to idle: the moment for the NEXT scan's DMA
     if (!c->batch_mode && it == 0) {
-      stage_issue_deferred(c, (may_prebin && !query_waves) ? pose_in : nullptr);  // (the next scan is binned behind its copy, under this registration's guess; a stream of small scans is not binned at all)
+      stage_issue_deferred(c, (p.may_prebin && !p.query_waves) ? pose_in : nullptr);  // (the next scan is binned behind its copy, under this registration's guess; a stream of small scans is not binned at all)
     }
-    if ((rc = await_outer(it))) return rc;
+    if ((rc = await_outer(c, p, it))) return rc;
     last = it;
-    if (c->h_ring[it & 1]->reg_done || it + 1 >= max_outer) break;
-    if (!c->speculate && (rc = enqueue_outer_a(it + 1))) return rc;  // SOICP_SPECULATE=0: no launch that could turn out a no-op
-    if ((rc = enqueue_outer_b(it + 1))) return rc;
+    if (c->h_ring[it & 1]->reg_done || it + 1 >= p.max_outer) break;
+    if (!c->speculate && (rc = enqueue_outer_a(c, p, it + 1))) return rc;  // SOICP_SPECULATE=0: no launch that could turn out a no-op
+    if ((rc = enqueue_outer_b(c, p, it + 1))) return rc;
   }
-  c->h_state = c->h_ring[last & 1];
+  note_registration_done(c, c->h_ring[last & 1], p.mp, p.n, true, !c->batch_mode && !c->borrow.on);
   const DevState& H = *c->h_state;
-  note_packing(c, H, mp, n);
-  // (scans of a stream have one size: the list of this registration decides the packing of the next -- results do not depend on it)
-  c->knn_list_fits = ((H.bin_packed >> 21) & 0x1FFFFFull) + (H.bin_packed >> 42) <= (unsigned long long)kKnnBlocks * 4ull;
-  if (!c->batch_mode && !c->borrow.on) c->done_count_seen = H.done_count;  // (registrations completed on the context's state block: so_icp_register_sequence)
   fill_result(c, H, pose_in, st, pose_out, !c->batch_mode);
   st->time_elapsed_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_icp).count();  // :199-200
-  if (timed) {  // keep only the launches that did real work (no-op launches after convergence are excluded)
-    std::vector<EventSpan> real;
-    for (size_t i = 0; i < c->spans.size(); ++i) {
-      const EventSpan& sp = c->spans[i];
-      bool keep = (sp.kind == 2);
-      for (int it = 0; it < H.n_iterations && !keep; ++it) {
-        if (sp.kind == 0 && it < (int)knn_span_of_outer.size() && i == knn_span_of_outer[it]) keep = true;
-        // (a persistent solve launch is ONE span per outer iteration, the per-evaluation schedule 1 + #LM iterations)
-        if (sp.kind == 1 && it < (int)eval_span_first.size() && i >= eval_span_first[it] &&
-            i < eval_span_first[it] + (persistent ? 1 : 1 + (size_t)std::max(H.iters[it].lm_iterations, 0))) keep = true;
-      }
-      if (keep) { EventSpan r = sp; r.units = (uint32_t)(H.bin_packed & 0x1FFFFFull); real.push_back(r); }
-    }
-    c->spans.swap(real);
-    // profiling mode brackets the solve launches too: the last one has published its result but its stop event may not
-    // have signalled yet (hipEventElapsedTime would refuse it) -- wait for the stream there; the k-NN events of mode 1
-    // completed long ago
-    if (c->cfg.time_kernels >= 2) HIP_TRY(c, hipStreamSynchronize(s));
-    spans_collect(c);
-    for (int it = 0; it < H.n_iterations && c->cfg.time_kernels >= 2; ++it)
-      for (int r = 0; r < kHistReplicas; ++r) {
-        const int32_t* hh = c->h_hist + ((size_t)it * kHistReplicas + r) * kHistStride;
-        c->timing.knn_group_passes += hh[16]; c->timing.knn_fallback_lanes += hh[17];
-        c->timing.knn_packed_rows += hh[20]; c->timing.knn_packed_rows_too_many_runs += hh[21]; c->timing.knn_packed_rows_tile_full += hh[22];
-        c->timing.knn_packed_kept += hh[23];
-        c->timing.knn_candidates_scanned += (int64_t)hh[18] * 16;
-      }
-  }
+  if (p.timed && (rc = collect_timing(c, p, H))) return rc;
   c->timing.registrations++;
   c->timing.host_ms_total += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_begin).count();
   return SO_ICP_OK;

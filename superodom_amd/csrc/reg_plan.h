@@ -1,0 +1,59 @@
+// reg_plan.h -- the decisions of a registration's host schedule that need no device: limits, the query split, table and work-list
+// sizes, the window rule of a chained start.  Plain arithmetic, one definition each for icp_context.cpp, sequence.cpp, batch.cpp and
+// staging.cpp; compiled for the host alone by tests/native/reg_plan_host.cpp.
+#pragma once
+#include <algorithm>
+#include <cstddef>
+#include <cstdint>
+
+#include "so_math.h"
+
+namespace soicp::host {
+
+// loop bounds of a registration: LidarSlam.h:273 (4 outer iterations, 4 LM iterations where the configuration gives none); the
+// caps are the per-iteration statistics of so_icp_stats (SO_ICP_MAX_OUTER, checked in ctx.h) and the solve launch's slots
+constexpr int kOuterCap = 16, kLmCap = 16;
+inline int outer_limit(int max_iterations) { return std::min(max_iterations > 0 ? max_iterations : 4, kOuterCap); }
+inline int lm_limit(int lm_max_iterations) { return std::min(lm_max_iterations > 0 ? lm_max_iterations : 4, kLmCap); }
+
+// scans of this many points or more are refused (refuse_scan_size, icp_context.cpp): the work-list counters hold 21 bits each
+constexpr size_t kMaxScanPoints = (size_t)1 << 21;
+
+// upper bound of the queries the sampling rule keeps of n points (the rule keeps ~ rate * n points)
+inline size_t kept_upper_bound(int max_sf, size_t n) { return (max_sf >= 0 && n > (size_t)max_sf) ? (size_t)max_sf + 2 : n; }
+// A SMALL scan -- the stock operating point of the node: max_surface_features 2000 / 4000 of a pre-filtered cloud -- is not binned at
+// all: every kept query gets a wavefront of its own (knn_query_wave_kernel, up to `max_kept` = kQueryWaveMaxKept of them)
+inline bool query_wave_count_ok(int max_sf, size_t n, size_t max_kept) { return n != 0 && kept_upper_bound(max_sf, n) <= max_kept; }
+
+// SO_ICP_SHARD_QUERIES: rank's share of a scan of n points -- the 64-point segments rank, rank + world, ...; the partial last
+// segment is segment number n / 64
+struct QueryShare { size_t own_full; bool own_tail; size_t n_own; };
+inline QueryShare query_split_share(size_t n, size_t world, size_t rank) {
+  const size_t s_full = n / 64, tail = n % 64, own_full = s_full > rank ? (s_full - rank + world - 1) / world : 0;
+  const bool own_tail = tail != 0 && (s_full % world) == rank;
+  return QueryShare{own_full, own_tail, own_full * 64 + (own_tail ? tail : 0)};
+}
+
+// the hash table for the binning of a scan of n points: >= 2 slots per query
+inline uint32_t bin_table_log2(size_t n) {
+  uint32_t lg = 16;
+  while ((1ull << lg) < 2 * (unsigned long long)n) ++lg;
+  return lg;
+}
+
+// DevState::bin_packed = kept queries | normal chunks << 21 | light chunks << 42: the work list (normal + light chunks) fits the
+// k-NN grid of `wavefronts` one chunk per wavefront
+inline bool work_list_fits(unsigned long long bin_packed, unsigned long long wavefronts) { return ((bin_packed >> 21) & 0x1FFFFFull) + (bin_packed >> 42) <= wavefronts; }
+inline uint32_t work_list_kept(unsigned long long bin_packed) { return (uint32_t)(bin_packed & 0x1FFFFFull); }
+
+// The window would not roll for a pose at t (LocalMap.h:169-287: the sensor's block stays >= 3 blocks from the border), and no
+// pose within `margin` of it lies in another block: placing the window for a PREDICTED guess is placing it for the actual one
+inline bool cube_stable(const int origin[3], const int dims[3], const double t[3], double margin) {
+  for (int a = 0; a < 3; ++a) {
+    const int lo = cube_coord(t[a] - margin, origin[a]), hi = cube_coord(t[a] + margin, origin[a]);
+    if (lo != hi || lo < 3 || lo >= dims[a] - 3) return false;
+  }
+  return true;
+}
+
+}  // namespace soicp::host

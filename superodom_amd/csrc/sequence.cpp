@@ -14,6 +14,7 @@
 #include <algorithm>
 #include <chrono>
 #include <cstring>
+#include <string>
 #include <vector>
 
 #include "ctx.h"
@@ -30,10 +31,11 @@ bool chained_path(const so_icp_ctx* c, int count, int scans_on_device, size_t st
          (scans_on_device || stride_bytes == 12) && count > 1;
 }
 
-struct SeqRun {
-  const float* d_scan = nullptr; size_t n = 0;
+constexpr int kNotStaged = -1001;  // SequenceCall::stage of an announced scan: not staged ahead (internal: never leaves this file)
+
+struct SeqRun : RegWork {                  // (d_scan, n, query_waves, work list, bounds: what the launches read)
   so_icp_ctx::StageSlot* slot = nullptr;   // host scan (its HBM copy) and / or the work list binned ahead; nullptr: resident scan swept by query waves
-  bool query_waves = false, binned = false, enqueued = false, chained = false, needs_event = false;
+  bool binned = false, enqueued = false, chained = false, needs_event = false;
   bool copied = false;                      // the H2D copy of this (host) scan is already in the sequence's queue (issued one registration early)
   bool timed = false;                       // time_kernels 1: this registration's sweeps carry timing events
   struct KnnEv { int it; hipEvent_t a, b; };
@@ -43,25 +45,318 @@ struct SeqRun {
   int pos[3] = {0, 0, 0}; int count_5x5 = 0;
   unsigned long long seq_base = 0; int ring = 0; int enq_iters = 0;
   MatchParams mp; EvalParams ep;
-  const float4* d_binned = nullptr; const uint32_t* d_chunks = nullptr;
 };
-inline bool cube_stable(const so_icp_ctx* c, const double t[3], double margin) {
-  // the window would not roll for a pose here (LocalMap.h:169-287: the sensor's block stays >= 3 blocks from the border), and no
-  // pose within `margin` of it lies in another block: placing the window for the PREDICTED guess is placing it for the actual one
-  const int* o = map_origin(c);
-  const int dim[3] = {kMapW, kMapH, kMapD};
-  for (int a = 0; a < 3; ++a) {
-    const int lo = cube_coord(t[a] - margin, o[a]), hi = cube_coord(t[a] + margin, o[a]);
-    if (lo != hi || lo < 3 || lo >= dim[a] - 3) return false;
+
+// One so_icp_register_sequence call: its arguments, the run record of every scan, what the call before staged for scan 0
+struct SequenceCall {
+  so_icp_ctx* c; int count; const void* const* scans; const size_t* n_points; size_t stride_bytes; int scans_on_device;
+  const double* pose0; const double* deltas; double* poses_out; double* guesses_out; so_icp_stats* stats; int* n_done;
+  std::vector<SeqRun> runs;
+  so_icp_ctx::SeqNext adopted;
+  int slot_base = 0;
+
+  const double* delta(int k) const { return deltas + 7 * (size_t)k; }
+  // the pose the chain continues from: the optimised pose of the registration, before MannualYawCorrection (fill_result)
+  void chain_from(int k, double T[7]) const {
+    const so_icp_stats& s = stats[k];
+    if (s.n_iterations > 0) std::memcpy(T, s.iterations[std::min(s.n_iterations, SO_ICP_MAX_OUTER) - 1].pose_after, 7 * sizeof(double));
+    else std::memcpy(T, poses_out + 7 * (size_t)k, 7 * sizeof(double));
   }
-  return true;
-}
-// a small scan is not binned: its queries are swept one wavefront each (register_core_once)
-bool sweeps_query_waves(const so_icp_ctx* c, size_t n) {
-  const int max_sf = c->cfg.max_surface_features;
-  const size_t kept_upper = (max_sf >= 0 && n > (size_t)max_sf) ? (size_t)max_sf + 2 : n;
-  return c->query_waves && n && kept_upper <= kQueryWaveMaxKept;
-}
+  void exact_guess(int k, double g[7]) const {  // of scan k, once scan k - 1 is done
+    if (k == 0) { std::memcpy(g, pose0, 7 * sizeof(double)); return; }
+    double T[7];
+    chain_from(k - 1, T); pose_compose(T, delta(k), g);
+  }
+  int run_plain(int k, const double guess[7]) {  // one registration through the ordinary entry points
+    if (guesses_out) std::memcpy(guesses_out + 7 * (size_t)k, guess, 7 * sizeof(double));
+    return scans_on_device ? so_icp_register_dev(c, scans[k], n_points[k], guess, poses_out + 7 * (size_t)k, &stats[k])
+                           : so_icp_register(c, static_cast<const float*>(scans[k]), n_points[k], stride_bytes, guess, poses_out + 7 * (size_t)k, &stats[k]);
+  }
+  int run_unchained() {  // the registrations one after the other, guesses composed on the host
+    for (int k = 0; k < count; ++k) {
+      double guess[7];
+      exact_guess(k, guess);
+      const int rc = run_plain(k, guess);
+      if (rc) return rc;
+      if (n_done) *n_done = k + 1;
+    }
+    return SO_ICP_OK;
+  }
+
+  void init_run(SeqRun& r, size_t n, int k) {  // (k: position in the slot rotation, `count` for the announced scan)
+    r.n = n;
+    r.query_waves = c->query_waves && query_wave_count_ok(c->cfg.max_surface_features, n, kQueryWaveMaxKept);  // (as register_core_once sweeps it)
+    r.ring = (k & 1) * 2;
+    if (!scans_on_device || !r.query_waves) r.slot = &c->seq_slot[(slot_base + k) % so_icp_ctx::kStageSlots];
+    r.max_outer = outer_limit(c->cfg.max_iterations); r.lm_max = lm_limit(c->cfg.lm_max_iterations);
+    r.corr = CorrBuffers{c->d_nd.as<double4>(), c->d_coeff.as<double>(), c->d_status.as<uint8_t>()};
+  }
+  int copy_in(SeqRun& r, const void* src) {  // a host scan into its slot, on the sequence's own queue
+    if (r.copied) return SO_ICP_OK;
+    HIP_TRY(c, r.slot->dev.reserve((r.n + 64) * 12));
+    HIP_TRY(c, hipMemcpyAsync(r.slot->dev.p, src, r.n * 12, hipMemcpyHostToDevice, c->seq_stream));
+    r.copied = true;
+    return SO_ICP_OK;
+  }
+  // the scan's way to HBM and its work list, on the sequence's own queue: copy (host scans), scan_keys -> bin_offsets -> bin_place under
+  // `pose` (scans swept in chunks), one event.  Slot k % 3: its last user, scan k - 3, was collected before scan k - 1 was enqueued.
+  // `announced`: the scan that will start the NEXT call (so_icp_sequence_announce_next), staged beside this call's last registration.
+  // For that one any return but SO_ICP_OK only means "not staged ahead" (stage_announced), and the hash table is taken as the last
+  // binning of this call left it -- clean at this size, or not used: never re-ensured or cleared under the registrations in flight.
+  int stage(SeqRun& r, const void* src, const double pose[7], bool announced) {
+    r.d_scan = static_cast<const float*>(src);
+    r.binned = false; r.needs_event = false;
+    if (!r.slot || !r.n) { if (!scans_on_device) r.d_scan = nullptr; return announced ? kNotStaged : SO_ICP_OK; }
+    so_icp_ctx::StageSlot& sl = *r.slot;
+    if (!sl.ev) HIP_TRY(c, hipEventCreateWithFlags(&sl.ev, hipEventDisableTiming));
+    if (!scans_on_device) {
+      const int rc = copy_in(r, src);
+      if (rc) return rc;
+      r.d_scan = sl.dev.as<float>();
+      r.needs_event = true;
+    }
+    if (!r.query_waves) {
+      if (!c->prebin) return SO_ICP_OK;  // (binned by the registration itself: never chained)
+      HIP_TRY(c, sl.reserve_worklist(r.n));
+      if (announced) { if (c->sbin.log2 != bin_table_log2(r.n)) return kNotStaged; }
+      else HIP_TRY(c, c->sbin.ensure(bin_table_log2(r.n), c->seq_stream));
+      if (!bin_into_slot(c, r.d_scan, r.n, pose, c->seq_stream, c->sbin, sl)) return fail(c, SO_ICP_E_HIP, "so_icp_register_sequence: the binning launches were refused");
+      r.binned = true; r.needs_event = true;
+      r.d_binned = sl.pb_binned.as<float4>(); r.d_chunks = sl.pb_chunks.as<uint32_t>();
+    }
+    if (r.needs_event) HIP_TRY(c, hipEventRecord(sl.ev, c->seq_stream));
+    return SO_ICP_OK;
+  }
+  // The copy of a host scan TWO registrations ahead (its slot's last user, scan k - 3, has been collected): the binning of scan k + 1 is then
+  // enqueued with its scan long in HBM and runs beside the FIRST SWEEP of registration k -- hundreds of short wavefronts next to a sweep that
+  // leaves 60 % of its issue slots empty -- instead of behind a 34 us copy, beside the first solve, whose one wavefront per SIMD it slowed
+  // by ~5 us (41 - 43 us against 36 - 37 for the second solve of the same registration: profiles/r06/sequence_timeline_flag_wait.txt).
+  int copy_ahead(int k) {
+    if (k >= count || scans_on_device) return SO_ICP_OK;
+    SeqRun& r = runs[(size_t)k];
+    return (r.slot && r.n) ? copy_in(r, scans[k]) : SO_ICP_OK;
+  }
+  // the scan that will start the NEXT call: on its way to HBM and binned beside this call's last registration `last`
+  void stage_announced(const SeqRun& last) {
+    so_icp_ctx::SeqNext& nx = c->seq_next;
+    nx.announced = false;
+    double pred[7];
+    pose_compose(last.guess, nx.delta, pred);
+    nx.scan = nx.next_scan; nx.n = nx.next_n;
+    nx.slot = (slot_base + count) % so_icp_ctx::kStageSlots;
+    SeqRun rn;
+    init_run(rn, nx.n, count);
+    std::string err = c->err;  // (a failure is no error of this call: neither its return value nor its text)
+    nx.staged = stage(rn, nx.scan, pred, true) == SO_ICP_OK;
+    if (!nx.staged) c->err.swap(err);
+    (void)hipGetLastError();
+    nx.binned = rn.binned; nx.needs_event = rn.needs_event; nx.d_scan = nx.staged ? rn.d_scan : nullptr;
+  }
+  // host side of a registration's start (register_core_once): window, map view, parameters.  false + rc == 0: cannot be started this way
+  bool prepare(int k, const double guess[7], bool chained, int* rc_out) {
+    SeqRun& r = runs[(size_t)k];
+    *rc_out = SO_ICP_OK;
+    std::memcpy(r.guess, guess, sizeof(r.guess));
+    if (!r.query_waves && !r.binned) return false;
+    if (!c->no_map_shift) {
+      const int dims[3] = {kMapW, kMapH, kMapD};
+      if (chained && !cube_stable(map_origin(c), dims, guess, 1.0)) return false;
+      map_shift(c, guess, r.pos); std::memcpy(c->last_pos, r.pos, sizeof(r.pos));
+    } else std::memcpy(r.pos, c->last_pos, sizeof(r.pos));
+    r.count_5x5 = map_count_5x5(c, r.pos);
+    if (!(r.count_5x5 > 50)) { if (!chained) *rc_out = SO_ICP_NOT_ENOUGH_MAP_FEATURES; return false; }  // LidarSlam.cpp:113-116
+    if ((*rc_out = upload_map(c))) return false;
+    r.seq_base = registration_params(c, map_plane_res(c), r.n, r.binned ? r.slot->pb_chunk_cap : 0, r.ring, r.mp, r.ep);
+    r.chained = chained;
+    // (every seventh registration -- a period coprime to the scan rotation of the benchmarks: an event pair on a dispatch was measured at
+    //  ~8 us of queue time here, where no idle moment between back-to-back chained launches hides it: 4 % of the rate at every third)
+    r.timed = c->cfg.time_kernels == 1 && (k % 7) == 0;
+    r.knn_ev.clear();
+    r.chain_expect = chained ? c->done_count_seen + 1u : 0u;  // (exactly the registration in front of this one completes in between)
+    r.mp.chain_expect = r.chain_expect; r.ep.chain_expect = r.chain_expect;
+    return true;
+  }
+  // outer iterations [it0, it1) of run k into the queue; the solve of it1 - 1 reports by itself (nothing of this registration is
+  // enqueued behind it yet), the others leave their report to the sweep behind them (EvalParams::defer_publish)
+  int enqueue(int k, int it0, int it1) {
+    SeqRun& r = runs[(size_t)k];
+    // Scan and work list come from the other queue.  The host WATCHES that queue's event for the scan (the copy went out a registration
+    // ago, the binning a moment ago: tens of microseconds, and the registration in front has only just begun) and enqueues this
+    // registration's launches once it has fired -- then nothing has to order the two queues on the device.  Measured alternatives: a
+    // barrier packet in front of the first launch (hipStreamWaitEvent) costs 5.6 us of command-processor time between two registrations;
+    // a first launch that polls a flag in device memory costs nothing -- and deadlocks when it is dispatched before the binning
+    // kernels it waits for (its 4 096 spinning wavefronts fill the chip: seen once, on a first call whose allocations had held the host up).
+    if (it0 == 0 && r.needs_event) {
+      const auto t_w = std::chrono::steady_clock::now();
+      bool fired = false;
+      for (unsigned spin = 0;; ++spin) {
+        const hipError_t q = hipEventQuery(r.slot->ev);
+        if (q == hipSuccess) { fired = true; break; }
+        if (q != hipErrorNotReady) break;
+        if ((spin & 15u) == 15u && std::chrono::steady_clock::now() - t_w > std::chrono::microseconds(400)) break;
+      }
+      (void)hipGetLastError();
+      if (!fired) HIP_TRY(c, hipStreamWaitEvent(c->stream, r.slot->ev, 0));  // (the other queue is late: let the device order the two)
+    }
+    for (int it = it0; it < it1; ++it) {
+      MatchParams mp_it = r.mp;
+      mp_it.publish_prev = (it > it0) ? 1 : 0;  // (the solve in front of this sweep deferred its report)
+      hipEvent_t ka = nullptr, kb = nullptr;
+      if (r.timed) {  // (the events ride on the dispatch packet, no marker packets)
+        ka = next_event(c); kb = next_event(c);
+        if (ka && kb) r.knn_ev.push_back(SeqRun::KnnEv{it, ka, kb}); else ka = kb = nullptr;
+      }
+      launch_sweep(c, r, mp_it, it == 0, it == 0 ? r.slot : nullptr, r.guess, r.chain_expect, ka, kb);
+      EvalParams ep_it = r.ep;
+      ep_it.defer_publish = (it + 1 < it1) ? 1 : 0;
+      if (k + 1 < count) { ep_it.chain_next = 1; std::memcpy(ep_it.chain_delta, delta(k + 1), sizeof(ep_it.chain_delta)); }  // (whichever solve ends this registration forms the next guess)
+      launch_persistent_solve(c, r, ep_it, r.mp);
+    }
+    HIP_TRY(c, hipGetLastError());
+    r.enq_iters = it1; r.enqueued = true;
+    return SO_ICP_OK;
+  }
+  // prepare, then the iterations a registration gets enqueued ahead: what the last one needed (so_icp_ctx::seq_depth)
+  bool start(int k, const double guess[7], bool chained, int* rc_out) {
+    if (!prepare(k, guess, chained, rc_out)) return false;
+    *rc_out = enqueue(k, 0, std::max(1, std::min(c->seq_depth, runs[(size_t)k].max_outer)));
+    return true;
+  }
+  int await(int k, int it) {
+    const SeqRun& r = runs[(size_t)k];
+    const Report rep = await_report(c, &c->h_ring[r.ring + (it & 1)]->seq, r.seq_base | (unsigned long long)(it + 1), c->stream);
+    if (rep != Report::kDrained) return rep == Report::kReported ? SO_ICP_OK : SO_ICP_E_HIP;
+    return fail(c, SO_ICP_E_HIP, "so_icp_register_sequence: registration state was not published by the device");
+  }
+  // the results of run k, reported last by outer iteration `last`
+  int collect(int k, int last, std::chrono::steady_clock::time_point t_icp) {
+    SeqRun& r = runs[(size_t)k];
+    so_icp_stats* st = &stats[k];
+    // (a registration swept by query waves builds no work list: knn_list_fits stays; the state block is the context's own)
+    note_registration_done(c, c->h_ring[r.ring + (last & 1)], r.mp, r.n, !r.query_waves, true);
+    const DevState& H = *c->h_state;
+    std::memset(st, 0, sizeof(*st));
+    st->flags = (r.slot && !scans_on_device ? SO_ICP_FLAG_STAGED_SCAN : 0u) | (r.binned ? SO_ICP_FLAG_BINNED_AHEAD : 0u) |
+                (r.query_waves ? SO_ICP_FLAG_QUERY_WAVES : 0u) | (r.chained ? SO_ICP_FLAG_CHAINED : 0u);
+    fill_stats_header(c, st, r.pos, r.count_5x5, r.n);
+    double guess[7];
+    std::memcpy(guess, H.pose_in, sizeof(guess));  // (what the device formed for a chained registration; the host's own argument otherwise)
+    if (guesses_out) std::memcpy(guesses_out + 7 * (size_t)k, guess, sizeof(guess));
+    c->seq_depth = std::max(1, H.n_iterations);
+    for (const SeqRun::KnnEv& e : r.knn_ev) {  // sweeps that did real work (a launch behind the converged iteration was a no-op); they ended long ago
+      float ms = 0;
+      if (e.it < H.n_iterations && hipEventElapsedTime(&ms, e.a, e.b) == hipSuccess) {
+        c->timing.knn_ms_total += ms; c->timing.knn_launches++;
+        c->timing.knn_queries += r.query_waves ? (int64_t)r.n : (int64_t)work_list_kept(H.bin_packed); c->timing.knn_map_points += c->view.n_points;
+      }
+    }
+    (void)hipGetLastError();
+    fill_result(c, H, guess, st, poses_out + 7 * (size_t)k, true);
+    st->time_elapsed_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_icp).count();
+    c->timing.registrations++;
+    if (r.chained) {
+      c->timing.seq_chained++;
+      // the window was placed for the predicted guess: the actual one must lie in the same block (cube_stable saw to it)
+      const int* o = map_origin(c);
+      if (cube_coord(guess[0], o[0]) != r.pos[0] || cube_coord(guess[1], o[1]) != r.pos[1] || cube_coord(guess[2], o[2]) != r.pos[2])
+        return fail(c, SO_ICP_E_HIP, "so_icp_register_sequence: a chained guess left the map block its window was placed for");
+    }
+    return SO_ICP_OK;
+  }
+
+  int run_chained() {
+    if (!c->seq_stream) HIP_TRY(c, hipStreamCreateWithFlags(&c->seq_stream, hipStreamNonBlocking));
+    struct Drain {  // an early return must not leave copies reading the caller's buffers, nor launches of this call in the queue
+      so_icp_ctx* c; bool ok = false;
+      ~Drain() { if (!ok) { (void)hipStreamSynchronize(c->seq_stream); (void)hipStreamSynchronize(c->stream); (void)hipGetLastError(); c->ev_used = 0; } }
+    } drain{c};
+    size_t n_max = 0;
+    for (int k = 0; k < count; ++k) {
+      if (n_points[k] >= kMaxScanPoints) return refuse_scan_size(c);
+      n_max = std::max(n_max, n_points[k]);
+    }
+    int rc = SO_ICP_OK;
+    if ((rc = reserve_scan_buffers(c, n_max))) return rc;  // (once, for the longest scan: nothing is re-allocated under a registration in flight)
+    if ((rc = upload_map(c))) return rc;                   // (the binning ahead of scan 0 reads the map view before the first prepare())
+    // scan 0 may already be in HBM with its work list: the call before this one staged it beside its last registration (so_icp_sequence_announce_next)
+    adopted = c->seq_next;
+    const bool adopt = adopted.staged && adopted.scan == scans[0] && adopted.n == n_points[0];
+    slot_base = adopt ? adopted.slot : 0;
+    c->seq_next.staged = false;
+    runs.resize((size_t)count);
+    for (int k = 0; k < count; ++k) init_run(runs[(size_t)k], n_points[k], k);
+    // scan 0: an ordinary start from pose0
+    if (adopt) {
+      SeqRun& r0 = runs[0];
+      r0.d_scan = adopted.d_scan; r0.binned = adopted.binned; r0.needs_event = adopted.needs_event;
+      if (r0.binned) { r0.d_binned = r0.slot->pb_binned.as<float4>(); r0.d_chunks = r0.slot->pb_chunks.as<uint32_t>(); }
+    } else if ((rc = stage(runs[0], scans[0], pose0, false))) return rc;
+    if ((rc = copy_ahead(1))) return rc;
+    bool started = start(0, pose0, false, &rc);
+    if (rc) return rc;
+    for (int k = 0; k < count; ++k) {
+      SeqRun& r = runs[(size_t)k];
+      bool next_started = false;
+      if (!started) {
+        // this scan cannot be started from here (an empty scan, too little map, a window about to roll, ...): the ordinary entry point,
+        // from the guess the chain arithmetic gives -- same results, and the next scan starts a new chain
+        double guess[7];
+        exact_guess(k, guess);
+        if (hipStreamSynchronize(c->seq_stream) != hipSuccess) return fail(c, SO_ICP_E_HIP, "so_icp_register_sequence: copy queue");
+        if ((rc = run_plain(k, guess))) return rc;
+        if (n_done) *n_done = k + 1;
+        if (k + 1 < count) {  // (after a plain registration: the next scan starts a chain of its own)
+          double g[7];
+          exact_guess(k + 1, g);
+          if ((rc = stage(runs[(size_t)k + 1], scans[k + 1], g, false))) return rc;
+          started = start(k + 1, g, false, &rc);
+          if (rc && rc != SO_ICP_NOT_ENOUGH_MAP_FEATURES) return rc;
+        }
+        continue;
+      }
+      const auto t_icp = std::chrono::steady_clock::now();
+      // the NEXT scan: on its way to HBM, binned under the host's prediction of its guess, and -- the point of this entry -- its
+      // registration enqueued behind this one's launches
+      if (k + 1 < count) {
+        double pred[7];
+        pose_compose(r.guess, delta(k + 1), pred);  // (this registration will move r.guess by centimetres: good enough to bin under and to place the window)
+        if ((rc = stage(runs[(size_t)k + 1], scans[k + 1], pred, false))) return rc;
+        if ((rc = copy_ahead(k + 2))) return rc;
+        next_started = start(k + 1, pred, true, &rc);
+        if (rc) return rc;
+      } else if (c->seq_next.announced && !scans_on_device) {
+        stage_announced(r);
+      }
+      // this registration's reports
+      int last = 0;
+      for (int it = 0;; ++it) {
+        if ((rc = await(k, it))) return rc;
+        last = it;
+        if (c->h_ring[r.ring + (it & 1)]->reg_done || it + 1 >= r.max_outer) break;
+        if (it + 1 >= r.enq_iters) {
+          // it needs more outer iterations than were enqueued ahead: the chained registration behind it has found it unfinished
+          // and turned itself off (DevState::done_count); one iteration at a time from here, the next scan starts again afterwards
+          if (next_started) { next_started = false; runs[(size_t)k + 1].enqueued = false; c->timing.seq_chain_breaks++; }
+          if ((rc = enqueue(k, it + 1, it + 2))) return rc;
+        }
+      }
+      if ((rc = collect(k, last, t_icp))) return rc;
+      if (k + 1 < count && !next_started && !runs[(size_t)k + 1].enqueued) {
+        // an ordinary start of the next scan, from the exact guess (after a broken chain: its copy and work list are where they were)
+        double g[7];
+        exact_guess(k + 1, g);
+        next_started = start(k + 1, g, false, &rc);
+        if (rc && rc != SO_ICP_NOT_ENOUGH_MAP_FEATURES) return rc;
+      }
+      started = next_started;
+      if (n_done) *n_done = k + 1;
+    }
+    c->scan_staged = false;
+    c->ev_used = 0;  // (the timing events of this call are free again)
+    drain.ok = true;
+    return SO_ICP_OK;
+  }
+};
 
 }  // namespace
 
@@ -92,345 +387,8 @@ int so_icp_register_sequence(so_icp_ctx* c, int count, const void* const* scans,
   for (int k = 0; k < count; ++k) if (!scans[k] && n_points[k]) return SO_ICP_E_INVALID;
   std::vector<so_icp_stats> local_stats;
   if (!stats) { local_stats.resize((size_t)count); stats = local_stats.data(); }
-  const bool fast = chained_path(c, count, scans_on_device, stride_bytes);
-  // the pose the chain continues from: the optimised pose of the registration, before MannualYawCorrection (fill_result)
-  auto chain_from = [&](int k, double T[7]) {
-    const so_icp_stats& s = stats[k];
-    if (s.n_iterations > 0) std::memcpy(T, s.iterations[std::min(s.n_iterations, SO_ICP_MAX_OUTER) - 1].pose_after, 7 * sizeof(double));
-    else std::memcpy(T, poses_out + 7 * (size_t)k, 7 * sizeof(double));
-  };
-  auto run_plain = [&](int k, const double guess[7]) -> int {  // one registration through the ordinary entry points
-    if (guesses_out) std::memcpy(guesses_out + 7 * (size_t)k, guess, 7 * sizeof(double));
-    return scans_on_device ? so_icp_register_dev(c, scans[k], n_points[k], guess, poses_out + 7 * (size_t)k, &stats[k])
-                           : so_icp_register(c, static_cast<const float*>(scans[k]), n_points[k], stride_bytes, guess, poses_out + 7 * (size_t)k, &stats[k]);
-  };
-  if (!fast) {
-    double guess[7];
-    std::memcpy(guess, pose0, sizeof(guess));
-    for (int k = 0; k < count; ++k) {
-      if (k) { double T[7]; chain_from(k - 1, T); pose_compose(T, deltas + 7 * (size_t)k, guess); }
-      const int rc = run_plain(k, guess);
-      if (rc) return rc;
-      if (n_done) *n_done = k + 1;
-    }
-    return SO_ICP_OK;
-  }
-
-  // ---------------- chained path
-  hipStream_t s = c->stream;
-  if (!c->seq_stream) HIP_TRY(c, hipStreamCreateWithFlags(&c->seq_stream, hipStreamNonBlocking));
-  struct Drain {  // an early return must not leave copies reading the caller's buffers, nor launches of this call in the queue
-    so_icp_ctx* c; bool ok = false;
-    ~Drain() { if (!ok) { (void)hipStreamSynchronize(c->seq_stream); (void)hipStreamSynchronize(c->stream); (void)hipGetLastError(); c->ev_used = 0; } }
-  } drain{c};
-  size_t n_max = 0;
-  for (int k = 0; k < count; ++k) {
-    if (n_points[k] >= ((size_t)1 << 21)) return fail(c, SO_ICP_E_UNSUPPORTED, "scan of 2^21 points or more: the work-list counters hold 21 bits each (chunk descriptors 26)");
-    n_max = std::max(n_max, n_points[k]);
-  }
-  { const int rc = reserve_scan_buffers(c, n_max); if (rc) return rc; }  // (once, for the longest scan: nothing is re-allocated under a registration in flight)
-  { const int rc = upload_map(c); if (rc) return rc; }                   // (the binning ahead of scan 0 reads the map view before the first prepare())
-  const int max_outer = std::min(c->cfg.max_iterations > 0 ? c->cfg.max_iterations : 4, SO_ICP_MAX_OUTER);
-  const int lm_max = std::min(c->cfg.lm_max_iterations > 0 ? c->cfg.lm_max_iterations : 4, 16);
-  const int max_sf = c->cfg.max_surface_features;
-  DevState* ds = c->d_state;
-  CorrBuffers corr{c->d_nd.as<double4>(), c->d_coeff.as<double>(), c->d_status.as<uint8_t>()};
-  std::vector<SeqRun> runs((size_t)count);
-  // scan 0 may already be in HBM with its work list: the call before this one staged it beside its last registration (so_icp_sequence_announce_next)
-  so_icp_ctx::SeqNext adopted = c->seq_next;
-  const bool adopt = adopted.staged && adopted.scan == scans[0] && adopted.n == n_points[0];
-  const int slot_base = adopt ? adopted.slot : 0;
-  c->seq_next.staged = false;
-  for (int k = 0; k < count; ++k) {
-    SeqRun& r = runs[(size_t)k];
-    r.n = n_points[k];
-    r.query_waves = sweeps_query_waves(c, r.n);
-    r.ring = (k & 1) * 2;
-    if (!scans_on_device || !r.query_waves) r.slot = &c->seq_slot[(slot_base + k) % so_icp_ctx::kStageSlots];
-  }
-  // the scan's way to HBM and its work list, on the sequence's own queue: copy (host scans), scan_keys -> bin_offsets -> bin_place under
-  // `pose` (scans swept in chunks), one event.  Slot k % 3: its last user, scan k - 3, was collected before scan k - 1 was enqueued.
-  auto stage_scan = [&](int k, const double pose[7]) -> int {
-    SeqRun& r = runs[(size_t)k];
-    r.d_scan = static_cast<const float*>(scans[k]);
-    r.binned = false; r.needs_event = false;
-    if (!r.slot || !r.n) { if (!scans_on_device) r.d_scan = nullptr; return SO_ICP_OK; }
-    so_icp_ctx::StageSlot& sl = *r.slot;
-    if (!sl.ev) HIP_TRY(c, hipEventCreateWithFlags(&sl.ev, hipEventDisableTiming));
-    if (!scans_on_device) {
-      if (!r.copied) {
-        HIP_TRY(c, sl.dev.reserve((r.n + 64) * 12));
-        HIP_TRY(c, hipMemcpyAsync(sl.dev.p, scans[k], r.n * 12, hipMemcpyHostToDevice, c->seq_stream));
-        r.copied = true;
-      }
-      r.d_scan = sl.dev.as<float>();
-      r.needs_event = true;
-    }
-    if (!r.query_waves) {
-      if (!c->prebin) return SO_ICP_OK;  // (binned by the registration itself: never chained)
-      HIP_TRY(c, sl.reserve_worklist(r.n));
-      HIP_TRY(c, c->sbin.ensure(bin_table_log2(r.n), c->seq_stream));
-      if (!bin_into_slot(c, r.d_scan, r.n, pose, c->seq_stream, c->sbin, sl)) return fail(c, SO_ICP_E_HIP, "so_icp_register_sequence: the binning launches were refused");
-      r.binned = true; r.needs_event = true;
-      r.d_binned = sl.pb_binned.as<float4>(); r.d_chunks = sl.pb_chunks.as<uint32_t>();
-    }
-    if (r.needs_event) HIP_TRY(c, hipEventRecord(sl.ev, c->seq_stream));
-    return SO_ICP_OK;
-  };
-  // The copy of a host scan TWO registrations ahead (its slot's last user, scan k - 3, has been collected): the binning of scan k + 1 is then
-  // enqueued with its scan long in HBM and runs beside the FIRST SWEEP of registration k -- hundreds of short wavefronts next to a sweep that
-  // leaves 60 % of its issue slots empty -- instead of behind a 34 us copy, beside the first solve, whose one wavefront per SIMD it slowed
-  // by ~5 us (41 - 43 us against 36 - 37 for the second solve of the same registration: profiles/r06/sequence_timeline_flag_wait.txt).
-  auto copy_ahead = [&](int k) -> int {
-    if (k >= count || scans_on_device) return SO_ICP_OK;
-    SeqRun& r = runs[(size_t)k];
-    if (!r.slot || !r.n || r.copied) return SO_ICP_OK;
-    so_icp_ctx::StageSlot& sl = *r.slot;
-    HIP_TRY(c, sl.dev.reserve((r.n + 64) * 12));
-    HIP_TRY(c, hipMemcpyAsync(sl.dev.p, scans[k], r.n * 12, hipMemcpyHostToDevice, c->seq_stream));
-    r.copied = true;
-    return SO_ICP_OK;
-  };
-  // host side of a registration's start (register_core_once): window, map view, parameters.  false + rc == 0: cannot be started this way
-  auto prepare = [&](int k, const double guess[7], bool chained, int* rc_out) -> bool {
-    SeqRun& r = runs[(size_t)k];
-    *rc_out = SO_ICP_OK;
-    std::memcpy(r.guess, guess, sizeof(r.guess));
-    if (!r.query_waves && !r.binned) return false;
-    if (!c->no_map_shift) {
-      if (chained && !cube_stable(c, guess, 1.0)) return false;
-      map_shift(c, guess, r.pos); std::memcpy(c->last_pos, r.pos, sizeof(r.pos));
-    } else std::memcpy(r.pos, c->last_pos, sizeof(r.pos));
-    r.count_5x5 = map_count_5x5(c, r.pos);
-    if (!(r.count_5x5 > 50)) { if (!chained) *rc_out = SO_ICP_NOT_ENOUGH_MAP_FEATURES; return false; }  // LidarSlam.cpp:113-116
-    if ((*rc_out = upload_map(c))) return false;
-    r.seq_base = registration_params(c, map_plane_res(c), r.n, r.binned ? r.slot->pb_chunk_cap : 0, r.ring, r.mp, r.ep);
-    r.chained = chained;
-    // (every seventh registration -- a period coprime to the scan rotation of the benchmarks: an event pair on a dispatch was measured at
-    //  ~8 us of queue time here, where no idle moment between back-to-back chained launches hides it: 4 % of the rate at every third)
-    r.timed = c->cfg.time_kernels == 1 && (k % 7) == 0;
-    r.knn_ev.clear();
-    r.chain_expect = chained ? c->done_count_seen + 1u : 0u;  // (exactly the registration in front of this one completes in between)
-    r.mp.chain_expect = r.chain_expect; r.ep.chain_expect = r.chain_expect;
-    return true;
-  };
-  // outer iterations [it0, it1) of run k into the queue; `last_publishes`: the solve of it1 - 1 reports by itself (nothing of this
-  // registration is enqueued behind it yet), the others leave their report to the sweep behind them (EvalParams::defer_publish)
-  auto enqueue = [&](int k, int it0, int it1) -> int {
-    SeqRun& r = runs[(size_t)k];
-    // Scan and work list come from the other queue.  The host WATCHES that queue's event for the scan (the copy went out a registration
-    // ago, the binning a moment ago: tens of microseconds, and the registration in front has only just begun) and enqueues this
-    // registration's launches once it has fired -- then nothing has to order the two queues on the device.  Measured alternatives: a
-    // barrier packet in front of the first launch (hipStreamWaitEvent) costs 5.6 us of command-processor time between two registrations;
-    // a first launch that polls a flag in device memory costs nothing -- and deadlocks when it is dispatched before the binning
-    // kernels it waits for (its 4 096 spinning wavefronts fill the chip: seen once, on a first call whose allocations had held the host up).
-    if (it0 == 0 && r.needs_event) {
-      const auto t_w = std::chrono::steady_clock::now();
-      bool fired = false;
-      for (unsigned spin = 0;; ++spin) {
-        const hipError_t q = hipEventQuery(r.slot->ev);
-        if (q == hipSuccess) { fired = true; break; }
-        if (q != hipErrorNotReady) break;
-        if ((spin & 15u) == 15u && std::chrono::steady_clock::now() - t_w > std::chrono::microseconds(400)) break;
-      }
-      (void)hipGetLastError();
-      if (!fired) HIP_TRY(c, hipStreamWaitEvent(s, r.slot->ev, 0));  // (the other queue is late: let the device order the two)
-    }
-    for (int it = it0; it < it1; ++it) {
-      MatchParams mp_it = r.mp;
-      mp_it.publish_prev = (it > it0) ? 1 : 0;  // (the solve in front of this sweep deferred its report)
-      hipEvent_t ka = nullptr, kb = nullptr;
-      if (r.timed) {  // (the events ride on the dispatch packet, no marker packets)
-        ka = next_event(c); kb = next_event(c);
-        if (ka && kb) r.knn_ev.push_back(SeqRun::KnnEv{it, ka, kb}); else ka = kb = nullptr;
-      }
-      if (r.query_waves) {
-        launch_knn_query_waves(r.d_scan, (uint32_t)r.n, ds, r.guess, max_outer, lm_max, it == 0, c->d_hist, c->view, mp_it, max_sf, c->d_status.as<uint8_t>(),
-                               c->d_nbr5.as<uint32_t>(), s, ka, kb, it == 0 ? r.chain_expect : 0u);
-      } else {
-        if (it == 0) begin_in_sweep(c, mp_it, *r.slot, r.n, r.guess, max_outer, lm_max, r.chain_expect);
-        launch_knn_plane(r.d_binned, r.d_chunks, ds, c->view, mp_it, corr, c->d_nbr5.as<uint32_t>(), c->d_hist, s, ka, kb);
-      }
-      EvalParams ep_it = r.ep;
-      ep_it.defer_publish = (it + 1 < it1) ? 1 : 0;
-      ep_it.epoch_base = (++c->solve_launches) << 5;
-      if (k + 1 < count) { ep_it.chain_next = 1; std::memcpy(ep_it.chain_delta, deltas + 7 * (size_t)(k + 1), sizeof(ep_it.chain_delta)); }  // (whichever solve ends this registration forms the next guess)
-      launch_solve(lm_max, r.d_scan, r.d_scan + 1, r.d_scan + 2, corr, ds, ep_it, c->d_partials, c->d_ticket, c->d_hist, c->d_sums, c->view,
-                   c->d_nbr5.as<uint32_t>(), r.mp, (uint32_t)r.n, (uint32_t)c->n_cus, s);
-    }
-    HIP_TRY(c, hipGetLastError());
-    r.enq_iters = it1; r.enqueued = true;
-    return SO_ICP_OK;
-  };
-  auto await = [&](int k, int it) -> int {
-    SeqRun& r = runs[(size_t)k];
-    volatile unsigned long long* seq = &c->h_ring[r.ring + (it & 1)]->seq;
-    const unsigned long long want = r.seq_base | (unsigned long long)(it + 1);
-    auto next_check = std::chrono::steady_clock::now() + std::chrono::milliseconds(5);
-    for (unsigned spin = 1;; ++spin) {
-      if (*seq == want) break;
-      if ((spin & 0x3FFu) != 0) continue;
-      const auto now = std::chrono::steady_clock::now();
-      if (now < next_check) continue;
-      next_check = now + std::chrono::milliseconds(1);
-      if (hipStreamQuery(s) != hipErrorNotReady) {  // everything enqueued has completed and the report is not there
-        (void)hipGetLastError();
-        if (*seq == want) break;
-        HIP_TRY(c, hipStreamSynchronize(s));
-        if (*seq == want) break;
-        return fail(c, SO_ICP_E_HIP, "so_icp_register_sequence: registration state was not published by the device");
-      }
-    }
-    std::atomic_thread_fence(std::memory_order_acquire);
-    return SO_ICP_OK;
-  };
-  const int depth0 = std::max(1, std::min(c->seq_depth, max_outer));
-  int rc = SO_ICP_OK;
-  // scan 0: an ordinary start from pose0
-  if (adopt) {
-    SeqRun& r0 = runs[0];
-    r0.d_scan = adopted.d_scan; r0.binned = adopted.binned; r0.needs_event = adopted.needs_event;
-    if (r0.binned) { r0.d_binned = r0.slot->pb_binned.as<float4>(); r0.d_chunks = r0.slot->pb_chunks.as<uint32_t>(); }
-  } else if ((rc = stage_scan(0, pose0))) return rc;
-  if ((rc = copy_ahead(1))) return rc;
-  bool started = prepare(0, pose0, false, &rc);
-  if (rc) return rc;
-  if (started && (rc = enqueue(0, 0, depth0))) return rc;
-  for (int k = 0; k < count; ++k) {
-    SeqRun& r = runs[(size_t)k];
-    so_icp_stats* st = &stats[k];
-    double* pose_out = poses_out + 7 * (size_t)k;
-    if (!started) {
-      // this scan cannot be started from here (an empty scan, too little map, a window about to roll, ...): the ordinary entry point,
-      // from the guess the chain arithmetic gives -- same results, and the next scan starts a new chain
-      double guess[7];
-      if (k == 0) std::memcpy(guess, pose0, sizeof(guess)); else { double T[7]; chain_from(k - 1, T); pose_compose(T, deltas + 7 * (size_t)k, guess); }
-      if ((rc = hipStreamSynchronize(c->seq_stream)) != hipSuccess) return fail(c, SO_ICP_E_HIP, "so_icp_register_sequence: copy queue");
-      if ((rc = run_plain(k, guess))) return rc;
-    } else {
-      const auto t_icp = std::chrono::steady_clock::now();
-      // the NEXT scan: on its way to HBM, binned under the host's prediction of its guess, and -- the point of this entry -- its
-      // registration enqueued behind this one's launches
-      bool next_started = false;
-      if (k + 1 < count) {
-        double pred[7];
-        pose_compose(r.guess, deltas + 7 * (size_t)(k + 1), pred);  // (this registration will move r.guess by centimetres: good enough to bin under and to place the window)
-        if ((rc = stage_scan(k + 1, pred))) return rc;
-        if ((rc = copy_ahead(k + 2))) return rc;
-        int prc = 0;
-        next_started = prepare(k + 1, pred, true, &prc);
-        if (prc) return prc;
-        if (next_started && (rc = enqueue(k + 1, 0, std::max(1, std::min(c->seq_depth, max_outer))))) return rc;
-      } else if (c->seq_next.announced && !scans_on_device) {
-        // the scan that will start the NEXT call: on its way to HBM and binned beside this call's last registration
-        so_icp_ctx::SeqNext& nx = c->seq_next;
-        nx.announced = false;
-        double pred[7];
-        pose_compose(r.guess, nx.delta, pred);
-        SeqRun rn;  // (a run record of its own, outside `runs`: the vector must not move under the references held here)
-        nx.scan = nx.next_scan; nx.n = nx.next_n;
-        rn.n = nx.n;
-        rn.query_waves = sweeps_query_waves(c, rn.n);
-        nx.slot = (slot_base + count) % so_icp_ctx::kStageSlots;
-        rn.slot = &c->seq_slot[nx.slot];
-        const void* one[1] = {nx.scan};
-        {  // (stage_scan() of the lambda above, for a scan that is not in `scans`; a failure only means "not staged ahead")
-          SeqRun& rr = rn;
-          rr.d_scan = nullptr; rr.binned = false; rr.needs_event = false;
-          so_icp_ctx::StageSlot& sl = *rr.slot;
-          bool ok = rr.n > 0;
-          if (ok && !sl.ev) ok = hipEventCreateWithFlags(&sl.ev, hipEventDisableTiming) == hipSuccess;
-          if (ok) ok = sl.dev.reserve((rr.n + 64) * 12) == hipSuccess && hipMemcpyAsync(sl.dev.p, one[0], rr.n * 12, hipMemcpyHostToDevice, c->seq_stream) == hipSuccess;
-          if (ok) { rr.d_scan = sl.dev.as<float>(); rr.needs_event = true; }
-          if (ok && !rr.query_waves && c->prebin) {  // (the table as the last binning of this call left it: clean, or not used here)
-            ok = sl.reserve_worklist(rr.n) == hipSuccess && c->sbin.log2 == bin_table_log2(rr.n);
-            if (ok) { rr.binned = bin_into_slot(c, rr.d_scan, rr.n, pred, c->seq_stream, c->sbin, sl); ok = rr.binned; }
-          }
-          if (ok && rr.needs_event) ok = hipEventRecord(sl.ev, c->seq_stream) == hipSuccess;
-          (void)hipGetLastError();
-          nx.staged = ok; nx.binned = rr.binned; nx.needs_event = rr.needs_event; nx.d_scan = rr.d_scan;
-        }
-      }
-      // this registration's reports
-      int last = 0;
-      for (int it = 0;; ++it) {
-        if ((rc = await(k, it))) return rc;
-        last = it;
-        if (c->h_ring[r.ring + (it & 1)]->reg_done || it + 1 >= max_outer) break;
-        if (it + 1 >= r.enq_iters) {
-          // it needs more outer iterations than were enqueued ahead: the chained registration behind it has found it unfinished
-          // and turned itself off (DevState::done_count); one iteration at a time from here, the next scan starts again afterwards
-          if (next_started) { next_started = false; runs[(size_t)k + 1].enqueued = false; c->timing.seq_chain_breaks++; }
-          if ((rc = enqueue(k, it + 1, it + 2))) return rc;
-        }
-      }
-      const DevState& H = *c->h_ring[r.ring + (last & 1)];
-      c->h_state = c->h_ring[r.ring + (last & 1)];
-      std::memset(st, 0, sizeof(*st));
-      st->flags = (r.slot && !scans_on_device ? SO_ICP_FLAG_STAGED_SCAN : 0u) | (r.binned ? SO_ICP_FLAG_BINNED_AHEAD : 0u) |
-                  (r.query_waves ? SO_ICP_FLAG_QUERY_WAVES : 0u) | (r.chained ? SO_ICP_FLAG_CHAINED : 0u);
-      if (c->have_hist) uncertainty_from_hist(c->prev_obs_hist, st->uncertainty);  // LidarSlam.cpp:47
-      st->pos_in_localmap[0] = r.pos[0]; st->pos_in_localmap[1] = r.pos[1]; st->pos_in_localmap[2] = r.pos[2];
-      st->laser_cloud_surf_from_map_num = r.count_5x5;
-      st->laser_cloud_surf_stack_num = (int32_t)r.n;
-      st->startup_count = c->startup_count;
-      double guess[7];
-      std::memcpy(guess, H.pose_in, sizeof(guess));  // (what the device formed for a chained registration; the host's own argument otherwise)
-      if (guesses_out) std::memcpy(guesses_out + 7 * (size_t)k, guess, sizeof(guess));
-      note_packing(c, H, r.mp, r.n);
-      if (!r.query_waves) c->knn_list_fits = ((H.bin_packed >> 21) & 0x1FFFFFull) + (H.bin_packed >> 42) <= (unsigned long long)kKnnBlocks * 4ull;
-      c->done_count_seen = H.done_count;
-      c->seq_depth = std::max(1, H.n_iterations);
-      for (const SeqRun::KnnEv& e : r.knn_ev) {  // sweeps that did real work (a launch behind the converged iteration was a no-op); they ended long ago
-        float ms = 0;
-        if (e.it < H.n_iterations && hipEventElapsedTime(&ms, e.a, e.b) == hipSuccess) {
-          c->timing.knn_ms_total += ms; c->timing.knn_launches++;
-          c->timing.knn_queries += r.query_waves ? (int64_t)r.n : (int64_t)(H.bin_packed & 0x1FFFFFull); c->timing.knn_map_points += c->view.n_points;
-        }
-      }
-      (void)hipGetLastError();
-      fill_result(c, H, guess, st, pose_out, true);
-      st->time_elapsed_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_icp).count();
-      c->timing.registrations++;
-      if (r.chained) {
-        c->timing.seq_chained++;
-        // the window was placed for the predicted guess: the actual one must lie in the same block (cube_stable saw to it)
-        const int* o = map_origin(c);
-        if (cube_coord(guess[0], o[0]) != r.pos[0] || cube_coord(guess[1], o[1]) != r.pos[1] || cube_coord(guess[2], o[2]) != r.pos[2])
-          return fail(c, SO_ICP_E_HIP, "so_icp_register_sequence: a chained guess left the map block its window was placed for");
-      }
-      if (k + 1 < count && !next_started && !runs[(size_t)k + 1].enqueued) {
-        // an ordinary start of the next scan, from the exact guess (after a broken chain: its copy and work list are where they were)
-        SeqRun& nx = runs[(size_t)k + 1];
-        double T[7], g[7];
-        chain_from(k, T); pose_compose(T, deltas + 7 * (size_t)(k + 1), g);
-        int prc = 0;
-        next_started = prepare(k + 1, g, false, &prc);
-        if (prc && prc != SO_ICP_NOT_ENOUGH_MAP_FEATURES) return prc;
-        if (next_started && (rc = enqueue(k + 1, 0, std::max(1, std::min(c->seq_depth, max_outer))))) return rc;
-        (void)nx;
-      }
-      started = next_started;
-      if (n_done) *n_done = k + 1;
-      continue;
-    }
-    // (after a plain registration: the next scan starts a chain of its own)
-    if (n_done) *n_done = k + 1;
-    started = false;
-    if (k + 1 < count) {
-      double T[7], g[7];
-      chain_from(k, T); pose_compose(T, deltas + 7 * (size_t)(k + 1), g);
-      if ((rc = stage_scan(k + 1, g))) return rc;
-      int prc = 0;
-      started = prepare(k + 1, g, false, &prc);
-      if (prc && prc != SO_ICP_NOT_ENOUGH_MAP_FEATURES) return prc;
-      if (started && (rc = enqueue(k + 1, 0, std::max(1, std::min(c->seq_depth, max_outer))))) return rc;
-    }
-  }
-  c->scan_staged = false;
-  c->ev_used = 0;  // (the timing events of this call are free again)
-  drain.ok = true;
-  return SO_ICP_OK;
+  SequenceCall call{c, count, scans, n_points, stride_bytes, scans_on_device, pose0, deltas, poses_out, guesses_out, stats, n_done};
+  return chained_path(c, count, scans_on_device, stride_bytes) ? call.run_chained() : call.run_unchained();
 }
 
 }  // extern "C"

@@ -34,7 +34,7 @@ static void stage_finish_direct(so_icp_ctx::StageSlot& sl) {
 // slot's scan buffer: a hipMalloc / hipFree is a device-wide synchronisation and must not sit in a registration's critical path,
 // where stage_prebin runs.  A failure only means "not binned ahead".
 static void stage_prebin_reserve(so_icp_ctx* c, so_icp_ctx::StageSlot& sl, size_t n) {
-  if (!c->prebin || !n || n >= ((size_t)1 << 21)) return;
+  if (!c->prebin || !n || n >= kMaxScanPoints) return;
   if (sl.reserve_worklist(n) != hipSuccess || c->pbin.reserve(bin_table_log2(n)) != hipSuccess) (void)hipGetLastError();
 }
 // Binning ahead (so_icp_ctx::prebin): scan_keys -> bin_offsets -> bin_place of a scan in HBM into the slot's pb_* buffers on queue `s`,
@@ -58,7 +58,7 @@ bool bin_into_slot(so_icp_ctx* c, const float* d_scan, size_t n, const double po
 static void stage_prebin(so_icp_ctx* c, so_icp_ctx::StageSlot& sl, const double* pose) {
   sl.prebinned = false;
   const size_t n = sl.n;
-  if (!c->prebin || !pose || !n || n >= ((size_t)1 << 21)) return;
+  if (!c->prebin || !pose || !n || n >= kMaxScanPoints) return;
   const uint32_t lg = bin_table_log2(n);
   const size_t m = n + 256;
   const bool ok = sl.pb_keys.cap >= m * 4 && sl.pb_vals.cap >= m * 4 && sl.pb_chunks.cap >= m * 4 && sl.pb_binned.cap >= m * 16 && sl.pb_ctr.cap >= 64 &&
