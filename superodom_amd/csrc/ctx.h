@@ -5,7 +5,9 @@
 //   sequence.cpp          so_icp_register_sequence, so_icp_sequence_announce_next
 //   batch.cpp             so_icp_register_batch
 //   reg_plan.h            what all three decide without a device: loop limits, query split, table and work-list sizes, window rule
-//   localization.cpp      so_icp_localization(_dev), de-skew, so_icp_transform_cloud, the pre-filter
+//   localization.cpp      so_icp_localization(_dev): one frame of LidarSLAM::Localization from a host or a resident scan
+//   prefilter.cpp         so_icp_prefilter_announce / _scan(_dev): adjustVoxelSize + VoxelGrid, decided on the device or on the host
+//   cloud_steps.cpp       so_icp_deskew_scan(_dev), so_icp_transform_cloud, so_icp_download_scan
 //   multi_gpu.cpp         RCCL, in-process groups, peer exchange, shard helpers
 //   localization_sequence.cpp, feature_extraction.cpp
 #pragma once
@@ -94,6 +96,10 @@ struct BinHashTable {
 static_assert(kOuterCap == SO_ICP_MAX_OUTER, "outer_limit (reg_plan.h) caps at the per-iteration statistics of so_icp_stats");
 
 struct InprocGroup;  // so_icp_comm_init_inprocess (multi_gpu.cpp)
+
+// Life of a stage slot (so_icp_stage_scan, staging.cpp): empty -> (queued: the copy thread owns it) -> ready -> in use by the registration
+// that consumes it -> empty; failed: the copy thread's error waits in the slot for the call that asks for the scan
+enum class StageState : int { kFailed = -1, kEmpty = 0, kQueued = 1, kReady = 2, kInUse = 3 };
 
 }  // namespace soicp::host
 
@@ -208,7 +214,7 @@ struct so_icp_ctx {
   struct StageSlot {
     const float* src = nullptr; size_t n = 0, stride = 0;  // identity of the staged host buffer
     DevBuf dev; float* pinned = nullptr; size_t pinned_cap = 0;
-    int state = 0;  // 0 empty, 1 queued (the copy thread owns it), 2 ready, 3 in use by the registration in flight, -1 failed
+    StageState state = StageState::kEmpty;
     unsigned long long seq = 0;          // announcement number (newer scans have larger ones)
     hipEvent_t ev = nullptr;             // direct path: end of the H2D copy on the copy stream
     bool ev_pending = false;             //   ... which may still be reading the caller's buffer
@@ -300,6 +306,13 @@ namespace soicp::host {
 
 // sets the text so_icp_last_error returns and passes `code` through
 inline int fail(so_icp_ctx* c, int code, const std::string& msg) { c->err = msg; return code; }
+// what a DeviceMap member returns (device_map.h: -1 out of memory / a full cube, -2 a HIP error, its text in c->err; else >= 0) as a C ABI code
+inline int map_status(int r) { return r >= 0 ? SO_ICP_OK : (r == -1 ? SO_ICP_E_NOMEM : SO_ICP_E_HIP); }
+// the stride rule of the entries that read float x y z records: 0 means packed (12 bytes); a multiple of 4
+inline int normalise_stride(so_icp_ctx* c, size_t* stride_bytes) {
+  if (*stride_bytes == 0) *stride_bytes = 12;
+  return *stride_bytes % 4 ? fail(c, SO_ICP_E_INVALID, "stride_bytes must be a multiple of 4") : SO_ICP_OK;
+}
 
 }  // namespace soicp::host
 

@@ -71,7 +71,7 @@ int map_count_5x5(const so_icp_ctx* c, const int pos[3]) { return c->dmap ? c->d
 const int* map_origin(const so_icp_ctx* c) { return c->dmap ? c->dmap->origin() : c->map.origin(); }
 
 int upload_map(so_icp_ctx* c) {
-  if (c->dmap) { const int rv = c->dmap->view(c->view, c->err); return rv == 0 ? SO_ICP_OK : (rv == -1 ? SO_ICP_E_NOMEM : SO_ICP_E_HIP); }
+  if (c->dmap) { const int rv = c->dmap->view(c->view, c->err); return map_status(rv); }
   if (c->uploaded_version == c->map.version()) return SO_ICP_OK;
   c->map.build_canonical(c->query_split ? 0 : c->cfg.rank, c->query_split ? 1 : c->cfg.world_size, c->cm);
   const CanonicalMap& m = c->cm;
@@ -640,8 +640,7 @@ hipStream_t aux_stream(so_icp_ctx* c) {
 }
 
 int upload_scan_impl(so_icp_ctx* c, const float* xyz, size_t n, size_t stride_bytes, DevBuf& dst, bool wait) {
-  if (stride_bytes == 0) stride_bytes = 12;
-  if (stride_bytes % 4) return fail(c, SO_ICP_E_INVALID, "stride_bytes must be a multiple of 4");
+  if (const int rc = normalise_stride(c, &stride_bytes)) return rc;
   HIP_TRY(c, dst.reserve((n + 64) * 12));
   if (!n) return SO_ICP_OK;
   if (stride_bytes == 12) {
@@ -890,12 +889,11 @@ int so_icp_map_shift(so_icp_ctx* c, const double t[3], int pos[3]) {
 }
 int so_icp_map_add_surf(so_icp_ctx* c, const float* xyz, size_t n, size_t stride_bytes) {
   if (!c || (!xyz && n)) return SO_ICP_E_INVALID;
-  if (stride_bytes == 0) stride_bytes = 12;
-  if (stride_bytes % 4) return fail(c, SO_ICP_E_INVALID, "stride_bytes must be a multiple of 4");
+  if (const int rc = normalise_stride(c, &stride_bytes)) return rc;
   if (c->dmap) {  // bin + VoxelGrid + index rebuild on the device (map_kernels.hip)
     HIP_TRY(c, hipSetDevice(c->cfg.device_id));
     const int r = c->dmap->add_surf_host(xyz, n, stride_bytes / 4, c->err);
-    if (r < 0) { group_abort(c); return r == -1 ? SO_ICP_E_NOMEM : SO_ICP_E_HIP; }
+    if (r < 0) { group_abort(c); return map_status(r); }
     const int xr = exchange_map_counts(c);
     return xr ? xr : r;
   }

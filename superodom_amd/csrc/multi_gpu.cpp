@@ -192,7 +192,7 @@ int reshard_for_resolution(so_icp_ctx* c, float line_res, float plane_res) {
     for (int k = 0; k < W; ++k) all[(size_t)k].assign(host.begin() + (long)(longest * (size_t)k), host.begin() + (long)(longest * (size_t)k + (size_t)len[(size_t)k]));
   }
   const int rc = c->dmap->reshard(all, line_res, plane_res, c->err);
-  if (rc < 0) return rc == -1 ? SO_ICP_E_NOMEM : SO_ICP_E_HIP;
+  if (rc < 0) return map_status(rc);
   c->uploaded_version = 0;
   return SO_ICP_OK;
 }

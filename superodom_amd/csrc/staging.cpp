@@ -14,10 +14,10 @@
 
 namespace soicp::host {
 
-// Slot life: empty -> (queued, copy thread) -> ready -> in use by the registration that consumes it -> empty.
-// Everything below runs under stage_mu: so_icp_stage_scan may come from another thread than the registration calls.
+// Slot life: StageState (ctx.h).  Everything below runs under stage_mu: so_icp_stage_scan may come from another thread than the
+// registration calls.
 static bool stage_any_queued(const so_icp_ctx* c) {
-  for (const so_icp_ctx::StageSlot& sl : c->stage) if (sl.state == 1) return true;
+  for (const so_icp_ctx::StageSlot& sl : c->stage) if (sl.state == StageState::kQueued) return true;
   return false;
 }
 // the copy of a direct slot has left the caller's buffer (host-side wait; a no-op in steady state: the copy was enqueued
@@ -29,6 +29,16 @@ static void stage_finish_direct(so_icp_ctx::StageSlot& sl) {
     sl.tail_stream = nullptr; sl.prebinned = false; sl.ev_pending = false;
   }
   if (sl.ev_pending) { (void)hipEventSynchronize(sl.ev); sl.ev_pending = false; }
+}
+// the slot holds an announcement of this very buffer
+static bool announces(const so_icp_ctx::StageSlot& sl, const float* xyz, size_t n, size_t stride_bytes) {
+  return sl.src == xyz && sl.n == n && sl.stride == stride_bytes;
+}
+// the slot's announcement is dropped: once the copy thread has let go of it and its copy has left the caller's buffer, it is empty
+static void retire_slot(std::unique_lock<std::mutex>& lk, so_icp_ctx* c, so_icp_ctx::StageSlot& sl) {
+  c->stage_cv.wait(lk, [&] { return sl.state != StageState::kQueued; });
+  stage_finish_direct(sl);
+  sl.src = nullptr; sl.state = StageState::kEmpty;
 }
 // the buffers stage_prebin needs for a scan of n points, reserved by the ANNOUNCING thread (so_icp_stage_scan, under stage_mu) next to the
 // slot's scan buffer: a hipMalloc / hipFree is a device-wide synchronisation and must not sit in a registration's critical path,
@@ -77,7 +87,7 @@ static hipError_t stage_issue_copy(so_icp_ctx* c, so_icp_ctx::StageSlot& sl) {
   sl.prebinned = false;
   const hipError_t e = hipMemcpyAsync(sl.dev.p, sl.src, sl.n * 12, hipMemcpyHostToDevice, c->copy_stream);
   if (e == hipSuccess) { sl.tail_stream = c->copy_stream; return e; }
-  sl.state = -1; sl.err = std::string("so_icp_stage_scan: ") + hipGetErrorString(e);
+  sl.state = StageState::kFailed; sl.err = std::string("so_icp_stage_scan: ") + hipGetErrorString(e);
   return e;
 }
 static hipError_t stage_tail(so_icp_ctx* c, so_icp_ctx::StageSlot& sl, const double* pose = nullptr) {
@@ -102,14 +112,14 @@ void stage_issue_deferred(so_icp_ctx* c, const double* prebin_pose) {
   if (!c->stage_started) return;
   std::lock_guard<std::mutex> lk(c->stage_mu);
   for (so_icp_ctx::StageSlot& sl : c->stage) {
-    if (sl.state == 2 && sl.deferred) { if (stage_issue_copy(c, sl) == hipSuccess) (void)stage_tail(c, sl, prebin_pose); }
-    else if (sl.state == 2 && sl.tail_stream) (void)stage_tail(c, sl, prebin_pose);
+    if (sl.state == StageState::kReady && sl.deferred) { if (stage_issue_copy(c, sl) == hipSuccess) (void)stage_tail(c, sl, prebin_pose); }
+    else if (sl.state == StageState::kReady && sl.tail_stream) (void)stage_tail(c, sl, prebin_pose);
   }
 }
 void stage_issue_deferred_copy(so_icp_ctx* c) {  // (the registration in flight: copy now, stage_issue_deferred for the rest later)
   if (!c->stage_started) return;
   std::lock_guard<std::mutex> lk(c->stage_mu);
-  for (so_icp_ctx::StageSlot& sl : c->stage) if (sl.state == 2 && sl.deferred) (void)stage_issue_copy(c, sl);
+  for (so_icp_ctx::StageSlot& sl : c->stage) if (sl.state == StageState::kReady && sl.deferred) (void)stage_issue_copy(c, sl);
 }
 static bool host_range_registered(const so_icp_ctx* c, const void* p, size_t bytes) {
   const char* q = static_cast<const char*>(p);
@@ -132,7 +142,7 @@ static void stage_worker(so_icp_ctx* c) {
         bool waiting = false;
         auto deadline = now + std::chrono::hours(1);
         for (so_icp_ctx::StageSlot& q : c->stage) {
-          if (!(q.state == 2 && q.deferred)) continue;
+          if (!(q.state == StageState::kReady && q.deferred)) continue;
           const auto due = q.t_announced + std::chrono::microseconds(300);
           if (due <= now) (void)stage_issue(c, q); else { waiting = true; deadline = std::min(deadline, due); }
         }
@@ -163,7 +173,7 @@ static void stage_worker(so_icp_ctx* c) {
       }
       lk.lock();
       if (!got) {
-        auto any_deferred = [&] { for (const so_icp_ctx::StageSlot& q : c->stage) if (q.state == 2 && q.deferred) return true; return false; };
+        auto any_deferred = [&] { for (const so_icp_ctx::StageSlot& q : c->stage) if (q.state == StageState::kReady && q.deferred) return true; return false; };
         c->stage_parked.store(true);
         c->stage_cv.wait(lk, [&] { return c->stage_quit || stage_any_queued(c) || any_deferred(); });
         c->stage_parked.store(false);
@@ -172,7 +182,7 @@ static void stage_worker(so_icp_ctx* c) {
     }
     if (c->stage_quit) return;
     so_icp_ctx::StageSlot* pick = nullptr;  // oldest queued announcement first
-    for (so_icp_ctx::StageSlot& q : c->stage) if (q.state == 1 && (!pick || q.seq < pick->seq)) pick = &q;
+    for (so_icp_ctx::StageSlot& q : c->stage) if (q.state == StageState::kQueued && (!pick || q.seq < pick->seq)) pick = &q;
     so_icp_ctx::StageSlot& sl = *pick;
     const float* src = sl.src; const size_t n = sl.n, stride = sl.stride; const unsigned long long seq = sl.seq;
     lk.unlock();
@@ -200,7 +210,7 @@ static void stage_worker(so_icp_ctx* c) {
     }
     if (e != hipSuccess) err = std::string("so_icp_stage_scan: ") + hipGetErrorString(e);
     lk.lock();
-    if (sl.seq == seq && sl.state == 1) { sl.state = err.empty() ? 2 : -1; sl.err = err; }
+    if (sl.seq == seq && sl.state == StageState::kQueued) { sl.state = err.empty() ? StageState::kReady : StageState::kFailed; sl.err = err; }
     c->stage_cv.notify_all();
   }
 }
@@ -216,36 +226,32 @@ static const float* take_staged(so_icp_ctx* c, const float* xyz, size_t n, size_
   if (!c->stage_started) return nullptr;
   so_icp_ctx::StageSlot* best = nullptr;
   for (so_icp_ctx::StageSlot& sl : c->stage) {
-    if (sl.state == 0 || sl.state == 3 || sl.src != xyz || sl.n != n || sl.stride != stride_bytes) continue;
+    if (sl.state == StageState::kEmpty || sl.state == StageState::kInUse || !announces(sl, xyz, n, stride_bytes)) continue;
     if (sl.seq < c->stage_consumed_seq) {
       // announced before a scan that has been consumed since: its frame was skipped, and the caller may have refilled the
       // buffer meanwhile (allowed once a later so_icp_stage_scan has returned) -- never served
-      c->stage_cv.wait(lk, [&] { return sl.state != 1; });
-      stage_finish_direct(sl);
-      sl.src = nullptr; sl.state = 0;
+      retire_slot(lk, c, sl);
       continue;
     }
     if (!best || sl.seq > best->seq) best = &sl;
   }
   if (!best) return nullptr;
   for (so_icp_ctx::StageSlot& sl : c->stage) {  // older announcements of the same buffer: superseded
-    if (&sl == best || sl.state == 0 || sl.state == 3 || sl.src != xyz || sl.n != n || sl.stride != stride_bytes) continue;
-    c->stage_cv.wait(lk, [&] { return sl.state != 1; });
-    stage_finish_direct(sl);
-    sl.src = nullptr; sl.state = 0;
+    if (&sl == best || sl.state == StageState::kEmpty || sl.state == StageState::kInUse || !announces(sl, xyz, n, stride_bytes)) continue;
+    retire_slot(lk, c, sl);
   }
   so_icp_ctx::StageSlot& sl = *best;
-  if (sl.state == 1) {
+  if (sl.state == StageState::kQueued) {
     const auto t0 = std::chrono::steady_clock::now();
-    c->stage_cv.wait(lk, [&] { return sl.state != 1; });
+    c->stage_cv.wait(lk, [&] { return sl.state != StageState::kQueued; });
     c->timing.stage_wait_ms_total += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
   }
-  const int state = sl.state;
+  const StageState state = sl.state;
   sl.src = nullptr;
-  if (state == 2) {
+  if (state == StageState::kReady) {
     if (sl.deferred) {  // (no registration came by to enqueue it: the first scan of a run)
       sl.src = xyz;
-      if (stage_issue(c, sl) != hipSuccess) { c->err = sl.err; *rc = SO_ICP_E_HIP; sl.src = nullptr; sl.state = 0; return nullptr; }
+      if (stage_issue(c, sl) != hipSuccess) { c->err = sl.err; *rc = SO_ICP_E_HIP; sl.src = nullptr; sl.state = StageState::kEmpty; return nullptr; }
       sl.src = nullptr;
     }
     if (sl.tail_stream) (void)stage_tail(c, sl);  // (no registration finished what it had begun: not binned ahead)
@@ -257,11 +263,11 @@ static const float* take_staged(so_icp_ctx* c, const float* xyz, size_t n, size_
       (void)hipGetLastError();
       stage_finish_direct(sl);  // (cannot order the streams on the device: wait here)
     }
-    sl.state = 3; c->stage_in_use = &sl; c->stage_consumed_seq = sl.seq;
+    sl.state = StageState::kInUse; c->stage_in_use = &sl; c->stage_consumed_seq = sl.seq;
     return sl.dev.as<float>();  // (so_icp_stage_scan -- possibly on another thread -- leaves a slot in use alone)
   }
-  sl.state = 0;
-  if (state == -1) { c->err = sl.err; *rc = SO_ICP_E_HIP; }
+  sl.state = StageState::kEmpty;
+  if (state == StageState::kFailed) { c->err = sl.err; *rc = SO_ICP_E_HIP; }
   return nullptr;
 }
 // A call that reads (xyz, n, stride) itself -- map seeding -- without consuming a staged copy of it: the copy is dropped, so that
@@ -270,17 +276,15 @@ void drop_staged(so_icp_ctx* c, const float* xyz, size_t n, size_t stride_bytes)
   std::unique_lock<std::mutex> lk(c->stage_mu);
   if (!c->stage_started) return;
   for (so_icp_ctx::StageSlot& sl : c->stage) {
-    if (sl.state == 0 || sl.state == 3 || sl.src != xyz || sl.n != n || sl.stride != stride_bytes) continue;
-    c->stage_cv.wait(lk, [&] { return sl.state != 1; });
-    stage_finish_direct(sl);
-    sl.src = nullptr; sl.state = 0;
+    if (sl.state == StageState::kEmpty || sl.state == StageState::kInUse || !announces(sl, xyz, n, stride_bytes)) continue;
+    retire_slot(lk, c, sl);
   }
 }
 void release_staged(so_icp_ctx* c) {
   if (!c->stage_in_use) return;
   std::lock_guard<std::mutex> lk(c->stage_mu);
   c->stage_in_use->ev_pending = false;  // (the registration that read the slot has completed, and the copy before it)
-  c->stage_in_use->state = 0;
+  c->stage_in_use->state = StageState::kEmpty;
   c->stage_in_use = nullptr;
 }
 
@@ -319,8 +323,8 @@ int so_icp_stage_scan(so_icp_ctx* c, const float* xyz, size_t n, size_t stride_b
     // The same buffer announced again supersedes its older copy (so_icp.h: this is also how a caller takes a staged buffer
     // back -- so_icp_stage_cancel); failed slots are recycled.
     for (so_icp_ctx::StageSlot& sl : c->stage) {
-      if (sl.state == 1 && sl.src == xyz) c->stage_cv.wait(lk, [&] { return sl.state != 1; });
-      if ((sl.state == 2 && sl.src == xyz) || sl.state == -1) { stage_finish_direct(sl); sl.src = nullptr; sl.state = 0; }
+      if (sl.state == StageState::kQueued && sl.src == xyz) c->stage_cv.wait(lk, [&] { return sl.state != StageState::kQueued; });
+      if ((sl.state == StageState::kReady && sl.src == xyz) || sl.state == StageState::kFailed) retire_slot(lk, c, sl);
     }
     if (n == 0 && stride_bytes == SIZE_MAX) return SO_ICP_OK;  // (so_icp_stage_cancel: withdraw only)
     // Slot: an empty one; else a ready copy that was announced BEFORE the scan consumed last (its frame was skipped: it would
@@ -330,10 +334,10 @@ int so_icp_stage_scan(so_icp_ctx* c, const float* xyz, size_t n, size_t stride_b
     // own registration call).
     so_icp_ctx::StageSlot* pick = nullptr;
     bool in_flight = false;
-    for (so_icp_ctx::StageSlot& sl : c->stage) { if (sl.state == 0 && !pick) pick = &sl; in_flight = in_flight || sl.state == 3; }
+    for (so_icp_ctx::StageSlot& sl : c->stage) { if (sl.state == StageState::kEmpty && !pick) pick = &sl; in_flight = in_flight || sl.state == StageState::kInUse; }
     if (!pick)
       for (so_icp_ctx::StageSlot& sl : c->stage)
-        if (sl.state == 2 && (sl.seq < c->stage_consumed_seq || !in_flight) && (!pick || sl.seq < pick->seq)) pick = &sl;
+        if (sl.state == StageState::kReady && (sl.seq < c->stage_consumed_seq || !in_flight) && (!pick || sl.seq < pick->seq)) pick = &sl;
     if (!pick) { c->timing.stage_declined++; return SO_ICP_STAGE_DECLINED; }
     so_icp_ctx::StageSlot& sl = *pick;
     stage_finish_direct(sl);  // (an evicted copy must have left its caller's buffer)
@@ -341,15 +345,15 @@ int so_icp_stage_scan(so_icp_ctx* c, const float* xyz, size_t n, size_t stride_b
     sl.prebinned = false;  // (the slot's work list belongs to the scan it held before)
     if (stride_bytes == 12 && n && host_range_registered(c, xyz, n * 12)) {
       // registered (pinned) host memory, packed xyz: no pack, no copy thread -- the DMA reads the caller's buffer itself
-      sl.state = 0;  // (until the copy is enqueued: an error below leaves the slot empty)
+      sl.state = StageState::kEmpty;  // (until the copy is enqueued: an error below leaves the slot empty)
       HIP_TRY(c, sl.dev.reserve((n + 64) * 12));
       stage_prebin_reserve(c, sl, n);  // (what the binning ahead of this scan will need: allocated here, off the registration's path)
       if (!sl.ev) HIP_TRY(c, hipEventCreateWithFlags(&sl.ev, hipEventDisableTiming));
-      sl.state = 2;
+      sl.state = StageState::kReady;
       sl.deferred = true; sl.t_announced = std::chrono::steady_clock::now(); queued = true; dma_only = true;  // (the copy thread is the time-out)
       c->timing.staged_direct++;
     } else {
-      sl.state = 1; queued = true;
+      sl.state = StageState::kQueued; queued = true;
       c->timing.staged_copied++;
     }
   }
