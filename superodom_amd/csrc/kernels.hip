@@ -1542,9 +1542,9 @@ __device__ __forceinline__ bool eval_slot_active(const DevState* st, int slot) {
 }
 
 // The Ceres-equivalent LM controller plus the outer ICP bookkeeping (LidarSlam.cpp:119-148, 242-251).
-// Executed by ONE thread on an LDS copy of the controller state.
+// Two forms on an LDS copy of the controller state: lm_control (one thread) and lm_control_wave (one wavefront).
 struct LmCtl {       // LDS copy of the DevState fields the controller reads (prefetched with the state: no global
-  double T[7];       // round trips inside the single-thread controller)
+  double T[7];       // round trips inside the controller)
   int32_t lm_max, outer_iter, max_outer, pad;
 };
 
@@ -1572,32 +1572,6 @@ __device__ __forceinline__ int lm_solve_finished(DevState* st, const LmCtl& ctl,
   return 0;
 }
 
-__device__ __forceinline__ int lm_control_regs(int slot, DevState* st, LmState& S, const LmSums& sums, const LmCtl& ctl, bool persist,
-                                               int* reg_done_out = nullptr) {
-  if (reg_done_out) *reg_done_out = 0;
-  // persist (solve_kernel): the next pose travels in the hand-off record and nobody reads lm_more, so a pass that is
-  // followed by another one issues no global store at all (a store would have to drain before the next barrier)
-  int more;
-  double unused_pose[7];
-  double* next_pose = persist ? unused_pose : st->eval_pose;
-  if (slot == 0) more = lm_begin(S, ctl.T, sums, ctl.lm_max, next_pose);
-#ifdef SO_LM_STAMPS
-  else more = lm_feed(S, sums, next_pose, slot == 1 ? st->dbg : nullptr);
-#else
-  else more = lm_feed(S, sums, next_pose);
-#endif
-  if (!persist || !more) st->lm_more = more;
-  if (more) return 1;
-  const int rd = lm_solve_finished(st, ctl, S.x, S.count, S.lm_iterations, S.num_successful, S.termination, S.initial_cost, S.x_cost, sums);
-  if (rd) {
-    if (reg_done_out) *reg_done_out = 1;
-    const bool have = S.count >= 1.0;
-    for (int i = 0; i < 36; ++i) st->JtJ[i] = have ? S.H[i] : 0.0;
-    for (int i = 0; i < 6; ++i) st->Jtr[i] = have ? S.g[i] : 0.0;
-  }
-  return 0;
-}
-
 typedef unsigned int u4v __attribute__((ext_vector_type(4)));
 // 16-byte agent-scope (sc1) store / load: one access, bypassing the non-coherent per-XCD L2 state [MI355X guide, G16]
 __device__ __forceinline__ void store16_sc1(u4v* p, u4v v) { asm volatile("global_store_dwordx4 %0, %1, off sc1" ::"v"(p), "v"(v) : "memory"); }
@@ -1616,61 +1590,52 @@ __device__ __forceinline__ u4v load16_sys(const u4v* p) {
 }
 
 #define SO_LM_INLINE __forceinline__  // (out of line, the callee-saved registers go through scratch: +1 us per call)
-// hand / want / pose_out (persistent solve): the controller's thread publishes the hand-off record {next pose, more?}
-// straight from its registers, BEFORE the state goes back to LDS -- the other workgroups are already evaluating the
-// next pose while this thread is still tidying up.
-__device__ SO_LM_INLINE int lm_control(int slot, DevState* st, LmState& S_lds, const LmSums& sums_lds, const LmCtl& ctl, bool persist = false,
-                                       u4v* hand = nullptr, unsigned long long want = 0, double* pose_out = nullptr, int* reg_done_out = nullptr) {
-  // register copies: the controller is one thread's serial fp64 chain, and every LDS round trip inside it (~100 cycles,
-  // nothing to overlap with) would sit on the critical path of the whole device
-  // (the sums stay in LDS: they are read once, where a successful step adopts them; H is symmetric: only its upper
-  //  triangle lives in registers, the mirror image is rebuilt on the way out -- the full state plus the sums would not
-  //  fit the 256 architectural registers and the spill traffic would sit on the same critical path)
+// dst <- src between the LDS home of the controller state and one thread's registers.  H is symmetric: only its upper triangle
+// is read, the mirror image is rebuilt on the way -- the full state plus the sums would not fit the 256 architectural registers
+// and the spill traffic would sit on the controller's critical path.
+__device__ __forceinline__ void copy_lm_state(LmState& dst, const LmState& src) {
+#pragma unroll
+  for (int i = 0; i < 7; ++i) { dst.x[i] = src.x[i]; dst.cand[i] = src.cand[i]; }
+#pragma unroll
+  for (int i = 0; i < 6; ++i) {
+    dst.g[i] = src.g[i]; dst.scale[i] = src.scale[i]; dst.diag[i] = src.diag[i];
+#pragma unroll
+    for (int j = i; j < 6; ++j) { const double h = src.H[6 * i + j]; dst.H[6 * i + j] = h; dst.H[6 * j + i] = h; }
+  }
+  dst.x_cost = src.x_cost; dst.x_norm = src.x_norm; dst.inv_radius = src.inv_radius; dst.decrease_factor = src.decrease_factor;
+  dst.inv_model_cost_change = src.inv_model_cost_change; dst.step_norm = src.step_norm; dst.cand_norm = src.cand_norm;
+  dst.model_cost_change = src.model_cost_change; dst.initial_cost = src.initial_cost; dst.count = src.count;
+  dst.iter = src.iter; dst.max_iter = src.max_iter; dst.reuse_diagonal = src.reuse_diagonal; dst.invalid_steps = src.invalid_steps;
+  dst.num_successful = src.num_successful; dst.termination = src.termination; dst.done = src.done; dst.lm_iterations = src.lm_iterations;
+}
+// The one-thread controller (the per-evaluation launches and lm_step_kernel): lm_solver.h on register copies of the state, the
+// next pose to st->eval_pose, "another evaluation follows" to st->lm_more; a solve that ends goes through lm_solve_finished.
+__device__ SO_LM_INLINE int lm_control(int slot, DevState* st, LmState& S_lds, const LmSums& sums_lds, const LmCtl& ctl) {
+  // register copies: the controller is one thread's serial fp64 chain, and every LDS round trip inside it (~100 cycles, nothing to
+  // overlap with) would sit on the critical path of the whole device (the sums stay in LDS: read once, where a successful step adopts them)
   LmState S;
-#pragma unroll
-  for (int i = 0; i < 7; ++i) { S.x[i] = S_lds.x[i]; S.cand[i] = S_lds.cand[i]; }
-#pragma unroll
-  for (int i = 0; i < 6; ++i) {
-    S.g[i] = S_lds.g[i]; S.scale[i] = S_lds.scale[i]; S.diag[i] = S_lds.diag[i];
-#pragma unroll
-    for (int j = i; j < 6; ++j) { S.H[6 * i + j] = S_lds.H[6 * i + j]; S.H[6 * j + i] = S.H[6 * i + j]; }
+  copy_lm_state(S, S_lds);
+  int more;
+  if (slot == 0) more = lm_begin(S, ctl.T, sums_lds, ctl.lm_max, st->eval_pose);
+#ifdef SO_LM_STAMPS
+  else more = lm_feed(S, sums_lds, st->eval_pose, slot == 1 ? st->dbg : nullptr);
+#else
+  else more = lm_feed(S, sums_lds, st->eval_pose);
+#endif
+  st->lm_more = more;
+  if (!more && lm_solve_finished(st, ctl, S.x, S.count, S.lm_iterations, S.num_successful, S.termination, S.initial_cost, S.x_cost, sums_lds)) {
+    const bool have = S.count >= 1.0;  // the registration is over too: the final normal equations
+    for (int i = 0; i < 36; ++i) st->JtJ[i] = have ? S.H[i] : 0.0;
+    for (int i = 0; i < 6; ++i) st->Jtr[i] = have ? S.g[i] : 0.0;
   }
-  S.x_cost = S_lds.x_cost; S.x_norm = S_lds.x_norm; S.inv_radius = S_lds.inv_radius; S.decrease_factor = S_lds.decrease_factor;
-  S.inv_model_cost_change = S_lds.inv_model_cost_change; S.step_norm = S_lds.step_norm; S.cand_norm = S_lds.cand_norm;
-  S.model_cost_change = S_lds.model_cost_change; S.initial_cost = S_lds.initial_cost; S.count = S_lds.count;
-  S.iter = S_lds.iter; S.max_iter = S_lds.max_iter; S.reuse_diagonal = S_lds.reuse_diagonal; S.invalid_steps = S_lds.invalid_steps;
-  S.num_successful = S_lds.num_successful; S.termination = S_lds.termination; S.done = S_lds.done; S.lm_iterations = S_lds.lm_iterations;
-  const int more_ = lm_control_regs(slot, st, S, sums_lds, ctl, persist, reg_done_out);
-  if (hand) {
-#pragma unroll
-    for (int k = 0; k < 8; ++k) {
-      const unsigned long long val = (k < 7) ? (unsigned long long)__double_as_longlong(S.cand[k < 7 ? k : 0]) : (unsigned long long)more_;
-      const u4v v = {(unsigned int)val, (unsigned int)(val >> 32), (unsigned int)want, (unsigned int)(want >> 32)};
-      store16_sc1(hand + k, v);
-    }
-#pragma unroll
-    for (int k = 0; k < 7; ++k) pose_out[k] = S.cand[k];
-  }
-#pragma unroll
-  for (int i = 0; i < 7; ++i) { S_lds.x[i] = S.x[i]; S_lds.cand[i] = S.cand[i]; }
-#pragma unroll
-  for (int i = 0; i < 6; ++i) {
-    S_lds.g[i] = S.g[i]; S_lds.scale[i] = S.scale[i]; S_lds.diag[i] = S.diag[i];
-#pragma unroll
-    for (int j = i; j < 6; ++j) { S_lds.H[6 * i + j] = S.H[6 * i + j]; S_lds.H[6 * j + i] = S.H[6 * i + j]; }
-  }
-  S_lds.x_cost = S.x_cost; S_lds.x_norm = S.x_norm; S_lds.inv_radius = S.inv_radius; S_lds.decrease_factor = S.decrease_factor;
-  S_lds.inv_model_cost_change = S.inv_model_cost_change; S_lds.step_norm = S.step_norm; S_lds.cand_norm = S.cand_norm;
-  S_lds.model_cost_change = S.model_cost_change; S_lds.initial_cost = S.initial_cost; S_lds.count = S.count;
-  S_lds.iter = S.iter; S_lds.max_iter = S.max_iter; S_lds.reuse_diagonal = S.reuse_diagonal; S_lds.invalid_steps = S.invalid_steps;
-  S_lds.num_successful = S.num_successful; S_lds.termination = S.termination; S_lds.done = S.done; S_lds.lm_iterations = S.lm_iterations;
+  copy_lm_state(S_lds, S);
 #ifdef SO_LM_STAMPS
   if (slot == 1) st->dbg[7] = wall_clock64();
 #endif
-  return more_;
+  return more;
 }
 
-// ---- Round 5: the controller across the lanes of ONE wavefront (persistent solve, single registration).
+// ---- Round 5: the controller across the lanes of ONE wavefront (persistent solve, single and batched).
 // The one-thread controller above is an instruction stream of ~750 fp64 operations and LDS moves on one lane -- 3.7 us per pass
 // (in-kernel stamps), 2.5 of them in front of the hand-off every other workgroup is waiting for.  Most of that stream is WIDE
 // work done element after element: ~70 state words in and out of LDS, 27 sums unpacked, 21 entries scaled twice, six
@@ -1679,8 +1644,8 @@ __device__ SO_LM_INLINE int lm_control(int slot, DevState* st, LmState& S_lds, c
 // the six Jacobi scale factors one sqrt + division, the hand-off one store.  What is a dependent chain -- the 6x6 Cholesky
 // (six pivots through rsqrt), the substitutions, the model cost change, the quaternion update -- stays the code of
 // lm_solver.h, run by every lane on the same (gathered) operands, so every element goes through the operations of the
-// one-thread controller in the same order: identical bits (the batched solve and the per-evaluation launches keep the
-// one-thread form; tests/test_gpu_configs.py compares them bit for bit on registrations, tests/test_gpu_lm_scripts.py branch by
+// one-thread controller in the same order: identical bits (the per-evaluation launches and lm_step_kernel keep the
+// one-thread form, the batched solve runs this one; tests/test_gpu_configs.py compares them bit for bit on registrations, tests/test_gpu_lm_scripts.py branch by
 // branch on scripted sums).  The state's home is the LDS copy; what the next
 // lm_feed needs beyond the sums (lm_after_candidate) and the store-back run AFTER the hand-off has been published.
 __device__ __forceinline__ int lm_control_wave(int slot, DevState* st, LmState& S, const LmSums& sums, const LmCtl& ctl, double* gather /* LDS, >= 56 doubles */,
@@ -2041,8 +2006,127 @@ struct CorrCache {
 };
 enum { kPassNotLast = 0, kPassMore = 1, kPassDone = 2, kPassSums = 3 };
 
-// One evaluation pass of this workgroup at `pose`: accumulate, reduce, hand off.  Returns kPassNotLast in every
-// workgroup but the one that arrives last; that one reduces the partial records and (fuse_lm) runs the LM controller:
+// phase stamps of a pass (PROF with SOICP_ABLATE & 128), written to st->dbg by the pass's finisher
+struct PassStamps { unsigned long long begin = 0, loop = 0, red = 0, arrived = 0, loaded = 0, sums = 0, ctl = 0; };
+// word3 "records arrived -> loaded": the single registration's pushed hand-over has no such phase (its fit record keeps
+// solve_kernel's "kernel entry -> first pass begins" there)
+template <bool FIT>
+__device__ __forceinline__ void store_stamps(DevState* st, const PassStamps& T, bool word3) {
+  const unsigned long long t_lm = wall_clock64();
+  unsigned long long* d = st->dbg + (FIT ? 0 : 8);
+  d[0] = T.loop - T.begin; d[1] = T.red - T.loop; d[2] = T.arrived - T.red; if (word3) d[3] = T.loaded - T.arrived; d[4] = T.sums - T.loaded;
+  d[5] = t_lm - T.sums; d[6] = t_lm - T.begin; d[7] = T.ctl - T.sums;
+}
+// ---- The hand-over of the per-evaluation launches (eval_kernel; see eval_pass for the return codes): this workgroup's record
+// `mine` is stored and counted; workgroup 0 waits for the count, adds the records and runs lm_control (st->lm_more and
+// st->eval_pose tell the next launch what to do) or, !fuse_lm, leaves the sums in `out`.
+template <bool FIT, bool PROF>
+__device__ __forceinline__ int hand_over_ticketed(int slot, int fuse_lm, double mine, DevState* __restrict__ st, const EvalParams& ep,
+                                                  double* __restrict__ partials, uint32_t* __restrict__ ticket, int32_t* __restrict__ hist,
+                                                  LmSums* __restrict__ out, EvalShared& sh, PassStamps& T) {
+  const int tid = threadIdx.x;
+  const int abl = PROF ? ep.ablate : 0;
+  const bool stamp = PROF && (abl & 128) != 0;
+  // The record goes to the finisher WITHOUT release/acquire fences (each costs microseconds on gfx950): the 29
+  // partial sums are 8-byte agent-scope relaxed atomic stores (write-through, sc1), drained with vmcnt(0) by the
+  // storing wave before the arrival ticket; the consumer reads them with agent-scope relaxed atomic loads
+  // (sc1: served by L2, never a stale L1 line).  [MI355X guide, G16 "8-B agent atomics both sides"]
+  if (tid < kNAcc)
+    __hip_atomic_store(&partials[(size_t)tid * kPartStride + blockIdx.x], mine, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+  if (FIT && tid >= 32 && tid < 48 && sh.lh[tid - 32])  // histograms: device-scope atomics on 16 replicas, visible before the ticket
+    __hip_atomic_fetch_add(&hist[(blockIdx.x % kHistReplicas) * kHistStride + (tid - 32)], sh.lh[tid - 32], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+  __syncthreads();
+  if (stamp) T.red = wall_clock64();
+  // Arrival: one fire-and-forget add per workgroup, spread over 16 counters on separate lines (256 adds on ONE word
+  // serialise for ~2 us); workgroup 0 is the designated finisher and polls the 16 counters with one 16-lane load.
+  if (tid == 0) __hip_atomic_fetch_add(&ticket[(blockIdx.x & (kArriveCounters - 1)) * kArriveStrideWords], 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+  if (blockIdx.x != 0) return kPassNotLast;
+  if (tid < 64) {
+    const uint32_t lanes = kArriveCounters;
+    const uint32_t expect = (tid < (int)lanes) ? (gridDim.x + lanes - 1u - (uint32_t)tid) / lanes : 0u;  // workgroups b with b % 16 == tid
+    const unsigned long long t0 = wall_clock64();
+    bool ok = false;
+    for (;;) {
+      uint32_t v = 0;
+      if (tid < (int)lanes) v = __hip_atomic_load(&ticket[tid * kArriveStrideWords], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+      if (__ballot(v != expect) == 0ull) { ok = true; break; }
+      if (wall_clock64() - t0 > ep.timeout_ticks) break;  // give up instead of hanging the device (EvalParams::timeout_ticks)
+    }
+    if (tid < (int)lanes) __hip_atomic_store(&ticket[tid * kArriveStrideWords], 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);  // re-arm
+    if (tid == 0) sh.is_last = ok;
+  }
+  __syncthreads();
+  if (!sh.is_last) return kPassNotLast;  // timeout: the solve is abandoned, the host reports the missing publication
+  if (stamp) T.arrived = wall_clock64();
+  // thread b fetches workgroup b's record from the transposed table partials[a][b] (coalesced: 4 lines per wave
+  // load).  The compiler serialises agent-scope atomic loads with a vmcnt(0) after each (6 us measured), so the 29
+  // sc1 loads are issued back to back, the controller state is fetched behind them, and ONE wait covers all.
+  {
+    constexpr int kRec = (SO_SOLVE_BLOCKS + 255) / 256;  // records per thread
+    double r[kRec][kNAcc];
+    bool have[kRec];
+#pragma unroll
+    for (int q = 0; q < kRec; ++q) {
+      have[q] = (uint32_t)(tid + 256 * q) < gridDim.x;  // no divergence around the asm: a register copy before the wait would read garbage
+      const double* rec = partials + (have[q] ? tid + 256 * q : 0);
+#pragma unroll
+      for (int a = 0; a < kNAcc; ++a)
+        asm volatile("global_load_dwordx2 %0, %1, off sc1" : "=v"(r[q][a]) : "v"(rec + a * kPartStride) : "memory");
+    }
+    if (fuse_lm) {  // (coherent loads: cheap insurance, one word per thread)
+      if (tid < (int)(sizeof(LmState) / 8))
+        reinterpret_cast<double*>(&sh.S)[tid] = __hip_atomic_load(reinterpret_cast<const double*>(&st->S) + tid, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+      load_ctl(sh.ctl, st, tid, 128);
+    }
+#pragma unroll
+    for (int q = 0; q < kRec; ++q)
+      asm volatile("s_waitcnt vmcnt(0)"
+                   : "+v"(r[q][0]), "+v"(r[q][1]), "+v"(r[q][2]), "+v"(r[q][3]), "+v"(r[q][4]), "+v"(r[q][5]), "+v"(r[q][6]), "+v"(r[q][7]),
+                     "+v"(r[q][8]), "+v"(r[q][9]), "+v"(r[q][10]), "+v"(r[q][11]), "+v"(r[q][12]), "+v"(r[q][13]), "+v"(r[q][14]),
+                     "+v"(r[q][15]), "+v"(r[q][16]), "+v"(r[q][17]), "+v"(r[q][18]), "+v"(r[q][19]), "+v"(r[q][20]), "+v"(r[q][21]),
+                     "+v"(r[q][22]), "+v"(r[q][23]), "+v"(r[q][24]), "+v"(r[q][25]), "+v"(r[q][26]), "+v"(r[q][27]), "+v"(r[q][28])
+                   :: "memory");
+#pragma unroll
+    for (int a = 0; a < kNAcc; ++a) {
+      double v = have[0] ? r[0][a] : 0.0;
+#pragma unroll
+      for (int q = 1; q < kRec; ++q) v += have[q] ? r[q][a] : 0.0;  // fixed order: record tid, tid + 256, ...
+      sh.red[tid][a] = v;
+    }
+  }
+  __syncthreads();
+  if (stamp) T.loaded = wall_clock64();
+  const double total = reduce_records(sh.red, sh.part, tid);
+  double* o = reinterpret_cast<double*>(&sh.sums);
+  if (tid < kNAcc) {
+    o[tid] = total;  // cost, count, Jtr[6], JtJ[21]
+  } else if (tid >= 32 && tid < 48) {
+    int h = 0;
+#pragma unroll
+    for (int r = 0; r < kHistReplicas; ++r)
+      h += __hip_atomic_load(&hist[r * kHistStride + (tid - 32)], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    o[kNAcc + (tid - 32)] = (double)h;
+  }
+  __syncthreads();
+  copy_words(reinterpret_cast<double*>(out), o, (int)(sizeof(LmSums) / 8), tid, 256);
+  if (stamp) T.sums = wall_clock64();
+  if (!fuse_lm) return kPassSums;  // sharded map: the sums are all-reduced first, lm_step_kernel runs the controller
+  if (tid == 0) sh.more = (abl & 32) ? 1 : lm_control(slot, st, sh.S, sh.sums, sh.ctl);  // sh.S / sh.ctl arrived with the partials
+  __syncthreads();
+  if (stamp) T.ctl = wall_clock64();
+  // the solve is over: clear the histogram replicas for the next outer iteration (ResetDistanceParameters, LidarSlam.cpp:847-852)
+  if (!sh.more) { hist[tid] = 0; hist[256 + tid] = 0; }
+  if (tid < (int)(sizeof(LmState) / 8))
+    __hip_atomic_store(reinterpret_cast<double*>(&st->S) + tid, reinterpret_cast<const double*>(&sh.S)[tid], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+  if (!sh.more) publish_state(st, ep, sh.ctl.outer_iter, tid, 256);
+  // (the plain-evaluation record is the one of slot 1: never the pass that publishes)
+  if (stamp && tid == 0 && (FIT || slot == 1)) store_stamps<FIT>(st, T, true);
+  return sh.more ? kPassMore : kPassDone;
+}
+// One evaluation pass of this workgroup at `pose`: accumulate, reduce, hand off -- pushed inside this function (PERSIST), through
+// hand_over_ticketed otherwise (ticket, out and fuse_lm are only forwarded to it).  Returns kPassNotLast in every
+// workgroup but the finisher; that one reduces the partial records and (fuse_lm) runs the LM controller:
 // kPassMore = another evaluation is requested at sh.S.cand, kPassDone = the solve ended (state published),
 // kPassSums = !fuse_lm, the sums are in `out` for the all-reduce.
 // PROF  : profiling / test-hook instantiation (phase stamps, SOICP_ABLATE switches), launched only when SOICP_ABLATE is set.
@@ -2067,7 +2151,6 @@ __device__ __forceinline__ int eval_pass(int slot, int fuse_lm, const Pose& pose
   // PERSIST (solve_kernel): workgroup 0 is the finisher of every pass of the launch, so the controller state stays in
   // its LDS from pass to pass and goes to memory only when the solve ends; the workgroup records are PUSHED (tagged
   // 16-byte chunks, see below) instead of stored + counted
-  constexpr bool keep_state = PERSIST;
   double (*red)[kRedStride] = sh.red;
   double (*part)[32] = sh.part;
   LmSums& sh_sums = sh.sums;
@@ -2075,7 +2158,6 @@ __device__ __forceinline__ int eval_pass(int slot, int fuse_lm, const Pose& pose
   LmCtl& sh_ctl = sh.ctl;
   int& sh_more = sh.more;
   int32_t* lh = sh.lh;
-  bool& is_last = sh.is_last;
   const int tid = threadIdx.x;
   static_assert(!BATCH || PERSIST, "batched hypotheses run in the persistent solve launch");
   const int abl = PROF ? ep.ablate : 0;
@@ -2083,8 +2165,8 @@ __device__ __forceinline__ int eval_pass(int slot, int fuse_lm, const Pose& pose
   const uint32_t V = BATCH ? span.V : gridDim.x;                    // workgroups of the (virtual) grid
   const uint32_t vb_begin = BATCH ? span.vb0 : blockIdx.x, vb_end = BATCH ? span.vb1 : blockIdx.x + 1u;
   const bool is_ctl = BATCH ? span.ctl : (blockIdx.x == 0);         // this workgroup collects the records and runs the controller
-  unsigned long long t_begin = 0, t_loop = 0, t_red = 0, t_ticket = 0, t_loaded = 0, t_sums = 0, t_lm = 0;
-  if (stamp) t_begin = wall_clock64();
+  PassStamps T;
+  if (stamp) T.begin = wall_clock64();
   if (FIT) {
     if (tid < 16) lh[tid] = 0;
     __syncthreads();
@@ -2134,6 +2216,13 @@ __device__ __forceinline__ int eval_pass(int slot, int fuse_lm, const Pose& pose
 #pragma unroll
       for (int b = a; b < 6; ++b) { acc[k] = SO_FMA(wj, J[b], acc[k]); ++k; }
     }
+  };
+  // an accepted correspondence at the pass's pose: rotate, translate, sum
+  auto at_pose = [&](double px, double py, double pz, const double4& nd, double c) {
+    double wx, wy, wz;
+    quat_rotate<double>(pose.q, px, py, pz, wx, wy, wz);
+    wx += pose.t[0]; wy += pose.t[1]; wz += pose.t[2];
+    tail(px, py, pz, wx, wy, wz, nd, c);
   };
   // one query: (FIT) plane fit from the prefetched neighbour coordinates, then residual / Jacobian / sums.
   // trip = 0 / 1: the query is one of the two this thread owns in every pass of a persistent solve -- an accepted
@@ -2256,31 +2345,20 @@ __device__ __forceinline__ int eval_pass(int slot, int fuse_lm, const Pose& pose
       const double c = cc->c[trip][tid];
       const double4 nd = make_double4(cc->nx[trip][tid], cc->ny[trip][tid], cc->nz[trip][tid], cc->nw[trip][tid]);
       const double px = (double)cc->px[trip][tid], py = (double)cc->py[trip][tid], pz = (double)cc->pz[trip][tid];
-      if (c >= 0.0) {
-        double wx, wy, wz;
-        quat_rotate<double>(pose.q, px, py, pz, wx, wy, wz);
-        wx += pose.t[0]; wy += pose.t[1]; wz += pose.t[2];
-        tail(px, py, pz, wx, wy, wz, nd, c);
-      }
+      if (c >= 0.0) at_pose(px, py, pz, nd, c);
     }
     for (uint32_t q = 2, j; (j = query_of(vb, V, tid, q)) < n_kept; ++q) body(j, corr.status[j], nullptr, -1);
   } else if (BATCH) {
     if (vb + 1u < vb_end) fetch2(vb + 1u, nxt);
 #pragma unroll
     for (int q = 0; q < 2; ++q)
-      if (cur[q].st == SO_MATCH_SUCCESS) {  // (the arithmetic of body(), on the record fetched ahead)
-        const double px = (double)cur[q].x, py = (double)cur[q].y, pz = (double)cur[q].z;
-        double wx, wy, wz;
-        quat_rotate<double>(pose.q, px, py, pz, wx, wy, wz);
-        wx += pose.t[0]; wy += pose.t[1]; wz += pose.t[2];
-        tail(px, py, pz, wx, wy, wz, cur[q].nd, cur[q].c);
-      }
+      if (cur[q].st == SO_MATCH_SUCCESS) at_pose((double)cur[q].x, (double)cur[q].y, (double)cur[q].z, cur[q].nd, cur[q].c);  // (the record fetched ahead)
     for (uint32_t q = 2, j; (j = query_of(vb, V, tid, q)) < n_kept; ++q) body(j, corr.status[j], nullptr, -1);
     cur[0] = nxt[0]; cur[1] = nxt[1];
   } else {
     for (uint32_t q = 0, j; (j = query_of(vb, V, tid, q)) < n_kept; ++q) body(j, corr.status[j], nullptr, -1);
   }
-  if (stamp) t_loop = wall_clock64();
+  if (stamp) T.loop = wall_clock64();
   // workgroup reduction in registers (wave_reduce_scatter), fixed order
   // BATCH: the wavefront totals alternate between two buffers, so that ONE barrier per virtual workgroup (the one inside
   // wg_reduce) orders everything: a wavefront that writes buffer b again has passed the barrier of the virtual
@@ -2313,7 +2391,7 @@ __device__ __forceinline__ int eval_pass(int slot, int fuse_lm, const Pose& pose
   }
   }  // virtual workgroups
   if (PERSIST) {
-    if (stamp) t_red = wall_clock64();
+    if (stamp) T.red = wall_clock64();
     if (!is_ctl) return kPassNotLast;
     constexpr int kPoll = 8 * kNAcc;  // 232 polling threads
     const bool poller = tid < kPoll;
@@ -2343,7 +2421,7 @@ __device__ __forceinline__ int eval_pass(int slot, int fuse_lm, const Pose& pose
       if (wall_clock64() - t0 > ep.timeout_ticks) break;  // give up instead of hanging the device (EvalParams::timeout_ticks)
     }
     if (!__syncthreads_and(ok ? 1 : 0)) return kPassNotLast;  // timeout: the solve is abandoned, the host reports the missing publication
-    if (stamp) t_ticket = t_loaded = wall_clock64();
+    if (stamp) T.arrived = T.loaded = wall_clock64();
     {
       double sum = 0;
       int hsum = 0;
@@ -2450,7 +2528,7 @@ __device__ __forceinline__ int eval_pass(int slot, int fuse_lm, const Pose& pose
       if (tid == 0) sh.peer_seq = (unsigned long long)xtag;
       __syncthreads();
     }
-    if (stamp) t_sums = wall_clock64();
+    if (stamp) T.sums = wall_clock64();
     // (BATCH too, round 6: the one-thread controller on the LDS copy of its state was what spilled -- 316 bytes of scratch per lane in a launch
     //  capped at 256 registers --, in the serial code every virtual workgroup's pass waits for)
     if (tid < 64) {  // the controller's wavefront (publishes the hand-off)
@@ -2462,8 +2540,7 @@ __device__ __forceinline__ int eval_pass(int slot, int fuse_lm, const Pose& pose
       if (tid == 0) sh_more = more_;
     }
     __syncthreads();
-    unsigned long long t_ctl = 0;
-    if (stamp) t_ctl = wall_clock64();
+    if (stamp) T.ctl = wall_clock64();
     if (!sh_more) {  // the solve is over: histogram replicas cleared for the next outer iteration, state to memory, publish
       hist[tid] = 0; hist[256 + tid] = 0;
       if (PEER && ep.peer_world > 1 && tid == 0) st->peer_seq = sh.peer_seq;
@@ -2479,116 +2556,10 @@ __device__ __forceinline__ int eval_pass(int slot, int fuse_lm, const Pose& pose
       // (a solve that does not end the registration may leave the report to the next k-NN launch, see EvalParams)
       if (!ep.defer_publish || sh.reg_done) publish_state(st, ep, sh_ctl.outer_iter, tid, 256);
     }
-    if (stamp && tid == 0 && (FIT || slot == 1)) {
-      t_lm = wall_clock64();
-      unsigned long long* d = st->dbg + (FIT ? 0 : 8);
-      // (word 3, "load partials", does not exist in this path: the fit record's is solve_kernel's "kernel entry -> first pass begins")
-      d[0] = t_loop - t_begin; d[1] = t_red - t_loop; d[2] = t_ticket - t_red; if (!FIT || BATCH) d[3] = t_loaded - t_ticket; d[4] = t_sums - t_loaded;
-      d[5] = t_lm - t_sums; d[6] = t_lm - t_begin; d[7] = t_ctl - t_sums;
-    }
+    if (stamp && tid == 0 && (FIT || slot == 1)) store_stamps<FIT>(st, T, !FIT || BATCH);
     return sh_more ? kPassMore : kPassDone;
   }
-  // Hand-off to the last workgroup WITHOUT release/acquire fences (each costs microseconds on gfx950): the 29
-  // partial sums are 8-byte agent-scope relaxed atomic stores (write-through, sc1), drained with vmcnt(0) by the
-  // storing wave before the arrival ticket; the consumer reads them with agent-scope relaxed atomic loads
-  // (sc1: served by L2, never a stale L1 line).  [MI355X guide, G16 "8-B agent atomics both sides"]
-  if (tid < kNAcc)
-    __hip_atomic_store(&partials[(size_t)tid * kPartStride + blockIdx.x], mine, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-  if (FIT && tid >= 32 && tid < 48 && lh[tid - 32])  // histograms: device-scope atomics on 16 replicas, visible before the ticket
-    __hip_atomic_fetch_add(&hist[(blockIdx.x % kHistReplicas) * kHistStride + (tid - 32)], lh[tid - 32], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-  __syncthreads();
-  if (stamp) t_red = wall_clock64();
-  // Arrival: one fire-and-forget add per workgroup, spread over 16 counters on separate lines (256 adds on ONE word
-  // serialise for ~2 us); workgroup 0 is the designated finisher and polls the 16 counters with one 16-lane load.
-  if (tid == 0) __hip_atomic_fetch_add(&ticket[(blockIdx.x & (kArriveCounters - 1)) * kArriveStrideWords], 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-  if (blockIdx.x != 0) return kPassNotLast;
-  if (tid < 64) {
-    const uint32_t lanes = kArriveCounters;
-    const uint32_t expect = (tid < (int)lanes) ? (gridDim.x + lanes - 1u - (uint32_t)tid) / lanes : 0u;  // workgroups b with b % 16 == tid
-    const unsigned long long t0 = wall_clock64();
-    bool ok = false;
-    for (;;) {
-      uint32_t v = 0;
-      if (tid < (int)lanes) v = __hip_atomic_load(&ticket[tid * kArriveStrideWords], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-      if (__ballot(v != expect) == 0ull) { ok = true; break; }
-      if (wall_clock64() - t0 > ep.timeout_ticks) break;  // give up instead of hanging the device (EvalParams::timeout_ticks)
-    }
-    if (tid < (int)lanes) __hip_atomic_store(&ticket[tid * kArriveStrideWords], 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);  // re-arm
-    if (tid == 0) is_last = ok;
-  }
-  __syncthreads();
-  if (!is_last) return kPassNotLast;  // timeout: the solve is abandoned, the host reports the missing publication
-  if (stamp) t_ticket = wall_clock64();
-  // thread b fetches workgroup b's record from the transposed table partials[a][b] (coalesced: 4 lines per wave
-  // load).  The compiler serialises agent-scope atomic loads with a vmcnt(0) after each (6 us measured), so the 29
-  // sc1 loads are issued back to back, the controller state is fetched behind them, and ONE wait covers all.
-  {
-    constexpr int kRec = (SO_SOLVE_BLOCKS + 255) / 256;  // records per thread
-    double r[kRec][kNAcc];
-    bool have[kRec];
-#pragma unroll
-    for (int q = 0; q < kRec; ++q) {
-      have[q] = (uint32_t)(tid + 256 * q) < gridDim.x;  // no divergence around the asm: a register copy before the wait would read garbage
-      const double* rec = partials + (have[q] ? tid + 256 * q : 0);
-#pragma unroll
-      for (int a = 0; a < kNAcc; ++a)
-        asm volatile("global_load_dwordx2 %0, %1, off sc1" : "=v"(r[q][a]) : "v"(rec + a * kPartStride) : "memory");
-    }
-    if (fuse_lm) {  // (coherent loads: cheap insurance, one word per thread)
-      if (!keep_state && tid < (int)(sizeof(LmState) / 8))
-        reinterpret_cast<double*>(&sh_S)[tid] = __hip_atomic_load(reinterpret_cast<const double*>(&st->S) + tid, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-      load_ctl(sh_ctl, st, tid, 128);
-    }
-#pragma unroll
-    for (int q = 0; q < kRec; ++q)
-      asm volatile("s_waitcnt vmcnt(0)"
-                   : "+v"(r[q][0]), "+v"(r[q][1]), "+v"(r[q][2]), "+v"(r[q][3]), "+v"(r[q][4]), "+v"(r[q][5]), "+v"(r[q][6]), "+v"(r[q][7]),
-                     "+v"(r[q][8]), "+v"(r[q][9]), "+v"(r[q][10]), "+v"(r[q][11]), "+v"(r[q][12]), "+v"(r[q][13]), "+v"(r[q][14]),
-                     "+v"(r[q][15]), "+v"(r[q][16]), "+v"(r[q][17]), "+v"(r[q][18]), "+v"(r[q][19]), "+v"(r[q][20]), "+v"(r[q][21]),
-                     "+v"(r[q][22]), "+v"(r[q][23]), "+v"(r[q][24]), "+v"(r[q][25]), "+v"(r[q][26]), "+v"(r[q][27]), "+v"(r[q][28])
-                   :: "memory");
-#pragma unroll
-    for (int a = 0; a < kNAcc; ++a) {
-      double v = have[0] ? r[0][a] : 0.0;
-#pragma unroll
-      for (int q = 1; q < kRec; ++q) v += have[q] ? r[q][a] : 0.0;  // fixed order: record tid, tid + 256, ...
-      red[tid][a] = v;
-    }
-  }
-  __syncthreads();
-  if (stamp) t_loaded = wall_clock64();
-  const double total = reduce_records(red, part, tid);
-  double* o = reinterpret_cast<double*>(&sh_sums);
-  if (tid < kNAcc) {
-    o[tid] = total;  // cost, count, Jtr[6], JtJ[21]
-  } else if (tid >= 32 && tid < 48) {
-    int h = 0;
-#pragma unroll
-    for (int r = 0; r < kHistReplicas; ++r)
-      h += __hip_atomic_load(&hist[r * kHistStride + (tid - 32)], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    o[kNAcc + (tid - 32)] = (double)h;
-  }
-  __syncthreads();
-  copy_words(reinterpret_cast<double*>(out), o, (int)(sizeof(LmSums) / 8), tid, 256);
-  if (stamp) t_sums = wall_clock64();
-  if (!fuse_lm) return kPassSums;  // sharded map: the sums are all-reduced first, lm_step_kernel runs the controller
-  if (tid == 0) sh_more = (abl & 32) ? 1 : lm_control(slot, st, sh_S, sh_sums, sh_ctl);  // sh_S / sh_ctl arrived with the partials
-  __syncthreads();
-  unsigned long long t_ctl = 0;
-  if (stamp) t_ctl = wall_clock64();
-  // the solve is over: clear the histogram replicas for the next outer iteration (ResetDistanceParameters, LidarSlam.cpp:847-852)
-  if (!sh_more) { hist[tid] = 0; hist[256 + tid] = 0; }
-  if ((!keep_state || !sh_more) && tid < (int)(sizeof(LmState) / 8))
-    __hip_atomic_store(reinterpret_cast<double*>(&st->S) + tid, reinterpret_cast<const double*>(&sh_S)[tid], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-  if (!sh_more) publish_state(st, ep, sh_ctl.outer_iter, tid, 256);
-  if (stamp && tid == 0 && (FIT || slot == 1)) {  // (the plain-evaluation record is the one of slot 1: never the pass that publishes)
-    t_lm = wall_clock64();
-    unsigned long long* d = st->dbg + (FIT ? 0 : 8);
-    d[0] = t_loop - t_begin; d[1] = t_red - t_loop; d[2] = t_ticket - t_red; d[3] = t_loaded - t_ticket; d[4] = t_sums - t_loaded;
-    d[5] = t_lm - t_sums; d[6] = t_lm - t_begin; d[7] = t_ctl - t_sums;
-  }
-  return sh_more ? kPassMore : kPassDone;
+  return hand_over_ticketed<FIT, PROF>(slot, fuse_lm, mine, st, ep, partials, ticket, hist, out, sh, T);
 }
 
 static_assert(sizeof(LmState) / 8 <= 256, "controller state is moved one word per thread");
