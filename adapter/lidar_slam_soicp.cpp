@@ -4,6 +4,8 @@
 #include "lidar_slam_soicp.h"
 
 #include <algorithm>
+#include <cstddef>
+#include <cstdlib>
 #include <stdexcept>
 
 namespace super_odometry_soicp {
@@ -22,6 +24,11 @@ void LidarSLAM::ensure_context() {
   cfg.line_res = localMap.lineRes_; cfg.plane_res = localMap.planeRes_;  // :103-104
   gpu_ = so_icp_create(&cfg);
   if (!gpu_) throw std::runtime_error(std::string("so_icp_create: ") + so_icp_last_error(nullptr));
+  // SOICP_NODE_MAP_INTENSITY=1: the surf cloud's intensity travels through pre-filter, map insert and map export, as in the reference's
+  // PointXYZI clouds (so_icp_set_cloud_intensity); off by default: the map topics carry x y z and zeros
+  const char* ev = std::getenv("SOICP_NODE_MAP_INTENSITY");
+  if (ev && std::atoi(ev) && so_icp_set_cloud_intensity(gpu_, (int)offsetof(Point, intensity)) < 0)
+    throw std::runtime_error(std::string("so_icp_set_cloud_intensity: ") + so_icp_last_error(gpu_));
 }
 
 void LocalMapFacade::setOrigin(const Vector3d& t) {

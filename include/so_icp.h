@@ -195,6 +195,29 @@ int so_icp_device_count(void);
 int so_icp_set_resolution(so_icp_ctx *ctx, float line_res, float plane_res);
 int so_icp_set_max_surface_features(so_icp_ctx *ctx, int max_surface_features);
 int so_icp_set_max_iterations(so_icp_ctx *ctx, int max_iterations);
+/* The surf cloud's INTENSITY through pre-filter, map insert and map export.  In the reference the surf cloud is pcl::PointXYZI, its
+ * intensity the point's sweep-relative time (featureExtraction.cpp:513), and the field survives the whole path: adjustVoxelSize's
+ * pcl::VoxelGrid<PointXYZI> averages every field per leaf (downsample_all_data, PCL's default; laserMapping.cpp:639-645),
+ * transformAndAddToMap copies the point and rewrites x y z only (LidarSlam.cpp:69-71, superodom_utils.h:126-130),
+ * LocalMap::addSurfPointCloud runs the same VoxelGrid over every touched cube (LocalMap.h:621-627), and publishTopic sends the map
+ * clouds through pcl::toROSMsg, 32 bytes per point as they are (laserMapping.cpp:437-456).
+ * offset_bytes: -1 (the state of a new context) = off: every entry point gives the bytes it gave without this call.  Otherwise the
+ * byte offset of a FLOAT32 intensity inside a point record, 16 for pcl::PointXYZI; < 12 or not a multiple of 4: SO_ICP_E_INVALID.
+ * A host-only context, one on the host-side map (SOICP_HOST_MAP=1, plane_res < 0.05) or world_size > 1: SO_ICP_E_UNSUPPORTED.
+ * The switch may change between calls; points in the map keep the intensity they have.  While it is on:
+ *  - so_icp_map_add_surf, so_icp_localization (seeding and register + insert; staged with so_icp_stage_scan or not: the same map; and
+ *    so_icp_localization_sequence on host scans, which runs it) and so_icp_prefilter_scan(_dev) read a point's intensity at
+ *    offset_bytes when stride_bytes >= offset_bytes + 4; else the point's intensity is 0.
+ *  - so_icp_localization_dev inserts with the pre-filter's intensities when called with exactly the last pre-filter's *d_filtered_out
+ *    and *n_out; any other resident scan inserts intensity 0.
+ *  - so_icp_map_export_records writes 1.0f at byte 12 (stride_bytes >= 16: data[3] of the PointXYZI constructor) and the intensity at
+ *    byte 16 (stride_bytes >= 20).  so_icp_map_export and every registration entry are unaffected.
+ * Rules (pcl::CentroidPoint<PointXYZI>: AccumulatorXYZ a Vector3f sum, AccumulatorIntensity a float sum, both divided by the count as
+ * float; PCL is not part of this project's test oracle, the rules are restated like the x y z centroid's): a leaf's intensity is the
+ * sequential float sum of its members' intensities in the member order of the x y z sums -- old centroids of the cube first, then the
+ * new points in scan order -- divided by (float)count; a lone point keeps its intensity.  Intensity is data: no cube, leaf, cell,
+ * order, gate or count depends on it, and a NaN or infinite one makes its leaf's intensity non-finite and changes nothing else. */
+int so_icp_set_cloud_intensity(so_icp_ctx *ctx, int offset_bytes);
 
 /* -------- LocalMap (LM.h) ------------------------------------------------------------------ */
 int so_icp_map_set_origin(so_icp_ctx *ctx, const double t_w_cur[3], int origin_out[3]); /* LocalMap::setOrigin, LM.h:146-164 */
@@ -208,8 +231,8 @@ int so_icp_map_add_surf(so_icp_ctx *ctx, const float *xyz, size_t n, size_t stri
 int so_icp_map_count_5x5(so_icp_ctx *ctx, const int pos[3], int *n_edge, int *n_surf);  /* get5x5LocalMapFeatureSize, LM.h:292-318 */
 /* getAllLocalMap / get5x5LocalMap (LM.h:646-688): points in the canonical (device) order */
 int so_icp_map_export(so_icp_ctx *ctx, float *xyz, size_t cap_points, size_t *n_out, int only_5x5, const int pos[3]);
-/* The same points as RECORDS of stride_bytes (float x, y, z first, the remaining bytes zero -- stride 32: pcl::PointXYZI with intensity 0,
- * what pcl::toROSMsg puts into the laser_cloud_map / laser_cloud_surround messages, lmap.cpp:437-462), written straight to `out`: the
+/* The same points as RECORDS of stride_bytes (float x, y, z first, the remaining bytes zero; with so_icp_set_cloud_intensity on, 1.0f at
+ * byte 12 and the intensity at byte 16 -- stride 32: the pcl::PointXYZI pcl::toROSMsg puts into the laser_cloud_map / laser_cloud_surround messages, lmap.cpp:437-462), written straight to `out`: the
  * payload area of the message being assembled.  One gather, one copy (DMA when `out` lies in so_icp_host_alloc / _register memory), one
  * synchronisation -- so_icp_map_export makes a round trip per occupied cube.  out == NULL (or more points than cap_points): the count only. */
 int so_icp_map_export_records(so_icp_ctx *ctx, void *out, size_t stride_bytes, size_t cap_points, size_t *n_out, int only_5x5, const int pos[3]);
@@ -550,6 +573,12 @@ int so_icp_extract_features_untimed_dev(so_icp_ctx *ctx, const void *d_raw, uint
 /* so_icp_prefilter_scan on a cloud already in HBM and complete (e.g. *d_surface_out above, stride 32): same results, bit for bit */
 int so_icp_prefilter_scan_dev(so_icp_ctx *ctx, const void *d_surf, size_t n, size_t stride_bytes, int auto_voxel_size, float line_res,
                               float plane_res, void **d_filtered_out, size_t *n_out, so_icp_prefilter_info *info);
+
+/* The intensities of the last so_icp_prefilter_scan(_dev) output, index for index with its *d_filtered_out (per leaf: the rules at
+ * so_icp_set_cloud_intensity; "leaf size too small": passed through in input order).  out: host copy of cap floats, or NULL;
+ * *d_out (d_out may be NULL): device array owned by the context, valid as long as that *d_filtered_out.  The switch was off during
+ * that pre-filter: *n_out = 0, SO_ICP_OK. */
+int so_icp_prefilter_intensity(so_icp_ctx *ctx, float *out, size_t cap, void **d_out, size_t *n_out);
 
 /* -------- one step after Seam A: the registered scan laserMapping::publishTopic builds
  * (src/LaserMapping/laserMapping.cpp:464-493 with utils::pointAssociateToMap, src/utils/superodom_utils.cpp:148-158).

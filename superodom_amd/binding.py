@@ -210,7 +210,7 @@ EXPORTED = ["so_icp_default_config", "so_icp_create", "so_icp_destroy", "so_icp_
             "so_icp_localization_sequence", "so_icp_extract_features", "so_icp_extract_features_dev", "so_icp_prefilter_scan_dev",
             "so_icp_livox_default_layout", "so_icp_extract_features_livox", "so_icp_extract_features_livox_dev",
             "so_icp_registered_scan", "so_icp_registered_scan_dev", "so_icp_extract_features_untimed", "so_icp_extract_features_untimed_dev",
-            "so_icp_debug_lm_script"]
+            "so_icp_debug_lm_script", "so_icp_set_cloud_intensity", "so_icp_prefilter_intensity"]
 
 _lib = None
 
@@ -233,6 +233,8 @@ def load():
     L.so_icp_set_resolution.argtypes = [vp, C.c_float, C.c_float]
     L.so_icp_set_max_surface_features.argtypes = [vp, C.c_int]
     L.so_icp_set_max_iterations.argtypes = [vp, C.c_int]
+    L.so_icp_set_cloud_intensity.argtypes = [vp, C.c_int]
+    L.so_icp_prefilter_intensity.argtypes = [vp, f32p, C.c_size_t, C.POINTER(vp), C.POINTER(C.c_size_t)]
     L.so_icp_map_set_origin.argtypes = [vp, f64p, i32p]
     L.so_icp_map_shift.argtypes = [vp, f64p, i32p]
     L.so_icp_map_add_surf.argtypes = [vp, f32p, C.c_size_t, C.c_size_t]
@@ -389,6 +391,16 @@ class LidarSlamGpu:
     def add_surf_point_cloud(self, xyz):
         xyz = _f32(xyz).reshape(-1, 3)
         return self._check(self.L.so_icp_map_add_surf(self.h, _p(xyz, C.c_float), len(xyz), 12))
+
+    def set_cloud_intensity(self, offset_bytes):
+        """so_icp_set_cloud_intensity: byte offset of the FLOAT32 intensity in a point record (16: pcl::PointXYZI), -1: off.
+        Returns the C code (negative: refused) -- it does not raise."""
+        return self.L.so_icp_set_cloud_intensity(self.h, int(offset_bytes))
+
+    def add_surf_records(self, records):
+        """so_icp_map_add_surf on records: float32 array (n, w), x y z in the first three columns, stride 4 w bytes"""
+        rec = _f32(records); assert rec.ndim == 2 and rec.shape[1] >= 3
+        return self._check(self.L.so_icp_map_add_surf(self.h, _p(rec, C.c_float), len(rec), 4 * rec.shape[1]))
 
     def count_5x5(self, pos):
         pos = np.ascontiguousarray(pos, dtype=np.int32); ne = C.c_int32(); ns = C.c_int32()
@@ -612,6 +624,20 @@ class LidarSlamGpu:
                                                     len(scan), 12, float(time_laser_odometry), _p(out, C.c_double), C.byref(st)))
         return rc, out, st
 
+    def localization_records(self, initialization, T_w_lidar, records, time_laser_odometry):
+        """so_icp_localization on records: contiguous float32 array (n, w), stride 4 w bytes (the array itself is handed over, so a
+        staged copy of it is recognised)"""
+        assert isinstance(records, np.ndarray) and records.dtype == np.float32 and records.flags.c_contiguous and records.ndim == 2
+        T = np.ascontiguousarray(T_w_lidar, dtype=np.float64); out = np.zeros(7); st = Stats()
+        rc = self._check(self.L.so_icp_localization(self.h, int(bool(initialization)), _p(T, C.c_double), _p(records, C.c_float),
+                                                    len(records), 4 * records.shape[1], float(time_laser_odometry), _p(out, C.c_double), C.byref(st)))
+        return rc, out, st
+
+    def stage_scan_records(self, records):
+        """so_icp_stage_scan on records (see localization_records)"""
+        assert isinstance(records, np.ndarray) and records.dtype == np.float32 and records.flags.c_contiguous and records.ndim == 2
+        self._check(self.L.so_icp_stage_scan(self.h, _p(records, C.c_float), len(records), 4 * records.shape[1]))
+
     def localization_dev(self, initialization, T_w_lidar, d_scan, n, time_laser_odometry):
         T = np.ascontiguousarray(T_w_lidar, dtype=np.float64); out = np.zeros(7); st = Stats()
         rc = self._check(self.L.so_icp_localization_dev(self.h, int(bool(initialization)), _p(T, C.c_double), d_scan, n,
@@ -636,6 +662,20 @@ class LidarSlamGpu:
         self._check(self.L.so_icp_prefilter_scan(self.h, _p(pts, C.c_float), len(pts), 12, int(bool(auto_voxel_size)), float(line_res),
                                                  float(plane_res), C.byref(d), C.byref(n), C.byref(info)))
         return d.value, n.value, info
+
+    def prefilter_scan_records(self, records, auto_voxel_size, line_res, plane_res):
+        """so_icp_prefilter_scan on records: float32 array (n, w), stride 4 w bytes; returns (d_scan, n, PrefilterInfo)."""
+        rec = _f32(records); assert rec.ndim == 2 and rec.shape[1] >= 3
+        d = C.c_void_p(); n = C.c_size_t(0); info = PrefilterInfo()
+        self._check(self.L.so_icp_prefilter_scan(self.h, _p(rec, C.c_float), len(rec), 4 * rec.shape[1], int(bool(auto_voxel_size)), float(line_res),
+                                                 float(plane_res), C.byref(d), C.byref(n), C.byref(info)))
+        return d.value, n.value, info
+
+    def prefilter_intensity(self, n_expected):
+        """so_icp_prefilter_intensity: the last pre-filter's intensities -> (float32 array, device address or None)"""
+        out = np.zeros(max(int(n_expected), 1), np.float32); d = C.c_void_p(); n = C.c_size_t(0)
+        self._check(self.L.so_icp_prefilter_intensity(self.h, _p(out, C.c_float), int(n_expected), C.byref(d), C.byref(n)))
+        return out[:n.value].copy(), d.value
 
     def prefilter_scan_dev(self, d_surf, n, stride_bytes, auto_voxel_size, line_res, plane_res):
         """so_icp_prefilter_scan on a cloud resident in HBM (d_surf: device address); returns (d_scan, n, PrefilterInfo)."""

@@ -148,6 +148,12 @@ struct so_icp_ctx {
   uint32_t* h_pf_kept = nullptr;      // pinned: so_icp_transform_cloud's count of kept points
   size_t pf_temp_for = 0, pf_temp_need = 0;  // map_sort_temp_bytes(pf_temp_for) == pf_temp_need (the query costs two library calls)
   bool pf_fast = true;                // SOICP_PREFILTER_FAST=0: statistics read back, decided on the host, then the filter (rounds 1-3)
+  // so_icp_set_cloud_intensity: byte offset of the FLOAT32 intensity in a point record, -1: off (the map's fourth lane stays 0)
+  int intensity_off = -1;
+  DevBuf d_inten;                     // so_icp_localization on a host scan: the scan's intensities next to resolve_scan's packed xyz
+  float* h_inten = nullptr; size_t h_inten_cap = 0;  // pinned: where they are gathered from the caller's records
+  DevBuf pf_inten;                    // the pre-filter's intensities, index for index with pf_out
+  size_t pf_inten_n = 0; bool pf_inten_on = false;   // points of the last pre-filter's output / the switch was on during it
   hipEvent_t ev_upload = nullptr;     // a scan uploaded through the auxiliary queue: the context's queue waits for it
   std::shared_ptr<void> fe_state;     // so_icp_extract_features(_dev) (feature_extraction.cpp)
   std::shared_ptr<void> rs_state;     // so_icp_registered_scan(_dev) (feature_extraction.cpp): buffers of its own
@@ -309,6 +315,10 @@ inline int fail(so_icp_ctx* c, int code, const std::string& msg) { c->err = msg;
 // what a DeviceMap member returns (device_map.h: -1 out of memory / a full cube, -2 a HIP error, its text in c->err; else >= 0) as a C ABI code
 inline int map_status(int r) { return r >= 0 ? SO_ICP_OK : (r == -1 ? SO_ICP_E_NOMEM : SO_ICP_E_HIP); }
 // the stride rule of the entries that read float x y z records: 0 means packed (12 bytes); a multiple of 4
+// where record i's intensity is, given where its x is: inside the record when the switch is on and the record holds it, else nowhere (0)
+inline const float* intensity_in(const so_icp_ctx* c, const float* xyz, size_t stride_bytes) {
+  return (c->intensity_off >= 0 && stride_bytes >= (size_t)c->intensity_off + 4) ? xyz + c->intensity_off / 4 : nullptr;
+}
 inline int normalise_stride(so_icp_ctx* c, size_t* stride_bytes) {
   if (*stride_bytes == 0) *stride_bytes = 12;
   return *stride_bytes % 4 ? fail(c, SO_ICP_E_INVALID, "stride_bytes must be a multiple of 4") : SO_ICP_OK;

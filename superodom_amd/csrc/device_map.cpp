@@ -105,6 +105,7 @@ void DeviceMap::clear() {
   std::fill(slot_owned_.begin(), slot_owned_.end(), 0u);
   std::fill(slot_full_.begin(), slot_full_.end(), 0u);
   slot_table_dirty_ = true;
+  carries_intensity_ = false;
 }
 
 void DeviceMap::set_origin(const double t[3]) {  // LocalMap.h:146-164
@@ -367,30 +368,41 @@ int DeviceMap::ensure_grid(size_t gn, std::string& err, bool library_scan) {
   return 0;
 }
 
-int DeviceMap::add_surf_host(const float* xyz, size_t n, size_t stride_floats, std::string& err) {
+int DeviceMap::add_surf_host(const float* xyz, size_t n, size_t stride_floats, std::string& err, const float* inten, size_t inten_stride) {
   if (const int rs = settle(err); rs < 0) return rs;  // (a deferred insert may still read the staging buffer)
   if (!n) return 0;
   if (stride_floats == 0) stride_floats = 3;
-  DM_TRY(ensure_stage(n * stride_floats));
+  // an intensity inside the points' own records travels with them; any other is packed behind them in the staging buffer
+  const bool in_record = inten && inten_stride == stride_floats && inten >= xyz && (size_t)(inten - xyz) < stride_floats;
+  const size_t side = (inten && !in_record) ? n : 0;
+  DM_TRY(ensure_stage(n * stride_floats + side));
   DM_TRY(hipMemcpyAsync(d_stage_, xyz, n * stride_floats * sizeof(float), hipMemcpyHostToDevice, stream_));
-  return add_surf_dev(d_stage_, n, stride_floats, err);
+  if (!inten) return add_surf_dev(d_stage_, n, stride_floats, err);
+  if (in_record) return add_surf_dev(d_stage_, n, stride_floats, err, d_stage_ + (inten - xyz), stride_floats);
+  std::vector<float> packed(n);
+  for (size_t i = 0; i < n; ++i) packed[i] = inten[i * inten_stride];
+  DM_TRY(hipMemcpyAsync(d_stage_ + n * stride_floats, packed.data(), n * sizeof(float), hipMemcpyHostToDevice, stream_));
+  DM_TRY(hipStreamSynchronize(stream_));  // (`packed` leaves with this call)
+  return add_surf_dev(d_stage_, n, stride_floats, err, d_stage_ + n * stride_floats, 1);
 }
 
-int DeviceMap::add_surf_dev(const float* d_xyz, size_t n, size_t stride_floats, std::string& err) {
+int DeviceMap::add_surf_dev(const float* d_xyz, size_t n, size_t stride_floats, std::string& err, const float* d_inten, size_t inten_stride) {
   if (const int rs = settle(err); rs < 0) return rs;
   if (!n) return 0;
   if (stride_floats == 0) stride_floats = 3;
-  const int r = insert_fast(d_xyz, n, stride_floats, nullptr, nullptr, false, err);
-  return r != kNotFast ? r : add_surf_legacy(d_xyz, n, stride_floats, err);
+  const int r = insert_fast(d_xyz, n, stride_floats, nullptr, nullptr, d_inten, inten_stride, nullptr, false, err);
+  return r != kNotFast ? r : add_surf_legacy(d_xyz, n, stride_floats, d_inten, inten_stride, err);
 }
 
-int DeviceMap::add_scan_dev(const float* d_scan, size_t n, const double T[7], float* d_world, bool defer, std::string& err) {
+int DeviceMap::add_scan_dev(const float* d_scan, size_t n, const double T[7], float* d_world, bool defer, std::string& err, const float* d_inten,
+                            float* d_inten_world) {
   if (const int rs = settle(err); rs < 0) return rs;
   if (!n) return 0;
-  const int r = insert_fast(d_scan, n, 3, T, d_world, defer, err);
+  if (d_inten && !d_inten_world) { err = "DeviceMap::add_scan_dev: intensities without a place for them"; return -2; }
+  const int r = insert_fast(d_scan, n, 3, T, d_world, d_inten, 1, d_inten_world, defer, err);
   if (r != kNotFast) return r;
   launch_transform_scan(d_scan, (uint32_t)n, pose_from_array(T), d_world, stream_);
-  return add_surf_legacy(d_world, n, 3, err);
+  return add_surf_legacy(d_world, n, 3, d_inten, 1, err);  // (not deferred: the caller's intensities are read before this returns)
 }
 
 // ---- the insert laid out by the device -----------------------------------------------------------------------------
@@ -423,7 +435,8 @@ int DeviceMap::sync_meta(std::string& err) {
   return 0;
 }
 
-int DeviceMap::insert_fast(const float* d_in, size_t n, size_t stride_floats, const double* T, float* d_world, bool defer, std::string& err) {
+int DeviceMap::insert_fast(const float* d_in, size_t n, size_t stride_floats, const double* T, float* d_world, const float* d_inten,
+                           size_t inten_stride, float* d_inten_world, bool defer, std::string& err) {
   if (!fast_enabled_ || !hash_grouping_ || world_ > 1 || slot_cube_.empty() || n >= (1u << 30)) return kNotFast;
   if (slot_cube_.size() > (size_t)kMaxSlots) return kNotFast;  // (the device's per-slot tables hold kMaxSlots entries: the host lays such rounds out)
   if (skip_fast_ > 0) { --skip_fast_; return kNotFast; }
@@ -455,6 +468,12 @@ int DeviceMap::insert_fast(const float* d_in, size_t n, size_t stride_floats, co
   a.d_xyz = T ? d_world : d_in; a.n_new = (uint32_t)n; a.stride_floats = T ? 3u : (uint32_t)stride_floats; a.n_old = (uint32_t)n_old_ub;
   // the launches are sized for what the last device-built round held (+ 25 %), not for the whole map: the kernels stride
   a.n_old_grid = (uint32_t)std::max<size_t>(1, std::min<size_t>(n_old_ub, est_old_ ? est_old_ + est_old_ / 4 + 16384 : n_old_ub));
+  // (transform: the intensities are copied next to the world points in front of the first kernel, and the insert reads them there:
+  //  that kernel stays the last reader of the caller's arrays)
+  if (T && d_inten) DM_TRY(hipMemcpyAsync(d_inten_world, d_inten, n * sizeof(float), hipMemcpyDeviceToDevice, stream_));
+  a.d_inten = (T && d_inten) ? d_inten_world : d_inten; a.inten_stride = T ? 1u : (uint32_t)inten_stride;
+  carries_intensity_ = carries_intensity_ || d_inten != nullptr;
+  a.intensity = carries_intensity_;
   a.d_cube_of = d_cube_of_; a.inv_leaf = 1.0f / plane_res_;
   a.rank = 0; a.world = 1; a.d_owned = nullptr;
   a.grid_is_clean = true;
@@ -473,6 +492,7 @@ int DeviceMap::insert_fast(const float* d_in, size_t n, size_t stride_floats, co
   DM_TRY(hipGetLastError());
   DM_TRY(hipEventRecord(ev_fast_, stream_));
   pending_.on = true; pending_.d_xyz = a.d_xyz; pending_.n = n; pending_.stride = a.stride_floats; pending_.seq = f.seq;
+  pending_.d_inten = a.d_inten; pending_.inten_stride = a.inten_stride;
   if (!defer) return settle(err);
   // the caller may recycle the buffer of the input points as soon as this returns: wait until the front kernel (the only one
   // that reads them; long done by the time a dozen launches have been enqueued) says so
@@ -535,10 +555,10 @@ int DeviceMap::settle(std::string& err) {
   ++fast_fallbacks_;
   if (R.halt == kFastHaltMultiRound) skip_fast_ = 16;
   if (R.halt == kFastHaltOverflow) grid_zero_upto_ = 0;  // (the centroids of the round were counted into the grids as they were produced)
-  return add_surf_legacy(pending_.d_xyz, pending_.n, pending_.stride, err);
+  return add_surf_legacy(pending_.d_xyz, pending_.n, pending_.stride, pending_.d_inten, pending_.inten_stride, err);
 }
 
-int DeviceMap::add_surf_legacy(const float* d_xyz, size_t n, size_t stride_floats, std::string& err) {
+int DeviceMap::add_surf_legacy(const float* d_xyz, size_t n, size_t stride_floats, const float* d_inten, size_t inten_stride, std::string& err) {
   if (!n) return 0;
   if (stride_floats == 0) stride_floats = 3;
   meta_dirty_ = true;  // (the host lays the rounds out and changes counts / slots: the device's copies follow before its next round)
@@ -576,6 +596,9 @@ int DeviceMap::add_surf_legacy(const float* d_xyz, size_t n, size_t stride_float
     a.tt = tt;
     a.rank = rank_; a.world = world_; a.d_owned = world_ > 1 ? d_small_ + kCntOwned : nullptr;
     a.d_xyz = d_xyz; a.n_new = (uint32_t)n; a.stride_floats = (uint32_t)stride_floats; a.n_old = n_old;
+    a.d_inten = d_inten; a.inten_stride = (uint32_t)inten_stride;
+    carries_intensity_ = carries_intensity_ || d_inten != nullptr;
+    a.intensity = carries_intensity_;
     a.d_cube_of = d_cube_of_; a.inv_leaf = inv_leaf;
     a.grid_is_clean = grid_clean_upto((size_t)tt.n * ncell1_ + 1);  // fill only what no round has cleared yet
     // first stage: leaf grouping through a hash table (default) or the stable radix sort of the whole working set
@@ -760,7 +783,7 @@ size_t DeviceMap::export_points(float* xyz, size_t cap, bool only_5x5, const int
   return n;
 }
 
-size_t DeviceMap::export_records(void* out, size_t stride, size_t cap, bool only_5x5, const int pos[3], std::string& err) {
+size_t DeviceMap::export_records(void* out, size_t stride, size_t cap, bool only_5x5, const int pos[3], bool with_intensity, std::string& err) {
   if (settle(err) < 0) return 0;
   std::vector<std::pair<int, uint32_t>> todo;  // (slot, count) in ascending cube index: the order of export_points
   size_t n = 0;
@@ -779,7 +802,7 @@ size_t DeviceMap::export_records(void* out, size_t stride, size_t cap, bool only
   if (ensure_stage(words) != hipSuccess) { err = "DeviceMap: export staging alloc failed"; return 0; }  // (the staging buffer of export_points, counted in 32-bit words)
   size_t at = 0;
   for (const auto& sc : todo) {
-    launch_gather_export_records(d_pool_, kCapPerSlot, (uint32_t)sc.first, sc.second, reinterpret_cast<uint32_t*>(d_stage_) + at * (stride / 4), (uint32_t)(stride / 4), stream_);
+    launch_gather_export_records(d_pool_, kCapPerSlot, (uint32_t)sc.first, sc.second, reinterpret_cast<uint32_t*>(d_stage_) + at * (stride / 4), (uint32_t)(stride / 4), with_intensity, stream_);
     at += sc.second;
   }
   if (hipMemcpyAsync(out, d_stage_, n * stride, hipMemcpyDeviceToHost, stream_) != hipSuccess || hipStreamSynchronize(stream_) != hipSuccess) {

@@ -1,7 +1,7 @@
 // device_map.h -- the HBM-resident LocalMap (the whole map, or this rank's shard of it): the device pool is the authoritative store, the host
 // keeps only the block bookkeeping of include/super_odometry/LidarProcess/LocalMap.h (origin_, which block holds data,
 // per-block point counts).  Layout: every occupied 50 m cube owns a fixed region ("slot") of kCapPerSlot points in
-// one pool of {x,y,z,0} records plus its nc^3+1 cell table; canonical index = slot * kCapPerSlot + position, so a map
+// one pool of {x,y,z,intensity} records plus its nc^3+1 cell table; canonical index = slot * kCapPerSlot + position, so a map
 // insert rewrites only the touched cubes and shiftMap is pure bookkeeping.
 #pragma once
 #include <hip/hip_runtime_api.h>
@@ -52,13 +52,18 @@ class DeviceMap {
   int reshard(const std::vector<std::vector<uint8_t>>& blobs, float line_res, float plane_res, std::string& err);
   void clear();
   // LocalMap::addSurfPointCloud on the device.  d_xyz: device pointer, stride in floats.  Returns #points inside the window or <0.
-  int add_surf_dev(const float* d_xyz, size_t n, size_t stride_floats, std::string& err);
-  int add_surf_host(const float* xyz, size_t n, size_t stride_floats, std::string& err);
+  // Intensity (pcl::PointXYZI's fourth field, averaged per leaf like x y z): point i's at inten[i * inten_stride], in the same kind of
+  // memory as the points; nullptr: 0.  add_surf_host stages it with the points (it may lie inside their records).
+  int add_surf_dev(const float* d_xyz, size_t n, size_t stride_floats, std::string& err, const float* d_inten = nullptr, size_t inten_stride = 0);
+  int add_surf_host(const float* xyz, size_t n, size_t stride_floats, std::string& err, const float* inten = nullptr, size_t inten_stride = 0);
   // transformAndAddToMap (LidarSlam.cpp:60-80) on the device: world = T * scan (packed xyz, sensor frame) is written to d_world
   // and inserted.  defer: return as soon as the launches are in the queue and nothing reads d_scan any more; the map's
   // bookkeeping is brought up to date by the next call of any member (settle).  Returns the number of points inside the
   // window (0 when deferred) or < 0.
-  int add_scan_dev(const float* d_scan, size_t n, const double T[7], float* d_world, bool defer, std::string& err);
+  // d_inten: the scan's intensities (n floats) or nullptr; they are copied to d_inten_world (n floats, the caller's, like d_world) in
+  // front of the first launch, the last reader of d_scan
+  int add_scan_dev(const float* d_scan, size_t n, const double T[7], float* d_world, bool defer, std::string& err, const float* d_inten = nullptr,
+                   float* d_inten_world = nullptr);
   bool defer_enabled() const { return defer_enabled_; }
   bool insert_in_flight() const { return pending_.on; }  // a deferred insert has not been settled yet
   // completes a deferred insert: bookkeeping from the device's report, or -- when the device could not lay the round out --
@@ -67,9 +72,10 @@ class DeviceMap {
   // (inserts laid out by the device / of those, the ones the host had to repeat round by round)
   void fast_stats(unsigned& inserts, unsigned& fallbacks) const { inserts = fast_inserts_; fallbacks = fast_fallbacks_; }
   size_t export_points(float* xyz, size_t cap, bool only_5x5, const int pos[3], std::string& err);
-  // the same points as records of `stride` bytes (x, y, z floats first, the rest zero), every cube gathered into ONE staging buffer, ONE
+  // the same points as records of `stride` bytes (x, y, z floats first, the rest zero; with_intensity: 1.0f at byte 12 and the intensity
+  // at byte 16 where the record has room), every cube gathered into ONE staging buffer, ONE
   // copy to `out` (pinned memory: by DMA), ONE synchronisation; out == nullptr: the count only
-  size_t export_records(void* out, size_t stride, size_t cap, bool only_5x5, const int pos[3], std::string& err);
+  size_t export_records(void* out, size_t stride, size_t cap, bool only_5x5, const int pos[3], bool with_intensity, std::string& err);
   int view(DevMapView& v, std::string& err);  // refreshes the device cube_slot table when the bookkeeping changed; 0, -1 (a cube is full), -2 (device error)
   // leaf keys hold 9 or 10 bits per axis (50 / planeRes + 4 leaves per cube axis must fit): planeRes >= 0.05
   bool supported_resolution(float plane_res) const { return plane_res >= 0.0499f; }
@@ -77,9 +83,10 @@ class DeviceMap {
   static size_t max_touched(uint32_t lbits) { return lbits == 9u ? (size_t)kMaxTouched : (size_t)4; }
 
  private:
-  int add_surf_legacy(const float* d_xyz, size_t n, size_t stride_floats, std::string& err);  // host-built rounds
+  int add_surf_legacy(const float* d_xyz, size_t n, size_t stride_floats, const float* d_inten, size_t inten_stride, std::string& err);  // host-built rounds
   static constexpr int kNotFast = -100;
-  int insert_fast(const float* d_in, size_t n, size_t stride_floats, const double* T, float* d_world, bool defer, std::string& err);
+  int insert_fast(const float* d_in, size_t n, size_t stride_floats, const double* T, float* d_world, const float* d_inten, size_t inten_stride,
+                  float* d_inten_world, bool defer, std::string& err);
   int ensure_fast(std::string& err);
   int sync_meta(std::string& err);
   int upload_slot_table(std::string& err);
@@ -109,6 +116,7 @@ class DeviceMap {
                                      // centroid drifted out of its leaf -- the pass-through grouping is off for the cube)
   bool slot_table_dirty_ = true;
   bool hash_grouping_ = true;
+  bool carries_intensity_ = false;   // an insert since the last clear() brought intensities: the pool's fourth lane may be non-zero
   // device
   float4* d_pool_ = nullptr; uint32_t* d_cell_start_ = nullptr; int32_t* d_cube_slot_ = nullptr; int slots_alloc_ = 0;
   // work buffers
@@ -135,7 +143,7 @@ class DeviceMap {
   bool meta_dirty_ = true;    // the host changed slot counts / resolutions / slots behind the device's back: upload before the next device-built round
   bool fast_clean_ = false;   // d_cube_cnt_ / d_scan_state_ / d_tickets_ are all zero (the report kernel leaves them so)
   unsigned long long fast_seq_ = 0;
-  struct Pending { bool on = false; const float* d_xyz = nullptr; size_t n = 0, stride = 0; unsigned long long seq = 0; } pending_;
+  struct Pending { bool on = false; const float *d_xyz = nullptr, *d_inten = nullptr; size_t n = 0, stride = 0, inten_stride = 0; unsigned long long seq = 0; } pending_;
   size_t est_old_ = 0;        // old points of the last device-built round (sizes the next one's launches)
   int skip_fast_ = 0;         // inserts to go round by round after the device met a scan that needs several rounds
   unsigned fast_inserts_ = 0, fast_fallbacks_ = 0;

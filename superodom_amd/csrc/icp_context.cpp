@@ -689,7 +689,7 @@ so_icp_ctx::~so_icp_ctx() {
   for (DevBuf* b : {&d_world, &d_mpts, &d_cell_start, &d_cube_slot, &d_scan_own, &d_keys0, &d_vals0, &d_chunks,
                     &d_binned, &d_nd, &d_coeff, &d_status, &d_nbr5, &d_small, &d_q, &d_nbr, &d_d2, &d_idx,
                     &d_found, &d_fblist, &d_kdbg, &pf_stage, &pf_in, &pf_out, &pf_small, &pf_w, &pf_s, &pf_k0, &pf_k1, &pf_v0, &pf_v1, &pf_flags, &pf_pos,
-                    &pf_heads, &pf_temp, &pf_dec, &d_counts, &d_sub})
+                    &pf_heads, &pf_temp, &pf_dec, &d_counts, &d_sub, &d_inten, &pf_inten})
     b->release();
   bin.release(); pbin.release();
   for (DevBuf& b : resident_scans) b.release();
@@ -701,6 +701,7 @@ so_icp_ctx::~so_icp_ctx() {
   if (h_u32) (void)hipHostFree(h_u32);
   if (h_pf) (void)hipHostFree(h_pf);
   if (h_pf_kept) (void)hipHostFree(h_pf_kept);
+  if (h_inten) (void)hipHostFree(h_inten);
   for (hipEvent_t e : ev_pool) (void)hipEventDestroy(e);
   dmap.reset();  // (waits for a deferred insert on `stream`)
   if (pf_stream) { (void)hipStreamSynchronize(pf_stream); (void)hipStreamDestroy(pf_stream); }
@@ -868,6 +869,17 @@ int so_icp_set_resolution(so_icp_ctx* c, float line_res, float plane_res) {
   c->cfg.line_res = line_res; c->cfg.plane_res = plane_res;
   return SO_ICP_OK;
 }
+// The surf cloud's fourth field (pcl::PointXYZI::intensity) through pre-filter, insert and export -- so_icp.h has the rules
+int so_icp_set_cloud_intensity(so_icp_ctx* c, int offset_bytes) {
+  if (!c) return SO_ICP_E_INVALID;
+  if (offset_bytes == -1) { c->intensity_off = -1; return SO_ICP_OK; }
+  if (offset_bytes < 12 || offset_bytes % 4) return fail(c, SO_ICP_E_INVALID, "so_icp_set_cloud_intensity: -1, or the 4-byte aligned offset (>= 12) of a FLOAT32 behind x y z");
+  if (c->host_only) return fail(c, SO_ICP_E_UNSUPPORTED, "so_icp_set_cloud_intensity: a host-only context keeps no intensity");
+  if (!c->dmap) return fail(c, SO_ICP_E_UNSUPPORTED, "so_icp_set_cloud_intensity: the host-side map (SOICP_HOST_MAP=1, plane_res < 0.05) keeps no intensity");
+  if (c->cfg.world_size > 1) return fail(c, SO_ICP_E_UNSUPPORTED, "so_icp_set_cloud_intensity: sharded maps (world_size > 1) keep no intensity");
+  c->intensity_off = offset_bytes;
+  return SO_ICP_OK;
+}
 int so_icp_set_max_surface_features(so_icp_ctx* c, int v) { if (!c) return SO_ICP_E_INVALID; c->cfg.max_surface_features = v; return SO_ICP_OK; }
 int so_icp_set_max_iterations(so_icp_ctx* c, int v) { if (!c || v < 1) return SO_ICP_E_INVALID; c->cfg.max_iterations = v; return SO_ICP_OK; }
 
@@ -892,7 +904,7 @@ int so_icp_map_add_surf(so_icp_ctx* c, const float* xyz, size_t n, size_t stride
   if (const int rc = normalise_stride(c, &stride_bytes)) return rc;
   if (c->dmap) {  // bin + VoxelGrid + index rebuild on the device (map_kernels.hip)
     HIP_TRY(c, hipSetDevice(c->cfg.device_id));
-    const int r = c->dmap->add_surf_host(xyz, n, stride_bytes / 4, c->err);
+    const int r = c->dmap->add_surf_host(xyz, n, stride_bytes / 4, c->err, intensity_in(c, xyz, stride_bytes), stride_bytes / 4);
     if (r < 0) { group_abort(c); return map_status(r); }
     const int xr = exchange_map_counts(c);
     return xr ? xr : r;
@@ -922,7 +934,7 @@ int so_icp_map_export_records(so_icp_ctx* c, void* out, size_t stride_bytes, siz
   if (c->dmap) {
     HIP_TRY(c, hipSetDevice(c->cfg.device_id));
     c->err.clear();
-    n = c->dmap->export_records(out, stride_bytes, cap, only_5x5 != 0, pos ? pos : zero, c->err);
+    n = c->dmap->export_records(out, stride_bytes, cap, only_5x5 != 0, pos ? pos : zero, c->intensity_off >= 0, c->err);
     if (!c->err.empty()) return SO_ICP_E_HIP;
   } else {  // host-side map (sharded ranks, host-only contexts): through the packed export
     n = c->map.export_points(nullptr, 0, only_5x5 != 0, pos ? pos : zero);

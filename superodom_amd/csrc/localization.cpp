@@ -16,25 +16,53 @@ struct FrameScan {
   size_t n, stride_bytes;
 };
 
+// The intensities that go with a frame's scan (so_icp_set_cloud_intensity): in the caller's host records, or a device array of n floats
+// (the last pre-filter's, when the resident scan is its output), or none -- the map then takes 0
+struct FrameIntensity { const float* host = nullptr; size_t stride_floats = 0; const float* dev = nullptr; };
+
+FrameIntensity frame_intensity(const so_icp_ctx* c, const FrameScan& s) {
+  FrameIntensity fi;
+  if (c->intensity_off < 0) return fi;
+  if (s.on_host) { fi.host = intensity_in(c, s.xyz, s.stride_bytes); fi.stride_floats = s.stride_bytes / 4; }
+  else if (c->pf_inten_on && s.xyz == c->pf_out.as<float>() && s.n == c->pf_inten_n) fi.dev = c->pf_inten.as<float>();
+  return fi;
+}
+
 // transformAndAddToMap (LidarSlam.cpp:60-80) entirely on the device: one launch transforms the scan, finds every point's cube and
 // lays the insert round out; the insert is enqueued without a read-back and -- unless SOICP_MAP_FAST=sync -- completes behind
 // this call (device_map.h, settle)
-int insert_resident(so_icp_ctx* c, const float* d_scan, size_t n, const double T[7]) {
+int insert_resident(so_icp_ctx* c, const float* d_scan, size_t n, const double T[7], const FrameIntensity& fi) {
   if (const int rs = map_status(c->dmap->settle(c->err))) return rs;  // (before d_world may be re-allocated)
-  HIP_TRY(c, c->d_world.reserve((n + 64) * 12));
-  const int r = c->dmap->add_scan_dev(d_scan, n, T, c->d_world.as<float>(), c->dmap->defer_enabled() && !c->dmap->sharded(), c->err);
+  HIP_TRY(c, c->d_world.reserve((n + 64) * 16));  // world x y z, and behind them the intensities (transformAndAddToMap copies the point and rewrites x y z)
+  const float* d_inten = fi.dev;
+  if (fi.host && n) {
+    // gathered from the caller's records into pinned memory and sent down the context's queue in front of the insert (the insert
+    // before this one has been settled: nothing reads either buffer any more)
+    if (c->h_inten_cap < n) {
+      if (c->h_inten) (void)hipHostFree(c->h_inten);
+      c->h_inten = nullptr; c->h_inten_cap = 0;
+      HIP_TRY(c, hipHostMalloc(reinterpret_cast<void**>(&c->h_inten), (n + n / 4 + 64) * sizeof(float)));
+      c->h_inten_cap = n + n / 4 + 64;
+    }
+    for (size_t i = 0; i < n; ++i) c->h_inten[i] = fi.host[i * fi.stride_floats];
+    HIP_TRY(c, c->d_inten.reserve(n * sizeof(float) + 64));
+    HIP_TRY(c, hipMemcpyAsync(c->d_inten.p, c->h_inten, n * sizeof(float), hipMemcpyHostToDevice, c->stream));
+    d_inten = c->d_inten.as<float>();
+  }
+  const int r = c->dmap->add_scan_dev(d_scan, n, T, c->d_world.as<float>(), c->dmap->defer_enabled() && !c->dmap->sharded(), c->err, d_inten,
+                                      c->d_world.as<float>() + 3 * (n + 64));
   return r < 0 ? map_status(r) : exchange_map_counts(c);
 }
 
 // transformAndAddToMap with the transform on the host, in double (TransformPoint, superodom_utils.h:119-123)
-int insert_from_host(so_icp_ctx* c, const float* xyz, size_t n, size_t sf, const double T[7]) {
+int insert_from_host(so_icp_ctx* c, const float* xyz, size_t n, size_t sf, const double T[7], const FrameIntensity& fi) {
   std::vector<float> w(n * 3);
   for (size_t i = 0; i < n; ++i) {
     double ox, oy, oz;
     quat_rotate<double>(T + 3, (double)xyz[i * sf], (double)xyz[i * sf + 1], (double)xyz[i * sf + 2], ox, oy, oz);
     w[3 * i] = (float)(ox + T[0]); w[3 * i + 1] = (float)(oy + T[1]); w[3 * i + 2] = (float)(oz + T[2]);
   }
-  if (c->dmap) { const int r = c->dmap->add_surf_host(w.data(), n, 3, c->err); return r < 0 ? map_status(r) : exchange_map_counts(c); }
+  if (c->dmap) { const int r = c->dmap->add_surf_host(w.data(), n, 3, c->err, fi.host, fi.stride_floats); return r < 0 ? map_status(r) : exchange_map_counts(c); }
   return c->map.add_surf(w.data(), n, 3) < 0 ? fail(c, SO_ICP_E_INVALID, "LocalMap insert failed") : SO_ICP_OK;
 }
 
@@ -55,7 +83,8 @@ int register_and_insert(so_icp_ctx* c, const FrameScan& s, const float* d_scan, 
   // The insert, LidarSlam.cpp:163-167.  With a device map it reads the copy the registration ran on, which is still resident -- the
   // caller's, a stage slot or d_scan_own --, never the host buffer; without one the points are needed on the host (the resident entry
   // has handed such a context to the host entry)
-  rc = c->dmap ? insert_resident(c, d_scan, s.n, pose_out) : insert_from_host(c, s.xyz, s.n, s.stride_bytes / 4, pose_out);
+  const FrameIntensity fi = frame_intensity(c, s);
+  rc = c->dmap ? insert_resident(c, d_scan, s.n, pose_out, fi) : insert_from_host(c, s.xyz, s.n, s.stride_bytes / 4, pose_out, fi);
   if (rc) return rc;
   c->last_time = time;
   return SO_ICP_OK;
@@ -72,7 +101,8 @@ int localization_frame(so_icp_ctx* c, int initialization, const double T_in[7], 
     // transforms give the same bits: neither is routed through the other.)
     if (s.on_host && !c->host_only) drop_staged(c, s.xyz, s.n, s.stride_bytes);
     if (c->dmap) c->dmap->set_origin(T_in); else c->map.set_origin(T_in);
-    const int r = s.on_host ? insert_from_host(c, s.xyz, s.n, s.stride_bytes / 4, T_in) : insert_resident(c, s.xyz, s.n, T_in);
+    const FrameIntensity fi = frame_intensity(c, s);
+    const int r = s.on_host ? insert_from_host(c, s.xyz, s.n, s.stride_bytes / 4, T_in, fi) : insert_resident(c, s.xyz, s.n, T_in, fi);
     if (r) return r;
     c->last_time = time;
     return SO_ICP_MAP_SEEDED;

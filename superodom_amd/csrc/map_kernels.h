@@ -100,6 +100,9 @@ struct MapInsertArgs {
   const float* d_xyz;        // new world-frame points (device)
   uint32_t n_new, stride_floats, n_old;  // n_old: the round's old points (device-built round: an upper bound -- the kernels take the number from d_tt)
   uint32_t n_old_grid;       // device-built round: the number of old points the launches are sized for (an estimate; the kernels stride); 0 = n_old
+  const float* d_inten; uint32_t inten_stride;  // intensity of new point i at d_inten[i * inten_stride]; nullptr: 0.  Carried into the
+                                                // fourth lane of the pool and averaged per leaf like x y z; no kernel decides anything by it
+  bool intensity;            // the map carries intensities (this insert's or an earlier one's): the grouping kernels run the fourth sum
   const int32_t* d_cube_of;  // per new point: cube index or -1
   float inv_leaf;
   int32_t nc; uint32_t ncell1; double inv_cell;
@@ -146,6 +149,8 @@ void launch_vg_decide(const double* d_part, int blocks, uint32_t n, int auto_vox
                       uint32_t* d_counters, unsigned long long* d_scan_state, uint32_t n_state, hipStream_t s);
 struct VoxelFilterArgs {
   const float* d_xyz; uint32_t n, stride_floats;
+  const float* d_inten; uint32_t inten_stride;  // intensity of point i at d_inten[i * inten_stride]; nullptr: 0
+  float* d_out_inten;                           // non-null: the leaves' intensities, index for index with d_out
   float inv_leaf; int min_b[3], div_b[3];
   const VgDecision* d_decision;  // non-null: inv_leaf / min_b / div_b are read from here on the device; d_n_cent[kVgCntLeaves] is copied to its n_leaves
   unsigned long long* scan_state; uint32_t n_scan_state;  // non-null (all zero, d_n_cent[kVgCntTicket] too): flags + scan + heads in one launch
@@ -173,7 +178,8 @@ void launch_map_retable(const MapInsertArgs& a, hipStream_t s);  // resolution c
 void launch_shard_select(const float* d_xyz, uint32_t n, const MapTouched& tt, float inv_leaf, int nc, double inv_cell, int rank, int world,
                          float4* pool_slot, uint32_t cap, uint32_t* d_counters, hipStream_t s);
 void launch_gather_export(const float4* pool, uint32_t cap, uint32_t slot, uint32_t count, float* d_out, hipStream_t s);
-void launch_gather_export_records(const float4* pool, uint32_t cap, uint32_t slot, uint32_t count, uint32_t* d_out_words, uint32_t stride_words, hipStream_t s);
+void launch_gather_export_records(const float4* pool, uint32_t cap, uint32_t slot, uint32_t count, uint32_t* d_out_words, uint32_t stride_words,
+                                  bool with_intensity /* 1.0f at word 3, the pool's fourth lane at word 4 */, hipStream_t s);
 // pointAssociateToMap over a cloud (registered scan of the node): records rewritten in place, keep flags, number kept
 void launch_transform_cloud(uint8_t* d_pts, uint32_t n, uint32_t stride, const Pose& pose, uint8_t* d_keep, uint32_t* d_n_kept /* zeroed */, hipStream_t s);
 // removePointDistortion: records of `stride` bytes (float x y z at 0 4 8, float time at time_off), rewritten in place

@@ -208,7 +208,7 @@ __device__ __forceinline__ int touched_index(const MapTouched& tt, int cube) {
 }
 
 __global__ __launch_bounds__(256) void append_new_kernel(const float* __restrict__ xyz, uint32_t n, uint32_t stride_floats,
-                                                         const int32_t* __restrict__ cube_of,
+                                                         const float* __restrict__ inten, uint32_t inten_stride, const int32_t* __restrict__ cube_of,
                                                          const MapTouched* __restrict__ ttp, float inv_leaf, uint32_t n_old, float4* __restrict__ wpts,
                                                          uint32_t* __restrict__ keys, uint32_t* __restrict__ vals, int nc, double inv_cell,
                                                          int rank, int world) {
@@ -218,7 +218,7 @@ __global__ __launch_bounds__(256) void append_new_kernel(const float* __restrict
   const float* p = xyz + (size_t)i * stride_floats;
   const int cube = cube_of[i];
   const uint32_t e = n_old + i;
-  wpts[e] = make_float4(p[0], p[1], p[2], 0.f);
+  wpts[e] = make_float4(p[0], p[1], p[2], inten ? inten[(size_t)i * inten_stride] : 0.f);  // (intensity: carried, never looked at)
   vals[e] = e;
   if (cube < 0) { keys[e] = 0xFFFFFFFFu; return; }  // outside the 21x21x11 window: dropped (LocalMap.h:605)
   const int t = touched_index(tt, cube);
@@ -298,16 +298,19 @@ __device__ __forceinline__ bool defer_long_leaf(uint32_t o, uint32_t len, uint32
   return true;
 }
 
+// A leaf's intensity: pcl::CentroidPoint<PointXYZI>'s AccumulatorIntensity -- a float sum of its own, in the member order of the x y z
+// sums, divided by the same float count.  (PCL is not part of this project's oracle: the rule is restated, like the x y z centroid.)
+__device__ __forceinline__ float leaf_intensity(float sum, uint32_t count) { return sum / (float)count; }
 // centroid = float sum / float count, then its cell key for the second sort
 // (cc.grid != nullptr: the centroid is also counted into its cell of the dense grids right away -- the second stage's
 //  cell_count_kernel folded into the kernels that produce the centroids; its rank inside the cell goes to cc.rank[o])
 struct CellCount { uint32_t* grid; uint32_t* rank; uint32_t ncell1; };
-__device__ __forceinline__ uint32_t emit_centroid(uint32_t o, uint32_t key, float s0, float s1, float s2, uint32_t count, const MapTouched& tt,
+__device__ __forceinline__ uint32_t emit_centroid(uint32_t o, uint32_t key, float s0, float s1, float s2, float inten, uint32_t count, const MapTouched& tt,
                                                   int nc, double inv_cell, float4* __restrict__ cent, uint32_t* __restrict__ keys2,
                                                   uint32_t* __restrict__ vals2, const CellCount cc = CellCount{nullptr, nullptr, 0u}) {
   const float cnt = (float)count;
   const float cx = s0 / cnt, cy = s1 / cnt, cz = s2 / cnt;
-  cent[o] = make_float4(cx, cy, cz, 0.f);
+  cent[o] = make_float4(cx, cy, cz, inten);  // (the leaf's intensity, see leaf_intensity: carried, decides nothing below)
   const int t = (int)(key >> (3u * tt.lbits));
   int g[3];
   cell_coords(cx, cy, cz, tt.cube_min[t], inv_cell, nc, g);
@@ -439,7 +442,7 @@ __global__ __launch_bounds__(256) void leaf_centroid_kernel(const uint32_t* __re
   const uint32_t beg = heads[o], end = heads[o + 1];
   const uint32_t key = keys[beg];
   if (defer_long_leaf(o, long_list ? end - beg : 0u, long_list, long_count)) return;  // (no list: no leaf is long; else leaf_centroid_long_kernel takes it)
-  float s0 = 0.f, s1 = 0.f, s2 = 0.f;
+  float s0 = 0.f, s1 = 0.f, s2 = 0.f, s3 = 0.f;
   constexpr int B = 16;
   float4 cur[B], nxt[B];
 #pragma unroll
@@ -452,11 +455,11 @@ __global__ __launch_bounds__(256) void leaf_centroid_kernel(const uint32_t* __re
     }
 #pragma unroll
     for (int k = 0; k < B; ++k)
-      if (j + k < end) { s0 += cur[k].x; s1 += cur[k].y; s2 += cur[k].z; }
+      if (j + k < end) { s0 += cur[k].x; s1 += cur[k].y; s2 += cur[k].z; s3 += cur[k].w; }
 #pragma unroll
     for (int k = 0; k < B; ++k) cur[k] = nxt[k];
   }
-  emit_centroid(o, key, s0, s1, s2, end - beg, tt, nc, inv_cell, cent, keys2, vals2);
+  emit_centroid(o, key, s0, s1, s2, leaf_intensity(s3, end - beg), end - beg, tt, nc, inv_cell, cent, keys2, vals2);
 }
 
 // leaves with more than kLongLeaf points (the ground right under the sensor: ~1000 scan points in one 0.2 m leaf): one
@@ -473,7 +476,7 @@ __global__ __launch_bounds__(256) void leaf_centroid_long_kernel(const uint32_t*
   if (w >= n_long) return;
   const uint32_t o = long_list[w];
   const uint32_t beg = heads[o], end = heads[o + 1];
-  float s0 = 0.f, s1 = 0.f, s2 = 0.f;
+  float s0 = 0.f, s1 = 0.f, s2 = 0.f, s3 = 0.f;
   float4 cur = spts[beg + lane < end ? beg + lane : end - 1];
   for (uint32_t j = beg; j < end; j += 64) {
     const uint32_t jn = j + 64;
@@ -482,16 +485,17 @@ __global__ __launch_bounds__(256) void leaf_centroid_long_kernel(const uint32_t*
     // lanes behind the end contribute +0.0f (s + 0.0f == s exactly), so the in-order sum is a fixed, fully unrolled
     // sequence of 64 lane reads -- the same in every lane
     const bool live = j + (uint32_t)lane < end;
-    const float x = live ? cur.x : 0.f, y = live ? cur.y : 0.f, z = live ? cur.z : 0.f;
+    const float x = live ? cur.x : 0.f, y = live ? cur.y : 0.f, z = live ? cur.z : 0.f, iw = live ? cur.w : 0.f;
 #pragma unroll
     for (int k = 0; k < 64; ++k) {
       s0 += __uint_as_float(__builtin_amdgcn_readlane(__float_as_uint(x), k));
       s1 += __uint_as_float(__builtin_amdgcn_readlane(__float_as_uint(y), k));
       s2 += __uint_as_float(__builtin_amdgcn_readlane(__float_as_uint(z), k));
+      s3 += __uint_as_float(__builtin_amdgcn_readlane(__float_as_uint(iw), k));
     }
     cur = nxt;
   }
-  if (lane == 0) emit_centroid(o, keys[beg], s0, s1, s2, end - beg, tt, nc, inv_cell, cent, keys2, vals2);
+  if (lane == 0) emit_centroid(o, keys[beg], s0, s1, s2, leaf_intensity(s3, end - beg), end - beg, tt, nc, inv_cell, cent, keys2, vals2);
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -514,7 +518,7 @@ __device__ __forceinline__ uint32_t leaf_hash(uint32_t key, uint32_t log2_size) 
 
 // (the new points' part of the working set -- append_new_kernel's job on the sort path -- is produced here as well: one launch less)
 __global__ __launch_bounds__(256) void leafhash_insert_new_kernel(const float* __restrict__ xyz, uint32_t n_new, uint32_t stride_floats,
-                                                                  const int32_t* __restrict__ cube_of,
+                                                                  const float* __restrict__ inten, uint32_t inten_stride, const int32_t* __restrict__ cube_of,
                                                                   const MapTouched* __restrict__ ttp, float inv_leaf, int nc, double inv_cell, int rank, int world,
                                                                   float4* __restrict__ wpts, uint32_t* __restrict__ keys, LeafTable ht,
                                                                   uint32_t* __restrict__ mslot, uint32_t* __restrict__ mrank) {
@@ -525,7 +529,7 @@ __global__ __launch_bounds__(256) void leafhash_insert_new_kernel(const float* _
   uint32_t key = kLeafEmpty;
   if (i < n_new) {
     const float* p = xyz + (size_t)i * stride_floats;
-    wpts[e] = make_float4(p[0], p[1], p[2], 0.f);
+    wpts[e] = make_float4(p[0], p[1], p[2], inten ? inten[(size_t)i * inten_stride] : 0.f);
     const int cube = cube_of[i];
     const int t = cube < 0 ? -1 : touched_index(tt, cube);  // outside the 21x21x11 window (LocalMap.h:605) / a cube of another round: dropped
     if (t >= 0 && !(world > 1 && !shard_keeps_leaf(p[0], p[1], p[2], inv_leaf, tt, t, nc, inv_cell, rank, world)))
@@ -598,7 +602,7 @@ __global__ __launch_bounds__(256) void leafhash_match_old_kernel(const float4* _
         keys2[e] = kLeafEmpty;  // a hole of the centroid index space: the point lives on in its group
       } else {
         // the only point of its leaf: sum = 0 + p, count = 1
-        k2 = emit_centroid(e, key, 0.f + p.x, 0.f + p.y, 0.f + p.z, 1u, tt, nc, inv_cell, cent, keys2, nullptr);
+        k2 = emit_centroid(e, key, 0.f + p.x, 0.f + p.y, 0.f + p.z, 0.f + p.w /* sum / 1.0f */, 1u, tt, nc, inv_cell, cent, keys2, nullptr);
       }
     }
     if (cc.grid) {
@@ -694,6 +698,9 @@ __global__ __launch_bounds__(256) void leafhash_place_kernel(const uint32_t* __r
 // Groups of up to 16 members: one thread per group (sorting network in registers): 95 % of the groups of a raw 128-beam
 // sweep.  Groups of 17..64 (leafhash_offsets_kernel's medium list): one wavefront each (bitonic network over the lanes,
 // then the sum in lane order).  ONE launch: workgroups [0, small_blocks) take the first kind, the others the second.
+// INTEN (all three kinds): the map carries intensities -- the fourth sum runs beside x, y, z; without it the fourth lane is written as 0,
+// the code of a map that never saw one (MapInsertArgs::intensity)
+template <bool INTEN>
 __device__ __forceinline__ void leafhash_small_groups(uint32_t g, const uint32_t* __restrict__ gstart, const uint32_t* __restrict__ gcount,
                                                       const unsigned long long* __restrict__ cursor, const uint32_t* __restrict__ members,
                                                       const float4* __restrict__ wpts, const uint32_t* __restrict__ leaf_keys,
@@ -712,14 +719,14 @@ __device__ __forceinline__ void leafhash_small_groups(uint32_t g, const uint32_t
 #define SO_CSWAP(a, b) { t = min(a, b); b = max(a, b); a = t; }
     SO_CSWAP(e[0], e[1]) SO_CSWAP(e[2], e[3]) SO_CSWAP(e[0], e[2]) SO_CSWAP(e[1], e[3]) SO_CSWAP(e[1], e[2])
 #undef SO_CSWAP
-    float s0 = 0.f, s1 = 0.f, s2 = 0.f;
+    float s0 = 0.f, s1 = 0.f, s2 = 0.f, s3 = 0.f;
     float4 p[4];
 #pragma unroll
     for (int k = 0; k < 4; ++k) p[k] = wpts[(uint32_t)k < cnt ? e[k] : e[0]];
 #pragma unroll
     for (int k = 0; k < 4; ++k)
-      if ((uint32_t)k < cnt) { s0 += p[k].x; s1 += p[k].y; s2 += p[k].z; }
-    emit_centroid(n_old + g, leaf_keys[e[0]], s0, s1, s2, cnt, tt, nc, inv_cell, cent, keys2, nullptr, cc);
+      if ((uint32_t)k < cnt) { s0 += p[k].x; s1 += p[k].y; s2 += p[k].z; if (INTEN) s3 += p[k].w; }
+    emit_centroid(n_old + g, leaf_keys[e[0]], s0, s1, s2, INTEN ? leaf_intensity(s3, cnt) : 0.f, cnt, tt, nc, inv_cell, cent, keys2, nullptr, cc);
     return;
   }
 #pragma unroll
@@ -743,13 +750,14 @@ __device__ __forceinline__ void leafhash_small_groups(uint32_t g, const uint32_t
   float4 p[16];
 #pragma unroll
   for (int k = 0; k < 16; ++k) p[k] = wpts[(uint32_t)k < cnt ? e[k] : e[0]];
-  float s0 = 0.f, s1 = 0.f, s2 = 0.f;
+  float s0 = 0.f, s1 = 0.f, s2 = 0.f, s3 = 0.f;
 #pragma unroll
   for (int k = 0; k < 16; ++k)
-    if ((uint32_t)k < cnt) { s0 += p[k].x; s1 += p[k].y; s2 += p[k].z; }
-  emit_centroid(n_old + g, leaf_keys[e[0]], s0, s1, s2, cnt, tt, nc, inv_cell, cent, keys2, nullptr, cc);
+    if ((uint32_t)k < cnt) { s0 += p[k].x; s1 += p[k].y; s2 += p[k].z; if (INTEN) s3 += p[k].w; }
+  emit_centroid(n_old + g, leaf_keys[e[0]], s0, s1, s2, INTEN ? leaf_intensity(s3, cnt) : 0.f, cnt, tt, nc, inv_cell, cent, keys2, nullptr, cc);
 }
 
+template <bool INTEN>
 __device__ __forceinline__ void leafhash_medium_groups(uint32_t first_wave, uint32_t n_waves, int lane, const uint32_t* __restrict__ gstart,
                                                        const uint32_t* __restrict__ gcount, const uint32_t* __restrict__ members,
                                                        const float4* __restrict__ wpts, const uint32_t* __restrict__ leaf_keys, uint32_t n_old,
@@ -773,16 +781,17 @@ __device__ __forceinline__ void leafhash_medium_groups(uint32_t first_wave, uint
     // lane i now holds the group's i-th member in working-set order; lanes behind the end contribute +0.0f (s + 0.0f == s)
     const float4 p = wpts[(uint32_t)lane < c ? v : 0u];
     const bool live = (uint32_t)lane < c;
-    const float x = live ? p.x : 0.f, y = live ? p.y : 0.f, z = live ? p.z : 0.f;
-    float s0 = 0.f, s1 = 0.f, s2 = 0.f;
+    const float x = live ? p.x : 0.f, y = live ? p.y : 0.f, z = live ? p.z : 0.f, iw = live ? p.w : 0.f;
+    float s0 = 0.f, s1 = 0.f, s2 = 0.f, s3 = 0.f;
 #pragma unroll
     for (int k = 0; k < 64; ++k) {
       s0 += __uint_as_float(__builtin_amdgcn_readlane(__float_as_uint(x), k));
       s1 += __uint_as_float(__builtin_amdgcn_readlane(__float_as_uint(y), k));
       s2 += __uint_as_float(__builtin_amdgcn_readlane(__float_as_uint(z), k));
+      if (INTEN) s3 += __uint_as_float(__builtin_amdgcn_readlane(__float_as_uint(iw), k));
     }
     const uint32_t first = (uint32_t)__builtin_amdgcn_readlane((int)v, 0);
-    if (lane == 0) emit_centroid(n_old + g, leaf_keys[first], s0, s1, s2, c, tt, nc, inv_cell, cent, keys2, nullptr, cc);
+    if (lane == 0) emit_centroid(n_old + g, leaf_keys[first], s0, s1, s2, INTEN ? leaf_intensity(s3, c) : 0.f, c, tt, nc, inv_cell, cent, keys2, nullptr, cc);
   }
 }
 
@@ -792,19 +801,21 @@ __device__ __forceinline__ void leafhash_medium_groups(uint32_t first_wave, uint
 // working-set order follows from its wavefront: members are counted per wavefront (a direct-address table in LDS, one
 // entry per 64 scan points), a scan turns the counts into run positions, and inside its run a member sits where it
 // sits in the list.  (A 2 048-element bitonic sort in LDS took 150 us here, ranking the runs against each other 35 us.)
-// The points are gathered into LDS in final order and three wavefronts add up x, y and z in sequence, 64 values per
+// The points are gathered into LDS in final order and four wavefronts add up x, y, z and the intensity in sequence, 64 values per
 // round out of their lanes.  More members than kGiantCap, more than 64 x kGiantCap new points in the round, or more than
 // 64 old points in one leaf: *overflow is raised, the second stage stands still and the host repeats the round with the
 // sort-based first stage.
 constexpr int kGiantThreads = 1024;                       // four members per thread at most: one round trip per phase
-// dynamic LDS: x, y, z of up to kGiantCap members + per-wavefront counts and first list positions, one entry per wavefront of
-// leafhash_insert_new_kernel rounded up to the workgroup size (64 KB for a 131 072-point sweep: two workgroups per CU)
+// dynamic LDS: x, y, z (and, when the map carries it, the intensity) of up to kGiantCap members + per-wavefront counts and first list positions, one entry per
+// wavefront of leafhash_insert_new_kernel rounded up to the workgroup size (64 KB for a 131 072-point sweep, 80 KB with the intensity: two
+// workgroups in a compute unit's 160 KiB either way, and 32 wavefronts per compute unit allow no more than two of 1 024 threads)
 static inline uint32_t giant_hist_entries(uint32_t n_new) {
   const uint32_t nb = (n_new + 63u) >> 6;
   const uint32_t r = (nb + kGiantThreads - 1u) / kGiantThreads * kGiantThreads;
   return r < (uint32_t)kGiantThreads ? (uint32_t)kGiantThreads : (r > kGiantCap ? kGiantCap : r);
 }
-static inline size_t giant_lds_bytes(uint32_t n_new) { return ((size_t)kGiantCap * 3 + (size_t)giant_hist_entries(n_new) * 2) * 4; }
+static inline size_t giant_lds_bytes(uint32_t n_new, bool inten) { return ((size_t)kGiantCap * (inten ? 4 : 3) + (size_t)giant_hist_entries(n_new) * 2) * 4; }
+template <bool INTEN>
 __device__ __forceinline__ void leafhash_giant_groups(uint32_t first_leaf, uint32_t leaf_stride, const uint32_t* __restrict__ gstart,
                                                       const uint32_t* __restrict__ gcount, const uint32_t* __restrict__ members,
                                                       const float4* __restrict__ wpts, const uint32_t* __restrict__ leaf_keys, uint32_t n_old,
@@ -815,9 +826,10 @@ __device__ __forceinline__ void leafhash_giant_groups(uint32_t first_leaf, uint3
   float* sx = reinterpret_cast<float*>(lds);
   float* sy = reinterpret_cast<float*>(lds + kGiantCap);
   float* sz = reinterpret_cast<float*>(lds + 2 * kGiantCap);
-  uint32_t* hist = lds + 3 * kGiantCap;   // [nhist]: nhist = giant_hist_entries(n_new), a multiple of the workgroup size
+  float* sw = reinterpret_cast<float*>(lds + 3 * kGiantCap);  // intensity (INTEN)
+  uint32_t* hist = lds + (INTEN ? 4 : 3) * kGiantCap;   // [nhist]: nhist = giant_hist_entries(n_new), a multiple of the workgroup size
   uint32_t* fpos = hist + nhist;
-  __shared__ uint32_t wtot[kGiantThreads / 64], sums[3], olds[64], n_olds, first_e;
+  __shared__ uint32_t wtot[kGiantThreads / 64], sums[4], olds[64], n_olds, first_e;
   const int tid = threadIdx.x, lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   constexpr int kPer = kGiantCap / kGiantThreads;  // 4
   const uint32_t hper = nhist / (uint32_t)kGiantThreads;  // 1..4 table entries per thread
@@ -884,15 +896,16 @@ __device__ __forceinline__ void leafhash_giant_groups(uint32_t first_leaf, uint3
         at = n_o + hist[b] + (i - fpos[b]);
       }
       sx[at] = p[k].x; sy[at] = p[k].y; sz[at] = p[k].z;
+      if (INTEN) sw[at] = p[k].w;
       if (at == 0) first_e = e[k];  // the first member in working-set order (its leaf key goes with the centroid)
     }
     __syncthreads();
-    if (tid < 192) {
-      // wavefronts 0, 1, 2 add x, y, z: three independent chains of dependent additions, one addition per element.  Every
+    if (tid < (INTEN ? 256 : 192)) {
+      // wavefronts 0, 1, 2 (and 3) add x, y, z (and the intensity): independent chains of dependent additions, one addition per element.  Every
       // lane reads the SAME sixteen values from LDS (a broadcast, no bank conflict) and adds them in order -- the operands
       // arrive in the lane's own registers, the next sixteen are on their way meanwhile.  (Handing the elements of one
       // register around with v_readlane cost readlane + wait state + add per element: 28 us for a leaf of 1 636 points.)
-      const float* src = tid < 64 ? sx : (tid < 128 ? sy : sz);
+      const float* src = tid < 64 ? sx : (tid < 128 ? sy : (tid < 192 ? sz : sw));
       float acc = 0.f;
       const uint32_t n16 = cnt & ~15u;
       float4 bufa[4], bufb[4];  // two register sets taking turns (no copies between them)
@@ -919,8 +932,8 @@ __device__ __forceinline__ void leafhash_giant_groups(uint32_t first_leaf, uint3
     }
     __syncthreads();
     if (tid == 0)
-      emit_centroid(n_old + g, leaf_keys[first_e], __uint_as_float(sums[0]), __uint_as_float(sums[1]), __uint_as_float(sums[2]), cnt, tt, nc, inv_cell,
-                    cent, keys2, nullptr, cc);
+      emit_centroid(n_old + g, leaf_keys[first_e], __uint_as_float(sums[0]), __uint_as_float(sums[1]), __uint_as_float(sums[2]),
+                    INTEN ? leaf_intensity(__uint_as_float(sums[3]), cnt) : 0.f, cnt, tt, nc, inv_cell, cent, keys2, nullptr, cc);
   }
 }
 
@@ -928,6 +941,7 @@ __device__ __forceinline__ void leafhash_giant_groups(uint32_t first_leaf, uint3
 // leaves with more than 64 members (one leaf at a time each), the next small_blocks take one group of up to 16 members per
 // thread, the rest one group of 17..64 members per wavefront.  The few long leaves of a raw sweep (its slowest took 23 us)
 // run beside the ten thousand short ones instead of behind them; workgroups of the first kind without a leaf end at once.
+template <bool INTEN>
 __global__ __launch_bounds__(kGiantThreads) void leafhash_centroids_kernel(const uint32_t* __restrict__ gstart, const uint32_t* __restrict__ gcount,
                                                                  const unsigned long long* __restrict__ cursor, const uint32_t* __restrict__ members,
                                                                  const float4* __restrict__ wpts, const uint32_t* __restrict__ leaf_keys,
@@ -940,17 +954,17 @@ __global__ __launch_bounds__(kGiantThreads) void leafhash_centroids_kernel(const
   const MapTouched& tt = *ttp;
   const uint32_t n_old = tt.old_prefix[kMaxTouched];
   if (blockIdx.x < giant_blocks)
-    leafhash_giant_groups(blockIdx.x, giant_blocks, gstart, gcount, members, wpts, leaf_keys, n_old, n_new, nhist, tt, nc, inv_cell, cent, keys2, giant_list,
+    leafhash_giant_groups<INTEN>(blockIdx.x, giant_blocks, gstart, gcount, members, wpts, leaf_keys, n_old, n_new, nhist, tt, nc, inv_cell, cent, keys2, giant_list,
                           giant_count, overflow, cc);
   else if (blockIdx.x < giant_blocks + small_blocks) {
     // (four of the sixteen wavefronts work, the others end at once: 256 groups per workgroup spread the gathers over all the
     //  compute units -- with 1 024 groups per workgroup half of them sat idle and this part took 19 us instead of 11)
     if (threadIdx.x < 256u)
-      leafhash_small_groups((blockIdx.x - giant_blocks) * 256u + threadIdx.x, gstart, gcount, cursor, members, wpts, leaf_keys, n_old, tt, nc, inv_cell,
+      leafhash_small_groups<INTEN>((blockIdx.x - giant_blocks) * 256u + threadIdx.x, gstart, gcount, cursor, members, wpts, leaf_keys, n_old, tt, nc, inv_cell,
                             cent, keys2, n_cent, cc);
   }
   else
-    leafhash_medium_groups(((blockIdx.x - giant_blocks - small_blocks) * blockDim.x + threadIdx.x) >> 6,
+    leafhash_medium_groups<INTEN>(((blockIdx.x - giant_blocks - small_blocks) * blockDim.x + threadIdx.x) >> 6,
                            ((gridDim.x - giant_blocks - small_blocks) * blockDim.x) >> 6, threadIdx.x & 63, gstart, gcount, members, wpts, leaf_keys, n_old, tt,
                            nc, inv_cell, cent, keys2, medium_list, medium_count, cc);
 }
@@ -963,17 +977,20 @@ __global__ __launch_bounds__(256) void gather_export_kernel(const float4* __rest
   out_xyz[3 * i] = p.x; out_xyz[3 * i + 1] = p.y; out_xyz[3 * i + 2] = p.z;
 }
 
-// the same gather into RECORDS of stride_words 32-bit words -- float x, y, z at words 0..2, the rest zero (pcl::PointXYZI: 8 words, intensity 0):
+// the same gather into RECORDS of stride_words 32-bit words -- float x, y, z at words 0..2, the rest zero; with_intensity: 1.0f at
+// word 3 (data[3] of the PointXYZI constructor) and the intensity at word 4, the 32 bytes pcl::toROSMsg copies per point --:
 // the payload of a sensor_msgs/PointCloud2 as the node publishes its map clouds (laserMapping.cpp:437-462), written where the message is
 __global__ __launch_bounds__(256) void gather_export_records_kernel(const float4* __restrict__ pool, uint32_t cap, uint32_t slot, uint32_t count,
-                                                                    uint32_t* __restrict__ out_words, uint32_t stride_words) {
+                                                                    uint32_t* __restrict__ out_words, uint32_t stride_words, bool with_intensity) {
   const uint32_t t = blockIdx.x * blockDim.x + threadIdx.x;  // one thread per output WORD: coalesced stores whatever the record size
   const uint32_t i = t / stride_words, w = t - i * stride_words;
   if (i >= count) return;
   uint32_t v = 0u;
-  if (w < 3u) {
+  if (w < 3u || (with_intensity && w == 4u)) {
     const float4 p = pool[(size_t)slot * cap + i];
-    v = __float_as_uint(w == 0u ? p.x : (w == 1u ? p.y : p.z));
+    v = __float_as_uint(w == 0u ? p.x : (w == 1u ? p.y : (w == 2u ? p.z : p.w)));
+  } else if (with_intensity && w == 3u) {
+    v = __float_as_uint(1.0f);
   }
   out_words[t] = v;
 }
@@ -1030,7 +1047,7 @@ __global__ __launch_bounds__(256) void cell_table_kernel(const uint32_t* __restr
   cell_start[(size_t)tt.slot[t] * ncell1 + c] = tt.slot[t] * cap + local;
   if (c == ncell1 - 1) counts[t] = local;
 }
-// pass 1: every centroid into its cell's range of a scratch array, at the atomic rank, leaf key in .w
+// pass 1: every centroid (all four lanes) into its cell's range of a scratch array, at the atomic rank, leaf key alongside
 __global__ __launch_bounds__(256) void cell_place_kernel(const uint32_t* __restrict__ keys2, const uint32_t* __restrict__ rank,
                                                          const uint32_t* __restrict__ n_cent, const uint32_t* __restrict__ grid_scan,
                                                          const float4* __restrict__ cent, const MapTouched* __restrict__ ttp, uint32_t ncell1, float inv_leaf,
@@ -1051,8 +1068,8 @@ __global__ __launch_bounds__(256) void cell_place_kernel(const uint32_t* __restr
 // pass 2: final position inside the cell = number of the cell's centroids with a smaller leaf key (one centroid per leaf:
 // the keys are distinct), i.e. ascending leaf order -- what the stable sort by (cell, leaf) produced
 // (After a resolution change -- launch_map_retable -- a cube may hold points of an older, different leaf grid, where two
-//  points can share a leaf key: the order then falls back on the coordinates' bit patterns and, for bitwise equal points,
-//  on the placement rank, so that every point keeps a position of its own.)
+//  points can share a leaf key: the order then falls back on the coordinates' bit patterns, then the intensity's, and, for bitwise
+//  equal records, on the placement rank, so that every point keeps a position of its own.)
 __global__ __launch_bounds__(256) void cell_rank_kernel(const uint32_t* __restrict__ keys2, const uint32_t* __restrict__ n_cent,
                                                         const uint32_t* __restrict__ grid_scan,
                                                         const float4* __restrict__ cent, const float4* __restrict__ tmp,
@@ -1078,7 +1095,8 @@ __global__ __launch_bounds__(256) void cell_rank_kernel(const uint32_t* __restri
         const float4 u = tmp[beg + j];
         const uint32_t ux = __float_as_uint(u.x), uy = __float_as_uint(u.y), uz = __float_as_uint(u.z);
         const uint32_t vx = __float_as_uint(v.x), vy = __float_as_uint(v.y), vz = __float_as_uint(v.z);
-        less = uz != vz ? uz < vz : (uy != vy ? uy < vy : (ux != vx ? ux < vx : j < mine));
+        const uint32_t uw = __float_as_uint(u.w), vw = __float_as_uint(v.w);
+        less = uz != vz ? uz < vz : (uy != vy ? uy < vy : (ux != vx ? ux < vx : (uw != vw ? uw < vw : j < mine)));
       }
       r += less ? 1u : 0u;
     }
@@ -1365,7 +1383,8 @@ __global__ __launch_bounds__(256) void vg_stats_kernel(const float* __restrict__
 }
 
 // pcl::VoxelGrid leaf index: ijk = floor(p * inv_leaf) - min_b in float arithmetic, idx = i0 + i1*d0 + i2*d0*d1
-__global__ __launch_bounds__(256) void vg_keys_kernel(const float* __restrict__ xyz, uint32_t n, uint32_t stride_floats, float inv_leaf,
+__global__ __launch_bounds__(256) void vg_keys_kernel(const float* __restrict__ xyz, uint32_t n, uint32_t stride_floats,
+                                                      const float* __restrict__ inten, uint32_t inten_stride, float inv_leaf,
                                                       int mb0, int mb1, int mb2, int d0, int d01, float4* __restrict__ wpts,
                                                       uint32_t* __restrict__ keys, uint32_t* __restrict__ vals,
                                                       const VgDecision* __restrict__ dec) {
@@ -1377,15 +1396,17 @@ __global__ __launch_bounds__(256) void vg_keys_kernel(const float* __restrict__ 
   }
   const float* p = xyz + (size_t)i * stride_floats;
   const float x = p[0], y = p[1], z = p[2];
-  wpts[i] = make_float4(x, y, z, 0.f);
+  wpts[i] = make_float4(x, y, z, inten ? inten[(size_t)i * inten_stride] : 0.f);
   vals[i] = i;
   const int i0 = (int)(floorf(x * inv_leaf) - (float)mb0), i1 = (int)(floorf(y * inv_leaf) - (float)mb1), i2 = (int)(floorf(z * inv_leaf) - (float)mb2);
   keys[i] = (uint32_t)(i0 + i1 * d0 + i2 * d01);
 }
 
-// centroid of every leaf (float sums in the stable-sorted input order), packed xyz out; long leaves go to the wavefront kernel
+// centroid of every leaf (float sums in the stable-sorted input order), packed xyz out -- and, out_i given, the leaf's intensity
+// (downsample_all_data: the same sum over the fourth field) in an array of its own; long leaves go to the wavefront kernel
+template <bool INTEN>
 __global__ __launch_bounds__(256) void vg_centroid_kernel(const uint32_t* __restrict__ heads, const uint32_t* __restrict__ n_cent,
-                                                          const float4* __restrict__ spts, float* __restrict__ out,
+                                                          const float4* __restrict__ spts, float* __restrict__ out, float* __restrict__ out_i,
                                                           uint32_t* __restrict__ long_list, uint32_t* __restrict__ long_count,
                                                           VgDecision* __restrict__ dec) {
   const uint32_t o = blockIdx.x * blockDim.x + threadIdx.x;
@@ -1393,7 +1414,7 @@ __global__ __launch_bounds__(256) void vg_centroid_kernel(const uint32_t* __rest
   if (o >= *n_cent) return;
   const uint32_t beg = heads[o], end = heads[o + 1];
   if (defer_long_leaf(o, end - beg, long_list, long_count)) return;  // (vg_centroid_long_kernel takes it)
-  float s0 = 0.f, s1 = 0.f, s2 = 0.f;
+  float s0 = 0.f, s1 = 0.f, s2 = 0.f, s3 = 0.f;
   constexpr int B = 16;
   for (uint32_t j = beg; j < end; j += B) {
     float4 cur[B];
@@ -1401,26 +1422,28 @@ __global__ __launch_bounds__(256) void vg_centroid_kernel(const uint32_t* __rest
     for (int k = 0; k < B; ++k) cur[k] = spts[j + k < end ? j + k : end - 1];
 #pragma unroll
     for (int k = 0; k < B; ++k)
-      if (j + k < end) { s0 += cur[k].x; s1 += cur[k].y; s2 += cur[k].z; }
+      if (j + k < end) { s0 += cur[k].x; s1 += cur[k].y; s2 += cur[k].z; if (INTEN) s3 += cur[k].w; }
   }
   const float cnt = (float)(end - beg);
   out[3 * (size_t)o] = s0 / cnt; out[3 * (size_t)o + 1] = s1 / cnt; out[3 * (size_t)o + 2] = s2 / cnt;
+  if (INTEN) out_i[o] = leaf_intensity(s3, end - beg);
 }
 // long leaves (the ground under the sensor: up to ~1 600 points of a raw sweep in one leaf): one WAVEFRONT per leaf and
-// coordinate.  The wavefront fetches 256 points at a time (coalesced, the next 256 in flight), parks its coordinate in LDS,
+// coordinate (and one more for the intensity when it is asked for).  The wavefront fetches 256 points at a time (coalesced, the next 256 in flight), parks its coordinate in LDS,
 // and every lane adds the same values in order from its own registers: one dependent addition per element (handing the
 // elements around with v_readlane cost readlane + wait state + add per element and coordinate: 20 us for 1 636 points).
 // Values behind the end of the leaf are +0.0f (s + 0.0f == s).
 __global__ __launch_bounds__(256) void vg_centroid_long_kernel(const uint32_t* __restrict__ heads, const float4* __restrict__ spts,
-                                                               float* __restrict__ out, const uint32_t* __restrict__ long_list,
-                                                               const uint32_t* __restrict__ long_count) {
+                                                               float* __restrict__ out, float* __restrict__ out_i,
+                                                               const uint32_t* __restrict__ long_list, const uint32_t* __restrict__ long_count) {
   __shared__ __attribute__((aligned(16))) float buf[4][2][256];
+  const uint32_t n_axes = out_i ? 4u : 3u;  // (the fourth field of the points: the intensity)
   const uint32_t w = (blockIdx.x * blockDim.x + threadIdx.x) >> 6;
   const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
   const uint32_t n_long = *long_count < kMaxLongLeaves ? *long_count : kMaxLongLeaves;
-  if (w >= 3u * n_long) return;
-  const uint32_t o = long_list[w / 3u];
-  const uint32_t axis = w % 3u;
+  if (w >= n_axes * n_long) return;
+  const uint32_t o = long_list[w / n_axes];
+  const uint32_t axis = w % n_axes;
   const uint32_t beg = heads[o], end = heads[o + 1];
   const float* src = reinterpret_cast<const float*>(spts) + axis;
   float s = 0.f;
@@ -1449,7 +1472,10 @@ __global__ __launch_bounds__(256) void vg_centroid_long_kernel(const uint32_t* _
       s += v.x; s += v.y; s += v.z; s += v.w;
     }
   }
-  if (lane == 0) out[3 * (size_t)o + axis] = s / (float)(end - beg);
+  if (lane == 0) {
+    if (axis < 3u) out[3 * (size_t)o + axis] = s / (float)(end - beg);
+    else out_i[o] = s / (float)(end - beg);
+  }
 }
 
 // adjustVoxelSize's decision and the leaf grid of pcl::VoxelGrid, on the device (VgDecision): what so_icp_prefilter_scan used to
@@ -1595,8 +1621,8 @@ static uint32_t* launch_first_stage_hashed(const MapInsertArgs& a, hipStream_t s
   uint32_t* giant_list = medium_list + a.n_new / 16u + 2u;
   const uint32_t n_old_grid = a.n_old_grid ? a.n_old_grid : a.n_old, total = n_old_grid + a.n_new;  // (launch sizes)
   if (a.n_new)
-    hipLaunchKernelGGL(leafhash_insert_new_kernel, grid_for(a.n_new, 256), dim3(256), 0, s, a.d_xyz, a.n_new, a.stride_floats, a.d_cube_of,
-                       a.d_tt, a.inv_leaf, a.nc, a.inv_cell, a.rank, a.world, a.wpts, a.keys0, ht, a.keys1, a.vals1);
+    hipLaunchKernelGGL(leafhash_insert_new_kernel, grid_for(a.n_new, 256), dim3(256), 0, s, a.d_xyz, a.n_new, a.stride_floats, a.d_inten,
+                       a.inten_stride, a.d_cube_of, a.d_tt, a.inv_leaf, a.nc, a.inv_cell, a.rank, a.world, a.wpts, a.keys0, ht, a.keys1, a.vals1);
   if (a.n_old)
     hipLaunchKernelGGL(leafhash_match_old_kernel, grid_for(n_old_grid, 256), dim3(256), 0, s, a.pool, a.cap, a.inv_leaf, a.keys0, a.wpts, ht,
                        a.keys1, a.vals1, a.d_tt, a.nc, a.inv_cell, a.cent, keys2, cc);
@@ -1606,11 +1632,14 @@ static uint32_t* launch_first_stage_hashed(const MapInsertArgs& a, hipStream_t s
   const uint32_t max_medium = a.n_new / 16u + 1u, max_giant = a.n_new / 64u + 1u;
   const uint32_t small_blocks = (a.n_new ? a.n_new + 255u : 256u) / 256u;  // (256 groups per workgroup, see the kernel)
   const uint32_t medium_blocks = max_medium < 2048u ? (max_medium + 15u) / 16u : 128u, giant_blocks = max_giant < 512u ? max_giant : 512u;
-  const size_t giant_lds = giant_lds_bytes(a.n_new);
+  const size_t giant_lds = giant_lds_bytes(a.n_new, a.intensity);
   const uint32_t nhist = giant_hist_entries(a.n_new);
+  // (the fourth sum is compiled in only for a map that carries intensities: always on, it put leafhash_centroids_kernel above the
+  //  spread of its own run-to-run times -- profiles/map_intensity/README.md)
+  auto centroids = a.intensity ? leafhash_centroids_kernel<true> : leafhash_centroids_kernel<false>;
   // (per launch, not once per process: the attribute belongs to the current device, and one process may drive several)
-  (void)hipFuncSetAttribute(reinterpret_cast<const void*>(leafhash_centroids_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)giant_lds);
-  hipLaunchKernelGGL(leafhash_centroids_kernel, dim3(giant_blocks + small_blocks + medium_blocks), dim3(kGiantThreads), giant_lds, s, a.heads, a.flags, cursor,
+  (void)hipFuncSetAttribute(reinterpret_cast<const void*>(centroids), hipFuncAttributeMaxDynamicSharedMemorySize, (int)giant_lds);
+  hipLaunchKernelGGL(centroids, dim3(giant_blocks + small_blocks + medium_blocks), dim3(kGiantThreads), giant_lds, s, a.heads, a.flags, cursor,
                      a.pos, a.wpts, a.keys0, a.n_new, nhist, a.d_tt, a.nc, a.inv_cell, a.cent, keys2, a.d_n_cent, medium_list, medium_count, giant_list,
                      giant_count, halt_word(a), giant_blocks, small_blocks, cc);
   return keys2;
@@ -1634,8 +1663,8 @@ void launch_map_insert(const MapInsertArgs& a, hipStream_t s) {
     } else if (a.n_old)
       hipLaunchKernelGGL(gather_old_kernel, grid_for(a.n_old, 256), dim3(256), 0, s, a.d_tt, a.pool, a.cap, a.inv_leaf, a.n_old, a.wpts, a.keys0, a.vals0);
     if (a.n_new)
-      hipLaunchKernelGGL(append_new_kernel, grid_for(a.n_new, 256), dim3(256), 0, s, a.d_xyz, a.n_new, a.stride_floats, a.d_cube_of,
-                         a.d_tt, a.inv_leaf, a.n_old, a.wpts, a.keys0, a.vals0, a.nc, a.inv_cell, a.rank, a.world);
+      hipLaunchKernelGGL(append_new_kernel, grid_for(a.n_new, 256), dim3(256), 0, s, a.d_xyz, a.n_new, a.stride_floats, a.d_inten,
+                         a.inten_stride, a.d_cube_of, a.d_tt, a.inv_leaf, a.n_old, a.wpts, a.keys0, a.vals0, a.nc, a.inv_cell, a.rank, a.world);
   }
   uint32_t* keys2 = a.keys0;  // cell key per centroid, input of the second stage
   if (hashed) {
@@ -1690,7 +1719,7 @@ __global__ __launch_bounds__(256) void retable_gather_kernel(const MapTouched* _
   if (e >= n_old) return;
   const int t = touched_of_old(&tt, e);
   const float4 p = pool[(size_t)tt.slot[t] * cap + (e - tt.old_prefix[t])];
-  cent[e] = make_float4(p.x, p.y, p.z, 0.f);
+  cent[e] = p;
   int g[3];
   cell_coords(p.x, p.y, p.z, tt.cube_min[t], inv_cell, nc, g);
   keys2[e] = cell_key(t, cell_index(g, nc));
@@ -1736,8 +1765,8 @@ void launch_vg_stats(const float* d_xyz, uint32_t n, uint32_t stride_floats, dou
 void launch_voxel_filter(const VoxelFilterArgs& a, hipStream_t s) {
   const uint32_t n = a.n;
   uint32_t* n_leaves = a.d_n_cent + kVgCntLeaves;
-  hipLaunchKernelGGL(vg_keys_kernel, grid_for(n, 256), dim3(256), 0, s, a.d_xyz, n, a.stride_floats, a.inv_leaf, a.min_b[0], a.min_b[1],
-                     a.min_b[2], a.div_b[0], a.div_b[0] * a.div_b[1], a.wpts, a.keys0, a.vals0, a.d_decision);
+  hipLaunchKernelGGL(vg_keys_kernel, grid_for(n, 256), dim3(256), 0, s, a.d_xyz, n, a.stride_floats, a.d_inten, a.inten_stride, a.inv_leaf, a.min_b[0],
+                     a.min_b[1], a.min_b[2], a.div_b[0], a.div_b[0] * a.div_b[1], a.wpts, a.keys0, a.vals0, a.d_decision);
   size_t tb = a.temp_bytes;
   (void)map_sort(a.temp, tb, a.keys0, a.keys1, a.vals0, a.vals1, (size_t)n, s);  // stable: input order inside a leaf
   if (a.scan_state && (n + kHeadsItems - 1u) / kHeadsItems <= a.n_scan_state) {
@@ -1746,9 +1775,11 @@ void launch_voxel_filter(const VoxelFilterArgs& a, hipStream_t s) {
   } else {
     launch_leaf_heads(a.keys1, a.vals1, n, a.flags, a.pos, a.wpts, a.spts, a.heads, n_leaves, a.temp, a.temp_bytes, s);
   }
-  hipLaunchKernelGGL(vg_centroid_kernel, grid_for(n, 256), dim3(256), 0, s, a.heads, n_leaves, a.spts, a.d_out, a.flags, a.d_n_cent + kVgCntLongLeaves,
-                     const_cast<VgDecision*>(a.d_decision));
-  hipLaunchKernelGGL(vg_centroid_long_kernel, dim3(3 * kMaxLongLeaves / 4), dim3(256), 0, s, a.heads, a.spts, a.d_out, a.flags, a.d_n_cent + kVgCntLongLeaves);
+  // (the fourth sum only where it is asked for: always on, vg_centroid_kernel sat at the upper end of its own run-to-run spread)
+  hipLaunchKernelGGL(a.d_out_inten ? vg_centroid_kernel<true> : vg_centroid_kernel<false>, grid_for(n, 256), dim3(256), 0, s, a.heads, n_leaves, a.spts, a.d_out,
+                     a.d_out_inten, a.flags, a.d_n_cent + kVgCntLongLeaves, const_cast<VgDecision*>(a.d_decision));
+  hipLaunchKernelGGL(vg_centroid_long_kernel, dim3((a.d_out_inten ? 4 : 3) * kMaxLongLeaves / 4), dim3(256), 0, s, a.heads, a.spts, a.d_out, a.d_out_inten,
+                     a.flags, a.d_n_cent + kVgCntLongLeaves);
 }
 // ---- featureExtraction::removePointDistortion (featureExtraction.cpp:223-314): SURVEY 8(f) row f4, the step that produces
 // the cloud the feature extraction (and through it this path) consumes.  One thread per point: pose of the stamped-pose
@@ -1814,10 +1845,11 @@ void launch_transform_cloud(uint8_t* d_pts, uint32_t n, uint32_t stride, const P
   hipLaunchKernelGGL(transform_cloud_kernel, grid_for(n, 256), dim3(256), 0, s, d_pts, n, stride, pose, d_keep, d_n_kept);
 }
 
-void launch_gather_export_records(const float4* pool, uint32_t cap, uint32_t slot, uint32_t count, uint32_t* d_out_words, uint32_t stride_words, hipStream_t s) {
+void launch_gather_export_records(const float4* pool, uint32_t cap, uint32_t slot, uint32_t count, uint32_t* d_out_words, uint32_t stride_words, bool with_intensity,
+                                  hipStream_t s) {
   if (!count) return;
   const uint64_t words = (uint64_t)count * stride_words;
-  hipLaunchKernelGGL(gather_export_records_kernel, dim3((uint32_t)((words + 255u) / 256u)), dim3(256), 0, s, pool, cap, slot, count, d_out_words, stride_words);
+  hipLaunchKernelGGL(gather_export_records_kernel, dim3((uint32_t)((words + 255u) / 256u)), dim3(256), 0, s, pool, cap, slot, count, d_out_words, stride_words, with_intensity);
 }
 void launch_gather_export(const float4* pool, uint32_t cap, uint32_t slot, uint32_t count, float* d_out, hipStream_t s) {
   if (!count) return;

@@ -41,6 +41,7 @@ so_icp_prefilter_info default_info(float line_res, float plane_res) {
 // the way out with a cloud of n_out points in pf_out
 int done(const Job& j, so_icp_prefilter_info li, size_t n_out) {
   *j.d_out = j.c->pf_out.p; *j.n_out = n_out;
+  j.c->pf_inten_n = n_out; j.c->pf_inten_on = j.c->intensity_off >= 0;  // (what so_icp_prefilter_intensity and so_icp_localization_dev go by)
   li.reserved = j.announced ? 1 : 0;
   if (j.info) *j.info = li;
   return SO_ICP_OK;
@@ -53,6 +54,7 @@ int prefilter_reserve_work(so_icp_ctx* c, size_t n) {
   if (c->pf_temp_for != cap) { c->pf_temp_need = map_sort_temp_bytes(cap) + 256; c->pf_temp_for = cap; }
   HIP_TRY(c, c->pf_temp.reserve(c->pf_temp_need));
   HIP_TRY(c, c->pf_out.reserve((n + 64) * 12));
+  if (c->intensity_off >= 0) HIP_TRY(c, c->pf_inten.reserve((n + 64) * 4));
   return SO_ICP_OK;
 }
 
@@ -64,6 +66,9 @@ VoxelFilterArgs filter_args(so_icp_ctx* c, size_t n, uint32_t sf) {
   a.keys0 = c->pf_k0.as<uint32_t>(); a.keys1 = c->pf_k1.as<uint32_t>(); a.vals0 = c->pf_v0.as<uint32_t>(); a.vals1 = c->pf_v1.as<uint32_t>();
   a.flags = c->pf_flags.as<uint32_t>(); a.pos = c->pf_pos.as<uint32_t>(); a.heads = c->pf_heads.as<uint32_t>();
   a.d_out = c->pf_out.as<float>();
+  // the intensity column (so_icp_set_cloud_intensity): read out of the records in pf_in, averaged per leaf into an array of its own
+  a.d_inten = intensity_in(c, c->pf_in.as<float>(), (size_t)sf * 4); a.inten_stride = sf;
+  a.d_out_inten = c->intensity_off >= 0 ? c->pf_inten.as<float>() : nullptr;
   a.temp = c->pf_temp.p; a.temp_bytes = c->pf_temp.cap;
   return a;
 }
@@ -172,6 +177,12 @@ int host_filter(const Job& j, const double acc[10], const so_icp_prefilter_info&
   if (dx * dy * dz > (int64_t)INT32_MAX) {
     if (j.sf == 3) HIP_TRY(c, hipMemcpyAsync(c->pf_out.p, c->pf_in.p, n * 12, hipMemcpyDeviceToDevice, j.s));
     else HIP_TRY(c, hipMemcpy2DAsync(c->pf_out.p, 12, c->pf_in.p, j.stride_bytes, 12, n, hipMemcpyDeviceToDevice, j.s));
+    if (c->intensity_off >= 0) {  // the intensities pass through with the points, in input order
+      HIP_TRY(c, c->pf_inten.reserve((n + 64) * 4));
+      if (const float* src = intensity_in(c, c->pf_in.as<float>(), j.stride_bytes))
+        HIP_TRY(c, hipMemcpy2DAsync(c->pf_inten.p, 4, src, j.stride_bytes, 4, n, hipMemcpyDeviceToDevice, j.s));
+      else HIP_TRY(c, hipMemsetAsync(c->pf_inten.p, 0, n * 4, j.s));
+    }
     HIP_TRY(c, hipStreamSynchronize(j.s));
     return done(j, li, n);
   }
@@ -225,6 +236,7 @@ int prefilter_scan_impl(so_icp_ctx* c, const float* xyz, bool xyz_on_device, siz
   Job j{c, aux_stream(c), n, stride_bytes, (uint32_t)(stride_bytes / 4), auto_voxel_size, line_res, plane_res, false, d_out, n_out, info};
   so_icp_prefilter_info li = default_info(line_res, plane_res);
   *d_out = nullptr; *n_out = 0;
+  c->pf_inten_n = 0; c->pf_inten_on = c->intensity_off >= 0;
   if (!n) { if (info) *info = li; return so_icp_set_resolution(c, line_res, plane_res); }
   int rc = take_or_upload(j, xyz, xyz_on_device);
   if (rc) return rc;
@@ -258,6 +270,25 @@ int so_icp_prefilter_announce(so_icp_ctx* c, const float* xyz, size_t n, size_t 
   HIP_TRY(c, c->pf_stage.reserve(n * stride_bytes + 64));
   HIP_TRY(c, hipMemcpyAsync(c->pf_stage.p, xyz, n * stride_bytes, hipMemcpyHostToDevice, s));
   c->pf_announced.ptr = xyz; c->pf_announced.n = n; c->pf_announced.stride = stride_bytes; c->pf_announced.on = true;
+  return SO_ICP_OK;
+}
+
+int so_icp_prefilter_intensity(so_icp_ctx* c, float* out, size_t cap, void** d_out, size_t* n_out) {
+  if (!c || !n_out) return SO_ICP_E_INVALID;
+  NEED_DEVICE(c);
+  *n_out = 0;
+  if (d_out) *d_out = nullptr;
+  if (!c->pf_inten_on || !c->pf_inten_n) return SO_ICP_OK;  // (the switch was off during the last pre-filter: it kept none)
+  const size_t n = c->pf_inten_n;
+  if (out) {
+    if (cap < n) return fail(c, SO_ICP_E_INVALID, "so_icp_prefilter_intensity: out holds fewer floats than the last pre-filter's output has points");
+    HIP_TRY(c, hipSetDevice(c->cfg.device_id));
+    hipStream_t s = aux_stream(c);
+    HIP_TRY(c, hipMemcpyAsync(out, c->pf_inten.p, n * sizeof(float), hipMemcpyDeviceToHost, s));
+    HIP_TRY(c, hipStreamSynchronize(s));
+  }
+  if (d_out) *d_out = c->pf_inten.p;
+  *n_out = n;
   return SO_ICP_OK;
 }
 
