@@ -11,6 +11,9 @@
 // --sequence: a replay (LidarSLAM::LocalizationSequence): frame 0 seeds the map, frames 1.. run as ONE sequence from guess 1 with the
 //          motion predictions guess_(k-1)^-1 * guess_k; prints one line per frame (index and pose, %.17g) and writes
 //          out.bin: int32 status, int32 n_done, float64 T_w_lidar[n_done][7]
+// --correspondences: the frames as without a flag, with LidarSLAM::keep_correspondences on; behind the output above, the last frame's
+//          correspondence set (LidarSLAM::LastCorrespondences at the optimised pose): the so_icp_correspondence_info as it is, then
+//          n_accepted so_icp_correspondence records as they are
 #include <cstdint>
 #include <cstdio>
 #include <cstring>
@@ -92,6 +95,8 @@ int main(int argc, char** argv) {
       fclose(in); fclose(out);
       return 0;
     }
+    const bool correspondences = argc > 3 && std::strcmp(argv[3], "--correspondences") == 0;
+    slam.keep_correspondences = correspondences;
     bool initialization = false;                        // laserMapping.cpp: first frame seeds the map
     for (int f = 0; f < n_frames; ++f) {
       if (f + 1 < n_frames && f >= 1) slam.StageNextScan(clouds[f + 1]);  // what the feature callback would do
@@ -114,6 +119,13 @@ int main(int argc, char** argv) {
     const PointCloud<Point> near = slam.localMap.get5x5LocalMap(slam.pos_in_localmap);  // laserMapping.cpp:439
     wr<uint64_t>(out, (uint64_t)near.points.size());
     for (const Point& p : near.points) { wr<float>(out, p.x); wr<float>(out, p.y); wr<float>(out, p.z); }
+    if (correspondences) {
+      std::vector<so_icp_correspondence> recs;
+      so_icp_correspondence_info info;
+      slam.LastCorrespondences(nullptr, recs, &info);
+      wr(out, info);
+      if (!recs.empty()) fwrite(recs.data(), sizeof(so_icp_correspondence), recs.size(), out);
+    }
     fclose(in); fclose(out);
   } catch (const std::exception& e) {
     fprintf(stderr, "adapter_driver: %s\n", e.what());  // what process() would log (laserMapping.cpp:788-790)

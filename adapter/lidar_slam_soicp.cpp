@@ -76,6 +76,30 @@ void LidarSLAM::push_knobs() {
   if (so_icp_set_resolution(gpu_, localMap.lineRes_, localMap.planeRes_) < 0) throw std::runtime_error(so_icp_last_error(gpu_));
   so_icp_set_max_surface_features(gpu_, OptSet.max_surface_features);
   so_icp_set_max_iterations(gpu_, (int)LocalizationICPMaxIter);
+  if (keep_correspondences != pushed_keep_correspondences_) {
+    if (so_icp_keep_correspondences(gpu_, keep_correspondences ? 1 : 0) < 0) throw std::runtime_error(so_icp_last_error(gpu_));
+    pushed_keep_correspondences_ = keep_correspondences;
+  }
+}
+
+int LidarSLAM::LastCorrespondences(const Transformd* pose, std::vector<so_icp_correspondence>& out, so_icp_correspondence_info* info) {
+  ensure_context();
+  so_icp_correspondence_info local;
+  if (!info) info = &local;
+  double T[7];
+  if (pose) { T[0] = pose->pos.x(); T[1] = pose->pos.y(); T[2] = pose->pos.z(); T[3] = pose->rot.x(); T[4] = pose->rot.y(); T[5] = pose->rot.z(); T[6] = pose->rot.w(); }
+  // the registration counted the accepted points (iterations.back().num_surf_from_scan): room for them, one call
+  const size_t cap = last_raw.n_iterations > 0 && last_raw.n_iterations <= SO_ICP_MAX_OUTER ? (size_t)last_raw.iterations[last_raw.n_iterations - 1].num_surf_from_scan : 0;
+  out.resize(cap);
+  if (so_icp_correspondences(gpu_, pose ? T : nullptr, out.data(), out.size(), nullptr, nullptr, 0, nullptr, info) < 0)
+    throw std::runtime_error(std::string("so_icp_correspondences: ") + so_icp_last_error(gpu_));
+  if (info->n_accepted > out.size()) {  // (a set the adapter's own statistics do not describe: sized by the call's answer)
+    out.resize((size_t)info->n_accepted);
+    if (so_icp_correspondences(gpu_, pose ? T : nullptr, out.data(), out.size(), nullptr, nullptr, 0, nullptr, info) < 0)
+      throw std::runtime_error(std::string("so_icp_correspondences: ") + so_icp_last_error(gpu_));
+  }
+  out.resize((size_t)info->n_accepted);
+  return (int)info->n_accepted;
 }
 
 void LidarSLAM::read_back(int32_t n_edge_points, const double T_out[7], double timeLaserOdometry) {

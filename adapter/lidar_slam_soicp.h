@@ -103,6 +103,10 @@ class LidarSLAM {
   uint8_t* PinnedScratch(int which, size_t bytes);
   void LocalizationPrefiltered(bool initialization, PredictionSource predictodom, Transformd T_w_lidar_in, const void* d_planner_xyz,
                                size_t n_planner, int32_t n_edge_points, double timeLaserOdometry);
+  // The correspondence set of the last Localization() that registered (the reference's features_corres, LidarSlam.h:209-222; needs
+  // keep_correspondences below): the accepted correspondences in scan order with residual and weight at *pose (nullptr: the optimised
+  // pose), so_icp_correspondences.  Returns their number; 0 with info->valid == 0 when there is nothing to export.  info may be nullptr.
+  int LastCorrespondences(const Transformd* pose, std::vector<so_icp_correspondence>& out, so_icp_correspondence_info* info);
 
   // ---- public fields laserMapping.cpp reads / writes (same names) ----
   Transformd T_w_lidar, last_T_w_lidar;
@@ -120,9 +124,10 @@ class LidarSLAM {
   double lasttimeLaserOdometry = 0;
   // ---- libsoicp specifics ----
   int device_id = 0;                   // HIP device of this process (one process per GPU)
+  bool keep_correspondences = false;   // pushed before each call like the knobs above: registrations keep their set for LastCorrespondences
   uint32_t last_flags = 0;             // so_icp_stats::flags of the last call (degraded modes, for the node's log)
   int last_status = 0;                 // so_icp_localization return code of the last call
-  so_icp_stats last_raw;               // everything the C ABI returned (JtJ / Jtr, per-iteration histograms)
+  so_icp_stats last_raw{};             // everything the C ABI returned (JtJ / Jtr, per-iteration histograms)
 
  private:
   friend class LocalMapFacade;
@@ -130,6 +135,7 @@ class LidarSLAM {
   void push_knobs();
   void read_back(int32_t n_edge_points, const double T_out[7], double timeLaserOdometry);
   so_icp_ctx* gpu_ = nullptr;
+  bool pushed_keep_correspondences_ = false;
   struct Scratch { uint8_t* p = nullptr; size_t cap = 0; };
   std::vector<Scratch> scratch_;
 };

@@ -386,6 +386,74 @@ int so_icp_localization_dev(so_icp_ctx *ctx, int initialization, const double T_
 /* copy a resident scan (packed float xyz) back to the host */
 int so_icp_download_scan(so_icp_ctx *ctx, const void *d_scan_xyz, size_t n, float *out_xyz);
 
+/* -------- what Seam A leaves behind: the CORRESPONDENCE SET of the last registration -- the reference's features_corres
+ * (tbb::concurrent_vector<OptimizationParameter>, LS.h:209-222), filled by extractFeaturesConstraints (LS.cpp:299-344) on every outer
+ * iteration: per scan point the MatchingResult, and per accepted point the plane (NormDir, negative_OA_dot_norm) and the
+ * residualCoefficient.  The registration already stores all of it in memory of the context; this entry reads it there (one launch of
+ * a kernel of its own; no registration kernel takes part and none was changed for it).  What a caller does with it: colour or mask the
+ * registered scan by residual, keep points that matched nothing out of the map, hand a factor-graph back end point-to-plane factors
+ * instead of one pose, re-evaluate the cost of the fixed set at another pose.
+ * Not exported: the correspondences of so_icp_register_batch's hypotheses, those of a sharded context (world_size > 1), the
+ * neighbours' coordinates and the observability labels (not stored), normal equations (so_icp_stats::JtJ / Jtr are those of the set
+ * at the default pose; at another pose the caller sums them from the records: J = [n, p x (R^T n)], JtJ += weight J J^T,
+ * Jtr += weight residual J). */
+/* One accepted correspondence of the last outer iteration (LS.h:209-222: Xvalue, NormDir, negative_OA_dot_norm,
+ * residualCoefficient), plus its residual and weight at the evaluation pose. */
+typedef struct {
+  uint32_t index;   /* position of the point in the scan */
+  float p[3];       /* the scan point, sensor frame, the scan's own bits */
+  double n[3];      /* NormDir */
+  double d;         /* negative_OA_dot_norm */
+  double coeff;     /* residualCoefficient */
+  double residual;  /* n . (R(q) p + t) + d at pose_eval (lidarOptimization.cpp:59-61) */
+  double weight;    /* coeff * rho'(residual^2): this row's factor in J^T J and J^T r */
+} so_icp_correspondence;   /* 72 bytes */
+typedef struct {
+  uint64_t n_points, n_accepted;
+  int32_t valid;            /* 0: nothing to export (below); every count 0 */
+  int32_t outer_iteration;  /* = so_icp_stats::n_iterations - 1 of that registration */
+  double pose_fit[7];       /* the pose the correspondences were formed at: the registration's guess when n_iterations == 1 (in a chained
+                               sequence guesses_out[k]), else iterations[n_iterations - 2].pose_after */
+  double pose_eval[7];      /* the pose residual, weight and cost are evaluated at */
+  double cost;              /* sum 0.5 * coeff * rho(residual^2) over the records: Ceres' cost of the set at pose_eval */
+} so_icp_correspondence_info;
+/* The switch.  A new context has it off, and while it is off every entry does exactly what it does without this feature (no launch,
+ * copy, allocation or synchronisation is added) and so_icp_correspondences reports valid = 0.  While it is on, every registration that
+ * ends with SO_ICP_OK -- so_icp_register, _register_dev, so_icp_localization(_dev) with initialization = 1, the last registration of
+ * so_icp_register_sequence, the last frame of so_icp_localization_sequence -- leaves what the export needs in memory the context owns.
+ * The records and status bytes are there anyway; the SCAN is not (it may lie in a stage slot that so_icp_stage_scan refills from another
+ * thread as soon as the call returns, in the caller's device buffer, or in the pre-filter's output), so the registration keeps a
+ * packed copy of it: one device-to-device copy of 12 n bytes in the context's queue, in front of the registration's first launch (a
+ * staged scan has arrived by then and its slot is released only after the registration has reported, which is behind the copy); the
+ * last registration of a CHAINED so_icp_register_sequence copies behind its report and waits for the copy.
+ * Turning the switch off drops the set.  world_size > 1: SO_ICP_E_UNSUPPORTED; a host-only context: SO_ICP_E_HIP. */
+int so_icp_keep_correspondences(so_icp_ctx *ctx, int on);
+/* The set of the last registration.  info->valid = 0 (SO_ICP_OK, every count 0, no output touched) when the switch was off during the
+ * last registration, there has been none, the last registration-family call returned anything but SO_ICP_OK
+ * (SO_ICP_NOT_ENOUGH_MAP_FEATURES, SO_ICP_MAP_SEEDED, an error) or was so_icp_register_batch.  Nothing else invalidates it: not the map
+ * insert of so_icp_localization, not a pre-filter, not a staged announcement, not so_icp_knn_surf.
+ * pose (nullable): where residual, weight and cost are evaluated; NULL = stats.iterations[n_iterations - 1].pose_after, the optimised
+ * pose BEFORE MannualYawCorrection (LS.cpp:891-913), where so_icp_stats::JtJ / Jtr were formed.  The arithmetic is the solve's own
+ * (quat_rotate in fp64, + t, the fused dot product, s = r^2 against a^2, v = 1 - s (1 / a^2), rho' = 0.5 v^2 (tukey_variant 0) or v^2 (1),
+ * 0 outside the window; rho = rho_out (1 - v^3) inside, rho_out = a^2 / 6 or a^2 / 3 outside), with the a^2 and the variant of THAT
+ * registration: a later so_icp_set_resolution does not change them.  At the default pose the records carry the residuals and weights
+ * of the registration's last evaluation, and cost its final_cost up to the order of the sum; at pose_fit, its initial_cost.
+ * Outputs, each nullable:
+ *  records     the accepted correspondences (status 0) in ascending index; NULL or cap_records < n_accepted: the counts only
+ *  status_out  [i] = the MatchingResult byte of point i, 254 = not sampled (what so_icp_debug_match_status gives)
+ *  residual_out[i] = (float)residual of an accepted point, NaN otherwise; both per-point arrays need cap_points >= n_points
+ *                    (SO_ICP_E_INVALID otherwise)
+ *  *d_records_out  a device buffer owned by the context with the same record bytes, valid until the next so_icp_correspondences
+ *                  call; no other entry writes it
+ * cost is a deterministic sum (per-tile partial sums in a fixed tree, the tiles added in tile order): two calls give the same bits.
+ * One launch, one copy per requested host output (and one of the counts and tile sums), one synchronisation, on the context's queue
+ * behind whatever the last call left there.  A registered scan of 0 points: valid = 1, zero counts.  SO_ICP_E_UNSUPPORTED for a scan
+ * of 2^31 points or more (the registration entries refuse far smaller ones). */
+int so_icp_correspondences(so_icp_ctx *ctx, const double pose[7] /* nullable */,
+                           so_icp_correspondence *records, size_t cap_records,
+                           uint8_t *status_out, float *residual_out, size_t cap_points,
+                           void **d_records_out, so_icp_correspondence_info *info);
+
 /* -------- the step before Seam A: laserMapping::adjustVoxelSize (lmap.cpp:598-651) on the device ----------------
  * auto_voxel_size != 0: average_distance = mean|x| * mean|y| * mean|z| of the surf cloud chooses the resolutions
  * (< 25: 0.1 / 0.2, > 65: 0.4 / 0.8, else unchanged), count_far_points (> 3 m) > 3000 raises increase_blind_radius.

@@ -196,6 +196,22 @@ class LmScriptResult(C.Structure):
                 ("done_count", C.c_uint32), ("reserved", C.c_uint32), ("iterations", IterStats * 16)]
 
 
+class Correspondence(C.Structure):
+    """so_icp_correspondence: one accepted correspondence of the last outer iteration (72 bytes)"""
+    _fields_ = [("index", C.c_uint32), ("p", C.c_float * 3), ("n", C.c_double * 3), ("d", C.c_double), ("coeff", C.c_double),
+                ("residual", C.c_double), ("weight", C.c_double)]
+
+
+class CorrespondenceInfo(C.Structure):
+    _fields_ = [("n_points", C.c_uint64), ("n_accepted", C.c_uint64), ("valid", C.c_int32), ("outer_iteration", C.c_int32),
+                ("pose_fit", C.c_double * 7), ("pose_eval", C.c_double * 7), ("cost", C.c_double)]
+
+
+# the same record as a numpy structured type (np.frombuffer over so_icp_correspondence bytes)
+CORRESPONDENCE_DTYPE = np.dtype([("index", "<u4"), ("p", "<f4", 3), ("n", "<f8", 3), ("d", "<f8"), ("coeff", "<f8"), ("residual", "<f8"),
+                                 ("weight", "<f8")])
+assert CORRESPONDENCE_DTYPE.itemsize == C.sizeof(Correspondence) == 72
+
 EXPORTED = ["so_icp_default_config", "so_icp_create", "so_icp_destroy", "so_icp_last_error", "so_icp_abi_version",
             "so_icp_device_available", "so_icp_set_resolution", "so_icp_set_max_surface_features", "so_icp_set_max_iterations",
             "so_icp_map_set_origin", "so_icp_map_shift", "so_icp_map_add_surf", "so_icp_map_count_5x5", "so_icp_map_export",
@@ -210,7 +226,8 @@ EXPORTED = ["so_icp_default_config", "so_icp_create", "so_icp_destroy", "so_icp_
             "so_icp_localization_sequence", "so_icp_extract_features", "so_icp_extract_features_dev", "so_icp_prefilter_scan_dev",
             "so_icp_livox_default_layout", "so_icp_extract_features_livox", "so_icp_extract_features_livox_dev",
             "so_icp_registered_scan", "so_icp_registered_scan_dev", "so_icp_extract_features_untimed", "so_icp_extract_features_untimed_dev",
-            "so_icp_debug_lm_script", "so_icp_set_cloud_intensity", "so_icp_prefilter_intensity"]
+            "so_icp_debug_lm_script", "so_icp_set_cloud_intensity", "so_icp_prefilter_intensity",
+            "so_icp_keep_correspondences", "so_icp_correspondences"]
 
 _lib = None
 
@@ -311,6 +328,8 @@ def load():
     L.so_icp_peer_export.argtypes = [vp, u8p]
     L.so_icp_peer_connect.argtypes = [vp, u8p, i32p]
     L.so_icp_peer_enable.argtypes = [vp, C.c_int]
+    L.so_icp_keep_correspondences.argtypes = [vp, C.c_int]
+    L.so_icp_correspondences.argtypes = [vp, f64p, vp, C.c_size_t, u8p, f32p, C.c_size_t, C.POINTER(vp), C.POINTER(CorrespondenceInfo)]
     _lib = L
     return L
 
@@ -503,6 +522,58 @@ class LidarSlamGpu:
         out = np.zeros(n, np.uint8)
         self._check(self.L.so_icp_debug_match_status(self.h, _p(out, C.c_uint8), n))
         return out
+
+    def keep_correspondences(self, on):
+        """so_icp_keep_correspondences: registrations from here on leave their correspondence set for correspondences(); returns the C code"""
+        return self.L.so_icp_keep_correspondences(self.h, int(bool(on)))
+
+    def _correspondences(self, pose, want_points, cap, want_records, d_out):
+        pose = None if pose is None else np.ascontiguousarray(pose, np.float64)
+        info = CorrespondenceInfo()
+        if cap is None:  # a sizing call first (counts only): one launch more than a call with `cap`
+            self._check(self.L.so_icp_correspondences(self.h, None, None, 0, None, None, 0, None, C.byref(info)))
+            cap = int(info.n_points)
+        cap = int(cap)
+        rec = np.zeros(cap if want_records else 0, CORRESPONDENCE_DTYPE)
+        status = np.zeros(cap, np.uint8) if want_points else None
+        resid = np.zeros(cap, np.float32) if want_points else None
+        self._check(self.L.so_icp_correspondences(self.h, None if pose is None else _p(pose, C.c_double),
+                                                  rec.ctypes.data_as(C.c_void_p) if want_records else None, len(rec),
+                                                  None if status is None else _p(status, C.c_uint8), None if resid is None else _p(resid, C.c_float),
+                                                  cap if want_points else 0, d_out, C.byref(info)))
+        n, na = int(info.n_points), int(info.n_accepted)
+        return rec[:na], (None if status is None else status[:n]), (None if resid is None else resid[:n]), info
+
+    def correspondences(self, pose=None, want_points=True, cap=None):
+        """so_icp_correspondences: the accepted correspondences of the last registration as a structured array (CORRESPONDENCE_DTYPE,
+        ascending index), the status byte and the float residual (NaN where not accepted) of every scan point (None without
+        want_points) and the CorrespondenceInfo.  pose: where residual, weight and cost are evaluated (None: the optimised pose).
+        cap: an upper bound of the scan's points, when the caller knows one (saves the sizing call).  info.valid == 0: empty arrays."""
+        return self._correspondences(pose, want_points, cap, True, None)
+
+    def prepare_correspondences(self, cap, want_points=True):
+        """so_icp_correspondences at the default pose with pre-built arguments and buffers for `cap` points (timed loops).  Returns
+        (call, records, status or None, residual or None, info): call() performs the C call and returns its code; the first
+        info.n_accepted records and info.n_points per-point entries are then current."""
+        rec = np.zeros(int(cap), CORRESPONDENCE_DTYPE); info = CorrespondenceInfo()
+        status = np.zeros(int(cap), np.uint8) if want_points else None
+        resid = np.zeros(int(cap), np.float32) if want_points else None
+        fn, args = self.L.so_icp_correspondences, (self.h, None, rec.ctypes.data_as(C.c_void_p), len(rec), None if status is None else _p(status, C.c_uint8),
+                                                   None if resid is None else _p(resid, C.c_float), int(cap) if want_points else 0, None, C.byref(info))
+        return (lambda: fn(*args)), rec, status, resid, info
+
+    def correspondences_dev(self, pose=None, cap=None):
+        """the same, the records left in HBM: (device address of the context-owned record buffer -- valid until the next call --, info)"""
+        d = C.c_void_p()
+        _, _, _, info = self._correspondences(pose, False, 0 if cap is None else cap, False, C.byref(d))
+        return d.value, info
+
+    def download_bytes(self, d_ptr, nbytes):
+        """nbytes from a device address, through so_icp_download_scan (whole 12-byte units; the buffers of this library are padded)"""
+        units = (int(nbytes) + 11) // 12
+        out = np.zeros(units * 3, np.float32)
+        self._check(self.L.so_icp_download_scan(self.h, C.c_void_p(d_ptr), units, _p(out, C.c_float)))
+        return out.view(np.uint8)[:int(nbytes)].copy()
 
     def neighbours(self, n):
         """the five neighbours (canonical map indices) the last k-NN sweep left for every query (so_icp_debug_neighbours)"""

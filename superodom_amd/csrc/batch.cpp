@@ -192,6 +192,7 @@ int so_icp_register_batch(so_icp_ctx* c, const float* xyz, const void* d_scan, s
   HIP_TRY(c, hipSetDevice(c->cfg.device_id));
   if (c->cfg.world_size != 1)  // (hypotheses are independent: replicate the map and split THEM over the ranks -- bench.py's batch64)
     return fail(c, SO_ICP_E_UNSUPPORTED, "so_icp_register_batch needs the whole map on one device (world_size == 1)");
+  c->corr_last.valid = false;  // (so_icp_correspondences: the hypotheses keep their records in the batch's own arrays)
   if (n_hyp == 0) return 0;
   const float* scan = static_cast<const float*>(d_scan);
   if (!scan) {

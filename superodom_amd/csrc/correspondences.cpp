@@ -1,0 +1,131 @@
+// correspondences.cpp -- so_icp_keep_correspondences and so_icp_correspondences: the correspondence set of the last registration
+// (the reference's features_corres, LidarSlam.h:209-222) read where the registration left it.  The registration entries keep a packed
+// copy of their scan and a small record of what they ran (keep_scan_copy, note_correspondences) while the switch is on; the export is
+// one launch of corr_kernels.hip's kernel on the context's queue.
+#include <hip/hip_runtime_api.h>
+
+#include <algorithm>
+#include <cstring>
+#include <memory>
+
+#include "corr_kernels.h"
+#include "ctx.h"
+
+namespace soicp::host {
+
+int keep_scan_copy(so_icp_ctx* c, const float* d_scan, size_t n) {
+  if (!n) return SO_ICP_OK;
+  HIP_TRY(c, c->corr_scan.reserve(n * 12 + 64));
+  HIP_TRY(c, hipMemcpyAsync(c->corr_scan.p, d_scan, n * 12, hipMemcpyDeviceToDevice, c->stream));
+  return SO_ICP_OK;
+}
+
+void note_correspondences(so_icp_ctx* c, const DevState& H, const double guess[7], size_t n, const EvalParams& ep) {
+  so_icp_ctx::CorrLast& L = c->corr_last;
+  const int n_it = std::min(H.n_iterations, (int)SO_ICP_MAX_OUTER);
+  L.n = n; L.n_accepted = n_it < 1 ? 0u : (uint32_t)H.iters[n_it - 1].num_surf;
+  L.a2 = ep.a2; L.variant = ep.variant;
+  L.outer_iteration = n_it - 1;
+  // (a registration without an outer iteration formed nothing: both poses are its guess)
+  std::memcpy(L.pose_fit, n_it <= 1 ? guess : H.iters[n_it - 2].pose_after, sizeof(L.pose_fit));
+  std::memcpy(L.pose_eval, n_it < 1 ? guess : H.iters[n_it - 1].pose_after, sizeof(L.pose_eval));
+  L.valid = true;
+}
+
+}  // namespace soicp::host
+
+namespace {
+
+// The export's own buffers: nothing here is written by another entry, and the export writes no other entry's buffers
+struct CorrExportState {
+  DevBuf records, status, residual;
+  DevBuf small;              // {n_accepted, ticket, -, -} | tile sums of the cost | look-back words of the compaction
+  uint8_t* h_small = nullptr;  // pinned read-back of the counters and the tile sums
+  size_t h_small_cap = 0;
+  ~CorrExportState() {
+    for (DevBuf* b : {&records, &status, &residual, &small}) b->release();
+    if (h_small) (void)hipHostFree(h_small);
+  }
+};
+
+CorrExportState* export_state_of(so_icp_ctx* c) {
+  if (!c->corr_state) c->corr_state = std::make_shared<CorrExportState>();
+  return static_cast<CorrExportState*>(c->corr_state.get());
+}
+
+}  // namespace
+
+extern "C" {
+
+int so_icp_keep_correspondences(so_icp_ctx* c, int on) {
+  if (!c) return SO_ICP_E_INVALID;
+  NEED_DEVICE(c);
+  if (c->cfg.world_size > 1) return fail(c, SO_ICP_E_UNSUPPORTED, "so_icp_keep_correspondences: a sharded context (world_size > 1) keeps its correspondences per rank");
+  c->corr_keep = on != 0;
+  if (!c->corr_keep) c->corr_last.valid = false;
+  return SO_ICP_OK;
+}
+
+int so_icp_correspondences(so_icp_ctx* c, const double pose[7], so_icp_correspondence* records, size_t cap_records, uint8_t* status_out,
+                           float* residual_out, size_t cap_points, void** d_records_out, so_icp_correspondence_info* info) {
+  static_assert(sizeof(so_icp_correspondence) == kCorrRecordBytes, "the kernel writes so_icp_correspondence records");
+  if (!c) return SO_ICP_E_INVALID;
+  NEED_DEVICE(c);
+  so_icp_correspondence_info local;
+  if (!info) info = &local;
+  std::memset(info, 0, sizeof(*info));
+  const so_icp_ctx::CorrLast& L = c->corr_last;
+  if (!c->corr_keep || !L.valid) return SO_ICP_OK;
+  const size_t n = L.n;
+  if (n >= ((size_t)1 << 31)) return fail(c, SO_ICP_E_UNSUPPORTED, "so_icp_correspondences: too many points");
+  if ((status_out || residual_out) && cap_points < n)
+    return fail(c, SO_ICP_E_INVALID, "so_icp_correspondences: the per-point outputs need cap_points >= the points of the registered scan");
+  HIP_TRY(c, hipSetDevice(c->cfg.device_id));
+  info->valid = 1; info->n_points = n; info->outer_iteration = L.outer_iteration;
+  std::memcpy(info->pose_fit, L.pose_fit, sizeof(info->pose_fit));
+  std::memcpy(info->pose_eval, pose ? pose : L.pose_eval, sizeof(info->pose_eval));
+  CorrExportState& st = *export_state_of(c);
+  if (d_records_out) *d_records_out = nullptr;
+  if (!n) return SO_ICP_OK;
+  const size_t nblk = correspondence_workgroups((uint32_t)n), cost_off = 16, state_off = cost_off + nblk * 8, small_bytes = state_off + nblk * 8;
+  HIP_TRY(c, st.records.reserve(n * kCorrRecordBytes + 64));
+  HIP_TRY(c, st.status.reserve(n + 64));
+  HIP_TRY(c, st.residual.reserve(n * 4 + 64));
+  HIP_TRY(c, st.small.reserve(small_bytes));
+  if (st.h_small_cap < state_off) {
+    if (st.h_small) (void)hipHostFree(st.h_small);
+    st.h_small = nullptr; st.h_small_cap = 0;
+    HIP_TRY(c, hipHostMalloc(reinterpret_cast<void**>(&st.h_small), state_off + state_off / 4 + 256));
+    st.h_small_cap = state_off + state_off / 4 + 256;
+  }
+  hipStream_t s = c->stream;
+  uint32_t* d_counts = st.small.as<uint32_t>();
+  HIP_TRY(c, hipMemsetAsync(st.small.p, 0, small_bytes, s));
+  CorrExportIn in;
+  in.scan = c->corr_scan.as<float>();
+  in.corr = CorrBuffers{c->d_nd.as<double4>(), c->d_coeff.as<double>(), c->d_status.as<uint8_t>()};
+  in.n = (uint32_t)n; in.pose = pose_from_array(info->pose_eval); in.a2 = L.a2; in.variant = L.variant;
+  launch_correspondences(in, st.records.as<uint8_t>(), st.status.as<uint8_t>(), st.residual.as<float>(), d_counts,
+                         reinterpret_cast<double*>(st.small.as<uint8_t>() + cost_off),
+                         reinterpret_cast<unsigned long long*>(st.small.as<uint8_t>() + state_off), d_counts + 1, s);
+  HIP_TRY(c, hipGetLastError());
+  // The number of records is what the registration counted (iterations[last].num_surf_from_scan): the copy is sized by it rather than
+  // by a second wait for the kernel's own count, which is checked against it afterwards
+  const bool want_records = records && cap_records >= L.n_accepted;
+  if (want_records && L.n_accepted) HIP_TRY(c, hipMemcpyAsync(records, st.records.p, (size_t)L.n_accepted * kCorrRecordBytes, hipMemcpyDeviceToHost, s));
+  if (status_out) HIP_TRY(c, hipMemcpyAsync(status_out, st.status.p, n, hipMemcpyDeviceToHost, s));
+  if (residual_out) HIP_TRY(c, hipMemcpyAsync(residual_out, st.residual.p, n * 4, hipMemcpyDeviceToHost, s));
+  HIP_TRY(c, hipMemcpyAsync(st.h_small, st.small.p, state_off, hipMemcpyDeviceToHost, s));
+  HIP_TRY(c, hipStreamSynchronize(s));
+  uint32_t n_accepted;
+  std::memcpy(&n_accepted, st.h_small, 4);
+  if (n_accepted != L.n_accepted)
+    return fail(c, SO_ICP_E_HIP, "so_icp_correspondences: the status bytes hold another number of accepted points than the registration reported");
+  double cost = 0;  // the tiles in tile order
+  for (size_t b = 0; b < nblk; ++b) { double t; std::memcpy(&t, st.h_small + cost_off + b * 8, 8); cost += t; }
+  info->n_accepted = n_accepted; info->cost = cost;
+  if (d_records_out) *d_records_out = st.records.p;
+  return SO_ICP_OK;
+}
+
+}  // extern "C"

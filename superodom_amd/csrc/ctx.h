@@ -8,6 +8,7 @@
 //   localization.cpp      so_icp_localization(_dev): one frame of LidarSLAM::Localization from a host or a resident scan
 //   prefilter.cpp         so_icp_prefilter_announce / _scan(_dev): adjustVoxelSize + VoxelGrid, decided on the device or on the host
 //   cloud_steps.cpp       so_icp_deskew_scan(_dev), so_icp_transform_cloud, so_icp_download_scan
+//   correspondences.cpp   so_icp_keep_correspondences, so_icp_correspondences: the last registration's correspondence set
 //   multi_gpu.cpp         RCCL, in-process groups, peer exchange, shard helpers
 //   localization_sequence.cpp, feature_extraction.cpp
 #pragma once
@@ -157,6 +158,18 @@ struct so_icp_ctx {
   hipEvent_t ev_upload = nullptr;     // a scan uploaded through the auxiliary queue: the context's queue waits for it
   std::shared_ptr<void> fe_state;     // so_icp_extract_features(_dev) (feature_extraction.cpp)
   std::shared_ptr<void> rs_state;     // so_icp_registered_scan(_dev) (feature_extraction.cpp): buffers of its own
+  // so_icp_keep_correspondences / so_icp_correspondences (correspondences.cpp): the switch, the packed copy of the last registered
+  // scan (the records themselves stay in d_nd / d_coeff / d_status), and what the last registration-family call left for the export
+  bool corr_keep = false;
+  DevBuf corr_scan;
+  struct CorrLast {
+    bool valid = false;               // the last registration-family call ended with SO_ICP_OK, with the switch on
+    size_t n = 0; uint32_t n_accepted = 0;   // points of the scan / iterations[last].num_surf_from_scan
+    double a2 = 0; int variant = 0;   // EvalParams::a2 / ::variant of that registration
+    int outer_iteration = 0;
+    double pose_fit[7] = {0, 0, 0, 0, 0, 0, 1}, pose_eval[7] = {0, 0, 0, 0, 0, 0, 1};  // where the set was formed / the default evaluation pose
+  } corr_last;
+  std::shared_ptr<void> corr_state;   // so_icp_correspondences: buffers of its own
   hipStream_t pf_stream = nullptr;    // the pre-filter's own queue: the next frame's upload + VoxelGrid run BESIDE the map insert the previous
   // Seam B scratch
   DevBuf d_q, d_nbr, d_d2, d_idx, d_found, d_fblist;
@@ -388,6 +401,12 @@ void drop_staged(so_icp_ctx* c, const float* xyz, size_t n, size_t stride_bytes)
 void release_staged(so_icp_ctx* c);
 bool bin_into_slot(so_icp_ctx* c, const float* d_scan, size_t n, const double pose[7], hipStream_t s, BinHashTable& table,
                    so_icp_ctx::StageSlot& sl);
+
+// correspondences.cpp: what the registration entries do for so_icp_correspondences while so_icp_ctx::corr_keep is on
+inline bool keeps_correspondences(const so_icp_ctx* c) { return c->corr_keep && !c->batch_mode && !c->borrow.on && c->cfg.world_size <= 1; }
+int keep_scan_copy(so_icp_ctx* c, const float* d_scan, size_t n);  // the packed copy, enqueued on the context's queue
+// the record of a registration that ended with SO_ICP_OK, reported in H from the guess `guess` with the loss parameters of `ep`
+void note_correspondences(so_icp_ctx* c, const DevState& H, const double guess[7], size_t n, const EvalParams& ep);
 
 // multi_gpu.cpp
 int exchange_map_counts(so_icp_ctx* c);

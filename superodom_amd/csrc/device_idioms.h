@@ -104,4 +104,34 @@ __device__ __forceinline__ void copy_pose_table(double* tab_lds, const double* _
   for (uint32_t k = threadIdx.x; k < n_poses * kStampedPoseDoubles; k += blockDim.x) tab_lds[k] = poses[k];
 }
 
+// surf_sample_kernel's decoupled look-back as a function, for registered_scan_kernel (feature_kernels.hip)
+// and correspondences_kernel (corr_kernels.hip): run by the first wavefront of workgroup
+// `bid` (ticket order) once it knows `agg`, the number it keeps.  Records = flag << 62 | value (flag 1: this workgroup's own count,
+// 2: the count up to and including it), all zero before the launch, vector atomics at agent scope.  Publishes agg, walks back 64
+// records at a time until a flag-2 record, publishes the inclusive count and returns the number kept in front of the workgroup
+// (on every lane).  surf_sample_kernel keeps its own copy in line: calling this from it changes its register allocation and
+// instruction order, and that kernel's code stays as measured.
+__device__ __forceinline__ uint32_t lookback_exclusive(unsigned long long* state, uint32_t bid, uint32_t agg, int lane) {
+  if (lane == 0) __hip_atomic_store(&state[bid], ((bid == 0u ? 2ull : 1ull) << 62) | (unsigned long long)agg, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+  uint32_t excl = 0;
+  int base = (int)bid - 1;
+  while (base >= 0) {
+    const int j = base - lane;
+    unsigned long long r = 2ull << 62;
+    if (j >= 0) {
+      do { r = __hip_atomic_load(&state[j], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); } while ((r >> 62) == 0ull);
+    }
+    const unsigned long long mi = __ballot((r >> 62) == 2ull);
+    const int first = mi ? __ffsll((long long)mi) - 1 : 64;
+    uint32_t contrib = lane <= first ? (uint32_t)(r & 0xFFFFFFFFull) : 0u;
+#pragma unroll
+    for (int d = 32; d >= 1; d >>= 1) contrib += (uint32_t)__shfl_xor((int)contrib, d, 64);
+    excl += contrib;
+    if (mi) break;
+    base -= 64;
+  }
+  if (lane == 0 && bid != 0u) __hip_atomic_store(&state[bid], (2ull << 62) | (unsigned long long)(excl + agg), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+  return excl;
+}
+
 }  // namespace soicp

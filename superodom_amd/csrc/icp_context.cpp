@@ -559,6 +559,8 @@ static int register_core_once(so_icp_ctx* c, const float* d_scan, size_t n, cons
   if (!st) st = &local;
   std::memset(st, 0, sizeof(*st));
   if (n >= kMaxScanPoints) return refuse_scan_size(c);
+  const bool keep_corr = keeps_correspondences(c);  // so_icp_keep_correspondences: this registration leaves its set for so_icp_correspondences
+  if (!c->batch_mode && !c->borrow.on) c->corr_last.valid = false;
   st->flags = (c->retried ? SO_ICP_FLAG_RETRIED : 0u) | (!c->dmap && !c->borrow.on ? SO_ICP_FLAG_HOST_MAP : 0u) |
               (c->cfg.world_size > 1 ? SO_ICP_FLAG_SHARDED : 0u) | (c->query_split ? SO_ICP_FLAG_QUERY_SPLIT : 0u) |
               (c->scan_staged ? SO_ICP_FLAG_STAGED_SCAN : 0u) | (c->direct_readback ? 0u : SO_ICP_FLAG_COPY_READBACK);
@@ -576,6 +578,9 @@ static int register_core_once(so_icp_ctx* c, const float* d_scan, size_t n, cons
   RegPlan p;
   plan_registration(c, p, d_scan, n, pose_in);
   if ((rc = claim_buffers(c, p))) return rc;
+  // (the scan may lie in a stage slot that is refilled once this call has returned: the copy goes in front of the first launch, so it
+  //  has been made when the registration reports)
+  if (keep_corr && (rc = keep_scan_copy(c, p.d_scan, p.n))) return rc;
   const auto t_icp = std::chrono::steady_clock::now();  // TicToc t_opt, LidarSlam.cpp:118
   if ((rc = begin_registration(c, p))) return rc;
   st->flags |= p.flags;
@@ -606,6 +611,7 @@ static int register_core_once(so_icp_ctx* c, const float* d_scan, size_t n, cons
   note_registration_done(c, c->h_ring[last & 1], p.mp, p.n, true, !c->batch_mode && !c->borrow.on);
   const DevState& H = *c->h_state;
   fill_result(c, H, pose_in, st, pose_out, !c->batch_mode);
+  if (keep_corr) note_correspondences(c, H, pose_in, p.n, p.ep);
   st->time_elapsed_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_icp).count();  // :199-200
   if (p.timed && (rc = collect_timing(c, p, H))) return rc;
   c->timing.registrations++;
@@ -687,7 +693,7 @@ so_icp_ctx::~so_icp_ctx() {
   batch.release();
   if (comm && rccl.CommDestroy) rccl.CommDestroy(comm);
   for (DevBuf* b : {&d_world, &d_mpts, &d_cell_start, &d_cube_slot, &d_scan_own, &d_keys0, &d_vals0, &d_chunks,
-                    &d_binned, &d_nd, &d_coeff, &d_status, &d_nbr5, &d_small, &d_q, &d_nbr, &d_d2, &d_idx,
+                    &d_binned, &d_nd, &d_coeff, &d_status, &d_nbr5, &corr_scan, &d_small, &d_q, &d_nbr, &d_d2, &d_idx,
                     &d_found, &d_fblist, &d_kdbg, &pf_stage, &pf_in, &pf_out, &pf_small, &pf_w, &pf_s, &pf_k0, &pf_k1, &pf_v0, &pf_v1, &pf_flags, &pf_pos,
                     &pf_heads, &pf_temp, &pf_dec, &d_counts, &d_sub, &d_inten, &pf_inten})
     b->release();
@@ -1023,6 +1029,7 @@ int so_icp_register_dev(so_icp_ctx* c, const void* d_scan, size_t n, const doubl
   if (!c || !pose_in || !pose_out || (!d_scan && n)) return SO_ICP_E_INVALID;
   NEED_DEVICE(c);
   HIP_TRY(c, hipSetDevice(c->cfg.device_id));
+  c->corr_last.valid = false;
   return register_core(c, static_cast<const float*>(d_scan), n, pose_in, pose_out, st);
 }
 
@@ -1030,6 +1037,7 @@ int so_icp_register(so_icp_ctx* c, const float* xyz, size_t n, size_t stride_byt
   if (!c || !pose_in || !pose_out || (!xyz && n)) return SO_ICP_E_INVALID;
   NEED_DEVICE(c);
   HIP_TRY(c, hipSetDevice(c->cfg.device_id));
+  c->corr_last.valid = false;
   const float* d_scan = nullptr;
   int rc = resolve_scan(c, xyz, n, stride_bytes, &d_scan);  // the copy announced with so_icp_stage_scan, or a plain upload
   if (rc) return rc;

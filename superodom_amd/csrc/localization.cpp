@@ -93,6 +93,7 @@ int register_and_insert(so_icp_ctx* c, const FrameScan& s, const float* d_scan, 
 // One frame of Localization(): seed the map (initializeMapping), or register + accept + insert
 int localization_frame(so_icp_ctx* c, int initialization, const double T_in[7], const FrameScan& s, double time, double pose_out[7],
                        so_icp_stats* st) {
+  c->corr_last.valid = false;  // (so_icp_correspondences: set again by a registration that ends with SO_ICP_OK)
   if (!initialization) {  // initializeMapping, LidarSlam.cpp:83-94
     std::memcpy(pose_out, T_in, 7 * sizeof(double));
     if (st) std::memset(st, 0, sizeof(*st));

@@ -252,6 +252,13 @@ struct SequenceCall {
     }
     (void)hipGetLastError();
     fill_result(c, H, guess, st, poses_out + 7 * (size_t)k, true);
+    if (k == count - 1 && keeps_correspondences(c)) {
+      // so_icp_correspondences exports the LAST registration of the run (the records of the others were overwritten by the launches
+      // chained behind them).  Its scan lies in a slot the next call refills on the sequence's own queue: copied now, and waited for
+      if (const int rc = keep_scan_copy(c, r.d_scan, r.n)) return rc;
+      HIP_TRY(c, hipStreamSynchronize(c->stream));
+      note_correspondences(c, H, guess, r.n, r.ep);
+    }
     st->time_elapsed_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_icp).count();
     c->timing.registrations++;
     if (r.chained) {
@@ -388,7 +395,10 @@ int so_icp_register_sequence(so_icp_ctx* c, int count, const void* const* scans,
   std::vector<so_icp_stats> local_stats;
   if (!stats) { local_stats.resize((size_t)count); stats = local_stats.data(); }
   SequenceCall call{c, count, scans, n_points, stride_bytes, scans_on_device, pose0, deltas, poses_out, guesses_out, stats, n_done};
-  return chained_path(c, count, scans_on_device, stride_bytes) ? call.run_chained() : call.run_unchained();
+  c->corr_last.valid = false;
+  const int rc = chained_path(c, count, scans_on_device, stride_bytes) ? call.run_chained() : call.run_unchained();
+  if (rc != SO_ICP_OK) c->corr_last.valid = false;  // (so_icp_correspondences: only a run that completed leaves its last registration's set)
+  return rc;
 }
 
 }  // extern "C"
