@@ -14,6 +14,12 @@
 // --correspondences: the frames as without a flag, with LidarSLAM::keep_correspondences on; behind the output above, the last frame's
 //          correspondence set (LidarSLAM::LastCorrespondences at the optimised pose): the so_icp_correspondence_info as it is, then
 //          n_accepted so_icp_correspondence records as they are
+// --seam-c: the frames as without a flag, but every frame after the seeding one is registered by the HOST loop below (the reference's
+//          LidarSlam.cpp:119-148 around LidarSLAM::MatchPlanes, LidarSLAM::CorrespondenceSums and so_icp_lm_begin / _feed: what a caller
+//          that keeps its own solver writes) instead of Localization()'s registration, and its scan inserted at that pose through
+//          localMap.addSurfPointCloud.  Same output format; the fields a registration derives from the tracker (startupCount,
+//          uncertainty) stay as the match reports them, total_translation is |pose - guess|, flags those of the last match
+#include <cmath>
 #include <cstdint>
 #include <cstdio>
 #include <cstring>
@@ -43,6 +49,58 @@ static Transformd between(const Transformd& a, const Transformd& b) {
   Transformd d;
   d.pos = Vector3d(tx, ty, tz); d.rot = Quaterniond(w, x, y, z);
   return d;
+}
+
+// LidarSlam.cpp:119-148 on the host: match at the current pose; so_icp_lm_begin on the match's sums; one CorrespondenceSums per
+// candidate -> so_icp_lm_feed until the solver is done; stop at num_successful_steps == 1 or the last iteration.  Returns the match's
+// code when a match did not end with SO_ICP_OK.  *st: the statistics of the last match; *n_outer: outer iterations run.
+static int register_through_seam(LidarSLAM& slam, const PointCloud<Point>::Ptr& cloud, Transformd& T, int max_outer, int lm_max, so_icp_stats* st,
+                                 int* n_outer) {
+  *n_outer = 0;
+  for (int it = 0; it < max_outer; ++it) {
+    const int rc = slam.MatchPlanes(T, cloud, st);
+    if (rc != SO_ICP_OK) return rc;
+    so_icp_sums at;
+    std::memset(&at, 0, sizeof(at));
+    const so_icp_iter_stats& m = st->iterations[0];
+    at.cost = m.initial_cost; at.count = (double)m.num_surf_from_scan;
+    for (int i = 0, k = 0; i < 6; ++i) { at.Jtr[i] = st->Jtr[i]; for (int j = i; j < 6; ++j) at.JtJ[k++] = st->JtJ[6 * i + j]; }
+    for (int h = 0; h < SO_ICP_N_REJECT; ++h) at.hist[h] = (double)m.reject_hist[h];
+    for (int h = 0; h < SO_ICP_N_OBS; ++h) at.hist[SO_ICP_N_REJECT + h] = (double)m.obs_hist[h];
+    const double x0[7] = {T.pos.x(), T.pos.y(), T.pos.z(), T.rot.x(), T.rot.y(), T.rot.z(), T.rot.w()};
+    so_icp_lm_state S;
+    double next[7];
+    int more = so_icp_lm_begin(&S, x0, &at, lm_max, next);
+    std::vector<Transformd> cand(1);
+    std::vector<so_icp_sums> sums;
+    while (more > 0) {
+      cand[0].pos = Vector3d(next[0], next[1], next[2]); cand[0].rot = Quaterniond(next[6], next[3], next[4], next[5]);
+      slam.CorrespondenceSums(cand, sums);
+      more = so_icp_lm_feed(&S, &sums[0], next);
+    }
+    double x[7];
+    so_icp_iter_stats solved;
+    so_icp_lm_result(&S, x, &solved);
+    T.pos = Vector3d(x[0], x[1], x[2]); T.rot = Quaterniond(x[6], x[3], x[4], x[5]);
+    *n_outer = it + 1;
+    if (solved.num_successful_steps == 1) break;
+  }
+  return SO_ICP_OK;
+}
+
+// TransformPoint (superodom_utils.h:119-123): rot * p + pos in double, rounded to float -- the cloud transformAndAddToMap inserts
+static PointCloud<Point> to_world(const PointCloud<Point>& cloud, const Transformd& T) {
+  PointCloud<Point> w = cloud;
+  const double qx = T.rot.x(), qy = T.rot.y(), qz = T.rot.z(), qw = T.rot.w();
+  for (Point& p : w.points) {  // Eigen::QuaternionBase::_transformVector: v + w uv + u x uv, uv = 2 (u x v)
+    const double vx = p.x, vy = p.y, vz = p.z;
+    double ux = qy * vz - qz * vy, uy = qz * vx - qx * vz, uz = qx * vy - qy * vx;
+    ux += ux; uy += uy; uz += uz;
+    p.x = (float)(vx + qw * ux + (qy * uz - qz * uy) + T.pos.x());
+    p.y = (float)(vy + qw * uy + (qz * ux - qx * uz) + T.pos.y());
+    p.z = (float)(vz + qw * uz + (qx * uy - qy * ux) + T.pos.z());
+  }
+  return w;
 }
 
 int main(int argc, char** argv) {
@@ -96,11 +154,32 @@ int main(int argc, char** argv) {
       return 0;
     }
     const bool correspondences = argc > 3 && std::strcmp(argv[3], "--correspondences") == 0;
-    slam.keep_correspondences = correspondences;
+    const bool seam_c = argc > 3 && std::strcmp(argv[3], "--seam-c") == 0;
+    slam.keep_correspondences = correspondences || seam_c;
     bool initialization = false;                        // laserMapping.cpp: first frame seeds the map
     for (int f = 0; f < n_frames; ++f) {
-      if (f + 1 < n_frames && f >= 1) slam.StageNextScan(clouds[f + 1]);  // what the feature callback would do
-      slam.Localization(initialization, LidarSLAM::PredictionSource::LIO_ODOM, guesses[f], edge, clouds[f], times[f]);
+      if (seam_c && initialization) {
+        Transformd T = guesses[f];
+        so_icp_stats st;
+        int n_outer = 0;
+        slam.last_status = register_through_seam(slam, clouds[f], T, (int)slam.LocalizationICPMaxIter, 4, &st, &n_outer);
+        slam.last_flags = st.flags; slam.last_raw = st;
+        slam.pos_in_localmap = Vector3i(st.pos_in_localmap[0], st.pos_in_localmap[1], st.pos_in_localmap[2]);
+        slam.stats.laser_cloud_surf_from_map_num = st.laser_cloud_surf_from_map_num;
+        slam.stats.uncertainty_x = st.uncertainty[0]; slam.stats.uncertainty_y = st.uncertainty[1]; slam.stats.uncertainty_z = st.uncertainty[2];
+        slam.stats.uncertainty_roll = st.uncertainty[3]; slam.stats.uncertainty_pitch = st.uncertainty[4]; slam.stats.uncertainty_yaw = st.uncertainty[5];
+        slam.stats.iterations.clear();
+        if (slam.last_status == SO_ICP_OK) {
+          slam.T_w_lidar = slam.last_T_w_lidar = T;
+          const double dx = T.pos.x() - guesses[f].pos.x(), dy = T.pos.y() - guesses[f].pos.y(), dz = T.pos.z() - guesses[f].pos.z();
+          slam.stats.total_translation = std::sqrt(dx * dx + dy * dy + dz * dz);
+          for (int i = 0; i < n_outer; ++i) { IterationStats is{}; is.num_surf_from_scan = st.iterations[0].num_surf_from_scan; slam.stats.iterations.push_back(is); }
+          slam.localMap.addSurfPointCloud(to_world(*clouds[f], T));  // transformAndAddToMap, LidarSlam.cpp:60-80
+        }
+      } else {
+        if (f + 1 < n_frames && f >= 1 && !seam_c) slam.StageNextScan(clouds[f + 1]);  // what the feature callback would do
+        slam.Localization(initialization, LidarSLAM::PredictionSource::LIO_ODOM, guesses[f], edge, clouds[f], times[f]);
+      }
       initialization = true;
       slam.frame_count = f; slam.laser_imu_sync = 1;    // :740-741
       wr<int32_t>(out, slam.last_status); wr<int32_t>(out, slam.startupCount);

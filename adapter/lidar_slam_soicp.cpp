@@ -102,6 +102,30 @@ int LidarSLAM::LastCorrespondences(const Transformd* pose, std::vector<so_icp_co
   return (int)info->n_accepted;
 }
 
+int LidarSLAM::MatchPlanes(const Transformd& T, const PointCloud<Point>::Ptr& planner_point, so_icp_stats* st) {
+  ensure_context();
+  push_knobs();
+  const double pose[7] = {T.pos.x(), T.pos.y(), T.pos.z(), T.rot.x(), T.rot.y(), T.rot.z(), T.rot.w()};
+  const float* xyz = planner_point && !planner_point->points.empty() ? reinterpret_cast<const float*>(planner_point->points.data()) : nullptr;
+  const size_t n = planner_point ? planner_point->points.size() : 0;
+  const int rc = so_icp_match(gpu_, xyz, n, sizeof(Point), pose, st);
+  if (rc < 0) throw std::runtime_error(std::string("so_icp_match: ") + so_icp_last_error(gpu_));
+  return rc;
+}
+
+void LidarSLAM::CorrespondenceSums(const std::vector<Transformd>& poses, std::vector<so_icp_sums>& sums) {
+  ensure_context();
+  std::vector<double> flat(poses.size() * 7);
+  for (size_t k = 0; k < poses.size(); ++k) {
+    const Transformd& T = poses[k];
+    const double p[7] = {T.pos.x(), T.pos.y(), T.pos.z(), T.rot.x(), T.rot.y(), T.rot.z(), T.rot.w()};
+    std::copy(p, p + 7, flat.begin() + 7 * k);
+  }
+  sums.resize(poses.size());
+  if (so_icp_correspondence_sums(gpu_, flat.data(), (int)poses.size(), sums.data()) < 0)
+    throw std::runtime_error(std::string("so_icp_correspondence_sums: ") + so_icp_last_error(gpu_));
+}
+
 void LidarSLAM::read_back(int32_t n_edge_points, const double T_out[7], double timeLaserOdometry) {
   const so_icp_stats& st = last_raw;
   last_flags = st.flags;

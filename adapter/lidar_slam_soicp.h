@@ -107,6 +107,15 @@ class LidarSLAM {
   // keep_correspondences below): the accepted correspondences in scan order with residual and weight at *pose (nullptr: the optimised
   // pose), so_icp_correspondences.  Returns their number; 0 with info->valid == 0 when there is nothing to export.  info may be nullptr.
   int LastCorrespondences(const Transformd* pose, std::vector<so_icp_correspondence>& out, so_icp_correspondence_info* info);
+  // Seam C, for a caller that keeps its own solver (a Ceres problem with further factors, an iterated-EKF front end): one pass of
+  // extractFeaturesConstraints (LidarSlam.cpp:299-344) at T_w_lidar_in without solving -- so_icp_match; needs keep_correspondences.  The
+  // set it forms is the one LastCorrespondences and CorrespondenceSums read; *st (may be nullptr) receives num_surf_from_scan, both
+  // histograms, the cost and JtJ / Jtr at that pose.  Tracker state (startupCount, last_T_w_lidar, uncertainty) and the map stay as they
+  // are.  Returns so_icp_register's code (SO_ICP_NOT_ENOUGH_MAP_FEATURES included); last_status is left alone.
+  int MatchPlanes(const Transformd& T_w_lidar_in, const PointCloud<Point>::Ptr& planner_point, so_icp_stats* st);
+  // cost and loss-corrected normal equations of that set at up to SO_ICP_SUMS_MAX_POSES poses, summed on the device
+  // (so_icp_correspondence_sums): sums[k] is what so_icp_lm_begin / so_icp_lm_feed take
+  void CorrespondenceSums(const std::vector<Transformd>& poses, std::vector<so_icp_sums>& sums);
 
   // ---- public fields laserMapping.cpp reads / writes (same names) ----
   Transformd T_w_lidar, last_T_w_lidar;

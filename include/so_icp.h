@@ -394,9 +394,9 @@ int so_icp_download_scan(so_icp_ctx *ctx, const void *d_scan_xyz, size_t n, floa
  * registered scan by residual, keep points that matched nothing out of the map, hand a factor-graph back end point-to-plane factors
  * instead of one pose, re-evaluate the cost of the fixed set at another pose.
  * Not exported: the correspondences of so_icp_register_batch's hypotheses, those of a sharded context (world_size > 1), the
- * neighbours' coordinates and the observability labels (not stored), normal equations (so_icp_stats::JtJ / Jtr are those of the set
- * at the default pose; at another pose the caller sums them from the records: J = [n, p x (R^T n)], JtJ += weight J J^T,
- * Jtr += weight residual J). */
+ * neighbours' coordinates and the observability labels (not stored).  Normal equations: so_icp_stats::JtJ / Jtr are those of the set
+ * at the default pose; at other poses so_icp_correspondence_sums (below, with so_icp_match) sums them on the device -- or the caller
+ * sums them from the records: J = [n, p x (R^T n)], JtJ += weight J J^T, Jtr += weight residual J. */
 /* One accepted correspondence of the last outer iteration (LS.h:209-222: Xvalue, NormDir, negative_OA_dot_norm,
  * residualCoefficient), plus its residual and weight at the evaluation pose. */
 typedef struct {
@@ -723,6 +723,42 @@ typedef struct { double opaque[96]; } so_icp_lm_state;
 int so_icp_lm_begin(so_icp_lm_state *s, const double x0[7], const so_icp_sums *sums_at_x0, int max_iterations, double next_pose[7]);
 int so_icp_lm_feed(so_icp_lm_state *s, const so_icp_sums *sums_at_next, double next_pose[7]);
 int so_icp_lm_result(const so_icp_lm_state *s, double pose[7], so_icp_iter_stats *stats /* solver fields only */);
+
+/* -------- SEAM C: for a caller that keeps its own solver.  The reference rebuilds its Ceres problem on every outer ICP iteration
+ * from extractFeaturesConstraints (LS.cpp:119-133, 299-344); a host that adds factors of its own to that problem (the absolute pose
+ * prior of addAbsolutePoseConstraints, an iterated-EKF front end that needs n, d, p per iteration) cannot use Seam A, which solves.
+ * so_icp_match is one pass of extractFeaturesConstraints at a pose of the caller's; so_icp_correspondence_sums is the evaluation of
+ * the set it left at the poses the caller's solver tries.  The loop  match -> host solve (sums per candidate) -> match ...  with
+ * so_icp_lm_begin / so_icp_lm_feed as the solver is so_icp_register (tests/seam_c_ref.py register_through_seam).
+ *
+ * so_icp_match / so_icp_match_dev: the matching half of one outer iteration at `pose` -- sub-sampling, world transform, 5-NN, plane fit
+ * and gates, residualCoefficient, both histograms -- and the evaluation at `pose`: what a registration from `pose` does before its
+ * first LM step, through the registration's own kernels (one outer iteration, no LM iteration, one launch per evaluation).
+ * stats: n_iterations = 1; iterations[0] holds num_surf_from_scan, reject_hist, obs_hist and initial_cost == final_cost, with
+ * lm_iterations = num_successful_steps = termination = 0 and pose_after = pose (termination is so_icp_lm_begin's for max_iterations 0:
+ * 4 when no point was accepted, 3 when the gradient at `pose` is already below tolerance); JtJ / Jtr are at `pose`.  Return codes are
+ * so_icp_register's (SO_ICP_NOT_ENOUGH_MAP_FEATURES included); the map window is placed as so_icp_register places it for `pose`.
+ * Needs so_icp_keep_correspondences(ctx, 1) (SO_ICP_E_INVALID otherwise): the match leaves its set as "the last registration's" --
+ * outer_iteration 0, pose_fit = pose_eval = pose -- for so_icp_correspondences and so_icp_correspondence_sums.
+ * Left alone: the previous observability histogram (so_icp_stats::uncertainty of later calls), startup_count, the tracker's last pose
+ * and time, the map's contents, scans announced with so_icp_stage_scan / so_icp_sequence_announce_next (a staged copy of this very
+ * buffer is not consumed: the match uploads it again), the chain of so_icp_register_sequence, so_icp_timing::registrations.
+ * world_size > 1: SO_ICP_E_UNSUPPORTED; a host-only context: SO_ICP_E_HIP. */
+int so_icp_match(so_icp_ctx *ctx, const float *scan_xyz, size_t n, size_t stride_bytes, const double pose[7], so_icp_stats *stats);
+int so_icp_match_dev(so_icp_ctx *ctx, const void *d_scan_xyz, size_t n, const double pose[7], so_icp_stats *stats);
+/* Cost and loss-corrected normal equations of the KEPT set (whichever call left it: a registration entry or so_icp_match) at n_poses
+ * poses, summed on the device: per pose cost, count (= n_accepted), Jtr[6], JtJ[21] (upper triangle) with
+ * J = [n, p x (R^T n)], JtJ += weight J J^T, Jtr += weight residual J, residual and weight as in so_icp_correspondence, with the a^2
+ * and Tukey variant of the call that formed the set; hist[16] = the reject and observability histograms of the outer iteration that
+ * formed it (constant over the poses: what so_icp_lm_begin / _feed carry through).  sums_out[k] is what so_icp_lm_begin / so_icp_lm_feed take.
+ * Every sum is a fixed tree (a thread's points in order, a butterfly over the wavefront, the four wavefronts in order, the 1 024-point
+ * tiles in tile order; no atomics): two calls give the same bits, pose k's sums do not depend on the other poses of the call, and cost
+ * is so_icp_correspondences(pose).cost bit for bit.  The points are read once per call, whatever n_poses; two launches, one copy of
+ * the poses in, one of n_poses x 45 doubles out, one synchronisation, on the context's queue.
+ * Nothing kept (the switch off, no set, info.valid would be 0): SO_ICP_OK and every output zero.  NULL poses / sums_out or n_poses
+ * outside 1 .. SO_ICP_SUMS_MAX_POSES: SO_ICP_E_INVALID.  A host-only context: SO_ICP_E_HIP. */
+#define SO_ICP_SUMS_MAX_POSES 64
+int so_icp_correspondence_sums(so_icp_ctx *ctx, const double *poses /* n_poses x 7 */, int n_poses, so_icp_sums *sums_out /* n_poses */);
 
 /* -------- measurement ------------------------------------------------------------------------ */
 int so_icp_get_timing(so_icp_ctx *ctx, so_icp_timing *t);

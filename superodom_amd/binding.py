@@ -227,7 +227,9 @@ EXPORTED = ["so_icp_default_config", "so_icp_create", "so_icp_destroy", "so_icp_
             "so_icp_livox_default_layout", "so_icp_extract_features_livox", "so_icp_extract_features_livox_dev",
             "so_icp_registered_scan", "so_icp_registered_scan_dev", "so_icp_extract_features_untimed", "so_icp_extract_features_untimed_dev",
             "so_icp_debug_lm_script", "so_icp_set_cloud_intensity", "so_icp_prefilter_intensity",
-            "so_icp_keep_correspondences", "so_icp_correspondences"]
+            "so_icp_keep_correspondences", "so_icp_correspondences",
+            "so_icp_match", "so_icp_match_dev", "so_icp_correspondence_sums"]
+SUMS_MAX_POSES = 64
 
 _lib = None
 
@@ -330,6 +332,9 @@ def load():
     L.so_icp_peer_enable.argtypes = [vp, C.c_int]
     L.so_icp_keep_correspondences.argtypes = [vp, C.c_int]
     L.so_icp_correspondences.argtypes = [vp, f64p, vp, C.c_size_t, u8p, f32p, C.c_size_t, C.POINTER(vp), C.POINTER(CorrespondenceInfo)]
+    L.so_icp_match.argtypes = [vp, f32p, C.c_size_t, C.c_size_t, f64p, C.POINTER(Stats)]
+    L.so_icp_match_dev.argtypes = [vp, vp, C.c_size_t, f64p, C.POINTER(Stats)]
+    L.so_icp_correspondence_sums.argtypes = [vp, f64p, C.c_int, C.POINTER(Sums)]
     _lib = L
     return L
 
@@ -567,6 +572,34 @@ class LidarSlamGpu:
         d = C.c_void_p()
         _, _, _, info = self._correspondences(pose, False, 0 if cap is None else cap, False, C.byref(d))
         return d.value, info
+
+    # ---- Seam C: the matching half at a pose of the caller's, and the kept set's sums on the device ----
+    def match(self, scan, pose):
+        """so_icp_match: one outer iteration's matching half and the evaluation at `pose` (needs keep_correspondences(True)); -> (rc, Stats)"""
+        scan = _f32(scan).reshape(-1, 3); pose = np.ascontiguousarray(pose, dtype=np.float64)
+        st = Stats()
+        rc = self._check(self.L.so_icp_match(self.h, _p(scan, C.c_float), len(scan), 12, _p(pose, C.c_double), C.byref(st)))
+        return rc, st
+
+    def match_dev(self, d_scan, n, pose):
+        pose = np.ascontiguousarray(pose, dtype=np.float64); st = Stats()
+        rc = self._check(self.L.so_icp_match_dev(self.h, d_scan, n, _p(pose, C.c_double), C.byref(st)))
+        return rc, st
+
+    def correspondence_sums(self, poses):
+        """so_icp_correspondence_sums: the kept set's cost and normal equations at `poses` ([7] or [k, 7], k <= SUMS_MAX_POSES) -> an
+        array of k Sums (what LmDriver.begin / feed take)"""
+        poses = np.ascontiguousarray(poses, dtype=np.float64).reshape(-1, 7)
+        out = (Sums * len(poses))()
+        self._check(self.L.so_icp_correspondence_sums(self.h, _p(poses, C.c_double), len(poses), out))
+        return out
+
+    def prepare_correspondence_sums(self, poses):
+        """the same with pre-built arguments (timed loops): (call, poses array the caller may rewrite in place, Sums array)"""
+        poses = np.ascontiguousarray(poses, dtype=np.float64).reshape(-1, 7).copy()
+        out = (Sums * len(poses))()
+        fn, args = self.L.so_icp_correspondence_sums, (self.h, poses.ctypes.data_as(_F64P), len(poses), out)
+        return (lambda: fn(*args)), poses, out
 
     def download_bytes(self, d_ptr, nbytes):
         """nbytes from a device address, through so_icp_download_scan (whole 12-byte units; the buffers of this library are padded)"""

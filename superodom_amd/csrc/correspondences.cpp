@@ -2,11 +2,15 @@
 // (the reference's features_corres, LidarSlam.h:209-222) read where the registration left it.  The registration entries keep a packed
 // copy of their scan and a small record of what they ran (keep_scan_copy, note_correspondences) while the switch is on; the export is
 // one launch of corr_kernels.hip's kernel on the context's queue.
+// so_icp_match(_dev) forms such a set at a pose of the caller's without solving (a registration of one outer iteration and no LM
+// iteration, so_icp_ctx::match_only); so_icp_correspondence_sums sums the kept set at up to 64 poses on the device
+// (corr_sums_kernels.hip).  Together: the matching half and the per-step evaluation of a solver the caller keeps.
 #include <hip/hip_runtime_api.h>
 
 #include <algorithm>
 #include <cstring>
 #include <memory>
+#include <string>
 
 #include "corr_kernels.h"
 #include "ctx.h"
@@ -29,6 +33,8 @@ void note_correspondences(so_icp_ctx* c, const DevState& H, const double guess[7
   // (a registration without an outer iteration formed nothing: both poses are its guess)
   std::memcpy(L.pose_fit, n_it <= 1 ? guess : H.iters[n_it - 2].pose_after, sizeof(L.pose_fit));
   std::memcpy(L.pose_eval, n_it < 1 ? guess : H.iters[n_it - 1].pose_after, sizeof(L.pose_eval));
+  // (the histograms of the iteration that formed the set: LmSums::hist of so_icp_correspondence_sums; host memory only)
+  for (int h = 0; h < 16; ++h) L.hist[h] = n_it < 1 ? 0 : (h < 7 ? H.iters[n_it - 1].reject_hist[h] : H.iters[n_it - 1].obs_hist[h - 7]);
   L.valid = true;
 }
 
@@ -51,6 +57,37 @@ struct CorrExportState {
 CorrExportState* export_state_of(so_icp_ctx* c) {
   if (!c->corr_state) c->corr_state = std::make_shared<CorrExportState>();
   return static_cast<CorrExportState*>(c->corr_state.get());
+}
+
+// so_icp_correspondence_sums' own buffers
+struct CorrSumsState {
+  DevBuf poses, partials, sums;  // the pose table | one partial vector per (tile, pose) | n_poses LmSums
+  double* h_io = nullptr;        // pinned: the poses on their way in, the sums on their way out
+  ~CorrSumsState() {
+    for (DevBuf* b : {&poses, &partials, &sums}) b->release();
+    if (h_io) (void)hipHostFree(h_io);
+  }
+};
+
+CorrSumsState* sums_state_of(so_icp_ctx* c) {
+  if (!c->corr_sums_state) c->corr_sums_state = std::make_shared<CorrSumsState>();
+  return static_cast<CorrSumsState*>(c->corr_sums_state.get());
+}
+
+// so_icp_match(_dev) behind the argument checks: the registration's own path with so_icp_ctx::match_only set
+int match_core(so_icp_ctx* c, const float* d_scan, size_t n, const double pose[7], so_icp_stats* st) {
+  double pose_out[7];
+  c->scan_staged = false;  // (the scan is the caller's or the context's own upload: no stage slot is consulted or released)
+  c->match_only = true;
+  const int rc = register_core(c, d_scan, n, pose, pose_out, st);
+  c->match_only = false;
+  return rc;
+}
+int match_refusal(so_icp_ctx* c, const char* entry) {
+  if (c->cfg.world_size > 1) return fail(c, SO_ICP_E_UNSUPPORTED, std::string(entry) + ": a sharded context (world_size > 1) keeps its correspondences per rank");
+  if (!c->corr_keep)
+    return fail(c, SO_ICP_E_INVALID, std::string(entry) + ": the match leaves its result as the kept correspondence set -- turn it on first with so_icp_keep_correspondences(ctx, 1)");
+  return SO_ICP_OK;
 }
 
 }  // namespace
@@ -125,6 +162,70 @@ int so_icp_correspondences(so_icp_ctx* c, const double pose[7], so_icp_correspon
   for (size_t b = 0; b < nblk; ++b) { double t; std::memcpy(&t, st.h_small + cost_off + b * 8, 8); cost += t; }
   info->n_accepted = n_accepted; info->cost = cost;
   if (d_records_out) *d_records_out = st.records.p;
+  return SO_ICP_OK;
+}
+
+int so_icp_match_dev(so_icp_ctx* c, const void* d_scan, size_t n, const double pose[7], so_icp_stats* st) {
+  if (!c || !pose || (!d_scan && n)) return SO_ICP_E_INVALID;
+  NEED_DEVICE(c);
+  if (const int rc = match_refusal(c, "so_icp_match_dev")) return rc;
+  HIP_TRY(c, hipSetDevice(c->cfg.device_id));
+  c->corr_last.valid = false;
+  return match_core(c, static_cast<const float*>(d_scan), n, pose, st);
+}
+
+int so_icp_match(so_icp_ctx* c, const float* xyz, size_t n, size_t stride_bytes, const double pose[7], so_icp_stats* st) {
+  if (!c || !pose || (!xyz && n)) return SO_ICP_E_INVALID;
+  NEED_DEVICE(c);
+  if (const int rc = match_refusal(c, "so_icp_match")) return rc;
+  HIP_TRY(c, hipSetDevice(c->cfg.device_id));
+  c->corr_last.valid = false;
+  // a plain upload into the context's own scan buffer: a copy of this scan announced with so_icp_stage_scan stays in its slot for the
+  // registration it was announced for (the launches that read the upload have completed when the match has reported)
+  if (const int rc = upload_scan_impl(c, xyz, n, stride_bytes, c->d_scan_own, /*wait=*/false)) return rc;
+  return match_core(c, c->d_scan_own.as<float>(), n, pose, st);
+}
+
+int so_icp_correspondence_sums(so_icp_ctx* c, const double* poses, int n_poses, so_icp_sums* sums_out) {
+  static_assert(SO_ICP_SUMS_MAX_POSES == kCorrSumsMaxPoses, "the pose table of correspondence_sums_kernel");
+  if (!c) return SO_ICP_E_INVALID;
+  if (!poses || !sums_out) return fail(c, SO_ICP_E_INVALID, "so_icp_correspondence_sums: poses and sums_out must not be NULL");
+  if (n_poses < 1 || n_poses > SO_ICP_SUMS_MAX_POSES) return fail(c, SO_ICP_E_INVALID, "so_icp_correspondence_sums: n_poses must be 1 .. SO_ICP_SUMS_MAX_POSES");
+  NEED_DEVICE(c);
+  std::memset(sums_out, 0, (size_t)n_poses * sizeof(so_icp_sums));
+  const so_icp_ctx::CorrLast& L = c->corr_last;
+  if (!c->corr_keep || !L.valid) return SO_ICP_OK;
+  CorrSumsHist hist;
+  for (int h = 0; h < 16; ++h) hist.v[h] = (double)L.hist[h];
+  const size_t n = L.n;
+  if (!n) {  // a kept set of no points: zero sums, its histograms
+    for (int k = 0; k < n_poses; ++k) std::memcpy(sums_out[k].hist, hist.v, sizeof(hist.v));
+    return SO_ICP_OK;
+  }
+  if (n >= ((size_t)1 << 31)) return fail(c, SO_ICP_E_UNSUPPORTED, "so_icp_correspondence_sums: too many points");
+  HIP_TRY(c, hipSetDevice(c->cfg.device_id));
+  CorrSumsState& st = *sums_state_of(c);
+  const size_t nblk = correspondence_workgroups((uint32_t)n), pose_bytes = (size_t)n_poses * 7 * sizeof(double), sums_bytes = (size_t)n_poses * sizeof(so_icp_sums);
+  if (!st.h_io) HIP_TRY(c, hipHostMalloc(reinterpret_cast<void**>(&st.h_io), (size_t)SO_ICP_SUMS_MAX_POSES * sizeof(so_icp_sums)));
+  HIP_TRY(c, st.poses.reserve((size_t)SO_ICP_SUMS_MAX_POSES * 7 * sizeof(double)));
+  HIP_TRY(c, st.sums.reserve((size_t)SO_ICP_SUMS_MAX_POSES * sizeof(so_icp_sums)));
+  HIP_TRY(c, st.partials.reserve(nblk * (size_t)n_poses * kCorrSumsAcc * sizeof(double)));
+  hipStream_t s = c->stream;
+  // (the poses go through pinned memory: the copy is then asynchronous whatever the caller's buffer is, and the caller's is free at once)
+  std::memcpy(st.h_io, poses, pose_bytes);
+  HIP_TRY(c, hipMemcpyAsync(st.poses.p, st.h_io, pose_bytes, hipMemcpyHostToDevice, s));
+  CorrSumsIn in;
+  in.scan = c->corr_scan.as<float>();
+  in.corr = CorrBuffers{c->d_nd.as<double4>(), c->d_coeff.as<double>(), c->d_status.as<uint8_t>()};
+  in.n = (uint32_t)n; in.a2 = L.a2; in.variant = L.variant;
+  launch_correspondence_sums(in, st.poses.as<double>(), (uint32_t)n_poses, hist, st.partials.as<double>(), st.sums.as<double>(), s);
+  HIP_TRY(c, hipGetLastError());
+  HIP_TRY(c, hipMemcpyAsync(st.h_io, st.sums.p, sums_bytes, hipMemcpyDeviceToHost, s));
+  HIP_TRY(c, hipStreamSynchronize(s));
+  std::memcpy(sums_out, st.h_io, sums_bytes);
+  for (int k = 0; k < n_poses; ++k)
+    if (sums_out[k].count != (double)L.n_accepted)
+      return fail(c, SO_ICP_E_HIP, "so_icp_correspondence_sums: the status bytes hold another number of accepted points than the registration reported");
   return SO_ICP_OK;
 }
 

@@ -8,7 +8,8 @@
 //   localization.cpp      so_icp_localization(_dev): one frame of LidarSLAM::Localization from a host or a resident scan
 //   prefilter.cpp         so_icp_prefilter_announce / _scan(_dev): adjustVoxelSize + VoxelGrid, decided on the device or on the host
 //   cloud_steps.cpp       so_icp_deskew_scan(_dev), so_icp_transform_cloud, so_icp_download_scan
-//   correspondences.cpp   so_icp_keep_correspondences, so_icp_correspondences: the last registration's correspondence set
+//   correspondences.cpp   so_icp_keep_correspondences, so_icp_correspondences: the last registration's correspondence set;
+//                         so_icp_match(_dev), so_icp_correspondence_sums: the set formed at a pose of the caller's, its sums on the device
 //   multi_gpu.cpp         RCCL, in-process groups, peer exchange, shard helpers
 //   localization_sequence.cpp, feature_extraction.cpp
 #pragma once
@@ -168,8 +169,13 @@ struct so_icp_ctx {
     double a2 = 0; int variant = 0;   // EvalParams::a2 / ::variant of that registration
     int outer_iteration = 0;
     double pose_fit[7] = {0, 0, 0, 0, 0, 0, 1}, pose_eval[7] = {0, 0, 0, 0, 0, 0, 1};  // where the set was formed / the default evaluation pose
+    int32_t hist[16] = {};            // reject_hist[7] | obs_hist[9] of the outer iteration that formed the set (so_icp_correspondence_sums)
   } corr_last;
   std::shared_ptr<void> corr_state;   // so_icp_correspondences: buffers of its own
+  std::shared_ptr<void> corr_sums_state;  // so_icp_correspondence_sums: buffers of its own
+  // so_icp_match(_dev): the registration in progress is one outer iteration's matching half and the evaluation at the guess (one
+  // outer iteration, ZERO LM iterations, per-evaluation launches); it leaves tracker, staged scans and packing policy alone
+  bool match_only = false;
   hipStream_t pf_stream = nullptr;    // the pre-filter's own queue: the next frame's upload + VoxelGrid run BESIDE the map insert the previous
   // Seam B scratch
   DevBuf d_q, d_nbr, d_d2, d_idx, d_found, d_fblist;

@@ -323,6 +323,9 @@ void plan_registration(const so_icp_ctx* c, RegPlan& p, const float* d_scan, siz
   p.d_scan = d_scan; p.n = p.n_total = n; p.pose_in = pose_in;
   p.max_outer = outer_limit(c->cfg.max_iterations);
   p.lm_max = lm_limit(c->cfg.lm_max_iterations);
+  // so_icp_match: the matching half of ONE outer iteration and the evaluation at the guess -- lm_begin ends the solve at once
+  // (iter >= max_iter, termination 0) with the sums of the guess, and the registration with it (lm_limit maps 0 to 4: not through it)
+  if (c->match_only) { p.max_outer = 1; p.lm_max = 0; }
   const bool own = !c->batch_mode && !c->borrow.on;  // this context's own registration, on its own map
   const bool one_device = c->cfg.world_size <= 1;
   const bool controller = !(c->ablate & 32);         // (ablated controller: per-evaluation launches, read-back by copy)
@@ -355,7 +358,8 @@ void plan_registration(const so_icp_ctx* c, RegPlan& p, const float* d_scan, siz
   //  evaluation there; only workgroup 0 of a launch ever waits, for workgroups that finish unconditionally)
   p.peer = c->peer_on && !one_device && c->persistent_solve && !c->batch_mode && controller;
   p.exchange = !p.peer && (c->comm != nullptr || c->group != nullptr);
-  p.persistent = c->persistent_solve && !p.exchange && (!c->batch_mode || c->batch_single) && controller;
+  // (so_icp_match: the per-evaluation launch of slot 0, whose one-thread controller is lm_solver.h as it stands; no pass follows it)
+  p.persistent = c->persistent_solve && !p.exchange && (!c->batch_mode || c->batch_single) && controller && !c->match_only;
   // deferred report: possible when the host always has the next k-NN launch in the queue before it waits for a report
   p.defer_reports = p.persistent && p.direct_rb && c->speculate;
   p.flags = (p.query_waves ? SO_ICP_FLAG_QUERY_WAVES : 0u) | (p.pb ? SO_ICP_FLAG_BINNED_AHEAD : 0u) | (p.persistent ? 0u : SO_ICP_FLAG_PER_EVAL_LAUNCHES);
@@ -594,12 +598,12 @@ static int register_core_once(so_icp_ctx* c, const float* d_scan, size_t n, cons
   if ((rc = enqueue_outer_a(c, p, 0))) return rc;
   // the NEXT scan's DMA goes out right behind this registration's first launch (the rest of what the copy queue does for that
   // scan follows below, once the launches that are not urgent -- the first sweep lasts 20 us -- are in the queue as well)
-  if (!c->batch_mode) stage_issue_deferred_copy(c);
+  if (!c->batch_mode && !c->match_only) stage_issue_deferred_copy(c);  // (so_icp_match leaves announced scans where they are)
   if ((rc = enqueue_outer_b(c, p, 0))) return rc;
   for (int it = 0;; ++it) {
     if (c->speculate && it + 1 < p.max_outer && (rc = enqueue_outer_a(c, p, it + 1))) return rc;
     // this registration's launches are in the queue and the host is about to idle: the moment for the NEXT scan's DMA
-    if (!c->batch_mode && it == 0) {
+    if (!c->batch_mode && !c->match_only && it == 0) {
       stage_issue_deferred(c, (p.may_prebin && !p.query_waves) ? pose_in : nullptr);  // (the next scan is binned behind its copy, under this registration's guess; a stream of small scans is not binned at all)
     }
     if ((rc = await_outer(c, p, it))) return rc;
@@ -608,12 +612,13 @@ static int register_core_once(so_icp_ctx* c, const float* d_scan, size_t n, cons
     if (!c->speculate && (rc = enqueue_outer_a(c, p, it + 1))) return rc;  // SOICP_SPECULATE=0: no launch that could turn out a no-op
     if ((rc = enqueue_outer_b(c, p, it + 1))) return rc;
   }
-  note_registration_done(c, c->h_ring[last & 1], p.mp, p.n, true, !c->batch_mode && !c->borrow.on);
+  note_registration_done(c, c->h_ring[last & 1], p.mp, p.n, !c->match_only, !c->batch_mode && !c->borrow.on);
   const DevState& H = *c->h_state;
-  fill_result(c, H, pose_in, st, pose_out, !c->batch_mode);
+  fill_result(c, H, pose_in, st, pose_out, !c->batch_mode && !c->match_only);
   if (keep_corr) note_correspondences(c, H, pose_in, p.n, p.ep);
   st->time_elapsed_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_icp).count();  // :199-200
   if (p.timed && (rc = collect_timing(c, p, H))) return rc;
+  if (c->match_only) return SO_ICP_OK;  // (not a registration of so_icp_timing)
   c->timing.registrations++;
   c->timing.host_ms_total += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_begin).count();
   return SO_ICP_OK;
