@@ -19,6 +19,9 @@
 //          that keeps its own solver writes) instead of Localization()'s registration, and its scan inserted at that pose through
 //          localMap.addSurfPointCloud.  Same output format; the fields a registration derives from the tracker (startupCount,
 //          uncertainty) stay as the match reports them, total_translation is |pose - guess|, flags those of the last match
+// --vio-prior: the frames as without a flag, with predictodom = VIO_ODOM, isDegenerate set and Visual_confidence_factor = 0.9 on every frame:
+//          Localization() adds the reference's absolute pose prior on the guess (LidarSlam.cpp:281-297).  Same output; one line per frame
+//          on stdout: index, stats.prediction_source
 #include <cmath>
 #include <cstdint>
 #include <cstdio>
@@ -155,7 +158,9 @@ int main(int argc, char** argv) {
     }
     const bool correspondences = argc > 3 && std::strcmp(argv[3], "--correspondences") == 0;
     const bool seam_c = argc > 3 && std::strcmp(argv[3], "--seam-c") == 0;
+    const bool vio_prior = argc > 3 && std::strcmp(argv[3], "--vio-prior") == 0;
     slam.keep_correspondences = correspondences || seam_c;
+    if (vio_prior) { slam.isDegenerate = true; slam.Visual_confidence_factor = 0.9; }
     bool initialization = false;                        // laserMapping.cpp: first frame seeds the map
     for (int f = 0; f < n_frames; ++f) {
       if (seam_c && initialization) {
@@ -178,7 +183,9 @@ int main(int argc, char** argv) {
         }
       } else {
         if (f + 1 < n_frames && f >= 1 && !seam_c) slam.StageNextScan(clouds[f + 1]);  // what the feature callback would do
-        slam.Localization(initialization, LidarSLAM::PredictionSource::LIO_ODOM, guesses[f], edge, clouds[f], times[f]);
+        slam.Localization(initialization, vio_prior ? LidarSLAM::PredictionSource::VIO_ODOM : LidarSLAM::PredictionSource::LIO_ODOM, guesses[f], edge, clouds[f],
+                          times[f]);
+        if (vio_prior) printf("frame %d: prediction_source %d\n", f, (int)slam.stats.prediction_source);
       }
       initialization = true;
       slam.frame_count = f; slam.laser_imu_sync = 1;    // :740-741

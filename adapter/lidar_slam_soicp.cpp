@@ -4,8 +4,10 @@
 #include "lidar_slam_soicp.h"
 
 #include <algorithm>
+#include <cmath>
 #include <cstddef>
 #include <cstdlib>
+#include <cstring>
 #include <stdexcept>
 
 namespace super_odometry_soicp {
@@ -149,7 +151,7 @@ void LidarSLAM::read_back(int32_t n_edge_points, const double T_out[7], double t
   stats.total_translation = st.total_translation; stats.total_rotation = st.total_rotation;
   stats.translation_from_last = st.translation_from_last; stats.rotation_from_last = st.rotation_from_last;
   stats.time_elapsed = st.time_elapsed_ms;
-  stats.prediction_source = 0;
+  stats.prediction_source = st.prediction_source;                         // LidarSlam.cpp:278, 297
   for (int i = 0; i < st.n_iterations; ++i) {
     IterationStats it;
     it.translation_norm = st.iterations[i].translation_norm; it.rotation_norm = st.iterations[i].rotation_norm;
@@ -158,7 +160,34 @@ void LidarSLAM::read_back(int32_t n_edge_points, const double T_out[7], double t
   }
 }
 
-void LidarSLAM::Localization(bool initialization, PredictionSource /*predictodom: only the dead VIO prior reads it, LidarSlam.cpp:281-283*/,
+void LidarSLAM::SetPosePrior(const Transformd& T, const double information[36]) {
+  ensure_context();
+  const double T_meas[7] = {T.pos.x(), T.pos.y(), T.pos.z(), T.rot.x(), T.rot.y(), T.rot.z(), T.rot.w()};
+  so_icp_pose_prior prior;
+  if (so_icp_pose_prior_from_information(information, T_meas, &prior) != SO_ICP_OK)
+    throw std::invalid_argument("SetPosePrior: the information matrix is not positive semi-definite");
+  if (so_icp_set_pose_prior(gpu_, &prior) < 0) throw std::runtime_error(std::string("so_icp_set_pose_prior: ") + so_icp_last_error(gpu_));
+}
+
+// shouldAddAbsolutePoseConstraints + addAbsolutePoseConstraints, LidarSlam.cpp:281-297: information = diag((1 - uncertainty_xyz) *
+// max(50, int(n * 0.1)) * V, max(10, int(n * 0.01)) * V twice, max(5, int(n * 0.001)) * 0) on `position`, n the feature count of every
+// evaluation -- stated exactly by U = its square root without the counts, and the counts as the rows' floor and fraction.  The
+// uncertainties are those this object holds, from the frame before (lidarOdomUncer).
+void LidarSLAM::add_absolute_pose_constraints(bool initialization, PredictionSource predictodom, const Transformd& position) {
+  if (!initialization || !(predictodom == PredictionSource::VIO_ODOM && isDegenerate == true && Visual_confidence_factor != 0)) return;
+  so_icp_pose_prior prior;
+  std::memset(&prior, 0, sizeof(prior));
+  const double T_meas[7] = {position.pos.x(), position.pos.y(), position.pos.z(), position.rot.x(), position.rot.y(), position.rot.z(), position.rot.w()};
+  std::memcpy(prior.T_meas, T_meas, sizeof(T_meas));
+  const double V = Visual_confidence_factor;
+  const double diag[6] = {std::sqrt((1 - stats.uncertainty_x) * V), std::sqrt((1 - stats.uncertainty_y) * V), std::sqrt((1 - stats.uncertainty_z) * V),
+                          std::sqrt(V), std::sqrt(V), 0.0};
+  const double floor_[6] = {50, 50, 50, 10, 10, 5}, fraction[6] = {0.1, 0.1, 0.1, 0.01, 0.01, 0.001};
+  for (int i = 0; i < 6; ++i) { prior.sqrt_information[7 * i] = diag[i]; prior.count_floor[i] = floor_[i]; prior.count_fraction[i] = fraction[i]; }
+  if (so_icp_set_pose_prior(gpu_, &prior) < 0) throw std::runtime_error(std::string("so_icp_set_pose_prior: ") + so_icp_last_error(gpu_));
+}
+
+void LidarSLAM::Localization(bool initialization, PredictionSource predictodom /*read by the VIO prior alone, LidarSlam.cpp:281-283*/,
                              Transformd position, PointCloud<Point>::Ptr edge_point /*dead path, LidarSlam.cpp:402-512: only its size is reported*/,
                              PointCloud<Point>::Ptr planner_point, double timeLaserOdometry) {
   ensure_context();
@@ -168,6 +197,7 @@ void LidarSLAM::Localization(bool initialization, PredictionSource /*predictodom
   double T_out[7];
   const float* xyz = planner_point && !planner_point->points.empty() ? reinterpret_cast<const float*>(planner_point->points.data()) : nullptr;
   const size_t n = planner_point ? planner_point->points.size() : 0;
+  add_absolute_pose_constraints(initialization, predictodom, position);
   last_status = so_icp_localization(gpu_, initialization ? 1 : 0, T_in, xyz, n, sizeof(Point), timeLaserOdometry, T_out, &last_raw);
   if (last_status < 0) throw std::runtime_error(std::string("so_icp_localization: ") + so_icp_last_error(gpu_));
   read_back(edge_point ? (int32_t)edge_point->points.size() : 0, T_out, timeLaserOdometry);
@@ -266,13 +296,14 @@ uint8_t* LidarSLAM::PinnedScratch(int which, size_t bytes) {
   return sc.p;
 }
 
-void LidarSLAM::LocalizationPrefiltered(bool initialization, PredictionSource, Transformd position, const void* d_planner_xyz, size_t n_planner,
+void LidarSLAM::LocalizationPrefiltered(bool initialization, PredictionSource predictodom, Transformd position, const void* d_planner_xyz, size_t n_planner,
                                         int32_t n_edge_points, double timeLaserOdometry) {
   ensure_context();
   push_knobs();
   const double T_in[7] = {position.pos.x(), position.pos.y(), position.pos.z(),
                           position.rot.x(), position.rot.y(), position.rot.z(), position.rot.w()};
   double T_out[7];
+  add_absolute_pose_constraints(initialization, predictodom, position);
   last_status = so_icp_localization_dev(gpu_, initialization ? 1 : 0, T_in, d_planner_xyz, n_planner, timeLaserOdometry, T_out, &last_raw);
   if (last_status < 0) throw std::runtime_error(std::string("so_icp_localization_dev: ") + so_icp_last_error(gpu_));
   read_back(n_edge_points, T_out, timeLaserOdometry);

@@ -117,10 +117,18 @@ class LidarSLAM {
   // (so_icp_correspondence_sums): sums[k] is what so_icp_lm_begin / so_icp_lm_feed take
   void CorrespondenceSums(const std::vector<Transformd>& poses, std::vector<so_icp_sums>& sums);
 
+  // The absolute pose prior of the reference's Ceres problem for a caller with a prior of its own: `information` (row-major 6x6, positive
+  // semi-definite) on the pose T_w_i_meas goes into the NEXT Localization() / LocalizationPrefiltered() and is consumed by it
+  // (so_icp_pose_prior_from_information + so_icp_set_pose_prior).  Localization() itself restates shouldAddAbsolutePoseConstraints and
+  // addAbsolutePoseConstraints (LidarSlam.cpp:281-297): with predictodom == VIO_ODOM, isDegenerate and Visual_confidence_factor != 0 it
+  // sets the reference's prior on `position` -- and replaces one set here.
+  void SetPosePrior(const Transformd& T_w_i_meas, const double information[36]);
+
   // ---- public fields laserMapping.cpp reads / writes (same names) ----
   Transformd T_w_lidar, last_T_w_lidar;
   int startupCount = 0;
-  bool isDegenerate = false;           // never set by the reference either (LidarSlam.cpp:977-984 is commented out)
+  bool isDegenerate = false;           // never set by the reference either (LidarSlam.cpp:977-984 is commented out); a caller who sets it
+                                       // gets the reference's VIO prior (LidarSlam.cpp:281-297)
   Vector3i pos_in_localmap;
   OptimizationStats stats;
   LocalMapFacade localMap;
@@ -142,6 +150,7 @@ class LidarSLAM {
   friend class LocalMapFacade;
   void ensure_context();
   void push_knobs();
+  void add_absolute_pose_constraints(bool initialization, PredictionSource predictodom, const Transformd& position);
   void read_back(int32_t n_edge_points, const double T_out[7], double timeLaserOdometry);
   so_icp_ctx* gpu_ = nullptr;
   bool pushed_keep_correspondences_ = false;

@@ -121,7 +121,7 @@ typedef struct {
   int32_t n_iterations;                    /* outer ICP iterations executed */
   int32_t startup_count;                   /* LidarSLAM::startupCount side effect (LS.cpp:181) */
   int32_t pos_in_localmap[3];              /* LS.cpp:363 */
-  int32_t prediction_source;               /* LS.cpp:278: reset to 0 */
+  int32_t prediction_source;               /* LS.cpp:278: reset to 0; 1 when the registration carried a pose prior (:297) */
   double total_translation, total_rotation;
   double translation_from_last, rotation_from_last;
   double time_elapsed_ms;                  /* TicToc over the ICP loop, LS.cpp:118,199-200 */
@@ -151,6 +151,7 @@ typedef struct {
 
 #define SO_ICP_FLAG_CHAINED 0x400u           /* so_icp_register_sequence: this registration's launches were enqueued behind the registration before it, before
                                                  that one had reported; its guess (guesses_out) was formed on the device */
+#define SO_ICP_FLAG_POSE_PRIOR 0x800u        /* the registration carried the prior of so_icp_set_pose_prior: costs, JtJ and Jtr include it */
 
 /* average kernel durations since the last so_icp_reset_timing (HIP events on the context's stream) */
 typedef struct {
@@ -759,6 +760,45 @@ int so_icp_match_dev(so_icp_ctx *ctx, const void *d_scan_xyz, size_t n, const do
  * outside 1 .. SO_ICP_SUMS_MAX_POSES: SO_ICP_E_INVALID.  A host-only context: SO_ICP_E_HIP. */
 #define SO_ICP_SUMS_MAX_POSES 64
 int so_icp_correspondence_sums(so_icp_ctx *ctx, const double *poses /* n_poses x 7 */, int n_poses, so_icp_sums *sums_out /* n_poses */);
+
+/* -------- ABSOLUTE POSE PRIOR inside the device solve.  The reference's Ceres problem holds, beside the point-to-plane factors, one
+ * SE3AbsolutatePoseFactor (addAbsolutePoseConstraints, LS.cpp:285-297; SE3AbsolutatePoseFactor.cpp:9-51): in a degenerate scene the VIO
+ * pose holds the axes the lidar cannot observe.  It is one 6-row residual block, so it adds nothing per point: added to the 29 sums of
+ * every evaluation it is the same Ceres problem, and the registration stays one enqueue on the device.  At a pose {t, q = x y z w}
+ *   e[0..2] = t - t_m,  qe = conj(q_m) (x) q,  e[3..5] = 2 vec(qe)                       (qe as it is, factor :21-26)
+ *   B = blockdiag(I3, w' I3 + [v']x), (v', w') = qe negated when qe.w < 0               (in the Jacobian only, factor :41-43)
+ *   d_i = sqrt(max(count_floor[i], trunc(count * count_fraction[i]))) where count_floor[i] > 0, else 1;  count = the sums' count word
+ *   r = D U e,  J = D U B;   cost += r'r / 2,  Jtr += J'r,  JtJ += J'J;   count and hist stay.
+ * count_floor / count_fraction state the reference's information exactly (std::max(50, int(good_feature_num * 0.1)), LS.cpp:289-294).
+ * T_meas' quaternion is used as given (a unit quaternion is the caller's business).  The sign rule of B is Utility::Qleft's positify as its name
+ * states it (in the reference checkout this was written against its sign flip is commented out, utility.h:37-44): where qe.w < 0 -- T_meas given with the other sign, or more than 180 degrees away -- J is MINUS the derivative of r. */
+typedef struct {
+  double T_meas[7];             /* T_w_i_meas_ */
+  double sqrt_information[36];  /* row-major U, residual = U e: what SE3AbsolutatePoseFactor.h:20-23 keeps (L^T of the LLT) */
+  double count_floor[6], count_fraction[6];   /* all zero: U as given */
+} so_icp_pose_prior;            /* 55 doubles */
+/* U = L^T of the host LLT of `information` (row-major, its lower triangle is read), T_meas copied, count_floor / count_fraction zero.
+ * SO_ICP_E_INVALID when the matrix is not positive semi-definite with a non-negative diagonal; a zero pivot with a zero column below
+ * it is allowed (the reference's information(5,5) is 0) and gives a zero row. */
+int so_icp_pose_prior_from_information(const double information[36], const double T_meas[7], so_icp_pose_prior *out);
+/* Host only, no context: adds the prior at `pose` to *inout as above (one fp64 addition per word, the sum that was there on the left),
+ * reading inout->count for the row scale.  Bit for bit what the device adds: a Seam C host loop with this call behind every
+ * so_icp_correspondence_sums is the registration with the prior set. */
+int so_icp_pose_prior_sums(const so_icp_pose_prior *prior, const double pose[7], so_icp_sums *inout);
+/* ONE-SHOT: the prior goes into the next call of so_icp_register, so_icp_register_dev, so_icp_localization or so_icp_localization_dev
+ * (scan staged or not) and is consumed when that call returns, whatever it returns -- also a localization frame that seeds the map
+ * (initialization = 0) and a call that finds too little map.  A registration the context repeats by itself (SO_ICP_FLAG_RETRIED) keeps
+ * it for the repeat.  In that registration every evaluation the controller sees carries the prior; initial_cost, final_cost,
+ * so_icp_stats::JtJ and Jtr include it (the normal equations of the Ceres problem, as ceres::Covariance would see them);
+ * prediction_source = 1 (LS.cpp:297) and SO_ICP_FLAG_POSE_PRIOR is set.  num_surf_from_scan stays the number of plane correspondences,
+ * and an evaluation with none still ends the solve with termination 4 -- Ceres would solve the prior alone there, the reference returns
+ * before it gets that far (LS.cpp:113-116).  so_icp_correspondences and so_icp_correspondence_sums keep reporting the planes only.
+ * While a prior is pending so_icp_register_batch, so_icp_register_sequence, so_icp_localization_sequence and so_icp_match(_dev) return
+ * SO_ICP_E_UNSUPPORTED and leave it pending.  prior == NULL withdraws a pending prior.
+ * world_size > 1: SO_ICP_E_UNSUPPORTED; a host-only context: SO_ICP_E_HIP; a non-finite field or a T_meas quaternion of zero norm:
+ * SO_ICP_E_INVALID.  Setting is host work only (the prior travels as an argument of that registration's solve launches); a context on
+ * which no prior was ever set does nothing more than before in any entry. */
+int so_icp_set_pose_prior(so_icp_ctx *ctx, const so_icp_pose_prior *prior /* NULL withdraws */);
 
 /* -------- measurement ------------------------------------------------------------------------ */
 int so_icp_get_timing(so_icp_ctx *ctx, so_icp_timing *t);

@@ -48,6 +48,7 @@ FLAG_QUERY_SPLIT = 128
 FLAG_BINNED_AHEAD = 256
 FLAG_QUERY_WAVES = 512
 FLAG_CHAINED = 1024
+FLAG_POSE_PRIOR = 2048
 
 
 class RegistrationError(C.Structure):
@@ -207,6 +208,41 @@ class CorrespondenceInfo(C.Structure):
                 ("pose_fit", C.c_double * 7), ("pose_eval", C.c_double * 7), ("cost", C.c_double)]
 
 
+class PosePrior(C.Structure):
+    """so_icp_pose_prior: T_meas {t, q = x y z w}, row-major U (residual = U e), the count scaling of the rows (all zero: U as given)"""
+    _fields_ = [("T_meas", C.c_double * 7), ("sqrt_information", C.c_double * 36), ("count_floor", C.c_double * 6), ("count_fraction", C.c_double * 6)]
+
+
+def pose_prior(T_meas, sqrt_information, count_floor=None, count_fraction=None):
+    """a PosePrior from arrays: T_meas[7], U[6, 6] or [36], count_floor[6], count_fraction[6] (None: zeros)"""
+    p = PosePrior()
+    p.T_meas[:] = [float(v) for v in np.asarray(T_meas, dtype=np.float64).ravel()]
+    p.sqrt_information[:] = [float(v) for v in np.asarray(sqrt_information, dtype=np.float64).ravel()]
+    if count_floor is not None:
+        p.count_floor[:] = [float(v) for v in count_floor]
+    if count_fraction is not None:
+        p.count_fraction[:] = [float(v) for v in count_fraction]
+    return p
+
+
+def pose_prior_from_information(information, T_meas):
+    """so_icp_pose_prior_from_information: U = L^T of the LLT of `information` [6, 6] -> (rc, PosePrior)"""
+    info = np.ascontiguousarray(information, dtype=np.float64).reshape(36)
+    T = np.ascontiguousarray(T_meas, dtype=np.float64).reshape(7)
+    out = PosePrior()
+    rc = load().so_icp_pose_prior_from_information(_p(info, C.c_double), _p(T, C.c_double), C.byref(out))
+    return rc, out
+
+
+def pose_prior_sums(prior, pose, sums):
+    """so_icp_pose_prior_sums: adds the prior at `pose` to `sums` (a Sums, in place); returns it"""
+    pose = np.ascontiguousarray(pose, dtype=np.float64).reshape(7)
+    rc = load().so_icp_pose_prior_sums(C.byref(prior), _p(pose, C.c_double), C.byref(sums))
+    if rc:
+        raise SoIcpError(f"so_icp_pose_prior_sums: {rc}")
+    return sums
+
+
 # the same record as a numpy structured type (np.frombuffer over so_icp_correspondence bytes)
 CORRESPONDENCE_DTYPE = np.dtype([("index", "<u4"), ("p", "<f4", 3), ("n", "<f8", 3), ("d", "<f8"), ("coeff", "<f8"), ("residual", "<f8"),
                                  ("weight", "<f8")])
@@ -228,7 +264,8 @@ EXPORTED = ["so_icp_default_config", "so_icp_create", "so_icp_destroy", "so_icp_
             "so_icp_registered_scan", "so_icp_registered_scan_dev", "so_icp_extract_features_untimed", "so_icp_extract_features_untimed_dev",
             "so_icp_debug_lm_script", "so_icp_set_cloud_intensity", "so_icp_prefilter_intensity",
             "so_icp_keep_correspondences", "so_icp_correspondences",
-            "so_icp_match", "so_icp_match_dev", "so_icp_correspondence_sums"]
+            "so_icp_match", "so_icp_match_dev", "so_icp_correspondence_sums",
+            "so_icp_pose_prior_from_information", "so_icp_pose_prior_sums", "so_icp_set_pose_prior"]
 SUMS_MAX_POSES = 64
 
 _lib = None
@@ -335,6 +372,9 @@ def load():
     L.so_icp_match.argtypes = [vp, f32p, C.c_size_t, C.c_size_t, f64p, C.POINTER(Stats)]
     L.so_icp_match_dev.argtypes = [vp, vp, C.c_size_t, f64p, C.POINTER(Stats)]
     L.so_icp_correspondence_sums.argtypes = [vp, f64p, C.c_int, C.POINTER(Sums)]
+    L.so_icp_pose_prior_from_information.argtypes = [f64p, f64p, C.POINTER(PosePrior)]
+    L.so_icp_pose_prior_sums.argtypes = [C.POINTER(PosePrior), f64p, C.POINTER(Sums)]
+    L.so_icp_set_pose_prior.argtypes = [vp, C.POINTER(PosePrior)]
     _lib = L
     return L
 
@@ -585,6 +625,11 @@ class LidarSlamGpu:
         pose = np.ascontiguousarray(pose, dtype=np.float64); st = Stats()
         rc = self._check(self.L.so_icp_match_dev(self.h, d_scan, n, _p(pose, C.c_double), C.byref(st)))
         return rc, st
+
+    def set_pose_prior(self, prior):
+        """so_icp_set_pose_prior: `prior` (a PosePrior) goes into the next register / register_dev / localization(_dev) call and is consumed
+        by it; None withdraws a pending one"""
+        self._check(self.L.so_icp_set_pose_prior(self.h, C.byref(prior) if prior is not None else None))
 
     def correspondence_sums(self, poses):
         """so_icp_correspondence_sums: the kept set's cost and normal equations at `poses` ([7] or [k, 7], k <= SUMS_MAX_POSES) -> an

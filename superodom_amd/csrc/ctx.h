@@ -10,6 +10,7 @@
 //   cloud_steps.cpp       so_icp_deskew_scan(_dev), so_icp_transform_cloud, so_icp_download_scan
 //   correspondences.cpp   so_icp_keep_correspondences, so_icp_correspondences: the last registration's correspondence set;
 //                         so_icp_match(_dev), so_icp_correspondence_sums: the set formed at a pose of the caller's, its sums on the device
+//   pose_prior.cpp        so_icp_pose_prior_from_information, so_icp_pose_prior_sums, so_icp_set_pose_prior
 //   multi_gpu.cpp         RCCL, in-process groups, peer exchange, shard helpers
 //   localization_sequence.cpp, feature_extraction.cpp
 #pragma once
@@ -176,6 +177,10 @@ struct so_icp_ctx {
   // so_icp_match(_dev): the registration in progress is one outer iteration's matching half and the evaluation at the guess (one
   // outer iteration, ZERO LM iterations, per-evaluation launches); it leaves tracker, staged scans and packing policy alone
   bool match_only = false;
+  // so_icp_set_pose_prior: the prior of the NEXT registration entry (one-shot: PriorOneShot); it travels as the last argument of that
+  // registration's solve / evaluation launches
+  bool prior_pending = false;
+  PosePrior prior{};
   hipStream_t pf_stream = nullptr;    // the pre-filter's own queue: the next frame's upload + VoxelGrid run BESIDE the map insert the previous
   // Seam B scratch
   DevBuf d_q, d_nbr, d_d2, d_idx, d_found, d_fblist;
@@ -331,6 +336,13 @@ namespace soicp::host {
 
 // sets the text so_icp_last_error returns and passes `code` through
 inline int fail(so_icp_ctx* c, int code, const std::string& msg) { c->err = msg; return code; }
+// so_icp_set_pose_prior: so_icp_register(_dev) and so_icp_localization(_dev) consume the pending prior when they return, whatever they
+// return; the entries that cannot carry one refuse the call and leave it pending
+struct PriorOneShot { so_icp_ctx* c; ~PriorOneShot() { c->prior_pending = false; } };
+inline int refuse_pending_prior(so_icp_ctx* c, const char* entry) {
+  return c->prior_pending ? fail(c, SO_ICP_E_UNSUPPORTED, std::string(entry) + ": a pose prior is pending (so_icp_set_pose_prior); it goes into so_icp_register(_dev) "
+                                                          "or so_icp_localization(_dev) -- withdraw it with so_icp_set_pose_prior(ctx, NULL) first") : SO_ICP_OK;
+}
 // what a DeviceMap member returns (device_map.h: -1 out of memory / a full cube, -2 a HIP error, its text in c->err; else >= 0) as a C ABI code
 inline int map_status(int r) { return r >= 0 ? SO_ICP_OK : (r == -1 ? SO_ICP_E_NOMEM : SO_ICP_E_HIP); }
 // the stride rule of the entries that read float x y z records: 0 means packed (12 bytes); a multiple of 4
@@ -383,7 +395,7 @@ struct RegWork {
 void launch_sweep(so_icp_ctx* c, const RegWork& w, MatchParams& mp_it, bool first, const so_icp_ctx::StageSlot* begin_slot, const double pose[7],
                   uint32_t chain_expect, hipEvent_t ev_start, hipEvent_t ev_stop);
 // The whole solve of one outer iteration in one launch; gives `ep_it` (the caller's copy: defer_publish, chain_*) its epoch
-void launch_persistent_solve(so_icp_ctx* c, const RegWork& w, EvalParams& ep_it, const MatchParams& mp);
+void launch_persistent_solve(so_icp_ctx* c, const RegWork& w, EvalParams& ep_it, const MatchParams& mp, const PosePrior* prior = nullptr);
 // The host's wait for the report `want` in a pinned mirror's seq word; `s`: the queue whose draining ends the wait without one.  The
 // mirrors are polled; the watchdog of that wait is the clock and, once it has run out, the queue (so_icp_ctx::speculate has the
 // measured reason why nothing -- no event, no stream query -- accompanies the wait in the normal case).

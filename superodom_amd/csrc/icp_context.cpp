@@ -180,11 +180,11 @@ void launch_sweep(so_icp_ctx* c, const RegWork& w, MatchParams& mp_it, bool firs
 }
 // setupOptimizationProblem + solveOptimizationProblem (LidarSlam.cpp:213-240) of one outer iteration: the whole solve in one launch
 // (workgroups hand the next pose to each other on the device).  (The span is one of profiling mode, time_kernels 2.)
-void launch_persistent_solve(so_icp_ctx* c, const RegWork& w, EvalParams& ep_it, const MatchParams& mp) {
+void launch_persistent_solve(so_icp_ctx* c, const RegWork& w, EvalParams& ep_it, const MatchParams& mp, const PosePrior* prior) {
   ep_it.epoch_base = (++c->solve_launches) << 5;
   span_begin(c, 1, (uint32_t)w.n);
   launch_solve(w.lm_max, w.d_scan, w.d_scan + 1, w.d_scan + 2, w.corr, c->d_state, ep_it, c->d_partials, c->d_ticket, c->d_hist, c->d_sums, c->view,
-               c->d_nbr5.as<uint32_t>(), mp, (uint32_t)w.n, (uint32_t)c->n_cus, c->stream);
+               c->d_nbr5.as<uint32_t>(), mp, (uint32_t)w.n, (uint32_t)c->n_cus, c->stream, prior);
   span_end(c);
 }
 Report await_report(so_icp_ctx* c, const volatile unsigned long long* seq, unsigned long long want, hipStream_t s) {
@@ -310,7 +310,7 @@ struct RegPlan : RegWork {
   size_t n_total = 0;  // the whole scan; n: what this context registers of it (its share under a query split)
   QueryShare share{0, false, 0};
   bool solo = false, qsplit = false, may_prebin = false, begin_in_knn = false, rebin = false, direct_rb = false, timed = false, peer = false,
-       exchange = false, persistent = false, defer_reports = false;
+       exchange = false, persistent = false, defer_reports = false, prior = false;
   so_icp_ctx::StageSlot* pb = nullptr;  // the scan was binned ahead: its work list is in this slot
   uint32_t flags = 0, chunk_cap = 0;    // (flags: what of the modes goes into so_icp_stats::flags)
   BinTable bt{nullptr, nullptr, nullptr, 0};
@@ -362,7 +362,10 @@ void plan_registration(const so_icp_ctx* c, RegPlan& p, const float* d_scan, siz
   p.persistent = c->persistent_solve && !p.exchange && (!c->batch_mode || c->batch_single) && controller && !c->match_only;
   // deferred report: possible when the host always has the next k-NN launch in the queue before it waits for a report
   p.defer_reports = p.persistent && p.direct_rb && c->speculate;
-  p.flags = (p.query_waves ? SO_ICP_FLAG_QUERY_WAVES : 0u) | (p.pb ? SO_ICP_FLAG_BINNED_AHEAD : 0u) | (p.persistent ? 0u : SO_ICP_FLAG_PER_EVAL_LAUNCHES);
+  // so_icp_set_pose_prior: the PRIOR instantiations of the solve / evaluation kernels add it to every evaluation's sums
+  p.prior = carries_pose_prior(c->prior_pending, own, c->cfg.world_size, c->match_only) && !p.exchange;
+  p.flags = (p.query_waves ? SO_ICP_FLAG_QUERY_WAVES : 0u) | (p.pb ? SO_ICP_FLAG_BINNED_AHEAD : 0u) | (p.persistent ? 0u : SO_ICP_FLAG_PER_EVAL_LAUNCHES) |
+            (p.prior ? SO_ICP_FLAG_POSE_PRIOR : 0u);
 }
 
 // this rank's share of a split scan gathered into d_sub, the scan buffers, and where the sweeps find their work
@@ -436,7 +439,7 @@ int enqueue_eval(so_icp_ctx* c, RegPlan& p, int slot) {
   span_begin(c, 1, (uint32_t)p.n);
   const bool fuse_lm = !p.exchange;  // single device: the last workgroup of eval runs the LM controller itself
   launch_eval(slot, fuse_lm, p.d_scan, p.d_scan + 1, p.d_scan + 2, p.corr, ds, p.ep, c->d_partials,
-              c->d_ticket, c->d_hist, c->d_sums, c->view, c->d_nbr5.as<uint32_t>(), p.mp, (uint32_t)p.n, s);
+              c->d_ticket, c->d_hist, c->d_sums, c->view, c->d_nbr5.as<uint32_t>(), p.mp, (uint32_t)p.n, s, p.prior ? &c->prior : nullptr);
   span_end(c);
   if (!fuse_lm && c->group) {  // in-process group: through host memory (every member calls this the same number of times)
     HIP_TRY(c, hipMemcpyAsync(c->h_sums, c->d_sums, sizeof(LmSums), hipMemcpyDeviceToHost, s));
@@ -482,7 +485,7 @@ int enqueue_outer_b(so_icp_ctx* c, RegPlan& p, int it) {
     EvalParams ep_it = p.ep;
     // (deferred: the k-NN launch of it + 1 will be enqueued before the host waits)
     ep_it.defer_publish = (p.defer_reports && it + 1 < p.max_outer) ? 1 : 0;
-    launch_persistent_solve(c, p, ep_it, p.mp);
+    launch_persistent_solve(c, p, ep_it, p.mp, p.prior ? &c->prior : nullptr);
   } else {
     for (int slot = 1; slot <= p.lm_max; ++slot) { const int r = enqueue_eval(c, p, slot); if (r) return r; }
   }
@@ -615,6 +618,7 @@ static int register_core_once(so_icp_ctx* c, const float* d_scan, size_t n, cons
   note_registration_done(c, c->h_ring[last & 1], p.mp, p.n, !c->match_only, !c->batch_mode && !c->borrow.on);
   const DevState& H = *c->h_state;
   fill_result(c, H, pose_in, st, pose_out, !c->batch_mode && !c->match_only);
+  if (p.prior) st->prediction_source = 1;  // addAbsolutePoseConstraints, LidarSlam.cpp:297
   if (keep_corr) note_correspondences(c, H, pose_in, p.n, p.ep);
   st->time_elapsed_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_icp).count();  // :199-200
   if (p.timed && (rc = collect_timing(c, p, H))) return rc;
@@ -1031,7 +1035,9 @@ int so_icp_free_scan(so_icp_ctx* c, void* d_scan) {
 }
 
 int so_icp_register_dev(so_icp_ctx* c, const void* d_scan, size_t n, const double pose_in[7], double pose_out[7], so_icp_stats* st) {
-  if (!c || !pose_in || !pose_out || (!d_scan && n)) return SO_ICP_E_INVALID;
+  if (!c) return SO_ICP_E_INVALID;
+  const PriorOneShot consume{c};
+  if (!pose_in || !pose_out || (!d_scan && n)) return SO_ICP_E_INVALID;
   NEED_DEVICE(c);
   HIP_TRY(c, hipSetDevice(c->cfg.device_id));
   c->corr_last.valid = false;
@@ -1039,7 +1045,9 @@ int so_icp_register_dev(so_icp_ctx* c, const void* d_scan, size_t n, const doubl
 }
 
 int so_icp_register(so_icp_ctx* c, const float* xyz, size_t n, size_t stride_bytes, const double pose_in[7], double pose_out[7], so_icp_stats* st) {
-  if (!c || !pose_in || !pose_out || (!xyz && n)) return SO_ICP_E_INVALID;
+  if (!c) return SO_ICP_E_INVALID;
+  const PriorOneShot consume{c};
+  if (!pose_in || !pose_out || (!xyz && n)) return SO_ICP_E_INVALID;
   NEED_DEVICE(c);
   HIP_TRY(c, hipSetDevice(c->cfg.device_id));
   c->corr_last.valid = false;

@@ -6,6 +6,7 @@
 #include <cstdint>
 
 #include "lm_solver.h"
+#include "pose_prior.h"
 #include "so_math.h"
 
 namespace soicp {
@@ -230,11 +231,13 @@ void launch_knn_query_waves(const float* d_scan_xyz, uint32_t n, DevState* st, c
 void launch_eval(int slot, bool fuse_lm, const float* spx, const float* spy, const float* spz, const CorrBuffers& corr,
                  DevState* st, const EvalParams& ep, double* d_partials, uint32_t* d_ticket, int32_t* d_hist,
                  LmSums* d_sums, const DevMapView& map, const uint32_t* d_nbr5, const MatchParams& mp, uint32_t n_upper,
-                 hipStream_t s);
+                 hipStream_t s, const PosePrior* prior = nullptr /* the registration's pose prior (so_icp_set_pose_prior): eval_kernel_prior, whose
+                                                                    last ARGUMENT it is -- no copy, and the kernels without one keep their arguments */);
 // the whole solve (slot 0 .. lm_max) of one outer iteration in one launch (single device only)
 void launch_solve(int lm_max, const float* spx, const float* spy, const float* spz, const CorrBuffers& corr, DevState* st,
                   const EvalParams& ep, double* d_partials, uint32_t* d_ticket, int32_t* d_hist, LmSums* d_sums,
-                  const DevMapView& map, const uint32_t* d_nbr5, const MatchParams& mp, uint32_t n_upper, uint32_t max_blocks, hipStream_t s);
+                  const DevMapView& map, const uint32_t* d_nbr5, const MatchParams& mp, uint32_t n_upper, uint32_t max_blocks, hipStream_t s,
+                  const PosePrior* prior = nullptr /* as launch_eval's (solve_kernel_prior); single device only */);
 // workgroups of the single-registration solve launch for a scan of n_upper queries (the grid a batch stands in for)
 uint32_t solve_grid(uint32_t n_upper, uint32_t max_blocks);
 // workgroups of the batched solve launch that are certainly resident together on n_cus compute units (occupancy query of the

@@ -34,6 +34,7 @@
 #include "device_idioms.h"
 #include "kernels.h"
 #include "plane_fit.h"
+#include "pose_prior.h"
 
 namespace soicp {
 
@@ -1984,6 +1985,27 @@ __device__ __forceinline__ double reduce_records(double (*red)[kRedStride], doub
   return tot;
 }
 
+// ---- the absolute pose prior of a registration that carries one (pose_prior.h; PRIOR instantiations only).  Its 55 doubles are the
+// last argument of solve_kernel_prior / eval_kernel_prior (P points into the kernarg segment: no copy, no allocation, nothing in the
+// queue in front of the registration; the kernels without a prior keep their arguments).  The controller's workgroup forms every total
+// of a pass in thread `word` < kNAcc of its first wavefront; that thread adds the prior's word -- what needs the pose alone is formed
+// first (prior_prepare), the row scale needs the pass's count, which is thread 1's total.
+#ifndef SO_PRIOR_OVERLAP
+#define SO_PRIOR_OVERLAP 1  // persistent launch: prior_prepare runs in front of the wait for the pass's records (0: behind it)
+#endif
+static_assert(kNAcc == kPriorSumWords, "one thread per word of the prior's contribution");
+__device__ __forceinline__ void prior_prepare(const double* P, const Pose& pose, int word, PosePriorPart& part) {
+  double p7[7];
+  pose_to_array(pose, p7);
+  pose_prior_prepare(P, p7, word, part);
+}
+// total of thread `word` with the prior added (plane sum on the left); every thread word < kNAcc calls it together
+__device__ __forceinline__ double prior_added(const PosePriorPart& part, double tot, int word) {
+  const double count = __hiloint2double(__builtin_amdgcn_readlane(__double2hiint(tot), 1), __builtin_amdgcn_readlane(__double2loint(tot), 1));
+  const double v = pose_prior_finish(part, count, word);
+  return word == 1 ? tot : tot + v;
+}
+
 struct EvalShared {
   double red[256][kRedStride];  // 60 KB: per-thread accumulators, later the workgroup records
   double part[8][32];
@@ -2020,10 +2042,11 @@ __device__ __forceinline__ void store_stamps(DevState* st, const PassStamps& T, 
 // ---- The hand-over of the per-evaluation launches (eval_kernel; see eval_pass for the return codes): this workgroup's record
 // `mine` is stored and counted; workgroup 0 waits for the count, adds the records and runs lm_control (st->lm_more and
 // st->eval_pose tell the next launch what to do) or, !fuse_lm, leaves the sums in `out`.
-template <bool FIT, bool PROF>
+// PRIOR: the sums of the pass -- the controller's and those in `out` -- carry the pose prior `prior` at `pose`, the pass's pose.
+template <bool FIT, bool PROF, bool PRIOR = false>
 __device__ __forceinline__ int hand_over_ticketed(int slot, int fuse_lm, double mine, DevState* __restrict__ st, const EvalParams& ep,
                                                   double* __restrict__ partials, uint32_t* __restrict__ ticket, int32_t* __restrict__ hist,
-                                                  LmSums* __restrict__ out, EvalShared& sh, PassStamps& T) {
+                                                  LmSums* __restrict__ out, EvalShared& sh, PassStamps& T, const Pose& pose, const double* prior) {
   const int tid = threadIdx.x;
   const int abl = PROF ? ep.ablate : 0;
   const bool stamp = PROF && (abl & 128) != 0;
@@ -2100,6 +2123,11 @@ __device__ __forceinline__ int hand_over_ticketed(int slot, int fuse_lm, double 
   const double total = reduce_records(sh.red, sh.part, tid);
   double* o = reinterpret_cast<double*>(&sh.sums);
   if (tid < kNAcc) {
+    if constexpr (PRIOR) {
+      PosePriorPart part;
+      prior_prepare(prior, pose, tid, part);
+      o[tid] = prior_added(part, total, tid);
+    } else
     o[tid] = total;  // cost, count, Jtr[6], JtJ[21]
   } else if (tid >= 32 && tid < 48) {
     int h = 0;
@@ -2138,14 +2166,16 @@ __device__ __forceinline__ int hand_over_ticketed(int slot, int fuse_lm, double 
 struct WgSpan { uint32_t vb0, vb1, V; bool ctl; };
 // PEER  : the instantiation with the peer exchange compiled in (sharded registration, N > 1); the single-device launches carry
 //         none of its index arithmetic and arguments
-template <bool FIT, bool PERSIST = false, bool PROF = false, bool BATCH = false, bool PEER = false>
+// PRIOR : the registration carries a pose prior (single device, not BATCH): the controller's workgroup adds it -- the 55 doubles at
+//         `prior` -- to the pass's sums
+template <bool FIT, bool PERSIST = false, bool PROF = false, bool BATCH = false, bool PEER = false, bool PRIOR = false>
 __device__ __forceinline__ int eval_pass(int slot, int fuse_lm, const Pose& pose, const float* __restrict__ spx,
                                          const float* __restrict__ spy, const float* __restrict__ spz,
                                          const CorrBuffers& corr, DevState* __restrict__ st, const EvalParams& ep,
                                          double* __restrict__ partials, uint32_t* __restrict__ ticket,
                                          int32_t* __restrict__ hist, LmSums* __restrict__ out,
                                          const float4* __restrict__ mpts, const uint32_t* __restrict__ nbr5,
-                                         const MatchParams& mp, EvalShared& sh, unsigned long long pass_tag = 0,
+                                         const MatchParams& mp, EvalShared& sh, const double* prior, unsigned long long pass_tag = 0,
                                          CorrCache* cc = nullptr, u4v* hand = nullptr, unsigned long long want = 0,
                                          const WgSpan span = WgSpan{0, 0, 0, false}) {
   // PERSIST (solve_kernel): workgroup 0 is the finisher of every pass of the launch, so the controller state stays in
@@ -2160,6 +2190,7 @@ __device__ __forceinline__ int eval_pass(int slot, int fuse_lm, const Pose& pose
   int32_t* lh = sh.lh;
   const int tid = threadIdx.x;
   static_assert(!BATCH || PERSIST, "batched hypotheses run in the persistent solve launch");
+  static_assert(!PRIOR || (!BATCH && !PEER), "the pose prior belongs to the single registration on one device");
   const int abl = PROF ? ep.ablate : 0;
   const bool stamp = PROF && (abl & 128) != 0;
   const uint32_t V = BATCH ? span.V : gridDim.x;                    // workgroups of the (virtual) grid
@@ -2397,6 +2428,10 @@ __device__ __forceinline__ int eval_pass(int slot, int fuse_lm, const Pose& pose
     const bool poller = tid < kPoll;
     const int g = poller ? tid / kNAcc : 0, a = poller ? tid - g * kNAcc : 0;
     const u4v* base = rec + (poller ? tid : 0);
+    [[maybe_unused]] PosePriorPart prior_part;
+    if constexpr (PRIOR && SO_PRIOR_OVERLAP != 0) {  // the pass's pose is known: everything of the prior but the row scale, beside the records' way here
+      if (tid < kNAcc) prior_prepare(prior, pose, tid, prior_part);
+    }
     if (!BATCH) {
     u4v r[32];
     const unsigned long long t0 = wall_clock64();
@@ -2479,6 +2514,10 @@ __device__ __forceinline__ int eval_pass(int slot, int fuse_lm, const Pose& pose
       double tot = 0;
 #pragma unroll
       for (int cc8 = 0; cc8 < 8; ++cc8) tot += part[cc8][tid];
+      if constexpr (PRIOR) {
+        if (SO_PRIOR_OVERLAP == 0) prior_prepare(prior, pose, tid, prior_part);
+        tot = prior_added(prior_part, tot, tid);
+      }
       o[tid] = tot;  // cost, count, Jtr[6], JtJ[21]
     } else if (FIT && tid >= 32 && tid < 48) {  // the 16 counters; later passes of the solve keep them in LDS
       int h = 0;
@@ -2559,7 +2598,7 @@ __device__ __forceinline__ int eval_pass(int slot, int fuse_lm, const Pose& pose
     if (stamp && tid == 0 && (FIT || slot == 1)) store_stamps<FIT>(st, T, !FIT || BATCH);
     return sh_more ? kPassMore : kPassDone;
   }
-  return hand_over_ticketed<FIT, PROF>(slot, fuse_lm, mine, st, ep, partials, ticket, hist, out, sh, T);
+  return hand_over_ticketed<FIT, PROF, PRIOR>(slot, fuse_lm, mine, st, ep, partials, ticket, hist, out, sh, T, pose, prior);
 }
 
 static_assert(sizeof(LmState) / 8 <= 256, "controller state is moved one word per thread");
@@ -2568,6 +2607,7 @@ static_assert(sizeof(LmState) / 8 <= 256, "controller state is moved one word pe
 //              plane, inlier gate, coefficient, observability labels -> correspondence record + histograms), then
 //              the first evaluation at the outer pose.
 // FIT = false: evaluations at the poses requested by the LM controller.
+// (eval_kernel_prior: the same launch for a registration that carries a pose prior, see eval_pass)
 template <bool FIT, bool PROF>
 __global__ __launch_bounds__(256, SO_SOLVE_BLOCKS / 256) void eval_kernel(int slot, int fuse_lm, const float* __restrict__ spx,
                                                    const float* __restrict__ spy, const float* __restrict__ spz,
@@ -2576,14 +2616,29 @@ __global__ __launch_bounds__(256, SO_SOLVE_BLOCKS / 256) void eval_kernel(int sl
                                                    int32_t* __restrict__ hist, LmSums* __restrict__ out,
                                                    const float4* __restrict__ mpts, const uint32_t* __restrict__ nbr5,
                                                    MatchParams mp) {
-  __shared__ EvalShared sh;
-  if (SO_ENTRY_WARM) {
-    st = after_loaded(st, kernarg_lines<decltype(&eval_kernel<FIT, PROF>)>());
-    st = after_loaded(st, SO_WARM_FIELDS(st, DevState, max_outer, eval_pose));  // reg_done, lm_more, either pose
-  }
-  if (!eval_slot_active(st, slot)) return;
-  const Pose pose = pose_from_array(slot == 0 ? st->T : st->eval_pose);
-  (void)eval_pass<FIT, false, PROF>(slot, fuse_lm, pose, spx, spy, spz, corr, st, ep, partials, ticket, hist, out, mpts, nbr5, mp, sh);
+#define SO_BODY_KERNEL eval_kernel<FIT, PROF>
+#define SO_BODY_PRIOR false
+#define SO_BODY_PRIOR_WORDS nullptr
+#include "eval_kernel_body.inc"
+#undef SO_BODY_KERNEL
+#undef SO_BODY_PRIOR
+#undef SO_BODY_PRIOR_WORDS
+}
+template <bool FIT, bool PROF>
+__global__ __launch_bounds__(256, SO_SOLVE_BLOCKS / 256) void eval_kernel_prior(int slot, int fuse_lm, const float* __restrict__ spx,
+                                                   const float* __restrict__ spy, const float* __restrict__ spz,
+                                                   CorrBuffers corr, DevState* __restrict__ st, EvalParams ep,
+                                                   double* __restrict__ partials, uint32_t* __restrict__ ticket,
+                                                   int32_t* __restrict__ hist, LmSums* __restrict__ out,
+                                                   const float4* __restrict__ mpts, const uint32_t* __restrict__ nbr5,
+                                                   MatchParams mp, PosePrior prior) {
+#define SO_BODY_KERNEL eval_kernel_prior<FIT, PROF>
+#define SO_BODY_PRIOR true
+#define SO_BODY_PRIOR_WORDS reinterpret_cast<const double*>(&prior)
+#include "eval_kernel_body.inc"
+#undef SO_BODY_KERNEL
+#undef SO_BODY_PRIOR
+#undef SO_BODY_PRIOR_WORDS
 }
 
 // The whole solve of one outer iteration in ONE launch (single device): slot 0 = plane fit + first evaluation, then up
@@ -2604,74 +2659,31 @@ __global__ __launch_bounds__(256, BATCH ? 2 : 1) void solve_kernel(int lm_max, c
                                                     int32_t* __restrict__ hist, LmSums* __restrict__ out,
                                                     const float4* __restrict__ mpts, const uint32_t* __restrict__ nbr5,
                                                     MatchParams mp, BatchView bv) {
-  __shared__ EvalShared sh;
-  __shared__ CorrCache cache;  // 26 KB next to the 64 KB of EvalShared: gfx950 has 160 KB of LDS per CU, one workgroup each here
-  unsigned long long t_entry = 0;
-  if (PROF && !BATCH) t_entry = wall_clock64();  // (profiling: "kernel entry -> first pass begins", word 3 of the fit record)
-  if (SO_ENTRY_WARM) st = after_loaded(st, kernarg_lines<decltype(&solve_kernel<PROF, BATCH, PEER>)>());
-  WgSpan span{0, 0, 0, false};
-  if (BATCH) {
-    const uint32_t G = bv.wg_per_hyp, hi = blockIdx.x / G, sub = blockIdx.x - hi * G;
-    const size_t h = bv.active[hi];
-    st += h; corr.nd += h * bv.bs; corr.coeff += h * bv.bs; corr.status += h * bv.bs; nbr5 += h * 5 * bv.bs;
-    partials += h * bv.partial_stride; ticket += h * bv.sync_stride; hist += h * (kHistReplicas * kHistStride);
-    span.V = bv.v_grid;
-    span.vb0 = (uint32_t)(((unsigned long long)sub * bv.v_grid) / G);
-    span.vb1 = (uint32_t)(((unsigned long long)(sub + 1u) * bv.v_grid) / G);
-    span.ctl = sub == 0;
-  }
-  if (SO_ENTRY_WARM) st = after_loaded(st, state_lines<true, !BATCH>(st));
-  if (st->reg_done) return;
-  if (!BATCH && ep.chain_expect && st->done_count != ep.chain_expect) return;  // chained registration whose predecessor was not over: no-op
-  const int tid = threadIdx.x;
-  // hand-off record: 8 chunks of 16 bytes {value, epoch}, each written / read with ONE sc1 dwordx4 access (atomic as a
-  // unit), so a reader that sees the expected epoch in a chunk has that chunk's value: no second round trip, no
-  // publisher-side wait between data and flag.  Chunks 0..6 = next pose, chunk 7 = "another evaluation follows".
-  u4v* hand = reinterpret_cast<u4v*>(ticket + kHandoffWordOffset);
-  // epoch base of this launch: a kernel argument (the host counts its solve launches; 32 epochs per launch), larger than
-  // every epoch an earlier launch left in the hand-off record -- no memory round trip before the first pass can start
-  const unsigned long long e0 = ep.epoch_base;
-  Pose pose = pose_from_array(st->T);
-  if (tid == 0) {  // the controller's inputs are constant over the launch (read here, next to the pose: no fetch inside a pass)
-    sh.peer_seq = st->peer_seq;
-    for (int i = 0; i < 3; ++i) sh.ctl.T[i] = pose.t[i];
-    for (int i = 0; i < 4; ++i) sh.ctl.T[3 + i] = pose.q[i];
-    sh.ctl.lm_max = st->lm_max; sh.ctl.outer_iter = st->outer_iter; sh.ctl.max_outer = st->max_outer;
-  }
-  const unsigned long long tag0 = (e0 + 1ull) << 5;  // pass tags: unique over launches (every launch advances the epoch) and passes (slot <= 16)
-  if (PROF && !BATCH && (ep.ablate & 128) && tid == 0 && blockIdx.x == 0) st->dbg[3] = wall_clock64() - t_entry;
-  int code = eval_pass<true, true, PROF, BATCH, PEER>(0, 1, pose, spx, spy, spz, corr, st, ep, partials, ticket, hist, out, mpts, nbr5, mp, sh, tag0, &cache, hand, e0 + 1ull, span);
-  for (int slot = 1; slot <= lm_max; ++slot) {
-    __syncthreads();
-    const unsigned long long want = e0 + (unsigned long long)slot;
-    if (code == kPassMore || code == kPassDone) {
-      // this workgroup ran the controller, whose thread has already published {request, more?} with epoch `want` and
-      // left them in sh.pose / sh.more
-    } else if (tid < 64) {  // wait for the controller's workgroup: lanes 0..7 poll one chunk each
-      bool done = tid >= 8;
-      unsigned long long val = 0;
-      const unsigned long long t0 = wall_clock64();
-      bool ok = true;
-      for (;;) {
-        if (!done) {
-          const u4v v = load16_sc1(hand + tid);
-          const unsigned long long tag = ((unsigned long long)v.w << 32) | v.z;
-          if (tag - e0 >= (unsigned long long)slot && tag - e0 <= 64ull) { done = true; val = ((unsigned long long)v.y << 32) | v.x; }
-        }
-        if (__ballot(!done) == 0ull) break;
-        // (the controller's workgroup may itself be waiting for the other ranks' records: twice its patience + the local 50 ms)
-        if (wall_clock64() - t0 > 2ull * ep.timeout_ticks + 5000000ull) { ok = false; break; }  // give up instead of hanging the device
-        __builtin_amdgcn_s_sleep(1);
-      }
-      if (tid < 7) sh.pose[tid] = __longlong_as_double((long long)val);
-      if (tid == 7) sh.more = ok ? (int)val : -1;
-    }
-    __syncthreads();
-    if (sh.more != 1) return;  // solve ended (or timeout)
-    pose = pose_from_array(sh.pose);
-    __syncthreads();
-    code = eval_pass<false, true, PROF, BATCH, PEER>(slot, 1, pose, spx, spy, spz, corr, st, ep, partials, ticket, hist, out, mpts, nbr5, mp, sh, tag0 + (unsigned long long)slot, &cache, hand, want + 1ull, span);
-  }
+#define SO_BODY_KERNEL solve_kernel<PROF, BATCH, PEER>
+#define SO_BODY_PRIOR false
+#define SO_BODY_PRIOR_WORDS nullptr
+#include "solve_kernel_body.inc"
+#undef SO_BODY_KERNEL
+#undef SO_BODY_PRIOR
+#undef SO_BODY_PRIOR_WORDS
+}
+// the single-device launch of a registration that carries a pose prior (so_icp_set_pose_prior): solve_kernel<PROF, false, false> whose
+// controller's workgroup adds the prior to every pass's sums
+template <bool PROF>
+__global__ __launch_bounds__(256, 1) void solve_kernel_prior(int lm_max, const float* __restrict__ spx, const float* __restrict__ spy,
+                                                    const float* __restrict__ spz, CorrBuffers corr, DevState* __restrict__ st,
+                                                    EvalParams ep, double* __restrict__ partials, uint32_t* __restrict__ ticket,
+                                                    int32_t* __restrict__ hist, LmSums* __restrict__ out,
+                                                    const float4* __restrict__ mpts, const uint32_t* __restrict__ nbr5,
+                                                    MatchParams mp, BatchView bv, PosePrior prior) {
+  constexpr bool BATCH = false, PEER = false;
+#define SO_BODY_KERNEL solve_kernel_prior<PROF>
+#define SO_BODY_PRIOR true
+#define SO_BODY_PRIOR_WORDS reinterpret_cast<const double*>(&prior)
+#include "solve_kernel_body.inc"
+#undef SO_BODY_KERNEL
+#undef SO_BODY_PRIOR
+#undef SO_BODY_PRIOR_WORDS
 }
 
 // controller as its own launch (used when the sums pass through the RCCL all-reduce between eval and control)
@@ -2925,10 +2937,13 @@ uint32_t solve_grid(uint32_t n_upper, uint32_t max_blocks) {
 }
 void launch_eval(int slot, bool fuse_lm, const float* spx, const float* spy, const float* spz, const CorrBuffers& corr,
                  DevState* st, const EvalParams& ep, double* partials, uint32_t* ticket, int32_t* hist, LmSums* sums,
-                 const DevMapView& map, const uint32_t* nbr5, const MatchParams& mp, uint32_t n_upper, hipStream_t s) {
+                 const DevMapView& map, const uint32_t* nbr5, const MatchParams& mp, uint32_t n_upper, hipStream_t s, const PosePrior* prior) {
   const bool prof = ep.ablate != 0 || mp.ablate != 0;
-  if (slot == 0) {  // plane fit + first evaluation, dense over the queries
-    const uint32_t blocks = solve_grid(n_upper, 0);
+  const uint32_t blocks = slot == 0 ? solve_grid(n_upper, 0) : (uint32_t)kEvalBlocks;  // slot 0: plane fit + first evaluation, dense over the queries
+  if (prior) {  // (the prior travels as the launch's last argument)
+    auto* k = slot == 0 ? (prof ? eval_kernel_prior<true, true> : eval_kernel_prior<true, false>) : (prof ? eval_kernel_prior<false, true> : eval_kernel_prior<false, false>);
+    hipLaunchKernelGGL(k, dim3(blocks), dim3(256), 0, s, slot, fuse_lm ? 1 : 0, spx, spy, spz, corr, st, ep, partials, ticket, hist, sums, map.pts, nbr5, mp, *prior);
+  } else if (slot == 0) {
     auto* k = prof ? eval_kernel<true, true> : eval_kernel<true, false>;
     hipLaunchKernelGGL(k, dim3(blocks), dim3(256), 0, s, slot, fuse_lm ? 1 : 0, spx, spy, spz, corr, st, ep, partials, ticket, hist, sums, map.pts, nbr5, mp);
   } else {
@@ -2938,12 +2953,17 @@ void launch_eval(int slot, bool fuse_lm, const float* spx, const float* spy, con
 }
 void launch_solve(int lm_max, const float* spx, const float* spy, const float* spz, const CorrBuffers& corr, DevState* st,
                   const EvalParams& ep, double* partials, uint32_t* ticket, int32_t* hist, LmSums* sums, const DevMapView& map,
-                  const uint32_t* nbr5, const MatchParams& mp, uint32_t n_upper, uint32_t max_blocks, hipStream_t s) {
+                  const uint32_t* nbr5, const MatchParams& mp, uint32_t n_upper, uint32_t max_blocks, hipStream_t s, const PosePrior* prior) {
   // every workgroup must be resident for the whole launch (94 KB of LDS: one per compute unit)
   const uint32_t blocks = solve_grid(n_upper, max_blocks);
   const bool prof = ep.ablate != 0 || mp.ablate != 0;
   auto* k = ep.peer_world > 1 ? (prof ? solve_kernel<true, false, true> : solve_kernel<false, false, true>)
                               : (prof ? solve_kernel<true, false, false> : solve_kernel<false, false, false>);
+  if (prior && ep.peer_world <= 1) {  // (the prior travels as the launch's last argument)
+    auto* kp = prof ? solve_kernel_prior<true> : solve_kernel_prior<false>;
+    hipLaunchKernelGGL(kp, dim3(blocks), dim3(256), 0, s, lm_max, spx, spy, spz, corr, st, ep, partials, ticket, hist, sums, map.pts, nbr5, mp, kNoBatch, *prior);
+    return;
+  }
   hipLaunchKernelGGL(k, dim3(blocks), dim3(256), 0, s, lm_max, spx, spy, spz, corr, st, ep, partials, ticket, hist, sums, map.pts, nbr5, mp, kNoBatch);
 }
 uint32_t solve_batch_resident_blocks(uint32_t n_cus, int wg_per_cu) {

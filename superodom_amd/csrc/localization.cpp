@@ -126,7 +126,9 @@ extern "C" {
 
 int so_icp_localization(so_icp_ctx* c, int initialization, const double T_in[7], const float* xyz, size_t n, size_t stride_bytes,
                         double time_laser_odometry, double pose_out[7], so_icp_stats* st) {
-  if (!c || !T_in || !pose_out || (!xyz && n)) return SO_ICP_E_INVALID;
+  if (!c) return SO_ICP_E_INVALID;
+  const PriorOneShot consume{c};  // (a frame that seeds the map consumes it too)
+  if (!T_in || !pose_out || (!xyz && n)) return SO_ICP_E_INVALID;
   if (const int rc = normalise_stride(c, &stride_bytes)) return rc;
   if (!c->host_only) HIP_TRY(c, hipSetDevice(c->cfg.device_id));  // (the caller may sit on another device / thread)
   return localization_frame(c, initialization, T_in, FrameScan{true, xyz, n, stride_bytes}, time_laser_odometry, pose_out, st);
@@ -134,7 +136,9 @@ int so_icp_localization(so_icp_ctx* c, int initialization, const double T_in[7],
 
 int so_icp_localization_dev(so_icp_ctx* c, int initialization, const double T_in[7], const void* d_scan, size_t n,
                             double time_laser_odometry, double pose_out[7], so_icp_stats* st) {
-  if (!c || !T_in || !pose_out || (!d_scan && n)) return SO_ICP_E_INVALID;
+  if (!c) return SO_ICP_E_INVALID;
+  const PriorOneShot consume{c};
+  if (!T_in || !pose_out || (!d_scan && n)) return SO_ICP_E_INVALID;
   NEED_DEVICE(c);
   HIP_TRY(c, hipSetDevice(c->cfg.device_id));
   if (!c->dmap) {  // host-side LocalMap (sharded ranks): the insert needs the points on the host

@@ -30,6 +30,7 @@ int so_icp_localization_sequence(so_icp_ctx* c, int count, const void* const* sc
     if (!scans[k] && n_points[k]) return fail(c, SO_ICP_E_INVALID, "so_icp_localization_sequence: scans[" + std::to_string(k) + "] is NULL");
   if (count == 0) return SO_ICP_OK;
   NEED_DEVICE(c);
+  if (const int rc = refuse_pending_prior(c, "so_icp_localization_sequence")) return rc;
 
   double guess[7];
   std::memcpy(guess, pose0, sizeof(guess));

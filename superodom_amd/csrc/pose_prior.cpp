@@ -1,0 +1,50 @@
+// pose_prior.cpp -- the absolute pose prior of the reference's Ceres problem (addAbsolutePoseConstraints, LidarSlam.cpp:285-297) inside the
+// device solve: so_icp_pose_prior_from_information and so_icp_pose_prior_sums are host arithmetic (pose_prior.h, the header the kernels
+// compile too); so_icp_set_pose_prior keeps the prior for the launches of the next registration, whose last argument it becomes.
+#include <cmath>
+#include <cstring>
+
+#include "ctx.h"
+#include "pose_prior.h"
+
+static_assert(sizeof(so_icp_pose_prior) == sizeof(PosePrior) && sizeof(so_icp_pose_prior) == kPosePriorWords * 8, "so_icp_pose_prior is pose_prior.h's PosePrior");
+static_assert(offsetof(so_icp_pose_prior, sqrt_information) == kPriorU * 8 && offsetof(so_icp_pose_prior, count_floor) == kPriorFloor * 8 &&
+              offsetof(so_icp_pose_prior, count_fraction) == kPriorFraction * 8, "so_icp_pose_prior's words are where pose_prior.h reads them");
+static_assert(sizeof(so_icp_sums) == sizeof(LmSums), "so_icp_sums is LmSums");
+
+extern "C" {
+
+int so_icp_pose_prior_from_information(const double information[36], const double T_meas[7], so_icp_pose_prior* out) {
+  if (!information || !T_meas || !out) return SO_ICP_E_INVALID;
+  double U[36];
+  if (!pose_prior_llt(information, U)) return SO_ICP_E_INVALID;
+  std::memset(out, 0, sizeof(*out));
+  std::memcpy(out->T_meas, T_meas, sizeof(out->T_meas));
+  std::memcpy(out->sqrt_information, U, sizeof(U));
+  return SO_ICP_OK;
+}
+
+int so_icp_pose_prior_sums(const so_icp_pose_prior* prior, const double pose[7], so_icp_sums* inout) {
+  if (!prior || !pose || !inout) return SO_ICP_E_INVALID;
+  pose_prior_add(reinterpret_cast<const double*>(prior), pose, *reinterpret_cast<LmSums*>(inout));
+  return SO_ICP_OK;
+}
+
+int so_icp_set_pose_prior(so_icp_ctx* c, const so_icp_pose_prior* prior) {
+  if (!c) return SO_ICP_E_INVALID;
+  NEED_DEVICE(c);
+  if (c->cfg.world_size > 1)
+    return fail(c, SO_ICP_E_UNSUPPORTED, "so_icp_set_pose_prior: a sharded context (world_size > 1) sums every evaluation over the ranks; the prior belongs to one device");
+  if (!prior) { c->prior_pending = false; return SO_ICP_OK; }
+  const double* w = reinterpret_cast<const double*>(prior);
+  for (int i = 0; i < kPosePriorWords; ++i)
+    if (!std::isfinite(w[i])) return fail(c, SO_ICP_E_INVALID, "so_icp_set_pose_prior: a field of the prior is not finite");
+  const double* q = prior->T_meas + 3;
+  if (!(q[0] * q[0] + q[1] * q[1] + q[2] * q[2] + q[3] * q[3] > 0.0)) return fail(c, SO_ICP_E_INVALID, "so_icp_set_pose_prior: T_meas holds a quaternion of zero norm");
+  // host memory only: the prior is the last argument of the solve / evaluation launches of the registration that carries it
+  std::memcpy(&c->prior, prior, sizeof(c->prior));
+  c->prior_pending = true;
+  return SO_ICP_OK;
+}
+
+}  // extern "C"

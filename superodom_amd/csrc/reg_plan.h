@@ -16,6 +16,10 @@ constexpr int kOuterCap = 16, kLmCap = 16;
 inline int outer_limit(int max_iterations) { return std::min(max_iterations > 0 ? max_iterations : 4, kOuterCap); }
 inline int lm_limit(int lm_max_iterations) { return std::min(lm_max_iterations > 0 ? lm_max_iterations : 4, kLmCap); }
 
+// so_icp_set_pose_prior: the pending prior goes into a registration that is the context's own (no batch lane, no borrowed map), on one
+// device, and a registration (so_icp_match leaves it pending)
+inline bool carries_pose_prior(bool pending, bool own, int world_size, bool match_only) { return pending && own && world_size <= 1 && !match_only; }
+
 // scans of this many points or more are refused (refuse_scan_size, icp_context.cpp): the work-list counters hold 21 bits each
 constexpr size_t kMaxScanPoints = (size_t)1 << 21;
 

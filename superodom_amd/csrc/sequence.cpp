@@ -389,6 +389,7 @@ int so_icp_register_sequence(so_icp_ctx* c, int count, const void* const* scans,
   if (n_done) *n_done = 0;
   if (!c || count < 0 || (count && (!scans || !n_points || !pose0 || !poses_out)) || (count > 1 && !deltas)) return SO_ICP_E_INVALID;
   NEED_DEVICE(c);
+  if (const int rc = refuse_pending_prior(c, "so_icp_register_sequence")) return rc;
   HIP_TRY(c, hipSetDevice(c->cfg.device_id));
   if (stride_bytes == 0) stride_bytes = 12;
   for (int k = 0; k < count; ++k) if (!scans[k] && n_points[k]) return SO_ICP_E_INVALID;
