@@ -11,6 +11,8 @@
 // --sequence: a replay (LidarSLAM::LocalizationSequence): frame 0 seeds the map, frames 1.. run as ONE sequence from guess 1 with the
 //          motion predictions guess_(k-1)^-1 * guess_k; prints one line per frame (index and pose, %.17g) and writes
 //          out.bin: int32 status, int32 n_done, float64 T_w_lidar[n_done][7]
+//          --sequence --prior-at-guess: every frame of the run carries an absolute pose prior measured at its own guess
+//          (LidarSLAM::SetSequencePriors, SO_ICP_PRIOR_AT_GUESS): the U of --vio-prior with the uncertainty terms at 0
 // --correspondences: the frames as without a flag, with LidarSLAM::keep_correspondences on; behind the output above, the last frame's
 //          correspondence set (LidarSLAM::LastCorrespondences at the optimised pose): the so_icp_correspondence_info as it is, then
 //          n_accepted so_icp_correspondence records as they are
@@ -142,6 +144,15 @@ int main(int argc, char** argv) {
       std::vector<double> run_times(times.begin() + 1, times.end());
       std::vector<Transformd> predictions(run.size());
       for (size_t k = 1; k < run.size(); ++k) predictions[k] = between(guesses[k], guesses[k + 1]);
+      if (argc > 4 && std::strcmp(argv[4], "--prior-at-guess") == 0) {
+        so_icp_pose_prior prior;
+        std::memset(&prior, 0, sizeof(prior));
+        prior.T_meas[6] = 1.0;  // (not read: the measurement is the frame's guess)
+        const double V = 0.9, diag[6] = {std::sqrt(V), std::sqrt(V), std::sqrt(V), std::sqrt(V), std::sqrt(V), 0.0};
+        const double floor_[6] = {50, 50, 50, 10, 10, 5}, fraction[6] = {0.1, 0.1, 0.1, 0.01, 0.01, 0.001};
+        for (int i = 0; i < 6; ++i) { prior.sqrt_information[7 * i] = diag[i]; prior.count_floor[i] = floor_[i]; prior.count_fraction[i] = fraction[i]; }
+        slam.SetSequencePriors(std::vector<so_icp_pose_prior>(run.size(), prior), std::vector<uint8_t>(run.size(), (uint8_t)SO_ICP_PRIOR_AT_GUESS));
+      }
       std::vector<Transformd> poses;
       const int n_done = slam.LocalizationSequence(guesses[1], run, predictions, run_times, &poses);
       wr<int32_t>(out, slam.last_status); wr<int32_t>(out, n_done);

@@ -169,6 +169,13 @@ void LidarSLAM::SetPosePrior(const Transformd& T, const double information[36]) 
   if (so_icp_set_pose_prior(gpu_, &prior) < 0) throw std::runtime_error(std::string("so_icp_set_pose_prior: ") + so_icp_last_error(gpu_));
 }
 
+void LidarSLAM::SetSequencePriors(const std::vector<so_icp_pose_prior>& priors, const std::vector<uint8_t>& modes) {
+  ensure_context();
+  if (!modes.empty() && modes.size() != priors.size()) throw std::invalid_argument("SetSequencePriors: one mode per prior");
+  if (so_icp_set_sequence_priors(gpu_, (int)priors.size(), priors.empty() ? nullptr : priors.data(), modes.empty() ? nullptr : modes.data()) < 0)
+    throw std::runtime_error(std::string("so_icp_set_sequence_priors: ") + so_icp_last_error(gpu_));
+}
+
 // shouldAddAbsolutePoseConstraints + addAbsolutePoseConstraints, LidarSlam.cpp:281-297: information = diag((1 - uncertainty_xyz) *
 // max(50, int(n * 0.1)) * V, max(10, int(n * 0.01)) * V twice, max(5, int(n * 0.001)) * 0) on `position`, n the feature count of every
 // evaluation -- stated exactly by U = its square root without the counts, and the counts as the rows' floor and fraction.  The

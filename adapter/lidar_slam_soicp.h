@@ -123,6 +123,9 @@ class LidarSLAM {
   // addAbsolutePoseConstraints (LidarSlam.cpp:281-297): with predictodom == VIO_ODOM, isDegenerate and Visual_confidence_factor != 0 it
   // sets the reference's prior on `position` -- and replaces one set here.
   void SetPosePrior(const Transformd& T_w_i_meas, const double information[36]);
+  // One prior per frame of the NEXT LocalizationSequence(), which consumes them (so_icp_set_sequence_priors, passed through):
+  // modes[k] = SO_ICP_PRIOR_NONE / _GIVEN / _AT_GUESS (empty: all given); AT_GUESS measures at the frame's own guess.  Empty priors withdraw.
+  void SetSequencePriors(const std::vector<so_icp_pose_prior>& priors, const std::vector<uint8_t>& modes = {});
 
   // ---- public fields laserMapping.cpp reads / writes (same names) ----
   Transformd T_w_lidar, last_T_w_lidar;

@@ -800,6 +800,32 @@ int so_icp_pose_prior_sums(const so_icp_pose_prior *prior, const double pose[7],
  * which no prior was ever set does nothing more than before in any entry. */
 int so_icp_set_pose_prior(so_icp_ctx *ctx, const so_icp_pose_prior *prior /* NULL withdraws */);
 
+/* One prior PER FRAME of a run: ONE-SHOT, for the next so_icp_register_sequence or so_icp_localization_sequence call, which stays
+ * chained.  modes[k] says where frame k's measurement comes from:
+ *   NONE      frame k carries no prior: bit for bit and flag for flag the frame of a run without priors
+ *   GIVEN     priors[k] as it stands
+ *   AT_GUESS  priors[k] with T_meas replaced by the frame's own guess (guesses_out[k]); priors[k].T_meas is not read.  The reference
+ *             puts its prior on `position`, the frame's initial guess (LS.cpp:131, 224-226, 295); in a chained run the host never sees
+ *             the guess of frame k >= 1 before it enqueues that frame -- the solve that ends frame k - 1 forms it on the device --, so
+ *             "hold the unobservable axes at the prediction" is stated here and the measurement taken where the guess is formed.
+ * With P_k = priors[k] (AT_GUESS: T_meas := guesses_out[k]), frame k of so_icp_register_sequence is bit for bit
+ * so_icp_set_pose_prior(ctx, P_k) + so_icp_register from guesses_out[k], and frame k of so_icp_localization_sequence that call +
+ * so_icp_localization(initialization = 1), the map after every frame included -- chained or not, and across a broken chain.  A frame
+ * with a prior reports like the single entry: costs, JtJ and Jtr include it, prediction_source = 1, SO_ICP_FLAG_POSE_PRIOR.
+ * Both arrays are copied.  The next sequence call consumes the priors when it returns, whatever it returns; a call whose `count`
+ * differs returns SO_ICP_E_INVALID before it touches anything and leaves them pending.  count == 0 or priors == NULL withdraws.
+ * While the priors of a run are pending so_icp_register(_dev), so_icp_localization(_dev), so_icp_register_batch, so_icp_match(_dev)
+ * and so_icp_set_pose_prior return SO_ICP_E_UNSUPPORTED and leave them pending; a pending single prior is refused by both sequence
+ * entries as before, and by this call.  Validation as so_icp_set_pose_prior's, on the words a mode reads: a non-finite field or (GIVEN)
+ * a T_meas quaternion of zero norm SO_ICP_E_INVALID, a mode above 2 SO_ICP_E_INVALID, world_size > 1 SO_ICP_E_UNSUPPORTED, a host-only
+ * context SO_ICP_E_HIP.  Not in a run: the reference's uncertainty-scaled information (frame k's U would need frame k - 1's
+ * uncertainty, which the host does not have when it enqueues a chained frame). */
+#define SO_ICP_PRIOR_NONE     0
+#define SO_ICP_PRIOR_GIVEN    1
+#define SO_ICP_PRIOR_AT_GUESS 2
+int so_icp_set_sequence_priors(so_icp_ctx *ctx, int count, const so_icp_pose_prior *priors /* count */,
+                               const uint8_t *modes /* count; NULL = all GIVEN */);
+
 /* -------- measurement ------------------------------------------------------------------------ */
 int so_icp_get_timing(so_icp_ctx *ctx, so_icp_timing *t);
 int so_icp_reset_timing(so_icp_ctx *ctx);

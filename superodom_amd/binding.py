@@ -49,6 +49,7 @@ FLAG_BINNED_AHEAD = 256
 FLAG_QUERY_WAVES = 512
 FLAG_CHAINED = 1024
 FLAG_POSE_PRIOR = 2048
+PRIOR_NONE, PRIOR_GIVEN, PRIOR_AT_GUESS = 0, 1, 2  # SO_ICP_PRIOR_*: the modes of so_icp_set_sequence_priors
 
 
 class RegistrationError(C.Structure):
@@ -265,7 +266,7 @@ EXPORTED = ["so_icp_default_config", "so_icp_create", "so_icp_destroy", "so_icp_
             "so_icp_debug_lm_script", "so_icp_set_cloud_intensity", "so_icp_prefilter_intensity",
             "so_icp_keep_correspondences", "so_icp_correspondences",
             "so_icp_match", "so_icp_match_dev", "so_icp_correspondence_sums",
-            "so_icp_pose_prior_from_information", "so_icp_pose_prior_sums", "so_icp_set_pose_prior"]
+            "so_icp_pose_prior_from_information", "so_icp_pose_prior_sums", "so_icp_set_pose_prior", "so_icp_set_sequence_priors"]
 SUMS_MAX_POSES = 64
 
 _lib = None
@@ -375,6 +376,7 @@ def load():
     L.so_icp_pose_prior_from_information.argtypes = [f64p, f64p, C.POINTER(PosePrior)]
     L.so_icp_pose_prior_sums.argtypes = [C.POINTER(PosePrior), f64p, C.POINTER(Sums)]
     L.so_icp_set_pose_prior.argtypes = [vp, C.POINTER(PosePrior)]
+    L.so_icp_set_sequence_priors.argtypes = [vp, C.c_int, C.POINTER(PosePrior), C.POINTER(C.c_uint8)]
     _lib = L
     return L
 
@@ -630,6 +632,18 @@ class LidarSlamGpu:
         """so_icp_set_pose_prior: `prior` (a PosePrior) goes into the next register / register_dev / localization(_dev) call and is consumed
         by it; None withdraws a pending one"""
         self._check(self.L.so_icp_set_pose_prior(self.h, C.byref(prior) if prior is not None else None))
+
+    def set_sequence_priors(self, priors, modes=None):
+        """so_icp_set_sequence_priors: one PosePrior per frame of the next register_sequence / localization_sequence call, which consumes
+        them; modes[k] in PRIOR_NONE / PRIOR_GIVEN / PRIOR_AT_GUESS (None: all given).  priors None or empty withdraws pending ones"""
+        if priors is None or len(priors) == 0:
+            self._check(self.L.so_icp_set_sequence_priors(self.h, 0, None, None)); return
+        arr = (PosePrior * len(priors))(*priors)
+        m = None
+        if modes is not None:
+            assert len(modes) == len(priors)
+            m = (C.c_uint8 * len(priors))(*[int(v) for v in modes])
+        self._check(self.L.so_icp_set_sequence_priors(self.h, len(priors), arr, m))
 
     def correspondence_sums(self, poses):
         """so_icp_correspondence_sums: the kept set's cost and normal equations at `poses` ([7] or [k, 7], k <= SUMS_MAX_POSES) -> an

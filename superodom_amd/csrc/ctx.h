@@ -10,7 +10,7 @@
 //   cloud_steps.cpp       so_icp_deskew_scan(_dev), so_icp_transform_cloud, so_icp_download_scan
 //   correspondences.cpp   so_icp_keep_correspondences, so_icp_correspondences: the last registration's correspondence set;
 //                         so_icp_match(_dev), so_icp_correspondence_sums: the set formed at a pose of the caller's, its sums on the device
-//   pose_prior.cpp        so_icp_pose_prior_from_information, so_icp_pose_prior_sums, so_icp_set_pose_prior
+//   pose_prior.cpp        so_icp_pose_prior_from_information, so_icp_pose_prior_sums, so_icp_set_pose_prior, so_icp_set_sequence_priors
 //   multi_gpu.cpp         RCCL, in-process groups, peer exchange, shard helpers
 //   localization_sequence.cpp, feature_extraction.cpp
 #pragma once
@@ -21,6 +21,7 @@
 #include <chrono>
 #include <condition_variable>
 #include <cstdint>
+#include <cstring>
 #include <memory>
 #include <mutex>
 #include <string>
@@ -181,6 +182,13 @@ struct so_icp_ctx {
   // registration's solve / evaluation launches
   bool prior_pending = false;
   PosePrior prior{};
+  // so_icp_set_sequence_priors: one prior and one mode (SO_ICP_PRIOR_*) per frame of the NEXT so_icp_register_sequence /
+  // so_icp_localization_sequence call (one-shot: that call takes them out of the context when it starts, RunPriors::take)
+  struct RunPriors {
+    bool pending = false;
+    std::vector<PosePrior> priors;
+    std::vector<uint8_t> modes;
+  } run_priors;
   hipStream_t pf_stream = nullptr;    // the pre-filter's own queue: the next frame's upload + VoxelGrid run BESIDE the map insert the previous
   // Seam B scratch
   DevBuf d_q, d_nbr, d_d2, d_idx, d_found, d_fblist;
@@ -339,10 +347,42 @@ inline int fail(so_icp_ctx* c, int code, const std::string& msg) { c->err = msg;
 // so_icp_set_pose_prior: so_icp_register(_dev) and so_icp_localization(_dev) consume the pending prior when they return, whatever they
 // return; the entries that cannot carry one refuse the call and leave it pending
 struct PriorOneShot { so_icp_ctx* c; ~PriorOneShot() { c->prior_pending = false; } };
-inline int refuse_pending_prior(so_icp_ctx* c, const char* entry) {
-  return c->prior_pending ? fail(c, SO_ICP_E_UNSUPPORTED, std::string(entry) + ": a pose prior is pending (so_icp_set_pose_prior); it goes into so_icp_register(_dev) "
-                                                          "or so_icp_localization(_dev) -- withdraw it with so_icp_set_pose_prior(ctx, NULL) first") : SO_ICP_OK;
+// so_icp_set_sequence_priors: the priors of a run go into the next so_icp_register_sequence / so_icp_localization_sequence call
+// (`sequence_entry`); every other entry that could meet them refuses and leaves them pending
+inline int refuse_pending_run_priors(so_icp_ctx* c, const char* entry) {
+  return c->run_priors.pending ? fail(c, SO_ICP_E_UNSUPPORTED, std::string(entry) + ": the priors of a run are pending (so_icp_set_sequence_priors); they go into "
+                                                               "so_icp_register_sequence or so_icp_localization_sequence -- withdraw them with "
+                                                               "so_icp_set_sequence_priors(ctx, 0, NULL, NULL) first") : SO_ICP_OK;
 }
+inline int refuse_pending_prior(so_icp_ctx* c, const char* entry, bool sequence_entry = false) {
+  if (c->prior_pending)
+    return fail(c, SO_ICP_E_UNSUPPORTED, std::string(entry) + ": a pose prior is pending (so_icp_set_pose_prior); it goes into so_icp_register(_dev) "
+                                         "or so_icp_localization(_dev) -- withdraw it with so_icp_set_pose_prior(ctx, NULL) first");
+  return sequence_entry ? SO_ICP_OK : refuse_pending_run_priors(c, entry);
+}
+// The priors of one sequence call, taken out of the context when the call starts (so the per-frame entries it runs do not meet them,
+// and they are consumed whatever the call returns).  A call of another length leaves them where they are (count_matches).
+struct RunPriors {
+  std::vector<PosePrior> priors;
+  std::vector<uint8_t> modes;
+  static bool count_matches(const so_icp_ctx* c, int count) { return !c->run_priors.pending || (size_t)count == c->run_priors.priors.size(); }
+  void take(so_icp_ctx* c) {
+    if (!c->run_priors.pending) return;
+    priors.swap(c->run_priors.priors); modes.swap(c->run_priors.modes);
+    c->run_priors = so_icp_ctx::RunPriors{};
+  }
+  int mode(int k) const { return (size_t)k < modes.size() ? modes[(size_t)k] : SO_ICP_PRIOR_NONE; }
+  // P_k: priors[k], with T_meas = the frame's guess where the mode says so; false: frame k carries no prior
+  bool frame_prior(int k, const double guess[7], PosePrior& out) const {
+    if (mode(k) == SO_ICP_PRIOR_NONE) return false;
+    out = priors[(size_t)k];
+    if (mode(k) == SO_ICP_PRIOR_AT_GUESS) std::memcpy(out.T_meas, guess, sizeof(out.T_meas));
+    return true;
+  }
+  // frame k through a per-frame entry (so_icp_register(_dev), so_icp_localization(_dev)): P_k becomes the context's single prior,
+  // which that entry consumes -- what so_icp_set_pose_prior does, without its refusals
+  void arm(so_icp_ctx* c, int k, const double guess[7]) const { c->prior_pending = frame_prior(k, guess, c->prior); }
+};
 // what a DeviceMap member returns (device_map.h: -1 out of memory / a full cube, -2 a HIP error, its text in c->err; else >= 0) as a C ABI code
 inline int map_status(int r) { return r >= 0 ? SO_ICP_OK : (r == -1 ? SO_ICP_E_NOMEM : SO_ICP_E_HIP); }
 // the stride rule of the entries that read float x y z records: 0 means packed (12 bytes); a multiple of 4
@@ -395,7 +435,9 @@ struct RegWork {
 void launch_sweep(so_icp_ctx* c, const RegWork& w, MatchParams& mp_it, bool first, const so_icp_ctx::StageSlot* begin_slot, const double pose[7],
                   uint32_t chain_expect, hipEvent_t ev_start, hipEvent_t ev_stop);
 // The whole solve of one outer iteration in one launch; gives `ep_it` (the caller's copy: defer_publish, chain_*) its epoch
-void launch_persistent_solve(so_icp_ctx* c, const RegWork& w, EvalParams& ep_it, const MatchParams& mp, const PosePrior* prior = nullptr);
+// (`prior`: the registration's pose prior; `prior_at_guess`: its T_meas is the guess on the device, launch_solve)
+void launch_persistent_solve(so_icp_ctx* c, const RegWork& w, EvalParams& ep_it, const MatchParams& mp, const PosePrior* prior = nullptr,
+                             bool prior_at_guess = false);
 // The host's wait for the report `want` in a pinned mirror's seq word; `s`: the queue whose draining ends the wait without one.  The
 // mirrors are polled; the watchdog of that wait is the clock and, once it has run out, the queue (so_icp_ctx::speculate has the
 // measured reason why nothing -- no event, no stream query -- accompanies the wait in the normal case).

@@ -180,11 +180,11 @@ void launch_sweep(so_icp_ctx* c, const RegWork& w, MatchParams& mp_it, bool firs
 }
 // setupOptimizationProblem + solveOptimizationProblem (LidarSlam.cpp:213-240) of one outer iteration: the whole solve in one launch
 // (workgroups hand the next pose to each other on the device).  (The span is one of profiling mode, time_kernels 2.)
-void launch_persistent_solve(so_icp_ctx* c, const RegWork& w, EvalParams& ep_it, const MatchParams& mp, const PosePrior* prior) {
+void launch_persistent_solve(so_icp_ctx* c, const RegWork& w, EvalParams& ep_it, const MatchParams& mp, const PosePrior* prior, bool prior_at_guess) {
   ep_it.epoch_base = (++c->solve_launches) << 5;
   span_begin(c, 1, (uint32_t)w.n);
   launch_solve(w.lm_max, w.d_scan, w.d_scan + 1, w.d_scan + 2, w.corr, c->d_state, ep_it, c->d_partials, c->d_ticket, c->d_hist, c->d_sums, c->view,
-               c->d_nbr5.as<uint32_t>(), mp, (uint32_t)w.n, (uint32_t)c->n_cus, c->stream, prior);
+               c->d_nbr5.as<uint32_t>(), mp, (uint32_t)w.n, (uint32_t)c->n_cus, c->stream, prior, prior_at_guess);
   span_end(c);
 }
 Report await_report(so_icp_ctx* c, const volatile unsigned long long* seq, unsigned long long want, hipStream_t s) {
@@ -1036,6 +1036,7 @@ int so_icp_free_scan(so_icp_ctx* c, void* d_scan) {
 
 int so_icp_register_dev(so_icp_ctx* c, const void* d_scan, size_t n, const double pose_in[7], double pose_out[7], so_icp_stats* st) {
   if (!c) return SO_ICP_E_INVALID;
+  if (const int rc = refuse_pending_run_priors(c, "so_icp_register_dev")) return rc;
   const PriorOneShot consume{c};
   if (!pose_in || !pose_out || (!d_scan && n)) return SO_ICP_E_INVALID;
   NEED_DEVICE(c);
@@ -1046,6 +1047,7 @@ int so_icp_register_dev(so_icp_ctx* c, const void* d_scan, size_t n, const doubl
 
 int so_icp_register(so_icp_ctx* c, const float* xyz, size_t n, size_t stride_bytes, const double pose_in[7], double pose_out[7], so_icp_stats* st) {
   if (!c) return SO_ICP_E_INVALID;
+  if (const int rc = refuse_pending_run_priors(c, "so_icp_register")) return rc;
   const PriorOneShot consume{c};
   if (!pose_in || !pose_out || (!xyz && n)) return SO_ICP_E_INVALID;
   NEED_DEVICE(c);

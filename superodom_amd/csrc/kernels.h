@@ -237,7 +237,9 @@ void launch_eval(int slot, bool fuse_lm, const float* spx, const float* spy, con
 void launch_solve(int lm_max, const float* spx, const float* spy, const float* spz, const CorrBuffers& corr, DevState* st,
                   const EvalParams& ep, double* d_partials, uint32_t* d_ticket, int32_t* d_hist, LmSums* d_sums,
                   const DevMapView& map, const uint32_t* d_nbr5, const MatchParams& mp, uint32_t n_upper, uint32_t max_blocks, hipStream_t s,
-                  const PosePrior* prior = nullptr /* as launch_eval's (solve_kernel_prior); single device only */);
+                  const PosePrior* prior = nullptr /* as launch_eval's (solve_kernel_prior); single device only */,
+                  bool prior_at_guess = false /* solve_kernel_prior_at_guess: T_meas is DevState::pose_in, the guess the registration's BEGIN
+                                                 launch stored (a chained registration of a sequence: so_icp_set_sequence_priors) */);
 // workgroups of the single-registration solve launch for a scan of n_upper queries (the grid a batch stands in for)
 uint32_t solve_grid(uint32_t n_upper, uint32_t max_blocks);
 // workgroups of the batched solve launch that are certainly resident together on n_cus compute units (occupancy query of the

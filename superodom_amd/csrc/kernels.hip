@@ -1999,6 +1999,12 @@ __device__ __forceinline__ void prior_prepare(const double* P, const Pose& pose,
   pose_to_array(pose, p7);
   pose_prior_prepare(P, p7, word, part);
 }
+// the same with the measurement apart from the other words (solve_kernel_prior_at_guess: Tm = the frame's guess, in registers)
+__device__ __forceinline__ void prior_prepare_at(const double* Tm, const double* P, const Pose& pose, int word, PosePriorPart& part) {
+  double p7[7];
+  pose_to_array(pose, p7);
+  pose_prior_prepare_at(Tm, P, p7, word, part);
+}
 // total of thread `word` with the prior added (plane sum on the left); every thread word < kNAcc calls it together
 __device__ __forceinline__ double prior_added(const PosePriorPart& part, double tot, int word) {
   const double count = __hiloint2double(__builtin_amdgcn_readlane(__double2hiint(tot), 1), __builtin_amdgcn_readlane(__double2loint(tot), 1));
@@ -2167,8 +2173,10 @@ struct WgSpan { uint32_t vb0, vb1, V; bool ctl; };
 // PEER  : the instantiation with the peer exchange compiled in (sharded registration, N > 1); the single-device launches carry
 //         none of its index arithmetic and arguments
 // PRIOR : the registration carries a pose prior (single device, not BATCH): the controller's workgroup adds it -- the 55 doubles at
-//         `prior` -- to the pass's sums
-template <bool FIT, bool PERSIST = false, bool PROF = false, bool BATCH = false, bool PEER = false, bool PRIOR = false>
+//         `prior` -- to the pass's sums.  kPriorAtGuess (2, PERSIST only): T_meas is not the prior's own but the seven words at
+//         `prior_tm` (the frame's guess, see solve_kernel_prior_at_guess)
+constexpr int kPriorAtGuess = 2;
+template <bool FIT, bool PERSIST = false, bool PROF = false, bool BATCH = false, bool PEER = false, int PRIOR = 0>
 __device__ __forceinline__ int eval_pass(int slot, int fuse_lm, const Pose& pose, const float* __restrict__ spx,
                                          const float* __restrict__ spy, const float* __restrict__ spz,
                                          const CorrBuffers& corr, DevState* __restrict__ st, const EvalParams& ep,
@@ -2177,7 +2185,7 @@ __device__ __forceinline__ int eval_pass(int slot, int fuse_lm, const Pose& pose
                                          const float4* __restrict__ mpts, const uint32_t* __restrict__ nbr5,
                                          const MatchParams& mp, EvalShared& sh, const double* prior, unsigned long long pass_tag = 0,
                                          CorrCache* cc = nullptr, u4v* hand = nullptr, unsigned long long want = 0,
-                                         const WgSpan span = WgSpan{0, 0, 0, false}) {
+                                         const WgSpan span = WgSpan{0, 0, 0, false}, const double* prior_tm = nullptr) {
   // PERSIST (solve_kernel): workgroup 0 is the finisher of every pass of the launch, so the controller state stays in
   // its LDS from pass to pass and goes to memory only when the solve ends; the workgroup records are PUSHED (tagged
   // 16-byte chunks, see below) instead of stored + counted
@@ -2191,6 +2199,7 @@ __device__ __forceinline__ int eval_pass(int slot, int fuse_lm, const Pose& pose
   const int tid = threadIdx.x;
   static_assert(!BATCH || PERSIST, "batched hypotheses run in the persistent solve launch");
   static_assert(!PRIOR || (!BATCH && !PEER), "the pose prior belongs to the single registration on one device");
+  static_assert(PRIOR != kPriorAtGuess || PERSIST, "the prior at the guess belongs to the persistent solve");
   const int abl = PROF ? ep.ablate : 0;
   const bool stamp = PROF && (abl & 128) != 0;
   const uint32_t V = BATCH ? span.V : gridDim.x;                    // workgroups of the (virtual) grid
@@ -2429,8 +2438,12 @@ __device__ __forceinline__ int eval_pass(int slot, int fuse_lm, const Pose& pose
     const int g = poller ? tid / kNAcc : 0, a = poller ? tid - g * kNAcc : 0;
     const u4v* base = rec + (poller ? tid : 0);
     [[maybe_unused]] PosePriorPart prior_part;
-    if constexpr (PRIOR && SO_PRIOR_OVERLAP != 0) {  // the pass's pose is known: everything of the prior but the row scale, beside the records' way here
-      if (tid < kNAcc) prior_prepare(prior, pose, tid, prior_part);
+    if constexpr (PRIOR != 0 && SO_PRIOR_OVERLAP != 0) {  // the pass's pose is known: everything of the prior but the row scale, beside the records' way here
+      if constexpr (PRIOR == kPriorAtGuess) {
+        if (tid < kNAcc) prior_prepare_at(prior_tm, prior, pose, tid, prior_part);
+      } else {
+        if (tid < kNAcc) prior_prepare(prior, pose, tid, prior_part);
+      }
     }
     if (!BATCH) {
     u4v r[32];
@@ -2514,8 +2527,11 @@ __device__ __forceinline__ int eval_pass(int slot, int fuse_lm, const Pose& pose
       double tot = 0;
 #pragma unroll
       for (int cc8 = 0; cc8 < 8; ++cc8) tot += part[cc8][tid];
-      if constexpr (PRIOR) {
-        if (SO_PRIOR_OVERLAP == 0) prior_prepare(prior, pose, tid, prior_part);
+      if constexpr (PRIOR != 0) {
+        if (SO_PRIOR_OVERLAP == 0) {
+          if constexpr (PRIOR == kPriorAtGuess) prior_prepare_at(prior_tm, prior, pose, tid, prior_part);
+          else prior_prepare(prior, pose, tid, prior_part);
+        }
         tot = prior_added(prior_part, tot, tid);
       }
       o[tid] = tot;  // cost, count, Jtr[6], JtJ[21]
@@ -2598,7 +2614,7 @@ __device__ __forceinline__ int eval_pass(int slot, int fuse_lm, const Pose& pose
     if (stamp && tid == 0 && (FIT || slot == 1)) store_stamps<FIT>(st, T, !FIT || BATCH);
     return sh_more ? kPassMore : kPassDone;
   }
-  return hand_over_ticketed<FIT, PROF, PRIOR>(slot, fuse_lm, mine, st, ep, partials, ticket, hist, out, sh, T, pose, prior);
+  return hand_over_ticketed<FIT, PROF, PRIOR != 0>(slot, fuse_lm, mine, st, ep, partials, ticket, hist, out, sh, T, pose, prior);
 }
 
 static_assert(sizeof(LmState) / 8 <= 256, "controller state is moved one word per thread");
@@ -2660,7 +2676,7 @@ __global__ __launch_bounds__(256, BATCH ? 2 : 1) void solve_kernel(int lm_max, c
                                                     const float4* __restrict__ mpts, const uint32_t* __restrict__ nbr5,
                                                     MatchParams mp, BatchView bv) {
 #define SO_BODY_KERNEL solve_kernel<PROF, BATCH, PEER>
-#define SO_BODY_PRIOR false
+#define SO_BODY_PRIOR 0
 #define SO_BODY_PRIOR_WORDS nullptr
 #include "solve_kernel_body.inc"
 #undef SO_BODY_KERNEL
@@ -2678,7 +2694,27 @@ __global__ __launch_bounds__(256, 1) void solve_kernel_prior(int lm_max, const f
                                                     MatchParams mp, BatchView bv, PosePrior prior) {
   constexpr bool BATCH = false, PEER = false;
 #define SO_BODY_KERNEL solve_kernel_prior<PROF>
-#define SO_BODY_PRIOR true
+#define SO_BODY_PRIOR 1
+#define SO_BODY_PRIOR_WORDS reinterpret_cast<const double*>(&prior)
+#include "solve_kernel_body.inc"
+#undef SO_BODY_KERNEL
+#undef SO_BODY_PRIOR
+#undef SO_BODY_PRIOR_WORDS
+}
+// solve_kernel_prior for a CHAINED registration of a sequence whose prior is measured at the frame's own guess
+// (so_icp_set_sequence_priors, SO_ICP_PRIOR_AT_GUESS): the host does not know that guess when it enqueues the launch -- the solve
+// that ends the registration in front forms it (DevState::T_chain) --, so T_meas is DevState::pose_in, where the registration's
+// BEGIN launch stored the guess it started from; `prior` brings U, floors and fractions, its T_meas words are not read.
+template <bool PROF>
+__global__ __launch_bounds__(256, 1) void solve_kernel_prior_at_guess(int lm_max, const float* __restrict__ spx, const float* __restrict__ spy,
+                                                    const float* __restrict__ spz, CorrBuffers corr, DevState* __restrict__ st,
+                                                    EvalParams ep, double* __restrict__ partials, uint32_t* __restrict__ ticket,
+                                                    int32_t* __restrict__ hist, LmSums* __restrict__ out,
+                                                    const float4* __restrict__ mpts, const uint32_t* __restrict__ nbr5,
+                                                    MatchParams mp, BatchView bv, PosePrior prior) {
+  constexpr bool BATCH = false, PEER = false;
+#define SO_BODY_KERNEL solve_kernel_prior_at_guess<PROF>
+#define SO_BODY_PRIOR kPriorAtGuess
 #define SO_BODY_PRIOR_WORDS reinterpret_cast<const double*>(&prior)
 #include "solve_kernel_body.inc"
 #undef SO_BODY_KERNEL
@@ -2953,14 +2989,16 @@ void launch_eval(int slot, bool fuse_lm, const float* spx, const float* spy, con
 }
 void launch_solve(int lm_max, const float* spx, const float* spy, const float* spz, const CorrBuffers& corr, DevState* st,
                   const EvalParams& ep, double* partials, uint32_t* ticket, int32_t* hist, LmSums* sums, const DevMapView& map,
-                  const uint32_t* nbr5, const MatchParams& mp, uint32_t n_upper, uint32_t max_blocks, hipStream_t s, const PosePrior* prior) {
+                  const uint32_t* nbr5, const MatchParams& mp, uint32_t n_upper, uint32_t max_blocks, hipStream_t s, const PosePrior* prior,
+                  bool prior_at_guess) {
   // every workgroup must be resident for the whole launch (94 KB of LDS: one per compute unit)
   const uint32_t blocks = solve_grid(n_upper, max_blocks);
   const bool prof = ep.ablate != 0 || mp.ablate != 0;
   auto* k = ep.peer_world > 1 ? (prof ? solve_kernel<true, false, true> : solve_kernel<false, false, true>)
                               : (prof ? solve_kernel<true, false, false> : solve_kernel<false, false, false>);
   if (prior && ep.peer_world <= 1) {  // (the prior travels as the launch's last argument)
-    auto* kp = prof ? solve_kernel_prior<true> : solve_kernel_prior<false>;
+    auto* kp = prior_at_guess ? (prof ? solve_kernel_prior_at_guess<true> : solve_kernel_prior_at_guess<false>)
+                              : (prof ? solve_kernel_prior<true> : solve_kernel_prior<false>);
     hipLaunchKernelGGL(kp, dim3(blocks), dim3(256), 0, s, lm_max, spx, spy, spz, corr, st, ep, partials, ticket, hist, sums, map.pts, nbr5, mp, kNoBatch, *prior);
     return;
   }

@@ -30,7 +30,12 @@ int so_icp_localization_sequence(so_icp_ctx* c, int count, const void* const* sc
     if (!scans[k] && n_points[k]) return fail(c, SO_ICP_E_INVALID, "so_icp_localization_sequence: scans[" + std::to_string(k) + "] is NULL");
   if (count == 0) return SO_ICP_OK;
   NEED_DEVICE(c);
-  if (const int rc = refuse_pending_prior(c, "so_icp_localization_sequence")) return rc;
+  if (const int rc = refuse_pending_prior(c, "so_icp_localization_sequence", true)) return rc;
+  // so_icp_set_sequence_priors: one prior per frame of this call (another length: refused, they stay pending); taken out of the context
+  // here -- consumed whatever this call returns --, frame k's goes in as the single prior its per-frame entry consumes
+  if (!RunPriors::count_matches(c, count)) return fail(c, SO_ICP_E_INVALID, "so_icp_localization_sequence: count differs from that of the pending so_icp_set_sequence_priors call");
+  RunPriors run_priors;
+  run_priors.take(c);
 
   double guess[7];
   std::memcpy(guess, pose0, sizeof(guess));
@@ -42,6 +47,7 @@ int so_icp_localization_sequence(so_icp_ctx* c, int count, const void* const* sc
     double* pose_out = poses_out + 7 * (size_t)k;
     so_icp_stats local;
     so_icp_stats* st = stats ? stats + k : &local;
+    run_priors.arm(c, k, guess);
     const int rc = scans_on_device
                        ? so_icp_localization_dev(c, 1, guess, scans[k], n_points[k], times[k], pose_out, st)
                        : so_icp_localization(c, 1, guess, static_cast<const float*>(scans[k]), n_points[k], stride_bytes, times[k], pose_out, st);

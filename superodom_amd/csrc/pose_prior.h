@@ -12,6 +12,9 @@
 // give the same bits.  A word's work comes in two parts: what needs the pose alone (pose_prior_prepare: the rows of U e and the two
 // columns of U B the word reads) and what needs the count as well (pose_prior_finish) -- on the device the first part runs in
 // front of the wait for the pass's last record.
+// The measurement T_meas may lie apart from the other 48 words (so_icp_set_sequence_priors, SO_ICP_PRIOR_AT_GUESS: the frame's guess,
+// DevState::pose_in, with U / floor / fraction from the kernel's argument): the *_at forms take it as a pointer of its own, and the
+// forms without it are those with Tm = P -- the same chains on the same operands.
 #pragma once
 #include "lm_solver.h"
 #include "so_math.h"
@@ -42,10 +45,10 @@ SO_HD void pose_prior_columns(int word, int& i, int& j) {
   j = i + t - (6 * i - (i * (i - 1)) / 2);
 }
 
-// the residual e and the rotation block's quaternion (v', w') at `pose`
-SO_HD void pose_prior_error(const double* P, const double pose[7], double e[6], double m[4]) {
-  e[0] = pose[0] - P[0]; e[1] = pose[1] - P[1]; e[2] = pose[2] - P[2];
-  const double qc[4] = {-P[3], -P[4], -P[5], P[6]};
+// the residual e and the rotation block's quaternion (v', w') at `pose`; Tm: the measurement's seven words
+SO_HD void pose_prior_error(const double* Tm, const double pose[7], double e[6], double m[4]) {
+  e[0] = pose[0] - Tm[0]; e[1] = pose[1] - Tm[1]; e[2] = pose[2] - Tm[2];
+  const double qc[4] = {-Tm[3], -Tm[4], -Tm[5], Tm[6]};
   double qe[4];
   quat_mul(qc, pose + 3, qe);
   e[3] = 2.0 * qe[0]; e[4] = 2.0 * qe[1]; e[5] = 2.0 * qe[2];
@@ -73,9 +76,10 @@ SO_HD void pose_prior_column(const double* P, const double m[4], int c, double c
 // rest, so that nothing is read from memory once the count is known)
 struct PosePriorPart { double ue[6], ci[6], cj[6], floor[6], fraction[6]; };
 
-SO_HD void pose_prior_prepare(const double* P, const double pose[7], int word, PosePriorPart& part) {
+// (Tm: T_meas; P: the prior's 55 words, of which the first seven are not read)
+SO_HD void pose_prior_prepare_at(const double* Tm, const double* P, const double pose[7], int word, PosePriorPart& part) {
   double e[6], m[4];
-  pose_prior_error(P, pose, e, m);
+  pose_prior_error(Tm, pose, e, m);
   int i, j;
   pose_prior_columns(word, i, j);
   SO_PRIOR_UNROLL
@@ -91,6 +95,8 @@ SO_HD void pose_prior_prepare(const double* P, const double pose[7], int word, P
   SO_PRIOR_UNROLL
   for (int k = 0; k < 6; ++k) { part.floor[k] = P[kPriorFloor + k]; part.fraction[k] = P[kPriorFraction + k]; }
 }
+
+SO_HD void pose_prior_prepare(const double* P, const double pose[7], int word, PosePriorPart& part) { pose_prior_prepare_at(P, P, pose, word, part); }
 
 // LidarSlam.cpp:289-294: information(k, k) carries std::max(floor, int(good_feature_num * fraction)); its square root scales row k
 SO_HD double pose_prior_row_scale(double floor, double fraction, double count) {
@@ -112,16 +118,17 @@ SO_HD double pose_prior_finish(const PosePriorPart& part, double count, int word
 }
 
 // host form: the 28 words one after the other, plane sum on the left of every addition
-SO_HD void pose_prior_add(const double* P, const double pose[7], LmSums& sums) {
+SO_HD void pose_prior_add_at(const double* Tm, const double* P, const double pose[7], LmSums& sums) {
   double* o = reinterpret_cast<double*>(&sums);
   const double count = sums.count;
   for (int word = 0; word < kPriorSumWords; ++word) {
     if (word == 1) continue;
     PosePriorPart part;
-    pose_prior_prepare(P, pose, word, part);
+    pose_prior_prepare_at(Tm, P, pose, word, part);
     o[word] = o[word] + pose_prior_finish(part, count, word);
   }
 }
+SO_HD void pose_prior_add(const double* P, const double pose[7], LmSums& sums) { pose_prior_add_at(P, P, pose, sums); }
 
 // U = L^T of the LLT of a symmetric positive semi-definite matrix (its lower triangle is read).  A zero pivot with a zero column
 // below it is allowed (the reference's information(5,5) is 0) and leaves a zero row in U.  false: not such a matrix.

@@ -20,6 +20,15 @@ inline int lm_limit(int lm_max_iterations) { return std::min(lm_max_iterations >
 // device, and a registration (so_icp_match leaves it pending)
 inline bool carries_pose_prior(bool pending, bool own, int world_size, bool match_only) { return pending && own && world_size <= 1 && !match_only; }
 
+// so_icp_set_sequence_priors: which persistent-solve kernel the launches of frame k of so_icp_register_sequence's chained path use.
+// `mode`: the frame's SO_ICP_PRIOR_* (0 none, 1 given, 2 at the guess); `chained`: the frame's BEGIN launch takes its guess from
+// DevState::T_chain, so the host holds only a prediction of it.  Wherever the host knows the guess exactly -- frame 0, an unchained
+// start, the start after a broken chain -- it fills T_meas itself and solve_kernel_prior serves both modes.
+enum SolveKernelKind { kSolvePlain = 0, kSolvePrior = 1, kSolvePriorAtGuess = 2 };
+inline SolveKernelKind sequence_solve_kernel(int mode, bool chained) {
+  return mode == 0 ? kSolvePlain : ((mode == 2 && chained) ? kSolvePriorAtGuess : kSolvePrior);
+}
+
 // scans of this many points or more are refused (refuse_scan_size, icp_context.cpp): the work-list counters hold 21 bits each
 constexpr size_t kMaxScanPoints = (size_t)1 << 21;
 

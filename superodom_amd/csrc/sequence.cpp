@@ -9,6 +9,9 @@
 // ahead (what the last one needed); one that needs more makes the launches behind it no-ops, the host finishes it with further
 // launches and starts the next one again, unchained.  Every registration is the one so_icp_register runs from guesses_out[k]: same
 // kernels, same arguments, same sums -- identical bits (tests/test_gpu_sequence.py).
+// so_icp_set_sequence_priors gives every frame a pose prior of its own: frame k is then so_icp_set_pose_prior(P_k) + so_icp_register,
+// P_k's measurement being the frame's guess where the mode says so -- on the device for a chained frame (solve_kernel_prior_at_guess
+// reads DevState::pose_in), on the host elsewhere (tests/test_gpu_sequence_priors.py).
 #include <hip/hip_runtime_api.h>
 
 #include <algorithm>
@@ -45,6 +48,10 @@ struct SeqRun : RegWork {                  // (d_scan, n, query_waves, work list
   int pos[3] = {0, 0, 0}; int count_5x5 = 0;
   unsigned long long seq_base = 0; int ring = 0; int enq_iters = 0;
   MatchParams mp; EvalParams ep;
+  // so_icp_set_sequence_priors: the frame's SO_ICP_PRIOR_* and prior.  AT_GUESS: T_meas is filled by prepare() for a start whose guess
+  // the host knows exactly; for a chained start the launches take it from DevState::pose_in (reg_plan.h: sequence_solve_kernel)
+  int prior_mode = SO_ICP_PRIOR_NONE;
+  PosePrior prior{};
 };
 
 // One so_icp_register_sequence call: its arguments, the run record of every scan, what the call before staged for scan 0
@@ -52,6 +59,7 @@ struct SequenceCall {
   so_icp_ctx* c; int count; const void* const* scans; const size_t* n_points; size_t stride_bytes; int scans_on_device;
   const double* pose0; const double* deltas; double* poses_out; double* guesses_out; so_icp_stats* stats; int* n_done;
   std::vector<SeqRun> runs;
+  RunPriors run_priors;                     // so_icp_set_sequence_priors: taken out of the context when the call started (empty: none were set)
   so_icp_ctx::SeqNext adopted;
   int slot_base = 0;
 
@@ -69,6 +77,7 @@ struct SequenceCall {
   }
   int run_plain(int k, const double guess[7]) {  // one registration through the ordinary entry points
     if (guesses_out) std::memcpy(guesses_out + 7 * (size_t)k, guess, 7 * sizeof(double));
+    run_priors.arm(c, k, guess);  // (the frame's prior, measured at this guess where its mode says so; the entry below consumes it)
     return scans_on_device ? so_icp_register_dev(c, scans[k], n_points[k], guess, poses_out + 7 * (size_t)k, &stats[k])
                            : so_icp_register(c, static_cast<const float*>(scans[k]), n_points[k], stride_bytes, guess, poses_out + 7 * (size_t)k, &stats[k]);
   }
@@ -87,6 +96,8 @@ struct SequenceCall {
     r.n = n;
     r.query_waves = c->query_waves && query_wave_count_ok(c->cfg.max_surface_features, n, kQueryWaveMaxKept);  // (as register_core_once sweeps it)
     r.ring = (k & 1) * 2;
+    r.prior_mode = k < count ? run_priors.mode(k) : SO_ICP_PRIOR_NONE;
+    if (r.prior_mode != SO_ICP_PRIOR_NONE) r.prior = run_priors.priors[(size_t)k];
     if (!scans_on_device || !r.query_waves) r.slot = &c->seq_slot[(slot_base + k) % so_icp_ctx::kStageSlots];
     r.max_outer = outer_limit(c->cfg.max_iterations); r.lm_max = lm_limit(c->cfg.lm_max_iterations);
     r.corr = CorrBuffers{c->d_nd.as<double4>(), c->d_coeff.as<double>(), c->d_status.as<uint8_t>()};
@@ -157,6 +168,7 @@ struct SequenceCall {
     SeqRun& r = runs[(size_t)k];
     *rc_out = SO_ICP_OK;
     std::memcpy(r.guess, guess, sizeof(r.guess));
+    if (r.prior_mode == SO_ICP_PRIOR_AT_GUESS && !chained) std::memcpy(r.prior.T_meas, guess, sizeof(r.prior.T_meas));  // (exact: the BEGIN launch starts from this argument)
     if (!r.query_waves && !r.binned) return false;
     if (!c->no_map_shift) {
       const int dims[3] = {kMapW, kMapH, kMapD};
@@ -210,7 +222,8 @@ struct SequenceCall {
       EvalParams ep_it = r.ep;
       ep_it.defer_publish = (it + 1 < it1) ? 1 : 0;
       if (k + 1 < count) { ep_it.chain_next = 1; std::memcpy(ep_it.chain_delta, delta(k + 1), sizeof(ep_it.chain_delta)); }  // (whichever solve ends this registration forms the next guess)
-      launch_persistent_solve(c, r, ep_it, r.mp);
+      const SolveKernelKind kind = sequence_solve_kernel(r.prior_mode, r.chained);
+      launch_persistent_solve(c, r, ep_it, r.mp, kind == kSolvePlain ? nullptr : &r.prior, kind == kSolvePriorAtGuess);
     }
     HIP_TRY(c, hipGetLastError());
     r.enq_iters = it1; r.enqueued = true;
@@ -237,7 +250,8 @@ struct SequenceCall {
     const DevState& H = *c->h_state;
     std::memset(st, 0, sizeof(*st));
     st->flags = (r.slot && !scans_on_device ? SO_ICP_FLAG_STAGED_SCAN : 0u) | (r.binned ? SO_ICP_FLAG_BINNED_AHEAD : 0u) |
-                (r.query_waves ? SO_ICP_FLAG_QUERY_WAVES : 0u) | (r.chained ? SO_ICP_FLAG_CHAINED : 0u);
+                (r.query_waves ? SO_ICP_FLAG_QUERY_WAVES : 0u) | (r.chained ? SO_ICP_FLAG_CHAINED : 0u) |
+                (r.prior_mode != SO_ICP_PRIOR_NONE ? SO_ICP_FLAG_POSE_PRIOR : 0u);
     fill_stats_header(c, st, r.pos, r.count_5x5, r.n);
     double guess[7];
     std::memcpy(guess, H.pose_in, sizeof(guess));  // (what the device formed for a chained registration; the host's own argument otherwise)
@@ -252,6 +266,7 @@ struct SequenceCall {
     }
     (void)hipGetLastError();
     fill_result(c, H, guess, st, poses_out + 7 * (size_t)k, true);
+    if (r.prior_mode != SO_ICP_PRIOR_NONE) st->prediction_source = 1;  // addAbsolutePoseConstraints, LidarSlam.cpp:297
     if (k == count - 1 && keeps_correspondences(c)) {
       // so_icp_correspondences exports the LAST registration of the run (the records of the others were overwritten by the launches
       // chained behind them).  Its scan lies in a slot the next call refills on the sequence's own queue: copied now, and waited for
@@ -389,13 +404,19 @@ int so_icp_register_sequence(so_icp_ctx* c, int count, const void* const* scans,
   if (n_done) *n_done = 0;
   if (!c || count < 0 || (count && (!scans || !n_points || !pose0 || !poses_out)) || (count > 1 && !deltas)) return SO_ICP_E_INVALID;
   NEED_DEVICE(c);
-  if (const int rc = refuse_pending_prior(c, "so_icp_register_sequence")) return rc;
+  if (const int rc = refuse_pending_prior(c, "so_icp_register_sequence", true)) return rc;
+  // so_icp_set_sequence_priors: one prior per frame of THIS call -- a call of another length leaves them pending, this one takes them
+  // out of the context (consumed whatever it returns; the per-frame entries it may run do not meet them)
+  if (!RunPriors::count_matches(c, count)) return fail(c, SO_ICP_E_INVALID, "so_icp_register_sequence: count differs from that of the pending so_icp_set_sequence_priors call");
+  RunPriors run_priors;
+  run_priors.take(c);
   HIP_TRY(c, hipSetDevice(c->cfg.device_id));
   if (stride_bytes == 0) stride_bytes = 12;
   for (int k = 0; k < count; ++k) if (!scans[k] && n_points[k]) return SO_ICP_E_INVALID;
   std::vector<so_icp_stats> local_stats;
   if (!stats) { local_stats.resize((size_t)count); stats = local_stats.data(); }
   SequenceCall call{c, count, scans, n_points, stride_bytes, scans_on_device, pose0, deltas, poses_out, guesses_out, stats, n_done};
+  call.run_priors = std::move(run_priors);
   c->corr_last.valid = false;
   const int rc = chained_path(c, count, scans_on_device, stride_bytes) ? call.run_chained() : call.run_unchained();
   if (rc != SO_ICP_OK) c->corr_last.valid = false;  // (so_icp_correspondences: only a run that completed leaves its last registration's set)

@@ -1,8 +1,9 @@
-// solve_kernel_body.inc -- the body of solve_kernel and of solve_kernel_prior (kernels.hip), included once for each with
+// solve_kernel_body.inc -- the body of solve_kernel, solve_kernel_prior and solve_kernel_prior_at_guess (kernels.hip), included once
+// for each with
 //   SO_BODY_KERNEL  the kernel's own instantiation (its kernarg lines)
-//   SO_BODY_PRIOR   false / true: eval_pass without / with the pose prior
+//   SO_BODY_PRIOR   0 / 1 / kPriorAtGuess: eval_pass without the pose prior / with it / with it, T_meas = DevState::pose_in
 //   SO_BODY_PRIOR_WORDS   nullptr / the prior's 55 doubles (the kernel's last argument)
-// and PROF, BATCH, PEER in scope.  One text, two kernels of different names: a registration without a prior launches the
+// and PROF, BATCH, PEER in scope.  One text, three kernels of different names: a registration without a prior launches the
 // functions it always launched.
   __shared__ EvalShared sh;
   __shared__ CorrCache cache;  // 26 KB next to the 64 KB of EvalShared: gfx950 has 160 KB of LDS per CU, one workgroup each here
@@ -24,6 +25,18 @@
   if (st->reg_done) return;
   if (!BATCH && ep.chain_expect && st->done_count != ep.chain_expect) return;  // chained registration whose predecessor was not over: no-op
   const int tid = threadIdx.x;
+  // kPriorAtGuess: the measurement is the guess this registration's BEGIN launch stored (reg_begin_state) -- an earlier launch of
+  // the same queue, so a plain load; once, by the controller's first wavefront, the only one that reads it (eval_pass:
+  // prior_prepare_at, in front of the polling loop of every pass).  Behind the two returns above: a launch enqueued behind the
+  // registration's converged iteration, or behind a registration in front that was not over, never gets here, and a launch that
+  // does runs before the BEGIN launch of the next registration, which is behind it in the queue and the only writer of pose_in.
+  [[maybe_unused]] double prior_tm[7] = {0, 0, 0, 0, 0, 0, 1};
+  if constexpr (SO_BODY_PRIOR == kPriorAtGuess) {
+    if (blockIdx.x == 0 && tid < 64) {
+#pragma unroll
+      for (int i = 0; i < 7; ++i) prior_tm[i] = st->pose_in[i];
+    }
+  }
   // hand-off record: 8 chunks of 16 bytes {value, epoch}, each written / read with ONE sc1 dwordx4 access (atomic as a
   // unit), so a reader that sees the expected epoch in a chunk has that chunk's value: no second round trip, no
   // publisher-side wait between data and flag.  Chunks 0..6 = next pose, chunk 7 = "another evaluation follows".
@@ -40,7 +53,7 @@
   }
   const unsigned long long tag0 = (e0 + 1ull) << 5;  // pass tags: unique over launches (every launch advances the epoch) and passes (slot <= 16)
   if (PROF && !BATCH && (ep.ablate & 128) && tid == 0 && blockIdx.x == 0) st->dbg[3] = wall_clock64() - t_entry;
-  int code = eval_pass<true, true, PROF, BATCH, PEER, SO_BODY_PRIOR>(0, 1, pose, spx, spy, spz, corr, st, ep, partials, ticket, hist, out, mpts, nbr5, mp, sh, SO_BODY_PRIOR_WORDS, tag0, &cache, hand, e0 + 1ull, span);
+  int code = eval_pass<true, true, PROF, BATCH, PEER, SO_BODY_PRIOR>(0, 1, pose, spx, spy, spz, corr, st, ep, partials, ticket, hist, out, mpts, nbr5, mp, sh, SO_BODY_PRIOR_WORDS, tag0, &cache, hand, e0 + 1ull, span, prior_tm);
   for (int slot = 1; slot <= lm_max; ++slot) {
     __syncthreads();
     const unsigned long long want = e0 + (unsigned long long)slot;
@@ -70,5 +83,5 @@
     if (sh.more != 1) return;  // solve ended (or timeout)
     pose = pose_from_array(sh.pose);
     __syncthreads();
-    code = eval_pass<false, true, PROF, BATCH, PEER, SO_BODY_PRIOR>(slot, 1, pose, spx, spy, spz, corr, st, ep, partials, ticket, hist, out, mpts, nbr5, mp, sh, SO_BODY_PRIOR_WORDS, tag0 + (unsigned long long)slot, &cache, hand, want + 1ull, span);
+    code = eval_pass<false, true, PROF, BATCH, PEER, SO_BODY_PRIOR>(slot, 1, pose, spx, spy, spz, corr, st, ep, partials, ticket, hist, out, mpts, nbr5, mp, sh, SO_BODY_PRIOR_WORDS, tag0 + (unsigned long long)slot, &cache, hand, want + 1ull, span, prior_tm);
   }
