@@ -3,14 +3,13 @@
 // point, in scan order, with the residual and the robust weight of the record at a pose of the caller's choice.
 //   correspondences_kernel  reads the records the last fit pass left in memory (kernels.hip eval_pass: corr.nd / corr.coeff /
 //                           corr.status, indexed like the scan) and the scan copy the registration kept; compacts the accepted ones
-// Nothing here runs during a registration and no registration kernel is changed: the evaluation arithmetic is RESTATED below from
-// eval_pass's lambdas `tail` and `at_pose`, expression for expression, so a record's residual and weight at the last evaluation's
-// pose are the values that evaluation used (same headers, same -ffp-contract=off, the same explicit SO_FMA).
+// Nothing here runs during a registration and no registration kernel is changed; residual, loss and weight are plane_factor.h's, as
+// in eval_pass.
 #include <hip/hip_runtime.h>
 
 #include "corr_kernels.h"
 #include "device_idioms.h"
-#include "so_math.h"
+#include "plane_factor.h"
 
 namespace soicp {
 
@@ -34,8 +33,7 @@ __global__ __launch_bounds__(256) void correspondences_kernel(const float* __res
   if (tid == 0) s_bid = atomicAdd(ticket, 1u);
   __syncthreads();
   const uint32_t bid = s_bid;
-  // (eval_pass: the quotient s / a^2 as a product with the reciprocal, the comparison on s itself)
-  const double inv_a2 = 1.0 / a2, rho_out = (variant == 0) ? a2 / 6.0 : a2 / 3.0;
+  const TukeyLoss L(a2, variant);
   unsigned long long bal[kPer];
   float pf[kPer][3];
   double4 nd[kPer];
@@ -54,19 +52,9 @@ __global__ __launch_bounds__(256) void correspondences_kernel(const float* __res
       if (ok) {
         pf[q][0] = scan[(size_t)i * 3]; pf[q][1] = scan[(size_t)i * 3 + 1]; pf[q][2] = scan[(size_t)i * 3 + 2];
         nd[q] = cnd[i]; co[q] = ccoeff[i];
-        const double px = (double)pf[q][0], py = (double)pf[q][1], pz = (double)pf[q][2];
-        double wx, wy, wz;
-        quat_rotate<double>(pose.q, px, py, pz, wx, wy, wz);  // at_pose
-        wx += pose.t[0]; wy += pose.t[1]; wz += pose.t[2];
-        const double r = SO_FMA(nd[q].x, wx, SO_FMA(nd[q].y, wy, SO_FMA(nd[q].z, wz, nd[q].w)));  // tail
-        const double s = r * r;
+        const double r = plane_residual_at(pose.q, pose.t, (double)pf[q][0], (double)pf[q][1], (double)pf[q][2], nd[q].x, nd[q].y, nd[q].z, nd[q].w);
         double rho0, rho1;
-        if (s <= a2) {
-          const double v = 1.0 - s * inv_a2, v2 = v * v;
-          rho0 = rho_out * (1.0 - v2 * v); rho1 = (variant == 0) ? 0.5 * v2 : v2;
-        } else {
-          rho0 = rho_out; rho1 = 0;
-        }
+        tukey_rho(L, r * r, rho0, rho1);
         res[q] = r; wgt[q] = co[q] * rho1;
         cost = SO_FMA(0.5 * co[q], rho0, cost);
         rf = (float)r;

@@ -5,19 +5,18 @@
 //                                   point, and loops over the poses: one partial vector of the 29 sums per (tile, pose)
 //   correspondence_sums_add_kernel  adds the tiles in tile order, one thread per (pose, component), into so_icp_sums records (a pose's
 //                                   partial vectors reach its threads through LDS, 64 tiles at a time)
-// Nothing here runs during a registration.  The per-point arithmetic is correspondences_kernel's (residual, loss: eval_pass's `at_pose`
-// and `tail`, expression for expression) plus `tail`'s Jacobian row and sums; same headers, same -ffp-contract=off, the same explicit
-// SO_FMA.  No atomics: every sum is a fixed tree, so two calls give the same bits, a pose's sums do not depend on the other poses of
-// the call, and `cost` is so_icp_correspondences' cost at that pose bit for bit.
+// Nothing here runs during a registration.  The per-point arithmetic is plane_factor.h's, as in eval_pass and correspondences_kernel.
+// No atomics: every sum is a fixed tree, so two calls give the same bits, a pose's sums do not depend on the other poses of the call,
+// and `cost` is so_icp_correspondences' cost at that pose bit for bit.
 #include <hip/hip_runtime.h>
 
 #include "corr_kernels.h"
-#include "so_math.h"
+#include "plane_factor.h"
 
 namespace soicp {
 
 namespace {
-// a pose of the table in LDS: translation, quaternion, R(q) as Eigen::Quaternion::toRotationMatrix (eval_pass forms it the same way)
+// a pose of the table in LDS: translation, quaternion, R(q) (quat_to_matrix)
 struct SumsPose { double t[3], q[4], R[9]; };
 }  // namespace
 
@@ -30,6 +29,7 @@ __global__ __launch_bounds__(256) void correspondence_sums_kernel(const float* _
                                                                   const double* __restrict__ poses, uint32_t n_poses, double a2, int variant,
                                                                   double* __restrict__ partials) {
   constexpr int kPer = (int)(kCorrTile / 256u), kAcc = (int)kCorrSumsAcc;
+  static_assert(kAcc == kPlaneFactorSums, "plane_factor_add fills a partial vector");
   __shared__ SumsPose s_pose[kCorrSumsMaxPoses];
   __shared__ double s_part[2][4][kAcc];
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
@@ -38,17 +38,10 @@ __global__ __launch_bounds__(256) void correspondence_sums_kernel(const float* _
     SumsPose P;
     for (int k = 0; k < 3; ++k) P.t[k] = poses[(size_t)tid * 7 + k];
     for (int k = 0; k < 4; ++k) P.q[k] = poses[(size_t)tid * 7 + 3 + k];
-    const double qx = P.q[0], qy = P.q[1], qz = P.q[2], qw = P.q[3];
-    const double tx = 2 * qx, ty = 2 * qy, tz = 2 * qz;
-    const double twx = tx * qw, twy = ty * qw, twz = tz * qw, txx = tx * qx, txy = ty * qx, txz = tz * qx;
-    const double tyy = ty * qy, tyz = tz * qy, tzz = tz * qz;
-    P.R[0] = 1 - (tyy + tzz); P.R[1] = txy - twz; P.R[2] = txz + twy;
-    P.R[3] = txy + twz; P.R[4] = 1 - (txx + tzz); P.R[5] = tyz - twx;
-    P.R[6] = txz - twy; P.R[7] = tyz + twx; P.R[8] = 1 - (txx + tyy);
+    quat_to_matrix(P.q, P.R);
     s_pose[tid] = P;
   }
-  // (eval_pass: the quotient s / a^2 as a product with the reciprocal, the comparison on s itself)
-  const double inv_a2 = 1.0 / a2, rho_out = (variant == 0) ? a2 / 6.0 : a2 / 3.0;
+  const TukeyLoss L(a2, variant);
   bool ok[kPer];
   double pp[kPer][3];
   double4 nd[kPer];
@@ -74,36 +67,10 @@ __global__ __launch_bounds__(256) void correspondence_sums_kernel(const float* _
 #pragma unroll
     for (int q = 0; q < kPer; ++q) {
       if (!ok[q]) continue;
-      const double px = pp[q][0], py = pp[q][1], pz = pp[q][2];
-      double wx, wy, wz;
-      quat_rotate<double>(P.q, px, py, pz, wx, wy, wz);  // at_pose
-      wx += P.t[0]; wy += P.t[1]; wz += P.t[2];
-      const double r = SO_FMA(nd[q].x, wx, SO_FMA(nd[q].y, wy, SO_FMA(nd[q].z, wz, nd[q].w)));  // tail
-      const double s = r * r;
+      const double r = plane_residual_at(P.q, P.t, pp[q][0], pp[q][1], pp[q][2], nd[q].x, nd[q].y, nd[q].z, nd[q].w);
       double rho0, rho1;
-      if (s <= a2) {
-        const double v = 1.0 - s * inv_a2, v2 = v * v;
-        rho0 = rho_out * (1.0 - v2 * v); rho1 = (variant == 0) ? 0.5 * v2 : v2;
-      } else {
-        rho0 = rho_out; rho1 = 0;
-      }
-      const double w = co[q] * rho1;
-      // J = [n^T, (p x R^T n)^T]  (lidarOptimization.cpp:68-74)
-      const double m0 = SO_FMA(P.R[0], nd[q].x, SO_FMA(P.R[3], nd[q].y, P.R[6] * nd[q].z));
-      const double m1 = SO_FMA(P.R[1], nd[q].x, SO_FMA(P.R[4], nd[q].y, P.R[7] * nd[q].z));
-      const double m2 = SO_FMA(P.R[2], nd[q].x, SO_FMA(P.R[5], nd[q].y, P.R[8] * nd[q].z));
-      const double J[6] = {nd[q].x, nd[q].y, nd[q].z, SO_FMA(py, m2, -(pz * m1)), SO_FMA(pz, m0, -(px * m2)), SO_FMA(px, m1, -(py * m0))};
-      acc[0] = SO_FMA(0.5 * co[q], rho0, acc[0]);
-      acc[1] += 1.0;
-      const double wr = w * r;
-      int e = 8;
-#pragma unroll
-      for (int a = 0; a < 6; ++a) {
-        acc[2 + a] = SO_FMA(J[a], wr, acc[2 + a]);
-        const double wj = w * J[a];
-#pragma unroll
-        for (int b = a; b < 6; ++b) { acc[e] = SO_FMA(wj, J[b], acc[e]); ++e; }
-      }
+      tukey_rho(L, r * r, rho0, rho1);
+      plane_factor_add(P.R, pp[q][0], pp[q][1], pp[q][2], nd[q].x, nd[q].y, nd[q].z, co[q], r, rho0, co[q] * rho1, acc);
     }
 #pragma unroll
     for (int a = 0; a < kAcc; ++a) {

@@ -21,14 +21,6 @@ SO_HD void quat_normalized(const double q[4], double o[4]) {  // Eigen 3.4 norma
   if (n2 > 0) { const double n = sqrt(n2); o[0] = q[0] / n; o[1] = q[1] / n; o[2] = q[2] / n; o[3] = q[3] / n; }
   else { o[0] = q[0]; o[1] = q[1]; o[2] = q[2]; o[3] = q[3]; }
 }
-SO_HD void quat_to_matrix(const double q[4], double m[9]) {  // QuaternionBase::toRotationMatrix, row-major
-  const double tx = 2 * q[0], ty = 2 * q[1], tz = 2 * q[2];
-  const double twx = tx * q[3], twy = ty * q[3], twz = tz * q[3];
-  const double txx = tx * q[0], txy = ty * q[0], txz = tz * q[0], tyy = ty * q[1], tyz = tz * q[1], tzz = tz * q[2];
-  m[0] = 1 - (tyy + tzz); m[1] = txy - twz; m[2] = txz + twy;
-  m[3] = txy + twz; m[4] = 1 - (txx + tzz); m[5] = tyz - twx;
-  m[6] = txz - twy; m[7] = tyz + twx; m[8] = 1 - (txx + tyy);
-}
 SO_HD void matrix_to_quat(const double a[9], double q[4]) {  // quaternionbase_assign_impl<Matrix3>::run; branches written without indexed registers
   double t = a[0] + a[4] + a[8];
   if (t > 0) {

@@ -33,6 +33,7 @@
 #endif
 #include "device_idioms.h"
 #include "kernels.h"
+#include "plane_factor.h"
 #include "plane_fit.h"
 #include "pose_prior.h"
 
@@ -1524,7 +1525,7 @@ __global__ __launch_bounds__(256) void knn_query_wave_kernel(const float* __rest
 // ------------------------------------------------------------------------------------------------
 // LM evaluation: fused cost + J^T J + J^T r
 // ------------------------------------------------------------------------------------------------
-constexpr int kNAcc = 29;  // cost, count, Jtr[6], JtJ[21]
+constexpr int kNAcc = kPlaneFactorSums;  // cost, count, Jtr[6], JtJ[21]
 
 // Which queries a workgroup of the evaluation / solve launches walks: thread `tid` of (virtual) workgroup vb, trip q, grid of V
 // workgroups -- 256 consecutive scan points per workgroup and trip.  With V >= n / 256 every workgroup makes one trip over
@@ -2214,22 +2215,14 @@ __device__ __forceinline__ int eval_pass(int slot, int fuse_lm, const Pose& pose
   const uint32_t n_kept = (abl & 64) ? 0u : ep.n_queries;  // every query of the scan, original order
   const uint32_t qs = ep.q_stride;
   double acc[kNAcc];
-  // R(q) as Eigen::Quaternion::toRotationMatrix (lidarOptimization.cpp:70)
-  const double qx = pose.q[0], qy = pose.q[1], qz = pose.q[2], qw = pose.q[3];
-  const double tx = 2 * qx, ty = 2 * qy, tz = 2 * qz;
-  const double twx = tx * qw, twy = ty * qw, twz = tz * qw, txx = tx * qx, txy = ty * qx, txz = tz * qx;
-  const double tyy = ty * qy, tyz = tz * qy, tzz = tz * qz;
-  const double R00 = 1 - (tyy + tzz), R01 = txy - twz, R02 = txz + twy;
-  const double R10 = txy + twz, R11 = 1 - (txx + tzz), R12 = tyz - twx;
-  const double R20 = txz - twy, R21 = tyz + twx, R22 = 1 - (txx + tyy);
+  double R[9];  // lidarOptimization.cpp:70
+  quat_to_matrix(pose.q, R);
   const ObsAxes axes = obs_axes(pose);  // (FIT) sensor axes of the observability analysis: constant over the pass
-  // residual, robust weight, Jacobian row and the 29 sums of one accepted correspondence (w* = R p + t)
-  // (s / a^2 as a product with the reciprocal formed once per pass: the IEEE division sequence is ~28 instructions per
-  //  correspondence and evaluation; the quotient feeds the weights only -- the comparison s <= a^2 is on s itself)
+  // residual, robust weight, Jacobian row and the 29 sums of one accepted correspondence (w* = R p + t): plane_factor.h
+  // (the loss stays written out: TukeyLoss / tukey_rho of plane_factor.h state the same, but move 18 listings, profiles/plane_factor)
   const double inv_a2 = 1.0 / ep.a2, rho_out = (ep.variant == 0) ? ep.a2 / 6.0 : ep.a2 / 3.0;
   auto tail = [&](double px, double py, double pz, double wx, double wy, double wz, const double4& nd, double c) {
-    // (fused multiply-adds from here on: no thresholds downstream, see SO_FMA)
-    const double r = SO_FMA(nd.x, wx, SO_FMA(nd.y, wy, SO_FMA(nd.z, wz, nd.w)));  // lidarOptimization.cpp:61
+    const double r = plane_residual(nd.x, nd.y, nd.z, nd.w, wx, wy, wz);
     // ScaledLoss(TukeyLoss(a), c): rho, rho' [UPSTREAM ceres loss_function.cc]; corrector with rho''<=0
     const double s = r * r;
     double rho0, rho1;
@@ -2239,23 +2232,7 @@ __device__ __forceinline__ int eval_pass(int slot, int fuse_lm, const Pose& pose
     } else {
       rho0 = rho_out; rho1 = 0;
     }
-    const double w = c * rho1;
-    // J = [n^T, -n^T R [p]x] = [n^T, (p x R^T n)^T]  (lidarOptimization.cpp:68-74)
-    const double m0 = SO_FMA(R00, nd.x, SO_FMA(R10, nd.y, R20 * nd.z));
-    const double m1 = SO_FMA(R01, nd.x, SO_FMA(R11, nd.y, R21 * nd.z));
-    const double m2 = SO_FMA(R02, nd.x, SO_FMA(R12, nd.y, R22 * nd.z));
-    const double J[6] = {nd.x, nd.y, nd.z, SO_FMA(py, m2, -(pz * m1)), SO_FMA(pz, m0, -(px * m2)), SO_FMA(px, m1, -(py * m0))};
-    acc[0] = SO_FMA(0.5 * c, rho0, acc[0]);
-    acc[1] += 1.0;
-    const double wr = w * r;
-    int k = 8;
-#pragma unroll
-    for (int a = 0; a < 6; ++a) {
-      acc[2 + a] = SO_FMA(J[a], wr, acc[2 + a]);
-      const double wj = w * J[a];
-#pragma unroll
-      for (int b = a; b < 6; ++b) { acc[k] = SO_FMA(wj, J[b], acc[k]); ++k; }
-    }
+    plane_factor_add(R, px, py, pz, nd.x, nd.y, nd.z, c, r, rho0, c * rho1, acc);
   };
   // an accepted correspondence at the pass's pose: rotate, translate, sum
   auto at_pose = [&](double px, double py, double pz, const double4& nd, double c) {

@@ -43,7 +43,17 @@ SO_HD void quat_rotate(const T q[4], T vx, T vy, T vz, T& ox, T& oy, T& oz) {
   oz = vz + q[3] * uz + (q[0] * uy - q[1] * ux);
 }
 
-// a * b + c with one rounding.  Used where the restated arithmetic has no thresholds downstream (the LM controller's
+// Eigen::QuaternionBase::toRotationMatrix, row-major (the Jacobian's R(q), lidarOptimization.cpp:70; Twist.h:80-85)
+SO_HD void quat_to_matrix(const double q[4], double m[9]) {
+  const double tx = 2 * q[0], ty = 2 * q[1], tz = 2 * q[2];
+  const double twx = tx * q[3], twy = ty * q[3], twz = tz * q[3];
+  const double txx = tx * q[0], txy = ty * q[0], txz = tz * q[0], tyy = ty * q[1], tyz = tz * q[1], tzz = tz * q[2];
+  m[0] = 1 - (tyy + tzz); m[1] = txy - twz; m[2] = txz + twy;
+  m[3] = txy + twz; m[4] = 1 - (txx + tzz); m[5] = tyz - twx;
+  m[6] = txz - twy; m[7] = tyz + twx; m[8] = 1 - (txx + tyy);
+}
+
+// a * b + c with one rounding. Used where the restated arithmetic has no thresholds downstream (the LM controller's
 // linear algebra and the normal-equation sums): half the serial fp64 operations of the unfused form; the plane fit and
 // its gates keep the reference's unfused arithmetic (-ffp-contract=off).
 #define SO_FMA(a, b, c) __builtin_fma((a), (b), (c))

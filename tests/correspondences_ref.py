@@ -78,6 +78,21 @@ def expected(corrs, pose, plane_res, variant=0):
                 JtJ_abs=JtJ_abs, Jtr_abs=Jtr_abs, a2=a2)
 
 
+def check_fields_at(rec, pose, a2, variant, tag):
+    """residual and weight of every record (RECORD_DTYPE fields) against numpy from the record's own fields"""
+    if not len(rec):
+        return
+    r = residuals(rec["p"], rec["n"], rec["d"], pose)
+    _, w = loss(r, rec["coeff"], a2, variant)
+    r_bound = 64 * EPS * (np.linalg.norm(rec["p"].astype(np.float64), axis=1) + np.linalg.norm(pose[:3]) + np.abs(rec["d"]) + 1.0)
+    # (|dw/dr| <= 2 coeff |r| / a^2 is variant 0's; variant 1's slope is twice that, inside the 64 roundings budgeted per residual)
+    w_bound = r_bound * 2 * rec["coeff"] * np.abs(r) / a2 + 8 * EPS * rec["coeff"]
+    print(f"{tag}: max residual error / bound {np.max(np.abs(rec['residual'] - r) / r_bound):.3f}, max weight error / bound "
+          f"{np.max(np.abs(rec['weight'] - w) / np.maximum(w_bound, 1e-300)):.3f}")
+    assert np.all(np.abs(rec["residual"] - r) <= r_bound), tag
+    assert np.all(np.abs(rec["weight"] - w) <= w_bound), tag
+
+
 def sum_bound(n_terms, abs_sum):
     """two fp64 summations of N terms in different orders, plus a few dozen roundings per term"""
     return (2 * n_terms + 64) * EPS * abs_sum

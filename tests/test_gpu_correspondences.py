@@ -11,6 +11,7 @@ import numpy as np
 import pytest
 
 import correspondences_ref as cref
+import plane_factor_host as pfh
 from helpers import assert_same_bits, chain_deltas, run_staged_stream, scene_with_oracle
 from superodom_amd import synth
 
@@ -18,7 +19,6 @@ pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 DRIVER = os.path.join(ROOT, "adapter", "adapter_driver")
 TILE = 1024  # corr_kernels.h kCorrTile
-EPS = 2.0 ** -53
 
 
 def _ctx(oracle, make, scene="tiny", keep=True, **cfg):
@@ -73,7 +73,7 @@ def check_export(slam, scan, guess, st, plane_res, *, ocorrs=None, variant=0, ta
             print(f"{tag}: max |{f} - oracle| {err:.3e}")
             assert err <= 1e-10, (tag, f, err)
     for pose, name in ((np.array(info.pose_eval), "default pose"),):
-        _check_fields_at(rec, pose, a2, variant, f"{tag} {name}")
+        cref.check_fields_at(rec, pose, a2, variant, f"{tag} {name}")
     # costs: at the default pose the registration's final cost, at pose_fit its initial cost
     assert abs(info.cost - last.final_cost) <= 1e-9 * max(1.0, abs(last.final_cost)), (tag, info.cost, last.final_cost)
     _, _, _, info_fit = slam.correspondences(pose=np.array(info.pose_fit), cap=n)
@@ -93,21 +93,6 @@ def check_export(slam, scan, guess, st, plane_res, *, ocorrs=None, variant=0, ta
     if len(rec):
         assert slam.download_bytes(d_rec, 72 * len(rec)).tobytes() == first[0], (tag, "d_records_out")
     return rec, status, resid, info
-
-
-def _check_fields_at(rec, pose, a2, variant, tag):
-    """residual and weight of every record against numpy from the record's own fields"""
-    if not len(rec):
-        return
-    r = cref.residuals(rec["p"], rec["n"], rec["d"], pose)
-    _, w = cref.loss(r, rec["coeff"], a2, variant)
-    r_bound = 64 * EPS * (np.linalg.norm(rec["p"].astype(np.float64), axis=1) + np.linalg.norm(pose[:3]) + np.abs(rec["d"]) + 1.0)
-    # (|dw/dr| <= 2 coeff |r| / a^2 is variant 0's; variant 1's slope is twice that, inside the 64 roundings budgeted per residual)
-    w_bound = r_bound * 2 * rec["coeff"] * np.abs(r) / a2 + 8 * EPS * rec["coeff"]
-    print(f"{tag}: max residual error / bound {np.max(np.abs(rec['residual'] - r) / r_bound):.3f}, max weight error / bound "
-          f"{np.max(np.abs(rec['weight'] - w) / np.maximum(w_bound, 1e-300)):.3f}")
-    assert np.all(np.abs(rec["residual"] - r) <= r_bound), tag
-    assert np.all(np.abs(rec["weight"] - w) <= w_bound), tag
 
 
 _oracle_cache = {}
@@ -166,12 +151,41 @@ def test_composite_scan_and_both_tukey_branches(oracle, gpu_slam_factory, varian
     assert np.array_equal(status_up, status) and np.array_equal(rec_up["index"], rec["index"]) and bytes(info_up.pose_eval) == up.tobytes()
     for f in ("p", "n", "d", "coeff"):
         assert rec_up[f].tobytes() == rec[f].tobytes()
-    _check_fields_at(rec_up, up, a2, variant, f"composite v{variant} +1 m")
+    cref.check_fields_at(rec_up, up, a2, variant, f"composite v{variant} +1 m")
     term, _ = cref.loss(rec_up["residual"], rec_up["coeff"], a2, variant)
     assert abs(info_up.cost - term.sum()) <= cref.sum_bound(len(rec_up), np.abs(term).sum())
     ocost = oracle.evaluate(ocorrs, up, sc.plane_res, variant)[0]
     assert abs(info_up.cost - ocost) <= 1e-9 * max(1.0, abs(ocost))
     slam.close()
+
+
+# ---- residual and weight are the bits of the host build of plane_factor.h ------------------------------------------------------------
+@pytest.mark.parametrize("variant", [0, 1])
+def test_residual_and_weight_are_the_host_builds_bits(oracle, gpu_slam_factory, tiny, variant):
+    """The kernels and g++ (tests/plane_factor_host.py) compile the same text of plane_factor.h with -ffp-contract=off, and it uses only
+    + - * / and explicit fma, all correctly rounded on both sides: the export's residual and weight equal the host's to the bit -- at the
+    last evaluation's pose, with that pose passed as pose=, and at a displaced pose where both branches of the loss run.  Two tiles, the
+    second holding one point."""
+    sc, slam, _ = tiny if variant == 0 else _ctx(oracle, gpu_slam_factory, tukey_variant=variant, oracle_too=False)
+    scan = np.ascontiguousarray(sc.scan(0)[:TILE + 1], np.float32)
+    rc, pose, st = slam.register(scan, sc.guess(0))
+    assert rc == 0
+    a2 = cref.tukey_a2(sc.plane_res)
+    rec0, _, _, info = slam.correspondences(cap=len(scan))
+    assert info.valid == 1 and info.n_points == TILE + 1 and len(rec0) > 200
+    at_eval = np.array(info.pose_eval)
+    for tag, pose_arg, at in (("default pose", None, at_eval), ("pose=pose_eval", at_eval, at_eval), ("displaced", pfh.displaced(at_eval), None)):
+        rec, _, _, info_k = slam.correspondences(pose=pose_arg, cap=len(scan))
+        at = pose_arg if at is None else at
+        assert bytes(info_k.pose_eval) == at.tobytes() and np.array_equal(rec["index"], rec0["index"])
+        r, w, _, _ = pfh.evaluate(rec["p"], rec["n"], rec["d"], rec["coeff"], at, a2, variant)
+        if tag == "displaced":
+            outside = r * r > a2
+            assert outside.any() and (~outside).any(), "both branches of the loss must run"
+        assert rec["residual"].tobytes() == r.tobytes(), (variant, tag, "residual", int((rec["residual"] != r).sum()))
+        assert rec["weight"].tobytes() == w.tobytes(), (variant, tag, "weight", int((rec["weight"] != w).sum()))
+    if variant != 0:
+        slam.close()
 
 
 # ---- sampling: 254 bytes are present and the records skip them ---------------------------------------------------------------------
