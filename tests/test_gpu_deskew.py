@@ -7,19 +7,10 @@ import pytest
 from scipy.spatial.transform import Rotation as R
 
 import deskew_data as dd
+from deskew_data import close_in_ulps
 
 pytestmark = pytest.mark.gpu
 T0 = 1.7e9 + 0.25
-
-
-def close_in_ulps(a, b):
-    """(fraction of bit-identical values, largest difference in units of the float32 spacing at that magnitude)"""
-    a, b = a.reshape(-1), b.reshape(-1)
-    same = a.view(np.uint32) == b.view(np.uint32)
-    both_nan = np.isnan(a) & np.isnan(b)
-    d = np.abs(a.astype(np.float64) - b.astype(np.float64))[~(same | both_nan)]
-    ulp = np.spacing(np.maximum(np.abs(a), np.abs(b)).astype(np.float32)).astype(np.float64)[~(same | both_nan)]
-    return (same | both_nan).mean(), (d / ulp).max() if len(d) else 0.0
 
 
 @pytest.mark.parametrize("imu,stride,time_off,n_poses_rate", [(True, 32, 20, 200.0), (False, 32, 20, 200.0), (False, 16, 12, 50.0), (True, 32, 20, 8000.0)])

@@ -91,6 +91,25 @@ def test_pose_table_in_global_memory(gpu_slam_factory, sensor):
     assert _same(rec, want_rec) and _same(surf, want_surf)
 
 
+@pytest.mark.parametrize("axis", ["x", "z"])
+def test_lidar_mounted_half_a_turn_round(gpu_slam_factory, axis):
+    """T_i_l = 180 degrees about x / z under an IMU buffer: T_l_i * T_original_current of every point, and start * T_i_l, take one of
+    matrix_to_quat's hand-written branches (trace <= 0) in ingest_deskew_kernel's own inlined copy of deskew_point"""
+    slam = gpu_slam_factory()
+    buf, w, h, rs, _ = _sweep(fr.SENSOR_VELODYNE, seed=31)
+    layout = fr.layout_for(fr.SENSOR_VELODYNE, 1, 0.2, row_step=rs)
+    poses, til = dd.pose_buffer(T0, seed=32, translate=False, flip_signs=True), dd.half_turn_extrinsic(axis)
+    plain = fr.ingest(buf, w, h, layout)
+    assert dd.half_turn_census(plain, T0, poses, axis) > 20000
+    rec, surf, info = slam.extract_features(buf, w, h, layout, T0, poses, True, til)
+    want_rec, want_surf = _want(slam, buf, w, h, layout, poses, True, til)
+    assert _same(rec, want_rec), "cloud_nodistortion: the restated ingest + so_icp_deskew_scan, bit for bit"
+    assert info.n_surface == len(want_surf) > 0 and _same(surf, want_surf), "cloud_surface: count, order and bits"
+    _, dinfo = slam.deskew_scan(plain, 20, T0, poses, True, til)
+    assert info.n_clamped == dinfo.n_clamped == 0
+    assert list(info.q_w_original_l) == list(dinfo.q_w_original_l) and list(info.t_w_original_l) == list(dinfo.t_w_original_l)
+
+
 def test_knife_edges(gpu_slam_factory):
     """|d| one float either side of 1e-7, a norm equal to 0.2f * 0.2f, the precedence of the range gate, NaN neighbours, n = 0 1 2"""
     slam = gpu_slam_factory()

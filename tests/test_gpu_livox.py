@@ -90,6 +90,20 @@ def test_main_sweep_bit_for_bit(gpu_slam_factory, soicp, branch, step):
     assert np.array_equal(f[acc, 4], vals["reflectivity"][acc].astype(np.float32)) and np.array_equal(rec.view(np.uint32)[acc, 6], vals["line"][acc])
 
 
+@pytest.mark.parametrize("axis", ["x", "z"])
+def test_lidar_mounted_half_a_turn_round(gpu_slam_factory, soicp, axis):
+    """T_i_l = 180 degrees about x / z under an IMU buffer: T_l_i * T_original_current of every record, and start * T_i_l, take one of
+    matrix_to_quat's hand-written branches (trace <= 0) in livox_ingest_deskew_kernel's own inlined copy of deskew_point"""
+    slam = gpu_slam_factory()
+    vals = lr.gpu_sweep("cdr")
+    layout = soicp.livox_layout(1, 0.2, R_imu_laser_gravity=lr.R_TILT)
+    poses, til = dd.pose_buffer(T0, seed=33, translate=False, flip_signs=True), dd.half_turn_extrinsic(axis)
+    plain = lr.ingest(vals, np.array(layout.R_imu_laser_gravity[:]), layout.n_scans, lr.time_div)
+    assert dd.half_turn_census(plain, T0, poses, axis) > 2500
+    _, _, info = _run_and_compare(slam, vals, layout, poses, True, til, f"half a turn about {axis}")
+    assert info.n_clamped == 0
+
+
 def test_zero_records(gpu_slam_factory, soicp):
     """a rejected slot is the zero record before the de-skew, goes through the de-skew like any finite point, and is a sampling
     candidate: behind a point it is kept (|dx| > 1e-7), behind another zero record it is dropped"""

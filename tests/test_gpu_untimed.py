@@ -83,6 +83,23 @@ def test_sizes_around_the_tile_bit_for_bit(gpu_slam_factory, soicp, n):
     assert info.n_points < n or n <= 2
 
 
+@pytest.mark.parametrize("axis", ["x", "z"])
+def test_lidar_mounted_half_a_turn_round(gpu_slam_factory, soicp, axis):
+    """T_i_l = 180 degrees about x / z under an IMU buffer: T_l_i * T_original_current of every record, and start * T_i_l, take one of
+    matrix_to_quat's hand-written branches (trace <= 0) in untimed_ingest_deskew_kernel's own inlined copy of deskew_point.  The
+    sweep is the smallest that spans two tiles."""
+    slam = gpu_slam_factory()
+    vals = ur.gpu_sweep("n2049")
+    buf, w, h, rs = ur.payload(vals)
+    layout = soicp.untimed_layout(ur.XYZI, 16, rs, 16, 3, 0.2)
+    poses, til = dd.pose_buffer(T0, seed=34, translate=False, flip_signs=True), dd.half_turn_extrinsic(axis)
+    plain, _ = ur.ingest(vals["x"], vals["y"], vals["z"], vals["intensity"], 16)
+    assert dd.half_turn_census(plain, T0, poses, axis) > 1000
+    got = slam.extract_features_untimed(buf, w, h, layout, T0, poses, True, til)
+    _check(got, _want(slam, vals, 16, 3, 0.2, poses, True, til), f"half a turn about {axis}")
+    assert got[2].n_clamped == 0 and got[2].n_surface > 0
+
+
 def test_truncation_and_the_clamped_count(gpu_slam_factory, soicp):
     """the cut-off tail spans a tile boundary and holds would-be drops and would-be records (test_untimed_host.py); the pose buffer
     ends in the middle of the sweep, so the tail's points would all be clamped -- and must not be counted"""
