@@ -349,7 +349,9 @@ int so_icp_register_dev(so_icp_ctx *ctx, const void *d_scan_xyz, size_t n,
  * keep the batched solve resident falls back by itself (one workgroup per compute unit, then concurrent sequential
  * registrations on worker contexts that borrow this context's resident map); same bits.  d_scan_xyz != NULL
  * takes a scan already resident in HBM (so_icp_upload_scan), else scan_xyz is uploaded once.  Returns the number of
- * hypotheses that returned SO_ICP_OK (>= 0), or a negative error; rc_out[h] (nullable) = status of hypothesis h. */
+ * hypotheses that returned SO_ICP_OK (>= 0), or a negative error; rc_out[h] (nullable) = status of hypothesis h.
+ * so_icp_set_batch_priors (below) gives every hypothesis of the next call a pose prior of its own; that call consumes them, and a
+ * call whose n_hyp differs from theirs returns SO_ICP_E_INVALID and leaves them pending. */
 int so_icp_register_batch(so_icp_ctx *ctx, const float *scan_xyz, const void *d_scan_xyz, size_t n, size_t stride_bytes,
                           const double *poses_in, int n_hyp, double *poses_out, so_icp_stats *stats /* n_hyp, nullable */,
                           int32_t *rc_out /* n_hyp, nullable */);
@@ -793,8 +795,9 @@ int so_icp_pose_prior_sums(const so_icp_pose_prior *prior, const double pose[7],
  * prediction_source = 1 (LS.cpp:297) and SO_ICP_FLAG_POSE_PRIOR is set.  num_surf_from_scan stays the number of plane correspondences,
  * and an evaluation with none still ends the solve with termination 4 -- Ceres would solve the prior alone there, the reference returns
  * before it gets that far (LS.cpp:113-116).  so_icp_correspondences and so_icp_correspondence_sums keep reporting the planes only.
- * While a prior is pending so_icp_register_batch, so_icp_register_sequence, so_icp_localization_sequence and so_icp_match(_dev) return
- * SO_ICP_E_UNSUPPORTED and leave it pending.  prior == NULL withdraws a pending prior.
+ * While a prior is pending so_icp_register_batch, so_icp_register_sequence, so_icp_localization_sequence, so_icp_match(_dev) and
+ * so_icp_set_batch_priors return SO_ICP_E_UNSUPPORTED and leave it pending; this call is refused while the priors of a run or of a
+ * batch are pending.  prior == NULL withdraws a pending prior.
  * world_size > 1: SO_ICP_E_UNSUPPORTED; a host-only context: SO_ICP_E_HIP; a non-finite field or a T_meas quaternion of zero norm:
  * SO_ICP_E_INVALID.  Setting is host work only (the prior travels as an argument of that registration's solve launches); a context on
  * which no prior was ever set does nothing more than before in any entry. */
@@ -814,9 +817,9 @@ int so_icp_set_pose_prior(so_icp_ctx *ctx, const so_icp_pose_prior *prior /* NUL
  * with a prior reports like the single entry: costs, JtJ and Jtr include it, prediction_source = 1, SO_ICP_FLAG_POSE_PRIOR.
  * Both arrays are copied.  The next sequence call consumes the priors when it returns, whatever it returns; a call whose `count`
  * differs returns SO_ICP_E_INVALID before it touches anything and leaves them pending.  count == 0 or priors == NULL withdraws.
- * While the priors of a run are pending so_icp_register(_dev), so_icp_localization(_dev), so_icp_register_batch, so_icp_match(_dev)
- * and so_icp_set_pose_prior return SO_ICP_E_UNSUPPORTED and leave them pending; a pending single prior is refused by both sequence
- * entries as before, and by this call.  Validation as so_icp_set_pose_prior's, on the words a mode reads: a non-finite field or (GIVEN)
+ * While the priors of a run are pending so_icp_register(_dev), so_icp_localization(_dev), so_icp_register_batch, so_icp_match(_dev),
+ * so_icp_set_pose_prior and so_icp_set_batch_priors return SO_ICP_E_UNSUPPORTED and leave them pending; a pending single prior is
+ * refused by both sequence entries as before, and by this call, and so are the pending priors of a batch.  Validation as so_icp_set_pose_prior's, on the words a mode reads: a non-finite field or (GIVEN)
  * a T_meas quaternion of zero norm SO_ICP_E_INVALID, a mode above 2 SO_ICP_E_INVALID, world_size > 1 SO_ICP_E_UNSUPPORTED, a host-only
  * context SO_ICP_E_HIP.  Not in a run: the reference's uncertainty-scaled information (frame k's U would need frame k - 1's
  * uncertainty, which the host does not have when it enqueues a chained frame). */
@@ -825,6 +828,26 @@ int so_icp_set_pose_prior(so_icp_ctx *ctx, const so_icp_pose_prior *prior /* NUL
 #define SO_ICP_PRIOR_AT_GUESS 2
 int so_icp_set_sequence_priors(so_icp_ctx *ctx, int count, const so_icp_pose_prior *priors /* count */,
                                const uint8_t *modes /* count; NULL = all GIVEN */);
+
+/* One prior PER HYPOTHESIS of a batch: ONE-SHOT, for the next so_icp_register_batch call, inside its batched solve launches.  modes[h]:
+ *   NONE      hypothesis h carries no prior: bit for bit and flag for flag the hypothesis of a batch without priors
+ *   GIVEN     priors[h] as it stands
+ *   AT_GUESS  priors[h] with T_meas replaced by poses_in[h] of that batch call; priors[h].T_meas is not read
+ * With P_h = priors[h] (AT_GUESS: T_meas := poses_in[h]), hypothesis h of the batch is bit for bit so_icp_set_pose_prior(ctx, P_h) +
+ * so_icp_register from poses_in[h] on a context with the same map and history (`uncertainty` is carried over from the call before, as
+ * in every batch) -- on every path a batch can take: groups of more than 64, one workgroup per compute unit, chained rounds or not, a
+ * repeated group, concurrent registrations on worker contexts (SOICP_BATCH_MODE=lanes, an empty scan).  A hypothesis with a prior
+ * reports like the single entry: costs, JtJ and Jtr include it, prediction_source = 1, SO_ICP_FLAG_POSE_PRIOR; num_surf_from_scan counts
+ * the planes, and a pass with none ends with termination 4.  A batch whose priors are all NONE launches what a batch without launches.
+ * Both arrays are copied.  The next so_icp_register_batch takes the priors out of the context when it starts: they are gone when it
+ * returns, whatever it returns (too little map -- then no flag is set --, an error); a call whose n_hyp differs (n_hyp == 0 too)
+ * returns SO_ICP_E_INVALID before it touches anything and leaves them pending.  n_hyp == 0 or priors == NULL withdraws.
+ * While the priors of a batch are pending so_icp_register(_dev), so_icp_localization(_dev), so_icp_register_sequence,
+ * so_icp_localization_sequence, so_icp_match(_dev), so_icp_set_pose_prior and so_icp_set_sequence_priors return SO_ICP_E_UNSUPPORTED
+ * and leave them pending; this call is refused while a single prior or the priors of a run are pending.  Validation as
+ * so_icp_set_sequence_priors'.  Not in a batch: the reference's uncertainty-scaled information (the caller scales U). */
+int so_icp_set_batch_priors(so_icp_ctx *ctx, int n_hyp, const so_icp_pose_prior *priors /* n_hyp */,
+                            const uint8_t *modes /* n_hyp; NULL = all GIVEN */);
 
 /* -------- measurement ------------------------------------------------------------------------ */
 int so_icp_get_timing(so_icp_ctx *ctx, so_icp_timing *t);

@@ -266,7 +266,8 @@ EXPORTED = ["so_icp_default_config", "so_icp_create", "so_icp_destroy", "so_icp_
             "so_icp_debug_lm_script", "so_icp_set_cloud_intensity", "so_icp_prefilter_intensity",
             "so_icp_keep_correspondences", "so_icp_correspondences",
             "so_icp_match", "so_icp_match_dev", "so_icp_correspondence_sums",
-            "so_icp_pose_prior_from_information", "so_icp_pose_prior_sums", "so_icp_set_pose_prior", "so_icp_set_sequence_priors"]
+            "so_icp_pose_prior_from_information", "so_icp_pose_prior_sums", "so_icp_set_pose_prior", "so_icp_set_sequence_priors",
+            "so_icp_set_batch_priors"]
 SUMS_MAX_POSES = 64
 
 _lib = None
@@ -377,6 +378,7 @@ def load():
     L.so_icp_pose_prior_sums.argtypes = [C.POINTER(PosePrior), f64p, C.POINTER(Sums)]
     L.so_icp_set_pose_prior.argtypes = [vp, C.POINTER(PosePrior)]
     L.so_icp_set_sequence_priors.argtypes = [vp, C.c_int, C.POINTER(PosePrior), C.POINTER(C.c_uint8)]
+    L.so_icp_set_batch_priors.argtypes = [vp, C.c_int, C.POINTER(PosePrior), C.POINTER(C.c_uint8)]
     _lib = L
     return L
 
@@ -644,6 +646,19 @@ class LidarSlamGpu:
             assert len(modes) == len(priors)
             m = (C.c_uint8 * len(priors))(*[int(v) for v in modes])
         self._check(self.L.so_icp_set_sequence_priors(self.h, len(priors), arr, m))
+
+    def set_batch_priors(self, priors, modes=None):
+        """so_icp_set_batch_priors: one PosePrior per hypothesis of the next register_batch call, which consumes them; modes[h] in
+        PRIOR_NONE / PRIOR_GIVEN / PRIOR_AT_GUESS (None: all given; AT_GUESS: T_meas := poses_in[h] of that call).  priors None or
+        empty withdraws pending ones"""
+        if priors is None or len(priors) == 0:
+            self._check(self.L.so_icp_set_batch_priors(self.h, 0, None, None)); return
+        arr = (PosePrior * len(priors))(*priors)
+        m = None
+        if modes is not None:
+            assert len(modes) == len(priors)
+            m = (C.c_uint8 * len(priors))(*[int(v) for v in modes])
+        self._check(self.L.so_icp_set_batch_priors(self.h, len(priors), arr, m))
 
     def correspondence_sums(self, poses):
         """so_icp_correspondence_sums: the kept set's cost and normal equations at `poses` ([7] or [k, 7], k <= SUMS_MAX_POSES) -> an

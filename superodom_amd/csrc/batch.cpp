@@ -5,6 +5,8 @@
 // and runs its own LM controller (kernels.hip: solve_kernel<BATCH>) , one read-back of the state blocks }.  A hypothesis
 // is an independent registration: it leaves the rounds when its own termination rule fires (LidarSlam.cpp:141), and the
 // workgroups it held go to the others in the next round.  Results are bit-identical to so_icp_register per hypothesis.
+// so_icp_set_batch_priors: every hypothesis may carry a pose prior of its own -- a table of prior blocks copied in front of round 0,
+// read by solve_kernel_batch_prior, which a round launches only where a hypothesis of its list carries one (reg_plan.h).
 #include <hip/hip_runtime_api.h>
 
 #include <algorithm>
@@ -54,8 +56,22 @@ int batch_reserve(so_icp_ctx* c, uint32_t B, size_t n, uint32_t lg) {
   return SO_ICP_OK;
 }
 
+// so_icp_set_batch_priors: the table of prior blocks of a group (kernels.h: kBatchPriorStride) and its pinned source, for B hypotheses
+int batch_priors_reserve(so_icp_ctx* c, uint32_t B) {
+  so_icp_ctx::BatchBufs& b = c->batch;
+  if (B <= b.cap_prior_hyp) return SO_ICP_OK;
+  const uint32_t cap = std::max(B, b.cap_hyp);
+  if (b.h_priors) (void)hipHostFree(b.h_priors);
+  b.h_priors = nullptr; b.cap_prior_hyp = 0;
+  HIP_TRY(c, b.priors.reserve((size_t)cap * kBatchPriorStride * sizeof(double)));
+  HIP_TRY(c, hipHostMalloc(reinterpret_cast<void**>(&b.h_priors), (size_t)cap * kBatchPriorStride * sizeof(double)));
+  b.cap_prior_hyp = cap;
+  return SO_ICP_OK;
+}
+
+// `priors`: the priors of the whole batch (so_icp_set_batch_priors; nullptr: none), of which hypothesis h of this group is element base + h
 int register_batch_group(so_icp_ctx* c, const float* d_scan, size_t n, const double* poses_in, int B, double* poses_out, so_icp_stats* stats,
-                         int32_t* hyp_rc, const int pos[3], int count_5x5) {
+                         int32_t* hyp_rc, const int pos[3], int count_5x5, const RunPriors* priors, int base) {
   const auto t_begin = std::chrono::steady_clock::now();
   std::vector<so_icp_stats> local;
   if (!stats) { local.resize((size_t)B); stats = local.data(); }
@@ -82,6 +98,30 @@ int register_batch_group(so_icp_ctx* c, const float* d_scan, size_t n, const dou
   }
   HIP_TRY(c, hipMemcpyAsync(b.begin.p, b.h_begin, (size_t)B * sizeof(RegBeginArgs), hipMemcpyHostToDevice, s));
   HIP_TRY(c, hipMemcpyAsync(b.active.p, b.h_active, (size_t)B * 4, hipMemcpyHostToDevice, s));
+  // the hypotheses' priors: one block each, T_meas filled with the hypothesis' guess where its mode says so (the host knows every
+  // start pose of a batch); in the queue in front of round 0, so the solve launches read it with plain loads
+  std::vector<uint8_t> prior_modes;  // of this group; empty: no hypothesis of it carries a prior
+  if (priors) {
+    prior_modes.resize((size_t)B);
+    bool any = false;
+    for (int h = 0; h < B; ++h) any |= (prior_modes[(size_t)h] = (uint8_t)priors->mode(base + h)) != SO_ICP_PRIOR_NONE;
+    if (!any) prior_modes.clear();
+  }
+  if (!prior_modes.empty()) {
+    rc = batch_priors_reserve(c, (uint32_t)B);
+    if (rc) return rc;
+    std::memset(b.h_priors, 0, (size_t)B * kBatchPriorStride * sizeof(double));
+    for (int h = 0; h < B; ++h) {
+      double* blk = b.h_priors + (size_t)h * kBatchPriorStride;
+      PosePrior P;
+      if (!priors->frame_prior(base + h, poses_in + 7 * (size_t)h, P)) { blk[6] = 1.0; continue; }  // (mode word 0: nothing else of the block is read)
+      std::memcpy(blk, &P, sizeof(P));
+      const uint64_t mode_word = prior_modes[(size_t)h];
+      std::memcpy(blk + kBatchPriorModeWord, &mode_word, sizeof(mode_word));
+      stats[h].flags |= SO_ICP_FLAG_POSE_PRIOR;
+    }
+    HIP_TRY(c, hipMemcpyAsync(b.priors.p, b.h_priors, (size_t)B * kBatchPriorStride * sizeof(double), hipMemcpyHostToDevice, s));
+  }
   const float plane_res_now = map_plane_res(c);
   MatchParams mp = match_params(plane_res_now, c->ablate);
   mp.chunk_cap = b.bs;
@@ -91,7 +131,10 @@ int register_batch_group(so_icp_ctx* c, const float* d_scan, size_t n, const dou
   ep.n_queries = (uint32_t)n; ep.q_stride = 3;
   ep.timeout_ticks = 20000000ull;  // 200 ms: a pass of one hypothesis on a few workgroups lasts up to a millisecond
   const uint32_t v_grid = solve_grid((uint32_t)n, (uint32_t)c->n_cus);
-  const uint32_t resident = solve_batch_resident_blocks((uint32_t)c->n_cus, c->batch_degrade >= 1 ? 1 : 0);
+  const uint32_t resident_plain = solve_batch_resident_blocks((uint32_t)c->n_cus, c->batch_degrade >= 1 ? 1 : 0);
+  // (a round whose list holds a prior launches solve_kernel_batch_prior: ITS occupancy then says how many workgroups are resident together)
+  const uint32_t resident_prior = priors ? solve_batch_resident_blocks((uint32_t)c->n_cus, c->batch_degrade >= 1 ? 1 : 0, true) : resident_plain;
+  const uint32_t resident = std::min(resident_plain, resident_prior);
   if (resident < (uint32_t)B) {  // (the driver below sizes its groups by the resident workgroups; this is the second line of defence)
     c->err = "so_icp_register_batch: fewer resident solve workgroups (" + std::to_string(resident) + ") than hypotheses in the group (" + std::to_string(B) + ")";
     return kRetryWithoutPersistentSolve;  // degrade (fewer workgroups per hypothesis is not possible: one each) -> concurrent sequential registrations
@@ -125,8 +168,10 @@ int register_batch_group(so_icp_ctx* c, const float* d_scan, size_t n, const dou
       HIP_TRY(c, hipMemcpyAsync(b.active.p, b.h_active, (size_t)n_act * 4, hipMemcpyHostToDevice, s));
     }
     // workgroups per hypothesis: the resident grid split evenly (a power of two, never more than the grid they stand in for)
+    const bool with_prior = batch_solve_kernel(prior_modes.empty() ? nullptr : prior_modes.data(), act.data(), n_act) == kBatchSolvePrior;
+    const uint32_t resident_now = with_prior ? resident_prior : resident_plain;
     uint32_t G = 1;
-    while (2u * G * n_act <= resident && 2u * G <= v_grid) G *= 2u;
+    while (2u * G * n_act <= resident_now && 2u * G <= v_grid) G *= 2u;
     bv.wg_per_hyp = G;
     const int first = it;
     for (;;) {
@@ -138,7 +183,7 @@ int register_batch_group(so_icp_ctx* c, const float* d_scan, size_t n, const dou
       EvalParams ep_it = ep;
       ep_it.epoch_base = (++c->solve_launches) << 5;
       launch_solve_batch(lm_max, d_scan, d_scan + 1, d_scan + 2, corr, ds, ep_it, b.partials.as<double>(), b.sync.as<uint32_t>(), b.hist.as<int32_t>(),
-                         c->view, b.nbr5.as<uint32_t>(), mp, bv, n_act, s);
+                         c->view, b.nbr5.as<uint32_t>(), mp, bv, n_act, s, with_prior ? b.priors.as<double>() : nullptr);
       HIP_TRY(c, hipGetLastError());
       ++it;
       const bool chain = c->batch_chain && it < max_outer && it - 1 < so_icp_ctx::kBatchRoundsTracked && (it - 1 == 0 || c->batch_survivors[it - 1] >= 0.75f);
@@ -177,6 +222,7 @@ int register_batch_group(so_icp_ctx* c, const float* d_scan, size_t n, const dou
   for (int h = 0; h < B; ++h) {
     fill_result(c, b.h_states[h], poses_in + 7 * (size_t)h, stats + h, poses_out + 7 * (size_t)h, false);
     stats[h].time_elapsed_ms = ms;  // (of the whole group: the hypotheses advance together)
+    if (!prior_modes.empty() && prior_modes[(size_t)h] != SO_ICP_PRIOR_NONE) stats[h].prediction_source = 1;  // addAbsolutePoseConstraints, LidarSlam.cpp:297
   }
   return SO_ICP_OK;
 }
@@ -189,7 +235,13 @@ int so_icp_register_batch(so_icp_ctx* c, const float* xyz, const void* d_scan, s
                           int n_hyp, double* poses_out, so_icp_stats* stats, int32_t* rc_out) {
   if (!c || !poses_in || !poses_out || n_hyp < 0 || (!xyz && !d_scan && n)) return SO_ICP_E_INVALID;
   NEED_DEVICE(c);
-  if (const int rc = refuse_pending_prior(c, "so_icp_register_batch")) return rc;
+  if (const int rc = refuse_pending_prior(c, "so_icp_register_batch", false, true)) return rc;
+  if (!RunPriors::batch_count_matches(c, n_hyp)) return fail(c, SO_ICP_E_INVALID, "so_icp_register_batch: n_hyp differs from that of the pending so_icp_set_batch_priors call");
+  // so_icp_set_batch_priors: taken out of the context here, so they are consumed whatever this call returns; the group repeats and
+  // the fall-back to concurrent registrations below keep them
+  RunPriors batch_priors;
+  batch_priors.take(c->batch_priors);
+  const RunPriors* priors = batch_priors.any() ? &batch_priors : nullptr;  // (all NONE: the batch without priors, launch for launch)
   HIP_TRY(c, hipSetDevice(c->cfg.device_id));
   if (c->cfg.world_size != 1)  // (hypotheses are independent: replicate the map and split THEM over the ranks -- bench.py's batch64)
     return fail(c, SO_ICP_E_UNSUPPORTED, "so_icp_register_batch needs the whole map on one device (world_size == 1)");
@@ -215,11 +267,13 @@ int so_icp_register_batch(so_icp_ctx* c, const float* xyz, const void* d_scan, s
       // a group never holds more hypotheses than solve workgroups can be resident together (one workgroup per hypothesis at
       // least): on a device with few compute units -- SOICP_SOLVE_WORKGROUPS, a partitioned device, one workgroup per unit after
       // a failed co-residency wait -- the batch goes through in smaller groups instead of failing
-      const int cap = (int)std::min<uint32_t>((uint32_t)kBatchMaxConcurrent, solve_batch_resident_blocks((uint32_t)c->n_cus, c->batch_degrade >= 1 ? 1 : 0));
+      uint32_t resident = solve_batch_resident_blocks((uint32_t)c->n_cus, c->batch_degrade >= 1 ? 1 : 0);
+      if (priors) resident = std::min(resident, solve_batch_resident_blocks((uint32_t)c->n_cus, c->batch_degrade >= 1 ? 1 : 0, true));
+      const int cap = (int)std::min<uint32_t>((uint32_t)kBatchMaxConcurrent, resident);
       if (cap < 1) { c->batch_degrade = 2; break; }
       const int B = std::min(cap, n_hyp - base);
       rc = register_batch_group(c, scan, n, poses_in + 7 * (size_t)base, B, poses_out + 7 * (size_t)base, stats ? stats + base : nullptr,
-                                hrc.data() + base, pos, count);
+                                hrc.data() + base, pos, count, priors, base);
       // A batched solve launch needs its workgroups resident together.  If the device could not provide that (shared with another
       // process), the group is repeated with one workgroup per compute unit; if that fails too the context falls back to
       // concurrent sequential registrations (below) for the rest of its life.  so_icp_last_error keeps the notice.
@@ -270,7 +324,11 @@ int so_icp_register_batch(so_icp_ctx* c, const float* xyz, const void* d_scan, s
     if (hipSetDevice(c->cfg.device_id) != hipSuccess) { lane_rc[l] = SO_ICP_E_HIP; return; }
     for (int h = l; h < n_hyp; h += lanes) {
       so_icp_stats local;
+      // P_h becomes the lane context's single prior for this registration (RunPriors::arm: what so_icp_set_pose_prior does, without
+      // its refusals); a lane runs one launch per evaluation, eval_kernel_prior
+      if (priors) priors->arm(w, h, poses_in + 7 * (size_t)h);
       const int r = register_core(w, scan, n, poses_in + 7 * (size_t)h, poses_out + 7 * (size_t)h, stats ? stats + h : &local);
+      w->prior_pending = false;
       hyp_rc[h] = r;
       if (r < 0) { lane_rc[l] = r; return; }
     }

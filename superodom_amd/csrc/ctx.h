@@ -10,7 +10,8 @@
 //   cloud_steps.cpp       so_icp_deskew_scan(_dev), so_icp_transform_cloud, so_icp_download_scan
 //   correspondences.cpp   so_icp_keep_correspondences, so_icp_correspondences: the last registration's correspondence set;
 //                         so_icp_match(_dev), so_icp_correspondence_sums: the set formed at a pose of the caller's, its sums on the device
-//   pose_prior.cpp        so_icp_pose_prior_from_information, so_icp_pose_prior_sums, so_icp_set_pose_prior, so_icp_set_sequence_priors
+//   pose_prior.cpp        so_icp_pose_prior_from_information, so_icp_pose_prior_sums, so_icp_set_pose_prior, so_icp_set_sequence_priors,
+//                         so_icp_set_batch_priors
 //   multi_gpu.cpp         RCCL, in-process groups, peer exchange, shard helpers
 //   localization_sequence.cpp, feature_extraction.cpp
 #pragma once
@@ -189,7 +190,10 @@ struct so_icp_ctx {
     std::vector<PosePrior> priors;
     std::vector<uint8_t> modes;
   } run_priors;
-  hipStream_t pf_stream = nullptr;    // the pre-filter's own queue: the next frame's upload + VoxelGrid run BESIDE the map insert the previous
+  // so_icp_set_batch_priors: one prior and one mode per hypothesis of the NEXT so_icp_register_batch call (one-shot: taken out of the
+  // context when that call starts)
+  RunPriors batch_priors;
+  hipStream_t pf_stream = nullptr;   // the pre-filter's own queue: the next frame's upload + VoxelGrid run BESIDE the map insert the previous
   // Seam B scratch
   DevBuf d_q, d_nbr, d_d2, d_idx, d_found, d_fblist;
   // persistent LidarSLAM state
@@ -205,13 +209,18 @@ struct so_icp_ctx {
     bool tables_clean = false;
     DevBuf states, begin, active, qslot, qrank, binned, chunks, status, nbr5, nd, coeff, bin_key, bin_cnt, bin_off, partials, sync, hist;
     DevState* h_states = nullptr; RegBeginArgs* h_begin = nullptr; uint32_t* h_active = nullptr;  // pinned
+    // so_icp_set_batch_priors: the table of per-hypothesis prior blocks (kBatchPriorStride doubles each, kernels.h) and its pinned
+    // source; reserved by the first batch that carries a prior, never by one that does not
+    DevBuf priors; double* h_priors = nullptr; uint32_t cap_prior_hyp = 0;
     void release() {
       for (DevBuf* b : {&states, &begin, &active, &qslot, &qrank, &binned, &chunks, &status, &nbr5, &nd, &coeff, &bin_key, &bin_cnt,
-                        &bin_off, &partials, &sync, &hist}) b->release();
+                        &bin_off, &partials, &sync, &hist, &priors}) b->release();
       if (h_states) (void)hipHostFree(h_states);
       if (h_begin) (void)hipHostFree(h_begin);
       if (h_active) (void)hipHostFree(h_active);
-      h_states = nullptr; h_begin = nullptr; h_active = nullptr; cap_hyp = 0; bs = 0; table_log2 = 0; tables_clean = false;
+      if (h_priors) (void)hipHostFree(h_priors);
+      h_states = nullptr; h_begin = nullptr; h_active = nullptr; h_priors = nullptr; cap_hyp = 0; bs = 0; table_log2 = 0; tables_clean = false;
+      cap_prior_hyp = 0;
     }
   } batch;
   int batch_degrade = 0;  // 0: two solve workgroups per compute unit, 1: one (after a batched solve that was not co-resident, or
@@ -349,16 +358,26 @@ inline int fail(so_icp_ctx* c, int code, const std::string& msg) { c->err = msg;
 struct PriorOneShot { so_icp_ctx* c; ~PriorOneShot() { c->prior_pending = false; } };
 // so_icp_set_sequence_priors: the priors of a run go into the next so_icp_register_sequence / so_icp_localization_sequence call
 // (`sequence_entry`); every other entry that could meet them refuses and leaves them pending
-inline int refuse_pending_run_priors(so_icp_ctx* c, const char* entry) {
-  return c->run_priors.pending ? fail(c, SO_ICP_E_UNSUPPORTED, std::string(entry) + ": the priors of a run are pending (so_icp_set_sequence_priors); they go into "
-                                                               "so_icp_register_sequence or so_icp_localization_sequence -- withdraw them with "
-                                                               "so_icp_set_sequence_priors(ctx, 0, NULL, NULL) first") : SO_ICP_OK;
+// so_icp_set_batch_priors: the priors of a batch go into the next so_icp_register_batch call (`batch_entry` below, and the setter itself);
+// every other entry that could meet them refuses and leaves them pending
+inline int refuse_pending_batch_priors(so_icp_ctx* c, const char* entry) {
+  return c->batch_priors.pending ? fail(c, SO_ICP_E_UNSUPPORTED, std::string(entry) + ": the priors of a batch are pending (so_icp_set_batch_priors); they go into "
+                                                                 "so_icp_register_batch -- withdraw them with so_icp_set_batch_priors(ctx, 0, NULL, NULL) first")
+                                 : SO_ICP_OK;
 }
-inline int refuse_pending_prior(so_icp_ctx* c, const char* entry, bool sequence_entry = false) {
+inline int refuse_pending_run_priors(so_icp_ctx* c, const char* entry, bool batch_entry = false) {
+  if (c->run_priors.pending)
+    return fail(c, SO_ICP_E_UNSUPPORTED, std::string(entry) + ": the priors of a run are pending (so_icp_set_sequence_priors); they go into "
+                                         "so_icp_register_sequence or so_icp_localization_sequence -- withdraw them with "
+                                         "so_icp_set_sequence_priors(ctx, 0, NULL, NULL) first");
+  return batch_entry ? SO_ICP_OK : refuse_pending_batch_priors(c, entry);
+}
+inline int refuse_pending_prior(so_icp_ctx* c, const char* entry, bool sequence_entry = false, bool batch_entry = false) {
   if (c->prior_pending)
     return fail(c, SO_ICP_E_UNSUPPORTED, std::string(entry) + ": a pose prior is pending (so_icp_set_pose_prior); it goes into so_icp_register(_dev) "
                                          "or so_icp_localization(_dev) -- withdraw it with so_icp_set_pose_prior(ctx, NULL) first");
-  return sequence_entry ? SO_ICP_OK : refuse_pending_run_priors(c, entry);
+  if (sequence_entry) return batch_entry ? SO_ICP_OK : refuse_pending_batch_priors(c, entry);
+  return refuse_pending_run_priors(c, entry, batch_entry);
 }
 // The priors of one sequence call, taken out of the context when the call starts (so the per-frame entries it runs do not meet them,
 // and they are consumed whatever the call returns).  A call of another length leaves them where they are (count_matches).
@@ -366,11 +385,15 @@ struct RunPriors {
   std::vector<PosePrior> priors;
   std::vector<uint8_t> modes;
   static bool count_matches(const so_icp_ctx* c, int count) { return !c->run_priors.pending || (size_t)count == c->run_priors.priors.size(); }
-  void take(so_icp_ctx* c) {
-    if (!c->run_priors.pending) return;
-    priors.swap(c->run_priors.priors); modes.swap(c->run_priors.modes);
-    c->run_priors = so_icp_ctx::RunPriors{};
+  void take(so_icp_ctx::RunPriors& from) {
+    if (!from.pending) return;
+    priors.swap(from.priors); modes.swap(from.modes);
+    from = so_icp_ctx::RunPriors{};
   }
+  void take(so_icp_ctx* c) { take(c->run_priors); }
+  // so_icp_set_batch_priors keeps its priors in the same form: element k is hypothesis k, its guess poses_in[k]
+  static bool batch_count_matches(const so_icp_ctx* c, int n_hyp) { return !c->batch_priors.pending || (size_t)n_hyp == c->batch_priors.priors.size(); }
+  bool any() const { for (uint8_t m : modes) if (m != SO_ICP_PRIOR_NONE) return true; return false; }
   int mode(int k) const { return (size_t)k < modes.size() ? modes[(size_t)k] : SO_ICP_PRIOR_NONE; }
   // P_k: priors[k], with T_meas = the frame's guess where the mode says so; false: frame k carries no prior
   bool frame_prior(int k, const double guess[7], PosePrior& out) const {

@@ -363,7 +363,9 @@ void plan_registration(const so_icp_ctx* c, RegPlan& p, const float* d_scan, siz
   // deferred report: possible when the host always has the next k-NN launch in the queue before it waits for a report
   p.defer_reports = p.persistent && p.direct_rb && c->speculate;
   // so_icp_set_pose_prior: the PRIOR instantiations of the solve / evaluation kernels add it to every evaluation's sums
-  p.prior = carries_pose_prior(c->prior_pending, own, c->cfg.world_size, c->match_only) && !p.exchange;
+  // (a lane of so_icp_register_batch: its hypothesis' prior, armed by the batch itself -- so_icp_set_batch_priors; no public entry
+  //  leaves a prior pending on a context in batch mode)
+  p.prior = carries_pose_prior(c->prior_pending, own || c->batch_mode, c->cfg.world_size, c->match_only) && !p.exchange;
   p.flags = (p.query_waves ? SO_ICP_FLAG_QUERY_WAVES : 0u) | (p.pb ? SO_ICP_FLAG_BINNED_AHEAD : 0u) | (p.persistent ? 0u : SO_ICP_FLAG_PER_EVAL_LAUNCHES) |
             (p.prior ? SO_ICP_FLAG_POSE_PRIOR : 0u);
 }

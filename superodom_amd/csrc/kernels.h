@@ -243,12 +243,21 @@ void launch_solve(int lm_max, const float* spx, const float* spy, const float* s
 // workgroups of the single-registration solve launch for a scan of n_upper queries (the grid a batch stands in for)
 uint32_t solve_grid(uint32_t n_upper, uint32_t max_blocks);
 // workgroups of the batched solve launch that are certainly resident together on n_cus compute units (occupancy query of the
-// BATCH instantiation, at most two per compute unit; wg_per_cu > 0 overrides the per-CU number downwards)
-uint32_t solve_batch_resident_blocks(uint32_t n_cus, int wg_per_cu);
-// the solves of the hypotheses bv.active[0 .. n_hyp) in one launch of n_hyp * bv.wg_per_hyp workgroups (all resident)
+// BATCH instantiation -- with_priors: of solve_kernel_batch_prior, the kernel a group with a prior launches --, at most two per
+// compute unit; wg_per_cu > 0 overrides the per-CU number downwards)
+uint32_t solve_batch_resident_blocks(uint32_t n_cus, int wg_per_cu, bool with_priors = false);
+// so_icp_set_batch_priors: one block of kBatchPriorStride doubles per hypothesis of a group -- the 55 words of PosePrior (T_meas already
+// the hypothesis' guess where its mode says so), then the mode word (its low 32 bits: SO_ICP_PRIOR_*, 0 = the hypothesis carries none)
+constexpr int kBatchPriorStride = 64, kBatchPriorModeWord = kPosePriorWords;
+static_assert(kBatchPriorModeWord < kBatchPriorStride, "a prior block holds PosePrior and its mode word");
+// the solves of the hypotheses bv.active[0 .. n_hyp) in one launch of n_hyp * bv.wg_per_hyp workgroups (all resident).
+// d_prior_table: nullptr -- solve_kernel<PROF, true>, the launch of a batch without priors --, else the device table of prior blocks,
+// indexed like `st` by the hypothesis: solve_kernel_batch_prior, whose last argument it is (the caller passes it only where a
+// hypothesis of the list carries a prior: batch_solve_kernel, reg_plan.h)
 void launch_solve_batch(int lm_max, const float* spx, const float* spy, const float* spz, const CorrBuffers& corr, DevState* st,
                         const EvalParams& ep, double* d_partials, uint32_t* d_ticket, int32_t* d_hist, const DevMapView& map,
-                        const uint32_t* d_nbr5, const MatchParams& mp, const BatchView& bv, uint32_t n_hyp, hipStream_t s);
+                        const uint32_t* d_nbr5, const MatchParams& mp, const BatchView& bv, uint32_t n_hyp, hipStream_t s,
+                        const double* d_prior_table = nullptr);
 void launch_lm_step(int slot, DevState* st, const LmSums* d_sums, int32_t* d_hist, const EvalParams& ep, hipStream_t s);
 // test aid (so_icp_debug_lm_script): a script of sums for the LM controller, and what the controller left after every entry
 // (device mirrors of so_icp_lm_script_entry / so_icp_lm_script_step)

@@ -1994,6 +1994,9 @@ __device__ __forceinline__ double reduce_records(double (*red)[kRedStride], doub
 #ifndef SO_PRIOR_OVERLAP
 #define SO_PRIOR_OVERLAP 1  // persistent launch: prior_prepare runs in front of the wait for the pass's records (0: behind it)
 #endif
+#ifndef SO_BATCH_PRIOR_OVERLAP
+#define SO_BATCH_PRIOR_OVERLAP 0  // solve_kernel_batch_prior: 0 prepares behind the wait for the records, 1 in front of it (the same registers and scratch either way, profiles/batch_priors)
+#endif
 static_assert(kNAcc == kPriorSumWords, "one thread per word of the prior's contribution");
 __device__ __forceinline__ void prior_prepare(const double* P, const Pose& pose, int word, PosePriorPart& part) {
   double p7[7];
@@ -2175,8 +2178,11 @@ struct WgSpan { uint32_t vb0, vb1, V; bool ctl; };
 //         none of its index arithmetic and arguments
 // PRIOR : the registration carries a pose prior (single device, not BATCH): the controller's workgroup adds it -- the 55 doubles at
 //         `prior` -- to the pass's sums.  kPriorAtGuess (2, PERSIST only): T_meas is not the prior's own but the seven words at
-//         `prior_tm` (the frame's guess, see solve_kernel_prior_at_guess)
-constexpr int kPriorAtGuess = 2;
+//         `prior_tm` (the frame's guess, see solve_kernel_prior_at_guess).  kPriorBatch (3, BATCH only): `prior` is the hypothesis'
+//         block of the prior table in memory (kBatchPriorStride doubles, solve_kernel_batch_prior); its mode word says whether the
+//         hypothesis carries a prior at all, and the controller's wavefront prepares behind the wait for the records -- the launch is
+//         at the register cap, and a pass of a hypothesis on a few workgroups is long against the 55 loads
+constexpr int kPriorAtGuess = 2, kPriorBatch = 3;
 template <bool FIT, bool PERSIST = false, bool PROF = false, bool BATCH = false, bool PEER = false, int PRIOR = 0>
 __device__ __forceinline__ int eval_pass(int slot, int fuse_lm, const Pose& pose, const float* __restrict__ spx,
                                          const float* __restrict__ spy, const float* __restrict__ spz,
@@ -2199,7 +2205,8 @@ __device__ __forceinline__ int eval_pass(int slot, int fuse_lm, const Pose& pose
   int32_t* lh = sh.lh;
   const int tid = threadIdx.x;
   static_assert(!BATCH || PERSIST, "batched hypotheses run in the persistent solve launch");
-  static_assert(!PRIOR || (!BATCH && !PEER), "the pose prior belongs to the single registration on one device");
+  static_assert(!PRIOR || !PEER, "the pose prior belongs to one device");
+  static_assert(BATCH == (PRIOR == kPriorBatch) || !PRIOR, "a batch reads its priors from the table in memory, a single registration from the launch's argument");
   static_assert(PRIOR != kPriorAtGuess || PERSIST, "the prior at the guess belongs to the persistent solve");
   const int abl = PROF ? ep.ablate : 0;
   const bool stamp = PROF && (abl & 128) != 0;
@@ -2415,7 +2422,13 @@ __device__ __forceinline__ int eval_pass(int slot, int fuse_lm, const Pose& pose
     const int g = poller ? tid / kNAcc : 0, a = poller ? tid - g * kNAcc : 0;
     const u4v* base = rec + (poller ? tid : 0);
     [[maybe_unused]] PosePriorPart prior_part;
-    if constexpr (PRIOR != 0 && SO_PRIOR_OVERLAP != 0) {  // the pass's pose is known: everything of the prior but the row scale, beside the records' way here
+    // kPriorBatch: the hypothesis' mode word, the same for the whole workgroup (the table was copied in front of the batch's first launch)
+    [[maybe_unused]] bool prior_on = true;
+    if constexpr (PRIOR == kPriorBatch) prior_on = reinterpret_cast<const uint32_t*>(prior + kBatchPriorModeWord)[0] != 0u;
+    if constexpr (PRIOR == kPriorBatch && SO_BATCH_PRIOR_OVERLAP != 0) {
+      if (prior_on && tid < kNAcc) prior_prepare(prior, pose, tid, prior_part);
+    }
+    if constexpr (PRIOR != 0 && PRIOR != kPriorBatch && SO_PRIOR_OVERLAP != 0) {  // the pass's pose is known: everything of the prior but the row scale, beside the records' way here
       if constexpr (PRIOR == kPriorAtGuess) {
         if (tid < kNAcc) prior_prepare_at(prior_tm, prior, pose, tid, prior_part);
       } else {
@@ -2504,7 +2517,12 @@ __device__ __forceinline__ int eval_pass(int slot, int fuse_lm, const Pose& pose
       double tot = 0;
 #pragma unroll
       for (int cc8 = 0; cc8 < 8; ++cc8) tot += part[cc8][tid];
-      if constexpr (PRIOR != 0) {
+      if constexpr (PRIOR == kPriorBatch) {
+        if (prior_on) {  // (workgroup-uniform: a hypothesis without a prior adds nothing, and reads nothing of its block but the mode word)
+          if (SO_BATCH_PRIOR_OVERLAP == 0) prior_prepare(prior, pose, tid, prior_part);
+          tot = prior_added(prior_part, tot, tid);
+        }
+      } else if constexpr (PRIOR != 0) {
         if (SO_PRIOR_OVERLAP == 0) {
           if constexpr (PRIOR == kPriorAtGuess) prior_prepare_at(prior_tm, prior, pose, tid, prior_part);
           else prior_prepare(prior, pose, tid, prior_part);
@@ -2696,6 +2714,29 @@ __global__ __launch_bounds__(256, 1) void solve_kernel_prior_at_guess(int lm_max
 #include "solve_kernel_body.inc"
 #undef SO_BODY_KERNEL
 #undef SO_BODY_PRIOR
+#undef SO_BODY_PRIOR_WORDS
+}
+// solve_kernel<PROF, true> for a batch whose hypotheses carry pose priors (so_icp_set_batch_priors): the controller's workgroup of a
+// hypothesis adds that hypothesis' prior -- its block of `prior_table`, device memory copied in front of the batch's first launch: plain
+// loads, one lane per word of the sums -- to every pass's sums, as solve_kernel_prior does for the single registration; a hypothesis
+// whose mode word is 0 runs the plain hypothesis.  The table is the LAST argument and not a member of BatchView, which every batched
+// kernel takes: those keep their arguments and their code.
+template <bool PROF>
+__global__ __launch_bounds__(256, 2) void solve_kernel_batch_prior(int lm_max, const float* __restrict__ spx, const float* __restrict__ spy,
+                                                    const float* __restrict__ spz, CorrBuffers corr, DevState* __restrict__ st,
+                                                    EvalParams ep, double* __restrict__ partials, uint32_t* __restrict__ ticket,
+                                                    int32_t* __restrict__ hist, LmSums* __restrict__ out,
+                                                    const float4* __restrict__ mpts, const uint32_t* __restrict__ nbr5,
+                                                    MatchParams mp, BatchView bv, const double* __restrict__ prior_table) {
+  constexpr bool BATCH = true, PEER = false;
+#define SO_BODY_KERNEL solve_kernel_batch_prior<PROF>
+#define SO_BODY_PRIOR kPriorBatch
+#define SO_BODY_PRIOR_TABLE prior_table
+#define SO_BODY_PRIOR_WORDS prior_block
+#include "solve_kernel_body.inc"
+#undef SO_BODY_KERNEL
+#undef SO_BODY_PRIOR
+#undef SO_BODY_PRIOR_TABLE
 #undef SO_BODY_PRIOR_WORDS
 }
 
@@ -2981,18 +3022,26 @@ void launch_solve(int lm_max, const float* spx, const float* spy, const float* s
   }
   hipLaunchKernelGGL(k, dim3(blocks), dim3(256), 0, s, lm_max, spx, spy, spz, corr, st, ep, partials, ticket, hist, sums, map.pts, nbr5, mp, kNoBatch);
 }
-uint32_t solve_batch_resident_blocks(uint32_t n_cus, int wg_per_cu) {
+uint32_t solve_batch_resident_blocks(uint32_t n_cus, int wg_per_cu, bool with_priors) {
   int nb = 0;
-  if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, solve_kernel<false, true>, 256, 0) != hipSuccess || nb < 1) { (void)hipGetLastError(); nb = 1; }
+  const hipError_t e = with_priors ? hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, solve_kernel_batch_prior<false>, 256, 0)
+                                   : hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, solve_kernel<false, true>, 256, 0);
+  if (e != hipSuccess || nb < 1) { (void)hipGetLastError(); nb = 1; }
   if (nb > 2) nb = 2;  // (registers: two wavefronts per SIMD; LDS: two 66 KB workgroups)
   if (wg_per_cu >= 1 && wg_per_cu < nb) nb = wg_per_cu;
   return (uint32_t)nb * n_cus;
 }
 void launch_solve_batch(int lm_max, const float* spx, const float* spy, const float* spz, const CorrBuffers& corr, DevState* st,
                         const EvalParams& ep, double* partials, uint32_t* ticket, int32_t* hist, const DevMapView& map,
-                        const uint32_t* nbr5, const MatchParams& mp, const BatchView& bv, uint32_t n_hyp, hipStream_t s) {
+                        const uint32_t* nbr5, const MatchParams& mp, const BatchView& bv, uint32_t n_hyp, hipStream_t s, const double* prior_table) {
   if (!n_hyp) return;
   const bool prof = ep.ablate != 0 || mp.ablate != 0;
+  if (prior_table) {  // (a hypothesis of the list carries a prior: the table travels as the launch's last argument)
+    auto* kp = prof ? solve_kernel_batch_prior<true> : solve_kernel_batch_prior<false>;
+    hipLaunchKernelGGL(kp, dim3(n_hyp * bv.wg_per_hyp), dim3(256), 0, s, lm_max, spx, spy, spz, corr, st, ep, partials, ticket, hist, (LmSums*)nullptr, map.pts,
+                       nbr5, mp, bv, prior_table);
+    return;
+  }
   auto* k = prof ? solve_kernel<true, true> : solve_kernel<false, true>;
   hipLaunchKernelGGL(k, dim3(n_hyp * bv.wg_per_hyp), dim3(256), 0, s, lm_max, spx, spy, spz, corr, st, ep, partials, ticket, hist, (LmSums*)nullptr, map.pts,
                      nbr5, mp, bv);

@@ -28,6 +28,16 @@ enum SolveKernelKind { kSolvePlain = 0, kSolvePrior = 1, kSolvePriorAtGuess = 2 
 inline SolveKernelKind sequence_solve_kernel(int mode, bool chained) {
   return mode == 0 ? kSolvePlain : ((mode == 2 && chained) ? kSolvePriorAtGuess : kSolvePrior);
 }
+// so_icp_set_batch_priors: which batched solve kernel a round of so_icp_register_batch launches for the hypotheses active[0 .. n_active)
+// of its group.  `modes`: SO_ICP_PRIOR_* per hypothesis of the group (nullptr: the batch carries no priors).  The kernel with the prior
+// table only where a hypothesis of the list carries a prior; every other round launches what a batch without priors launches.
+enum BatchSolveKernelKind { kBatchSolvePlain = 0, kBatchSolvePrior = 1 };
+inline BatchSolveKernelKind batch_solve_kernel(const uint8_t* modes, const uint32_t* active, uint32_t n_active) {
+  if (!modes) return kBatchSolvePlain;
+  for (uint32_t k = 0; k < n_active; ++k)
+    if (modes[active[k]] != 0) return kBatchSolvePrior;
+  return kBatchSolvePlain;
+}
 
 // scans of this many points or more are refused (refuse_scan_size, icp_context.cpp): the work-list counters hold 21 bits each
 constexpr size_t kMaxScanPoints = (size_t)1 << 21;

@@ -1,9 +1,11 @@
-// solve_kernel_body.inc -- the body of solve_kernel, solve_kernel_prior and solve_kernel_prior_at_guess (kernels.hip), included once
-// for each with
+// solve_kernel_body.inc -- the body of solve_kernel, solve_kernel_prior, solve_kernel_prior_at_guess and solve_kernel_batch_prior
+// (kernels.hip), included once for each with
 //   SO_BODY_KERNEL  the kernel's own instantiation (its kernarg lines)
-//   SO_BODY_PRIOR   0 / 1 / kPriorAtGuess: eval_pass without the pose prior / with it / with it, T_meas = DevState::pose_in
-//   SO_BODY_PRIOR_WORDS   nullptr / the prior's 55 doubles (the kernel's last argument)
-// and PROF, BATCH, PEER in scope.  One text, three kernels of different names: a registration without a prior launches the
+//   SO_BODY_PRIOR   0 / 1 / kPriorAtGuess / kPriorBatch: eval_pass without the pose prior / with it / with it, T_meas = DevState::pose_in /
+//                   with the prior of the workgroup's hypothesis, where that has one
+//   SO_BODY_PRIOR_WORDS   nullptr / the prior's 55 doubles (the kernel's last argument) / prior_block
+//   SO_BODY_PRIOR_TABLE   (solve_kernel_batch_prior only) the table of per-hypothesis prior blocks, the kernel's last argument
+// and PROF, BATCH, PEER in scope.  One text, four kernels of different names: a registration or a batch without a prior launches the
 // functions it always launched.
   __shared__ EvalShared sh;
   __shared__ CorrCache cache;  // 26 KB next to the 64 KB of EvalShared: gfx950 has 160 KB of LDS per CU, one workgroup each here
@@ -11,9 +13,15 @@
   if (PROF && !BATCH) t_entry = wall_clock64();  // (profiling: "kernel entry -> first pass begins", word 3 of the fit record)
   if (SO_ENTRY_WARM) st = after_loaded(st, kernarg_lines<decltype(&SO_BODY_KERNEL)>());
   WgSpan span{0, 0, 0, false};
+#ifdef SO_BODY_PRIOR_TABLE
+  const double* prior_block = nullptr;  // this workgroup's hypothesis' block of the prior table
+#endif
   if (BATCH) {
     const uint32_t G = bv.wg_per_hyp, hi = blockIdx.x / G, sub = blockIdx.x - hi * G;
     const size_t h = bv.active[hi];
+#ifdef SO_BODY_PRIOR_TABLE
+    prior_block = SO_BODY_PRIOR_TABLE + h * kBatchPriorStride;
+#endif
     st += h; corr.nd += h * bv.bs; corr.coeff += h * bv.bs; corr.status += h * bv.bs; nbr5 += h * 5 * bv.bs;
     partials += h * bv.partial_stride; ticket += h * bv.sync_stride; hist += h * (kHistReplicas * kHistStride);
     span.V = bv.v_grid;
