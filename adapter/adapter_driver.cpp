@@ -170,7 +170,11 @@ int main(int argc, char** argv) {
     const bool correspondences = argc > 3 && std::strcmp(argv[3], "--correspondences") == 0;
     const bool seam_c = argc > 3 && std::strcmp(argv[3], "--seam-c") == 0;
     const bool vio_prior = argc > 3 && std::strcmp(argv[3], "--vio-prior") == 0;
-    slam.keep_correspondences = correspondences || seam_c;
+    // --geometry: per registration, the number of accepted correspondences and the observability histogram summed on the device from the
+    // geometry records' labels, next to the one in the registration's statistics (so_icp_correspondence_geometry)
+    const bool geometry = argc > 3 && std::strcmp(argv[3], "--geometry") == 0;
+    slam.keep_correspondences = correspondences || seam_c || geometry;
+    slam.keep_correspondence_geometry = geometry;
     if (vio_prior) { slam.isDegenerate = true; slam.Visual_confidence_factor = 0.9; }
     bool initialization = false;                        // laserMapping.cpp: first frame seeds the map
     for (int f = 0; f < n_frames; ++f) {
@@ -197,6 +201,18 @@ int main(int argc, char** argv) {
         slam.Localization(initialization, vio_prior ? LidarSLAM::PredictionSource::VIO_ODOM : LidarSLAM::PredictionSource::LIO_ODOM, guesses[f], edge, clouds[f],
                           times[f]);
         if (vio_prior) printf("frame %d: prediction_source %d\n", f, (int)slam.stats.prediction_source);
+      }
+      if (geometry && initialization && slam.last_status == SO_ICP_OK) {
+        std::vector<so_icp_correspondence_geometry_record> recs;
+        so_icp_correspondence_geometry_info info;
+        slam.LastCorrespondenceGeometry(recs, &info);
+        const so_icp_stats& st = slam.last_raw;
+        const int32_t* sh = st.iterations[st.n_iterations > 0 ? st.n_iterations - 1 : 0].obs_hist;
+        printf("frame %d: geometry valid %d n_accepted %llu records %zu obs_hist", f, (int)info.valid, (unsigned long long)info.n_accepted, recs.size());
+        for (int h = 0; h < SO_ICP_N_OBS; ++h) printf(" %d", (int)info.obs_hist[h]);
+        printf(" | stats");
+        for (int h = 0; h < SO_ICP_N_OBS; ++h) printf(" %d", (int)sh[h]);
+        printf("\n");
       }
       initialization = true;
       slam.frame_count = f; slam.laser_imu_sync = 1;    // :740-741

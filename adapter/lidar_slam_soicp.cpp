@@ -81,7 +81,30 @@ void LidarSLAM::push_knobs() {
   if (keep_correspondences != pushed_keep_correspondences_) {
     if (so_icp_keep_correspondences(gpu_, keep_correspondences ? 1 : 0) < 0) throw std::runtime_error(so_icp_last_error(gpu_));
     pushed_keep_correspondences_ = keep_correspondences;
+    if (!keep_correspondences) pushed_keep_correspondence_geometry_ = false;  // (the library turns the geometry switch off with it)
   }
+  const bool geometry = keep_correspondences && keep_correspondence_geometry;
+  if (geometry != pushed_keep_correspondence_geometry_) {
+    if (so_icp_keep_correspondence_geometry(gpu_, geometry ? 1 : 0) < 0) throw std::runtime_error(so_icp_last_error(gpu_));
+    pushed_keep_correspondence_geometry_ = geometry;
+  }
+}
+
+int LidarSLAM::LastCorrespondenceGeometry(std::vector<so_icp_correspondence_geometry_record>& out, so_icp_correspondence_geometry_info* info) {
+  ensure_context();
+  so_icp_correspondence_geometry_info local;
+  if (!info) info = &local;
+  const size_t cap = last_raw.n_iterations > 0 && last_raw.n_iterations <= SO_ICP_MAX_OUTER ? (size_t)last_raw.iterations[last_raw.n_iterations - 1].num_surf_from_scan : 0;
+  out.resize(cap);
+  if (so_icp_correspondence_geometry(gpu_, out.data(), out.size(), nullptr, 0, nullptr, info) < 0)
+    throw std::runtime_error(std::string("so_icp_correspondence_geometry: ") + so_icp_last_error(gpu_));
+  if (info->n_accepted > out.size()) {  // (a set the adapter's own statistics do not describe: sized by the call's answer)
+    out.resize((size_t)info->n_accepted);
+    if (so_icp_correspondence_geometry(gpu_, out.data(), out.size(), nullptr, 0, nullptr, info) < 0)
+      throw std::runtime_error(std::string("so_icp_correspondence_geometry: ") + so_icp_last_error(gpu_));
+  }
+  out.resize((size_t)info->n_accepted);
+  return (int)info->n_accepted;
 }
 
 int LidarSLAM::LastCorrespondences(const Transformd* pose, std::vector<so_icp_correspondence>& out, so_icp_correspondence_info* info) {

@@ -107,6 +107,9 @@ class LidarSLAM {
   // keep_correspondences below): the accepted correspondences in scan order with residual and weight at *pose (nullptr: the optimised
   // pose), so_icp_correspondences.  Returns their number; 0 with info->valid == 0 when there is nothing to export.  info may be nullptr.
   int LastCorrespondences(const Transformd* pose, std::vector<so_icp_correspondence>& out, so_icp_correspondence_info* info);
+  // The geometry of that set (needs keep_correspondence_geometry below): per accepted correspondence the five neighbours, the PCA and the
+  // observability labels, record j pairing with record j of LastCorrespondences (so_icp_correspondence_geometry).  Returns their number.
+  int LastCorrespondenceGeometry(std::vector<so_icp_correspondence_geometry_record>& out, so_icp_correspondence_geometry_info* info);
   // Seam C, for a caller that keeps its own solver (a Ceres problem with further factors, an iterated-EKF front end): one pass of
   // extractFeaturesConstraints (LidarSlam.cpp:299-344) at T_w_lidar_in without solving -- so_icp_match; needs keep_correspondences.  The
   // set it forms is the one LastCorrespondences and CorrespondenceSums read; *st (may be nullptr) receives num_surf_from_scan, both
@@ -145,6 +148,7 @@ class LidarSLAM {
   // ---- libsoicp specifics ----
   int device_id = 0;                   // HIP device of this process (one process per GPU)
   bool keep_correspondences = false;   // pushed before each call like the knobs above: registrations keep their set for LastCorrespondences
+  bool keep_correspondence_geometry = false;  // with keep_correspondences: registrations also keep the snapshot LastCorrespondenceGeometry refits from
   uint32_t last_flags = 0;             // so_icp_stats::flags of the last call (degraded modes, for the node's log)
   int last_status = 0;                 // so_icp_localization return code of the last call
   so_icp_stats last_raw{};             // everything the C ABI returned (JtJ / Jtr, per-iteration histograms)
@@ -156,7 +160,7 @@ class LidarSLAM {
   void add_absolute_pose_constraints(bool initialization, PredictionSource predictodom, const Transformd& position);
   void read_back(int32_t n_edge_points, const double T_out[7], double timeLaserOdometry);
   so_icp_ctx* gpu_ = nullptr;
-  bool pushed_keep_correspondences_ = false;
+  bool pushed_keep_correspondences_ = false, pushed_keep_correspondence_geometry_ = false;
   struct Scratch { uint8_t* p = nullptr; size_t cap = 0; };
   std::vector<Scratch> scratch_;
 };

@@ -396,9 +396,9 @@ int so_icp_download_scan(so_icp_ctx *ctx, const void *d_scan_xyz, size_t n, floa
  * a kernel of its own; no registration kernel takes part and none was changed for it).  What a caller does with it: colour or mask the
  * registered scan by residual, keep points that matched nothing out of the map, hand a factor-graph back end point-to-plane factors
  * instead of one pose, re-evaluate the cost of the fixed set at another pose.
- * Not exported: the correspondences of so_icp_register_batch's hypotheses, those of a sharded context (world_size > 1), the
- * neighbours' coordinates and the observability labels (not stored).  Normal equations: so_icp_stats::JtJ / Jtr are those of the set
- * at the default pose; at other poses so_icp_correspondence_sums (below, with so_icp_match) sums them on the device -- or the caller
+ * Not exported: the correspondences of so_icp_register_batch's hypotheses and those of a sharded context (world_size > 1).  The
+ * neighbours, the PCA and the observability labels of every accepted point: so_icp_correspondence_geometry, below.  Normal
+ * equations: so_icp_stats::JtJ / Jtr are those of the set at the default pose; at other poses so_icp_correspondence_sums (below, with so_icp_match) sums them on the device -- or the caller
  * sums them from the records: J = [n, p x (R^T n)], JtJ += weight J J^T, Jtr += weight residual J. */
 /* One accepted correspondence of the last outer iteration (LS.h:209-222: Xvalue, NormDir, negative_OA_dot_norm,
  * residualCoefficient), plus its residual and weight at the evaluation pose. */
@@ -456,6 +456,56 @@ int so_icp_correspondences(so_icp_ctx *ctx, const double pose[7] /* nullable */,
                            so_icp_correspondence *records, size_t cap_records,
                            uint8_t *status_out, float *residual_out, size_t cap_points,
                            void **d_records_out, so_icp_correspondence_info *info);
+
+/* -------- the GEOMETRY of the kept set: what the reference keeps of pcaFeature inside OptimizationParameter (LS.h:209-222) and what
+ * FeatureObservabilityAnalysis (LS.cpp:574-693) labels -- per accepted point the five neighbours it matched, the eigenvalues of their
+ * scatter, the PCA normal, the mean plane distance and the three observability labels that fill obs_hist (and so
+ * so_icp_stats::uncertainty, LS.cpp:289-291).  The registration does not store these; it SNAPSHOTS, behind the launch that produced
+ * its final report and in front of anything that can change the map (so_icp_localization's insert included), the five neighbour
+ * indices of every accepted point and the five map points they name -- the bits its last fit pass read -- into memory the context
+ * owns (one launch on the context's queue, 81 bytes per scan point).  The export refits from the snapshot with the fit pass's own
+ * code (plane_fit.h), so it depends on nothing a later call can change: not so_icp_map_add_surf, so_icp_map_shift,
+ * so_icp_set_resolution, a pre-filter or a staged announcement. */
+typedef struct {
+  uint32_t index;          /* position in the scan; record j pairs with record j of so_icp_correspondences */
+  uint32_t nbr_index[5];   /* canonical map indices AT THE TIME of the registration, nearest first (ties: ascending index) */
+  uint8_t  obs[3];         /* the three labels obs_hist counts: rotation #1, rotation #2, translation #1 (LS.cpp:336-339) */
+  uint8_t  reserved;
+  float    nbr[15];        /* the five neighbours, world frame, the map's own bits */
+  float    d2[5];          /* flann/octree.h:93-102 arithmetic, from the float query (float)(R(q) p + t) */
+  uint32_t pad;
+  double   pw[3];          /* the point at pose_fit, as the fit pass forms it */
+  double   eig[3];         /* ascending eigenvalues of the scatter S = sum (x-mu)(x-mu)^T  (not / N) */
+  double   pca_normal[3];  /* eigenvector of eig[0], flipped so that pca_normal . pw >= 0 (LS.cpp:553-561) */
+  double   mean_abs_dist;  /* the reference's "meanSquareDist": mean |n.p_j + d| (LS.cpp:792-844) */
+} so_icp_correspondence_geometry_record;   /* 192 bytes */
+/* (the record type carries the suffix _record: C has one namespace for typedefs and functions, and so_icp_correspondence_geometry is
+ *  the entry below) */
+typedef struct {
+  uint64_t n_points, n_accepted;
+  int32_t  valid, outer_iteration;   /* as in so_icp_correspondence_info */
+  double   pose_fit[7];
+  int32_t  obs_hist[9];    /* summed on the device from the records' labels (integer adds): iterations[last].obs_hist */
+  int32_t  reserved;
+} so_icp_correspondence_geometry_info;
+/* The switch.  A new context has it off; while it is off no entry gains a launch, copy, allocation or synchronisation and the export
+ * reports valid = 0.  It needs so_icp_keep_correspondences(ctx, 1) (SO_ICP_E_INVALID otherwise), and turning that switch off turns
+ * this one off too.  While it is on, every call that leaves a kept set -- so_icp_register, _register_dev, so_icp_localization(_dev)
+ * with initialization = 1, the last registration of so_icp_register_sequence, the last frame of so_icp_localization_sequence,
+ * so_icp_match(_dev) -- also leaves the snapshot.  world_size > 1: SO_ICP_E_UNSUPPORTED; a host-only context: SO_ICP_E_HIP. */
+int so_icp_keep_correspondence_geometry(so_icp_ctx *ctx, int on);
+/* The geometry of the kept set.  info->valid = 0 (SO_ICP_OK, every count 0, no output touched) in exactly the cases of
+ * so_icp_correspondences, and when this switch was off during the call that left the set.  Outputs, each nullable:
+ *  records     one per accepted point, ascending index; NULL or cap_records < n_accepted: the counts (and obs_hist) only
+ *  labels_out  [3 i .. 3 i + 2] = the labels of point i, 255 255 255 where its status is not 0; needs cap_points >= n_points
+ *              (SO_ICP_E_INVALID otherwise)
+ *  *d_records_out  a device buffer owned by the context with the same record bytes, valid until the next call of this entry; no
+ *                  other entry writes it
+ * Two calls return identical bytes.  One launch, one copy per requested host output and one of the counts, one synchronisation, on
+ * the context's queue.  A registered scan of 0 points: valid = 1, zero counts. */
+int so_icp_correspondence_geometry(so_icp_ctx *ctx, so_icp_correspondence_geometry_record *records, size_t cap_records,
+                                   uint8_t *labels_out, size_t cap_points,
+                                   void **d_records_out, so_icp_correspondence_geometry_info *info);
 
 /* -------- the step before Seam A: laserMapping::adjustVoxelSize (lmap.cpp:598-651) on the device ----------------
  * auto_voxel_size != 0: average_distance = mean|x| * mean|y| * mean|z| of the surf cloud chooses the resolutions
@@ -862,6 +912,10 @@ int so_icp_debug_match_status(so_icp_ctx *ctx, uint8_t *out, size_t n);
  * like the scan: out[5 * n].  Meaningful where that sweep found five neighbours inside the gate (every query the fit pass then judged: status
  * 0, 3, 4, 5); elsewhere the entries are whatever an earlier sweep left */
 int so_icp_debug_neighbours(so_icp_ctx *ctx, uint32_t *out, size_t n);
+/* test aid: the plane the export of so_icp_correspondence_geometry refits from its snapshot -- n[3], d, coeff (five doubles, 40 bytes)
+ * per accepted point, in the records' order -- to be held to so_icp_correspondences' records bit for bit.  One launch of the export
+ * kernel of its own; valid = 0 cases return SO_ICP_OK with *n_out = 0; cap < n_accepted: SO_ICP_E_INVALID */
+int so_icp_debug_correspondence_refit(so_icp_ctx *ctx, double *out, size_t cap, size_t *n_out);
 /* test aid: the DEVICE forms of the LM controller on a scripted sequence of sums -- no scan, no map.  The controller is a pure state
  * machine of (x0, sequence of sums), so a script drives any of its branches deterministically.
  *   form 0  the lane-parallel controller of the persistent solve (kernels.hip: lm_control_wave), run by one wavefront the way the solve's

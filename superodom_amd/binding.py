@@ -209,6 +209,18 @@ class CorrespondenceInfo(C.Structure):
                 ("pose_fit", C.c_double * 7), ("pose_eval", C.c_double * 7), ("cost", C.c_double)]
 
 
+class CorrespondenceGeometry(C.Structure):
+    """so_icp_correspondence_geometry_record: neighbours, PCA and observability labels of one accepted correspondence (192 bytes)"""
+    _fields_ = [("index", C.c_uint32), ("nbr_index", C.c_uint32 * 5), ("obs", C.c_uint8 * 3), ("reserved", C.c_uint8), ("nbr", C.c_float * 15),
+                ("d2", C.c_float * 5), ("pad", C.c_uint32), ("pw", C.c_double * 3), ("eig", C.c_double * 3), ("pca_normal", C.c_double * 3),
+                ("mean_abs_dist", C.c_double)]
+
+
+class CorrespondenceGeometryInfo(C.Structure):
+    _fields_ = [("n_points", C.c_uint64), ("n_accepted", C.c_uint64), ("valid", C.c_int32), ("outer_iteration", C.c_int32),
+                ("pose_fit", C.c_double * 7), ("obs_hist", C.c_int32 * 9), ("reserved", C.c_int32)]
+
+
 class PosePrior(C.Structure):
     """so_icp_pose_prior: T_meas {t, q = x y z w}, row-major U (residual = U e), the count scaling of the rows (all zero: U as given)"""
     _fields_ = [("T_meas", C.c_double * 7), ("sqrt_information", C.c_double * 36), ("count_floor", C.c_double * 6), ("count_fraction", C.c_double * 6)]
@@ -248,6 +260,9 @@ def pose_prior_sums(prior, pose, sums):
 CORRESPONDENCE_DTYPE = np.dtype([("index", "<u4"), ("p", "<f4", 3), ("n", "<f8", 3), ("d", "<f8"), ("coeff", "<f8"), ("residual", "<f8"),
                                  ("weight", "<f8")])
 assert CORRESPONDENCE_DTYPE.itemsize == C.sizeof(Correspondence) == 72
+CORRESPONDENCE_GEOMETRY_DTYPE = np.dtype([("index", "<u4"), ("nbr_index", "<u4", 5), ("obs", "u1", 3), ("reserved", "u1"), ("nbr", "<f4", 15), ("d2", "<f4", 5),
+                                          ("pad", "<u4"), ("pw", "<f8", 3), ("eig", "<f8", 3), ("pca_normal", "<f8", 3), ("mean_abs_dist", "<f8")])
+assert CORRESPONDENCE_GEOMETRY_DTYPE.itemsize == C.sizeof(CorrespondenceGeometry) == 192
 
 EXPORTED = ["so_icp_default_config", "so_icp_create", "so_icp_destroy", "so_icp_last_error", "so_icp_abi_version",
             "so_icp_device_available", "so_icp_set_resolution", "so_icp_set_max_surface_features", "so_icp_set_max_iterations",
@@ -266,6 +281,7 @@ EXPORTED = ["so_icp_default_config", "so_icp_create", "so_icp_destroy", "so_icp_
             "so_icp_debug_lm_script", "so_icp_set_cloud_intensity", "so_icp_prefilter_intensity",
             "so_icp_keep_correspondences", "so_icp_correspondences",
             "so_icp_match", "so_icp_match_dev", "so_icp_correspondence_sums",
+            "so_icp_keep_correspondence_geometry", "so_icp_correspondence_geometry", "so_icp_debug_correspondence_refit",
             "so_icp_pose_prior_from_information", "so_icp_pose_prior_sums", "so_icp_set_pose_prior", "so_icp_set_sequence_priors",
             "so_icp_set_batch_priors"]
 SUMS_MAX_POSES = 64
@@ -374,6 +390,9 @@ def load():
     L.so_icp_match.argtypes = [vp, f32p, C.c_size_t, C.c_size_t, f64p, C.POINTER(Stats)]
     L.so_icp_match_dev.argtypes = [vp, vp, C.c_size_t, f64p, C.POINTER(Stats)]
     L.so_icp_correspondence_sums.argtypes = [vp, f64p, C.c_int, C.POINTER(Sums)]
+    L.so_icp_keep_correspondence_geometry.argtypes = [vp, C.c_int]
+    L.so_icp_correspondence_geometry.argtypes = [vp, vp, C.c_size_t, u8p, C.c_size_t, C.POINTER(vp), C.POINTER(CorrespondenceGeometryInfo)]
+    L.so_icp_debug_correspondence_refit.argtypes = [vp, f64p, C.c_size_t, C.POINTER(C.c_size_t)]
     L.so_icp_pose_prior_from_information.argtypes = [f64p, f64p, C.POINTER(PosePrior)]
     L.so_icp_pose_prior_sums.argtypes = [C.POINTER(PosePrior), f64p, C.POINTER(Sums)]
     L.so_icp_set_pose_prior.argtypes = [vp, C.POINTER(PosePrior)]
@@ -616,6 +635,51 @@ class LidarSlamGpu:
         d = C.c_void_p()
         _, _, _, info = self._correspondences(pose, False, 0 if cap is None else cap, False, C.byref(d))
         return d.value, info
+
+    # ---- the geometry of the kept set: neighbours, PCA, observability labels ----
+    def keep_correspondence_geometry(self, on):
+        """so_icp_keep_correspondence_geometry: registrations from here on also leave the snapshot correspondence_geometry() refits
+        from (needs keep_correspondences(True)); returns the C code"""
+        return self.L.so_icp_keep_correspondence_geometry(self.h, int(bool(on)))
+
+    def _correspondence_geometry(self, cap, want_points, want_records, d_out):
+        info = CorrespondenceGeometryInfo()
+        if cap is None:  # a sizing call first (counts only): one launch more than a call with `cap`
+            self._check(self.L.so_icp_correspondence_geometry(self.h, None, 0, None, 0, None, C.byref(info)))
+            cap = int(info.n_points)
+        cap = int(cap)
+        rec = np.zeros(cap if want_records else 0, CORRESPONDENCE_GEOMETRY_DTYPE)
+        labels = np.zeros((cap, 3), np.uint8) if want_points else None
+        self._check(self.L.so_icp_correspondence_geometry(self.h, rec.ctypes.data_as(C.c_void_p) if want_records else None, len(rec),
+                                                          None if labels is None else _p(labels, C.c_uint8), cap if want_points else 0, d_out, C.byref(info)))
+        return rec[:int(info.n_accepted)], (None if labels is None else labels[:int(info.n_points)]), info
+
+    def correspondence_geometry(self, cap=None, want_points=True):
+        """so_icp_correspondence_geometry: one record (CORRESPONDENCE_GEOMETRY_DTYPE) per accepted correspondence of the last registration,
+        ascending index, pairing with correspondences(); the three observability labels of every scan point ([n, 3] uint8, 255 where the
+        point was not accepted; None without want_points) and the CorrespondenceGeometryInfo.  cap: an upper bound of the scan's points
+        (saves the sizing call).  info.valid == 0: empty arrays."""
+        return self._correspondence_geometry(cap, want_points, True, None)
+
+    def correspondence_geometry_dev(self):
+        """the same, the records left in HBM: (device address of the context-owned record buffer -- valid until the next call --, info)"""
+        d = C.c_void_p()
+        _, _, info = self._correspondence_geometry(0, False, False, C.byref(d))
+        return d.value, info
+
+    def prepare_correspondence_geometry(self, cap, want_points=True):
+        """so_icp_correspondence_geometry with pre-built arguments and buffers for `cap` points (timed loops): (call, records, labels, info)"""
+        rec = np.zeros(int(cap), CORRESPONDENCE_GEOMETRY_DTYPE); info = CorrespondenceGeometryInfo()
+        labels = np.zeros((int(cap), 3), np.uint8) if want_points else None
+        fn, args = self.L.so_icp_correspondence_geometry, (self.h, rec.ctypes.data_as(C.c_void_p), len(rec), None if labels is None else _p(labels, C.c_uint8),
+                                                           int(cap) if want_points else 0, None, C.byref(info))
+        return (lambda: fn(*args)), rec, labels, info
+
+    def debug_correspondence_refit(self, cap):
+        """so_icp_debug_correspondence_refit: the plane the geometry export refits per accepted point, [n_accepted, 5] = n[3], d, coeff"""
+        out = np.zeros((int(cap), 5), np.float64); n = C.c_size_t()
+        self._check(self.L.so_icp_debug_correspondence_refit(self.h, _p(out, C.c_double), int(cap), C.byref(n)))
+        return out[:n.value]
 
     # ---- Seam C: the matching half at a pose of the caller's, and the kept set's sums on the device ----
     def match(self, scan, pose):

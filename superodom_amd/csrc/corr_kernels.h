@@ -46,4 +46,34 @@ struct CorrSumsHist { double v[16]; };  // LmSums::hist of every record written:
 void launch_correspondence_sums(const CorrSumsIn& in, const double* d_poses, uint32_t n_poses, const CorrSumsHist& hist, double* d_partials,
                                 double* d_sums_out, hipStream_t s);
 
+// ---- corr_geometry_kernels.hip: so_icp_correspondence_geometry, the neighbours, PCA and observability labels of the kept set
+// bytes of one so_icp_correspondence_geometry_record; the refit's plane of so_icp_debug_correspondence_refit (n[3], d, coeff)
+constexpr uint32_t kCorrGeomRecordBytes = 192, kCorrRefitBytes = 40;
+// The snapshot a registration leaves while the switch is on, indexed like the scan: the status bytes, and for a point of status 0 its
+// five neighbour indices and the five map points they name
+struct NeighbourSnapshot {
+  uint8_t* status;   // n
+  uint32_t* idx;     // 5 n
+  float* pts;        // 15 n
+};
+// One launch: copies status[i], and where it is 0, nbr5[5 i ..] and map_pts[those].  n_map: the extent of map_pts in points (of the
+// device map's pool: its slots x kCapPerSlot); an index beyond it, which no accepted point holds, would be left as zeros
+void launch_neighbour_snapshot(const uint8_t* d_status, const uint32_t* d_nbr5, const float4* d_map_pts, uint32_t n_map, uint32_t n,
+                               const NeighbourSnapshot& snap, hipStream_t s);
+// What the export reads: the packed scan the registration kept, the snapshot, the pose the set was formed at and the gates of THAT
+// registration (MatchParams::sq_max_dist_f / ::max_point_dist)
+struct CorrGeomIn {
+  const float* scan;
+  NeighbourSnapshot snap;
+  uint32_t n;
+  Pose pose_fit;
+  float sq_max_dist_f;
+  double max_point_dist;
+};
+// d_records: room for n records of kCorrGeomRecordBytes (8-byte aligned); d_labels_out 3 n bytes; d_refit_out nullable, n x
+// kCorrRefitBytes; d_counts {n_accepted, ticket, points whose refit was not accepted, -} and d_obs_hist 9 int32, d_state
+// correspondence_workgroups(n) words: all zeroed by the caller.
+void launch_correspondence_geometry(const CorrGeomIn& in, uint8_t* d_records, uint8_t* d_labels_out, double* d_refit_out, uint32_t* d_counts,
+                                    int32_t* d_obs_hist, unsigned long long* d_state, hipStream_t s);
+
 }  // namespace soicp

@@ -5,6 +5,9 @@
 // so_icp_match(_dev) forms such a set at a pose of the caller's without solving (a registration of one outer iteration and no LM
 // iteration, so_icp_ctx::match_only); so_icp_correspondence_sums sums the kept set at up to 64 poses on the device
 // (corr_sums_kernels.hip).  Together: the matching half and the per-step evaluation of a solver the caller keeps.
+// so_icp_keep_correspondence_geometry and so_icp_correspondence_geometry: the neighbours, PCA and observability labels of the kept set.
+// The registration entries snapshot what the last fit pass read (keep_neighbour_snapshot, note_correspondence_geometry) while that
+// switch is on; the export refits from the snapshot (corr_geometry_kernels.hip).
 #include <hip/hip_runtime_api.h>
 
 #include <algorithm>
@@ -35,12 +38,97 @@ void note_correspondences(so_icp_ctx* c, const DevState& H, const double guess[7
   std::memcpy(L.pose_eval, n_it < 1 ? guess : H.iters[n_it - 1].pose_after, sizeof(L.pose_eval));
   // (the histograms of the iteration that formed the set: LmSums::hist of so_icp_correspondence_sums; host memory only)
   for (int h = 0; h < 16; ++h) L.hist[h] = n_it < 1 ? 0 : (h < 7 ? H.iters[n_it - 1].reject_hist[h] : H.iters[n_it - 1].obs_hist[h - 7]);
+  L.geometry = false;  // (note_correspondence_geometry, behind this call, says otherwise)
   L.valid = true;
 }
 
 }  // namespace soicp::host
 
 namespace {
+
+// so_icp_correspondence_geometry: the snapshot the registration entries write, and the export's own buffers (no other entry writes
+// those, and the export writes no other entry's buffers)
+struct CorrGeomState {
+  DevBuf snap_status, snap_idx, snap_pts;  // NeighbourSnapshot, indexed like the scan
+  DevBuf records, labels, refit;
+  DevBuf small;                // {n_accepted, ticket, refits not accepted, -} | obs_hist[9] + 3 | look-back words of the compaction
+  uint8_t* h_small = nullptr;  // pinned read-back of the counters and the histogram
+  ~CorrGeomState() {
+    for (DevBuf* b : {&snap_status, &snap_idx, &snap_pts, &records, &labels, &refit, &small}) b->release();
+    if (h_small) (void)hipHostFree(h_small);
+  }
+  NeighbourSnapshot snapshot() const { return NeighbourSnapshot{snap_status.as<uint8_t>(), snap_idx.as<uint32_t>(), snap_pts.as<float>()}; }
+};
+constexpr size_t kGeomHistOff = 16, kGeomStateOff = 64;  // CorrGeomState::small
+
+CorrGeomState* geometry_state_of(so_icp_ctx* c) {
+  if (!c->corr_geom_state) c->corr_geom_state = std::make_shared<CorrGeomState>();
+  return static_cast<CorrGeomState*>(c->corr_geom_state.get());
+}
+
+}  // namespace
+
+namespace soicp::host {
+
+int keep_neighbour_snapshot(so_icp_ctx* c, size_t n) {
+  if (!n) return SO_ICP_OK;
+  CorrGeomState& g = *geometry_state_of(c);
+  HIP_TRY(c, g.snap_status.reserve(n + 64));
+  HIP_TRY(c, g.snap_idx.reserve(n * 20 + 64));
+  HIP_TRY(c, g.snap_pts.reserve(n * 60 + 64));
+  // (canonical indices: positions in the host-built map, or slot * kCapPerSlot + position in the device map's pool)
+  const uint64_t map_extent = c->dmap ? (uint64_t)c->view.n_slots * kCapPerSlot : (uint64_t)c->view.n_points;
+  launch_neighbour_snapshot(c->d_status.as<uint8_t>(), c->d_nbr5.as<uint32_t>(), c->view.pts, (uint32_t)std::min<uint64_t>(map_extent, 0xFFFFFFFFull), (uint32_t)n,
+                            g.snapshot(), c->stream);
+  HIP_TRY(c, hipGetLastError());
+  return SO_ICP_OK;
+}
+
+void note_correspondence_geometry(so_icp_ctx* c, const MatchParams& mp) {
+  so_icp_ctx::CorrLast& L = c->corr_last;
+  L.sq_max_dist_f = mp.sq_max_dist_f; L.max_point_dist = mp.max_point_dist;
+  L.geometry = true;
+}
+
+}  // namespace soicp::host
+
+namespace {
+
+// One launch of the export kernel on the kept set and its snapshot `snap`, into the buffers of `g`; the counters and the histogram
+// are in g.h_small when it returns.  `records`, `labels_out`, `refit_out`: host destinations, each nullable
+int run_geometry_export(so_icp_ctx* c, const NeighbourSnapshot& snap, CorrGeomState& g, const char* entry, void* records, uint8_t* labels_out,
+                        double* refit_out) {
+  const so_icp_ctx::CorrLast& L = c->corr_last;
+  const size_t n = L.n;
+  const size_t nblk = correspondence_workgroups((uint32_t)n), small_bytes = kGeomStateOff + nblk * 8;
+  HIP_TRY(c, g.records.reserve(n * kCorrGeomRecordBytes + 64));
+  HIP_TRY(c, g.labels.reserve(n * 3 + 64));
+  if (refit_out) HIP_TRY(c, g.refit.reserve(n * kCorrRefitBytes + 64));
+  HIP_TRY(c, g.small.reserve(small_bytes));
+  if (!g.h_small) HIP_TRY(c, hipHostMalloc(reinterpret_cast<void**>(&g.h_small), kGeomStateOff));
+  hipStream_t s = c->stream;
+  HIP_TRY(c, hipMemsetAsync(g.small.p, 0, small_bytes, s));
+  CorrGeomIn in;
+  in.scan = c->corr_scan.as<float>();
+  in.snap = snap;
+  in.n = (uint32_t)n; in.pose_fit = pose_from_array(L.pose_fit); in.sq_max_dist_f = L.sq_max_dist_f; in.max_point_dist = L.max_point_dist;
+  launch_correspondence_geometry(in, g.records.as<uint8_t>(), g.labels.as<uint8_t>(), refit_out ? g.refit.as<double>() : nullptr, g.small.as<uint32_t>(),
+                                 reinterpret_cast<int32_t*>(g.small.as<uint8_t>() + kGeomHistOff),
+                                 reinterpret_cast<unsigned long long*>(g.small.as<uint8_t>() + kGeomStateOff), s);
+  HIP_TRY(c, hipGetLastError());
+  // (sized by what the registration counted, as so_icp_correspondences' copy is; the kernel's own count is checked afterwards)
+  if (records && L.n_accepted) HIP_TRY(c, hipMemcpyAsync(records, g.records.p, (size_t)L.n_accepted * kCorrGeomRecordBytes, hipMemcpyDeviceToHost, s));
+  if (refit_out && L.n_accepted) HIP_TRY(c, hipMemcpyAsync(refit_out, g.refit.p, (size_t)L.n_accepted * kCorrRefitBytes, hipMemcpyDeviceToHost, s));
+  if (labels_out) HIP_TRY(c, hipMemcpyAsync(labels_out, g.labels.p, n * 3, hipMemcpyDeviceToHost, s));
+  HIP_TRY(c, hipMemcpyAsync(g.h_small, g.small.p, kGeomStateOff, hipMemcpyDeviceToHost, s));
+  HIP_TRY(c, hipStreamSynchronize(s));
+  uint32_t counts[4];
+  std::memcpy(counts, g.h_small, sizeof(counts));
+  if (counts[0] != L.n_accepted)
+    return fail(c, SO_ICP_E_HIP, std::string(entry) + ": the snapshot holds another number of accepted points than the registration reported");
+  if (counts[2]) return fail(c, SO_ICP_E_HIP, std::string(entry) + ": the refit rejected a point the registration accepted");
+  return SO_ICP_OK;
+}
 
 // The export's own buffers: nothing here is written by another entry, and the export writes no other entry's buffers
 struct CorrExportState {
@@ -99,7 +187,60 @@ int so_icp_keep_correspondences(so_icp_ctx* c, int on) {
   NEED_DEVICE(c);
   if (c->cfg.world_size > 1) return fail(c, SO_ICP_E_UNSUPPORTED, "so_icp_keep_correspondences: a sharded context (world_size > 1) keeps its correspondences per rank");
   c->corr_keep = on != 0;
-  if (!c->corr_keep) c->corr_last.valid = false;
+  if (!c->corr_keep) { c->corr_last.valid = false; c->corr_geom_keep = false; }
+  return SO_ICP_OK;
+}
+
+int so_icp_keep_correspondence_geometry(so_icp_ctx* c, int on) {
+  if (!c) return SO_ICP_E_INVALID;
+  NEED_DEVICE(c);
+  if (c->cfg.world_size > 1) return fail(c, SO_ICP_E_UNSUPPORTED, "so_icp_keep_correspondence_geometry: a sharded context (world_size > 1) keeps its correspondences per rank");
+  if (on && !c->corr_keep)
+    return fail(c, SO_ICP_E_INVALID, "so_icp_keep_correspondence_geometry: the geometry belongs to the kept correspondence set -- turn that on first with so_icp_keep_correspondences(ctx, 1)");
+  c->corr_geom_keep = on != 0;
+  return SO_ICP_OK;
+}
+
+int so_icp_correspondence_geometry(so_icp_ctx* c, so_icp_correspondence_geometry_record* records, size_t cap_records, uint8_t* labels_out,
+                                   size_t cap_points, void** d_records_out, so_icp_correspondence_geometry_info* info) {
+  static_assert(sizeof(so_icp_correspondence_geometry_record) == kCorrGeomRecordBytes, "the kernel writes so_icp_correspondence_geometry_record records");
+  if (!c) return SO_ICP_E_INVALID;
+  NEED_DEVICE(c);
+  so_icp_correspondence_geometry_info local;
+  if (!info) info = &local;
+  std::memset(info, 0, sizeof(*info));
+  const so_icp_ctx::CorrLast& L = c->corr_last;
+  if (!c->corr_keep || !c->corr_geom_keep || !L.valid || !L.geometry) return SO_ICP_OK;
+  const size_t n = L.n;
+  if (n >= ((size_t)1 << 31)) return fail(c, SO_ICP_E_UNSUPPORTED, "so_icp_correspondence_geometry: too many points");
+  if (labels_out && cap_points < n)
+    return fail(c, SO_ICP_E_INVALID, "so_icp_correspondence_geometry: labels_out needs cap_points >= the points of the registered scan");
+  HIP_TRY(c, hipSetDevice(c->cfg.device_id));
+  info->valid = 1; info->n_points = n; info->outer_iteration = L.outer_iteration;
+  std::memcpy(info->pose_fit, L.pose_fit, sizeof(info->pose_fit));
+  if (d_records_out) *d_records_out = nullptr;
+  if (!n) return SO_ICP_OK;
+  CorrGeomState& g = *geometry_state_of(c);
+  const bool want_records = records && cap_records >= L.n_accepted;
+  if (const int rc = run_geometry_export(c, g.snapshot(), g, "so_icp_correspondence_geometry", want_records ? records : nullptr, labels_out, nullptr)) return rc;
+  info->n_accepted = L.n_accepted;
+  std::memcpy(info->obs_hist, g.h_small + kGeomHistOff, sizeof(info->obs_hist));
+  if (d_records_out) *d_records_out = g.records.p;
+  return SO_ICP_OK;
+}
+
+int so_icp_debug_correspondence_refit(so_icp_ctx* c, double* out, size_t cap, size_t* n_out) {
+  if (!c || !n_out) return SO_ICP_E_INVALID;
+  NEED_DEVICE(c);
+  *n_out = 0;
+  const so_icp_ctx::CorrLast& L = c->corr_last;
+  if (!c->corr_keep || !c->corr_geom_keep || !L.valid || !L.geometry || !L.n) return SO_ICP_OK;
+  if (!out || cap < L.n_accepted) return fail(c, SO_ICP_E_INVALID, "so_icp_debug_correspondence_refit: out needs room for five doubles per accepted point");
+  HIP_TRY(c, hipSetDevice(c->cfg.device_id));
+  // (buffers of its own, released when it returns: the records of the last so_icp_correspondence_geometry call stay as they are)
+  CorrGeomState scratch;
+  if (const int rc = run_geometry_export(c, geometry_state_of(c)->snapshot(), scratch, "so_icp_debug_correspondence_refit", nullptr, nullptr, out)) return rc;
+  *n_out = L.n_accepted;
   return SO_ICP_OK;
 }
 

@@ -10,6 +10,7 @@
 //   cloud_steps.cpp       so_icp_deskew_scan(_dev), so_icp_transform_cloud, so_icp_download_scan
 //   correspondences.cpp   so_icp_keep_correspondences, so_icp_correspondences: the last registration's correspondence set;
 //                         so_icp_match(_dev), so_icp_correspondence_sums: the set formed at a pose of the caller's, its sums on the device
+//                         so_icp_keep_correspondence_geometry, so_icp_correspondence_geometry: its neighbours, PCA and observability labels
 //   pose_prior.cpp        so_icp_pose_prior_from_information, so_icp_pose_prior_sums, so_icp_set_pose_prior, so_icp_set_sequence_priors,
 //                         so_icp_set_batch_priors
 //   multi_gpu.cpp         RCCL, in-process groups, peer exchange, shard helpers
@@ -173,7 +174,12 @@ struct so_icp_ctx {
     int outer_iteration = 0;
     double pose_fit[7] = {0, 0, 0, 0, 0, 0, 1}, pose_eval[7] = {0, 0, 0, 0, 0, 0, 1};  // where the set was formed / the default evaluation pose
     int32_t hist[16] = {};            // reject_hist[7] | obs_hist[9] of the outer iteration that formed the set (so_icp_correspondence_sums)
+    // so_icp_correspondence_geometry: the call that left the set also left the neighbour snapshot; the gates of THAT registration
+    bool geometry = false;
+    float sq_max_dist_f = 0; double max_point_dist = 0;   // MatchParams::sq_max_dist_f / ::max_point_dist
   } corr_last;
+  bool corr_geom_keep = false;        // so_icp_keep_correspondence_geometry: the switch (never on without corr_keep)
+  std::shared_ptr<void> corr_geom_state;  // so_icp_correspondence_geometry: the snapshot and the export's own buffers
   std::shared_ptr<void> corr_state;   // so_icp_correspondences: buffers of its own
   std::shared_ptr<void> corr_sums_state;  // so_icp_correspondence_sums: buffers of its own
   // so_icp_match(_dev): the registration in progress is one outer iteration's matching half and the evaluation at the guess (one
@@ -490,6 +496,13 @@ inline bool keeps_correspondences(const so_icp_ctx* c) { return c->corr_keep && 
 int keep_scan_copy(so_icp_ctx* c, const float* d_scan, size_t n);  // the packed copy, enqueued on the context's queue
 // the record of a registration that ended with SO_ICP_OK, reported in H from the guess `guess` with the loss parameters of `ep`
 void note_correspondences(so_icp_ctx* c, const DevState& H, const double guess[7], size_t n, const EvalParams& ep);
+// so_icp_keep_correspondence_geometry: what the same entries do for so_icp_correspondence_geometry while so_icp_ctx::corr_geom_keep is on
+inline bool keeps_correspondence_geometry(const so_icp_ctx* c) { return c->corr_geom_keep && keeps_correspondences(c); }
+// the snapshot of the n points' status bytes, neighbour indices and neighbour points: one launch on the context's queue, behind the
+// launch that produced the final report and in front of whatever changes the map next (reads d_status, d_nbr5 and c->view)
+int keep_neighbour_snapshot(so_icp_ctx* c, size_t n);
+// behind note_correspondences: the kept set has its snapshot, taken under the gates of `mp`
+void note_correspondence_geometry(so_icp_ctx* c, const MatchParams& mp);
 
 // multi_gpu.cpp
 int exchange_map_counts(so_icp_ctx* c);

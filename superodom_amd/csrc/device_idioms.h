@@ -32,6 +32,14 @@ __device__ __forceinline__ int cube_coord_f(float c, int origin) {
   return i;
 }
 
+// nanoflann::L2Distance::compute, flann/octree.h:93-102: float differences, squares and sum in double
+// (std::pow(float,int) promotes), narrowed to float.  (The k-NN sweeps of kernels.hip and the geometry export of
+// corr_geometry_kernels.hip; moved here from kernels.hip as it stands.)
+__device__ __forceinline__ float l2_d2(float qx, float qy, float qz, float px, float py, float pz) {
+  const float dx = qx - px, dy = qy - py, dz = qz - pz;
+  return (float)((double)dx * (double)dx + (double)dy * (double)dy + (double)dz * (double)dz);
+}
+
 // ---- launch entry: fetch what the first statements of a kernel read in one memory trip per batch (arguments, then state)
 // A launch starts cold: its kernel-argument segment was just written by the host side and its state block by the launch in front
 // (the scalar cache is invalidated between kernels).  The compiler sinks every argument load to its first use, and the early

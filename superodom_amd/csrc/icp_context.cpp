@@ -622,6 +622,10 @@ static int register_core_once(so_icp_ctx* c, const float* d_scan, size_t n, cons
   fill_result(c, H, pose_in, st, pose_out, !c->batch_mode && !c->match_only);
   if (p.prior) st->prediction_source = 1;  // addAbsolutePoseConstraints, LidarSlam.cpp:297
   if (keep_corr) note_correspondences(c, H, pose_in, p.n, p.ep);
+  if (keep_corr && keeps_correspondence_geometry(c)) {  // (the report is in: d_status and d_nbr5 are the last fit pass's; the caller's insert comes behind)
+    if ((rc = keep_neighbour_snapshot(c, p.n))) return rc;
+    note_correspondence_geometry(c, p.mp);
+  }
   st->time_elapsed_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_icp).count();  // :199-200
   if (p.timed && (rc = collect_timing(c, p, H))) return rc;
   if (c->match_only) return SO_ICP_OK;  // (not a registration of so_icp_timing)

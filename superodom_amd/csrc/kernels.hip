@@ -383,13 +383,7 @@ struct Top5 {
   }
 };
 
-// nanoflann::L2Distance::compute, flann/octree.h:93-102: float differences, squares and sum in double
-// (std::pow(float,int) promotes), narrowed to float.
-__device__ __forceinline__ float l2_d2(float qx, float qy, float qz, float px, float py, float pz) {
-  const float dx = qx - px, dy = qy - py, dz = qz - pz;
-  return (float)((double)dx * (double)dx + (double)dy * (double)dy + (double)dz * (double)dz);
-}
-
+// (l2_d2, nanoflann::L2Distance::compute: device_idioms.h)
 __device__ __forceinline__ uint32_t knn27(const DevMapView& m, const CellRef& c, float qx, float qy, float qz, Top5& top) {
   const uint32_t* tbl = m.cell_start + (size_t)c.slot * m.ncell1;
   const int nc = m.nc;

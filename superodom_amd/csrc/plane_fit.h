@@ -219,6 +219,58 @@ SO_HD int plane_fit5(const float nb[15], const double pw[3], const ObsAxes& axes
   return SO_FIT_SUCCESS;
 }
 
+// plane_fit5, and what it forms on its way and the reference keeps in pcaFeature (LidarSlam.h:209-222), handed out: ev (ascending
+// eigenvalues of the scatter S, not / N), nrm (the PCA normal, flipped towards pw, LidarSlam.cpp:553-561) and mean_abs (the
+// "meanSquareDist" of :792-844); valid when it returns SO_FIT_SUCCESS.  The export of so_icp_correspondence_geometry
+// (corr_geometry_kernels.hip) calls it.  A SECOND COPY of plane_fit5's statements, not one body the two share: with plane_fit5
+// forwarding to this function the sixteen fitting kernels of kernels.hip each moved by one to four instructions
+// (profiles/correspondence_geometry/compare_kernel_asm_one_body_not_kept.txt), and their code stays as measured.  Whoever changes one
+// changes the other: tests/test_correspondence_geometry_host.py holds the two to the same bits on the host,
+// tests/test_gpu_correspondence_geometry.py on the device.
+SO_HD int plane_fit5_geometry(const float nb[15], const double pw[3], const ObsAxes& axes, float sq_max_dist_f, double max_point_dist,
+                              double nd[4], double& coeff, int obs[3], double ev[3], double nrm[3], double& mean_abs_out,
+                              bool obs_as_written = false) {
+  double mx = 0, my = 0, mz = 0;
+  SO_UNROLL
+  for (int j = 0; j < 5; ++j) { mx += (double)nb[3 * j]; my += (double)nb[3 * j + 1]; mz += (double)nb[3 * j + 2]; }
+  mx = fit_div(mx, 5.0); my = fit_div(my, 5.0); mz = fit_div(mz, 5.0);
+  double s00 = 0, s01 = 0, s02 = 0, s11 = 0, s12 = 0, s22 = 0;
+  SO_UNROLL
+  for (int j = 0; j < 5; ++j) {
+    const double a = (double)nb[3 * j] - mx, b = (double)nb[3 * j + 1] - my, c = (double)nb[3 * j + 2] - mz;
+    s00 += a * a; s01 += a * b; s02 += a * c; s11 += b * b; s12 += b * c; s22 += c * c;
+  }
+  double adj[6], det_s, scale;
+  eig3_sym_direct_adj(s00, s01, s02, s11, s12, s22, ev, nrm, adj, det_s, scale);
+  if (ev[0] < 1e-6 || fit_div(ev[1], ev[2]) < 0.1) return SO_FIT_BAD_PCA;
+  const double w0 = __builtin_fma(adj[0], mx, __builtin_fma(adj[1], my, adj[2] * mz));
+  const double w1 = __builtin_fma(adj[1], mx, __builtin_fma(adj[3], my, adj[4] * mz));
+  const double w2 = __builtin_fma(adj[2], mx, __builtin_fma(adj[4], my, adj[5] * mz));
+  const double ww = __builtin_fma(w0, w0, __builtin_fma(w1, w1, w2 * w2));
+  const double D = __builtin_fma(scale, det_s, 5.0 * __builtin_fma(w0, mx, __builtin_fma(w1, my, w2 * mz)));
+  if (!(ww > 0.0) || !(D > 0.0) || !(D < 1.79e308)) return SO_FIT_INVALID;
+  const double rs = fit_rsqrt(ww);
+  const double n0 = -w0 * rs, n1 = -w1 * rs, n2 = -w2 * rs;
+  const double d = (0.2 * D) * rs;
+  double sum = 0;
+  bool too_far = false;
+  SO_UNROLL
+  for (int j = 0; j < 5; ++j) {
+    const double dist = fabs(n0 * (double)nb[3 * j] + n1 * (double)nb[3 * j + 1] + n2 * (double)nb[3 * j + 2] + d);
+    too_far |= dist > max_point_dist;
+    sum += dist;
+  }
+  if (too_far) return SO_FIT_MSE;
+  const double mean_abs = fit_div(sum, 5.0);
+  if (pw[0] * nrm[0] + pw[1] * nrm[1] + pw[2] * nrm[2] < 0) { nrm[0] = -nrm[0]; nrm[1] = -nrm[1]; nrm[2] = -nrm[2]; }
+  if (obs_as_written) fit_observability<true>(pw, ev, nrm, axes, obs[0], obs[1], obs[2]);
+  else fit_observability<false>(pw, ev, nrm, axes, obs[0], obs[1], obs[2]);
+  coeff = 1.0 - sqrt(fit_div(mean_abs, (double)sq_max_dist_f));
+  nd[0] = n0; nd[1] = n1; nd[2] = n2; nd[3] = d;
+  mean_abs_out = mean_abs;
+  return SO_FIT_SUCCESS;
+}
+
 // ------------------------------------------------------------------------------------------------
 // The same correspondence with the reference's own algorithms: column-pivoted Householder for the plane, optionally cyclic
 // Jacobi for the PCA.  Not on the production path -- the PROF kernels run it behind SOICP_ABLATE = 4096 / 512 for A/B runs and

@@ -271,8 +271,11 @@ struct SequenceCall {
       // so_icp_correspondences exports the LAST registration of the run (the records of the others were overwritten by the launches
       // chained behind them).  Its scan lies in a slot the next call refills on the sequence's own queue: copied now, and waited for
       if (const int rc = keep_scan_copy(c, r.d_scan, r.n)) return rc;
+      const bool geometry = keeps_correspondence_geometry(c);  // (so_icp_correspondence_geometry: its snapshot, in front of the same wait)
+      if (geometry) { if (const int rc = keep_neighbour_snapshot(c, r.n)) return rc; }
       HIP_TRY(c, hipStreamSynchronize(c->stream));
       note_correspondences(c, H, guess, r.n, r.ep);
+      if (geometry) note_correspondence_geometry(c, r.mp);
     }
     st->time_elapsed_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_icp).count();
     c->timing.registrations++;
