@@ -699,30 +699,26 @@ class LidarSlamGpu:
         by it; None withdraws a pending one"""
         self._check(self.L.so_icp_set_pose_prior(self.h, C.byref(prior) if prior is not None else None))
 
-    def set_sequence_priors(self, priors, modes=None):
-        """so_icp_set_sequence_priors: one PosePrior per frame of the next register_sequence / localization_sequence call, which consumes
-        them; modes[k] in PRIOR_NONE / PRIOR_GIVEN / PRIOR_AT_GUESS (None: all given).  priors None or empty withdraws pending ones"""
+    def _set_priors(self, setter, priors, modes):
         if priors is None or len(priors) == 0:
-            self._check(self.L.so_icp_set_sequence_priors(self.h, 0, None, None)); return
+            self._check(setter(self.h, 0, None, None)); return
         arr = (PosePrior * len(priors))(*priors)
         m = None
         if modes is not None:
             assert len(modes) == len(priors)
             m = (C.c_uint8 * len(priors))(*[int(v) for v in modes])
-        self._check(self.L.so_icp_set_sequence_priors(self.h, len(priors), arr, m))
+        self._check(setter(self.h, len(priors), arr, m))
+
+    def set_sequence_priors(self, priors, modes=None):
+        """so_icp_set_sequence_priors: one PosePrior per frame of the next register_sequence / localization_sequence call, which consumes
+        them; modes[k] in PRIOR_NONE / PRIOR_GIVEN / PRIOR_AT_GUESS (None: all given).  priors None or empty withdraws pending ones"""
+        self._set_priors(self.L.so_icp_set_sequence_priors, priors, modes)
 
     def set_batch_priors(self, priors, modes=None):
         """so_icp_set_batch_priors: one PosePrior per hypothesis of the next register_batch call, which consumes them; modes[h] in
         PRIOR_NONE / PRIOR_GIVEN / PRIOR_AT_GUESS (None: all given; AT_GUESS: T_meas := poses_in[h] of that call).  priors None or
         empty withdraws pending ones"""
-        if priors is None or len(priors) == 0:
-            self._check(self.L.so_icp_set_batch_priors(self.h, 0, None, None)); return
-        arr = (PosePrior * len(priors))(*priors)
-        m = None
-        if modes is not None:
-            assert len(modes) == len(priors)
-            m = (C.c_uint8 * len(priors))(*[int(v) for v in modes])
-        self._check(self.L.so_icp_set_batch_priors(self.h, len(priors), arr, m))
+        self._set_priors(self.L.so_icp_set_batch_priors, priors, modes)
 
     def correspondence_sums(self, poses):
         """so_icp_correspondence_sums: the kept set's cost and normal equations at `poses` ([7] or [k, 7], k <= SUMS_MAX_POSES) -> an

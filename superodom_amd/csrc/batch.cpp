@@ -71,7 +71,7 @@ int batch_priors_reserve(so_icp_ctx* c, uint32_t B) {
 
 // `priors`: the priors of the whole batch (so_icp_set_batch_priors; nullptr: none), of which hypothesis h of this group is element base + h
 int register_batch_group(so_icp_ctx* c, const float* d_scan, size_t n, const double* poses_in, int B, double* poses_out, so_icp_stats* stats,
-                         int32_t* hyp_rc, const int pos[3], int count_5x5, const RunPriors* priors, int base) {
+                         int32_t* hyp_rc, const int pos[3], int count_5x5, const PriorSet* priors, int base) {
   const auto t_begin = std::chrono::steady_clock::now();
   std::vector<so_icp_stats> local;
   if (!stats) { local.resize((size_t)B); stats = local.data(); }
@@ -235,13 +235,12 @@ int so_icp_register_batch(so_icp_ctx* c, const float* xyz, const void* d_scan, s
                           int n_hyp, double* poses_out, so_icp_stats* stats, int32_t* rc_out) {
   if (!c || !poses_in || !poses_out || n_hyp < 0 || (!xyz && !d_scan && n)) return SO_ICP_E_INVALID;
   NEED_DEVICE(c);
-  if (const int rc = refuse_pending_prior(c, "so_icp_register_batch", false, true)) return rc;
-  if (!RunPriors::batch_count_matches(c, n_hyp)) return fail(c, SO_ICP_E_INVALID, "so_icp_register_batch: n_hyp differs from that of the pending so_icp_set_batch_priors call");
+  if (const int rc = refuse_pending(c, "so_icp_register_batch", kPriorsBatch)) return rc;
+  if (!c->pending.count_matches(kPriorsBatch, n_hyp)) return fail(c, SO_ICP_E_INVALID, "so_icp_register_batch: n_hyp differs from that of the pending so_icp_set_batch_priors call");
   // so_icp_set_batch_priors: taken out of the context here, so they are consumed whatever this call returns; the group repeats and
   // the fall-back to concurrent registrations below keep them
-  RunPriors batch_priors;
-  batch_priors.take(c->batch_priors);
-  const RunPriors* priors = batch_priors.any() ? &batch_priors : nullptr;  // (all NONE: the batch without priors, launch for launch)
+  const PriorSet batch_priors = c->pending.take(kPriorsBatch);
+  const PriorSet* priors = batch_priors.any() ? &batch_priors : nullptr;  // (all NONE: the batch without priors, launch for launch)
   HIP_TRY(c, hipSetDevice(c->cfg.device_id));
   if (c->cfg.world_size != 1)  // (hypotheses are independent: replicate the map and split THEM over the ranks -- bench.py's batch64)
     return fail(c, SO_ICP_E_UNSUPPORTED, "so_icp_register_batch needs the whole map on one device (world_size == 1)");
@@ -324,11 +323,11 @@ int so_icp_register_batch(so_icp_ctx* c, const float* xyz, const void* d_scan, s
     if (hipSetDevice(c->cfg.device_id) != hipSuccess) { lane_rc[l] = SO_ICP_E_HIP; return; }
     for (int h = l; h < n_hyp; h += lanes) {
       so_icp_stats local;
-      // P_h becomes the lane context's single prior for this registration (RunPriors::arm: what so_icp_set_pose_prior does, without
-      // its refusals); a lane runs one launch per evaluation, eval_kernel_prior
+      // P_h becomes the lane context's single prior for this registration, which consumes it (PriorSet::arm: what so_icp_set_pose_prior
+      // does, without its refusals); a lane runs one launch per evaluation, eval_kernel_prior
       if (priors) priors->arm(w, h, poses_in + 7 * (size_t)h);
+      const PriorOneShot consume{w};
       const int r = register_core(w, scan, n, poses_in + 7 * (size_t)h, poses_out + 7 * (size_t)h, stats ? stats + h : &local);
-      w->prior_pending = false;
       hyp_rc[h] = r;
       if (r < 0) { lane_rc[l] = r; return; }
     }

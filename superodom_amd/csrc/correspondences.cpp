@@ -310,7 +310,7 @@ int so_icp_match_dev(so_icp_ctx* c, const void* d_scan, size_t n, const double p
   if (!c || !pose || (!d_scan && n)) return SO_ICP_E_INVALID;
   NEED_DEVICE(c);
   if (const int rc = match_refusal(c, "so_icp_match_dev")) return rc;
-  if (const int rc = refuse_pending_prior(c, "so_icp_match_dev")) return rc;
+  if (const int rc = refuse_pending(c, "so_icp_match_dev", kPriorsNone)) return rc;
   HIP_TRY(c, hipSetDevice(c->cfg.device_id));
   c->corr_last.valid = false;
   return match_core(c, static_cast<const float*>(d_scan), n, pose, st);
@@ -320,7 +320,7 @@ int so_icp_match(so_icp_ctx* c, const float* xyz, size_t n, size_t stride_bytes,
   if (!c || !pose || (!xyz && n)) return SO_ICP_E_INVALID;
   NEED_DEVICE(c);
   if (const int rc = match_refusal(c, "so_icp_match")) return rc;
-  if (const int rc = refuse_pending_prior(c, "so_icp_match")) return rc;
+  if (const int rc = refuse_pending(c, "so_icp_match", kPriorsNone)) return rc;
   HIP_TRY(c, hipSetDevice(c->cfg.device_id));
   c->corr_last.valid = false;
   // a plain upload into the context's own scan buffer: a copy of this scan announced with so_icp_stage_scan stays in its slot for the

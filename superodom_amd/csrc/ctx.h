@@ -185,20 +185,39 @@ struct so_icp_ctx {
   // so_icp_match(_dev): the registration in progress is one outer iteration's matching half and the evaluation at the guess (one
   // outer iteration, ZERO LM iterations, per-evaluation launches); it leaves tracker, staged scans and packing policy alone
   bool match_only = false;
-  // so_icp_set_pose_prior: the prior of the NEXT registration entry (one-shot: PriorOneShot); it travels as the last argument of that
-  // registration's solve / evaluation launches
-  bool prior_pending = false;
-  PosePrior prior{};
-  // so_icp_set_sequence_priors: one prior and one mode (SO_ICP_PRIOR_*) per frame of the NEXT so_icp_register_sequence /
-  // so_icp_localization_sequence call (one-shot: that call takes them out of the context when it starts, RunPriors::take)
-  struct RunPriors {
-    bool pending = false;
+  // The pose priors that wait for the NEXT entry of their kind (reg_plan.h: PriorKind, refused_prior) -- one slot, since the setters
+  // refuse one another: at most one kind is pending.
+  //   kPriorSingle (so_icp_set_pose_prior): `single`, the last argument of the solve / evaluation launches of the registration that
+  //     carries it; so_icp_register(_dev) and so_icp_localization(_dev) consume it when they return (PriorOneShot)
+  //   kPriorsRun (so_icp_set_sequence_priors), kPriorsBatch (so_icp_set_batch_priors): one prior and one mode (SO_ICP_PRIOR_*) per
+  //     frame / per hypothesis (its guess: poses_in[k]); the sequence or batch call takes them out of the context when it starts
+  //     (take), so the per-frame entries it runs do not meet them and they are consumed whatever it returns
+  struct PriorSet {
+    PriorKind kind = kPriorsNone;
+    PosePrior single{};
     std::vector<PosePrior> priors;
     std::vector<uint8_t> modes;
-  } run_priors;
-  // so_icp_set_batch_priors: one prior and one mode per hypothesis of the NEXT so_icp_register_batch call (one-shot: taken out of the
-  // context when that call starts)
-  RunPriors batch_priors;
+    void withdraw(PriorKind k) { if (kind == k) { kind = kPriorsNone; priors.clear(); modes.clear(); } }  // (another kind stays)
+    // a call of another length than the pending priors of its kind is refused and leaves them where they are
+    bool count_matches(PriorKind k, int count) const { return kind != k || (size_t)count == priors.size(); }
+    PriorSet take(PriorKind k) {  // -> the priors of kind k, out of the context; an empty set where none are pending
+      PriorSet out;
+      if (kind == k) { out.kind = k; out.priors.swap(priors); out.modes.swap(modes); kind = kPriorsNone; }
+      return out;
+    }
+    bool any() const { for (uint8_t m : modes) if (m != SO_ICP_PRIOR_NONE) return true; return false; }
+    int mode(int k) const { return (size_t)k < modes.size() ? modes[(size_t)k] : SO_ICP_PRIOR_NONE; }
+    // P_k: priors[k], with T_meas = the element's guess where the mode says so; false: element k carries no prior
+    bool frame_prior(int k, const double guess[7], PosePrior& out) const {
+      if (mode(k) == SO_ICP_PRIOR_NONE) return false;
+      out = priors[(size_t)k];
+      if (mode(k) == SO_ICP_PRIOR_AT_GUESS) std::memcpy(out.T_meas, guess, sizeof(out.T_meas));
+      return true;
+    }
+    // element k through a per-frame entry (so_icp_register(_dev), so_icp_localization(_dev), register_core on a batch lane): P_k becomes
+    // the single prior of `c`, whose own priors were taken out -- what so_icp_set_pose_prior does, without its refusals
+    void arm(so_icp_ctx* c, int k, const double guess[7]) const { c->pending.kind = frame_prior(k, guess, c->pending.single) ? kPriorSingle : kPriorsNone; }
+  } pending;
   hipStream_t pf_stream = nullptr;   // the pre-filter's own queue: the next frame's upload + VoxelGrid run BESIDE the map insert the previous
   // Seam B scratch
   DevBuf d_q, d_nbr, d_d2, d_idx, d_found, d_fblist;
@@ -359,59 +378,27 @@ namespace soicp::host {
 
 // sets the text so_icp_last_error returns and passes `code` through
 inline int fail(so_icp_ctx* c, int code, const std::string& msg) { c->err = msg; return code; }
-// so_icp_set_pose_prior: so_icp_register(_dev) and so_icp_localization(_dev) consume the pending prior when they return, whatever they
-// return; the entries that cannot carry one refuse the call and leave it pending
-struct PriorOneShot { so_icp_ctx* c; ~PriorOneShot() { c->prior_pending = false; } };
-// so_icp_set_sequence_priors: the priors of a run go into the next so_icp_register_sequence / so_icp_localization_sequence call
-// (`sequence_entry`); every other entry that could meet them refuses and leaves them pending
-// so_icp_set_batch_priors: the priors of a batch go into the next so_icp_register_batch call (`batch_entry` below, and the setter itself);
-// every other entry that could meet them refuses and leaves them pending
-inline int refuse_pending_batch_priors(so_icp_ctx* c, const char* entry) {
-  return c->batch_priors.pending ? fail(c, SO_ICP_E_UNSUPPORTED, std::string(entry) + ": the priors of a batch are pending (so_icp_set_batch_priors); they go into "
-                                                                 "so_icp_register_batch -- withdraw them with so_icp_set_batch_priors(ctx, 0, NULL, NULL) first")
-                                 : SO_ICP_OK;
-}
-inline int refuse_pending_run_priors(so_icp_ctx* c, const char* entry, bool batch_entry = false) {
-  if (c->run_priors.pending)
-    return fail(c, SO_ICP_E_UNSUPPORTED, std::string(entry) + ": the priors of a run are pending (so_icp_set_sequence_priors); they go into "
-                                         "so_icp_register_sequence or so_icp_localization_sequence -- withdraw them with "
-                                         "so_icp_set_sequence_priors(ctx, 0, NULL, NULL) first");
-  return batch_entry ? SO_ICP_OK : refuse_pending_batch_priors(c, entry);
-}
-inline int refuse_pending_prior(so_icp_ctx* c, const char* entry, bool sequence_entry = false, bool batch_entry = false) {
-  if (c->prior_pending)
-    return fail(c, SO_ICP_E_UNSUPPORTED, std::string(entry) + ": a pose prior is pending (so_icp_set_pose_prior); it goes into so_icp_register(_dev) "
-                                         "or so_icp_localization(_dev) -- withdraw it with so_icp_set_pose_prior(ctx, NULL) first");
-  if (sequence_entry) return batch_entry ? SO_ICP_OK : refuse_pending_batch_priors(c, entry);
-  return refuse_pending_run_priors(c, entry, batch_entry);
-}
-// The priors of one sequence call, taken out of the context when the call starts (so the per-frame entries it runs do not meet them,
-// and they are consumed whatever the call returns).  A call of another length leaves them where they are (count_matches).
-struct RunPriors {
-  std::vector<PosePrior> priors;
-  std::vector<uint8_t> modes;
-  static bool count_matches(const so_icp_ctx* c, int count) { return !c->run_priors.pending || (size_t)count == c->run_priors.priors.size(); }
-  void take(so_icp_ctx::RunPriors& from) {
-    if (!from.pending) return;
-    priors.swap(from.priors); modes.swap(from.modes);
-    from = so_icp_ctx::RunPriors{};
+using PriorSet = so_icp_ctx::PriorSet;
+// so_icp_set_pose_prior: so_icp_register(_dev) and so_icp_localization(_dev) consume the pending single prior when they return, whatever
+// they return
+struct PriorOneShot { so_icp_ctx* c; ~PriorOneShot() { c->pending.withdraw(kPriorSingle); } };
+// An entry that takes priors of kind `accepted` (kPriorsNone: none) is refused while another kind is pending, which stays (refused_prior)
+inline int refuse_pending(so_icp_ctx* c, const char* entry, PriorKind accepted) {
+  switch (refused_prior(c->pending.kind, accepted)) {
+    case kPriorSingle:
+      return fail(c, SO_ICP_E_UNSUPPORTED, std::string(entry) + ": a pose prior is pending (so_icp_set_pose_prior); it goes into so_icp_register(_dev) "
+                                           "or so_icp_localization(_dev) -- withdraw it with so_icp_set_pose_prior(ctx, NULL) first");
+    case kPriorsRun:
+      return fail(c, SO_ICP_E_UNSUPPORTED, std::string(entry) + ": the priors of a run are pending (so_icp_set_sequence_priors); they go into "
+                                           "so_icp_register_sequence or so_icp_localization_sequence -- withdraw them with "
+                                           "so_icp_set_sequence_priors(ctx, 0, NULL, NULL) first");
+    case kPriorsBatch:
+      return fail(c, SO_ICP_E_UNSUPPORTED, std::string(entry) + ": the priors of a batch are pending (so_icp_set_batch_priors); they go into "
+                                           "so_icp_register_batch -- withdraw them with so_icp_set_batch_priors(ctx, 0, NULL, NULL) first");
+    case kPriorsNone: break;
   }
-  void take(so_icp_ctx* c) { take(c->run_priors); }
-  // so_icp_set_batch_priors keeps its priors in the same form: element k is hypothesis k, its guess poses_in[k]
-  static bool batch_count_matches(const so_icp_ctx* c, int n_hyp) { return !c->batch_priors.pending || (size_t)n_hyp == c->batch_priors.priors.size(); }
-  bool any() const { for (uint8_t m : modes) if (m != SO_ICP_PRIOR_NONE) return true; return false; }
-  int mode(int k) const { return (size_t)k < modes.size() ? modes[(size_t)k] : SO_ICP_PRIOR_NONE; }
-  // P_k: priors[k], with T_meas = the frame's guess where the mode says so; false: frame k carries no prior
-  bool frame_prior(int k, const double guess[7], PosePrior& out) const {
-    if (mode(k) == SO_ICP_PRIOR_NONE) return false;
-    out = priors[(size_t)k];
-    if (mode(k) == SO_ICP_PRIOR_AT_GUESS) std::memcpy(out.T_meas, guess, sizeof(out.T_meas));
-    return true;
-  }
-  // frame k through a per-frame entry (so_icp_register(_dev), so_icp_localization(_dev)): P_k becomes the context's single prior,
-  // which that entry consumes -- what so_icp_set_pose_prior does, without its refusals
-  void arm(so_icp_ctx* c, int k, const double guess[7]) const { c->prior_pending = frame_prior(k, guess, c->prior); }
-};
+  return SO_ICP_OK;
+}
 // what a DeviceMap member returns (device_map.h: -1 out of memory / a full cube, -2 a HIP error, its text in c->err; else >= 0) as a C ABI code
 inline int map_status(int r) { return r >= 0 ? SO_ICP_OK : (r == -1 ? SO_ICP_E_NOMEM : SO_ICP_E_HIP); }
 // the stride rule of the entries that read float x y z records: 0 means packed (12 bytes); a multiple of 4

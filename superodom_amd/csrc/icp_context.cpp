@@ -365,7 +365,7 @@ void plan_registration(const so_icp_ctx* c, RegPlan& p, const float* d_scan, siz
   // so_icp_set_pose_prior: the PRIOR instantiations of the solve / evaluation kernels add it to every evaluation's sums
   // (a lane of so_icp_register_batch: its hypothesis' prior, armed by the batch itself -- so_icp_set_batch_priors; no public entry
   //  leaves a prior pending on a context in batch mode)
-  p.prior = carries_pose_prior(c->prior_pending, own || c->batch_mode, c->cfg.world_size, c->match_only) && !p.exchange;
+  p.prior = carries_pose_prior(c->pending.kind == kPriorSingle, own || c->batch_mode, c->cfg.world_size, c->match_only) && !p.exchange;
   p.flags = (p.query_waves ? SO_ICP_FLAG_QUERY_WAVES : 0u) | (p.pb ? SO_ICP_FLAG_BINNED_AHEAD : 0u) | (p.persistent ? 0u : SO_ICP_FLAG_PER_EVAL_LAUNCHES) |
             (p.prior ? SO_ICP_FLAG_POSE_PRIOR : 0u);
 }
@@ -441,7 +441,7 @@ int enqueue_eval(so_icp_ctx* c, RegPlan& p, int slot) {
   span_begin(c, 1, (uint32_t)p.n);
   const bool fuse_lm = !p.exchange;  // single device: the last workgroup of eval runs the LM controller itself
   launch_eval(slot, fuse_lm, p.d_scan, p.d_scan + 1, p.d_scan + 2, p.corr, ds, p.ep, c->d_partials,
-              c->d_ticket, c->d_hist, c->d_sums, c->view, c->d_nbr5.as<uint32_t>(), p.mp, (uint32_t)p.n, s, p.prior ? &c->prior : nullptr);
+              c->d_ticket, c->d_hist, c->d_sums, c->view, c->d_nbr5.as<uint32_t>(), p.mp, (uint32_t)p.n, s, p.prior ? &c->pending.single : nullptr);
   span_end(c);
   if (!fuse_lm && c->group) {  // in-process group: through host memory (every member calls this the same number of times)
     HIP_TRY(c, hipMemcpyAsync(c->h_sums, c->d_sums, sizeof(LmSums), hipMemcpyDeviceToHost, s));
@@ -487,7 +487,7 @@ int enqueue_outer_b(so_icp_ctx* c, RegPlan& p, int it) {
     EvalParams ep_it = p.ep;
     // (deferred: the k-NN launch of it + 1 will be enqueued before the host waits)
     ep_it.defer_publish = (p.defer_reports && it + 1 < p.max_outer) ? 1 : 0;
-    launch_persistent_solve(c, p, ep_it, p.mp, p.prior ? &c->prior : nullptr);
+    launch_persistent_solve(c, p, ep_it, p.mp, p.prior ? &c->pending.single : nullptr);
   } else {
     for (int slot = 1; slot <= p.lm_max; ++slot) { const int r = enqueue_eval(c, p, slot); if (r) return r; }
   }
@@ -1042,7 +1042,7 @@ int so_icp_free_scan(so_icp_ctx* c, void* d_scan) {
 
 int so_icp_register_dev(so_icp_ctx* c, const void* d_scan, size_t n, const double pose_in[7], double pose_out[7], so_icp_stats* st) {
   if (!c) return SO_ICP_E_INVALID;
-  if (const int rc = refuse_pending_run_priors(c, "so_icp_register_dev")) return rc;
+  if (const int rc = refuse_pending(c, "so_icp_register_dev", kPriorSingle)) return rc;
   const PriorOneShot consume{c};
   if (!pose_in || !pose_out || (!d_scan && n)) return SO_ICP_E_INVALID;
   NEED_DEVICE(c);
@@ -1053,7 +1053,7 @@ int so_icp_register_dev(so_icp_ctx* c, const void* d_scan, size_t n, const doubl
 
 int so_icp_register(so_icp_ctx* c, const float* xyz, size_t n, size_t stride_bytes, const double pose_in[7], double pose_out[7], so_icp_stats* st) {
   if (!c) return SO_ICP_E_INVALID;
-  if (const int rc = refuse_pending_run_priors(c, "so_icp_register")) return rc;
+  if (const int rc = refuse_pending(c, "so_icp_register", kPriorSingle)) return rc;
   const PriorOneShot consume{c};
   if (!pose_in || !pose_out || (!xyz && n)) return SO_ICP_E_INVALID;
   NEED_DEVICE(c);

@@ -127,7 +127,7 @@ extern "C" {
 int so_icp_localization(so_icp_ctx* c, int initialization, const double T_in[7], const float* xyz, size_t n, size_t stride_bytes,
                         double time_laser_odometry, double pose_out[7], so_icp_stats* st) {
   if (!c) return SO_ICP_E_INVALID;
-  if (const int rc = refuse_pending_run_priors(c, "so_icp_localization")) return rc;
+  if (const int rc = refuse_pending(c, "so_icp_localization", kPriorSingle)) return rc;
   const PriorOneShot consume{c};  // (a frame that seeds the map consumes it too)
   if (!T_in || !pose_out || (!xyz && n)) return SO_ICP_E_INVALID;
   if (const int rc = normalise_stride(c, &stride_bytes)) return rc;
@@ -138,7 +138,7 @@ int so_icp_localization(so_icp_ctx* c, int initialization, const double T_in[7],
 int so_icp_localization_dev(so_icp_ctx* c, int initialization, const double T_in[7], const void* d_scan, size_t n,
                             double time_laser_odometry, double pose_out[7], so_icp_stats* st) {
   if (!c) return SO_ICP_E_INVALID;
-  if (const int rc = refuse_pending_run_priors(c, "so_icp_localization_dev")) return rc;
+  if (const int rc = refuse_pending(c, "so_icp_localization_dev", kPriorSingle)) return rc;
   const PriorOneShot consume{c};
   if (!T_in || !pose_out || (!d_scan && n)) return SO_ICP_E_INVALID;
   NEED_DEVICE(c);

@@ -30,12 +30,11 @@ int so_icp_localization_sequence(so_icp_ctx* c, int count, const void* const* sc
     if (!scans[k] && n_points[k]) return fail(c, SO_ICP_E_INVALID, "so_icp_localization_sequence: scans[" + std::to_string(k) + "] is NULL");
   if (count == 0) return SO_ICP_OK;
   NEED_DEVICE(c);
-  if (const int rc = refuse_pending_prior(c, "so_icp_localization_sequence", true)) return rc;
+  if (const int rc = refuse_pending(c, "so_icp_localization_sequence", kPriorsRun)) return rc;
   // so_icp_set_sequence_priors: one prior per frame of this call (another length: refused, they stay pending); taken out of the context
   // here -- consumed whatever this call returns --, frame k's goes in as the single prior its per-frame entry consumes
-  if (!RunPriors::count_matches(c, count)) return fail(c, SO_ICP_E_INVALID, "so_icp_localization_sequence: count differs from that of the pending so_icp_set_sequence_priors call");
-  RunPriors run_priors;
-  run_priors.take(c);
+  if (!c->pending.count_matches(kPriorsRun, count)) return fail(c, SO_ICP_E_INVALID, "so_icp_localization_sequence: count differs from that of the pending so_icp_set_sequence_priors call");
+  const PriorSet run_priors = c->pending.take(kPriorsRun);
 
   double guess[7];
   std::memcpy(guess, pose0, sizeof(guess));

@@ -16,8 +16,15 @@ constexpr int kOuterCap = 16, kLmCap = 16;
 inline int outer_limit(int max_iterations) { return std::min(max_iterations > 0 ? max_iterations : 4, kOuterCap); }
 inline int lm_limit(int lm_max_iterations) { return std::min(lm_max_iterations > 0 ? lm_max_iterations : 4, kLmCap); }
 
-// so_icp_set_pose_prior: the pending prior goes into a registration that is the context's own (no batch lane, no borrowed map), on one
-// device, and a registration (so_icp_match leaves it pending)
+// Pose priors wait in ONE slot of the context for the entry that takes their kind: a single prior for so_icp_register(_dev) /
+// so_icp_localization(_dev), the priors of a run for the two sequence entries, the priors of a batch for so_icp_register_batch.  An entry
+// (a setter included) that takes kind `accepted` -- kPriorsNone: so_icp_match(_dev), which takes none -- goes on when the slot is empty
+// or holds that kind; otherwise it is refused because of what is pending, and that stays.  -> kPriorsNone: go on; else the kind in the way
+enum PriorKind { kPriorsNone = 0, kPriorSingle = 1, kPriorsRun = 2, kPriorsBatch = 3 };
+inline PriorKind refused_prior(PriorKind pending, PriorKind accepted) { return pending == accepted ? kPriorsNone : pending; }
+
+// so_icp_set_pose_prior: the pending prior (`pending`: the slot holds a single prior) goes into a registration that is the context's own
+// (no batch lane, no borrowed map), on one device, and a registration (so_icp_match refuses it)
 inline bool carries_pose_prior(bool pending, bool own, int world_size, bool match_only) { return pending && own && world_size <= 1 && !match_only; }
 
 // so_icp_set_sequence_priors: which persistent-solve kernel the launches of frame k of so_icp_register_sequence's chained path use.

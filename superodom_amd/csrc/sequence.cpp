@@ -59,7 +59,7 @@ struct SequenceCall {
   so_icp_ctx* c; int count; const void* const* scans; const size_t* n_points; size_t stride_bytes; int scans_on_device;
   const double* pose0; const double* deltas; double* poses_out; double* guesses_out; so_icp_stats* stats; int* n_done;
   std::vector<SeqRun> runs;
-  RunPriors run_priors;                     // so_icp_set_sequence_priors: taken out of the context when the call started (empty: none were set)
+  PriorSet run_priors;                      // so_icp_set_sequence_priors: taken out of the context when the call started (empty: none were set)
   so_icp_ctx::SeqNext adopted;
   int slot_base = 0;
 
@@ -407,12 +407,11 @@ int so_icp_register_sequence(so_icp_ctx* c, int count, const void* const* scans,
   if (n_done) *n_done = 0;
   if (!c || count < 0 || (count && (!scans || !n_points || !pose0 || !poses_out)) || (count > 1 && !deltas)) return SO_ICP_E_INVALID;
   NEED_DEVICE(c);
-  if (const int rc = refuse_pending_prior(c, "so_icp_register_sequence", true)) return rc;
+  if (const int rc = refuse_pending(c, "so_icp_register_sequence", kPriorsRun)) return rc;
   // so_icp_set_sequence_priors: one prior per frame of THIS call -- a call of another length leaves them pending, this one takes them
   // out of the context (consumed whatever it returns; the per-frame entries it may run do not meet them)
-  if (!RunPriors::count_matches(c, count)) return fail(c, SO_ICP_E_INVALID, "so_icp_register_sequence: count differs from that of the pending so_icp_set_sequence_priors call");
-  RunPriors run_priors;
-  run_priors.take(c);
+  if (!c->pending.count_matches(kPriorsRun, count)) return fail(c, SO_ICP_E_INVALID, "so_icp_register_sequence: count differs from that of the pending so_icp_set_sequence_priors call");
+  PriorSet run_priors = c->pending.take(kPriorsRun);
   HIP_TRY(c, hipSetDevice(c->cfg.device_id));
   if (stride_bytes == 0) stride_bytes = 12;
   for (int k = 0; k < count; ++k) if (!scans[k] && n_points[k]) return SO_ICP_E_INVALID;

@@ -19,6 +19,10 @@ void rp_query_split_share(unsigned long long n, unsigned long long world, unsign
 }
 unsigned rp_bin_table_log2(unsigned long long n) { return bin_table_log2((size_t)n); }
 int rp_work_list_fits(unsigned long long bin_packed, unsigned long long wavefronts) { return work_list_fits(bin_packed, wavefronts) ? 1 : 0; }
+// out = {kPriorsNone, kPriorSingle, kPriorsRun, kPriorsBatch}
+void rp_prior_kinds(int out[4]) { out[0] = kPriorsNone; out[1] = kPriorSingle; out[2] = kPriorsRun; out[3] = kPriorsBatch; }
+int rp_refused_prior(int pending, int accepted) { return refused_prior((PriorKind)pending, (PriorKind)accepted); }
+int rp_carries_pose_prior(int pending, int own, int world_size, int match_only) { return carries_pose_prior(pending != 0, own != 0, world_size, match_only != 0) ? 1 : 0; }
 int rp_cube_stable(const int origin[3], const int dims[3], const double t[3], double margin) { return cube_stable(origin, dims, t, margin) ? 1 : 0; }
 
 }  // extern "C"

@@ -299,6 +299,94 @@ def test_one_shot_count_withdrawal_and_refusals(soicp, gpu_slam_factory):
     sharded.close()
 
 
+# Which entry refuses which pending kind, and the whole text it leaves in so_icp_last_error
+PENDING_TEXT = {
+    "single": "a pose prior is pending (so_icp_set_pose_prior); it goes into so_icp_register(_dev) or so_icp_localization(_dev) -- "
+              "withdraw it with so_icp_set_pose_prior(ctx, NULL) first",
+    "run": "the priors of a run are pending (so_icp_set_sequence_priors); they go into so_icp_register_sequence or "
+           "so_icp_localization_sequence -- withdraw them with so_icp_set_sequence_priors(ctx, 0, NULL, NULL) first",
+    "batch": "the priors of a batch are pending (so_icp_set_batch_priors); they go into so_icp_register_batch -- withdraw them with "
+             "so_icp_set_batch_priors(ctx, 0, NULL, NULL) first",
+}
+REFUSED_BY = {
+    "single": ("so_icp_register_sequence", "so_icp_localization_sequence", "so_icp_set_sequence_priors", "so_icp_register_batch",
+               "so_icp_set_batch_priors", "so_icp_match", "so_icp_match_dev"),
+    "run": ("so_icp_register", "so_icp_register_dev", "so_icp_localization", "so_icp_localization_dev", "so_icp_set_pose_prior",
+            "so_icp_register_batch", "so_icp_set_batch_priors", "so_icp_match", "so_icp_match_dev"),
+    "batch": ("so_icp_register", "so_icp_register_dev", "so_icp_localization", "so_icp_localization_dev", "so_icp_set_pose_prior",
+              "so_icp_register_sequence", "so_icp_localization_sequence", "so_icp_set_sequence_priors", "so_icp_match", "so_icp_match_dev"),
+}
+
+
+def test_every_refusal_by_code_and_whole_text_and_the_withdrawal_order(soicp, gpu_slam_factory):
+    """Each kind of prior pending in turn: every entry that cannot take it returns -5 with the whole text above and leaves it pending;
+    so_icp_set_pose_prior(ctx, NULL) is refused like any other call of it, a withdrawal through one of the two other setters comes before
+    the refusal check and touches only its own kind, and a setter call that fails validation inside its list leaves what was pending."""
+    sc, scan, poses, priors, _, _ = bpd.batch_inputs("tiny5", "dense")
+    poses, guess = poses[:3], poses[0]
+    given = bpd.hypothesis_prior(priors, [bpd.AT_GUESS] * 3, 0, synth.perturb_pose(sc.gt_pose(bpd.SCAN_ID), 900, 0.02, 0.2))  # (a finite T_meas)
+    slam = _make(gpu_slam_factory, "tiny", keep=True)  # (so_icp_match refuses a context without the switch first)
+    d, n = slam.upload_scan(scan)
+    deltas = np.zeros((2, 7)); deltas[:, 6] = 1.0
+    entries = {
+        "so_icp_register": lambda: slam.register(scan, guess), "so_icp_register_dev": lambda: slam.register_dev(d, n, guess),
+        "so_icp_localization": lambda: slam.localization(True, guess, scan, 0.1),
+        "so_icp_localization_dev": lambda: slam.localization_dev(True, guess, d, n, 0.1),
+        "so_icp_set_pose_prior": lambda: slam.set_pose_prior(given),
+        "so_icp_register_sequence": lambda: slam.register_sequence([scan, scan], guess, deltas),
+        "so_icp_localization_sequence": lambda: slam.localization_sequence([scan, scan], guess, deltas, [0.1, 0.2]),
+        "so_icp_set_sequence_priors": lambda: slam.set_sequence_priors([given, given]),
+        "so_icp_register_batch": lambda: slam.register_batch(scan, poses), "so_icp_set_batch_priors": lambda: slam.set_batch_priors([given] * 3),
+        "so_icp_match": lambda: slam.match(scan, guess), "so_icp_match_dev": lambda: slam.match_dev(d, n, guess),
+    }
+    assert set(entries) == {e for es in REFUSED_BY.values() for e in es}
+
+    def refused(entry, call, kind):
+        with pytest.raises(soicp.SoIcpError) as e:
+            call()
+        assert str(e.value) == "so_icp error -5: %s: %s" % (entry, PENDING_TEXT[kind]), (kind, entry)
+        assert slam.last_error() == "%s: %s" % (entry, PENDING_TEXT[kind]), (kind, entry)
+    set_kind = {"single": lambda: slam.set_pose_prior(given), "run": lambda: slam.set_sequence_priors([given, given]),
+                "batch": lambda: slam.set_batch_priors([given] * 3)}
+    # the entry that takes the kind: every frame / hypothesis of it then carries a prior, and the same call again none
+    takes = {"single": lambda: [slam.register(scan, guess)[2]], "run": lambda: slam.register_sequence([scan, scan], guess, deltas)[3],
+             "batch": lambda: slam.register_batch(scan, poses)[3]}
+
+    def consumed_by_its_entry(kind, tag):
+        for want in (True, False):
+            assert [bool(st.flags & soicp.FLAG_POSE_PRIOR) for st in takes[kind]()] == [want] * {"single": 1, "run": 2, "batch": 3}[kind], (kind, tag, want)
+    arr = lambda ps: (soicp.PosePrior * len(ps))(*ps)
+    nan_u = soicp.PosePrior.from_buffer_copy(bytes(given)); nan_u.sqrt_information[7] = float("nan")
+    for kind in ("single", "run", "batch"):
+        set_kind[kind]()
+        for entry in REFUSED_BY[kind]:
+            refused(entry, entries[entry], kind)
+        if kind != "single":  # the refusal check of so_icp_set_pose_prior comes before its withdrawal
+            refused("so_icp_set_pose_prior", lambda: slam.set_pose_prior(None), kind)
+        # n 0 withdraws before any refusal check: SO_ICP_OK while another kind is pending, which stays
+        if kind != "run":
+            assert slam.L.so_icp_set_sequence_priors(slam.h, 0, None, None) == 0 and slam.L.so_icp_set_sequence_priors(slam.h, 0, arr([given]), None) == 0
+        if kind != "batch":
+            assert slam.L.so_icp_set_batch_priors(slam.h, 0, None, None) == 0 and slam.L.so_icp_set_batch_priors(slam.h, 2, None, None) == 0
+        refused("so_icp_match", entries["so_icp_match"], kind)
+        consumed_by_its_entry(kind, "after the refused calls and the withdrawals of the other kinds")
+    # a setter call that fails validation half-way through its list leaves what was pending
+    for kind, setter in (("run", slam.L.so_icp_set_sequence_priors), ("batch", slam.L.so_icp_set_batch_priors)):
+        set_kind[kind]()
+        assert setter(slam.h, 3, arr([given, nan_u, given]), None) == -1
+        assert slam.last_error() == "so_icp_set_%s_priors: a field of priors[1] is not finite" % {"run": "sequence", "batch": "batch"}[kind]
+        consumed_by_its_entry(kind, "after a call that failed validation")
+    set_kind["single"]()
+    assert slam.L.so_icp_set_pose_prior(slam.h, C.byref(nan_u)) == -1 and slam.last_error() == "so_icp_set_pose_prior: a field of the prior is not finite"
+    consumed_by_its_entry("single", "after a call that failed validation")
+    # each kind withdrawn by its own setter
+    for kind, withdraw in (("single", lambda: slam.set_pose_prior(None)), ("run", lambda: slam.set_sequence_priors(None)), ("batch", lambda: slam.set_batch_priors(None))):
+        set_kind[kind]()
+        withdraw()
+        assert not any(st.flags & soicp.FLAG_POSE_PRIOR for st in takes[kind]()), kind
+    slam.close()
+
+
 # ---- 6. the last outer iteration against a direct evaluation ------------------------------------------------------------------------------
 @pytest.mark.parametrize("kind", bpd.U_KINDS)
 def test_last_outer_iteration_against_correspondence_sums_and_the_host_prior(soicp, gpu_slam_factory, kind):

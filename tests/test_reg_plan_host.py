@@ -1,5 +1,5 @@
 """The decisions of a registration's host schedule that need no device (superodom_amd/csrc/reg_plan.h: loop limits, the query split,
-the query-wave switch, table and work-list sizes, the window rule of a chained start) compiled for the HOST and checked on the CPU.
+the query-wave switch, table and work-list sizes, the window rule of a chained start, which entry a pending pose prior refuses) compiled for the HOST and checked on the CPU.
 so_icp_register, so_icp_register_sequence and so_icp_register_batch all take these from that one header."""
 import ctypes as C
 import os
@@ -90,6 +90,32 @@ def test_work_list_fits(rp):
         assert rp.rp_work_list_fits(kept | normal << 21 | light << 42, limit), (normal, light)
         assert not rp.rp_work_list_fits(kept | (normal + 1) << 21 | light << 42, limit), (normal, light)
         assert not rp.rp_work_list_fits(kept | normal << 21 | (light + 1) << 42, limit), (normal, light)
+
+
+def test_which_entry_is_refused_by_which_pending_prior(rp):
+    kinds = (C.c_int * 4)()
+    rp.rp_prior_kinds(kinds)
+    none, single, run, batch = kinds
+    assert len({none, single, run, batch}) == 4
+    # rows: what the entry takes -- none: so_icp_match(_dev); single: so_icp_register(_dev), so_icp_localization(_dev), so_icp_set_pose_prior;
+    # run: so_icp_register_sequence, so_icp_localization_sequence, so_icp_set_sequence_priors; batch: so_icp_register_batch,
+    # so_icp_set_batch_priors.  Columns: what is pending.  The answer: nothing (go on), or the pending kind the refusal names
+    table = {
+        (none, none): none, (none, single): single, (none, run): run, (none, batch): batch,
+        (single, none): none, (single, single): none, (single, run): run, (single, batch): batch,
+        (run, none): none, (run, single): single, (run, run): none, (run, batch): batch,
+        (batch, none): none, (batch, single): single, (batch, run): run, (batch, batch): none,
+    }
+    assert len(table) == 16
+    for (accepted, pending), want in table.items():
+        assert rp.rp_refused_prior(pending, accepted) == want, (accepted, pending)
+
+
+def test_carries_pose_prior(rp):
+    # a pending single prior goes into the context's own registration on one device; so_icp_match never carries one
+    assert rp.rp_carries_pose_prior(1, 1, 1, 0) and rp.rp_carries_pose_prior(1, 1, 0, 0)
+    for args in ((0, 1, 1, 0), (1, 0, 1, 0), (1, 1, 2, 0), (1, 1, 1, 1)):
+        assert not rp.rp_carries_pose_prior(*args), args
 
 
 def test_cube_stable(rp):
