@@ -5,9 +5,25 @@
 #include <cstddef>
 #include <cstdint>
 
+#include "lm_endgame.h"
 #include "lm_solver.h"
 #include "pose_prior.h"
 #include "so_math.h"
+
+// A/B switches of the end of a solve (profiles/solve_endgame; SOICP_EXTRA_CXXFLAGS=-D...=0 builds the form before):
+//   SO_ENDGAME_IMAGE     the controller's workgroup of the persistent, non-batched solve keeps the state block in LDS and writes it
+//                        out once when the solve ends (0: every word through global memory, the block re-read for the mirror)
+//   SO_PUBLISH_FENCED    1: that flush ends in __threadfence_system() on every thread and a release store of `seq`, as publish_state_to does
+//   SO_PTOL_AT_PROPOSAL  ParameterToleranceReached is decided when the candidate is proposed: no evaluation pass for a step that ends the solve
+#ifndef SO_ENDGAME_IMAGE
+#define SO_ENDGAME_IMAGE 1
+#endif
+#ifndef SO_PUBLISH_FENCED
+#define SO_PUBLISH_FENCED 0
+#endif
+#ifndef SO_PTOL_AT_PROPOSAL
+#define SO_PTOL_AT_PROPOSAL 1
+#endif
 
 namespace soicp {
 
@@ -67,7 +83,9 @@ struct MatchParams {
 struct EvalParams {
   double a2;       // TukeyLoss a^2 with a = (double)sqrtf(3*planeRes)  (LidarSlam.cpp:271)
   int32_t variant; // 0: Ceres 2.0.0, 1: Ceres >= 2.1
-  int32_t ablate;  // profiling / test switches (env SOICP_ABLATE; PROF instantiations only): bit5 skip the LM controller, bit6 skip the point loop
+  int32_t ablate;  // profiling / test switches (env SOICP_ABLATE; PROF instantiations only): bit5 skip the LM controller, bit6 skip the point loop;
+                   // bit17 (131072, with bit7): DevState::dbg[8..15] carry the END-GAME record of the solve that ended last instead of the
+                   // evaluation pass's (eval_pass, kernels.hip; tools/eval_stamps.py --endgame)
   // the evaluation kernels walk the queries in ORIGINAL scan order (deterministic sums whatever the spatial binning did):
   // spx/spy/spz = scan, scan+1, scan+2 with q_stride 3; correspondence records are indexed by the original query index
   uint32_t n_queries, q_stride;
@@ -77,7 +95,8 @@ struct EvalParams {
   struct DevState* hring[2];
   unsigned long long seq_base;
   // 1: a solve that does NOT end the registration leaves the publication to the next k-NN launch (already enqueued by the
-  // host): the L2 write-back + system fence + PCIe stores (2.7 us) then overlap that sweep instead of delaying it
+  // host): the mirror's stores then overlap that sweep instead of delaying the solve's end (2.7 us while the block was re-read and
+  // fenced by every thread; profiles/solve_endgame has what the one flush from LDS of the solve that does publish costs)
   int32_t defer_publish;
   uint32_t chain_expect;  // see MatchParams::chain_expect
   // chain_next != 0: a chained registration may follow this one (so_icp_register_sequence): the solve that ends the registration leaves

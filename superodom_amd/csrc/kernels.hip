@@ -502,7 +502,8 @@ __device__ __forceinline__ int32_t approx_key(float m2qx, float m2qy, float m2qz
   return (int32_t)((__float_as_uint(v) & keep_mask) | (jloc & ~keep_mask));
 }
 
-__device__ __forceinline__ void publish_state_to(DevState* dst, const DevState* st, unsigned long long seq, int tid, int nthreads);  // below
+__device__ __forceinline__ void publish_state_to(DevState* dst, const DevState* st, unsigned long long seq, int tid, int nthreads,
+                                                 unsigned long long* eg = nullptr);  // below
 
 #ifndef SO_KNN_FILTER
 #define SO_KNN_FILTER 1  // stage only the candidates within the search radius of the group's bounding box (see knn_plane_kernel)
@@ -1644,9 +1645,16 @@ __device__ SO_LM_INLINE int lm_control(int slot, DevState* st, LmState& S_lds, c
 // one-thread form, the batched solve runs this one; tests/test_gpu_configs.py compares them bit for bit on registrations, tests/test_gpu_lm_scripts.py branch by
 // branch on scripted sums).  The state's home is the LDS copy; what the next
 // lm_feed needs beyond the sums (lm_after_candidate) and the store-back run AFTER the hand-off has been published.
+// `st` is where a solve that ends leaves its results: the state block in memory, or the launch's image of it in LDS (solve_kernel).
+// PTOL (the persistent, non-batched solve): a candidate whose step is within the parameter tolerance is not evaluated -- the next
+// lm_feed would end the solve on step_norm and x_norm alone, before it reads a sum (kernels.h lm_parameter_tolerance_at_proposal), so
+// the hand-off says "no further evaluation" and that lm_feed's one effect, termination 2, is applied here: state, pose, counts and
+// records are those of the protocol with the pass.  |x - cand|^2 then has to be in hand BEFORE the hand-off: seven dependent FMAs.
+// `eg` (profiling): clocks of the end game -- decision taken, hand-off issued, lm_solve_finished done.
+template <bool PTOL = false, bool EG = false>
 __device__ __forceinline__ int lm_control_wave(int slot, DevState* st, LmState& S, const LmSums& sums, const LmCtl& ctl, double* gather /* LDS, >= 56 doubles */,
                                                u4v* hand, unsigned long long want, double* pose_out, int* reg_done_out, int lane,
-                                               unsigned long long* dbg = nullptr) {
+                                               unsigned long long* dbg = nullptr, unsigned long long* eg = nullptr) {
   const bool is_mat = lane < 36, is_vec = lane >= 36 && lane < 42;
   const int li = is_mat ? lane / 6 : 0, lj = is_mat ? lane - 6 * li : (is_vec ? lane - 36 : 0);
   const int la = li < lj ? li : lj, lb = li < lj ? lj : li;          // (row, column) of the element's upper-triangle twin
@@ -1806,6 +1814,18 @@ __device__ __forceinline__ int lm_control_wave(int slot, DevState* st, LmState& 
     more = 1;
     break;
   }
+  // ---------------- PTOL: would the next lm_feed stop on the parameter tolerance?  Then this candidate is not evaluated.
+  [[maybe_unused]] double sn_early = 0;
+  [[maybe_unused]] bool ptol = false;
+  if constexpr (PTOL) {
+    if (more) {
+#pragma unroll
+      for (int i = 0; i < 7; ++i) sn_early = SO_FMA(x[i] - cand[i], x[i] - cand[i], sn_early);  // (lm_after_candidate's chain: the bits step_norm is formed from)
+      ptol = lm_parameter_tolerance_at_proposal(sn_early, x_norm);
+      if (ptol) more = 0;
+    }
+  }
+  if constexpr (EG) { if (eg) eg[0] = wall_clock64(); }
   // ---------------- hand-off {next pose, more?}: one 16-byte chunk per lane 0..7
   {
     double hv = cand[0];
@@ -1818,15 +1838,22 @@ __device__ __forceinline__ int lm_control_wave(int slot, DevState* st, LmState& 
     }
     if (lane < 7) pose_out[lane] = hv;
   }
+  if constexpr (EG) { if (eg) eg[1] = wall_clock64(); }
   // ---------------- behind the hand-off: what the next lm_feed needs, the state back to its home
-  if (more) {  // lm_after_candidate
+  if (more || (PTOL && ptol)) {  // lm_after_candidate
     inv_mcc = 1.0 / mcc_state;
     double sn = 0, n2 = 0;
+    if constexpr (PTOL) sn = sn_early;
+    else {
 #pragma unroll
-    for (int i = 0; i < 7; ++i) sn = SO_FMA(x[i] - cand[i], x[i] - cand[i], sn);
+      for (int i = 0; i < 7; ++i) sn = SO_FMA(x[i] - cand[i], x[i] - cand[i], sn);
+    }
 #pragma unroll
     for (int i = 0; i < 7; ++i) n2 = SO_FMA(cand[i], cand[i], n2);
     step_norm = sqrt(sn); cand_norm = sqrt(n2);
+  }
+  if constexpr (PTOL) {
+    if (ptol) { termination = 2; done = 1; }  // the lm_feed that would have followed the pass: ParameterToleranceReached, nothing else changes
   }
   if (is_mat) S.H[lane] = Hl;
   if (is_vec) S.g[lj] = gl;
@@ -1856,6 +1883,7 @@ __device__ __forceinline__ int lm_control_wave(int slot, DevState* st, LmState& 
       if (is_mat) st->JtJ[lane] = have ? Hl : 0.0;
       if (is_vec) st->Jtr[lj] = have ? gl : 0.0;
     }
+    if constexpr (EG) { if (eg) eg[2] = wall_clock64(); }
   } else if (lane == 0) *reg_done_out = 0;
   return more;
 }
@@ -1874,7 +1902,8 @@ __device__ __forceinline__ void load_ctl(LmCtl& ctl, const DevState* st, int tid
 __device__ __forceinline__ void publish_state(const DevState* st, const EvalParams& ep, int outer, int tid, int nthreads) {
   publish_state_to(ep.hring[outer & 1], st, ep.seq_base | (unsigned long long)(outer + 1), tid, nthreads);
 }
-__device__ __forceinline__ void publish_state_to(DevState* dst, const DevState* st, unsigned long long seq, int tid, int nthreads) {
+// (eg, profiling: clocks behind the copy, behind the fences and behind the seq store)
+__device__ __forceinline__ void publish_state_to(DevState* dst, const DevState* st, unsigned long long seq, int tid, int nthreads, unsigned long long* eg) {
   if (!dst) return;
   __threadfence_block();  // the controller thread's stores to *st are visible to the workgroup
   __syncthreads();
@@ -1882,9 +1911,44 @@ __device__ __forceinline__ void publish_state_to(DevState* dst, const DevState* 
   unsigned long long* out = reinterpret_cast<unsigned long long*>(dst);
   constexpr int kWords = (int)(offsetof(DevState, seq) / 8);
   for (int i = tid; i < kWords; i += nthreads) out[i] = src[i];
+  if (eg) eg[0] = wall_clock64();
   __threadfence_system();
   __syncthreads();
+  if (eg) eg[1] = wall_clock64();
   if (tid == 0) __hip_atomic_store(&dst->seq, seq, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
+  if (eg) eg[2] = wall_clock64();
+}
+// End of a solve in the launch that keeps its state block in LDS (solve_kernel, not batched): the image -- complete, a barrier behind
+// its last word -- goes to the block in memory with plain stores (the next launch of the queue reads it) and, when this solve
+// publishes, to the pinned mirror; nothing is read back.  The mirror is host-coherent memory: its words are written through with
+// system-scope 16-byte stores, every storing wavefront waits until its own have been acknowledged (vmcnt), and behind ONE barrier
+// one lane stores seq the same way -- the order the host relies on, without an L2 write-back and invalidate on 256 threads.
+// Called by the 256 threads of the controller's workgroup.
+constexpr int kStateChunks = (int)(offsetof(DevState, seq) / 16);
+static_assert(offsetof(DevState, seq) % 16 == 0 && alignof(u4v) == 16, "the state block up to seq goes out in 16-byte chunks");
+__device__ __forceinline__ void flush_state_image(DevState* st, DevState* mirror, const DevState* img, unsigned long long seq, int tid, unsigned long long* eg) {
+  const u4v* src = reinterpret_cast<const u4v*>(img);
+  u4v* out = reinterpret_cast<u4v*>(st);
+  u4v* pub = reinterpret_cast<u4v*>(mirror);
+  for (int i = tid; i < kStateChunks; i += 256) {
+    const u4v v = src[i];
+    out[i] = v;
+    if (mirror) store16_sys(pub + i, v);
+  }
+  if (!mirror) {
+    if (eg) eg[0] = wall_clock64();
+    return;
+  }
+  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+  if (eg) eg[0] = wall_clock64();
+  if (SO_PUBLISH_FENCED) __threadfence_system();
+  __syncthreads();
+  if (eg) eg[1] = wall_clock64();
+  if (tid == 0) {
+    if (SO_PUBLISH_FENCED) __hip_atomic_store(&mirror->seq, seq, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
+    else __hip_atomic_store(&mirror->seq, seq, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);  // (one sc0 sc1 store, no fence)
+  }
+  if (eg) eg[2] = wall_clock64();
 }
 
 // cooperative copy of the controller state between global memory and LDS (sizeof(LmState) is a multiple of 8)
@@ -2186,7 +2250,8 @@ __device__ __forceinline__ int eval_pass(int slot, int fuse_lm, const Pose& pose
                                          const float4* __restrict__ mpts, const uint32_t* __restrict__ nbr5,
                                          const MatchParams& mp, EvalShared& sh, const double* prior, unsigned long long pass_tag = 0,
                                          CorrCache* cc = nullptr, u4v* hand = nullptr, unsigned long long want = 0,
-                                         const WgSpan span = WgSpan{0, 0, 0, false}, const double* prior_tm = nullptr) {
+                                         const WgSpan span = WgSpan{0, 0, 0, false}, const double* prior_tm = nullptr,
+                                         DevState* img = nullptr /* PERSIST, not BATCH: the launch's LDS image of *st, see below */) {
   // PERSIST (solve_kernel): workgroup 0 is the finisher of every pass of the launch, so the controller state stays in
   // its LDS from pass to pass and goes to memory only when the solve ends; the workgroup records are PUSHED (tagged
   // 16-byte chunks, see below) instead of stored + counted
@@ -2575,32 +2640,74 @@ __device__ __forceinline__ int eval_pass(int slot, int fuse_lm, const Pose& pose
     if (stamp) T.sums = wall_clock64();
     // (BATCH too, round 6: the one-thread controller on the LDS copy of its state was what spilled -- 316 bytes of scratch per lane in a launch
     //  capped at 256 registers --, in the serial code every virtual workgroup's pass waits for)
+    // The non-batched launch keeps its state block in LDS (`img`, loaded at kernel entry): what a solve that ends leaves behind --
+    // lm_solve_finished's ~75 words, the normal equations, S, T_chain -- goes there, and the block goes out ONCE, 16 bytes a lane.
+    constexpr bool kImage = SO_ENDGAME_IMAGE != 0 && !BATCH;
+    constexpr bool kPtol = SO_PTOL_AT_PROPOSAL != 0 && !BATCH;
+    DevState* const sw = kImage ? img : st;
+    // end-game record (PROF, SOICP_ABLATE & 128 & 131072), in place of the evaluation pass's record dbg[8..15]; ticks of 10 ns:
+    //  [8] controller's decision -> hand-off issued  [9] -> lm_solve_finished and the normal equations done  [15] passes the launch ran
+    //      (these three are part of the block this solve publishes)
+    //  [10] -> state complete (barrier, histogram clear, S, T_chain)  [11] -> block written out (and the mirror's stores retired)
+    //  [12] -> fences / barrier in front of seq done  [13] -> seq stored  [14] decision -> seq stored
+    //      (taken behind the publication, by a solve that publishes itself only: they reach the host with the NEXT block this
+    //       context publishes, i.e. they describe the registration before)
+    const bool eg_stamp = stamp && (abl & 131072) != 0;
+    unsigned long long eg[3] = {0, 0, 0};
     if (tid < 64) {  // the controller's wavefront (publishes the hand-off)
 #ifdef SO_LM_STAMPS
-      const int more_ = lm_control_wave(slot, st, sh_S, sh_sums, sh_ctl, &sh.part_odd[0][0], hand, want, sh.pose, &sh.reg_done, tid, (slot == 1 && tid == 0) ? st->dbg : nullptr);
+      unsigned long long* const lm_dbg = (slot == 1 && tid == 0) ? sw->dbg : nullptr;
 #else
-      const int more_ = lm_control_wave(slot, st, sh_S, sh_sums, sh_ctl, &sh.part_odd[0][0], hand, want, sh.pose, &sh.reg_done, tid);
+      unsigned long long* const lm_dbg = nullptr;
 #endif
+      const int more_ = lm_control_wave<kPtol, PROF>(slot, sw, sh_S, sh_sums, sh_ctl, &sh.part_odd[0][0], hand, want, sh.pose, &sh.reg_done, tid, lm_dbg,
+                                               (PROF && eg_stamp) ? eg : nullptr);
       if (tid == 0) sh_more = more_;
     }
     __syncthreads();
     if (stamp) T.ctl = wall_clock64();
     if (!sh_more) {  // the solve is over: histogram replicas cleared for the next outer iteration, state to memory, publish
       hist[tid] = 0; hist[256 + tid] = 0;
-      if (PEER && ep.peer_world > 1 && tid == 0) st->peer_seq = sh.peer_seq;
-      if (tid < (int)(sizeof(LmState) / 8))
-        __hip_atomic_store(reinterpret_cast<double*>(&st->S) + tid, reinterpret_cast<const double*>(&sh_S)[tid], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-      // the guess of a chained registration behind this one (so_icp_register_sequence): this result o the delta the launch carries
-      if (!BATCH && ep.chain_next && sh.reg_done && tid == 0) {
-        double tf[7], nx[7];
-        for (int i = 0; i < 7; ++i) tf[i] = sh_S.x[i];  // (= DevState::T_final)
-        pose_compose(tf, ep.chain_delta, nx);
-        for (int i = 0; i < 7; ++i) st->T_chain[i] = nx[i];
-      }
+      if (PROF && eg_stamp && tid == 0) { sw->dbg[8] = eg[1] - eg[0]; sw->dbg[9] = eg[2] - eg[1]; sw->dbg[15] = (unsigned long long)(slot + 1); }
       // (a solve that does not end the registration may leave the report to the next k-NN launch, see EvalParams)
-      if (!ep.defer_publish || sh.reg_done) publish_state(st, ep, sh_ctl.outer_iter, tid, 256);
+      const bool publish = !ep.defer_publish || sh.reg_done;
+      unsigned long long eg_late[4] = {0, 0, 0, 0};
+      if constexpr (kImage) {
+        if (PEER && ep.peer_world > 1 && tid == 0) sw->peer_seq = sh.peer_seq;
+        if (tid < (int)(sizeof(LmState) / 8)) reinterpret_cast<double*>(&sw->S)[tid] = reinterpret_cast<const double*>(&sh_S)[tid];
+        // the guess of a chained registration behind this one (so_icp_register_sequence): this result o the delta the launch carries
+        // -- on a wavefront of its own, beside the copy of S
+        if (ep.chain_next && sh.reg_done && tid == 128) {
+          double tf[7], nx[7];
+          for (int i = 0; i < 7; ++i) tf[i] = sh_S.x[i];  // (= DevState::T_final)
+          pose_compose(tf, ep.chain_delta, nx);
+          for (int i = 0; i < 7; ++i) sw->T_chain[i] = nx[i];
+        }
+        __syncthreads();
+        if (PROF && eg_stamp) eg_late[0] = wall_clock64();
+        flush_state_image(st, publish ? ep.hring[sh_ctl.outer_iter & 1] : nullptr, sw, ep.seq_base | (unsigned long long)(sh_ctl.outer_iter + 1), tid,
+                          (PROF && eg_stamp) ? eg_late + 1 : nullptr);
+      } else {
+        if (PEER && ep.peer_world > 1 && tid == 0) st->peer_seq = sh.peer_seq;
+        if (tid < (int)(sizeof(LmState) / 8))
+          __hip_atomic_store(reinterpret_cast<double*>(&st->S) + tid, reinterpret_cast<const double*>(&sh_S)[tid], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        if (!BATCH && ep.chain_next && sh.reg_done && tid == 0) {
+          double tf[7], nx[7];
+          for (int i = 0; i < 7; ++i) tf[i] = sh_S.x[i];  // (= DevState::T_final)
+          pose_compose(tf, ep.chain_delta, nx);
+          for (int i = 0; i < 7; ++i) st->T_chain[i] = nx[i];
+        }
+        if (PROF && eg_stamp) eg_late[0] = wall_clock64();
+        if (publish) publish_state_to(ep.hring[sh_ctl.outer_iter & 1], st, ep.seq_base | (unsigned long long)(sh_ctl.outer_iter + 1), tid, 256, (PROF && eg_stamp) ? eg_late + 1 : nullptr);
+      }
+      if (PROF && eg_stamp && publish && tid == 0) {  // (a solve that leaves its report to the sweep keeps the last publishing solve's words)
+        const unsigned long long t_end = wall_clock64();
+        for (int i = 1; i < 4; ++i) if (!eg_late[i]) eg_late[i] = i == 3 ? t_end : eg_late[i - 1];  // (a segment this solve did not run: 0 ticks)
+        st->dbg[10] = eg_late[0] - eg[2]; st->dbg[11] = eg_late[1] - eg_late[0]; st->dbg[12] = eg_late[2] - eg_late[1];
+        st->dbg[13] = eg_late[3] - eg_late[2]; st->dbg[14] = eg_late[3] - eg[0];
+      }
     }
-    if (stamp && tid == 0 && (FIT || slot == 1)) store_stamps<FIT>(st, T, !FIT || BATCH);
+    if (stamp && tid == 0 && (FIT || (slot == 1 && !eg_stamp))) store_stamps<FIT>(sw, T, !FIT || BATCH);
     return sh_more ? kPassMore : kPassDone;
   }
   return hand_over_ticketed<FIT, PROF, PRIOR != 0>(slot, fuse_lm, mine, st, ep, partials, ticket, hist, out, sh, T, pose, prior);

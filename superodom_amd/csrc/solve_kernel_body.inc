@@ -9,6 +9,11 @@
 // functions it always launched.
   __shared__ EvalShared sh;
   __shared__ CorrCache cache;  // 26 KB next to the 64 KB of EvalShared: gfx950 has 160 KB of LDS per CU, one workgroup each here
+  // The non-batched launch's image of the state block up to `seq` (4 KB; workgroup 0 alone fills and uses it): loaded here, in the
+  // shadow of the fit pass; a solve that ends writes its results into it and the block goes out once (eval_pass, flush_state_image).
+  constexpr bool kStateImage = SO_ENDGAME_IMAGE != 0 && !BATCH;
+  __shared__ u4v state_image[kStateImage ? kStateChunks + 1 : 1];
+  DevState* const img = reinterpret_cast<DevState*>(state_image);
   unsigned long long t_entry = 0;
   if (PROF && !BATCH) t_entry = wall_clock64();  // (profiling: "kernel entry -> first pass begins", word 3 of the fit record)
   if (SO_ENTRY_WARM) st = after_loaded(st, kernarg_lines<decltype(&SO_BODY_KERNEL)>());
@@ -60,8 +65,15 @@
     sh.ctl.lm_max = st->lm_max; sh.ctl.outer_iter = st->outer_iter; sh.ctl.max_outer = st->max_outer;
   }
   const unsigned long long tag0 = (e0 + 1ull) << 5;  // pass tags: unique over launches (every launch advances the epoch) and passes (slot <= 16)
-  if (PROF && !BATCH && (ep.ablate & 128) && tid == 0 && blockIdx.x == 0) st->dbg[3] = wall_clock64() - t_entry;
-  int code = eval_pass<true, true, PROF, BATCH, PEER, SO_BODY_PRIOR>(0, 1, pose, spx, spy, spz, corr, st, ep, partials, ticket, hist, out, mpts, nbr5, mp, sh, SO_BODY_PRIOR_WORDS, tag0, &cache, hand, e0 + 1ull, span, prior_tm);
+  if (kStateImage && blockIdx.x == 0) {  // (nothing else writes *st while this launch runs: its kernels are one queue's, in order)
+    const u4v* block = reinterpret_cast<const u4v*>(st);
+    for (int i = tid; i < kStateChunks; i += 256) state_image[i] = block[i];
+  }
+  if (PROF && !BATCH && (ep.ablate & 128) && blockIdx.x == 0) {
+    if (kStateImage) __syncthreads();  // (the stamp's word has been loaded)
+    if (tid == 0) (kStateImage ? img : st)->dbg[3] = wall_clock64() - t_entry;
+  }
+  int code = eval_pass<true, true, PROF, BATCH, PEER, SO_BODY_PRIOR>(0, 1, pose, spx, spy, spz, corr, st, ep, partials, ticket, hist, out, mpts, nbr5, mp, sh, SO_BODY_PRIOR_WORDS, tag0, &cache, hand, e0 + 1ull, span, prior_tm, img);
   for (int slot = 1; slot <= lm_max; ++slot) {
     __syncthreads();
     const unsigned long long want = e0 + (unsigned long long)slot;
@@ -91,5 +103,5 @@
     if (sh.more != 1) return;  // solve ended (or timeout)
     pose = pose_from_array(sh.pose);
     __syncthreads();
-    code = eval_pass<false, true, PROF, BATCH, PEER, SO_BODY_PRIOR>(slot, 1, pose, spx, spy, spz, corr, st, ep, partials, ticket, hist, out, mpts, nbr5, mp, sh, SO_BODY_PRIOR_WORDS, tag0 + (unsigned long long)slot, &cache, hand, want + 1ull, span, prior_tm);
+    code = eval_pass<false, true, PROF, BATCH, PEER, SO_BODY_PRIOR>(slot, 1, pose, spx, spy, spz, corr, st, ep, partials, ticket, hist, out, mpts, nbr5, mp, sh, SO_BODY_PRIOR_WORDS, tag0 + (unsigned long long)slot, &cache, hand, want + 1ull, span, prior_tm, img);
   }

@@ -4,6 +4,11 @@
 Usage on a GPU box:  SOICP_ABLATE=128 python tools/eval_stamps.py [--workload os1_128_2m]
 Prints microseconds per phase for the FIT (slot 0) and the plain evaluation launch, averaged over registrations.
 wall_clock64 ticks at 100 MHz on gfx950 (10 ns).
+
+--endgame (sets SOICP_ABLATE=131200 = 128 | 131072): words 8..15 carry the END-GAME record of the solve that ended last instead of the
+evaluation pass's (kernels.hip eval_pass): the segments between the controller's decision that a solve is over and the `seq` store of
+its publication, and the passes the launch ran.  The segments behind the copy of the block are stamped after it has gone out: the
+host sees them with the next block the context publishes, i.e. they belong to the registration before.
 """
 import argparse
 import os
@@ -13,10 +18,14 @@ import numpy as np
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
+if "--endgame" in sys.argv:
+    os.environ["SOICP_ABLATE"] = str(128 | 131072)
 os.environ.setdefault("SOICP_ABLATE", "128")
 
 from superodom_amd import binding, synth  # noqa: E402
 
+ENDGAME = ["decision->hand-off issued", "->solve_finished+JtJ", "->state complete", "->block out (mirror stores retired)", "->fences/barrier",
+           "->seq stored", "decision->seq stored"]
 NAMES = ["loop", "lds_reduce+store", "ticket", "load_partials", "reduce+sums", "lm", "total", "controller"]
 # persistent solve (solve_kernel): the fit record has no "load_partials" phase, its word 3 is "kernel entry -> first pass begins"
 
@@ -28,6 +37,7 @@ def main():
     ap.add_argument("--scan", type=int, default=0, help="scan (and guess) of the trajectory registered by the plain loop")
     ap.add_argument("--staged", action="store_true", help="the bench's stream: four scans in rotation, each announced during the registration before it "
                                                            "(so_icp_stage_scan from pinned memory) -- the sweeps then run on chunks binned AHEAD, under the previous guess")
+    ap.add_argument("--endgame", action="store_true", help="end-game record of the solve that ended last in place of the evaluation pass's record")
     a = ap.parse_args()
     sc = synth.Scene(a.workload)
     slam = binding.LidarSlamGpu(device_id=0, plane_res=sc.plane_res, line_res=sc.plane_res / 2, max_iterations=5,
@@ -126,6 +136,11 @@ def main():
             if len(idle):
                 print("   idle workgroups: start offset p50 %.1f max %.1f us" % (np.percentile((idle[:, 0] - t0) * 0.01, 50), ((idle[:, 0] - t0) * 0.01).max()))
     print("solve: kernel entry -> first pass begins (us): %.2f  (controller's workgroup, thread 0; word 3 of the fit record)" % acc[0][3])
+    if a.endgame:
+        print("fit ", {n: round(float(v), 2) for n, v in zip(NAMES, acc[0])})
+        print("end game of the registration's last solve (us):", {n: round(float(v), 2) for n, v in zip(ENDGAME, acc[1][:7])})
+        print("passes run by that solve launch: %.2f" % (acc[1][7] * 100.0))
+        return
     for k, row in zip(("fit ", "eval"), acc):
         print(k, {n: round(float(v), 2) for n, v in zip(NAMES, row)})
 
