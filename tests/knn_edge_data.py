@@ -15,7 +15,12 @@ surfaces never reach:
               key's index field, around the 384-candidate tile and its multiples, around the 96 candidates / 1024 block points
               of a packed row
   faces       queries within 1e-3 m of a cube face, on it, at cube edges and corners, with the nearest map points across the
-              face; cubes of 4, 5 and 6 points; the last cube of the 21 x 21 x 11 window and a query beyond it
+              face; cubes of 1 .. 6 points; the last cube of the 21 x 21 x 11 window and a query beyond it; at planeRes 0.2, 0.4
+              (45 cells of 50/45 m) and 0.8 (32 cells)
+  gate_edge   the neighbour-distance gate d2[4] > 3 * planeRes: per direction and placement of the query a fifth neighbour exactly ON
+              the gate (or at the last float configuration inside it) and the float-adjacent one outside; planeRes 0.2, 0.33, 0.4, 0.8
+  cell_faces  map points and queries on interior cell faces of the grids whose cell is no binary fraction (57 and 45 cells per cube)
+  nonfinite_rows  NaN, +-inf and 1e12 written into rows of a scan (a function of a scan, not a family)
   xruns       scans for the binned-ahead path: chunks of queries from all over a lattice (more than 16 / 32 x-runs) and with lanes in
               eight cubes
   boundary_block  one chunk whose near block begins at the cube's own face (not a member of FAMILIES: one dedicated device test)
@@ -317,12 +322,28 @@ def dense(seed=4, n_cubes=7, site_list=None, name="dense"):
 # ------------------------------------------------------------------------------------------------------------------------
 # 4. cube faces and the window
 # ------------------------------------------------------------------------------------------------------------------------
-def faces(seed=5):
-    """planeRes 0.2.  A site sits at a point c of a cube face, edge or corner: a lattice of 2 m around c, thinned out INSIDE the
-    queries' own cube to the points at least 0.45 m (Chebyshev) from c, so that the points across the face are the nearest ones.  The
-    queries lie in one cube per site: the high side (on the face itself, one ulp, 1e-4 and 1e-3 beyond it) or the low side."""
+def _leaf(p, plane_res):
+    """the voxel filter's leaf of a point (the expression the Family constructor asserts with)"""
+    return np.floor(np.asarray(p, np.float32) * np.float32(np.float32(1.0) / np.float32(plane_res))).astype(np.int64)
+
+
+def _first_per_leaf(points, plane_res):
+    """drop every point whose leaf an earlier point of the list occupies (the order of the others is kept)"""
+    _, first = np.unique(_leaf(points, plane_res), axis=0, return_index=True)
+    return points[np.sort(first)]
+
+
+def faces(plane_res=0.2, seed=5):
+    """A site sits at a point c of a cube face, edge or corner: a lattice of 5 pitches (pitch = planeRes; 2 m at 0.2) around c, thinned
+    out INSIDE the queries' own cube to the points at least 2.25 pitches (0.45 m at 0.2; Chebyshev) from c, so that the points across the
+    face are the nearest ones.  The queries lie in one cube per site: the high side (on the face itself, one ulp, 1e-4 and 1e-3 beyond
+    it) or the low side.  Lattice, thinning radius and the queries' tangential offsets scale with planeRes (s = planeRes / 0.2); the sites
+    stay where they are, so at 0.4 and 0.8 their lattices overlap: every site's hole is cut out of every lattice and a leaf keeps the first
+    point that falls into it.  At 0.2 neither does anything, and the first `n_map_v1` map points / `n_queries_v1` queries are the bytes
+    the family had before it took planeRes.  Behind them: cubes of exactly 1, 2 and 3 points."""
     rng = np.random.default_rng(seed)
-    plane_res, pitch = 0.2, 0.2
+    pitch = plane_res
+    s = plane_res / 0.2
     mp, qs = [], []
     f32 = np.float32
 
@@ -350,44 +371,65 @@ def faces(seed=5):
             for hz in (True, False):
                 c = np.array([25.0 if hx else -25.0, -25.0 if hy else 25.0, 25.0 if hz else -25.0])
                 site_list.append(({0: (c[0], hx), 1: (c[1], hy), 2: (c[2], hz)}, c))
-    seen = {}
+    seen, holes = {}, []
     for axes, c in site_list:
         key = tuple(c)
         assert key not in seen, "every site has a lattice of its own"
-        g = _grid(_centres(c[0] - 1.0, c[0] + 1.0, pitch), _centres(c[1] - 1.0, c[1] + 1.0, pitch), _centres(c[2] - 1.0, c[2] + 1.0, pitch)).astype(np.float32)
+        g = _grid(_centres(c[0] - 1.0 * s, c[0] + 1.0 * s, pitch), _centres(c[1] - 1.0 * s, c[1] + 1.0 * s, pitch),
+                  _centres(c[2] - 1.0 * s, c[2] + 1.0 * s, pitch)).astype(np.float32)
         vals = [None, None, None]
         for a in range(3):
             if a in axes:
                 vals[a] = side_values(*axes[a])
             else:
-                vals[a] = [f32(c[a] + d) for d in (0.0, 0.1, -0.23) + tuple(rng.uniform(-0.3, 0.3, 1))]
+                vals[a] = [f32(c[a] + d * s) for d in (0.0, 0.1, -0.23) + tuple(rng.uniform(-0.3, 0.3, 1))]
         q = _grid(*vals).astype(np.float32)
         qcube = cube_of(q)
         assert (qcube == qcube[0]).all()
-        own = (cube_of(g) == qcube[0]).all(1)
-        near = np.abs(g.astype(np.float64) - c).max(1) < 0.45
-        seen[key] = g[~(own & near)]
+        seen[key] = g
+        holes.append((qcube[0], c))
         qs.append(q)
-    mp += list(seen.values())
+
+    def thinned(g):
+        for qcube, c in holes:
+            g = g[~((cube_of(g) == qcube).all(1) & (np.abs(g.astype(np.float64) - c).max(1) < 0.45 * s))]
+        return g
+
+    mp += [thinned(g) for g in seen.values()]
+
+    def small_cube(n, cx):
+        pts = np.array([cx, 10.0, 0.0]) + s * (np.arange(n)[:, None] * np.array([0.25, 0.0, 0.0]) + np.array([[0, 0.3 * (i % 2), 0.3 * (i % 3)] for i in range(n)]))
+        return [pts.astype(np.float32)], [(pts[:3] + s * np.array([0.05, 0.02, -0.04])).astype(np.float32),
+                                          np.array([[cx + 0.6 * s, 10.0 + 0.1 * s, 0.2 * s], [cx - 3.0, 9.0, 0.0]], np.float32)]
+
     # cubes holding exactly 4, 5 and 6 points
     for n, cx in ((4, 150.0), (5, 200.0), (6, 250.0)):
-        pts = np.array([cx, 10.0, 0.0]) + (np.arange(n)[:, None] * np.array([0.25, 0.0, 0.0]) + np.array([[0, 0.3 * (i % 2), 0.3 * (i % 3)] for i in range(n)]))
-        mp.append(pts.astype(np.float32))
-        qs.append((pts[:3] + np.array([0.05, 0.02, -0.04])).astype(np.float32))
-        qs.append(np.array([[cx + 0.6, 10.1, 0.2], [cx - 3.0, 9.0, 0.0]], np.float32))
+        m_, q_ = small_cube(n, cx)
+        mp += m_; qs += q_
     # the last cube of the window in x (cubes -10 .. 10 around a sensor at the origin: x in [-525, 525)) and beyond it
-    edge = _grid(_centres(523.0, 525.0, pitch), _centres(-1.0, 1.0, pitch), _centres(-1.0, 1.0, pitch)).astype(np.float32)
-    edge = edge[edge[:, 0] < f32(524.95)]
+    edge = _grid(_centres(525.0 - 2.0 * s, 525.0, pitch), _centres(-1.0 * s, 1.0 * s, pitch), _centres(-1.0 * s, 1.0 * s, pitch)).astype(np.float32)
+    edge = edge[edge[:, 0] < f32(525.0 - 0.05 * s)]
     mp.append(edge)
-    eq = _grid([f32(524.0), f32(524.9), np.nextafter(f32(525.0), f32(-np.inf)), f32(525.0), f32(525.5), f32(-526.0)], [f32(0.0), f32(0.31)], [f32(0.1), f32(-0.45)])
+    eq = _grid([f32(525.0 - 1.0 * s), f32(525.0 - 0.1 * s), np.nextafter(f32(525.0), f32(-np.inf)), f32(525.0), f32(525.5), f32(-526.0)],
+               [f32(0.0), f32(0.31 * s)], [f32(0.1 * s), f32(-0.45 * s)])
     qs.append(eq.astype(np.float32))
     # first and last cell of a cube, away from any site: the clamped neighbourhood over an ordinary lattice
     for cx in (-24.9, 24.9):
-        g = _grid(_centres(cx - 1.0 if cx > 0 else -25.0, 25.0 if cx > 0 else cx + 1.0, pitch), _centres(-20.0, -18.0, pitch), _centres(3.0, 5.0, pitch))
-        mp.append(g.astype(np.float32))
-        qs.append((np.array([cx, -19.0, 4.0]) + rng.uniform(-0.08, 0.08, (40, 3))).astype(np.float32))
+        g = _grid(_centres(cx - 1.0 * s if cx > 0 else -25.0, 25.0 if cx > 0 else cx + 1.0 * s, pitch), _centres(-19.0 - 1.0 * s, -19.0 + 1.0 * s, pitch),
+                  _centres(4.0 - 1.0 * s, 4.0 + 1.0 * s, pitch))
+        mp.append(thinned(g.astype(np.float32)))
+        qs.append((np.array([cx, -19.0, 4.0]) + s * rng.uniform(-0.08, 0.08, (40, 3))).astype(np.float32))
     n_face = sum(len(q) for q in qs[:len(site_list)])
-    return Family("faces", np.concatenate(mp), np.concatenate(qs), plane_res, n_face_queries=n_face, aim="faces")
+    n_map_v1, n_queries_v1 = sum(map(len, mp)), sum(map(len, qs))
+    # cubes holding exactly 1, 2 and 3 points (behind everything the family had before)
+    for n, cx in ((1, 300.0), (2, 350.0), (3, 400.0)):
+        m_, q_ = small_cube(n, cx)
+        mp += m_; qs += q_
+    mp = np.concatenate(mp)
+    if s != 1.0:
+        mp = _first_per_leaf(mp, plane_res)
+    name = "faces" if plane_res == 0.2 else f"faces_{plane_res}"
+    return Family(name, mp, np.concatenate(qs), plane_res, n_face_queries=n_face, n_map_v1=n_map_v1, n_queries_v1=n_queries_v1, aim="faces")
 
 
 def nearest_across(map_points, queries):
@@ -445,6 +487,268 @@ def boundary_block(seed=7):
     return Family("boundary_block", mp, q.astype(np.float32), pitch, aim="cover")
 
 
+# ------------------------------------------------------------------------------------------------------------------------
+# 6. the neighbour-distance gate: d2[4] > 3 * planeRes (float product) rejects the query
+# ------------------------------------------------------------------------------------------------------------------------
+def cell_of(p, plane_res):
+    """cell of a point inside its cube: the fp64 expression of locate (kernels.hip) / cell_coords (map_kernels.hip) on the point's
+    own float coordinates"""
+    nc, cell = grid_cells(plane_res)
+    p64 = np.asarray(p, np.float32).astype(np.float64)
+    mn = cube_of(p).astype(np.float64) * CUBE - 25.0
+    return np.clip(np.floor((p64 - mn) * (1.0 / cell)).astype(np.int64), 0, nc - 1)
+
+
+def gate_of(plane_res):
+    return np.float32(3) * np.float32(plane_res)
+
+
+_GG = 2.0 ** -12   # grid of every coordinate of a gate site but the tuned one
+_EPS = 2.0 ** -11  # "within 1e-3 m" of a cell or cube face
+GATE_DIRECTIONS = tuple((dx, dy, dz) for dx in (1, 0, -1) for dy in (1, 0, -1) for dz in (1, 0, -1) if (dx, dy, dz) != (0, 0, 0))
+GATE_PLACEMENTS = ("cell_middle", "cell_face", "cell_corner", "cube_face")
+
+
+def _ordered(x):
+    """float32 -> integers in the order of the floats (one step = the adjacent float)"""
+    i = np.asarray(x, np.float32).view(np.int32).astype(np.int64)
+    return np.where(i >= 0, i, -(i & 0x7FFFFFFF))
+
+
+def _unordered(o):
+    o = np.asarray(o, np.int64)
+    return np.where(o >= 0, o, (-o) | 0x80000000).astype(np.uint32).view(np.float32)
+
+
+def _sphere(n):
+    """n fixed unit vectors spread over the sphere"""
+    i = np.arange(n) + 0.5
+    z = 1 - 2 * i / n
+    phi = i * np.pi * (3 - np.sqrt(5.0))
+    return np.c_[np.sqrt(1 - z * z) * np.cos(phi), np.sqrt(1 - z * z) * np.sin(phi), z]
+
+
+def gate_edge(plane_res):
+    """A site: one query q, four map points at 0.8 r (r^2 = gate = float32(3) * float32(planeRes)) and a fifth ON the gate, along one
+    of the 26 axis / face-diagonal / space-diagonal directions.  The fifth is tuned in ONE coordinate (axis t: the first the direction
+    moves along), float by float: the `in` site of a pair holds the last configuration with d2_ref <= gate -- d2_ref == gate wherever a
+    small change of the fifth's offset along another axis reaches it (`n_equal` sites) --, the `out` site the float-adjacent one with
+    d2_ref > gate.  The two sites of a pair are the same configuration `shift` metres apart along axis s = t + 1: a whole number of
+    cells that is exact on the 2^-12 grid all s coordinates lie on, so the pair differs by that one float and by nothing else.  Every
+    other out site holds a sixth point at 1.3 r.
+    Four placements of the query per direction: the middle of a cell; 2^-11 m inside the cell face the direction (axis t) points at (the
+    fifth lies in the far part of the next cell); at the cell corner the direction points at (the fifth in the cell diagonally
+    opposite, for a space diagonal the corner cell of the 27-cell block); 2^-11 m inside a cube face (axis f = t + 2) with the fifth
+    inside the cube.  Axis t coordinates stay within 8 m of the origin (a float step there moves d2 by a few of its ulps); the sites
+    spread along s and f, 6 m apart; the three groups t = x, y, z lie in different cubes.
+    `patch`, `scan_a`, `pose_a`: a second registration far away for the binned-ahead path (see xruns)."""
+    from fractions import Fraction
+    f32, f64 = np.float32, np.float64
+    gate = gate_of(plane_res)
+    r = np.sqrt(f64(gate))
+    nc, cell = grid_cells(plane_res)
+    k = next(k for k in range(1, 200) if Fraction(50 * k, nc) >= 6 and (Fraction(50 * k, nc) / Fraction(1, 4096)).denominator == 1)
+    shift = float(Fraction(50 * k, nc))
+    snap = lambda v: np.round(np.asarray(v, f64) / _GG) * _GG
+    sphere = _sphere(96)
+    used = set()
+    group_off = {0: np.zeros(3), 1: np.array([100.0, 0.0, 0.0]), 2: np.array([0.0, -100.0, 0.0])}  # (axis f of the group: two cubes away)
+    rows = {}  # (group t, a row at a cube face?, its low face?) -> pairs handed out; a row holds per_row pairs along s
+    per_row = int((92.0 - shift) // (2 * shift)) + 1
+    regular = [(xt, xf) for xt in (-6.0, 0.0, 6.0) for xf in (-18.0, -12.0, -6.0, 0.0, 6.0, 12.0, 18.0)]
+    mp, qs, sites = [], [], []
+    n_equal = 0
+
+    def tune(q, p, t, f, sg):
+        """the float-adjacent pair of p[t] around the gate, moving away from q; the jitter of p[f] that reaches d2 == gate first"""
+        best = None
+        for j in range(96):
+            pj = p.copy()
+            pj[f] = p[f] + j * 2.0 ** -14
+            rest = sum(f64(f32(f32(q[a]) - f32(pj[a]))) ** 2 for a in range(3) if a != t)
+            o0 = _ordered(f32(q[t] + sg * np.sqrt(f64(gate) - rest)))
+            cand = np.repeat(pj.astype(f32)[None], 129, 0)
+            cand[:, t] = _unordered(o0 + sg * np.arange(-64, 65))
+            dd = d2_ref(q.astype(f32), cand)
+            assert (np.diff(dd) >= 0).all() and dd[0] <= gate < dd[-1]
+            i = int(np.nonzero(dd <= gate)[0][-1])
+            if best is None or dd[i] == gate:
+                best = (cand[i].copy(), cand[i + 1].copy(), bool(dd[i] == gate))
+            if dd[i] == gate:
+                break
+        return best
+
+    for pair, (d, placement) in enumerate((d, pl) for d in GATE_DIRECTIONS for pl in GATE_PLACEMENTS):
+        d = np.array(d)
+        t = int(np.nonzero(d)[0][0]); s = (t + 1) % 3; f = (t + 2) % 3
+        sg = int(d[t])
+        cube_face = placement == "cube_face"
+        low_face = d[f] >= 0
+        kind = (t, cube_face, low_face and cube_face)
+        n_in_kind = rows.get(kind, 0)
+        rows[kind] = n_in_kind + 1
+        row, m = divmod(n_in_kind, per_row)
+        nominal = np.zeros(3)
+        if cube_face:
+            nominal[t] = (-6.0, 0.0, 6.0)[row]
+        else:
+            nominal[t], nominal[f] = regular[row]
+        nominal[s] = -71.0 + m * 2 * shift
+        kk = np.floor((nominal + 25.0) / cell)
+        lo, hi = -25.0 + kk * cell, -25.0 + (kk + 1) * cell
+        q = snap(0.5 * (lo + hi))
+        toward = lambda a: snap(hi[a] - _EPS) if d[a] > 0 else snap(lo[a] + _EPS)  # (an axis the direction does not move along: the low side)
+        if placement == "cell_face":
+            q[t] = toward(t)
+        if placement == "cell_corner":
+            q = np.array([toward(a) for a in range(3)])
+        if cube_face:
+            q[f] = -25.0 + _EPS if low_face else 25.0 - _EPS
+        q = q + group_off[t]
+        assert np.array_equal(q.astype(f32).astype(f64), q)
+        p = q + snap(r * d / np.linalg.norm(d))
+        p_in, p_out, equal = tune(q, p, t, f, sg)
+        n_equal += equal
+        assert (cube_of(p_in) == cube_of(q)).all() and (cube_of(p_out) == cube_of(q)).all(), (plane_res, pair, "the fifth lies in the query's cube")
+        sh = np.zeros(3); sh[s] = shift
+        cfg_in = [q.astype(f32), p_in]
+        cfg_out = [(q + sh).astype(f32), (p_out.astype(f64) + sh).astype(f32)]
+        assert np.array_equal(cfg_out[1].astype(f64), p_out.astype(f64) + sh), "the shift is exact"
+
+        def free(c):
+            """c (at the in site) and its copy at the out site: on the grid, in the query's cube, in leaves nobody holds"""
+            both = np.stack([c, c + sh])
+            if not np.array_equal(both.astype(f32).astype(f64), both):
+                return None
+            if not ((cube_of(both[0]) == cube_of(q)).all() and (cube_of(both[1]) == cube_of(q + sh)).all()):
+                return None
+            leaves = [tuple(l) for l in _leaf(both, plane_res)]
+            return None if (leaves[0] in used or leaves[1] in used or leaves[0] == leaves[1]) else leaves
+
+        for l in _leaf(np.stack([p_in, p_out, cfg_out[1], (p_in.astype(f64) + sh).astype(f32)]), plane_res):
+            used.add(tuple(l))
+        near = []
+        for u in sphere[np.argsort(-(sphere @ d), kind="stable")]:  # (nearest to the direction first: inside the cube at a cube face)
+            c = q + snap(0.8 * r * u)
+            leaves = free(c)
+            if leaves is None or not (d2_ref(q.astype(f32), c.astype(f32)[None])[0] < 0.75 * gate):
+                continue
+            used.update(leaves); near.append(c)
+            if len(near) == 4:
+                break
+        assert len(near) == 4, (plane_res, pair, "four nearer points")
+        sixth = None
+        if pair % 2 == 0:
+            for u in sphere[np.argsort(sphere @ d, kind="stable")]:
+                c = q + snap(1.3 * r * u)
+                leaves = free(c)
+                if leaves is not None:
+                    used.update(leaves); sixth = c
+                    break
+            assert sixth is not None
+        dname = "".join(("-", "0", "+")[v + 1] for v in d)
+        for side, (qq, p5), off in (("in", cfg_in, np.zeros(3)), ("out", cfg_out, sh)):
+            pts = [(c + off).astype(f32) for c in near] + [p5] + ([(sixth + off).astype(f32)] if side == "out" and sixth is not None else [])
+            sites.append(dict(name=f"{dname}/{placement}/{side}", direction=tuple(d), placement=placement, side=side, query=len(qs),
+                              first_point=sum(map(len, mp)), fifth=sum(map(len, mp)) + 4, n_points=len(pts), equal=bool(equal and side == "in"),
+                              tuned_axis=t, shift_axis=s, sixth=len(pts) == 6))
+            mp.append(np.array(pts, f32)); qs.append(qq)
+    pitch = plane_res
+    patch = _grid(_centres(-3 * pitch, 3 * pitch, pitch), _centres(150.0 - 3 * pitch, 150.0 + 3 * pitch, pitch), _centres(50.0 - 3 * pitch, 50.0 + 3 * pitch, pitch))
+    mp.append(patch.astype(f32))
+    g = np.arange(-20.0, 20.0, 0.8)
+    scan_a = _grid(g, g, np.array([-50.8, -50.0, -49.2])).astype(f32)
+    return Family(f"gate_edge_{plane_res}", np.concatenate(mp), np.array(qs, f32), plane_res, sites=sites, n_equal=n_equal, shift=shift,
+                  gate=gate, scan_a=scan_a, pose_a=XRUNS_POSE_A, aim="gate")
+
+
+# ------------------------------------------------------------------------------------------------------------------------
+# 7. interior cell faces of grids whose cell is no binary fraction (57 cells at planeRes 0.25, 45 at 0.4)
+# ------------------------------------------------------------------------------------------------------------------------
+def _around(face_exact):
+    """the largest float below an exact (rational) coordinate and the smallest at or above it"""
+    from fractions import Fraction
+    v = np.float32(float(face_exact))
+    if Fraction(float(v)) >= face_exact:
+        return np.nextafter(v, np.float32(-np.inf)), v
+    return v, np.nextafter(v, np.float32(np.inf))
+
+
+def cell_faces(plane_res, seed=8):
+    """Cube (0, 0, 0); cell faces -25 + k * (50 / nc) for k = 1, nc // 2 and nc - 1.  A site lies on one face (each axis), on an edge
+    (two faces) or at a corner (three) of a cell, its queries on ONE side of every face of the site: at the nearest float at or above
+    the face and 1e-4 m above it (high), or at the nearest float below it and 1e-4 m below it (low).  Around the site a lattice of leaf
+    centres (pitch = planeRes), with a hole of 2.25 pitches on the queries' side, and -- per face -- four map points ON it, at those
+    same four coordinates, each in a leaf of its own next to the site's centre: the nearest neighbours of a query lie at and across
+    the cell face, in the cell the fp64 expression of the product puts them in.  `info`: the cell of every map point and query
+    (cell_of), the sites, and per face its exact position."""
+    from fractions import Fraction
+    f32 = np.float32
+    nc, cell = grid_cells(plane_res)
+    pitch = plane_res
+    specials, lattices, qs, holes, sites, face_values = [], [], [], [], [], {}
+    n = 0
+    for k in (1, nc // 2, nc - 1):
+        exact = Fraction(-25) + k * Fraction(50, nc)
+        below, at = _around(exact)
+        face_values[k] = (exact, below, at)
+        four = [below, at, f32(float(exact) - 1e-4), f32(float(exact) + 1e-4)]
+        for i, axes in enumerate(((0,), (1,), (2,), (0, 1), (0, 2), (1, 2), (0, 1, 2))):
+            for high in (True, False):
+                u = -22.0 + 3.4 * (2 * i + high) + 0.37
+                c = np.array([float(exact) if a in axes else u for a in range(3)])
+                cent = [_centres(c[a] - 4 * pitch, c[a] + 4 * pitch, pitch) for a in range(3)]
+                mid = [int(np.searchsorted(cent[a], c[a])) for a in range(3)]
+                lattices.append(_grid(*cent).astype(f32))
+                holes.append((axes, high, at, c))
+                for a in (axes if high or len(axes) < 3 else ()):  # (a corner's two sites share their centre and these points)
+                    b, e = (a + 1) % 3, (a + 2) % 3
+                    for j, v in enumerate(four):
+                        p = np.zeros(3, f32)
+                        p[a], p[b], p[e] = v, cent[b][mid[b] + j - 2], cent[e][mid[e] - 1 + a]
+                        specials.append(p)
+                vals = [([at, four[3]] if high else [below, four[2]]) if a in axes else [f32(c[a] + o * pitch) for o in (0.0, 0.5, -1.15)] for a in range(3)]
+                q = _grid(*vals).astype(f32)
+                sites.append(dict(k=k, axes=axes, high=high, first_query=n, n_queries=len(q)))
+                n += len(q)
+                qs.append(q)
+    lat = np.concatenate(lattices)
+    lat = lat[(cube_of(lat) == 0).all(1)]
+    for axes, high, at, c in holes:
+        own = np.all([(lat[:, a] >= at) == high for a in axes], axis=0)
+        lat = lat[~(own & (np.abs(lat.astype(np.float64) - c).max(1) < 2.25 * pitch))]
+    specials = _first_per_leaf(np.array(specials, f32), plane_res)  # (where two sites meet, the first one's point holds the leaf)
+    mp = _first_per_leaf(np.concatenate([specials, lat]), plane_res)
+    assert np.array_equal(mp[:len(specials)], specials)
+    for k, (exact, below, at) in face_values.items():
+        for a in range(3):
+            assert (specials[:, a] == below).any() and (specials[:, a] == at).any(), "map points float-adjacent across every face, on every axis"
+    q = np.concatenate(qs)
+    return Family(f"cell_faces_{plane_res}", mp, q, plane_res, n_on_faces=len(specials), sites=sites, face_values=face_values,
+                  map_cells=cell_of(mp, plane_res), query_cells=cell_of(q, plane_res), aim="cells")
+
+
+# ------------------------------------------------------------------------------------------------------------------------
+# 8. scan rows that are not finite, or far outside any window
+# ------------------------------------------------------------------------------------------------------------------------
+def nonfinite_rows(scan):
+    """A copy of the scan with NaN, +inf, -inf and 1e12 in single coordinates (every value on every axis) of its first and last row, of
+    rows 63 and 64, of a run of 64 consecutive rows and of a run of 16; and the sorted list of those rows."""
+    out = np.array(scan, np.float32, copy=True)
+    n = len(out)
+    assert n >= 1024
+    rows = np.array([0, 63, 64] + list(range(n // 4 + 3, n // 4 + 67)) + list(range(n // 2 + 5, n // 2 + 21)) + [n - 1])
+    assert len(np.unique(rows)) == len(rows) == 84 and (np.diff(rows) > 0).all()
+    bad = (np.float32(np.nan), np.float32(np.inf), np.float32(-np.inf), np.float32(1e12))
+    for j, row in enumerate(rows):
+        out[row, j % 3] = bad[j % 4]
+    return out, rows
+
+
+GATE_RES = (0.2, 0.33, 0.4, 0.8)
+CELL_FACE_RES = (0.25, 0.4)
+NEW_FAMILIES = tuple(f"gate_edge_{r}" for r in GATE_RES) + tuple(f"cell_faces_{r}" for r in CELL_FACE_RES) + ("faces_0.4", "faces_0.8")
+
 FAMILIES = {
     "ties_volume_0.25": lambda: ties_volume(0.25),
     "ties_volume_0.125": lambda: ties_volume(0.125),
@@ -455,6 +759,10 @@ FAMILIES = {
     "dense": dense,
     "faces": faces,
     "xruns": xruns,
+    **{f"gate_edge_{r}": (lambda r=r: gate_edge(r)) for r in GATE_RES},
+    **{f"cell_faces_{r}": (lambda r=r: cell_faces(r)) for r in CELL_FACE_RES},
+    "faces_0.4": lambda: faces(0.4),
+    "faces_0.8": lambda: faces(0.8),
 }
 _cache = {}
 

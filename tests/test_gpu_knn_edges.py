@@ -3,12 +3,14 @@ through every implementation of the exact 5-NN contract -- Seam B (knn_only_kern
 registration with and without packed light chunks (knn_plane_kernel), its instrumented instantiation with the branch counters, the
 one-wavefront-per-query sweep (knn_query_wave_kernel) and the batched sweep -- against the oracle (its map loaded from export_map(),
 so the index orders coincide) and against the numpy reference.  EVERY query is compared and every comparison is exact: status
-bytes, neighbour coordinates, canonical indices, bits of d2."""
+bytes, neighbour coordinates, canonical indices, bits of d2.  The gate sites (gate_edge: a fifth neighbour ON d2[4] == 3 * planeRes
+and one float outside it, on four grids) are also checked by name; Seam B also for k = 1 .. 4; and a scan with NaN, +-inf and 1e12
+in some of its rows goes through the chunked sweep, the query waves, a scan binned ahead, a resident scan and a batch."""
 import numpy as np
 import pytest
 
 import knn_edge_data as ked
-from helpers import assert_follows_oracle, assert_same_bits
+from helpers import CARRIED_OVER_FIELDS, assert_follows_oracle, assert_same_bits
 
 pytestmark = pytest.mark.gpu
 
@@ -64,6 +66,17 @@ def _expect_status(fam, ref):
     gate = np.float64(np.float32(3) * np.float32(fam.plane_res))
     st = np.where(~found, 1, np.where(d2[:, 4].astype(np.float64) > gate, 2, 0))
     return st
+
+
+def _check_gate_sites(fam, ms, what):
+    """gate_edge under the identity: TOO_FAR on exactly the `out` sites, a judged status on exactly the `in` ones -- by site name"""
+    if fam.info["aim"] != "gate":
+        return
+    sites = fam.info["sites"]
+    not_far = [s["name"] for s in sites if s["side"] == "out" and ms[s["query"]] != 2]
+    not_judged = [s["name"] for s in sites if s["side"] == "in" and ms[s["query"]] not in JUDGED]
+    assert not not_far and not not_judged, (what, "out sites not TOO_FAR", not_far, "in sites not judged", not_judged,
+                                            "of them with d2[4] == gate exactly", [s["name"] for s in sites if s["equal"] and s["name"] in not_judged])
 
 
 CAP_PER_SLOT = 1 << 20  # a canonical index of the device map is (slot of the cube) * 2^20 + position inside the cube (device_map.h)
@@ -162,6 +175,7 @@ def test_registration_sweep(oracle, soicp, gpu_slam_factory, monkeypatch, name, 
     st, ms, nb = _register(slam, scan, IDENTITY)
     slam.close()
     assert not (st.flags & soicp.FLAG_QUERY_WAVES)
+    _check_gate_sites(fam, ms, (name, pack))
     assert np.array_equal(ms, corrs["status"]), (name, "status bytes against the oracle")
     assert np.array_equal(ms == 1, want_status == 1) and np.array_equal(ms == 2, want_status == 2)
     n = _check_lists(exp, scan, ms, nb, want_status == 0, rnbr, ridx, (name, pack, "identity, numpy"))
@@ -227,6 +241,7 @@ def test_query_wave_sweep(oracle, soicp, gpu_slam_factory, name):
         want_status = _expect_status(fam, (rf, ridx, rd2, rnbr))
         st, ms, nb = _register(slam, part, IDENTITY)
         assert st.flags & soicp.FLAG_QUERY_WAVES, hex(st.flags)
+        _check_gate_sites(fam, ms, (name, "query waves"))
         assert np.array_equal(ms == 1, want_status == 1) and np.array_equal(ms == 2, want_status == 2)
         _check_lists(exp, part, ms, nb, want_status == 0, rnbr, ridx, (name, lo, "query waves, numpy"))
         orc, _, _, corrs = om.register(part, IDENTITY, oracle.default_config(max_iterations=1), want_corrs=True)
@@ -354,3 +369,184 @@ def test_a_block_face_on_the_cube_boundary_does_not_limit_the_certificate(oracle
     _check_lists(exp, q, ms, nb, np.ones(len(q), bool), rnbr, ridx, "boundary_block")
     print(f"boundary_block: group passes {t.knn_group_passes}, fallback lanes {t.knn_fallback_lanes}")
     assert t.knn_group_passes == 1 and t.knn_fallback_lanes == 0
+
+
+# ------------------------------------------------------------------------------------------------------------------------
+# the gate family binned ahead; Seam B at every k; scan rows that are not finite
+# ------------------------------------------------------------------------------------------------------------------------
+def test_gate_sites_binned_ahead_at_0_8(oracle, soicp, gpu_slam_factory):
+    """The pattern of test_chunks_binned_ahead_under_another_pose with the gate sites of the coarsest grid (planeRes 0.8: cells of
+    1.5625 m, gate radius 1.549 m) as scan B: binned under pose A, where it meets no cube, B is cut into chunks of 64 in arrival order
+    -- queries of sites metres and cubes apart in one chunk, the largest block-local coordinates the selection key sees.  Same
+    repetition rule, same requirement that the scan WAS binned ahead at least once."""
+    fam, exp, om, scan, ref = _setup(oracle, gpu_slam_factory, "gate_edge_0.8")
+    slam = _product(gpu_slam_factory, fam)
+    A, B = slam.host_alloc_like(fam.info["scan_a"]), slam.host_alloc_like(scan)
+    orc, _, _, corrs = om.register(B, IDENTITY, oracle.default_config(max_iterations=1), want_corrs=True)
+    assert orc == 0
+    ws = _expect_status(fam, ref)
+    ahead = 0
+    for attempt in range(16):
+        slam.stage_scan(B)
+        rc, _, _ = slam.register(A, fam.info["pose_a"])
+        assert rc == 0, slam.last_error()
+        st, ms, nb = _register(slam, B, IDENTITY)
+        assert st.flags & soicp.FLAG_STAGED_SCAN
+        ahead += bool(st.flags & soicp.FLAG_BINNED_AHEAD)
+        _check_gate_sites(fam, ms, ("binned ahead", attempt))
+        assert np.array_equal(ms, corrs["status"]), attempt
+        assert np.array_equal(ms == 1, ws == 1) and np.array_equal(ms == 2, ws == 2)
+        n = _check_lists(exp, B, ms, nb, ws == 0, ref[3], ref[1], (attempt, "numpy"))
+        _check_lists(exp, B, ms, nb, ws == 0, corrs["nbr"].reshape(-1, 5, 3), None, (attempt, "oracle"))
+        assert n == 104
+        if ahead >= 2:
+            break
+    slam.close()
+    print(f"gate_edge_0.8: binned ahead {ahead} times in {attempt + 1} rounds")
+    assert ahead >= 1, "the scan was never binned ahead: the path was not exercised"
+
+
+@pytest.mark.parametrize("name", NAMES)
+def test_seam_b_every_k(oracle, gpu_slam_factory, name):
+    """k = 1 .. 4: found flags, d2 bits, neighbour coordinates and canonical indices against the oracle on EVERY query and against the
+    numpy reference (the first k of its 5-list where the cube holds five points -- which the product's own 5-list must equal too --,
+    brute_knn(k=k) itself where it holds fewer).  A cube of fewer than k points leaves the reference's buffer: unfilled slots name the
+    cube's first point with d2 0, slot k - 1 carries FLT_MAX.  A query without a cube: all zero, index -1."""
+    fam, exp, om, scan, ref = _setup(oracle, gpu_slam_factory, name)
+    q = fam.queries
+    rf5, ridx5, rd25, rnbr5 = (a[:len(q)] for a in ref)
+    counts = ked.cell_counts(exp, q)
+    assert np.array_equal(counts > 0, rf5)
+    few = (counts > 0) & (counts < 5)
+    ec = ked.cube_of(exp)
+    first = {tuple(ec[s]): exp[s] for s in np.nonzero(np.r_[True, (np.diff(ec, axis=0) != 0).any(1)])[0]}  # (export_map() lists a cube in one run)
+    slam = _product(gpu_slam_factory, fam)
+    f5, nbr5, d25, idx5 = slam.nearest_k_search_surf(q, 5)
+    for k in (1, 2, 3, 4):
+        found, nbr, d2, idx = slam.nearest_k_search_surf(q, k)
+        assert nbr.shape == (len(q), k, 3)
+        # -- the oracle, every query
+        of, onbr, od2, oidx, _ = om.knn(q, k, use_grid=1)
+        assert np.array_equal(found, of) and np.array_equal(found.astype(bool), rf5), (name, k)
+        f = rf5
+        assert np.array_equal(d2[f].view(np.uint32), od2[f].view(np.uint32)), (name, k, "oracle", "d2 bits")
+        assert np.array_equal(nbr[f].view(np.uint32), onbr[f].view(np.uint32)), (name, k, "oracle", "neighbour coordinates")
+        # -- numpy
+        wd2, wnbr, widx = rd25[:, :k].copy(), rnbr5[:, :k].copy(), ridx5[:, :k].copy()
+        if few.any():
+            _, widx[few], wd2[few], wnbr[few] = ked.brute_knn(exp, q[few], k=k)
+        assert np.array_equal(d2[f].view(np.uint32), wd2[f].view(np.uint32)), (name, k, "numpy", "d2 bits")
+        assert np.array_equal(nbr[f].view(np.uint32), wnbr[f].view(np.uint32)), (name, k, "numpy", "neighbour coordinates")
+        rows = _export_index(exp, idx[f].astype(np.int64), ked.cube_of(wnbr[f][:, 0]))
+        assert np.array_equal(rows, widx[f]), (name, k, "canonical indices")
+        # -- the first k of the product's own 5-list
+        full = counts >= 5
+        assert np.array_equal(d2[full].view(np.uint32), d25[full][:, :k].view(np.uint32)) and np.array_equal(idx[full], idx5[full][:, :k]) and \
+            np.array_equal(nbr[full].view(np.uint32), nbr5[full][:, :k].view(np.uint32)), (name, k, "the k-list is the head of the 5-list")
+        # -- a cube of fewer than k points
+        for i in np.nonzero((counts > 0) & (counts < k))[0]:
+            m = counts[i]
+            p0 = first[tuple(ked.cube_of(q[i]))]
+            assert (nbr[i, m:] == p0).all() and (d2[i, m:k - 1] == 0).all() and d2[i, k - 1] == ked.FLT_MAX, (name, k, i, nbr[i], d2[i])
+            assert (idx[i, m:] & (CAP_PER_SLOT - 1) == 0).all() and (idx[i, m:] >> 20 == idx[i, 0] >> 20).all(), (name, k, i, idx[i])
+        for i in np.nonzero(counts == k)[0]:
+            assert d2[i, k - 1] < 1e30, "a cube of exactly k points fills every slot"
+        # -- no cube
+        assert (nbr[~f] == 0).all() and (d2[~f] == 0).all() and (idx[~f] == -1).all() and (found[~f] == 0).all(), (name, k)
+    slam.close()
+    if name.startswith("faces"):
+        assert {1, 2, 3, 4} <= set(counts.tolist()), "the cubes of 1 .. 4 points"
+
+
+_nonfinite = {}
+
+
+def _nonfinite_case(oracle, make, n_rows=None):
+    """the faces scan (padded by _scan_of; its first n_rows rows) with the non-finite rows in it, and the oracle's registration of
+    that very scan"""
+    if n_rows not in _nonfinite:
+        fam, exp, om, scan, ref = _setup(oracle, make, "faces")
+        bad, rows = ked.nonfinite_rows(scan[:n_rows])
+        orc, _, ost, corrs = om.register(bad, IDENTITY, oracle.default_config(max_iterations=1), want_corrs=True)
+        assert orc == 0 and (corrs["status"][rows] == 1).all()
+        assert ref[0][:len(bad)][rows].sum() > 60, "most of the rows had a cube before"
+        _nonfinite[n_rows] = (fam, exp, bad, rows, ost, corrs)
+    return _nonfinite[n_rows]
+
+
+def _check_nonfinite(exp, bad, rows, st, ms, nb, ost, corrs, what):
+    """the named rows are outside every window; every other row has the oracle's status and the oracle's list"""
+    assert (ms[rows] == 1).all(), (what, ms[rows])
+    assert np.array_equal(ms, corrs["status"]), (what, np.nonzero(ms != corrs["status"])[0][:10])
+    judged = np.isin(corrs["status"], JUDGED)
+    assert not judged[rows].any()
+    n = _check_lists(exp, bad, ms, nb, judged, corrs["nbr"].reshape(-1, 5, 3), None, what)
+    assert n > 1000
+    assert_follows_oracle(st, ost, what)
+
+
+@pytest.mark.parametrize("pack", ["1", "0"])
+def test_nonfinite_rows_in_the_chunked_sweep(oracle, soicp, gpu_slam_factory, monkeypatch, pack):
+    fam, exp, bad, rows, ost, corrs = _nonfinite_case(oracle, gpu_slam_factory)
+    monkeypatch.setenv("SOICP_KNN_PACK", pack)
+    slam = _product(gpu_slam_factory, fam)
+    st, ms, nb = _register(slam, bad, IDENTITY)
+    slam.close()
+    assert not (st.flags & soicp.FLAG_QUERY_WAVES)
+    _check_nonfinite(exp, bad, rows, st, ms, nb, ost, corrs, ("chunked", pack))
+
+
+def test_nonfinite_rows_in_the_query_waves(oracle, soicp, gpu_slam_factory):
+    fam, exp, bad, rows, ost, corrs = _nonfinite_case(oracle, gpu_slam_factory, 4096)
+    assert len(bad) == 4096 and rows[-1] == 4095
+    slam = _product(gpu_slam_factory, fam)
+    st, ms, nb = _register(slam, bad, IDENTITY)
+    slam.close()
+    assert st.flags & soicp.FLAG_QUERY_WAVES
+    _check_nonfinite(exp, bad, rows, st, ms, nb, ost, corrs, "query waves")
+
+
+def test_nonfinite_rows_in_a_scan_binned_ahead(oracle, soicp, gpu_slam_factory):
+    """announced, binned beside a registration of the clean scan, then registered (repeated until it WAS binned ahead, as above)"""
+    fam, exp, bad, rows, ost, corrs = _nonfinite_case(oracle, gpu_slam_factory)
+    slam = _product(gpu_slam_factory, fam)
+    A, B = slam.host_alloc_like(_setup(oracle, gpu_slam_factory, "faces")[3]), slam.host_alloc_like(bad)
+    ahead = 0
+    for attempt in range(16):
+        slam.stage_scan(B)
+        rc, _, _ = slam.register(A, IDENTITY)
+        assert rc == 0, slam.last_error()
+        st, ms, nb = _register(slam, B, IDENTITY)
+        assert st.flags & soicp.FLAG_STAGED_SCAN
+        ahead += bool(st.flags & soicp.FLAG_BINNED_AHEAD)
+        _check_nonfinite(exp, B, rows, st, ms, nb, ost, corrs, ("binned ahead", attempt))
+        if ahead >= 2:
+            break
+    slam.close()
+    print(f"non-finite rows: binned ahead {ahead} times in {attempt + 1} rounds")
+    assert ahead >= 1, "the scan was never binned ahead: the path was not exercised"
+
+
+def test_nonfinite_rows_in_a_resident_scan_and_a_batch(oracle, soicp, gpu_slam_factory):
+    """so_icp_register_dev and a batch of three equal the registration of the host scan, bit for bit"""
+    fam, exp, bad, rows, ost, corrs = _nonfinite_case(oracle, gpu_slam_factory)
+    slam = _product(gpu_slam_factory, fam)
+    rc, pose, st = slam.register(bad, IDENTITY)
+    assert rc == 0, slam.last_error()
+    d_scan, n = slam.upload_scan(bad)
+    rc, pose_d, st_d = slam.register_dev(d_scan, n, IDENTITY)
+    assert rc == 0, slam.last_error()
+    ms, nb = slam.match_status(n), slam.neighbours(n)
+    _check_nonfinite(exp, bad, rows, st_d, ms, nb, ost, corrs, "resident")
+    assert_same_bits(st_d, st, "resident", omit=CARRIED_OVER_FIELDS)
+    assert np.array_equal(pose_d, pose)
+    rc, pose2, st2 = slam.register(bad, IDENTITY)  # (the call before the batch: what its carried-over fields follow)
+    assert rc == 0
+    ok, rcs, poses, sts = slam.register_batch(bad, np.stack([IDENTITY, IDENTITY, IDENTITY]))
+    slam.free_scan(d_scan)
+    slam.close()
+    assert ok == 3 and (rcs == 0).all()
+    for h in range(3):
+        assert_same_bits(sts[h], st2, ("batch", h), omit=("uncertainty",))
+        assert np.array_equal(poses[h], pose2)
+        assert_follows_oracle(sts[h], ost, ("batch", h))
