@@ -396,7 +396,8 @@ int so_icp_download_scan(so_icp_ctx *ctx, const void *d_scan_xyz, size_t n, floa
  * a kernel of its own; no registration kernel takes part and none was changed for it).  What a caller does with it: colour or mask the
  * registered scan by residual, keep points that matched nothing out of the map, hand a factor-graph back end point-to-plane factors
  * instead of one pose, re-evaluate the cost of the fixed set at another pose.
- * Not exported: the correspondences of so_icp_register_batch's hypotheses and those of a sharded context (world_size > 1).  The
+ * The hypotheses of so_icp_register_batch: so_icp_keep_batch_correspondences and so_icp_batch_correspondences, far below.  Not exported:
+ * the correspondences of a sharded context (world_size > 1).  The
  * neighbours, the PCA and the observability labels of every accepted point: so_icp_correspondence_geometry, below.  Normal
  * equations: so_icp_stats::JtJ / Jtr are those of the set at the default pose; at other poses so_icp_correspondence_sums (below, with so_icp_match) sums them on the device -- or the caller
  * sums them from the records: J = [n, p x (R^T n)], JtJ += weight J J^T, Jtr += weight residual J. */
@@ -898,6 +899,56 @@ int so_icp_set_sequence_priors(so_icp_ctx *ctx, int count, const so_icp_pose_pri
  * so_icp_set_sequence_priors'.  Not in a batch: the reference's uncertainty-scaled information (the caller scales U). */
 int so_icp_set_batch_priors(so_icp_ctx *ctx, int n_hyp, const so_icp_pose_prior *priors /* n_hyp */,
                             const uint8_t *modes /* n_hyp; NULL = all GIVEN */);
+
+/* -------- the correspondence sets of a BATCH's hypotheses: which points each hypothesis matched, how the cost of its set behaves around
+ * its result, whether two hypotheses that ended at different poses explain the same points -- without registering them one by one.
+ * The switch.  A new context has it off, and while it is off so_icp_register_batch enqueues, allocates, copies and synchronises exactly
+ * what it does without this feature, and both exports below report valid = 0 / zero sums.  While it is on, a batch leaves in memory the
+ * context owns and no other entry writes: the plane, coefficient and status arrays of ALL n_hyp hypotheses (41 bytes per point and
+ * hypothesis; the batched kernels write them there instead of into the batch's working arrays -- other kernel arguments, the same
+ * kernels -- and the concurrent registrations of SOICP_BATCH_MODE=lanes, of an empty scan or of a degraded context each copy theirs
+ * there on their own queue), ONE packed copy of the scan (12 n bytes, device to device, in front of the batch's first launch) and per
+ * hypothesis what a single registration keeps: the accepted count, the loss, outer_iteration, pose_fit, pose_eval, both histograms,
+ * and valid = (rc_out[h] == SO_ICP_OK).  The set is replaced by the next so_icp_register_batch (which leaves none if it fails); nothing
+ * else invalidates it: not a single registration, a match, a map insert, a pre-filter or so_icp_set_resolution.  Turning the switch
+ * off drops the set and frees its memory.  Independent of so_icp_keep_correspondences: a batch still ends "the last registration's"
+ * set.  world_size > 1: SO_ICP_E_UNSUPPORTED; a host-only context: SO_ICP_E_HIP. */
+int so_icp_keep_batch_correspondences(so_icp_ctx *ctx, int on);
+/* so_icp_correspondences for a SELECTION of the last batch's hypotheses in one launch.  Entry k of the selection is hypothesis hyp[k]
+ * (hyp == NULL: k); indices may repeat and come in any order; one outside 0 .. n_hyp - 1 of that batch: SO_ICP_E_INVALID.  n_sel is
+ * 0 .. SO_ICP_BATCH_MAX_SELECTION (SO_ICP_E_INVALID beyond).  poses (nullable): entry k is evaluated at poses[7 k ..]; NULL = each
+ * hypothesis' own pose_eval.  info[k] is what so_icp_correspondences reports on a context that ran hypothesis hyp[k] alone with
+ * so_icp_keep_correspondences on -- counts, outer_iteration, pose_fit, pose_eval and cost, bit for bit; a hypothesis whose rc_out was not
+ * SO_ICP_OK has valid = 0 and no records.  Every info[k].valid is 0 (SO_ICP_OK, nothing else touched) while the switch is off or no
+ * batch has left a set.
+ * Outputs, each nullable:
+ *  records       the records of entry k at [first_record[k], first_record[k + 1]), ascending index, with residual and weight at the
+ *                entry's pose (there is no residual_out: the records carry the residuals); NULL or cap_records < first_record[n_sel]:
+ *                counts, first_record, info and cost only
+ *  first_record  n_sel + 1 offsets, formed on the host from the accepted counts the hypotheses reported
+ *  status_out    [k * n_points + i] = the MatchingResult byte of point i under hypothesis hyp[k] (a row of 254 for an entry with valid = 0);
+ *                needs cap_status >= n_sel * n_points (SO_ICP_E_INVALID otherwise)
+ *  *d_records_out  a device buffer owned by the context with the same record bytes, valid until the next so_icp_batch_correspondences
+ *                call; no other entry writes it
+ * One memset of the counters, one launch, one copy per requested host output and one of the counts and tile sums, one synchronisation,
+ * on the context's queue.  The kernel's count of every entry is held to the reported one (SO_ICP_E_HIP with a text otherwise). */
+#define SO_ICP_BATCH_MAX_SELECTION 1024
+int so_icp_batch_correspondences(so_icp_ctx *ctx, const int32_t *hyp /* n_sel, NULL = 0 .. n_sel-1 */, int n_sel,
+                                 const double *poses /* n_sel x 7, nullable: each hypothesis' own pose_eval */,
+                                 so_icp_correspondence *records, size_t cap_records,
+                                 uint64_t *first_record /* n_sel + 1 */,
+                                 uint8_t *status_out /* n_sel x n_points, nullable */, size_t cap_status,
+                                 void **d_records_out, so_icp_correspondence_info *info /* n_sel */);
+/* so_icp_correspondence_sums for a selection (as above) of the last batch's hypotheses: sums_out[k * n_poses + j] = the sums of
+ * hypothesis hyp[k]'s set at poses[(k * n_poses + j) * 7 ..], bit for bit what so_icp_correspondence_sums returns on a context that ran
+ * that hypothesis alone (the same per-point expression, the same tree, the tiles added in tile order; no atomics, nothing to clear),
+ * with that hypothesis' histograms.  A hypothesis without a set: zero sums.  As in the single path a hypothesis that carried a pose
+ * prior (so_icp_set_batch_priors) gets the sums of its planes only: the caller adds so_icp_pose_prior_sums.  Two launches for the whole
+ * selection.  n_poses outside 1 .. SO_ICP_SUMS_MAX_POSES, n_sel outside 0 .. SO_ICP_BATCH_MAX_SELECTION, an index outside the batch:
+ * SO_ICP_E_INVALID. */
+int so_icp_batch_correspondence_sums(so_icp_ctx *ctx, const int32_t *hyp, int n_sel,
+                                     const double *poses /* n_sel x n_poses x 7 */, int n_poses /* 1 .. SO_ICP_SUMS_MAX_POSES */,
+                                     so_icp_sums *sums_out /* n_sel x n_poses */);
 
 /* -------- measurement ------------------------------------------------------------------------ */
 int so_icp_get_timing(so_icp_ctx *ctx, so_icp_timing *t);

@@ -283,8 +283,10 @@ EXPORTED = ["so_icp_default_config", "so_icp_create", "so_icp_destroy", "so_icp_
             "so_icp_match", "so_icp_match_dev", "so_icp_correspondence_sums",
             "so_icp_keep_correspondence_geometry", "so_icp_correspondence_geometry", "so_icp_debug_correspondence_refit",
             "so_icp_pose_prior_from_information", "so_icp_pose_prior_sums", "so_icp_set_pose_prior", "so_icp_set_sequence_priors",
-            "so_icp_set_batch_priors"]
+            "so_icp_set_batch_priors",
+            "so_icp_keep_batch_correspondences", "so_icp_batch_correspondences", "so_icp_batch_correspondence_sums"]
 SUMS_MAX_POSES = 64
+BATCH_MAX_SELECTION = 1024
 
 _lib = None
 
@@ -398,6 +400,10 @@ def load():
     L.so_icp_set_pose_prior.argtypes = [vp, C.POINTER(PosePrior)]
     L.so_icp_set_sequence_priors.argtypes = [vp, C.c_int, C.POINTER(PosePrior), C.POINTER(C.c_uint8)]
     L.so_icp_set_batch_priors.argtypes = [vp, C.c_int, C.POINTER(PosePrior), C.POINTER(C.c_uint8)]
+    L.so_icp_keep_batch_correspondences.argtypes = [vp, C.c_int]
+    L.so_icp_batch_correspondences.argtypes = [vp, i32p, C.c_int, f64p, vp, C.c_size_t, C.POINTER(C.c_uint64), u8p, C.c_size_t, C.POINTER(vp),
+                                               C.POINTER(CorrespondenceInfo)]
+    L.so_icp_batch_correspondence_sums.argtypes = [vp, i32p, C.c_int, f64p, C.c_int, C.POINTER(Sums)]
     _lib = L
     return L
 
@@ -734,6 +740,74 @@ class LidarSlamGpu:
         out = (Sums * len(poses))()
         fn, args = self.L.so_icp_correspondence_sums, (self.h, poses.ctypes.data_as(_F64P), len(poses), out)
         return (lambda: fn(*args)), poses, out
+
+    # ---- the correspondence sets of a batch's hypotheses ----
+    def keep_batch_correspondences(self, on):
+        """so_icp_keep_batch_correspondences: register_batch calls from here on leave the sets of all their hypotheses for
+        batch_correspondences() / batch_correspondence_sums(); returns the C code"""
+        return self.L.so_icp_keep_batch_correspondences(self.h, int(bool(on)))
+
+    def batch_correspondences(self, hyp=None, n_sel=None, poses=None, want_status=True, cap_points=None, cap_records=None, want_records=True, d_out=None):
+        """so_icp_batch_correspondences for the selection `hyp` (None: hypotheses 0 .. n_sel - 1) of the last batch, entry k evaluated at
+        poses[k] (None: each hypothesis' own optimised pose).  -> (records of the whole selection (CORRESPONDENCE_DTYPE), first_record
+        [n_sel + 1]: entry k's records are records[first_record[k]:first_record[k + 1]], status [n_sel, n_points] or None, the n_sel
+        CorrespondenceInfo).  cap_points / cap_records: upper bounds of the scan's points / the selection's records, when the caller
+        knows them (saves the sizing call)."""
+        hyp = None if hyp is None else np.ascontiguousarray(hyp, np.int32)
+        n_sel = len(hyp) if hyp is not None else int(n_sel)
+        poses = None if poses is None else np.ascontiguousarray(poses, np.float64).reshape(n_sel, 7)
+        hp = None if hyp is None else _p(hyp, C.c_int32)
+        pp = None if poses is None else _p(poses, C.c_double)
+        info = (CorrespondenceInfo * max(n_sel, 1))()
+        first = np.zeros(n_sel + 1, np.uint64)
+        if cap_points is None or (want_records and cap_records is None):  # a sizing call first (counts only): one launch more
+            self._check(self.L.so_icp_batch_correspondences(self.h, hp, n_sel, pp, None, 0, _p(first, C.c_uint64), None, 0, None, info))
+            cap_points = max([int(info[k].n_points) for k in range(n_sel)], default=0)
+            cap_records = int(first[n_sel])
+        cap_points, cap_records = int(cap_points), int(cap_records or 0)
+        rec = np.zeros(cap_records if want_records else 0, CORRESPONDENCE_DTYPE)
+        status = np.zeros(n_sel * cap_points, np.uint8) if want_status else None
+        self._check(self.L.so_icp_batch_correspondences(self.h, hp, n_sel, pp, rec.ctypes.data_as(C.c_void_p) if want_records else None, len(rec),
+                                                        _p(first, C.c_uint64), None if status is None else _p(status, C.c_uint8),
+                                                        len(status) if status is not None else 0, d_out, info))
+        n = max([int(info[k].n_points) for k in range(n_sel)], default=0)
+        return rec[:int(first[n_sel])], first, (None if status is None else status[:n_sel * n].reshape(n_sel, n)), [info[k] for k in range(n_sel)]
+
+    def batch_correspondences_dev(self, hyp=None, n_sel=None, poses=None):
+        """the same, the records left in HBM: (device address of the context-owned record buffer -- valid until the next call --,
+        first_record, infos)"""
+        d = C.c_void_p()
+        _, first, _, infos = self.batch_correspondences(hyp, n_sel, poses, want_status=False, cap_points=0, cap_records=0, want_records=False, d_out=C.byref(d))
+        return d.value, first, infos
+
+    def batch_correspondence_sums(self, poses, hyp=None):
+        """so_icp_batch_correspondence_sums: poses [n_sel, n_poses, 7] (n_poses <= SUMS_MAX_POSES) -> Sums [n_sel][n_poses] as a flat ctypes
+        array (entry k, pose j at [k * n_poses + j]) of the selection `hyp` (None: 0 .. n_sel - 1) of the last batch"""
+        poses = np.ascontiguousarray(poses, dtype=np.float64)
+        assert poses.ndim == 3 and poses.shape[2] == 7
+        n_sel, n_poses = poses.shape[:2]
+        hyp = None if hyp is None else np.ascontiguousarray(hyp, np.int32)
+        assert hyp is None or len(hyp) == n_sel
+        out = (Sums * max(1, n_sel * n_poses))()
+        self._check(self.L.so_icp_batch_correspondence_sums(self.h, None if hyp is None else _p(hyp, C.c_int32), n_sel, _p(poses, C.c_double), n_poses, out))
+        return out
+
+    def prepare_batch_correspondences(self, n_sel, cap_points, cap_records, hyp=None):
+        """so_icp_batch_correspondences at the default poses with pre-built arguments and buffers (timed loops): (call, records, first, info)"""
+        hyp = None if hyp is None else np.ascontiguousarray(hyp, np.int32)
+        rec = np.zeros(int(cap_records), CORRESPONDENCE_DTYPE); first = np.zeros(n_sel + 1, np.uint64); info = (CorrespondenceInfo * max(n_sel, 1))()
+        fn, args = self.L.so_icp_batch_correspondences, (self.h, None if hyp is None else _p(hyp, C.c_int32), n_sel, None, rec.ctypes.data_as(C.c_void_p),
+                                                         len(rec), _p(first, C.c_uint64), None, 0, None, info)
+        return (lambda _hyp=hyp: fn(*args)), rec, first, info
+
+    def prepare_batch_correspondence_sums(self, poses, hyp=None):
+        """so_icp_batch_correspondence_sums with pre-built arguments (timed loops): (call, poses array, Sums array)"""
+        poses = np.ascontiguousarray(poses, dtype=np.float64).copy()
+        n_sel, n_poses = poses.shape[:2]
+        hyp = None if hyp is None else np.ascontiguousarray(hyp, np.int32)
+        out = (Sums * max(1, n_sel * n_poses))()
+        fn, args = self.L.so_icp_batch_correspondence_sums, (self.h, None if hyp is None else _p(hyp, C.c_int32), n_sel, poses.ctypes.data_as(_F64P), n_poses, out)
+        return (lambda _hyp=hyp: fn(*args)), poses, out
 
     def download_bytes(self, d_ptr, nbytes):
         """nbytes from a device address, through so_icp_download_scan (whole 12-byte units; the buffers of this library are padded)"""

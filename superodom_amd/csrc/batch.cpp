@@ -7,6 +7,8 @@
 // workgroups it held go to the others in the next round.  Results are bit-identical to so_icp_register per hypothesis.
 // so_icp_set_batch_priors: every hypothesis may carry a pose prior of its own -- a table of prior blocks copied in front of round 0,
 // read by solve_kernel_batch_prior, which a round launches only where a hypothesis of its list carries one (reg_plan.h).
+// so_icp_keep_batch_correspondences: while the switch is on, a group's kernels write their records into the slices of the kept set
+// (other kernel arguments, the same kernels) and a lane copies its context's records there; batch_correspondences.cpp exports them.
 #include <hip/hip_runtime_api.h>
 
 #include <algorithm>
@@ -22,9 +24,11 @@
 namespace {
 
 constexpr int kBatchMaxConcurrent = 64;
+// element stride of a hypothesis' arrays for a scan of n points
+uint32_t batch_stride(size_t n) { return (uint32_t)(((n + 256 + 63) / 64) * 64); }
 int batch_reserve(so_icp_ctx* c, uint32_t B, size_t n, uint32_t lg) {
   so_icp_ctx::BatchBufs& b = c->batch;
-  const uint32_t bs = (uint32_t)(((n + 256 + 63) / 64) * 64);
+  const uint32_t bs = batch_stride(n);
   const size_t T = (size_t)1 << lg;
   const size_t partial_bytes = (size_t)kFitBlocksMax * kRecordChunksMax * 16;
   if (B > b.cap_hyp || bs > b.bs || lg != b.table_log2) {
@@ -70,8 +74,9 @@ int batch_priors_reserve(so_icp_ctx* c, uint32_t B) {
 }
 
 // `priors`: the priors of the whole batch (so_icp_set_batch_priors; nullptr: none), of which hypothesis h of this group is element base + h
+// `keep`: the set this batch leaves (so_icp_keep_batch_correspondences; nullptr: the switch is off), hypothesis h of this group is its base + h
 int register_batch_group(so_icp_ctx* c, const float* d_scan, size_t n, const double* poses_in, int B, double* poses_out, so_icp_stats* stats,
-                         int32_t* hyp_rc, const int pos[3], int count_5x5, const PriorSet* priors, int base) {
+                         int32_t* hyp_rc, const int pos[3], int count_5x5, const PriorSet* priors, int base, so_icp_ctx::BatchCorrKept* keep) {
   const auto t_begin = std::chrono::steady_clock::now();
   std::vector<so_icp_stats> local;
   if (!stats) { local.resize((size_t)B); stats = local.data(); }
@@ -143,12 +148,14 @@ int register_batch_group(so_icp_ctx* c, const float* d_scan, size_t n, const dou
                (uint32_t)((size_t)kFitBlocksMax * kRecordChunksMax * 2), (uint32_t)(kSyncBytes / 4), 1u, v_grid};
   const BinTable bt{b.bin_key.as<uint32_t>(), b.bin_cnt.as<uint32_t>(), b.bin_off.as<uint32_t>(), lg};
   DevState* ds = b.states.as<DevState>();
-  CorrBuffers corr{b.nd.as<double4>(), b.coeff.as<double>(), b.status.as<uint8_t>()};
+  if (keep && keep->bs != b.bs) return fail(c, SO_ICP_E_HIP, "so_icp_register_batch: the kept correspondence arrays have another stride than the batch's");
+  // (the kernels add the hypothesis' index in the group x bs to these: with the switch on, slice base + h of the kept set)
+  const CorrBuffers corr = keep ? keep->slice((size_t)base) : CorrBuffers{b.nd.as<double4>(), b.coeff.as<double>(), b.status.as<uint8_t>()};
   // ---- binning of the scan under every hypothesis' pose: (queries x hypotheses) in three launches
   b.tables_clean = false;
   const double zero_pose[7] = {0, 0, 0, 0, 0, 0, 1};
   launch_scan_keys(d_scan, (uint32_t)n, ds, zero_pose, max_outer, lm_max, b.hist.as<int32_t>(), c->view, c->cfg.max_surface_features, 0, 1,
-                   b.qslot.as<uint32_t>(), b.qrank.as<uint32_t>(), b.status.as<uint8_t>(), bt, s, false, &bv, (uint32_t)B);
+                   b.qslot.as<uint32_t>(), b.qrank.as<uint32_t>(), corr.status, bt, s, false, &bv, (uint32_t)B);
   launch_bin_offsets(bt, b.chunks.as<uint32_t>(), b.bs, ds, s, &bv, (uint32_t)B);
   b.tables_clean = true;
   launch_bin_place(bt, d_scan, (uint32_t)n, b.qslot.as<uint32_t>(), b.qrank.as<uint32_t>(), b.binned.as<float4>(), s, nullptr, &bv, (uint32_t)B);
@@ -224,6 +231,10 @@ int register_batch_group(so_icp_ctx* c, const float* d_scan, size_t n, const dou
     stats[h].time_elapsed_ms = ms;  // (of the whole group: the hypotheses advance together)
     if (!prior_modes.empty() && prior_modes[(size_t)h] != SO_ICP_PRIOR_NONE) stats[h].prediction_source = 1;  // addAbsolutePoseConstraints, LidarSlam.cpp:297
   }
+  if (keep) {  // (host memory only: the records themselves are where the kernels wrote them)
+    keep->a2 = ep.a2; keep->variant = ep.variant;
+    for (int h = 0; h < B; ++h) fill_correspondence_record(keep->rec[(size_t)(base + h)], b.h_states[h], poses_in + 7 * (size_t)h, n, ep);
+  }
   return SO_ICP_OK;
 }
 
@@ -245,12 +256,18 @@ int so_icp_register_batch(so_icp_ctx* c, const float* xyz, const void* d_scan, s
   if (c->cfg.world_size != 1)  // (hypotheses are independent: replicate the map and split THEM over the ranks -- bench.py's batch64)
     return fail(c, SO_ICP_E_UNSUPPORTED, "so_icp_register_batch needs the whole map on one device (world_size == 1)");
   c->corr_last.valid = false;  // (so_icp_correspondences: the hypotheses keep their records in the batch's own arrays)
-  if (n_hyp == 0) return 0;
+  if (c->batch_corr) c->batch_corr->valid = false;  // (so_icp_batch_correspondences: this batch replaces the set, or leaves none)
+  if (n_hyp == 0) return c->batch_corr_keep ? batch_corr_begin(c, nullptr, n, 0, 0) : 0;
   const float* scan = static_cast<const float*>(d_scan);
   if (!scan) {
     const int rc = upload_scan_impl(c, xyz, n, stride_bytes, c->d_scan_own);
     if (rc) return rc;
     scan = c->d_scan_own.as<float>();
+  }
+  so_icp_ctx::BatchCorrKept* keep = nullptr;
+  if (c->batch_corr_keep) {  // (the stride the groups below will use: batch_reserve never shrinks it)
+    if (const int rc = batch_corr_begin(c, scan, n, n_hyp, std::max(batch_stride(n), c->batch.bs))) return rc;
+    keep = c->batch_corr.get();
   }
   // the map window is placed once, for hypothesis 0 (LidarSlam.cpp:363); every hypothesis sees that map
   int pos[3];
@@ -272,7 +289,7 @@ int so_icp_register_batch(so_icp_ctx* c, const float* xyz, const void* d_scan, s
       if (cap < 1) { c->batch_degrade = 2; break; }
       const int B = std::min(cap, n_hyp - base);
       rc = register_batch_group(c, scan, n, poses_in + 7 * (size_t)base, B, poses_out + 7 * (size_t)base, stats ? stats + base : nullptr,
-                                hrc.data() + base, pos, count, priors, base);
+                                hrc.data() + base, pos, count, priors, base, keep);
       // A batched solve launch needs its workgroups resident together.  If the device could not provide that (shared with another
       // process), the group is repeated with one workgroup per compute unit; if that fails too the context falls back to
       // concurrent sequential registrations (below) for the rest of its life.  so_icp_last_error keeps the notice.
@@ -288,6 +305,10 @@ int so_icp_register_batch(so_icp_ctx* c, const float* xyz, const void* d_scan, s
     if (c->batch_degrade < 2) {
       int ok = 0;
       for (int h = 0; h < n_hyp; ++h) { if (rc_out) rc_out[h] = hrc[(size_t)h]; if (hrc[(size_t)h] == SO_ICP_OK) ++ok; }
+      if (keep) {
+        for (int h = 0; h < n_hyp; ++h) keep->rec[(size_t)h].valid = keep->rec[(size_t)h].valid && hrc[(size_t)h] == SO_ICP_OK;
+        keep->valid = true;
+      }
       return ok;
     }
   }
@@ -318,6 +339,11 @@ int so_icp_register_batch(so_icp_ctx* c, const float* xyz, const void* d_scan, s
   }
   std::vector<int> lane_rc(lanes, 0);
   std::vector<int> hyp_rc((size_t)n_hyp, 0);
+  const EvalParams lane_ep = eval_params(bw.plane_res, c->cfg.tukey_variant, c->ablate);  // (the loss of every lane's registrations)
+  if (keep) {  // (groups that ran batched before the context degraded noted theirs: the lanes run every hypothesis again)
+    keep->a2 = lane_ep.a2; keep->variant = lane_ep.variant;
+    for (so_icp_ctx::CorrLast& r : keep->rec) r.valid = false;
+  }
   auto run_lane = [&](int l) {
     so_icp_ctx* w = lane_ctx[l];
     if (hipSetDevice(c->cfg.device_id) != hipSuccess) { lane_rc[l] = SO_ICP_E_HIP; return; }
@@ -330,7 +356,19 @@ int so_icp_register_batch(so_icp_ctx* c, const float* xyz, const void* d_scan, s
       const int r = register_core(w, scan, n, poses_in + 7 * (size_t)h, poses_out + 7 * (size_t)h, stats ? stats + h : &local);
       hyp_rc[h] = r;
       if (r < 0) { lane_rc[l] = r; return; }
+      if (keep && r == SO_ICP_OK) {
+        // the lane's context holds this hypothesis' records until its next registration: three copies into slice h on the lane's own
+        // queue, behind the registration and in front of the next one
+        fill_correspondence_record(keep->rec[(size_t)h], *w->h_state, poses_in + 7 * (size_t)h, n, lane_ep);
+        const CorrBuffers to = keep->slice((size_t)h);
+        hipError_t e = hipSuccess;
+        if (n) e = hipMemcpyAsync(to.nd, w->d_nd.p, n * sizeof(double4), hipMemcpyDeviceToDevice, w->stream);
+        if (n && e == hipSuccess) e = hipMemcpyAsync(to.coeff, w->d_coeff.p, n * sizeof(double), hipMemcpyDeviceToDevice, w->stream);
+        if (n && e == hipSuccess) e = hipMemcpyAsync(to.status, w->d_status.p, n, hipMemcpyDeviceToDevice, w->stream);
+        if (e != hipSuccess) { w->err = std::string("so_icp_register_batch: copy of a lane's correspondences: ") + hipGetErrorString(e); lane_rc[l] = SO_ICP_E_HIP; return; }
+      }
     }
+    if (keep && hipStreamSynchronize(w->stream) != hipSuccess) { w->err = "so_icp_register_batch: a lane's queue did not drain"; lane_rc[l] = SO_ICP_E_HIP; }
   };
   std::vector<std::thread> th;
   for (int l = 1; l < lanes; ++l) th.emplace_back(run_lane, l);
@@ -342,6 +380,7 @@ int so_icp_register_batch(so_icp_ctx* c, const float* xyz, const void* d_scan, s
     if (lane_rc[l] < 0 && !err) { err = lane_rc[l]; if (l > 0) c->err = "worker: " + lane_ctx[l]->err; }
   }
   for (int h = 0; h < n_hyp; ++h) { if (rc_out) rc_out[h] = hyp_rc[h]; if (hyp_rc[h] == SO_ICP_OK) ++ok; }
+  if (keep && !err) keep->valid = true;  // (a record is valid where its lane noted it, behind an SO_ICP_OK)
   return err ? err : ok;
 }
 

@@ -46,6 +46,31 @@ struct CorrSumsHist { double v[16]; };  // LmSums::hist of every record written:
 void launch_correspondence_sums(const CorrSumsIn& in, const double* d_poses, uint32_t n_poses, const CorrSumsHist& hist, double* d_partials,
                                 double* d_sums_out, hipStream_t s);
 
+// ---- so_icp_batch_correspondences / so_icp_batch_correspondence_sums: both exports for a selection of so_icp_register_batch's
+// hypotheses, one launch each (batch_correspondences_kernel in corr_kernels.hip, batch_correspondence_sums_kernel and its add kernel in
+// corr_sums_kernels.hip)
+constexpr uint32_t kCorrNoHypothesis = 0xFFFFFFFFu;  // in the table of hypothesis indices: an entry without a set (no point is read)
+// What they read: the batch's packed scan copy, the records of ALL its hypotheses (hypothesis h at element h * bs of each array), the
+// device table of the selection's hypothesis indices, the loss of THAT batch
+struct CorrBatchIn {
+  const float* scan;
+  CorrBuffers corr;
+  uint32_t bs, n, n_sel;
+  const uint32_t* hyp;  // n_sel, device
+  double a2;
+  int32_t variant;
+};
+// d_poses: n_sel x 7 doubles; d_rec_first: n_sel record offsets into d_records, which has room for the last entry's offset + n records;
+// d_status_out n_sel x n bytes; d_counts n_sel words; d_tile_cost and d_state n_sel x correspondence_workgroups(n) words each.  d_state,
+// d_ticket and d_counts zeroed by the caller.  One launch of n_sel x correspondence_workgroups(n) workgroups.
+void launch_batch_correspondences(const CorrBatchIn& in, const double* d_poses, const unsigned long long* d_rec_first, uint8_t* d_records,
+                                  uint8_t* d_status_out, uint32_t* d_counts, double* d_tile_cost, unsigned long long* d_state, uint32_t* d_ticket,
+                                  hipStream_t s);
+// d_poses: n_sel x n_poses x 7 doubles; d_hists: n_sel x 16 doubles; d_partials: n_sel x n_poses x correspondence_workgroups(n) x
+// kCorrSumsAcc doubles, every one written; d_sums_out: n_sel x n_poses LmSums.  Two launches, nothing to clear.
+void launch_batch_correspondence_sums(const CorrBatchIn& in, const double* d_poses, uint32_t n_poses, const double* d_hists, double* d_partials,
+                                      double* d_sums_out, hipStream_t s);
+
 // ---- corr_geometry_kernels.hip: so_icp_correspondence_geometry, the neighbours, PCA and observability labels of the kept set
 // bytes of one so_icp_correspondence_geometry_record; the refit's plane of so_icp_debug_correspondence_refit (n[3], d, coeff)
 constexpr uint32_t kCorrGeomRecordBytes = 192, kCorrRefitBytes = 40;

@@ -28,7 +28,10 @@ int keep_scan_copy(so_icp_ctx* c, const float* d_scan, size_t n) {
 }
 
 void note_correspondences(so_icp_ctx* c, const DevState& H, const double guess[7], size_t n, const EvalParams& ep) {
-  so_icp_ctx::CorrLast& L = c->corr_last;
+  fill_correspondence_record(c->corr_last, H, guess, n, ep);
+}
+
+void fill_correspondence_record(so_icp_ctx::CorrLast& L, const DevState& H, const double guess[7], size_t n, const EvalParams& ep) {
   const int n_it = std::min(H.n_iterations, (int)SO_ICP_MAX_OUTER);
   L.n = n; L.n_accepted = n_it < 1 ? 0u : (uint32_t)H.iters[n_it - 1].num_surf;
   L.a2 = ep.a2; L.variant = ep.variant;

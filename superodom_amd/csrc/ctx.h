@@ -182,6 +182,23 @@ struct so_icp_ctx {
   std::shared_ptr<void> corr_geom_state;  // so_icp_correspondence_geometry: the snapshot and the export's own buffers
   std::shared_ptr<void> corr_state;   // so_icp_correspondences: buffers of its own
   std::shared_ptr<void> corr_sums_state;  // so_icp_correspondence_sums: buffers of its own
+  // so_icp_keep_batch_correspondences (batch_correspondences.cpp): the switch, and what the last so_icp_register_batch left while it was
+  // on -- the records of ALL its hypotheses (hypothesis h at element h * bs of nd / coeff / status: the batched kernels of the group that
+  // starts at `base` write slice base + their own index, a lane copies its context's arrays into slice h), one packed copy of the scan,
+  // and per hypothesis what note_correspondences keeps of a single registration.  No other entry writes any of it.
+  bool batch_corr_keep = false;
+  struct BatchCorrKept {
+    DevBuf nd, coeff, status, scan;
+    uint32_t bs = 0;                    // element stride of a hypothesis' slice (BatchBufs::bs of that batch)
+    size_t n = 0; int n_hyp = 0;
+    bool valid = false;                 // the last batch with the switch on returned without an error
+    double a2 = 0; int variant = 0;     // EvalParams::a2 / ::variant of that batch
+    std::vector<CorrLast> rec;          // n_hyp; valid = the hypothesis ended with SO_ICP_OK
+    CorrBuffers slice(size_t h) const { return CorrBuffers{nd.as<double4>() + h * bs, coeff.as<double>() + h * bs, status.as<uint8_t>() + h * bs}; }
+    ~BatchCorrKept() { for (DevBuf* b : {&nd, &coeff, &status, &scan}) b->release(); }
+  };
+  std::unique_ptr<BatchCorrKept> batch_corr;
+  std::shared_ptr<void> batch_corr_state;  // so_icp_batch_correspondences / so_icp_batch_correspondence_sums: buffers of their own
   // so_icp_match(_dev): the registration in progress is one outer iteration's matching half and the evaluation at the guess (one
   // outer iteration, ZERO LM iterations, per-evaluation launches); it leaves tracker, staged scans and packing policy alone
   bool match_only = false;
@@ -483,6 +500,11 @@ inline bool keeps_correspondences(const so_icp_ctx* c) { return c->corr_keep && 
 int keep_scan_copy(so_icp_ctx* c, const float* d_scan, size_t n);  // the packed copy, enqueued on the context's queue
 // the record of a registration that ended with SO_ICP_OK, reported in H from the guess `guess` with the loss parameters of `ep`
 void note_correspondences(so_icp_ctx* c, const DevState& H, const double guess[7], size_t n, const EvalParams& ep);
+// the same record into `L` (so_icp_keep_batch_correspondences: one per hypothesis)
+void fill_correspondence_record(so_icp_ctx::CorrLast& L, const DevState& H, const double guess[7], size_t n, const EvalParams& ep);
+// batch_correspondences.cpp: what so_icp_register_batch does while so_icp_ctx::batch_corr_keep is on.  The set of a batch of n_hyp
+// hypotheses of n points: arrays at stride `bs` reserved, every record invalid, the packed scan copy enqueued on the context's queue
+int batch_corr_begin(so_icp_ctx* c, const float* d_scan, size_t n, int n_hyp, uint32_t bs);
 // so_icp_keep_correspondence_geometry: what the same entries do for so_icp_correspondence_geometry while so_icp_ctx::corr_geom_keep is on
 inline bool keeps_correspondence_geometry(const so_icp_ctx* c) { return c->corr_geom_keep && keeps_correspondences(c); }
 // the snapshot of the n points' status bytes, neighbour indices and neighbour points: one launch on the context's queue, behind the

@@ -46,6 +46,33 @@ inline BatchSolveKernelKind batch_solve_kernel(const uint8_t* modes, const uint3
   return kBatchSolvePlain;
 }
 
+// so_icp_batch_correspondences: the layout of one export over a selection of the last batch's hypotheses.
+// Entry k of the selection is hypothesis hyp[k] (hyp == nullptr: k).  -> the first entry whose index lies outside [0, n_hyp), -1: none
+inline int batch_selection_first_bad(const int32_t* hyp, int n_sel, int n_hyp) {
+  for (int k = 0; k < n_sel; ++k) {
+    const int h = hyp ? hyp[k] : k;
+    if (h < 0 || h >= n_hyp) return k;
+  }
+  return -1;
+}
+// The records of entry k occupy [first_record[k], first_record[k + 1]): as wide as the count its hypothesis reported, 0 for a hypothesis
+// that left no set; an index that repeats gets a range of its own each time.  `accepted`, `valid`: per hypothesis of the batch.
+// -> first_record[n_sel], the records of the whole selection
+inline uint64_t batch_record_ranges(const uint32_t* accepted, const uint8_t* valid, const int32_t* hyp, int n_sel, uint64_t* first_record) {
+  uint64_t at = 0;
+  for (int k = 0; k < n_sel; ++k) {
+    const int h = hyp ? hyp[k] : k;
+    first_record[k] = at;
+    at += valid[h] ? accepted[h] : 0u;
+  }
+  first_record[n_sel] = at;
+  return at;
+}
+// The export's workgroups draw one global ticket each; ticket t is tile t % nblk of entry t / nblk (hypothesis-major, nblk tiles per
+// entry), so the look-back of an entry only ever waits for smaller tickets.  constexpr: batch_correspondences_kernel calls it too
+struct BatchTicket { uint32_t entry, tile; };
+constexpr BatchTicket batch_ticket(uint32_t t, uint32_t nblk) { return BatchTicket{t / nblk, t - (t / nblk) * nblk}; }
+
 // scans of this many points or more are refused (refuse_scan_size, icp_context.cpp): the work-list counters hold 21 bits each
 constexpr size_t kMaxScanPoints = (size_t)1 << 21;
 
