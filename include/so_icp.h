@@ -396,7 +396,8 @@ int so_icp_download_scan(so_icp_ctx *ctx, const void *d_scan_xyz, size_t n, floa
  * a kernel of its own; no registration kernel takes part and none was changed for it).  What a caller does with it: colour or mask the
  * registered scan by residual, keep points that matched nothing out of the map, hand a factor-graph back end point-to-plane factors
  * instead of one pose, re-evaluate the cost of the fixed set at another pose.
- * The hypotheses of so_icp_register_batch: so_icp_keep_batch_correspondences and so_icp_batch_correspondences, far below.  Not exported:
+ * The hypotheses of so_icp_register_batch: so_icp_keep_batch_correspondences and so_icp_batch_correspondences, far below; EVERY frame of
+ * a run of so_icp_register_sequence / so_icp_localization_sequence: so_icp_keep_sequence_correspondences, behind them.  Not exported:
  * the correspondences of a sharded context (world_size > 1).  The
  * neighbours, the PCA and the observability labels of every accepted point: so_icp_correspondence_geometry, below.  Normal
  * equations: so_icp_stats::JtJ / Jtr are those of the set at the default pose; at other poses so_icp_correspondence_sums (below, with so_icp_match) sums them on the device -- or the caller
@@ -424,7 +425,9 @@ typedef struct {
 /* The switch.  A new context has it off, and while it is off every entry does exactly what it does without this feature (no launch,
  * copy, allocation or synchronisation is added) and so_icp_correspondences reports valid = 0.  While it is on, every registration that
  * ends with SO_ICP_OK -- so_icp_register, _register_dev, so_icp_localization(_dev) with initialization = 1, the last registration of
- * so_icp_register_sequence, the last frame of so_icp_localization_sequence -- leaves what the export needs in memory the context owns.
+ * so_icp_register_sequence, the last frame of so_icp_localization_sequence -- leaves what the export needs in memory the context owns
+ * (of a run only the LAST frame: the arrays are the context's own, and the frames behind a frame overwrite them; the sets of ALL frames
+ * are kept under a switch of their own, so_icp_keep_sequence_correspondences, far below).
  * The records and status bytes are there anyway; the SCAN is not (it may lie in a stage slot that so_icp_stage_scan refills from another
  * thread as soon as the call returns, in the caller's device buffer, or in the pre-filter's output), so the registration keeps a
  * packed copy of it: one device-to-device copy of 12 n bytes in the context's queue, in front of the registration's first launch (a
@@ -949,6 +952,66 @@ int so_icp_batch_correspondences(so_icp_ctx *ctx, const int32_t *hyp /* n_sel, N
 int so_icp_batch_correspondence_sums(so_icp_ctx *ctx, const int32_t *hyp, int n_sel,
                                      const double *poses /* n_sel x n_poses x 7 */, int n_poses /* 1 .. SO_ICP_SUMS_MAX_POSES */,
                                      so_icp_sums *sums_out /* n_sel x n_poses */);
+
+/* -------- the correspondence sets of a RUN's frames: so_icp_register_sequence and so_icp_localization_sequence are the entries for a
+ * backlog of feature clouds or a log replayed at full speed, and the callers of the export -- a factor-graph back end that wants
+ * point-to-plane factors (the reference's features_corres, LS.h:209-222) instead of one pose per frame, colouring or masking registered
+ * scans by residual -- are log-replay callers: they want the planes of EVERY frame, not of the last one.
+ * The switch.  A new context has it off, and while it is off both sequence entries enqueue, allocate, copy and synchronise exactly what
+ * they do without this feature, and both exports below report valid = 0 / zero sums.  While it is on, a call of either entry leaves in
+ * memory the context owns and no other entry writes, per frame: the plane, coefficient and status arrays of the frame's last fit pass
+ * (41 bytes per point), a packed copy of the frame's scan (12 bytes per point) -- 53 bytes per point and frame, sized by the sum of the
+ * frames' points, reserved before the run's first launch (nothing is allocated under a registration in flight; when it cannot be had the
+ * call returns SO_ICP_E_NOMEM before it touches anything) -- and what a single registration keeps: the accepted count, the loss of THAT
+ * frame, outer_iteration, pose_fit, pose_eval, both histograms, and valid = (the frame ended with SO_ICP_OK).  Frames from the one that
+ * stopped the run onwards, and every frame of a call that returned an error, have valid = 0.
+ * How the records get there: a frame the chained path of so_icp_register_sequence starts itself -- chained or not -- runs the same
+ * kernels with its slice of the set as their arguments (no copy, nothing between two chained registrations on the context's queue); a
+ * frame that goes through a per-frame entry (SOICP_SEQ_CHAIN=0, an empty scan, a frame the chained path cannot start, every frame of
+ * so_icp_localization_sequence) copies the context's three arrays into its slice behind its report, device to device on the context's
+ * queue -- in front of the map insert of so_icp_localization_sequence.  The scan copies of frames started by the chained path ride on the
+ * sequence's own copy queue, behind the scan's arrival or its binning, and the call waits for that queue before it returns.
+ * The set is replaced by the next sequence call of either kind (which leaves none if it fails before frame 0); nothing else
+ * invalidates it: not a single registration, a batch, a match, a map insert, a pre-filter or so_icp_set_resolution.  Turning the switch
+ * off drops the set and frees its memory.  Independent of so_icp_keep_correspondences and so_icp_keep_batch_correspondences: with the
+ * single switch on as well, the run's last frame still leaves "the last registration's" set, with the bytes it has without this switch.
+ * world_size > 1: SO_ICP_E_UNSUPPORTED; a host-only context: SO_ICP_E_HIP. */
+int so_icp_keep_sequence_correspondences(so_icp_ctx *ctx, int on);
+/* so_icp_correspondences for a SELECTION of the last run's frames in one launch.  Entry k of the selection is frame frames[k]
+ * (frames == NULL: k); indices may repeat and come in any order; one outside the kept run: SO_ICP_E_INVALID.  n_sel is
+ * 0 .. SO_ICP_SEQUENCE_MAX_SELECTION (SO_ICP_E_INVALID beyond).  poses (nullable): entry k is evaluated at poses[7 k ..]; NULL = each
+ * frame's own pose_eval.  info[k], the records, the status row and cost of entry k are, bit for bit, what so_icp_correspondences
+ * reports on a context that registered that frame alone from guesses_out[frames[k]] (with the frame's prior, if the run had priors)
+ * with so_icp_keep_correspondences on.  A frame without a set has valid = 0, no records and n_points = its points; a frame of 0 points
+ * has valid = 1 and zero counts.  Every info[k] is zero (SO_ICP_OK, nothing else touched) while the switch is off or no run has left a set.
+ * Outputs, each nullable:
+ *  records       the records of entry k at [first_record[k], first_record[k + 1]), ascending index, with residual and weight at the
+ *                entry's pose; NULL or cap_records < first_record[n_sel]: counts, offsets, info and cost only
+ *  first_record  n_sel + 1 offsets, formed on the host from the accepted counts the frames reported
+ *  status_out    [first_status[k] + i] = the MatchingResult byte of point i of frame frames[k] (254s for an entry with valid = 0); the
+ *                frames differ in their points, so row k is info[k].n_points long; needs cap_status >= the points of all selected
+ *                frames (SO_ICP_E_INVALID otherwise)
+ *  first_status  n_sel + 1 offsets of the status rows
+ *  *d_records_out  a device buffer owned by the context with the same record bytes, valid until the next
+ *                so_icp_sequence_correspondences call; no other entry writes it
+ * One memset of the counters, one launch, one copy per requested host output and one of the counts and tile sums, one synchronisation,
+ * on the context's queue.  The kernel's count of every entry is held to the reported one (SO_ICP_E_HIP with a text otherwise). */
+#define SO_ICP_SEQUENCE_MAX_SELECTION 1024
+int so_icp_sequence_correspondences(so_icp_ctx *ctx, const int32_t *frames /* n_sel, NULL = 0 .. n_sel-1 */, int n_sel,
+                                    const double *poses /* n_sel x 7, nullable: each frame's own pose_eval */,
+                                    so_icp_correspondence *records, size_t cap_records, uint64_t *first_record /* n_sel + 1 */,
+                                    uint8_t *status_out, size_t cap_status, uint64_t *first_status /* n_sel + 1, nullable */,
+                                    void **d_records_out, so_icp_correspondence_info *info /* n_sel */);
+/* so_icp_correspondence_sums for a selection (as above) of the last run's frames: sums_out[k * n_poses + j] = the sums of frame
+ * frames[k]'s set at poses[(k * n_poses + j) * 7 ..], bit for bit what so_icp_correspondence_sums returns on a context that registered
+ * that frame alone (the same per-point expression, the same tree, the tiles added in tile order; no atomics, nothing to clear), with
+ * that frame's histograms.  A frame without a set: zero sums.  As everywhere else a frame that carried a pose prior
+ * (so_icp_set_sequence_priors) gets the sums of its planes only: the caller adds so_icp_pose_prior_sums.  Two launches for the whole
+ * selection.  n_poses outside 1 .. SO_ICP_SUMS_MAX_POSES, n_sel outside 0 .. SO_ICP_SEQUENCE_MAX_SELECTION, an index outside the run:
+ * SO_ICP_E_INVALID. */
+int so_icp_sequence_correspondence_sums(so_icp_ctx *ctx, const int32_t *frames, int n_sel,
+                                        const double *poses /* n_sel x n_poses x 7 */, int n_poses /* 1 .. SO_ICP_SUMS_MAX_POSES */,
+                                        so_icp_sums *sums_out /* n_sel x n_poses */);
 
 /* -------- measurement ------------------------------------------------------------------------ */
 int so_icp_get_timing(so_icp_ctx *ctx, so_icp_timing *t);

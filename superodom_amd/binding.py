@@ -284,9 +284,11 @@ EXPORTED = ["so_icp_default_config", "so_icp_create", "so_icp_destroy", "so_icp_
             "so_icp_keep_correspondence_geometry", "so_icp_correspondence_geometry", "so_icp_debug_correspondence_refit",
             "so_icp_pose_prior_from_information", "so_icp_pose_prior_sums", "so_icp_set_pose_prior", "so_icp_set_sequence_priors",
             "so_icp_set_batch_priors",
+            "so_icp_keep_sequence_correspondences", "so_icp_sequence_correspondences", "so_icp_sequence_correspondence_sums",
             "so_icp_keep_batch_correspondences", "so_icp_batch_correspondences", "so_icp_batch_correspondence_sums"]
 SUMS_MAX_POSES = 64
 BATCH_MAX_SELECTION = 1024
+SEQUENCE_MAX_SELECTION = 1024
 
 _lib = None
 
@@ -404,6 +406,10 @@ def load():
     L.so_icp_batch_correspondences.argtypes = [vp, i32p, C.c_int, f64p, vp, C.c_size_t, C.POINTER(C.c_uint64), u8p, C.c_size_t, C.POINTER(vp),
                                                C.POINTER(CorrespondenceInfo)]
     L.so_icp_batch_correspondence_sums.argtypes = [vp, i32p, C.c_int, f64p, C.c_int, C.POINTER(Sums)]
+    L.so_icp_keep_sequence_correspondences.argtypes = [vp, C.c_int]
+    L.so_icp_sequence_correspondences.argtypes = [vp, i32p, C.c_int, f64p, vp, C.c_size_t, C.POINTER(C.c_uint64), u8p, C.c_size_t, C.POINTER(C.c_uint64),
+                                                  C.POINTER(vp), C.POINTER(CorrespondenceInfo)]
+    L.so_icp_sequence_correspondence_sums.argtypes = [vp, i32p, C.c_int, f64p, C.c_int, C.POINTER(Sums)]
     _lib = L
     return L
 
@@ -808,6 +814,69 @@ class LidarSlamGpu:
         out = (Sums * max(1, n_sel * n_poses))()
         fn, args = self.L.so_icp_batch_correspondence_sums, (self.h, None if hyp is None else _p(hyp, C.c_int32), n_sel, poses.ctypes.data_as(_F64P), n_poses, out)
         return (lambda _hyp=hyp: fn(*args)), poses, out
+
+    # ---- the correspondence sets of a run's frames ----
+    def keep_sequence_correspondences(self, on):
+        """so_icp_keep_sequence_correspondences: register_sequence / localization_sequence calls from here on leave the sets of all their
+        frames for sequence_correspondences() / sequence_correspondence_sums(); returns the C code"""
+        return self.L.so_icp_keep_sequence_correspondences(self.h, int(bool(on)))
+
+    def sequence_correspondences(self, frames=None, n_sel=None, poses=None, want_status=True, want_records=True, d_out=None):
+        """so_icp_sequence_correspondences for the selection `frames` (None: frames 0 .. n_sel - 1) of the last run, entry k evaluated at
+        poses[k] (None: each frame's own optimised pose).  -> (records of the whole selection (CORRESPONDENCE_DTYPE), first_record
+        [n_sel + 1]: entry k's records are records[first_record[k]:first_record[k + 1]], status bytes of the whole selection or None,
+        first_status [n_sel + 1]: entry k's row is status[first_status[k]:first_status[k + 1]], the n_sel CorrespondenceInfo).  A sizing
+        call (counts and offsets only) comes first."""
+        frames = None if frames is None else np.ascontiguousarray(frames, np.int32)
+        n_sel = len(frames) if frames is not None else int(n_sel)
+        poses = None if poses is None else np.ascontiguousarray(poses, np.float64).reshape(n_sel, 7)
+        fp = None if frames is None else _p(frames, C.c_int32)
+        pp = None if poses is None else _p(poses, C.c_double)
+        info = (CorrespondenceInfo * max(n_sel, 1))()
+        first = np.zeros(n_sel + 1, np.uint64); first_status = np.zeros(n_sel + 1, np.uint64)
+        self._check(self.L.so_icp_sequence_correspondences(self.h, fp, n_sel, pp, None, 0, _p(first, C.c_uint64), None, 0, _p(first_status, C.c_uint64), None, info))
+        rec = np.zeros(int(first[n_sel]) if want_records else 0, CORRESPONDENCE_DTYPE)
+        status = np.zeros(int(first_status[n_sel]), np.uint8) if want_status else None
+        self._check(self.L.so_icp_sequence_correspondences(self.h, fp, n_sel, pp, rec.ctypes.data_as(C.c_void_p) if want_records else None, len(rec),
+                                                           _p(first, C.c_uint64), None if status is None else _p(status, C.c_uint8),
+                                                           len(status) if status is not None else 0, _p(first_status, C.c_uint64), d_out, info))
+        return rec, first, status, first_status, [info[k] for k in range(n_sel)]
+
+    def sequence_correspondences_dev(self, frames=None, n_sel=None, poses=None):
+        """the same, the records left in HBM: (device address of the context-owned record buffer -- valid until the next call --,
+        first_record, infos)"""
+        d = C.c_void_p()
+        _, first, _, _, infos = self.sequence_correspondences(frames, n_sel, poses, want_status=False, want_records=False, d_out=C.byref(d))
+        return d.value, first, infos
+
+    def sequence_correspondence_sums(self, poses, frames=None):
+        """so_icp_sequence_correspondence_sums: poses [n_sel, n_poses, 7] (n_poses <= SUMS_MAX_POSES) -> Sums [n_sel][n_poses] as a flat
+        ctypes array (entry k, pose j at [k * n_poses + j]) of the selection `frames` (None: 0 .. n_sel - 1) of the last run"""
+        poses = np.ascontiguousarray(poses, dtype=np.float64)
+        assert poses.ndim == 3 and poses.shape[2] == 7
+        n_sel, n_poses = poses.shape[:2]
+        frames = None if frames is None else np.ascontiguousarray(frames, np.int32)
+        assert frames is None or len(frames) == n_sel
+        out = (Sums * max(1, n_sel * n_poses))()
+        self._check(self.L.so_icp_sequence_correspondence_sums(self.h, None if frames is None else _p(frames, C.c_int32), n_sel, _p(poses, C.c_double), n_poses, out))
+        return out
+
+    def prepare_sequence_correspondences(self, n_sel, cap_records, want_records=True):
+        """so_icp_sequence_correspondences over frames 0 .. n_sel - 1 at the default poses with pre-built arguments and buffers (timed
+        loops): (call, records, first, info)"""
+        rec = np.zeros(int(cap_records) if want_records else 0, CORRESPONDENCE_DTYPE); first = np.zeros(n_sel + 1, np.uint64)
+        info = (CorrespondenceInfo * max(n_sel, 1))(); d = C.c_void_p()
+        fn, args = self.L.so_icp_sequence_correspondences, (self.h, None, n_sel, None, rec.ctypes.data_as(C.c_void_p) if want_records else None, len(rec),
+                                                            _p(first, C.c_uint64), None, 0, None, C.byref(d), info)
+        return (lambda _d=d: fn(*args)), rec, first, info
+
+    def prepare_sequence_correspondence_sums(self, poses):
+        """so_icp_sequence_correspondence_sums over frames 0 .. n_sel - 1 with pre-built arguments (timed loops): (call, poses array, Sums array)"""
+        poses = np.ascontiguousarray(poses, dtype=np.float64).copy()
+        n_sel, n_poses = poses.shape[:2]
+        out = (Sums * max(1, n_sel * n_poses))()
+        fn, args = self.L.so_icp_sequence_correspondence_sums, (self.h, None, n_sel, poses.ctypes.data_as(_F64P), n_poses, out)
+        return (lambda: fn(*args)), poses, out
 
     def download_bytes(self, d_ptr, nbytes):
         """nbytes from a device address, through so_icp_download_scan (whole 12-byte units; the buffers of this library are padded)"""

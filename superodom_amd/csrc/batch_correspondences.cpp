@@ -38,22 +38,6 @@ int batch_corr_begin(so_icp_ctx* c, const float* d_scan, size_t n, int n_hyp, ui
 
 namespace {
 
-// A pinned host buffer that grows
-struct PinnedBuf {
-  uint8_t* p = nullptr;
-  size_t cap = 0;
-  hipError_t reserve(size_t bytes) {
-    if (bytes <= cap) return hipSuccess;
-    if (p) (void)hipHostFree(p);
-    p = nullptr; cap = 0;
-    const size_t want = bytes + bytes / 4 + 256;
-    const hipError_t e = hipHostMalloc(reinterpret_cast<void**>(&p), want);
-    if (e == hipSuccess) cap = want;
-    return e;
-  }
-  ~PinnedBuf() { if (p) (void)hipHostFree(p); }
-};
-
 // The exports' own buffers: nothing here is written by another entry, and the exports write no other entry's buffers
 struct BatchCorrExportState {
   DevBuf records, status;

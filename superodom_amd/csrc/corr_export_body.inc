@@ -5,7 +5,10 @@
 //                  1: entry k = ticket / nblk of a selection of hypotheses, tile = ticket % nblk; the kernel's arguments are the
 //                     hypotheses' arrays at stride bs, the entry tables (hyp, poses, rec_first) and the per-entry outputs, which the
 //                     body offsets to entry k's before the per-point text (no residual_out: the records carry the residuals)
-// One text, two kernels: the export of a single registration launches the function it always launched.
+//                  2: a selection of a run's frames (sequence_correspondences_kernel): as 1, but the entries differ in their point and
+//                     tile counts -- ticket -> (entry, tile) is reg_plan.h's sequence_ticket over the prefix table tile_first, and an
+//                     entry's geometry, loss and pose come from its CorrSeqEntry
+// One text, three kernels: the export of a single registration launches the function it always launched.
   constexpr int kPer = (int)(kCorrTile / 256u);
   __shared__ uint32_t s_bid, s_pre[kPer * 4], s_agg, s_excl;
   __shared__ double s_cost[4];
@@ -13,7 +16,27 @@
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   if (tid == 0) s_bid = atomicAdd(ticket, 1u);
   __syncthreads();
-#if SO_CORR_BATCH
+#if SO_CORR_BATCH == 2
+  // entry-major, as below: the tickets of entry k are tile_first[k] .. tile_first[k + 1] - 1, its look-back chain starts at its own word 0
+  // of the state table and waits only for smaller tickets; an entry without tiles has no ticket (its count stays the zero it was cleared to)
+  if (s_bid >= n_tiles) return;  // (never: the launch has n_tiles workgroups)
+  const host::BatchTicket mine_of = host::sequence_ticket(s_bid, tile_first, n_sel);  // (reg_plan.h)
+  const uint32_t entry = mine_of.entry, bid = mine_of.tile;
+  const CorrSeqEntry& E = entries[entry];
+  const uint32_t n = E.n, tile0 = tile_first[entry], nblk = tile_first[entry + 1u] - tile0;
+  const float* __restrict__ scan = scan_all + (size_t)E.at * 3;
+  const double4* __restrict__ cnd = cnd_all + (size_t)E.at;
+  const double* __restrict__ ccoeff = ccoeff_all + (size_t)E.at;
+  const uint8_t* __restrict__ cstatus = cstatus_all + (size_t)E.at;
+  const Pose pose = pose_from_array(E.pose);
+  const double a2 = E.a2;
+  const int variant = E.variant;
+  uint8_t* __restrict__ records = records_all + (size_t)E.rec_first * kCorrRecordBytes;
+  uint8_t* __restrict__ status_out = status_all + (size_t)E.status_first;
+  uint32_t* __restrict__ n_accepted = counts + entry;
+  double* __restrict__ tile_cost = tile_cost_all + tile0;
+  unsigned long long* __restrict__ state = state_all + tile0;
+#elif SO_CORR_BATCH
   // hypothesis-major: the workgroups of entry k hold consecutive tickets, so a workgroup's look-back waits only for workgroups with
   // smaller tickets, which were handed out earlier and therefore run; the entry's chain starts at its own word 0
   const host::BatchTicket mine_of = host::batch_ticket(s_bid, nblk);  // (reg_plan.h)

@@ -71,6 +71,39 @@ void launch_batch_correspondences(const CorrBatchIn& in, const double* d_poses, 
 void launch_batch_correspondence_sums(const CorrBatchIn& in, const double* d_poses, uint32_t n_poses, const double* d_hists, double* d_partials,
                                       double* d_sums_out, hipStream_t s);
 
+// ---- so_icp_sequence_correspondences / so_icp_sequence_correspondence_sums: both exports for a selection of the FRAMES of a run
+// (so_icp_register_sequence, so_icp_localization_sequence), whose point counts differ (sequence_correspondences_kernel in
+// corr_kernels.hip, sequence_correspondence_sums_kernel and its add kernel in corr_sums_kernels.hip)
+// One entry of the selection, as the kernels read it from a device table: where the frame's points lie in the kept arrays (point
+// `at` of nd / coeff / status, float 3 `at` of the packed scans), where its records and its status row go, the loss of THAT frame,
+// the evaluation pose (the export; the sums have a pose table of their own) and its points (0: an entry without a set, or an empty frame)
+struct CorrSeqEntry {
+  unsigned long long at, rec_first, status_first;
+  double a2;
+  double pose[7];
+  uint32_t n;
+  int32_t variant;
+};
+static_assert(sizeof(CorrSeqEntry) == 96, "the host fills a table of these");
+// What they read: the packed scans and the records of ALL frames of the run, the entry table and the prefix table of the entries' tile
+// counts (n_sel + 1 words, reg_plan.h: sequence_ticket), both on the device; n_tiles = tile_first[n_sel]
+struct CorrSeqIn {
+  const float* scan;
+  CorrBuffers corr;
+  const CorrSeqEntry* entries;
+  const uint32_t* tile_first;
+  uint32_t n_sel, n_tiles;
+};
+// d_records: room for the last entry's offset + the points of the largest selected frame; d_status_out: the rows of all entries;
+// d_counts n_sel words; d_tile_cost and d_state n_tiles words each.  d_state, d_ticket and d_counts zeroed by the caller.  One launch of
+// n_tiles workgroups.
+void launch_sequence_correspondences(const CorrSeqIn& in, uint8_t* d_records, uint8_t* d_status_out, uint32_t* d_counts, double* d_tile_cost,
+                                     unsigned long long* d_state, uint32_t* d_ticket, hipStream_t s);
+// d_poses: n_sel x n_poses x 7 doubles; d_hists: n_sel x 16 doubles; d_partials: n_tiles x n_poses x kCorrSumsAcc doubles (entry e at
+// tile_first[e] x n_poses vectors, [pose][tile] inside), every one written; d_sums_out: n_sel x n_poses LmSums.  Two launches.
+void launch_sequence_correspondence_sums(const CorrSeqIn& in, const double* d_poses, uint32_t n_poses, const double* d_hists, double* d_partials,
+                                         double* d_sums_out, hipStream_t s);
+
 // ---- corr_geometry_kernels.hip: so_icp_correspondence_geometry, the neighbours, PCA and observability labels of the kept set
 // bytes of one so_icp_correspondence_geometry_record; the refit's plane of so_icp_debug_correspondence_refit (n[3], d, coeff)
 constexpr uint32_t kCorrGeomRecordBytes = 192, kCorrRefitBytes = 40;

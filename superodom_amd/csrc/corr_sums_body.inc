@@ -5,6 +5,9 @@
 //                  1: entry blockIdx.y (partial sums) or blockIdx.x / n_poses (add) of a selection of so_icp_register_batch's hypotheses:
 //                     the hypotheses' arrays at stride bs, n_poses poses per entry, one histogram per entry; the body offsets to the
 //                     entry's before the text both share
+//                  2: entry sequence_ticket(blockIdx.x) (partial sums) or blockIdx.x / n_poses (add) of a selection of a run's frames:
+//                     the entries differ in their point and tile counts, an entry's geometry and loss come from its CorrSeqEntry, its
+//                     partial vectors lie at tile_first[entry] x n_poses, [pose][tile] inside
 // One text per pair: so_icp_correspondence_sums launches the functions it always launched, and an entry's sums are formed by the
 // same expressions, the same tree and the same tile order as those of a context that kept that hypothesis alone.
 #if !SO_SUMS_ADD
@@ -13,8 +16,25 @@
   __shared__ SumsPose s_pose[kCorrSumsMaxPoses];
   __shared__ double s_part[2][4][kAcc];
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+#if SO_SUMS_BATCH == 2
+  const host::BatchTicket mine_of = host::sequence_ticket(blockIdx.x, tile_first, n_sel);  // (no look-back here: the launch index serves)
+  const uint32_t entry = mine_of.entry, bid = mine_of.tile;
+  const CorrSeqEntry& E = entries[entry];
+  const uint32_t n = E.n, tile0 = tile_first[entry], ntile = tile_first[entry + 1u] - tile0;
+  const float* __restrict__ scan = scan_all + (size_t)E.at * 3;
+  const double4* __restrict__ cnd = cnd_all + (size_t)E.at;
+  const double* __restrict__ ccoeff = ccoeff_all + (size_t)E.at;
+  const uint8_t* __restrict__ cstatus = cstatus_all + (size_t)E.at;
+  const double a2 = E.a2;
+  const int variant = E.variant;
+  const double* __restrict__ poses = poses_all + (size_t)entry * n_poses * 7;
+  double* __restrict__ partials = partials_all + (size_t)tile0 * n_poses * kAcc;
+#define SO_SUMS_NTILE ntile
+#else
   const uint32_t bid = blockIdx.x;
-#if SO_SUMS_BATCH
+#define SO_SUMS_NTILE gridDim.x
+#endif
+#if SO_SUMS_BATCH == 1
   const uint32_t entry = blockIdx.y, h = hyp[entry];
   const uint32_t n = h == kCorrNoHypothesis ? 0u : n_points;  // (an entry without a set: every partial sum +0.0)
   const size_t slice = h == kCorrNoHypothesis ? 0 : (size_t)h * bs;
@@ -76,13 +96,19 @@
       for (int a = 0; a < kAcc; ++a) part[wave][a] = acc[a];
     }
     __syncthreads();
-    if (tid < kAcc) partials[((size_t)k * gridDim.x + bid) * kAcc + tid] = ((part[0][tid] + part[1][tid]) + part[2][tid]) + part[3][tid];
+    if (tid < kAcc) partials[((size_t)k * SO_SUMS_NTILE + bid) * kAcc + tid] = ((part[0][tid] + part[1][tid]) + part[2][tid]) + part[3][tid];
   }
+#undef SO_SUMS_NTILE
 #else
   constexpr uint32_t kAcc = kCorrSumsAcc, kWords = kCorrSumsWords, kChunk = 64;
   __shared__ double s_in[kChunk * kAcc];
   const uint32_t k = blockIdx.x, tid = threadIdx.x;
+#if SO_SUMS_BATCH == 2
+  const uint32_t entry = k / n_poses, tile0 = tile_first[entry], nblk = tile_first[entry + 1u] - tile0;
+  const double* mine = partials + ((size_t)tile0 * n_poses + (size_t)(k - entry * n_poses) * nblk) * kAcc;
+#else
   const double* mine = partials + (size_t)k * nblk * kAcc;
+#endif
   double v = 0;
   for (uint32_t b0 = 0; b0 < nblk; b0 += kChunk) {
     const uint32_t tiles = nblk - b0 < kChunk ? nblk - b0 : kChunk;

@@ -13,6 +13,8 @@
 //                         so_icp_keep_correspondence_geometry, so_icp_correspondence_geometry: its neighbours, PCA and observability labels
 //   pose_prior.cpp        so_icp_pose_prior_from_information, so_icp_pose_prior_sums, so_icp_set_pose_prior, so_icp_set_sequence_priors,
 //                         so_icp_set_batch_priors
+//   batch_correspondences.cpp, sequence_correspondences.cpp   the correspondence sets of a batch's hypotheses / of a run's frames:
+//                         the switches, what the batch and sequence entries keep while they are on, both exports
 //   multi_gpu.cpp         RCCL, in-process groups, peer exchange, shard helpers
 //   localization_sequence.cpp, feature_extraction.cpp
 #pragma once
@@ -54,6 +56,22 @@ struct DevBuf {
   }
   void release() { if (p) (void)hipFree(p); p = nullptr; cap = 0; }
   template <typename T> T* as() const { return reinterpret_cast<T*>(p); }
+};
+
+// A pinned host buffer that grows (the tables and read-backs of the batch and sequence correspondence exports)
+struct PinnedBuf {
+  uint8_t* p = nullptr;
+  size_t cap = 0;
+  hipError_t reserve(size_t bytes) {
+    if (bytes <= cap) return hipSuccess;
+    if (p) (void)hipHostFree(p);
+    p = nullptr; cap = 0;
+    const size_t want = bytes + bytes / 4 + 256;
+    const hipError_t e = hipHostMalloc(reinterpret_cast<void**>(&p), want);
+    if (e == hipSuccess) cap = want;
+    return e;
+  }
+  ~PinnedBuf() { if (p) (void)hipHostFree(p); }
 };
 
 // RCCL entry points: prototypes and types come from <rccl/rccl.h>; the library itself is resolved lazily with dlopen
@@ -199,6 +217,26 @@ struct so_icp_ctx {
   };
   std::unique_ptr<BatchCorrKept> batch_corr;
   std::shared_ptr<void> batch_corr_state;  // so_icp_batch_correspondences / so_icp_batch_correspondence_sums: buffers of their own
+  // so_icp_keep_sequence_correspondences (sequence_correspondences.cpp): the switch, and what the last so_icp_register_sequence or
+  // so_icp_localization_sequence left while it was on -- the records of ALL its frames (frame k at element at[k] of nd / coeff / status:
+  // a frame started by sequence.cpp's chained path gets that slice as the kernel arguments of its sweeps and solves, a frame that went
+  // through a per-frame entry copies the context's arrays there, seq_corr_note_plain), a packed copy of every frame's scan (float
+  // 3 at[k] of `scan`) and per frame what note_correspondences keeps of a single registration.  No other entry writes any of it.
+  bool seq_corr_keep = false;
+  struct SeqCorrKept {
+    DevBuf nd, coeff, status, scan;     // total points of the run each: 32 + 8 + 1 + 12 = 53 bytes per point and frame
+    std::vector<size_t> n, at;          // per frame: its points, its first element (a slice has the padding of the context's own arrays and starts at a multiple of 64)
+    size_t total = 0;
+    bool valid = false;                 // the last run with the switch on got as far as frame 0
+    std::vector<CorrLast> rec;          // per frame; valid = the frame ended with SO_ICP_OK
+    int frames() const { return (int)n.size(); }
+    CorrBuffers slice(size_t k) const { return CorrBuffers{nd.as<double4>() + at[k], coeff.as<double>() + at[k], status.as<uint8_t>() + at[k]}; }
+    float* scan_of(size_t k) const { return scan.as<float>() + 3 * at[k]; }
+    ~SeqCorrKept() { for (DevBuf* b : {&nd, &coeff, &status, &scan}) b->release(); }
+  };
+  std::unique_ptr<SeqCorrKept> seq_corr;
+  int seq_corr_frame = -1;                // >= 0: the per-frame entry in progress is this frame of a run that keeps its sets (seq_corr_note_plain)
+  std::shared_ptr<void> seq_corr_state;   // so_icp_sequence_correspondences / so_icp_sequence_correspondence_sums: buffers of their own
   // so_icp_match(_dev): the registration in progress is one outer iteration's matching half and the evaluation at the guess (one
   // outer iteration, ZERO LM iterations, per-evaluation launches); it leaves tracker, staged scans and packing policy alone
   bool match_only = false;
@@ -505,6 +543,22 @@ void fill_correspondence_record(so_icp_ctx::CorrLast& L, const DevState& H, cons
 // batch_correspondences.cpp: what so_icp_register_batch does while so_icp_ctx::batch_corr_keep is on.  The set of a batch of n_hyp
 // hypotheses of n points: arrays at stride `bs` reserved, every record invalid, the packed scan copy enqueued on the context's queue
 int batch_corr_begin(so_icp_ctx* c, const float* d_scan, size_t n, int n_hyp, uint32_t bs);
+// sequence_correspondences.cpp: what the two sequence entries do while so_icp_ctx::seq_corr_keep is on.
+inline bool keeps_sequence_correspondences(const so_icp_ctx* c) { return c->seq_corr_keep && c->cfg.world_size <= 1; }
+// The set of a run of `count` frames of n_points[k] points: every array reserved for the sum of the frames (SO_ICP_E_NOMEM when that
+// cannot be had), every record invalid.  Before the run's first launch; nothing of the set is allocated after it
+int seq_corr_begin(so_icp_ctx* c, int count, const size_t* n_points);
+// frame k's packed scan copy, device to device on queue `s`
+int seq_corr_copy_scan(so_icp_ctx* c, int k, const float* d_scan, hipStream_t s);
+// the context's own d_nd / d_coeff / d_status into frame k's slice, three copies on the context's queue (as a batch lane does)
+int seq_corr_copy_records(so_icp_ctx* c, int k);
+// frame k ended with SO_ICP_OK, reported in H from `guess` with the loss of `ep`: its host record
+void seq_corr_note(so_icp_ctx* c, int k, const DevState& H, const double guess[7], const EvalParams& ep);
+// register_core, for a frame that goes through a per-frame entry (so_icp_ctx::seq_corr_frame >= 0): scan copy, record copies and the
+// host record, behind the registration's report and in front of whatever the entry enqueues next (so_icp_localization: the insert)
+int seq_corr_note_plain(so_icp_ctx* c, const float* d_scan, size_t n, const DevState& H, const double guess[7], const EvalParams& ep);
+// a run that returned an error leaves no frame's set
+void seq_corr_fail(so_icp_ctx* c);
 // so_icp_keep_correspondence_geometry: what the same entries do for so_icp_correspondence_geometry while so_icp_ctx::corr_geom_keep is on
 inline bool keeps_correspondence_geometry(const so_icp_ctx* c) { return c->corr_geom_keep && keeps_correspondences(c); }
 // the snapshot of the n points' status bytes, neighbour indices and neighbour points: one launch on the context's queue, behind the

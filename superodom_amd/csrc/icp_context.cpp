@@ -167,7 +167,7 @@ void launch_sweep(so_icp_ctx* c, const RegWork& w, MatchParams& mp_it, bool firs
                   uint32_t chain_expect, hipEvent_t ev_start, hipEvent_t ev_stop) {
   if (w.query_waves) {
     launch_knn_query_waves(w.d_scan, (uint32_t)w.n, c->d_state, pose, w.max_outer, w.lm_max, first, c->d_hist, c->view, mp_it, c->cfg.max_surface_features,
-                           c->d_status.as<uint8_t>(), c->d_nbr5.as<uint32_t>(), c->stream, ev_start, ev_stop, first ? chain_expect : 0u);
+                           w.corr.status, c->d_nbr5.as<uint32_t>(), c->stream, ev_start, ev_stop, first ? chain_expect : 0u);
   } else {
     if (begin_slot) {  // the first sweep of a scan binned ahead starts the registration itself (MatchParams::begin): the prologue's arguments
       mp_it.begin = 1; mp_it.begin_args.max_outer = w.max_outer; mp_it.begin_args.lm_max = w.lm_max; mp_it.begin_max_surface_features = c->cfg.max_surface_features;
@@ -622,6 +622,7 @@ static int register_core_once(so_icp_ctx* c, const float* d_scan, size_t n, cons
   fill_result(c, H, pose_in, st, pose_out, !c->batch_mode && !c->match_only);
   if (p.prior) st->prediction_source = 1;  // addAbsolutePoseConstraints, LidarSlam.cpp:297
   if (keep_corr) note_correspondences(c, H, pose_in, p.n, p.ep);
+  if (c->seq_corr_frame >= 0 && (rc = seq_corr_note_plain(c, p.d_scan, p.n, H, pose_in, p.ep))) return rc;  // (a frame of a run that keeps its sets)
   if (keep_corr && keeps_correspondence_geometry(c)) {  // (the report is in: d_status and d_nbr5 are the last fit pass's; the caller's insert comes behind)
     if ((rc = keep_neighbour_snapshot(c, p.n))) return rc;
     note_correspondence_geometry(c, p.mp);

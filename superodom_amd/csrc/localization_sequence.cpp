@@ -34,7 +34,17 @@ int so_icp_localization_sequence(so_icp_ctx* c, int count, const void* const* sc
   // so_icp_set_sequence_priors: one prior per frame of this call (another length: refused, they stay pending); taken out of the context
   // here -- consumed whatever this call returns --, frame k's goes in as the single prior its per-frame entry consumes
   if (!c->pending.count_matches(kPriorsRun, count)) return fail(c, SO_ICP_E_INVALID, "so_icp_localization_sequence: count differs from that of the pending so_icp_set_sequence_priors call");
+  // so_icp_keep_sequence_correspondences: the set of this run, reserved before its first launch; every frame's registration copies its
+  // scan and the context's records into its slice behind its report and in front of its insert (seq_corr_note_plain).  Before the
+  // priors are taken: SO_ICP_E_NOMEM leaves them pending
+  bool keep = false;
+  if (keeps_sequence_correspondences(c)) {
+    HIP_TRY(c, hipSetDevice(c->cfg.device_id));
+    if (const int rc = seq_corr_begin(c, count, n_points)) return rc;
+    keep = c->seq_corr->valid;
+  }
   const PriorSet run_priors = c->pending.take(kPriorsRun);
+  struct Frame { so_icp_ctx* c; ~Frame() { c->seq_corr_frame = -1; } } frame{c};
 
   double guess[7];
   std::memcpy(guess, pose0, sizeof(guess));
@@ -47,9 +57,11 @@ int so_icp_localization_sequence(so_icp_ctx* c, int count, const void* const* sc
     so_icp_stats local;
     so_icp_stats* st = stats ? stats + k : &local;
     run_priors.arm(c, k, guess);
+    c->seq_corr_frame = keep ? k : -1;
     const int rc = scans_on_device
                        ? so_icp_localization_dev(c, 1, guess, scans[k], n_points[k], times[k], pose_out, st)
                        : so_icp_localization(c, 1, guess, static_cast<const float*>(scans[k]), n_points[k], stride_bytes, times[k], pose_out, st);
+    if (rc < 0 && keep) seq_corr_fail(c);  // (a run that failed leaves no frame's set)
     if (rc != SO_ICP_OK) return rc;  // SO_ICP_NOT_ENOUGH_MAP_FEATURES or an error: the run stops at this frame (neither accepted nor inserted)
     if (n_done) *n_done = k + 1;
   }

@@ -73,6 +73,29 @@ inline uint64_t batch_record_ranges(const uint32_t* accepted, const uint8_t* val
 struct BatchTicket { uint32_t entry, tile; };
 constexpr BatchTicket batch_ticket(uint32_t t, uint32_t nblk) { return BatchTicket{t / nblk, t - (t / nblk) * nblk}; }
 
+// so_icp_sequence_correspondences: the same export over a selection of a run's FRAMES, whose point counts -- and so their tile counts --
+// differ; an entry may have no tile at all (an empty frame, a frame without a set).  tile_first[0 .. n_sel]: the prefix sums of the
+// entries' tile counts (tile_first[0] = 0, tile_first[n_sel] = the tickets of the launch).  Ticket t, 0 <= t < tile_first[n_sel], is tile
+// t - tile_first[e] of the entry e with tile_first[e] <= t < tile_first[e + 1]: entry-major as above, so an entry's look-back still
+// only waits for smaller tickets, and an entry without tiles gets no ticket.  A search of the prefix table (<= 11 steps for 1 024
+// entries).  constexpr: sequence_correspondences_kernel and the sums kernels call it too
+constexpr BatchTicket sequence_ticket(uint32_t t, const uint32_t* tile_first, uint32_t n_sel) {
+  uint32_t lo = 0, hi = n_sel;  // tile_first[lo] <= t < tile_first[hi]
+  while (hi - lo > 1u) {
+    const uint32_t mid = lo + (hi - lo) / 2u;
+    if (tile_first[mid] <= t) lo = mid; else hi = mid;
+  }
+  return BatchTicket{lo, t - tile_first[lo]};
+}
+// The status row of entry k starts at first_status[k] and is as long as its frame (valid or not): frames differ in n_points.
+// -> first_status[n_sel], the bytes of all rows
+inline uint64_t sequence_status_ranges(const size_t* n_points, const int32_t* frames, int n_sel, uint64_t* first_status) {
+  uint64_t at = 0;
+  for (int k = 0; k < n_sel; ++k) { first_status[k] = at; at += n_points[frames ? frames[k] : k]; }
+  first_status[n_sel] = at;
+  return at;
+}
+
 // scans of this many points or more are refused (refuse_scan_size, icp_context.cpp): the work-list counters hold 21 bits each
 constexpr size_t kMaxScanPoints = (size_t)1 << 21;
 

@@ -62,6 +62,7 @@ struct SequenceCall {
   PriorSet run_priors;                      // so_icp_set_sequence_priors: taken out of the context when the call started (empty: none were set)
   so_icp_ctx::SeqNext adopted;
   int slot_base = 0;
+  bool keep = false;                        // so_icp_keep_sequence_correspondences: this call leaves every frame's set (seq_corr_begin has reserved it)
 
   const double* delta(int k) const { return deltas + 7 * (size_t)k; }
   // the pose the chain continues from: the optimised pose of the registration, before MannualYawCorrection (fill_result)
@@ -78,6 +79,9 @@ struct SequenceCall {
   int run_plain(int k, const double guess[7]) {  // one registration through the ordinary entry points
     if (guesses_out) std::memcpy(guesses_out + 7 * (size_t)k, guess, 7 * sizeof(double));
     run_priors.arm(c, k, guess);  // (the frame's prior, measured at this guess where its mode says so; the entry below consumes it)
+    // (keep: the registration copies its scan and the context's records into frame k's slice behind its report, seq_corr_note_plain)
+    struct Frame { so_icp_ctx* c; ~Frame() { c->seq_corr_frame = -1; } } frame{c};
+    c->seq_corr_frame = keep ? k : -1;
     return scans_on_device ? so_icp_register_dev(c, scans[k], n_points[k], guess, poses_out + 7 * (size_t)k, &stats[k])
                            : so_icp_register(c, static_cast<const float*>(scans[k]), n_points[k], stride_bytes, guess, poses_out + 7 * (size_t)k, &stats[k]);
   }
@@ -101,6 +105,17 @@ struct SequenceCall {
     if (!scans_on_device || !r.query_waves) r.slot = &c->seq_slot[(slot_base + k) % so_icp_ctx::kStageSlots];
     r.max_outer = outer_limit(c->cfg.max_iterations); r.lm_max = lm_limit(c->cfg.lm_max_iterations);
     r.corr = CorrBuffers{c->d_nd.as<double4>(), c->d_coeff.as<double>(), c->d_status.as<uint8_t>()};
+    // keep: the frame's sweeps and solves write its slice of the kept set instead -- other kernel arguments, the same kernels.  With
+    // so_icp_keep_correspondences on as well the LAST frame writes the context's arrays as it always did (so_icp_correspondences reads
+    // them there) and collect() copies them into its slice
+    if (keep && k < count && n && !(k == count - 1 && keeps_correspondences(c))) r.corr = c->seq_corr->slice((size_t)k);
+  }
+  // keep: the packed copy of frame k's scan, on the sequence's own queue behind the scan's arrival and its binning (not on the context's
+  // queue, where it would lie between two chained registrations); run_chained waits for that queue before it returns
+  int keep_scan(int k) {
+    if (!keep) return SO_ICP_OK;
+    const SeqRun& r = runs[(size_t)k];
+    return seq_corr_copy_scan(c, k, r.d_scan, c->seq_stream);
   }
   int copy_in(SeqRun& r, const void* src) {  // a host scan into its slot, on the sequence's own queue
     if (r.copied) return SO_ICP_OK;
@@ -267,12 +282,14 @@ struct SequenceCall {
     (void)hipGetLastError();
     fill_result(c, H, guess, st, poses_out + 7 * (size_t)k, true);
     if (r.prior_mode != SO_ICP_PRIOR_NONE) st->prediction_source = 1;  // addAbsolutePoseConstraints, LidarSlam.cpp:297
+    if (keep) seq_corr_note(c, k, H, guess, r.ep);  // (so_icp_sequence_correspondences: this frame's record; its slice holds its last fit pass)
     if (k == count - 1 && keeps_correspondences(c)) {
-      // so_icp_correspondences exports the LAST registration of the run (the records of the others were overwritten by the launches
-      // chained behind them).  Its scan lies in a slot the next call refills on the sequence's own queue: copied now, and waited for
+      // so_icp_correspondences exports the LAST registration of the run (the context's arrays hold the records of no other: the launches
+      // chained behind a frame overwrite them; the sets of ALL frames: so_icp_keep_sequence_correspondences).  Its scan lies in a slot the next call refills on the sequence's own queue: copied now, and waited for
       if (const int rc = keep_scan_copy(c, r.d_scan, r.n)) return rc;
       const bool geometry = keeps_correspondence_geometry(c);  // (so_icp_correspondence_geometry: its snapshot, in front of the same wait)
       if (geometry) { if (const int rc = keep_neighbour_snapshot(c, r.n)) return rc; }
+      if (keep) { if (const int rc = seq_corr_copy_records(c, k)) return rc; }  // (both switches on: this frame wrote the context's arrays)
       HIP_TRY(c, hipStreamSynchronize(c->stream));
       note_correspondences(c, H, guess, r.n, r.ep);
       if (geometry) note_correspondence_geometry(c, r.mp);
@@ -316,6 +333,7 @@ struct SequenceCall {
       r0.d_scan = adopted.d_scan; r0.binned = adopted.binned; r0.needs_event = adopted.needs_event;
       if (r0.binned) { r0.d_binned = r0.slot->pb_binned.as<float4>(); r0.d_chunks = r0.slot->pb_chunks.as<uint32_t>(); }
     } else if ((rc = stage(runs[0], scans[0], pose0, false))) return rc;
+    if ((rc = keep_scan(0))) return rc;
     if ((rc = copy_ahead(1))) return rc;
     bool started = start(0, pose0, false, &rc);
     if (rc) return rc;
@@ -334,6 +352,7 @@ struct SequenceCall {
           double g[7];
           exact_guess(k + 1, g);
           if ((rc = stage(runs[(size_t)k + 1], scans[k + 1], g, false))) return rc;
+          if ((rc = keep_scan(k + 1))) return rc;
           started = start(k + 1, g, false, &rc);
           if (rc && rc != SO_ICP_NOT_ENOUGH_MAP_FEATURES) return rc;
         }
@@ -346,6 +365,7 @@ struct SequenceCall {
         double pred[7];
         pose_compose(r.guess, delta(k + 1), pred);  // (this registration will move r.guess by centimetres: good enough to bin under and to place the window)
         if ((rc = stage(runs[(size_t)k + 1], scans[k + 1], pred, false))) return rc;
+        if ((rc = keep_scan(k + 1))) return rc;
         if ((rc = copy_ahead(k + 2))) return rc;
         next_started = start(k + 1, pred, true, &rc);
         if (rc) return rc;
@@ -378,6 +398,7 @@ struct SequenceCall {
     }
     c->scan_staged = false;
     c->ev_used = 0;  // (the timing events of this call are free again)
+    if (keep) HIP_TRY(c, hipStreamSynchronize(c->seq_stream));  // (the scan copies of the kept set)
     drain.ok = true;
     return SO_ICP_OK;
   }
@@ -411,17 +432,23 @@ int so_icp_register_sequence(so_icp_ctx* c, int count, const void* const* scans,
   // so_icp_set_sequence_priors: one prior per frame of THIS call -- a call of another length leaves them pending, this one takes them
   // out of the context (consumed whatever it returns; the per-frame entries it may run do not meet them)
   if (!c->pending.count_matches(kPriorsRun, count)) return fail(c, SO_ICP_E_INVALID, "so_icp_register_sequence: count differs from that of the pending so_icp_set_sequence_priors call");
-  PriorSet run_priors = c->pending.take(kPriorsRun);
   HIP_TRY(c, hipSetDevice(c->cfg.device_id));
   if (stride_bytes == 0) stride_bytes = 12;
   for (int k = 0; k < count; ++k) if (!scans[k] && n_points[k]) return SO_ICP_E_INVALID;
+  // so_icp_keep_sequence_correspondences: the set of this run, reserved here -- before the run's first launch, and before the call has
+  // touched anything (SO_ICP_E_NOMEM leaves the priors pending and the last registration's set valid)
+  const bool keep = keeps_sequence_correspondences(c);
+  if (keep) { if (const int rc = seq_corr_begin(c, count, n_points)) return rc; }
+  PriorSet run_priors = c->pending.take(kPriorsRun);
   std::vector<so_icp_stats> local_stats;
   if (!stats) { local_stats.resize((size_t)count); stats = local_stats.data(); }
   SequenceCall call{c, count, scans, n_points, stride_bytes, scans_on_device, pose0, deltas, poses_out, guesses_out, stats, n_done};
   call.run_priors = std::move(run_priors);
   c->corr_last.valid = false;
+  call.keep = keep && c->seq_corr->valid;
   const int rc = chained_path(c, count, scans_on_device, stride_bytes) ? call.run_chained() : call.run_unchained();
   if (rc != SO_ICP_OK) c->corr_last.valid = false;  // (so_icp_correspondences: only a run that completed leaves its last registration's set)
+  if (rc < 0 && call.keep) seq_corr_fail(c);        // (so_icp_sequence_correspondences: a run that failed leaves no frame's set)
   return rc;
 }
 
