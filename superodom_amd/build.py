@@ -13,7 +13,7 @@ CSRC = os.path.join(HERE, "csrc")
 LIBDIR = os.path.join(HERE, "lib")
 LIB = os.path.join(LIBDIR, "libsoicp.so")
 SOURCES = ["kernels.hip", "map_kernels.hip", "icp_context.cpp", "staging.cpp", "sequence.cpp", "batch.cpp", "localization.cpp", "prefilter.cpp", "cloud_steps.cpp", "multi_gpu.cpp",
-           "local_map.cpp", "device_map.cpp", "localization_sequence.cpp", "feature_kernels.hip", "feature_extraction.cpp", "corr_kernels.hip", "corr_sums_kernels.hip", "corr_geometry_kernels.hip", "correspondences.cpp", "batch_correspondences.cpp", "sequence_correspondences.cpp", "pose_prior.cpp"]
+           "local_map.cpp", "device_map.cpp", "localization_sequence.cpp", "feature_kernels.hip", "feature_extraction.cpp", "corr_kernels.hip", "corr_sums_kernels.hip", "corr_geometry_kernels.hip", "correspondences.cpp", "selection_correspondences.cpp", "pose_prior.cpp"]
 HEADERS = ["kernels.h", "device_idioms.h", "map_kernels.h", "device_map.h", "lm_solver.h", "lm_endgame.h", "local_map.h", "so_math.h", "deskew_math.h", "untimed_math.h", "plane_fit.h", "plane_factor.h", "ctx.h", "reg_plan.h", "feature_kernels.h", "corr_kernels.h", "pose_prior.h", "eval_kernel_body.inc", "solve_kernel_body.inc", "corr_export_body.inc", "corr_sums_body.inc", os.path.join("..", "..", "include", "so_icp.h")]
 ARCH = "gfx950"
 # -ffp-contract=off: the fp64 plane fit / evaluation follow the reference's unfused arithmetic

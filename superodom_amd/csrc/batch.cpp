@@ -8,7 +8,7 @@
 // so_icp_set_batch_priors: every hypothesis may carry a pose prior of its own -- a table of prior blocks copied in front of round 0,
 // read by solve_kernel_batch_prior, which a round launches only where a hypothesis of its list carries one (reg_plan.h).
 // so_icp_keep_batch_correspondences: while the switch is on, a group's kernels write their records into the slices of the kept set
-// (other kernel arguments, the same kernels) and a lane copies its context's records there; batch_correspondences.cpp exports them.
+// (other kernel arguments, the same kernels) and a lane copies its context's records there; selection_correspondences.cpp exports them.
 #include <hip/hip_runtime_api.h>
 
 #include <algorithm>
@@ -76,7 +76,7 @@ int batch_priors_reserve(so_icp_ctx* c, uint32_t B) {
 // `priors`: the priors of the whole batch (so_icp_set_batch_priors; nullptr: none), of which hypothesis h of this group is element base + h
 // `keep`: the set this batch leaves (so_icp_keep_batch_correspondences; nullptr: the switch is off), hypothesis h of this group is its base + h
 int register_batch_group(so_icp_ctx* c, const float* d_scan, size_t n, const double* poses_in, int B, double* poses_out, so_icp_stats* stats,
-                         int32_t* hyp_rc, const int pos[3], int count_5x5, const PriorSet* priors, int base, so_icp_ctx::BatchCorrKept* keep) {
+                         int32_t* hyp_rc, const int pos[3], int count_5x5, const PriorSet* priors, int base, so_icp_ctx::KeptSets* keep) {
   const auto t_begin = std::chrono::steady_clock::now();
   std::vector<so_icp_stats> local;
   if (!stats) { local.resize((size_t)B); stats = local.data(); }
@@ -148,7 +148,8 @@ int register_batch_group(so_icp_ctx* c, const float* d_scan, size_t n, const dou
                (uint32_t)((size_t)kFitBlocksMax * kRecordChunksMax * 2), (uint32_t)(kSyncBytes / 4), 1u, v_grid};
   const BinTable bt{b.bin_key.as<uint32_t>(), b.bin_cnt.as<uint32_t>(), b.bin_off.as<uint32_t>(), lg};
   DevState* ds = b.states.as<DevState>();
-  if (keep && keep->bs != b.bs) return fail(c, SO_ICP_E_HIP, "so_icp_register_batch: the kept correspondence arrays have another stride than the batch's");
+  // (hypothesis h of the set lies at h * its stride: the last slice of this group is where the kernels will write it)
+  if (keep && keep->at[(size_t)(base + B - 1)] != (size_t)(base + B - 1) * b.bs) return fail(c, SO_ICP_E_HIP, "so_icp_register_batch: the kept correspondence arrays have another stride than the batch's");
   // (the kernels add the hypothesis' index in the group x bs to these: with the switch on, slice base + h of the kept set)
   const CorrBuffers corr = keep ? keep->slice((size_t)base) : CorrBuffers{b.nd.as<double4>(), b.coeff.as<double>(), b.status.as<uint8_t>()};
   // ---- binning of the scan under every hypothesis' pose: (queries x hypotheses) in three launches
@@ -232,7 +233,6 @@ int register_batch_group(so_icp_ctx* c, const float* d_scan, size_t n, const dou
     if (!prior_modes.empty() && prior_modes[(size_t)h] != SO_ICP_PRIOR_NONE) stats[h].prediction_source = 1;  // addAbsolutePoseConstraints, LidarSlam.cpp:297
   }
   if (keep) {  // (host memory only: the records themselves are where the kernels wrote them)
-    keep->a2 = ep.a2; keep->variant = ep.variant;
     for (int h = 0; h < B; ++h) fill_correspondence_record(keep->rec[(size_t)(base + h)], b.h_states[h], poses_in + 7 * (size_t)h, n, ep);
   }
   return SO_ICP_OK;
@@ -264,7 +264,7 @@ int so_icp_register_batch(so_icp_ctx* c, const float* xyz, const void* d_scan, s
     if (rc) return rc;
     scan = c->d_scan_own.as<float>();
   }
-  so_icp_ctx::BatchCorrKept* keep = nullptr;
+  so_icp_ctx::KeptSets* keep = nullptr;
   if (c->batch_corr_keep) {  // (the stride the groups below will use: batch_reserve never shrinks it)
     if (const int rc = batch_corr_begin(c, scan, n, n_hyp, std::max(batch_stride(n), c->batch.bs))) return rc;
     keep = c->batch_corr.get();
@@ -341,7 +341,6 @@ int so_icp_register_batch(so_icp_ctx* c, const float* xyz, const void* d_scan, s
   std::vector<int> hyp_rc((size_t)n_hyp, 0);
   const EvalParams lane_ep = eval_params(bw.plane_res, c->cfg.tukey_variant, c->ablate);  // (the loss of every lane's registrations)
   if (keep) {  // (groups that ran batched before the context degraded noted theirs: the lanes run every hypothesis again)
-    keep->a2 = lane_ep.a2; keep->variant = lane_ep.variant;
     for (so_icp_ctx::CorrLast& r : keep->rec) r.valid = false;
   }
   auto run_lane = [&](int l) {

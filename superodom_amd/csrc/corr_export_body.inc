@@ -1,14 +1,13 @@
-// corr_export_body.inc -- the body of correspondences_kernel and batch_correspondences_kernel (corr_kernels.hip), included once for
-// each with
-//   SO_CORR_BATCH  0: one kept set; the ticket is the tile, and scan, cnd, ccoeff, cstatus, n, pose, records, status_out, residual_out,
-//                     n_accepted, tile_cost and state are the kernel's arguments
-//                  1: entry k = ticket / nblk of a selection of hypotheses, tile = ticket % nblk; the kernel's arguments are the
-//                     hypotheses' arrays at stride bs, the entry tables (hyp, poses, rec_first) and the per-entry outputs, which the
-//                     body offsets to entry k's before the per-point text (no residual_out: the records carry the residuals)
-//                  2: a selection of a run's frames (sequence_correspondences_kernel): as 1, but the entries differ in their point and
-//                     tile counts -- ticket -> (entry, tile) is reg_plan.h's sequence_ticket over the prefix table tile_first, and an
-//                     entry's geometry, loss and pose come from its CorrSeqEntry
-// One text, three kernels: the export of a single registration launches the function it always launched.
+// corr_export_body.inc -- the body of correspondences_kernel and selection_correspondences_kernel (corr_kernels.hip), included once
+// for each with
+//   SO_CORR_SELECTION  0: one kept set; the ticket is the tile, and scan, cnd, ccoeff, cstatus, n, pose, records, status_out,
+//                         residual_out, n_accepted, tile_cost and state are the kernel's arguments
+//                      1: a selection of kept sets -- a batch's hypotheses or a run's frames --, whose point and tile counts may
+//                         differ: ticket -> (entry, tile) is reg_plan.h's selection_ticket over the prefix table tile_first; the
+//                         kernel's arguments are the arrays of ALL entries, and the body offsets to the entry's records, scan and
+//                         outputs and takes its loss and pose from its CorrSelEntry before the per-point text (no residual_out: the
+//                         records carry the residuals)
+// One text, two kernels: the export of a single registration launches the function it always launched.
   constexpr int kPer = (int)(kCorrTile / 256u);
   __shared__ uint32_t s_bid, s_pre[kPer * 4], s_agg, s_excl;
   __shared__ double s_cost[4];
@@ -16,15 +15,16 @@
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   if (tid == 0) s_bid = atomicAdd(ticket, 1u);
   __syncthreads();
-#if SO_CORR_BATCH == 2
-  // entry-major, as below: the tickets of entry k are tile_first[k] .. tile_first[k + 1] - 1, its look-back chain starts at its own word 0
-  // of the state table and waits only for smaller tickets; an entry without tiles has no ticket (its count stays the zero it was cleared to)
+#if SO_CORR_SELECTION
+  // entry-major: the tickets of entry k are tile_first[k] .. tile_first[k + 1] - 1, so a workgroup's look-back waits only for workgroups
+  // with smaller tickets, which were handed out earlier and therefore run; the entry's chain starts at its own word 0 of the state
+  // table.  An entry without tiles has no ticket (its count stays the zero it was cleared to)
   if (s_bid >= n_tiles) return;  // (never: the launch has n_tiles workgroups)
-  const host::BatchTicket mine_of = host::sequence_ticket(s_bid, tile_first, n_sel);  // (reg_plan.h)
+  const host::BatchTicket mine_of = host::selection_ticket(s_bid, tile_first, n_sel, n_tiles);  // (reg_plan.h)
   const uint32_t entry = mine_of.entry, bid = mine_of.tile;
-  const CorrSeqEntry& E = entries[entry];
+  const CorrSelEntry& E = entries[entry];
   const uint32_t n = E.n, tile0 = tile_first[entry], nblk = tile_first[entry + 1u] - tile0;
-  const float* __restrict__ scan = scan_all + (size_t)E.at * 3;
+  const float* __restrict__ scan = scan_all + (size_t)E.scan_at * 3;
   const double4* __restrict__ cnd = cnd_all + (size_t)E.at;
   const double* __restrict__ ccoeff = ccoeff_all + (size_t)E.at;
   const uint8_t* __restrict__ cstatus = cstatus_all + (size_t)E.at;
@@ -36,23 +36,6 @@
   uint32_t* __restrict__ n_accepted = counts + entry;
   double* __restrict__ tile_cost = tile_cost_all + tile0;
   unsigned long long* __restrict__ state = state_all + tile0;
-#elif SO_CORR_BATCH
-  // hypothesis-major: the workgroups of entry k hold consecutive tickets, so a workgroup's look-back waits only for workgroups with
-  // smaller tickets, which were handed out earlier and therefore run; the entry's chain starts at its own word 0
-  const host::BatchTicket mine_of = host::batch_ticket(s_bid, nblk);  // (reg_plan.h)
-  const uint32_t entry = mine_of.entry, bid = mine_of.tile;
-  const uint32_t h = hyp[entry];
-  const uint32_t n = h == kCorrNoHypothesis ? 0u : n_points;  // (an entry without a set: no point, no record, a count of zero)
-  const size_t slice = h == kCorrNoHypothesis ? 0 : (size_t)h * bs;
-  const double4* __restrict__ cnd = cnd_all + slice;
-  const double* __restrict__ ccoeff = ccoeff_all + slice;
-  const uint8_t* __restrict__ cstatus = cstatus_all + slice;
-  const Pose pose = pose_from_array(poses + (size_t)entry * 7);
-  uint8_t* __restrict__ records = records_all + (size_t)rec_first[entry] * kCorrRecordBytes;
-  uint8_t* __restrict__ status_out = status_all + (size_t)entry * n_points;
-  uint32_t* __restrict__ n_accepted = counts + entry;
-  double* __restrict__ tile_cost = tile_cost_all + (size_t)entry * nblk;
-  unsigned long long* __restrict__ state = state_all + (size_t)entry * nblk;
 #else
   const uint32_t bid = s_bid;
 #endif
@@ -71,7 +54,7 @@
     if (i < n) {
       const uint8_t status = cstatus[i];
       ok = status == 0;  // MatchingResult::SUCCESS
-#if !SO_CORR_BATCH
+#if !SO_CORR_SELECTION
       float rf = __builtin_nanf("");
 #endif
       if (ok) {
@@ -82,12 +65,12 @@
         tukey_rho(L, r * r, rho0, rho1);
         res[q] = r; wgt[q] = co[q] * rho1;
         cost = SO_FMA(0.5 * co[q], rho0, cost);
-#if !SO_CORR_BATCH
+#if !SO_CORR_SELECTION
         rf = (float)r;
 #endif
       }
       status_out[i] = status;
-#if !SO_CORR_BATCH
+#if !SO_CORR_SELECTION
       residual_out[i] = rf;
 #endif
     }

@@ -46,63 +46,43 @@ struct CorrSumsHist { double v[16]; };  // LmSums::hist of every record written:
 void launch_correspondence_sums(const CorrSumsIn& in, const double* d_poses, uint32_t n_poses, const CorrSumsHist& hist, double* d_partials,
                                 double* d_sums_out, hipStream_t s);
 
-// ---- so_icp_batch_correspondences / so_icp_batch_correspondence_sums: both exports for a selection of so_icp_register_batch's
-// hypotheses, one launch each (batch_correspondences_kernel in corr_kernels.hip, batch_correspondence_sums_kernel and its add kernel in
-// corr_sums_kernels.hip)
-constexpr uint32_t kCorrNoHypothesis = 0xFFFFFFFFu;  // in the table of hypothesis indices: an entry without a set (no point is read)
-// What they read: the batch's packed scan copy, the records of ALL its hypotheses (hypothesis h at element h * bs of each array), the
-// device table of the selection's hypothesis indices, the loss of THAT batch
-struct CorrBatchIn {
-  const float* scan;
-  CorrBuffers corr;
-  uint32_t bs, n, n_sel;
-  const uint32_t* hyp;  // n_sel, device
-  double a2;
-  int32_t variant;
-};
-// d_poses: n_sel x 7 doubles; d_rec_first: n_sel record offsets into d_records, which has room for the last entry's offset + n records;
-// d_status_out n_sel x n bytes; d_counts n_sel words; d_tile_cost and d_state n_sel x correspondence_workgroups(n) words each.  d_state,
-// d_ticket and d_counts zeroed by the caller.  One launch of n_sel x correspondence_workgroups(n) workgroups.
-void launch_batch_correspondences(const CorrBatchIn& in, const double* d_poses, const unsigned long long* d_rec_first, uint8_t* d_records,
-                                  uint8_t* d_status_out, uint32_t* d_counts, double* d_tile_cost, unsigned long long* d_state, uint32_t* d_ticket,
-                                  hipStream_t s);
-// d_poses: n_sel x n_poses x 7 doubles; d_hists: n_sel x 16 doubles; d_partials: n_sel x n_poses x correspondence_workgroups(n) x
-// kCorrSumsAcc doubles, every one written; d_sums_out: n_sel x n_poses LmSums.  Two launches, nothing to clear.
-void launch_batch_correspondence_sums(const CorrBatchIn& in, const double* d_poses, uint32_t n_poses, const double* d_hists, double* d_partials,
-                                      double* d_sums_out, hipStream_t s);
-
-// ---- so_icp_sequence_correspondences / so_icp_sequence_correspondence_sums: both exports for a selection of the FRAMES of a run
-// (so_icp_register_sequence, so_icp_localization_sequence), whose point counts differ (sequence_correspondences_kernel in
-// corr_kernels.hip, sequence_correspondence_sums_kernel and its add kernel in corr_sums_kernels.hip)
-// One entry of the selection, as the kernels read it from a device table: where the frame's points lie in the kept arrays (point
-// `at` of nd / coeff / status, float 3 `at` of the packed scans), where its records and its status row go, the loss of THAT frame,
-// the evaluation pose (the export; the sums have a pose table of their own) and its points (0: an entry without a set, or an empty frame)
-struct CorrSeqEntry {
+// ---- the exports over a SELECTION of kept sets -- so_icp_batch_correspondences / so_icp_batch_correspondence_sums (the hypotheses of
+// so_icp_register_batch) and so_icp_sequence_correspondences / so_icp_sequence_correspondence_sums (the frames of a run): one launch of
+// selection_correspondences_kernel (corr_kernels.hip), two of selection_correspondence_sums_kernel and its add kernel
+// (corr_sums_kernels.hip), whichever of the two the selection comes from.
+// One entry of the selection, as the kernels read it from a device table: where the entry's records lie in the kept arrays (element
+// `at` of nd / coeff / status) and where its scan lies (point `scan_at` of the packed scans: a run keeps a scan per frame beside its
+// records, a batch one scan for all hypotheses), where its records and its status row go, the loss of THAT registration, the
+// evaluation pose (the export; the sums have a pose table of their own) and its points (0: an entry without a set, or an empty scan)
+struct CorrSelEntry {
   unsigned long long at, rec_first, status_first;
   double a2;
   double pose[7];
   uint32_t n;
   int32_t variant;
+  unsigned long long scan_at;
 };
-static_assert(sizeof(CorrSeqEntry) == 96, "the host fills a table of these");
-// What they read: the packed scans and the records of ALL frames of the run, the entry table and the prefix table of the entries' tile
-// counts (n_sel + 1 words, reg_plan.h: sequence_ticket), both on the device; n_tiles = tile_first[n_sel]
-struct CorrSeqIn {
+static_assert(sizeof(CorrSelEntry) == 104 && offsetof(CorrSelEntry, scan_at) == 96, "the host fills a table of these");
+// What they read: the packed scans and the records of ALL entries of the kept set, the entry table and the prefix table of the entries'
+// tile counts (n_sel + 1 words, reg_plan.h: selection_tile_table), both on the device; n_tiles = tile_first[n_sel], max_tiles the tiles
+// of the largest entry
+struct CorrSelIn {
   const float* scan;
   CorrBuffers corr;
-  const CorrSeqEntry* entries;
+  const CorrSelEntry* entries;
   const uint32_t* tile_first;
-  uint32_t n_sel, n_tiles;
+  uint32_t n_sel, n_tiles, max_tiles;
 };
-// d_records: room for the last entry's offset + the points of the largest selected frame; d_status_out: the rows of all entries;
+// d_records: room for the last entry's offset + the points of the largest selected entry; d_status_out: the rows of all entries;
 // d_counts n_sel words; d_tile_cost and d_state n_tiles words each.  d_state, d_ticket and d_counts zeroed by the caller.  One launch of
 // n_tiles workgroups.
-void launch_sequence_correspondences(const CorrSeqIn& in, uint8_t* d_records, uint8_t* d_status_out, uint32_t* d_counts, double* d_tile_cost,
-                                     unsigned long long* d_state, uint32_t* d_ticket, hipStream_t s);
+void launch_selection_correspondences(const CorrSelIn& in, uint8_t* d_records, uint8_t* d_status_out, uint32_t* d_counts, double* d_tile_cost,
+                                      unsigned long long* d_state, uint32_t* d_ticket, hipStream_t s);
 // d_poses: n_sel x n_poses x 7 doubles; d_hists: n_sel x 16 doubles; d_partials: n_tiles x n_poses x kCorrSumsAcc doubles (entry e at
-// tile_first[e] x n_poses vectors, [pose][tile] inside), every one written; d_sums_out: n_sel x n_poses LmSums.  Two launches.
-void launch_sequence_correspondence_sums(const CorrSeqIn& in, const double* d_poses, uint32_t n_poses, const double* d_hists, double* d_partials,
-                                         double* d_sums_out, hipStream_t s);
+// tile_first[e] x n_poses vectors, [pose][tile] inside), every one written; d_sums_out: n_sel x n_poses LmSums.  Two launches, the first
+// of max_tiles x n_sel workgroups.
+void launch_selection_correspondence_sums(const CorrSelIn& in, const double* d_poses, uint32_t n_poses, const double* d_hists, double* d_partials,
+                                          double* d_sums_out, hipStream_t s);
 
 // ---- corr_geometry_kernels.hip: so_icp_correspondence_geometry, the neighbours, PCA and observability labels of the kept set
 // bytes of one so_icp_correspondence_geometry_record; the refit's plane of so_icp_debug_correspondence_refit (n[3], d, coeff)

@@ -3,10 +3,9 @@
 // point, in scan order, with the residual and the robust weight of the record at a pose of the caller's choice.
 //   correspondences_kernel  reads the records the last fit pass left in memory (kernels.hip eval_pass: corr.nd / corr.coeff /
 //                           corr.status, indexed like the scan) and the scan copy the registration kept; compacts the accepted ones
-//   batch_correspondences_kernel  the same for a selection of so_icp_register_batch's hypotheses, all in one launch
-//                           (so_icp_batch_correspondences)
-//   sequence_correspondences_kernel  the same for a selection of the frames of a run, whose point counts differ
-//                           (so_icp_sequence_correspondences); all three kernels are one text, corr_export_body.inc
+//   selection_correspondences_kernel  the same for a selection of kept sets, all in one launch: the hypotheses of
+//                           so_icp_register_batch (so_icp_batch_correspondences) or the frames of a run, whose point counts differ
+//                           (so_icp_sequence_correspondences); one text, two kernels: corr_export_body.inc
 // Nothing here runs during a registration and no registration kernel is changed; residual, loss and weight are plane_factor.h's, as
 // in eval_pass.
 #include <hip/hip_runtime.h>
@@ -30,46 +29,27 @@ __global__ __launch_bounds__(256) void correspondences_kernel(const float* __res
                                                               uint8_t* __restrict__ status_out, float* __restrict__ residual_out,
                                                               uint32_t* __restrict__ n_accepted, double* __restrict__ tile_cost,
                                                               unsigned long long* __restrict__ state, uint32_t* __restrict__ ticket, uint32_t nblk) {
-#define SO_CORR_BATCH 0
+#define SO_CORR_SELECTION 0
 #include "corr_export_body.inc"
-#undef SO_CORR_BATCH
+#undef SO_CORR_SELECTION
 }
 
-// so_icp_batch_correspondences: the same export for a SELECTION of so_icp_register_batch's hypotheses in one launch.  Entry k of the
-// selection is hypothesis hyp[k] (kCorrNoHypothesis: an entry without a set), whose records lie at hyp[k] * bs in the kept arrays; it is
-// evaluated at poses[7 k ..], its records go to rec_first[k] of the record buffer, its status bytes to row k, its count to counts[k] and
-// its tile costs and look-back words to row k of tables of nblk words.  A workgroup takes ONE global ticket t and works on tile
-// t % nblk of entry t / nblk: it never depends on where the hardware placed it (blockIdx), only on workgroups that drew their tickets
-// before it.
-__global__ __launch_bounds__(256) void batch_correspondences_kernel(const float* __restrict__ scan, const double4* __restrict__ cnd_all,
-                                                                    const double* __restrict__ ccoeff_all, const uint8_t* __restrict__ cstatus_all,
-                                                                    uint32_t bs, uint32_t n_points, const uint32_t* __restrict__ hyp,
-                                                                    const double* __restrict__ poses, const unsigned long long* __restrict__ rec_first,
-                                                                    double a2, int variant, uint8_t* __restrict__ records_all,
-                                                                    uint8_t* __restrict__ status_all, uint32_t* __restrict__ counts,
-                                                                    double* __restrict__ tile_cost_all, unsigned long long* __restrict__ state_all,
-                                                                    uint32_t* __restrict__ ticket, uint32_t nblk) {
-#define SO_CORR_BATCH 1
+// so_icp_batch_correspondences / so_icp_sequence_correspondences: the same export for a SELECTION of kept sets in one launch.  Entry k is
+// described by entries[k] (corr_kernels.h: where its records and its scan lie in the kept arrays, its point count -- 0 for an entry
+// without a set --, its loss, its pose, where its records and its status row go); the entries have tile_first[k + 1] - tile_first[k]
+// tiles each, possibly none.  A workgroup takes ONE global ticket and works on the entry and tile selection_ticket maps it to
+// (reg_plan.h): it never depends on where the hardware placed it (blockIdx), only on workgroups that drew their tickets before it.
+// Counts, tile costs and look-back words: counts[k], and the words tile_first[k] .. of tables of n_tiles words.
+__global__ __launch_bounds__(256) void selection_correspondences_kernel(const float* __restrict__ scan_all, const double4* __restrict__ cnd_all,
+                                                                        const double* __restrict__ ccoeff_all, const uint8_t* __restrict__ cstatus_all,
+                                                                        const CorrSelEntry* __restrict__ entries, const uint32_t* __restrict__ tile_first,
+                                                                        uint32_t n_sel, uint32_t n_tiles, uint8_t* __restrict__ records_all,
+                                                                        uint8_t* __restrict__ status_all, uint32_t* __restrict__ counts,
+                                                                        double* __restrict__ tile_cost_all, unsigned long long* __restrict__ state_all,
+                                                                        uint32_t* __restrict__ ticket) {
+#define SO_CORR_SELECTION 1
 #include "corr_export_body.inc"
-#undef SO_CORR_BATCH
-}
-
-// so_icp_sequence_correspondences: the same export for a selection of a run's FRAMES in one launch.  Entry k is described by entries[k]
-// (corr_kernels.h: where the frame's points lie in the kept arrays, its point count -- 0 for an entry without a set --, its loss, its
-// pose, where its records and its status row go); the entries have tile_first[k + 1] - tile_first[k] tiles each, possibly none.  A
-// workgroup takes ONE global ticket and works on the entry and tile sequence_ticket maps it to (reg_plan.h): as above it depends only
-// on workgroups that drew their tickets before it, never on one the hardware has not placed yet.  Counts, tile costs and look-back words:
-// counts[k], and the words tile_first[k] .. of tables of n_tiles words.
-__global__ __launch_bounds__(256) void sequence_correspondences_kernel(const float* __restrict__ scan_all, const double4* __restrict__ cnd_all,
-                                                                       const double* __restrict__ ccoeff_all, const uint8_t* __restrict__ cstatus_all,
-                                                                       const CorrSeqEntry* __restrict__ entries, const uint32_t* __restrict__ tile_first,
-                                                                       uint32_t n_sel, uint32_t n_tiles, uint8_t* __restrict__ records_all,
-                                                                       uint8_t* __restrict__ status_all, uint32_t* __restrict__ counts,
-                                                                       double* __restrict__ tile_cost_all, unsigned long long* __restrict__ state_all,
-                                                                       uint32_t* __restrict__ ticket) {
-#define SO_CORR_BATCH 2
-#include "corr_export_body.inc"
-#undef SO_CORR_BATCH
+#undef SO_CORR_SELECTION
 }
 
 void launch_correspondences(const CorrExportIn& in, uint8_t* d_records, uint8_t* d_status_out, float* d_residual_out, uint32_t* d_n_accepted,
@@ -80,20 +60,11 @@ void launch_correspondences(const CorrExportIn& in, uint8_t* d_records, uint8_t*
                                               d_status_out, d_residual_out, d_n_accepted, d_tile_cost, d_state, d_ticket, nblk);
 }
 
-void launch_batch_correspondences(const CorrBatchIn& in, const double* d_poses, const unsigned long long* d_rec_first, uint8_t* d_records,
-                                  uint8_t* d_status_out, uint32_t* d_counts, double* d_tile_cost, unsigned long long* d_state, uint32_t* d_ticket,
-                                  hipStream_t s) {
-  const uint32_t nblk = correspondence_workgroups(in.n);
-  if (!nblk || !in.n_sel) return;
-  batch_correspondences_kernel<<<nblk * in.n_sel, 256, 0, s>>>(in.scan, in.corr.nd, in.corr.coeff, in.corr.status, in.bs, in.n, in.hyp, d_poses, d_rec_first,
-                                                              in.a2, in.variant, d_records, d_status_out, d_counts, d_tile_cost, d_state, d_ticket, nblk);
-}
-
-void launch_sequence_correspondences(const CorrSeqIn& in, uint8_t* d_records, uint8_t* d_status_out, uint32_t* d_counts, double* d_tile_cost,
-                                     unsigned long long* d_state, uint32_t* d_ticket, hipStream_t s) {
+void launch_selection_correspondences(const CorrSelIn& in, uint8_t* d_records, uint8_t* d_status_out, uint32_t* d_counts, double* d_tile_cost,
+                                      unsigned long long* d_state, uint32_t* d_ticket, hipStream_t s) {
   if (!in.n_tiles || !in.n_sel) return;
-  sequence_correspondences_kernel<<<in.n_tiles, 256, 0, s>>>(in.scan, in.corr.nd, in.corr.coeff, in.corr.status, in.entries, in.tile_first, in.n_sel,
-                                                            in.n_tiles, d_records, d_status_out, d_counts, d_tile_cost, d_state, d_ticket);
+  selection_correspondences_kernel<<<in.n_tiles, 256, 0, s>>>(in.scan, in.corr.nd, in.corr.coeff, in.corr.status, in.entries, in.tile_first, in.n_sel,
+                                                             in.n_tiles, d_records, d_status_out, d_counts, d_tile_cost, d_state, d_ticket);
 }
 
 }  // namespace soicp

@@ -1,27 +1,27 @@
 // corr_sums_body.inc -- the bodies of corr_sums_kernels.hip's kernels, included once for each kernel with
-//   SO_SUMS_ADD    0: the per-tile partial sums (correspondence_sums_kernel, batch_correspondence_sums_kernel)
-//                  1: the tiles added in tile order (correspondence_sums_add_kernel, batch_correspondence_sums_add_kernel)
-//   SO_SUMS_BATCH  0: one kept set, the kernel's arguments as they are
-//                  1: entry blockIdx.y (partial sums) or blockIdx.x / n_poses (add) of a selection of so_icp_register_batch's hypotheses:
-//                     the hypotheses' arrays at stride bs, n_poses poses per entry, one histogram per entry; the body offsets to the
-//                     entry's before the text both share
-//                  2: entry sequence_ticket(blockIdx.x) (partial sums) or blockIdx.x / n_poses (add) of a selection of a run's frames:
-//                     the entries differ in their point and tile counts, an entry's geometry and loss come from its CorrSeqEntry, its
-//                     partial vectors lie at tile_first[entry] x n_poses, [pose][tile] inside
-// One text per pair: so_icp_correspondence_sums launches the functions it always launched, and an entry's sums are formed by the
-// same expressions, the same tree and the same tile order as those of a context that kept that hypothesis alone.
+//   SO_SUMS_ADD        0: the per-tile partial sums (correspondence_sums_kernel, selection_correspondence_sums_kernel)
+//                      1: the tiles added in tile order (correspondence_sums_add_kernel, selection_correspondence_sums_add_kernel)
+//   SO_SUMS_SELECTION  0: one kept set, the kernel's arguments as they are
+//                      1: entry blockIdx.y (partial sums) or blockIdx.x / n_poses (add) of a selection of kept sets -- a batch's
+//                         hypotheses or a run's frames --, whose point and tile counts may differ (the grid is as wide as the largest
+//                         entry; a workgroup beyond its entry's tiles leaves at once): an entry's records, scan and loss come from
+//                         its CorrSelEntry, it has n_poses poses and one histogram of its own, and its partial vectors lie at
+//                         tile_first[entry] x n_poses, [pose][tile] inside
+// One text per pair, two kernels each: so_icp_correspondence_sums launches the functions it always launched, and an entry's sums are
+// formed by the same expressions, the same tree and the same tile order as those of a context that kept that entry alone.
 #if !SO_SUMS_ADD
   constexpr int kPer = (int)(kCorrTile / 256u), kAcc = (int)kCorrSumsAcc;
   static_assert(kAcc == kPlaneFactorSums, "plane_factor_add fills a partial vector");
   __shared__ SumsPose s_pose[kCorrSumsMaxPoses];
   __shared__ double s_part[2][4][kAcc];
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-#if SO_SUMS_BATCH == 2
-  const host::BatchTicket mine_of = host::sequence_ticket(blockIdx.x, tile_first, n_sel);  // (no look-back here: the launch index serves)
-  const uint32_t entry = mine_of.entry, bid = mine_of.tile;
-  const CorrSeqEntry& E = entries[entry];
-  const uint32_t n = E.n, tile0 = tile_first[entry], ntile = tile_first[entry + 1u] - tile0;
-  const float* __restrict__ scan = scan_all + (size_t)E.at * 3;
+#if SO_SUMS_SELECTION
+  const uint32_t entry = blockIdx.y, bid = blockIdx.x;  // (no look-back here, so no ticket: the launch index serves)
+  const CorrSelEntry& E = entries[entry];
+  const uint32_t n = E.n;
+  if (bid * kCorrTile >= n) return;  // (an entry smaller than the largest of the selection; the whole workgroup, in front of every barrier)
+  const uint32_t tile0 = tile_first[entry], ntile = tile_first[entry + 1u] - tile0;
+  const float* __restrict__ scan = scan_all + (size_t)E.scan_at * 3;
   const double4* __restrict__ cnd = cnd_all + (size_t)E.at;
   const double* __restrict__ ccoeff = ccoeff_all + (size_t)E.at;
   const uint8_t* __restrict__ cstatus = cstatus_all + (size_t)E.at;
@@ -33,16 +33,6 @@
 #else
   const uint32_t bid = blockIdx.x;
 #define SO_SUMS_NTILE gridDim.x
-#endif
-#if SO_SUMS_BATCH == 1
-  const uint32_t entry = blockIdx.y, h = hyp[entry];
-  const uint32_t n = h == kCorrNoHypothesis ? 0u : n_points;  // (an entry without a set: every partial sum +0.0)
-  const size_t slice = h == kCorrNoHypothesis ? 0 : (size_t)h * bs;
-  const double4* __restrict__ cnd = cnd_all + slice;
-  const double* __restrict__ ccoeff = ccoeff_all + slice;
-  const uint8_t* __restrict__ cstatus = cstatus_all + slice;
-  const double* __restrict__ poses = poses_all + (size_t)entry * n_poses * 7;
-  double* __restrict__ partials = partials_all + (size_t)entry * n_poses * gridDim.x * kAcc;
 #endif
   if ((uint32_t)tid < n_poses) {
     SumsPose P;
@@ -103,7 +93,7 @@
   constexpr uint32_t kAcc = kCorrSumsAcc, kWords = kCorrSumsWords, kChunk = 64;
   __shared__ double s_in[kChunk * kAcc];
   const uint32_t k = blockIdx.x, tid = threadIdx.x;
-#if SO_SUMS_BATCH == 2
+#if SO_SUMS_SELECTION
   const uint32_t entry = k / n_poses, tile0 = tile_first[entry], nblk = tile_first[entry + 1u] - tile0;
   const double* mine = partials + ((size_t)tile0 * n_poses + (size_t)(k - entry * n_poses) * nblk) * kAcc;
 #else
@@ -119,7 +109,7 @@
     __syncthreads();
   }
   if (tid < kAcc) sums_out[(size_t)k * kWords + tid] = v;
-#if SO_SUMS_BATCH
+#if SO_SUMS_SELECTION
   else if (tid < kWords) sums_out[(size_t)k * kWords + tid] = hists[(size_t)(k / n_poses) * (kWords - kAcc) + (tid - kAcc)];
 #else
   else if (tid < kWords) sums_out[(size_t)k * kWords + tid] = hist.v[tid - kAcc];

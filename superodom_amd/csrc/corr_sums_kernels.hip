@@ -5,10 +5,10 @@
 //                                   point, and loops over the poses: one partial vector of the 29 sums per (tile, pose)
 //   correspondence_sums_add_kernel  adds the tiles in tile order, one thread per (pose, component), into so_icp_sums records (a pose's
 //                                   partial vectors reach its threads through LDS, 64 tiles at a time)
-//   batch_correspondence_sums_kernel, batch_correspondence_sums_add_kernel  the same two for a selection of so_icp_register_batch's
-//                                   hypotheses in one launch each (so_icp_batch_correspondence_sums)
-//   sequence_correspondence_sums_kernel, sequence_correspondence_sums_add_kernel  the same two for a selection of a run's frames, whose
-//                                   point counts differ (so_icp_sequence_correspondence_sums); one text per triple, corr_sums_body.inc
+//   selection_correspondence_sums_kernel, selection_correspondence_sums_add_kernel  the same two for a selection of kept sets in one
+//                                   launch each: the hypotheses of so_icp_register_batch (so_icp_batch_correspondence_sums) or the
+//                                   frames of a run, whose point counts differ (so_icp_sequence_correspondence_sums); one text per
+//                                   pair, two kernels each: corr_sums_body.inc
 // Nothing here runs during a registration.  The per-point arithmetic is plane_factor.h's, as in eval_pass and correspondences_kernel.
 // No atomics: every sum is a fixed tree, so two calls give the same bits, a pose's sums do not depend on the other poses of the call,
 // and `cost` is so_icp_correspondences' cost at that pose bit for bit.
@@ -16,7 +16,6 @@
 
 #include "corr_kernels.h"
 #include "plane_factor.h"
-#include "reg_plan.h"
 
 namespace soicp {
 
@@ -34,39 +33,24 @@ __global__ __launch_bounds__(256) void correspondence_sums_kernel(const float* _
                                                                   const double* __restrict__ poses, uint32_t n_poses, double a2, int variant,
                                                                   double* __restrict__ partials) {
 #define SO_SUMS_ADD 0
-#define SO_SUMS_BATCH 0
+#define SO_SUMS_SELECTION 0
 #include "corr_sums_body.inc"
-#undef SO_SUMS_BATCH
+#undef SO_SUMS_SELECTION
 #undef SO_SUMS_ADD
 }
-// so_icp_batch_correspondence_sums: grid (tiles, entries of the selection).  Entry blockIdx.y is hypothesis hyp[entry] of the last batch
-// (kCorrNoHypothesis: an entry without a set), its records at hyp[entry] * bs of the kept arrays, its n_poses poses -- the table in LDS --
-// at poses_all[entry][..][7]; partials_all: [entry][pose][tile][kCorrSumsAcc].
-__global__ __launch_bounds__(256) void batch_correspondence_sums_kernel(const float* __restrict__ scan, const double4* __restrict__ cnd_all,
-                                                                        const double* __restrict__ ccoeff_all, const uint8_t* __restrict__ cstatus_all,
-                                                                        uint32_t bs, uint32_t n_points, const uint32_t* __restrict__ hyp,
-                                                                        const double* __restrict__ poses_all, uint32_t n_poses, double a2, int variant,
-                                                                        double* __restrict__ partials_all) {
+// so_icp_batch_correspondence_sums / so_icp_sequence_correspondence_sums: grid (tiles of the largest entry, entries of the selection).
+// Workgroup (b, k) is tile b of entry k, and leaves at once where the entry has fewer tiles (nothing is compacted, so the launch index
+// serves and no ticket is drawn).  An entry's records, scan and loss come from entries[entry], its n_poses poses -- the table in LDS --
+// from poses_all[entry][..][7]; its partial vectors lie at tile_first[entry] x n_poses of partials_all, [pose][tile] inside.
+__global__ __launch_bounds__(256) void selection_correspondence_sums_kernel(const float* __restrict__ scan_all, const double4* __restrict__ cnd_all,
+                                                                            const double* __restrict__ ccoeff_all, const uint8_t* __restrict__ cstatus_all,
+                                                                            const CorrSelEntry* __restrict__ entries, const uint32_t* __restrict__ tile_first,
+                                                                            const double* __restrict__ poses_all, uint32_t n_poses,
+                                                                            double* __restrict__ partials_all) {
 #define SO_SUMS_ADD 0
-#define SO_SUMS_BATCH 1
+#define SO_SUMS_SELECTION 1
 #include "corr_sums_body.inc"
-#undef SO_SUMS_BATCH
-#undef SO_SUMS_ADD
-}
-
-// so_icp_sequence_correspondence_sums: one workgroup per tile of the selection, n_tiles = tile_first[n_sel] in all; workgroup b is the
-// tile sequence_ticket(b) names (reg_plan.h: the export's mapping; nothing is compacted, so the launch index serves as the ticket).  An
-// entry's geometry and loss come from entries[entry], its n_poses poses -- the table in LDS -- from poses_all[entry][..][7]; its partial
-// vectors lie at tile_first[entry] x n_poses of partials_all, [pose][tile] inside.
-__global__ __launch_bounds__(256) void sequence_correspondence_sums_kernel(const float* __restrict__ scan_all, const double4* __restrict__ cnd_all,
-                                                                           const double* __restrict__ ccoeff_all, const uint8_t* __restrict__ cstatus_all,
-                                                                           const CorrSeqEntry* __restrict__ entries, const uint32_t* __restrict__ tile_first,
-                                                                           uint32_t n_sel, const double* __restrict__ poses_all, uint32_t n_poses,
-                                                                           double* __restrict__ partials_all) {
-#define SO_SUMS_ADD 0
-#define SO_SUMS_BATCH 2
-#include "corr_sums_body.inc"
-#undef SO_SUMS_BATCH
+#undef SO_SUMS_SELECTION
 #undef SO_SUMS_ADD
 }
 
@@ -78,31 +62,21 @@ __global__ __launch_bounds__(256) void sequence_correspondence_sums_kernel(const
 __global__ __launch_bounds__(256) void correspondence_sums_add_kernel(const double* __restrict__ partials, uint32_t nblk, CorrSumsHist hist,
                                                                       double* __restrict__ sums_out) {
 #define SO_SUMS_ADD 1
-#define SO_SUMS_BATCH 0
+#define SO_SUMS_SELECTION 0
 #include "corr_sums_body.inc"
-#undef SO_SUMS_BATCH
-#undef SO_SUMS_ADD
-}
-// One workgroup per (entry, pose) of so_icp_batch_correspondence_sums: the same additions, then the 16 histogram words of the entry's
-// hypothesis (hists: [entry][16])
-__global__ __launch_bounds__(256) void batch_correspondence_sums_add_kernel(const double* __restrict__ partials, uint32_t nblk, uint32_t n_poses,
-                                                                            const double* __restrict__ hists, double* __restrict__ sums_out) {
-#define SO_SUMS_ADD 1
-#define SO_SUMS_BATCH 1
-#include "corr_sums_body.inc"
-#undef SO_SUMS_BATCH
+#undef SO_SUMS_SELECTION
 #undef SO_SUMS_ADD
 }
 
-// One workgroup per (entry, pose) of so_icp_sequence_correspondence_sums: the entry's own number of tiles, added in tile order (none: +0.0
-// throughout), then the 16 histogram words of the entry's frame
-__global__ __launch_bounds__(256) void sequence_correspondence_sums_add_kernel(const double* __restrict__ partials, const uint32_t* __restrict__ tile_first,
-                                                                               uint32_t n_poses, const double* __restrict__ hists,
-                                                                               double* __restrict__ sums_out) {
+// One workgroup per (entry, pose) of the selection: the entry's own number of tiles, added in tile order (none: +0.0 throughout), then
+// the 16 histogram words of the entry's hypothesis or frame (hists: [entry][16])
+__global__ __launch_bounds__(256) void selection_correspondence_sums_add_kernel(const double* __restrict__ partials, const uint32_t* __restrict__ tile_first,
+                                                                                uint32_t n_poses, const double* __restrict__ hists,
+                                                                                double* __restrict__ sums_out) {
 #define SO_SUMS_ADD 1
-#define SO_SUMS_BATCH 2
+#define SO_SUMS_SELECTION 1
 #include "corr_sums_body.inc"
-#undef SO_SUMS_BATCH
+#undef SO_SUMS_SELECTION
 #undef SO_SUMS_ADD
 }
 
@@ -115,22 +89,13 @@ void launch_correspondence_sums(const CorrSumsIn& in, const double* d_poses, uin
   correspondence_sums_add_kernel<<<n_poses, 256, 0, s>>>(d_partials, nblk, hist, d_sums_out);
 }
 
-void launch_batch_correspondence_sums(const CorrBatchIn& in, const double* d_poses, uint32_t n_poses, const double* d_hists, double* d_partials,
-                                      double* d_sums_out, hipStream_t s) {
-  const uint32_t nblk = correspondence_workgroups(in.n);
-  if (!nblk || !in.n_sel || !n_poses || n_poses > kCorrSumsMaxPoses) return;
-  batch_correspondence_sums_kernel<<<dim3(nblk, in.n_sel), 256, 0, s>>>(in.scan, in.corr.nd, in.corr.coeff, in.corr.status, in.bs, in.n, in.hyp, d_poses,
-                                                                       n_poses, in.a2, in.variant, d_partials);
-  batch_correspondence_sums_add_kernel<<<in.n_sel * n_poses, 256, 0, s>>>(d_partials, nblk, n_poses, d_hists, d_sums_out);
-}
-
-void launch_sequence_correspondence_sums(const CorrSeqIn& in, const double* d_poses, uint32_t n_poses, const double* d_hists, double* d_partials,
-                                         double* d_sums_out, hipStream_t s) {
+void launch_selection_correspondence_sums(const CorrSelIn& in, const double* d_poses, uint32_t n_poses, const double* d_hists, double* d_partials,
+                                          double* d_sums_out, hipStream_t s) {
   if (!in.n_sel || !n_poses || n_poses > kCorrSumsMaxPoses) return;
   if (in.n_tiles)
-    sequence_correspondence_sums_kernel<<<in.n_tiles, 256, 0, s>>>(in.scan, in.corr.nd, in.corr.coeff, in.corr.status, in.entries, in.tile_first, in.n_sel,
-                                                                  d_poses, n_poses, d_partials);
-  sequence_correspondence_sums_add_kernel<<<in.n_sel * n_poses, 256, 0, s>>>(d_partials, in.tile_first, n_poses, d_hists, d_sums_out);
+    selection_correspondence_sums_kernel<<<dim3(in.max_tiles, in.n_sel), 256, 0, s>>>(in.scan, in.corr.nd, in.corr.coeff, in.corr.status, in.entries,
+                                                                                     in.tile_first, d_poses, n_poses, d_partials);
+  selection_correspondence_sums_add_kernel<<<in.n_sel * n_poses, 256, 0, s>>>(d_partials, in.tile_first, n_poses, d_hists, d_sums_out);
 }
 
 }  // namespace soicp

@@ -55,10 +55,9 @@ struct CorrGeomState {
   DevBuf snap_status, snap_idx, snap_pts;  // NeighbourSnapshot, indexed like the scan
   DevBuf records, labels, refit;
   DevBuf small;                // {n_accepted, ticket, refits not accepted, -} | obs_hist[9] + 3 | look-back words of the compaction
-  uint8_t* h_small = nullptr;  // pinned read-back of the counters and the histogram
+  PinnedBuf h_small;           // read-back of the counters and the histogram
   ~CorrGeomState() {
     for (DevBuf* b : {&snap_status, &snap_idx, &snap_pts, &records, &labels, &refit, &small}) b->release();
-    if (h_small) (void)hipHostFree(h_small);
   }
   NeighbourSnapshot snapshot() const { return NeighbourSnapshot{snap_status.as<uint8_t>(), snap_idx.as<uint32_t>(), snap_pts.as<float>()}; }
 };
@@ -108,7 +107,7 @@ int run_geometry_export(so_icp_ctx* c, const NeighbourSnapshot& snap, CorrGeomSt
   HIP_TRY(c, g.labels.reserve(n * 3 + 64));
   if (refit_out) HIP_TRY(c, g.refit.reserve(n * kCorrRefitBytes + 64));
   HIP_TRY(c, g.small.reserve(small_bytes));
-  if (!g.h_small) HIP_TRY(c, hipHostMalloc(reinterpret_cast<void**>(&g.h_small), kGeomStateOff));
+  HIP_TRY(c, g.h_small.reserve(kGeomStateOff));
   hipStream_t s = c->stream;
   HIP_TRY(c, hipMemsetAsync(g.small.p, 0, small_bytes, s));
   CorrGeomIn in;
@@ -123,10 +122,10 @@ int run_geometry_export(so_icp_ctx* c, const NeighbourSnapshot& snap, CorrGeomSt
   if (records && L.n_accepted) HIP_TRY(c, hipMemcpyAsync(records, g.records.p, (size_t)L.n_accepted * kCorrGeomRecordBytes, hipMemcpyDeviceToHost, s));
   if (refit_out && L.n_accepted) HIP_TRY(c, hipMemcpyAsync(refit_out, g.refit.p, (size_t)L.n_accepted * kCorrRefitBytes, hipMemcpyDeviceToHost, s));
   if (labels_out) HIP_TRY(c, hipMemcpyAsync(labels_out, g.labels.p, n * 3, hipMemcpyDeviceToHost, s));
-  HIP_TRY(c, hipMemcpyAsync(g.h_small, g.small.p, kGeomStateOff, hipMemcpyDeviceToHost, s));
+  HIP_TRY(c, hipMemcpyAsync(g.h_small.p, g.small.p, kGeomStateOff, hipMemcpyDeviceToHost, s));
   HIP_TRY(c, hipStreamSynchronize(s));
   uint32_t counts[4];
-  std::memcpy(counts, g.h_small, sizeof(counts));
+  std::memcpy(counts, g.h_small.p, sizeof(counts));
   if (counts[0] != L.n_accepted)
     return fail(c, SO_ICP_E_HIP, std::string(entry) + ": the snapshot holds another number of accepted points than the registration reported");
   if (counts[2]) return fail(c, SO_ICP_E_HIP, std::string(entry) + ": the refit rejected a point the registration accepted");
@@ -137,11 +136,9 @@ int run_geometry_export(so_icp_ctx* c, const NeighbourSnapshot& snap, CorrGeomSt
 struct CorrExportState {
   DevBuf records, status, residual;
   DevBuf small;              // {n_accepted, ticket, -, -} | tile sums of the cost | look-back words of the compaction
-  uint8_t* h_small = nullptr;  // pinned read-back of the counters and the tile sums
-  size_t h_small_cap = 0;
+  PinnedBuf h_small;         // read-back of the counters and the tile sums
   ~CorrExportState() {
     for (DevBuf* b : {&records, &status, &residual, &small}) b->release();
-    if (h_small) (void)hipHostFree(h_small);
   }
 };
 
@@ -153,10 +150,9 @@ CorrExportState* export_state_of(so_icp_ctx* c) {
 // so_icp_correspondence_sums' own buffers
 struct CorrSumsState {
   DevBuf poses, partials, sums;  // the pose table | one partial vector per (tile, pose) | n_poses LmSums
-  double* h_io = nullptr;        // pinned: the poses on their way in, the sums on their way out
+  PinnedBuf h_io;                // the poses on their way in, the sums on their way out
   ~CorrSumsState() {
     for (DevBuf* b : {&poses, &partials, &sums}) b->release();
-    if (h_io) (void)hipHostFree(h_io);
   }
 };
 
@@ -227,7 +223,7 @@ int so_icp_correspondence_geometry(so_icp_ctx* c, so_icp_correspondence_geometry
   const bool want_records = records && cap_records >= L.n_accepted;
   if (const int rc = run_geometry_export(c, g.snapshot(), g, "so_icp_correspondence_geometry", want_records ? records : nullptr, labels_out, nullptr)) return rc;
   info->n_accepted = L.n_accepted;
-  std::memcpy(info->obs_hist, g.h_small + kGeomHistOff, sizeof(info->obs_hist));
+  std::memcpy(info->obs_hist, g.h_small.p + kGeomHistOff, sizeof(info->obs_hist));
   if (d_records_out) *d_records_out = g.records.p;
   return SO_ICP_OK;
 }
@@ -273,12 +269,7 @@ int so_icp_correspondences(so_icp_ctx* c, const double pose[7], so_icp_correspon
   HIP_TRY(c, st.status.reserve(n + 64));
   HIP_TRY(c, st.residual.reserve(n * 4 + 64));
   HIP_TRY(c, st.small.reserve(small_bytes));
-  if (st.h_small_cap < state_off) {
-    if (st.h_small) (void)hipHostFree(st.h_small);
-    st.h_small = nullptr; st.h_small_cap = 0;
-    HIP_TRY(c, hipHostMalloc(reinterpret_cast<void**>(&st.h_small), state_off + state_off / 4 + 256));
-    st.h_small_cap = state_off + state_off / 4 + 256;
-  }
+  HIP_TRY(c, st.h_small.reserve(state_off));
   hipStream_t s = c->stream;
   uint32_t* d_counts = st.small.as<uint32_t>();
   HIP_TRY(c, hipMemsetAsync(st.small.p, 0, small_bytes, s));
@@ -296,14 +287,14 @@ int so_icp_correspondences(so_icp_ctx* c, const double pose[7], so_icp_correspon
   if (want_records && L.n_accepted) HIP_TRY(c, hipMemcpyAsync(records, st.records.p, (size_t)L.n_accepted * kCorrRecordBytes, hipMemcpyDeviceToHost, s));
   if (status_out) HIP_TRY(c, hipMemcpyAsync(status_out, st.status.p, n, hipMemcpyDeviceToHost, s));
   if (residual_out) HIP_TRY(c, hipMemcpyAsync(residual_out, st.residual.p, n * 4, hipMemcpyDeviceToHost, s));
-  HIP_TRY(c, hipMemcpyAsync(st.h_small, st.small.p, state_off, hipMemcpyDeviceToHost, s));
+  HIP_TRY(c, hipMemcpyAsync(st.h_small.p, st.small.p, state_off, hipMemcpyDeviceToHost, s));
   HIP_TRY(c, hipStreamSynchronize(s));
   uint32_t n_accepted;
-  std::memcpy(&n_accepted, st.h_small, 4);
+  std::memcpy(&n_accepted, st.h_small.p, 4);
   if (n_accepted != L.n_accepted)
     return fail(c, SO_ICP_E_HIP, "so_icp_correspondences: the status bytes hold another number of accepted points than the registration reported");
   double cost = 0;  // the tiles in tile order
-  for (size_t b = 0; b < nblk; ++b) { double t; std::memcpy(&t, st.h_small + cost_off + b * 8, 8); cost += t; }
+  for (size_t b = 0; b < nblk; ++b) { double t; std::memcpy(&t, st.h_small.p + cost_off + b * 8, 8); cost += t; }
   info->n_accepted = n_accepted; info->cost = cost;
   if (d_records_out) *d_records_out = st.records.p;
   return SO_ICP_OK;
@@ -352,23 +343,23 @@ int so_icp_correspondence_sums(so_icp_ctx* c, const double* poses, int n_poses, 
   HIP_TRY(c, hipSetDevice(c->cfg.device_id));
   CorrSumsState& st = *sums_state_of(c);
   const size_t nblk = correspondence_workgroups((uint32_t)n), pose_bytes = (size_t)n_poses * 7 * sizeof(double), sums_bytes = (size_t)n_poses * sizeof(so_icp_sums);
-  if (!st.h_io) HIP_TRY(c, hipHostMalloc(reinterpret_cast<void**>(&st.h_io), (size_t)SO_ICP_SUMS_MAX_POSES * sizeof(so_icp_sums)));
+  HIP_TRY(c, st.h_io.reserve((size_t)SO_ICP_SUMS_MAX_POSES * sizeof(so_icp_sums)));
   HIP_TRY(c, st.poses.reserve((size_t)SO_ICP_SUMS_MAX_POSES * 7 * sizeof(double)));
   HIP_TRY(c, st.sums.reserve((size_t)SO_ICP_SUMS_MAX_POSES * sizeof(so_icp_sums)));
   HIP_TRY(c, st.partials.reserve(nblk * (size_t)n_poses * kCorrSumsAcc * sizeof(double)));
   hipStream_t s = c->stream;
   // (the poses go through pinned memory: the copy is then asynchronous whatever the caller's buffer is, and the caller's is free at once)
-  std::memcpy(st.h_io, poses, pose_bytes);
-  HIP_TRY(c, hipMemcpyAsync(st.poses.p, st.h_io, pose_bytes, hipMemcpyHostToDevice, s));
+  std::memcpy(st.h_io.p, poses, pose_bytes);
+  HIP_TRY(c, hipMemcpyAsync(st.poses.p, st.h_io.p, pose_bytes, hipMemcpyHostToDevice, s));
   CorrSumsIn in;
   in.scan = c->corr_scan.as<float>();
   in.corr = CorrBuffers{c->d_nd.as<double4>(), c->d_coeff.as<double>(), c->d_status.as<uint8_t>()};
   in.n = (uint32_t)n; in.a2 = L.a2; in.variant = L.variant;
   launch_correspondence_sums(in, st.poses.as<double>(), (uint32_t)n_poses, hist, st.partials.as<double>(), st.sums.as<double>(), s);
   HIP_TRY(c, hipGetLastError());
-  HIP_TRY(c, hipMemcpyAsync(st.h_io, st.sums.p, sums_bytes, hipMemcpyDeviceToHost, s));
+  HIP_TRY(c, hipMemcpyAsync(st.h_io.p, st.sums.p, sums_bytes, hipMemcpyDeviceToHost, s));
   HIP_TRY(c, hipStreamSynchronize(s));
-  std::memcpy(sums_out, st.h_io, sums_bytes);
+  std::memcpy(sums_out, st.h_io.p, sums_bytes);
   for (int k = 0; k < n_poses; ++k)
     if (sums_out[k].count != (double)L.n_accepted)
       return fail(c, SO_ICP_E_HIP, "so_icp_correspondence_sums: the status bytes hold another number of accepted points than the registration reported");

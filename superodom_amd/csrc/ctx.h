@@ -13,8 +13,8 @@
 //                         so_icp_keep_correspondence_geometry, so_icp_correspondence_geometry: its neighbours, PCA and observability labels
 //   pose_prior.cpp        so_icp_pose_prior_from_information, so_icp_pose_prior_sums, so_icp_set_pose_prior, so_icp_set_sequence_priors,
 //                         so_icp_set_batch_priors
-//   batch_correspondences.cpp, sequence_correspondences.cpp   the correspondence sets of a batch's hypotheses / of a run's frames:
-//                         the switches, what the batch and sequence entries keep while they are on, both exports
+//   selection_correspondences.cpp   the correspondence sets of a batch's hypotheses and of a run's frames: the switches, what the
+//                         batch and sequence entries keep while they are on, the exports and sums of both over one host path
 //   multi_gpu.cpp         RCCL, in-process groups, peer exchange, shard helpers
 //   localization_sequence.cpp, feature_extraction.cpp
 #pragma once
@@ -200,43 +200,32 @@ struct so_icp_ctx {
   std::shared_ptr<void> corr_geom_state;  // so_icp_correspondence_geometry: the snapshot and the export's own buffers
   std::shared_ptr<void> corr_state;   // so_icp_correspondences: buffers of its own
   std::shared_ptr<void> corr_sums_state;  // so_icp_correspondence_sums: buffers of its own
-  // so_icp_keep_batch_correspondences (batch_correspondences.cpp): the switch, and what the last so_icp_register_batch left while it was
-  // on -- the records of ALL its hypotheses (hypothesis h at element h * bs of nd / coeff / status: the batched kernels of the group that
-  // starts at `base` write slice base + their own index, a lane copies its context's arrays into slice h), one packed copy of the scan,
-  // and per hypothesis what note_correspondences keeps of a single registration.  No other entry writes any of it.
-  bool batch_corr_keep = false;
-  struct BatchCorrKept {
+  // so_icp_keep_batch_correspondences / so_icp_keep_sequence_correspondences (selection_correspondences.cpp): the switches, and what the
+  // last so_icp_register_batch / the last so_icp_register_sequence or so_icp_localization_sequence left while its switch was on -- the
+  // records of ALL its entries (hypotheses / frames), entry k at element at[k] of nd / coeff / status, the packed scan of entry k at
+  // point scan_at[k] of `scan`, and per entry what note_correspondences keeps of a single registration.
+  //   a batch: one scan copy for all hypotheses (scan_at = 0), hypothesis h at h * bs (BatchBufs::bs of that batch): the batched kernels
+  //     of the group that starts at `base` write slice base + their own index, a lane copies its context's arrays into slice h
+  //   a run:   a scan copy per frame at the frame's records (scan_at = at; a slice has the padding of the context's own arrays and starts
+  //     at a multiple of 64: 32 + 8 + 1 + 12 = 53 bytes per point and frame): a frame started by sequence.cpp's chained path gets its
+  //     slice as the kernel arguments of its sweeps and solves, a frame that went through a per-frame entry copies the context's arrays
+  //     there (seq_corr_note_plain)
+  // Two independent sets -- both switches may be on --, each with export buffers of its own.  No other entry writes any of it.
+  struct KeptSets {
     DevBuf nd, coeff, status, scan;
-    uint32_t bs = 0;                    // element stride of a hypothesis' slice (BatchBufs::bs of that batch)
-    size_t n = 0; int n_hyp = 0;
-    bool valid = false;                 // the last batch with the switch on returned without an error
-    double a2 = 0; int variant = 0;     // EvalParams::a2 / ::variant of that batch
-    std::vector<CorrLast> rec;          // n_hyp; valid = the hypothesis ended with SO_ICP_OK
-    CorrBuffers slice(size_t h) const { return CorrBuffers{nd.as<double4>() + h * bs, coeff.as<double>() + h * bs, status.as<uint8_t>() + h * bs}; }
-    ~BatchCorrKept() { for (DevBuf* b : {&nd, &coeff, &status, &scan}) b->release(); }
-  };
-  std::unique_ptr<BatchCorrKept> batch_corr;
-  std::shared_ptr<void> batch_corr_state;  // so_icp_batch_correspondences / so_icp_batch_correspondence_sums: buffers of their own
-  // so_icp_keep_sequence_correspondences (sequence_correspondences.cpp): the switch, and what the last so_icp_register_sequence or
-  // so_icp_localization_sequence left while it was on -- the records of ALL its frames (frame k at element at[k] of nd / coeff / status:
-  // a frame started by sequence.cpp's chained path gets that slice as the kernel arguments of its sweeps and solves, a frame that went
-  // through a per-frame entry copies the context's arrays there, seq_corr_note_plain), a packed copy of every frame's scan (float
-  // 3 at[k] of `scan`) and per frame what note_correspondences keeps of a single registration.  No other entry writes any of it.
-  bool seq_corr_keep = false;
-  struct SeqCorrKept {
-    DevBuf nd, coeff, status, scan;     // total points of the run each: 32 + 8 + 1 + 12 = 53 bytes per point and frame
-    std::vector<size_t> n, at;          // per frame: its points, its first element (a slice has the padding of the context's own arrays and starts at a multiple of 64)
-    size_t total = 0;
-    bool valid = false;                 // the last run with the switch on got as far as frame 0
-    std::vector<CorrLast> rec;          // per frame; valid = the frame ended with SO_ICP_OK
-    int frames() const { return (int)n.size(); }
+    std::vector<size_t> n, at, scan_at;  // per entry: its points, its first element, the first point of its scan
+    size_t total = 0;                    // elements of nd / coeff / status
+    bool valid = false;                  // the last batch with the switch on returned without an error / the last run got as far as frame 0
+    std::vector<CorrLast> rec;           // per entry; valid = the hypothesis / the frame ended with SO_ICP_OK
+    int entries() const { return (int)n.size(); }
     CorrBuffers slice(size_t k) const { return CorrBuffers{nd.as<double4>() + at[k], coeff.as<double>() + at[k], status.as<uint8_t>() + at[k]}; }
-    float* scan_of(size_t k) const { return scan.as<float>() + 3 * at[k]; }
-    ~SeqCorrKept() { for (DevBuf* b : {&nd, &coeff, &status, &scan}) b->release(); }
+    float* scan_of(size_t k) const { return scan.as<float>() + 3 * scan_at[k]; }
+    ~KeptSets() { for (DevBuf* b : {&nd, &coeff, &status, &scan}) b->release(); }
   };
-  std::unique_ptr<SeqCorrKept> seq_corr;
+  bool batch_corr_keep = false, seq_corr_keep = false;
+  std::unique_ptr<KeptSets> batch_corr, seq_corr;
+  std::shared_ptr<void> batch_corr_state, seq_corr_state;  // the exports and sums of each set: buffers of their own
   int seq_corr_frame = -1;                // >= 0: the per-frame entry in progress is this frame of a run that keeps its sets (seq_corr_note_plain)
-  std::shared_ptr<void> seq_corr_state;   // so_icp_sequence_correspondences / so_icp_sequence_correspondence_sums: buffers of their own
   // so_icp_match(_dev): the registration in progress is one outer iteration's matching half and the evaluation at the guess (one
   // outer iteration, ZERO LM iterations, per-evaluation launches); it leaves tracker, staged scans and packing policy alone
   bool match_only = false;
@@ -540,10 +529,10 @@ int keep_scan_copy(so_icp_ctx* c, const float* d_scan, size_t n);  // the packed
 void note_correspondences(so_icp_ctx* c, const DevState& H, const double guess[7], size_t n, const EvalParams& ep);
 // the same record into `L` (so_icp_keep_batch_correspondences: one per hypothesis)
 void fill_correspondence_record(so_icp_ctx::CorrLast& L, const DevState& H, const double guess[7], size_t n, const EvalParams& ep);
-// batch_correspondences.cpp: what so_icp_register_batch does while so_icp_ctx::batch_corr_keep is on.  The set of a batch of n_hyp
+// selection_correspondences.cpp: what so_icp_register_batch does while so_icp_ctx::batch_corr_keep is on.  The set of a batch of n_hyp
 // hypotheses of n points: arrays at stride `bs` reserved, every record invalid, the packed scan copy enqueued on the context's queue
 int batch_corr_begin(so_icp_ctx* c, const float* d_scan, size_t n, int n_hyp, uint32_t bs);
-// sequence_correspondences.cpp: what the two sequence entries do while so_icp_ctx::seq_corr_keep is on.
+// what the two sequence entries do while so_icp_ctx::seq_corr_keep is on.
 inline bool keeps_sequence_correspondences(const so_icp_ctx* c) { return c->seq_corr_keep && c->cfg.world_size <= 1; }
 // The set of a run of `count` frames of n_points[k] points: every array reserved for the sum of the frames (SO_ICP_E_NOMEM when that
 // cannot be had), every record invalid.  Before the run's first launch; nothing of the set is allocated after it

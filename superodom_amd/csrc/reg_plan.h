@@ -68,19 +68,28 @@ inline uint64_t batch_record_ranges(const uint32_t* accepted, const uint8_t* val
   first_record[n_sel] = at;
   return at;
 }
-// The export's workgroups draw one global ticket each; ticket t is tile t % nblk of entry t / nblk (hypothesis-major, nblk tiles per
-// entry), so the look-back of an entry only ever waits for smaller tickets.  constexpr: batch_correspondences_kernel calls it too
-struct BatchTicket { uint32_t entry, tile; };
-constexpr BatchTicket batch_ticket(uint32_t t, uint32_t nblk) { return BatchTicket{t / nblk, t - (t / nblk) * nblk}; }
 
-// so_icp_sequence_correspondences: the same export over a selection of a run's FRAMES, whose point counts -- and so their tile counts --
-// differ; an entry may have no tile at all (an empty frame, a frame without a set).  tile_first[0 .. n_sel]: the prefix sums of the
-// entries' tile counts (tile_first[0] = 0, tile_first[n_sel] = the tickets of the launch).  Ticket t, 0 <= t < tile_first[n_sel], is tile
-// t - tile_first[e] of the entry e with tile_first[e] <= t < tile_first[e + 1]: entry-major as above, so an entry's look-back still
-// only waits for smaller tickets, and an entry without tiles gets no ticket.  A search of the prefix table (<= 11 steps for 1 024
-// entries).  constexpr: sequence_correspondences_kernel and the sums kernels call it too
-constexpr BatchTicket sequence_ticket(uint32_t t, const uint32_t* tile_first, uint32_t n_sel) {
+// The same exports over a selection of a run's FRAMES (so_icp_sequence_correspondences) share all of the above; the kernels are the same
+// too.  The entries' point counts -- and so their tile counts -- may differ, and an entry may have no tile at all (an empty scan, an
+// entry without a set).  tile_first[0 .. n_sel]: the prefix sums of the entries' tile counts (tile_first[0] = 0, tile_first[n_sel] = the
+// tickets of the launch), from the entries' points (0 for an entry without a set) and the points of a tile.  -> tile_first[n_sel]
+inline uint32_t selection_tile_table(const uint32_t* n_points, uint32_t n_sel, uint32_t tile, uint32_t* tile_first) {
+  uint32_t tiles = 0;
+  for (uint32_t k = 0; k < n_sel; ++k) { tile_first[k] = tiles; tiles += n_points[k] / tile + (n_points[k] % tile ? 1u : 0u); }
+  tile_first[n_sel] = tiles;
+  return tiles;
+}
+// The export's workgroups draw one global ticket each.  Ticket t, 0 <= t < tile_first[n_sel], is tile t - tile_first[e] of the entry e
+// with tile_first[e] <= t < tile_first[e + 1]: entry-major, so the look-back of an entry only ever waits for smaller tickets, and an
+// entry without tiles gets no ticket; for entries of nblk tiles each, tile t % nblk of entry t / nblk.  n_tiles = tile_first[n_sel].
+// The first look is at the entry t would belong to if all entries were equal -- a batch, a run of equal frames: found at once, the two
+// words read side by side --, then a search of what is left of the prefix table (<= 11 steps for 1 024 entries).  (t x n_sel < 2^31:
+// at most 2^11 tiles per entry, kMaxScanPoints, and 2^10 entries.)  constexpr: selection_correspondences_kernel calls it too
+struct BatchTicket { uint32_t entry, tile; };
+constexpr BatchTicket selection_ticket(uint32_t t, const uint32_t* tile_first, uint32_t n_sel, uint32_t n_tiles) {
   uint32_t lo = 0, hi = n_sel;  // tile_first[lo] <= t < tile_first[hi]
+  const uint32_t guess = t * n_sel / n_tiles, first = tile_first[guess], next = tile_first[guess + 1u];
+  if (first <= t) { lo = guess; if (t < next) hi = guess + 1u; } else hi = guess;
   while (hi - lo > 1u) {
     const uint32_t mid = lo + (hi - lo) / 2u;
     if (tile_first[mid] <= t) lo = mid; else hi = mid;

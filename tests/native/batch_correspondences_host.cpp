@@ -2,7 +2,8 @@
 // (tests/test_batch_correspondences_host.py drives it through ctypes; built on demand by the test, g++ -O2 -ffp-contract=off like the
 // library):
 //   reg_plan.h    batch_selection_first_bad, batch_record_ranges: the selection's check and its record ranges
-//                 batch_ticket: which (entry, tile) a workgroup of the export works on, from the ticket it drew
+//                 selection_ticket: which (entry, tile) a workgroup of the export works on, from the ticket it drew -- for a batch
+//                 over the uniform prefix table tile_first[k] = k * nblk
 #include "reg_plan.h"
 
 using namespace soicp::host;
@@ -15,8 +16,8 @@ int bc_selection_first_bad(const int32_t* hyp, int n_sel, int n_hyp) { return ba
 uint64_t bc_record_ranges(const uint32_t* accepted, const uint8_t* valid, const int32_t* hyp, int n_sel, uint64_t* first_record) {
   return batch_record_ranges(accepted, valid, hyp, n_sel, first_record);
 }
-void bc_ticket(uint32_t t, uint32_t nblk, uint32_t out[2]) {
-  const BatchTicket b = batch_ticket(t, nblk);
+void bc_ticket(uint32_t t, const uint32_t* tile_first, uint32_t n_sel, uint32_t out[2]) {
+  const BatchTicket b = selection_ticket(t, tile_first, n_sel, tile_first[n_sel]);
   out[0] = b.entry; out[1] = b.tile;
 }
 

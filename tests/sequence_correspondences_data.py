@@ -61,7 +61,7 @@ def poses_near(pose, n_poses, seed):
 
 
 def tile_first(ns):
-    """the prefix table of the entries' tile counts (reg_plan.h: sequence_ticket)"""
+    """the prefix table of the entries' tile counts (reg_plan.h: selection_tile_table)"""
     return np.concatenate([[0], np.cumsum([(n + TILE - 1) // TILE for n in ns])]).astype(np.uint32)
 
 

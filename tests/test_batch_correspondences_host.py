@@ -31,7 +31,7 @@ def native():
     L.bc_selection_first_bad.argtypes = [i32p, C.c_int, C.c_int]
     L.bc_record_ranges.argtypes = [C.POINTER(C.c_uint32), C.POINTER(C.c_uint8), i32p, C.c_int, C.POINTER(C.c_uint64)]
     L.bc_record_ranges.restype = C.c_uint64
-    L.bc_ticket.argtypes = [C.c_uint32, C.c_uint32, C.POINTER(C.c_uint32)]; L.bc_ticket.restype = None
+    L.bc_ticket.argtypes = [C.c_uint32, C.POINTER(C.c_uint32), C.c_uint32, C.POINTER(C.c_uint32)]; L.bc_ticket.restype = None
     return L
 
 
@@ -143,12 +143,14 @@ def test_selection_check(native):
 
 @pytest.mark.parametrize("nblk, n_sel", [(1, 1), (1, 5), (2, 3), (4, 3), (5, 7), (128, 2)])
 def test_every_ticket_of_small_grids(native, nblk, n_sel):
-    """hypothesis-major: the tickets of entry k are k * nblk .. (k + 1) * nblk - 1, tile after tile -- so a workgroup's look-back (tiles
-    below its own, same entry) only ever names smaller tickets, and every (entry, tile) is worked on exactly once"""
+    """hypothesis-major: over a batch's prefix table, tile_first[k] = k * nblk, the tickets of entry k are k * nblk .. (k + 1) * nblk - 1,
+    tile after tile -- so a workgroup's look-back (tiles below its own, same entry) only ever names smaller tickets, and every
+    (entry, tile) is worked on exactly once"""
     seen = []
     out = (C.c_uint32 * 2)()
+    tile_first = (C.c_uint32 * (n_sel + 1))(*[k * nblk for k in range(n_sel + 1)])
     for t in range(nblk * n_sel):
-        native.bc_ticket(t, nblk, out)
+        native.bc_ticket(t, tile_first, n_sel, out)
         k, tile = out[0], out[1]
         assert (k, tile) == (t // nblk, t % nblk) and k < n_sel and tile < nblk
         assert all(k * nblk + below < t for below in range(tile)), "a predecessor of the chain with a larger ticket"
@@ -159,7 +161,7 @@ def test_every_ticket_of_small_grids(native, nblk, n_sel):
 def test_reg_plan_still_needs_no_device_headers():
     text = open(os.path.join(HDR, "reg_plan.h")).read()
     assert sorted(re.findall(r'#include\s+[<"]([^>"]+)[>"]', text)) == ["algorithm", "cstddef", "cstdint", "so_math.h"]
-    assert "batch_record_ranges" in text and "batch_ticket" in text
+    assert "batch_record_ranges" in text and "selection_ticket" in text
 
 
 def test_the_cases():

@@ -164,7 +164,7 @@ def test_status_offsets_and_record_ranges(native):
 def test_reg_plan_still_needs_no_device_headers():
     text = open(os.path.join(HDR, "reg_plan.h")).read()
     assert sorted(re.findall(r'#include\s+[<"]([^>"]+)[>"]', text)) == ["algorithm", "cstddef", "cstdint", "so_math.h"]
-    assert "sequence_ticket" in text and "sequence_status_ranges" in text
+    assert "selection_ticket" in text and "sequence_status_ranges" in text
 
 
 def test_the_runs():
