@@ -144,5 +144,10 @@ inline bool cube_stable(const int origin[3], const int dims[3], const double t[3
   }
   return true;
 }
+// The pose under which the scan BEHIND registration k is binned ahead and its window placed while k still runs (so_icp_register_sequence):
+// k's exact guess -- known to the host since k - 1 was collected -- moved on by the next delta.  It misses the guess the device will
+// form by the correction registration k makes, one frame's worth.  (Composed from the PREDICTION of k's guess instead, the corrections
+// of all frames since the chain began add up: metres and tens of degrees after a few hundred frames.)
+inline void predicted_guess(const double exact_guess_k[7], const double delta_next[7], double pred[7]) { pose_compose(exact_guess_k, delta_next, pred); }
 
 }  // namespace soicp::host

@@ -162,12 +162,19 @@ struct SequenceCall {
     SeqRun& r = runs[(size_t)k];
     return (r.slot && r.n) ? copy_in(r, scans[k]) : SO_ICP_OK;
   }
-  // the scan that will start the NEXT call: on its way to HBM and binned beside this call's last registration `last`
-  void stage_announced(const SeqRun& last) {
+  // the host's prediction of the guess of the scan BEHIND registration k, formed while k runs (k - 1 has been collected on every path
+  // by then: chained, after a chain break, after run_plain): anchored on k's exact guess, never on the prediction k was started under
+  void predict_next(int k, const double delta_next[7], double pred[7]) const {
+    double g[7];
+    exact_guess(k, g);
+    predicted_guess(g, delta_next, pred);
+  }
+  // the scan that will start the NEXT call: on its way to HBM and binned beside this call's last registration
+  void stage_announced() {
     so_icp_ctx::SeqNext& nx = c->seq_next;
     nx.announced = false;
     double pred[7];
-    pose_compose(last.guess, nx.delta, pred);
+    predict_next(count - 1, nx.delta, pred);
     nx.scan = nx.next_scan; nx.n = nx.next_n;
     nx.slot = (slot_base + count) % so_icp_ctx::kStageSlots;
     SeqRun rn;
@@ -363,14 +370,18 @@ struct SequenceCall {
       // registration enqueued behind this one's launches
       if (k + 1 < count) {
         double pred[7];
-        pose_compose(r.guess, delta(k + 1), pred);  // (this registration will move r.guess by centimetres: good enough to bin under and to place the window)
+        // exact_guess(k) o delta_(k+1), NOT r.guess o delta_(k+1): r.guess of a chained registration is itself a prediction, and a chain of
+        // predictions gathers the correction of every frame since the call began (metres after a few hundred frames: chunks that
+        // straddle cells, then a window refused by cube_stable).  This registration moves its exact guess by centimetres: good enough
+        // to bin under and to place the window, and no worse at frame 1 000 than at frame 1
+        predict_next(k, delta(k + 1), pred);
         if ((rc = stage(runs[(size_t)k + 1], scans[k + 1], pred, false))) return rc;
         if ((rc = keep_scan(k + 1))) return rc;
         if ((rc = copy_ahead(k + 2))) return rc;
         next_started = start(k + 1, pred, true, &rc);
         if (rc) return rc;
       } else if (c->seq_next.announced && !scans_on_device) {
-        stage_announced(r);
+        stage_announced();
       }
       // this registration's reports
       int last = 0;

@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """so_icp_register_sequence on the configuration of record (131 072-point scans vs the 2 M-point map), or on the stock operating point
 (--stock: pre-filtered resident clouds, max_surface_features 2000): registrations per second of one call over --count scans, beside the loop of
-single calls.  usage (GPU box): python tools/seq_rate.py [--count 48] [--stock] [--reps 3]; under rocprofv3: tools/seq_timeline.sh"""
+single calls.  usage (GPU box): python tools/seq_rate.py [--count 48] [--stock] [--reps 3] [--frame-blocks]; under rocprofv3: tools/seq_timeline.sh"""
 import argparse, os, sys, time
 import numpy as np
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -10,6 +10,7 @@ from superodom_amd import binding, synth  # noqa: E402
 
 ap = argparse.ArgumentParser(); ap.add_argument("--count", type=int, default=48); ap.add_argument("--stock", action="store_true")
 ap.add_argument("--reps", type=int, default=3); ap.add_argument("--no-single", action="store_true", help="skip the loop of single calls (kernel timelines of the sequence alone)")
+ap.add_argument("--frame-blocks", action="store_true", help="per call: mean time_elapsed_ms of every block of 100 frames, and the frames not flagged CHAINED")
 a = ap.parse_args()
 sc = synth.Scene("os1_128_2m")
 S = 4
@@ -44,6 +45,10 @@ for rep in range(a.reps):
     tm = cx.timing()
     print("[sequence%s] %d registrations in one call: %.4f ms each (%.0f /s), chained %d, outer %.2f, chain breaks so far %d" % (
         " stock" if a.stock else "", K, 1e3 * t, 1 / t, sum(1 for s_ in st if s_.flags & binding.FLAG_CHAINED), sum(s_.n_iterations for s_ in st) / K, tm.seq_chain_breaks))
+    if a.frame_blocks:  # (a frame's time runs from the moment the host turns to it to its collection: a long call's slow stretches show here)
+        ms = [s_.time_elapsed_ms for s_ in st]
+        print("  ms per frame, blocks of 100:", " ".join("%.3f" % (sum(ms[b:b + 100]) / len(ms[b:b + 100])) for b in range(0, K, 100)))
+        print("  frames not flagged CHAINED:", [k for k, s_ in enumerate(st) if not s_.flags & binding.FLAG_CHAINED])
 # the loop of single calls on the same scans (resident / staged entry of the bench)
 stk = [binding.Stats() for _ in range(K)]; pk = [np.zeros(7) for _ in range(K)]
 if a.stock and not a.no_single:
