@@ -912,8 +912,8 @@ int so_icp_set_batch_priors(so_icp_ctx *ctx, int n_hyp, const so_icp_pose_prior 
  * kernels -- and the concurrent registrations of SOICP_BATCH_MODE=lanes, of an empty scan or of a degraded context each copy theirs
  * there on their own queue), ONE packed copy of the scan (12 n bytes, device to device, in front of the batch's first launch) and per
  * hypothesis what a single registration keeps: the accepted count, the loss, outer_iteration, pose_fit, pose_eval, both histograms,
- * and valid = (rc_out[h] == SO_ICP_OK).  The set is replaced by the next so_icp_register_batch (which leaves none if it fails); nothing
- * else invalidates it: not a single registration, a match, a map insert, a pre-filter or so_icp_set_resolution.  Turning the switch
+ * and valid = (rc_out[h] == SO_ICP_OK).  The set is replaced by the next so_icp_register_batch or so_icp_match_batch (which leaves none if it
+ * fails); nothing else invalidates it: not a single registration, a single match, a map insert, a pre-filter or so_icp_set_resolution.  Turning the switch
  * off drops the set and frees its memory.  Independent of so_icp_keep_correspondences: a batch still ends "the last registration's"
  * set.  world_size > 1: SO_ICP_E_UNSUPPORTED; a host-only context: SO_ICP_E_HIP. */
 int so_icp_keep_batch_correspondences(so_icp_ctx *ctx, int on);
@@ -952,6 +952,40 @@ int so_icp_batch_correspondences(so_icp_ctx *ctx, const int32_t *hyp /* n_sel, N
 int so_icp_batch_correspondence_sums(so_icp_ctx *ctx, const int32_t *hyp, int n_sel,
                                      const double *poses /* n_sel x n_poses x 7 */, int n_poses /* 1 .. SO_ICP_SUMS_MAX_POSES */,
                                      so_icp_sums *sums_out /* n_sel x n_poses */);
+
+/* -------- SEAM C for a BATCH: so_icp_match for ONE scan at n_poses poses in one call -- a caller that solves on the host (a
+ * multi-hypothesis iterated EKF, a back end with factors of its own per hypothesis) or only scores poses (cost, accepted count, normal
+ * equations and observability histogram over a grid of perturbations: an alignment-risk estimate) without n_poses single matches, each
+ * with its own binning, sweep, evaluation and synchronisation, and without n_poses registrations whose solves it throws away.
+ * Scan arguments, return value and rc_out are so_icp_register_batch's: d_scan_xyz != NULL takes a resident scan, else scan_xyz is
+ * uploaded once; the call returns the number of poses that ended SO_ICP_OK, or a negative error.
+ * stats[h] is, to the bit, what so_icp_match_dev reports for the same scan at poses[h] on a context of its own (same map, plane_res,
+ * max_surface_features and Tukey variant): n_iterations = 1, the whole of iterations[0] (counts, both histograms, initial_cost ==
+ * final_cost, pose_after = poses[h], zeros in the LM fields, so_icp_match's termination), JtJ, Jtr, pos_in_localmap and
+ * laser_cloud_surf_from_map_num.  Exempt: time_elapsed_ms (the wall time of the hypothesis' group of up to 64) and flags -- the batch
+ * sets SO_ICP_FLAG_HOST_MAP and SO_ICP_FLAG_COPY_READBACK where they hold, as so_icp_register_batch does, and none of the bits that
+ * describe a single registration's schedule (SO_ICP_FLAG_PER_EVAL_LAUNCHES, _QUERY_WAVES, _BINNED_AHEAD, _STAGED_SCAN).
+ * The map window is shifted ONCE, for poses[0], as in so_icp_register_batch: the bit-for-bit statement holds for poses that lie in the
+ * map block of poses[0] (a single match at a pose of another block would have rolled the window for it).
+ * The entry needs no keep switch.  With so_icp_keep_batch_correspondences on it leaves the batch's kept set -- every pose's slice, one
+ * scan copy, per pose outer_iteration 0 and pose_fit = pose_eval = poses[h] -- and so_icp_batch_correspondences /
+ * so_icp_batch_correspondence_sums work on it unchanged: entry h equals what so_icp_correspondences / so_icp_correspondence_sums give
+ * after the single match.  With the switch off the stats are the same bytes and a set an earlier batch left is dropped.  The single
+ * registration's set (so_icp_keep_correspondences) is not touched.
+ * Left alone: everything so_icp_match leaves alone (the previous observability histogram, startup_count, the tracker's last pose and
+ * time, the map's contents, announced and staged scans, the chain of so_icp_register_sequence, so_icp_timing::registrations), and the
+ * statistics by which later so_icp_register_batch calls chain their rounds.
+ * One launch fits and evaluates every (pose, point) of a group (3 binning launches, 1 sweep, that launch, one read-back); no workgroup
+ * of it waits for another, so SOICP_BATCH_MODE, SOICP_BATCH_CHAIN and the fall-backs of so_icp_register_batch (one workgroup per compute
+ * unit, lanes) do not apply to it: any n_poses goes through in groups of 64.
+ * Refusals: a pending prior of any kind (so_icp_set_pose_prior, _sequence_priors, _batch_priors): SO_ICP_E_UNSUPPORTED, and the prior
+ * stays pending; world_size > 1: SO_ICP_E_UNSUPPORTED; a host-only context: SO_ICP_E_HIP; NULL poses or stats, n_poses < 0, n > 0
+ * without a scan: SO_ICP_E_INVALID; n of 2^21 or more: so_icp_register_batch's refusal.  n_poses == 0 returns 0.  A 5x5x5 surf count
+ * <= 50: every rc_out[h] = SO_ICP_NOT_ENOUGH_MAP_FEATURES and the call returns 0.  n == 0: every pose reports what so_icp_match
+ * reports for an empty scan. */
+int so_icp_match_batch(so_icp_ctx *ctx, const float *scan_xyz, const void *d_scan_xyz, size_t n, size_t stride_bytes,
+                       const double *poses /* n_poses x 7 */, int n_poses,
+                       so_icp_stats *stats /* n_poses */, int32_t *rc_out /* n_poses, nullable */);
 
 /* -------- the correspondence sets of a RUN's frames: so_icp_register_sequence and so_icp_localization_sequence are the entries for a
  * backlog of feature clouds or a log replayed at full speed, and the callers of the export -- a factor-graph back end that wants

@@ -280,7 +280,7 @@ EXPORTED = ["so_icp_default_config", "so_icp_create", "so_icp_destroy", "so_icp_
             "so_icp_registered_scan", "so_icp_registered_scan_dev", "so_icp_extract_features_untimed", "so_icp_extract_features_untimed_dev",
             "so_icp_debug_lm_script", "so_icp_set_cloud_intensity", "so_icp_prefilter_intensity",
             "so_icp_keep_correspondences", "so_icp_correspondences",
-            "so_icp_match", "so_icp_match_dev", "so_icp_correspondence_sums",
+            "so_icp_match", "so_icp_match_dev", "so_icp_match_batch", "so_icp_correspondence_sums",
             "so_icp_keep_correspondence_geometry", "so_icp_correspondence_geometry", "so_icp_debug_correspondence_refit",
             "so_icp_pose_prior_from_information", "so_icp_pose_prior_sums", "so_icp_set_pose_prior", "so_icp_set_sequence_priors",
             "so_icp_set_batch_priors",
@@ -393,6 +393,7 @@ def load():
     L.so_icp_correspondences.argtypes = [vp, f64p, vp, C.c_size_t, u8p, f32p, C.c_size_t, C.POINTER(vp), C.POINTER(CorrespondenceInfo)]
     L.so_icp_match.argtypes = [vp, f32p, C.c_size_t, C.c_size_t, f64p, C.POINTER(Stats)]
     L.so_icp_match_dev.argtypes = [vp, vp, C.c_size_t, f64p, C.POINTER(Stats)]
+    L.so_icp_match_batch.argtypes = [vp, f32p, vp, C.c_size_t, C.c_size_t, f64p, C.c_int, C.POINTER(Stats), i32p]
     L.so_icp_correspondence_sums.argtypes = [vp, f64p, C.c_int, C.POINTER(Sums)]
     L.so_icp_keep_correspondence_geometry.argtypes = [vp, C.c_int]
     L.so_icp_correspondence_geometry.argtypes = [vp, vp, C.c_size_t, u8p, C.c_size_t, C.POINTER(vp), C.POINTER(CorrespondenceGeometryInfo)]
@@ -705,6 +706,20 @@ class LidarSlamGpu:
         pose = np.ascontiguousarray(pose, dtype=np.float64); st = Stats()
         rc = self._check(self.L.so_icp_match_dev(self.h, d_scan, n, _p(pose, C.c_double), C.byref(st)))
         return rc, st
+
+    def match_batch(self, scan, poses, d_scan=None, n=None):
+        """so_icp_match_batch: the same scan matched at many poses in one call, no solve.  scan: host array, or None with (d_scan, n) from
+        upload_scan.  Returns (number of poses that ended SO_ICP_OK, rc[n_poses], stats list); with keep_batch_correspondences(True)
+        the call leaves the batch's kept set (batch_correspondences / batch_correspondence_sums)."""
+        poses = np.ascontiguousarray(poses, dtype=np.float64).reshape(-1, 7)
+        B = len(poses)
+        rcs = np.zeros(B, np.int32); st = (Stats * max(B, 1))()
+        if d_scan is None:
+            scan = _f32(scan).reshape(-1, 3)
+            ok = self._check(self.L.so_icp_match_batch(self.h, _p(scan, C.c_float), None, len(scan), 12, _p(poses, C.c_double), B, st, _p(rcs, C.c_int32)))
+        else:
+            ok = self._check(self.L.so_icp_match_batch(self.h, None, d_scan, n, 12, _p(poses, C.c_double), B, st, _p(rcs, C.c_int32)))
+        return ok, rcs, list(st)[:B]
 
     def set_pose_prior(self, prior):
         """so_icp_set_pose_prior: `prior` (a PosePrior) goes into the next register / register_dev / localization(_dev) call and is consumed

@@ -9,6 +9,9 @@
 // read by solve_kernel_batch_prior, which a round launches only where a hypothesis of its list carries one (reg_plan.h).
 // so_icp_keep_batch_correspondences: while the switch is on, a group's kernels write their records into the slices of the kept set
 // (other kernel arguments, the same kernels) and a lane copies its context's records there; selection_correspondences.cpp exports them.
+// so_icp_match_batch: the same scan MATCHED at many poses, nothing solved -- a group's set-up and round 0's sweep, then ONE launch that fits
+// and evaluates every (pose, point) (kernels.hip: match_batch_kernel); no workgroup of it waits for another, so none of the residency
+// rules below apply to it.  It leaves the batch's kept set like a batch does.
 #include <hip/hip_runtime_api.h>
 
 #include <algorithm>
@@ -75,24 +78,40 @@ int batch_priors_reserve(so_icp_ctx* c, uint32_t B) {
 
 // `priors`: the priors of the whole batch (so_icp_set_batch_priors; nullptr: none), of which hypothesis h of this group is element base + h
 // `keep`: the set this batch leaves (so_icp_keep_batch_correspondences; nullptr: the switch is off), hypothesis h of this group is its base + h
-int register_batch_group(so_icp_ctx* c, const float* d_scan, size_t n, const double* poses_in, int B, double* poses_out, so_icp_stats* stats,
-                         int32_t* hyp_rc, const int pos[3], int count_5x5, const PriorSet* priors, int base, so_icp_ctx::KeptSets* keep) {
-  const auto t_begin = std::chrono::steady_clock::now();
-  std::vector<so_icp_stats> local;
-  if (!stats) { local.resize((size_t)B); stats = local.data(); }
+// ---- What a group of so_icp_register_batch and a group of so_icp_match_batch share: the stats headers and the refusals that need no
+// launch (batch_group_header), then the group's buffers, prologue arguments, active list, kernel parameters, BatchView, kept-set slice
+// and the three binning launches (batch_group_begin).  Behind them the queue holds every hypothesis' prologue and binned scan.
+struct BatchGroup {
+  std::vector<so_icp_stats> local;  // (the caller passed no stats)
+  so_icp_stats* stats = nullptr;
+  MatchParams mp; EvalParams ep;    // of the group's sweeps and passes
+  BatchView bv{nullptr, nullptr, 0, 0, 0, 0, 0, 0};
+  DevState* ds = nullptr;
+  CorrBuffers corr{nullptr, nullptr, nullptr};  // (the kernels add the hypothesis' index in the group x bs to these: with the switch on, slice base + h of the kept set)
+  uint32_t v_grid = 0;              // workgroups of the single-registration fit pass a hypothesis' workgroups stand in for
+};
+// -> 1: go on to batch_group_begin; 0: the group is over (hyp_rc says how); < 0: the call is refused
+int batch_group_header(so_icp_ctx* c, size_t n, const double* poses_in, int B, double* poses_out /* nullptr: the entry returns no poses */,
+                       so_icp_stats* stats, int32_t* hyp_rc, const int pos[3], int count_5x5, BatchGroup& g) {
+  if (!stats) { g.local.resize((size_t)B); stats = g.local.data(); }
+  g.stats = stats;
   for (int h = 0; h < B; ++h) {
     so_icp_stats* st = stats + h;
     std::memset(st, 0, sizeof(*st));
     st->flags = (!c->dmap ? SO_ICP_FLAG_HOST_MAP : 0u) | (c->direct_readback ? 0u : SO_ICP_FLAG_COPY_READBACK);
-    std::memcpy(poses_out + 7 * (size_t)h, poses_in + 7 * (size_t)h, 7 * sizeof(double));
+    if (poses_out) std::memcpy(poses_out + 7 * (size_t)h, poses_in + 7 * (size_t)h, 7 * sizeof(double));
     fill_stats_header(c, st, pos, count_5x5, n);
     hyp_rc[h] = SO_ICP_OK;
   }
-  if (!(count_5x5 > 50)) { for (int h = 0; h < B; ++h) hyp_rc[h] = SO_ICP_NOT_ENOUGH_MAP_FEATURES; return SO_ICP_OK; }  // LidarSlam.cpp:113-116
+  if (!(count_5x5 > 50)) { for (int h = 0; h < B; ++h) hyp_rc[h] = SO_ICP_NOT_ENOUGH_MAP_FEATURES; return 0; }  // LidarSlam.cpp:113-116
   if (n >= kMaxScanPoints) return refuse_scan_size(c);
-  const int max_outer = outer_limit(c->cfg.max_iterations), lm_max = lm_limit(c->cfg.lm_max_iterations);
+  return 1;
+}
+// `keep`: the set this call leaves (so_icp_keep_batch_correspondences; nullptr: the switch is off), hypothesis h of this group is its base + h
+int batch_group_begin(so_icp_ctx* c, const char* entry, const float* d_scan, size_t n, const double* poses_in, int B, int max_outer, int lm_max,
+                      int base, so_icp_ctx::KeptSets* keep, BatchGroup& g) {
   const uint32_t lg = bin_table_log2(n);
-  int rc = batch_reserve(c, (uint32_t)B, n, lg);
+  const int rc = batch_reserve(c, (uint32_t)B, n, lg);
   if (rc) return rc;
   so_icp_ctx::BatchBufs& b = c->batch;
   hipStream_t s = c->stream;
@@ -103,6 +122,58 @@ int register_batch_group(so_icp_ctx* c, const float* d_scan, size_t n, const dou
   }
   HIP_TRY(c, hipMemcpyAsync(b.begin.p, b.h_begin, (size_t)B * sizeof(RegBeginArgs), hipMemcpyHostToDevice, s));
   HIP_TRY(c, hipMemcpyAsync(b.active.p, b.h_active, (size_t)B * 4, hipMemcpyHostToDevice, s));
+  const float plane_res_now = map_plane_res(c);
+  g.mp = match_params(plane_res_now, c->ablate);
+  g.mp.chunk_cap = b.bs;
+  g.mp.hring[0] = g.mp.hring[1] = nullptr; g.mp.seq_base = 0; g.mp.publish_prev = 0;
+  g.mp.packed_leftover = &b.states.as<DevState>()->packed_leftover;
+  g.ep = eval_params(plane_res_now, c->cfg.tukey_variant, c->ablate);
+  g.ep.n_queries = (uint32_t)n; g.ep.q_stride = 3;
+  g.ep.timeout_ticks = 20000000ull;  // 200 ms: a pass of one hypothesis on a few workgroups lasts up to a millisecond
+  g.v_grid = solve_grid((uint32_t)n, (uint32_t)c->n_cus);
+  g.bv = BatchView{b.active.as<uint32_t>(), b.begin.as<RegBeginArgs>(), b.bs, (uint32_t)((size_t)1 << lg),
+                   (uint32_t)((size_t)kFitBlocksMax * kRecordChunksMax * 2), (uint32_t)(kSyncBytes / 4), 1u, g.v_grid};
+  const BinTable bt{b.bin_key.as<uint32_t>(), b.bin_cnt.as<uint32_t>(), b.bin_off.as<uint32_t>(), lg};
+  g.ds = b.states.as<DevState>();
+  // (hypothesis h of the set lies at h * its stride: the last slice of this group is where the kernels will write it)
+  if (keep && keep->at[(size_t)(base + B - 1)] != (size_t)(base + B - 1) * b.bs) return fail(c, SO_ICP_E_HIP, std::string(entry) + ": the kept correspondence arrays have another stride than the batch's");
+  g.corr = keep ? keep->slice((size_t)base) : CorrBuffers{b.nd.as<double4>(), b.coeff.as<double>(), b.status.as<uint8_t>()};
+  if (!n) return SO_ICP_OK;  // (so_icp_match_batch on an empty scan: nothing to bin, its one launch carries the prologue)
+  // ---- binning of the scan under every hypothesis' pose: (queries x hypotheses) in three launches
+  b.tables_clean = false;
+  const double zero_pose[7] = {0, 0, 0, 0, 0, 0, 1};
+  launch_scan_keys(d_scan, (uint32_t)n, g.ds, zero_pose, max_outer, lm_max, b.hist.as<int32_t>(), c->view, c->cfg.max_surface_features, 0, 1,
+                   b.qslot.as<uint32_t>(), b.qrank.as<uint32_t>(), g.corr.status, bt, s, false, &g.bv, (uint32_t)B);
+  launch_bin_offsets(bt, b.chunks.as<uint32_t>(), b.bs, g.ds, s, &g.bv, (uint32_t)B);
+  b.tables_clean = true;
+  launch_bin_place(bt, d_scan, (uint32_t)n, b.qslot.as<uint32_t>(), b.qrank.as<uint32_t>(), b.binned.as<float4>(), s, nullptr, &g.bv, (uint32_t)B);
+  HIP_TRY(c, hipGetLastError());
+  return SO_ICP_OK;
+}
+
+// `priors`: the priors of the whole batch (so_icp_set_batch_priors; nullptr: none), of which hypothesis h of this group is element base + h
+// `keep`: as batch_group_begin's
+int register_batch_group(so_icp_ctx* c, const float* d_scan, size_t n, const double* poses_in, int B, double* poses_out, so_icp_stats* stats_io,
+                         int32_t* hyp_rc, const int pos[3], int count_5x5, const PriorSet* priors, int base, so_icp_ctx::KeptSets* keep) {
+  const auto t_begin = std::chrono::steady_clock::now();
+  BatchGroup g;
+  int rc = batch_group_header(c, n, poses_in, B, poses_out, stats_io, hyp_rc, pos, count_5x5, g);
+  if (rc <= 0) return rc;
+  so_icp_stats* const stats = g.stats;
+  const int max_outer = outer_limit(c->cfg.max_iterations), lm_max = lm_limit(c->cfg.lm_max_iterations);
+  const uint32_t resident_plain = solve_batch_resident_blocks((uint32_t)c->n_cus, c->batch_degrade >= 1 ? 1 : 0);
+  // (a round whose list holds a prior launches solve_kernel_batch_prior: ITS occupancy then says how many workgroups are resident together)
+  const uint32_t resident_prior = priors ? solve_batch_resident_blocks((uint32_t)c->n_cus, c->batch_degrade >= 1 ? 1 : 0, true) : resident_plain;
+  const uint32_t resident = std::min(resident_plain, resident_prior);
+  if (resident < (uint32_t)B) {  // (the driver below sizes its groups by the resident workgroups; this is the second line of defence)
+    c->err = "so_icp_register_batch: fewer resident solve workgroups (" + std::to_string(resident) + ") than hypotheses in the group (" + std::to_string(B) + ")";
+    return kRetryWithoutPersistentSolve;  // degrade (fewer workgroups per hypothesis is not possible: one each) -> concurrent sequential registrations
+  }
+  if ((rc = batch_group_begin(c, "so_icp_register_batch", d_scan, n, poses_in, B, max_outer, lm_max, base, keep, g))) return rc;
+  so_icp_ctx::BatchBufs& b = c->batch;
+  hipStream_t s = c->stream;
+  const MatchParams& mp = g.mp; const EvalParams& ep = g.ep; BatchView& bv = g.bv; DevState* const ds = g.ds; const CorrBuffers corr = g.corr;
+  const uint32_t v_grid = g.v_grid;
   // the hypotheses' priors: one block each, T_meas filled with the hypothesis' guess where its mode says so (the host knows every
   // start pose of a batch); in the queue in front of round 0, so the solve launches read it with plain loads
   std::vector<uint8_t> prior_modes;  // of this group; empty: no hypothesis of it carries a prior
@@ -127,40 +198,6 @@ int register_batch_group(so_icp_ctx* c, const float* d_scan, size_t n, const dou
     }
     HIP_TRY(c, hipMemcpyAsync(b.priors.p, b.h_priors, (size_t)B * kBatchPriorStride * sizeof(double), hipMemcpyHostToDevice, s));
   }
-  const float plane_res_now = map_plane_res(c);
-  MatchParams mp = match_params(plane_res_now, c->ablate);
-  mp.chunk_cap = b.bs;
-  mp.hring[0] = mp.hring[1] = nullptr; mp.seq_base = 0; mp.publish_prev = 0;
-  mp.packed_leftover = &b.states.as<DevState>()->packed_leftover;
-  EvalParams ep = eval_params(plane_res_now, c->cfg.tukey_variant, c->ablate);
-  ep.n_queries = (uint32_t)n; ep.q_stride = 3;
-  ep.timeout_ticks = 20000000ull;  // 200 ms: a pass of one hypothesis on a few workgroups lasts up to a millisecond
-  const uint32_t v_grid = solve_grid((uint32_t)n, (uint32_t)c->n_cus);
-  const uint32_t resident_plain = solve_batch_resident_blocks((uint32_t)c->n_cus, c->batch_degrade >= 1 ? 1 : 0);
-  // (a round whose list holds a prior launches solve_kernel_batch_prior: ITS occupancy then says how many workgroups are resident together)
-  const uint32_t resident_prior = priors ? solve_batch_resident_blocks((uint32_t)c->n_cus, c->batch_degrade >= 1 ? 1 : 0, true) : resident_plain;
-  const uint32_t resident = std::min(resident_plain, resident_prior);
-  if (resident < (uint32_t)B) {  // (the driver below sizes its groups by the resident workgroups; this is the second line of defence)
-    c->err = "so_icp_register_batch: fewer resident solve workgroups (" + std::to_string(resident) + ") than hypotheses in the group (" + std::to_string(B) + ")";
-    return kRetryWithoutPersistentSolve;  // degrade (fewer workgroups per hypothesis is not possible: one each) -> concurrent sequential registrations
-  }
-  BatchView bv{b.active.as<uint32_t>(), b.begin.as<RegBeginArgs>(), b.bs, (uint32_t)((size_t)1 << lg),
-               (uint32_t)((size_t)kFitBlocksMax * kRecordChunksMax * 2), (uint32_t)(kSyncBytes / 4), 1u, v_grid};
-  const BinTable bt{b.bin_key.as<uint32_t>(), b.bin_cnt.as<uint32_t>(), b.bin_off.as<uint32_t>(), lg};
-  DevState* ds = b.states.as<DevState>();
-  // (hypothesis h of the set lies at h * its stride: the last slice of this group is where the kernels will write it)
-  if (keep && keep->at[(size_t)(base + B - 1)] != (size_t)(base + B - 1) * b.bs) return fail(c, SO_ICP_E_HIP, "so_icp_register_batch: the kept correspondence arrays have another stride than the batch's");
-  // (the kernels add the hypothesis' index in the group x bs to these: with the switch on, slice base + h of the kept set)
-  const CorrBuffers corr = keep ? keep->slice((size_t)base) : CorrBuffers{b.nd.as<double4>(), b.coeff.as<double>(), b.status.as<uint8_t>()};
-  // ---- binning of the scan under every hypothesis' pose: (queries x hypotheses) in three launches
-  b.tables_clean = false;
-  const double zero_pose[7] = {0, 0, 0, 0, 0, 0, 1};
-  launch_scan_keys(d_scan, (uint32_t)n, ds, zero_pose, max_outer, lm_max, b.hist.as<int32_t>(), c->view, c->cfg.max_surface_features, 0, 1,
-                   b.qslot.as<uint32_t>(), b.qrank.as<uint32_t>(), corr.status, bt, s, false, &bv, (uint32_t)B);
-  launch_bin_offsets(bt, b.chunks.as<uint32_t>(), b.bs, ds, s, &bv, (uint32_t)B);
-  b.tables_clean = true;
-  launch_bin_place(bt, d_scan, (uint32_t)n, b.qslot.as<uint32_t>(), b.qrank.as<uint32_t>(), b.binned.as<float4>(), s, nullptr, &bv, (uint32_t)B);
-  HIP_TRY(c, hipGetLastError());
   std::vector<uint32_t> act((size_t)B);
   for (int h = 0; h < B; ++h) act[(size_t)h] = (uint32_t)h;
   // Rounds are CHAINED -- enqueued on the same list without the host looking at the report in between -- while most of the list is
@@ -234,6 +271,48 @@ int register_batch_group(so_icp_ctx* c, const float* d_scan, size_t n, const dou
   }
   if (keep) {  // (host memory only: the records themselves are where the kernels wrote them)
     for (int h = 0; h < B; ++h) fill_correspondence_record(keep->rec[(size_t)(base + h)], b.h_states[h], poses_in + 7 * (size_t)h, n, ep);
+  }
+  return SO_ICP_OK;
+}
+
+// so_icp_match_batch: the matching half of one outer iteration and the evaluation at the guess for the B hypotheses of a group -- the
+// group's set-up with the bounds of a match (one outer iteration, no LM iteration: plan_registration, icp_context.cpp), round 0's sweep,
+// and match_batch_kernel in place of the persistent solve.  One copy of begin arguments + list, 3 + 1 + 1 launches, one copy of the state
+// blocks, one synchronisation.  Nothing here waits inside a launch, so the group is as large as the buffers allow whatever is resident.
+int match_batch_group(so_icp_ctx* c, const float* d_scan, size_t n, const double* poses, int B, so_icp_stats* stats_io, int32_t* hyp_rc,
+                      const int pos[3], int count_5x5, int base, so_icp_ctx::KeptSets* keep) {
+  const auto t_begin = std::chrono::steady_clock::now();
+  BatchGroup g;
+  int rc = batch_group_header(c, n, poses, B, nullptr, stats_io, hyp_rc, pos, count_5x5, g);
+  if (rc <= 0) return rc;
+  if ((rc = batch_group_begin(c, "so_icp_match_batch", d_scan, n, poses, B, /*max_outer=*/1, /*lm_max=*/0, base, keep, g))) return rc;
+  so_icp_ctx::BatchBufs& b = c->batch;
+  hipStream_t s = c->stream;
+  // the hypotheses' arrival counters (reg_plan.h: match_batch_ticket_word): zero for every call, whatever a launch before left
+  static_assert(match_batch_ticket_word(1, kSyncBytes / 4) * 4 == (size_t)kSyncBytes, "one counter at the start of every hypothesis' hand-off block");
+  HIP_TRY(c, hipMemset2DAsync(b.sync.p, kSyncBytes, 0, 4, (size_t)B, s));
+  if (n) {  // round 0's sweep: the full pass at once (hypotheses +-0.5 m / +-5 degrees off)
+    MatchParams mp_it = g.mp;
+    mp_it.skip_near_pass = 1; mp_it.pack_light = 0;
+    launch_knn_plane(b.binned.as<float4>(), b.chunks.as<uint32_t>(), g.ds, c->view, mp_it, g.corr, b.nbr5.as<uint32_t>(), b.hist.as<int32_t>(), s, nullptr,
+                     nullptr, &g.bv, (uint32_t)B);
+  }
+  launch_match_batch(d_scan, n ? d_scan + 1 : nullptr, n ? d_scan + 2 : nullptr, g.corr, g.ds, g.ep, b.partials.as<double>(), b.sync.as<uint32_t>(), b.hist.as<int32_t>(), c->view,
+                     b.nbr5.as<uint32_t>(), g.mp, g.bv, (uint32_t)B, s);
+  HIP_TRY(c, hipGetLastError());
+  HIP_TRY(c, hipMemcpyAsync(b.h_states, g.ds, (size_t)B * sizeof(DevState), hipMemcpyDeviceToHost, s));
+  HIP_TRY(c, hipStreamSynchronize(s));
+  const double ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_begin).count();
+  for (int h = 0; h < B; ++h) {
+    const DevState& H = b.h_states[h];
+    if (!H.reg_done || H.n_iterations != 1)
+      return fail(c, SO_ICP_E_HIP, "so_icp_match_batch: hypothesis " + std::to_string(base + h) + " was not reported by the device");
+    double pose_unused[7];
+    fill_result(c, H, poses + 7 * (size_t)h, g.stats + h, pose_unused, false);
+    g.stats[h].time_elapsed_ms = ms;  // (of the whole group)
+  }
+  if (keep) {  // (host memory only: the records themselves are where the kernels wrote them)
+    for (int h = 0; h < B; ++h) fill_correspondence_record(keep->rec[(size_t)(base + h)], b.h_states[h], poses + 7 * (size_t)h, n, g.ep);
   }
   return SO_ICP_OK;
 }
@@ -381,6 +460,48 @@ int so_icp_register_batch(so_icp_ctx* c, const float* xyz, const void* d_scan, s
   for (int h = 0; h < n_hyp; ++h) { if (rc_out) rc_out[h] = hyp_rc[h]; if (hyp_rc[h] == SO_ICP_OK) ++ok; }
   if (keep && !err) keep->valid = true;  // (a record is valid where its lane noted it, behind an SO_ICP_OK)
   return err ? err : ok;
+}
+
+int so_icp_match_batch(so_icp_ctx* c, const float* xyz, const void* d_scan, size_t n, size_t stride_bytes, const double* poses, int n_poses,
+                       so_icp_stats* stats, int32_t* rc_out) {
+  if (!c || !poses || !stats || n_poses < 0 || (!xyz && !d_scan && n)) return SO_ICP_E_INVALID;
+  NEED_DEVICE(c);
+  if (const int rc = refuse_pending(c, "so_icp_match_batch", kPriorsNone)) return rc;  // (a match takes no prior: whatever is pending stays)
+  HIP_TRY(c, hipSetDevice(c->cfg.device_id));
+  if (c->cfg.world_size != 1) return fail(c, SO_ICP_E_UNSUPPORTED, "so_icp_match_batch needs the whole map on one device (world_size == 1)");
+  // (c->corr_last, the single registration's set, is not this entry's: it stays as it is)
+  if (c->batch_corr) c->batch_corr->valid = false;  // (so_icp_batch_correspondences: this call replaces the batch's set, or leaves none)
+  if (n_poses == 0) return c->batch_corr_keep ? batch_corr_begin(c, nullptr, n, 0, 0) : 0;
+  const float* scan = static_cast<const float*>(d_scan);
+  if (!scan && n) {
+    const int rc = upload_scan_impl(c, xyz, n, stride_bytes, c->d_scan_own);
+    if (rc) return rc;
+    scan = c->d_scan_own.as<float>();
+  }
+  so_icp_ctx::KeptSets* keep = nullptr;
+  if (c->batch_corr_keep) {  // (the stride the groups below will use: batch_reserve never shrinks it)
+    if (const int rc = batch_corr_begin(c, scan, n, n_poses, std::max(batch_stride(n), c->batch.bs))) return rc;
+    keep = c->batch_corr.get();
+  }
+  // the map window is placed once, for pose 0, as so_icp_register_batch places it; every pose sees that map
+  int pos[3];
+  map_shift(c, poses, pos);
+  std::memcpy(c->last_pos, pos, sizeof(pos));
+  if (const int rc = upload_map(c)) return rc;
+  const int count = map_count_5x5(c, pos);
+  std::vector<int32_t> hrc((size_t)n_poses, 0);
+  for (int base = 0; base < n_poses; base += kBatchMaxConcurrent) {
+    const int B = std::min(kBatchMaxConcurrent, n_poses - base);
+    const int rc = match_batch_group(c, scan, n, poses + 7 * (size_t)base, B, stats + base, hrc.data() + base, pos, count, base, keep);
+    if (rc < 0) return rc;
+  }
+  int ok = 0;
+  for (int h = 0; h < n_poses; ++h) { if (rc_out) rc_out[h] = hrc[(size_t)h]; if (hrc[(size_t)h] == SO_ICP_OK) ++ok; }
+  if (keep) {
+    for (int h = 0; h < n_poses; ++h) keep->rec[(size_t)h].valid = keep->rec[(size_t)h].valid && hrc[(size_t)h] == SO_ICP_OK;
+    keep->valid = true;
+  }
+  return ok;
 }
 
 }  // extern "C"

@@ -277,6 +277,12 @@ void launch_solve_batch(int lm_max, const float* spx, const float* spy, const fl
                         const EvalParams& ep, double* d_partials, uint32_t* d_ticket, int32_t* d_hist, const DevMapView& map,
                         const uint32_t* d_nbr5, const MatchParams& mp, const BatchView& bv, uint32_t n_hyp, hipStream_t s,
                         const double* d_prior_table = nullptr);
+// so_icp_match_batch: the fit pass and the evaluation at the guess of the hypotheses bv.active[0 .. n_hyp) in one launch of
+// n_hyp * bv.v_grid workgroups (match_batch_kernel; bv.wg_per_hyp is not read: no workgroup has to be resident beside another).
+// A hypothesis' arrival counter -- word match_batch_ticket_word(h, bv.sync_stride) of d_ticket, reg_plan.h -- must be zero.
+void launch_match_batch(const float* spx, const float* spy, const float* spz, const CorrBuffers& corr, DevState* st, const EvalParams& ep,
+                        double* d_partials, uint32_t* d_ticket, int32_t* d_hist, const DevMapView& map, const uint32_t* d_nbr5,
+                        const MatchParams& mp, const BatchView& bv, uint32_t n_hyp, hipStream_t s);
 void launch_lm_step(int slot, DevState* st, const LmSums* d_sums, int32_t* d_hist, const EvalParams& ep, hipStream_t s);
 // test aid (so_icp_debug_lm_script): a script of sums for the LM controller, and what the controller left after every entry
 // (device mirrors of so_icp_lm_script_entry / so_icp_lm_script_step)

@@ -36,6 +36,7 @@
 #include "plane_factor.h"
 #include "plane_fit.h"
 #include "pose_prior.h"
+#include "reg_plan.h"
 
 namespace soicp {
 
@@ -2111,11 +2112,20 @@ __device__ __forceinline__ void store_stamps(DevState* st, const PassStamps& T, 
 // `mine` is stored and counted; workgroup 0 waits for the count, adds the records and runs lm_control (st->lm_more and
 // st->eval_pose tell the next launch what to do) or, !fuse_lm, leaves the sums in `out`.
 // PRIOR: the sums of the pass -- the controller's and those in `out` -- carry the pose prior `prior` at `pose`, the pass's pose.
-template <bool FIT, bool PROF, bool PRIOR = false>
+// LAST (match_batch_kernel): this workgroup is number `wg` of the `nwg` that hand over to ONE finisher -- not of the launch: the workgroups
+//   of one hypothesis among many --, and the finisher is whichever of them arrives last: nobody waits, so the launch needs no workgroup
+//   resident beside another.  The records and the way they travel are the same (sc1 stores drained in front of the arrival, sc1 loads
+//   behind it); the arrival is ONE counter whose add returns the number of arrivals before, `partials` / `ticket` / `hist` / `st` are the
+//   hypothesis' own, the records lie in every second word (reg_plan.h: match_batch_partial_word), and nothing goes to `out`.
+template <bool FIT, bool PROF, bool PRIOR = false, bool LAST = false>
 __device__ __forceinline__ int hand_over_ticketed(int slot, int fuse_lm, double mine, DevState* __restrict__ st, const EvalParams& ep,
                                                   double* __restrict__ partials, uint32_t* __restrict__ ticket, int32_t* __restrict__ hist,
-                                                  LmSums* __restrict__ out, EvalShared& sh, PassStamps& T, const Pose& pose, const double* prior) {
+                                                  LmSums* __restrict__ out, EvalShared& sh, PassStamps& T, const Pose& pose, const double* prior,
+                                                  uint32_t wg_if_last = 0, uint32_t nwg_if_last = 0) {
   const int tid = threadIdx.x;
+  const uint32_t wg = LAST ? wg_if_last : blockIdx.x, nwg = LAST ? nwg_if_last : gridDim.x;
+  constexpr int kWord = LAST ? 2 : 1;  // words from one record value to the next
+  static_assert(!LAST || !PRIOR, "a match carries no prior");
   const int abl = PROF ? ep.ablate : 0;
   const bool stamp = PROF && (abl & 128) != 0;
   // The record goes to the finisher WITHOUT release/acquire fences (each costs microseconds on gfx950): the 29
@@ -2123,14 +2133,26 @@ __device__ __forceinline__ int hand_over_ticketed(int slot, int fuse_lm, double 
   // storing wave before the arrival ticket; the consumer reads them with agent-scope relaxed atomic loads
   // (sc1: served by L2, never a stale L1 line).  [MI355X guide, G16 "8-B agent atomics both sides"]
   if (tid < kNAcc)
-    __hip_atomic_store(&partials[(size_t)tid * kPartStride + blockIdx.x], mine, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    __hip_atomic_store(&partials[((size_t)tid * kPartStride + wg) * kWord], mine, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
   if (FIT && tid >= 32 && tid < 48 && sh.lh[tid - 32])  // histograms: device-scope atomics on 16 replicas, visible before the ticket
-    __hip_atomic_fetch_add(&hist[(blockIdx.x % kHistReplicas) * kHistStride + (tid - 32)], sh.lh[tid - 32], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    __hip_atomic_fetch_add(&hist[(wg % kHistReplicas) * kHistStride + (tid - 32)], sh.lh[tid - 32], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
   __syncthreads();
   if (stamp) T.red = wall_clock64();
   // Arrival: one fire-and-forget add per workgroup, spread over 16 counters on separate lines (256 adds on ONE word
   // serialise for ~2 us); workgroup 0 is the designated finisher and polls the 16 counters with one 16-lane load.
+  if constexpr (LAST) {
+    // Every record of this workgroup is in memory (sc1 stores, drained by every storing wavefront in front of the barrier above) when
+    // its one add goes out; the workgroup that counts nwg - 1 arrivals before its own finds all of them with sc1 loads.  It leaves the
+    // counter at zero for the next call (the host clears it in front of every launch as well).
+    if (tid == 0) {
+      const uint32_t before = __hip_atomic_fetch_add(ticket, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+      sh.is_last = before + 1u == nwg;
+      if (sh.is_last) __hip_atomic_store(ticket, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    }
+    __syncthreads();
+    if (!sh.is_last) return kPassNotLast;
+  } else {
   if (tid == 0) __hip_atomic_fetch_add(&ticket[(blockIdx.x & (kArriveCounters - 1)) * kArriveStrideWords], 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
   if (blockIdx.x != 0) return kPassNotLast;
   if (tid < 64) {
@@ -2149,6 +2171,7 @@ __device__ __forceinline__ int hand_over_ticketed(int slot, int fuse_lm, double 
   }
   __syncthreads();
   if (!sh.is_last) return kPassNotLast;  // timeout: the solve is abandoned, the host reports the missing publication
+  }
   if (stamp) T.arrived = wall_clock64();
   // thread b fetches workgroup b's record from the transposed table partials[a][b] (coalesced: 4 lines per wave
   // load).  The compiler serialises agent-scope atomic loads with a vmcnt(0) after each (6 us measured), so the 29
@@ -2159,11 +2182,11 @@ __device__ __forceinline__ int hand_over_ticketed(int slot, int fuse_lm, double 
     bool have[kRec];
 #pragma unroll
     for (int q = 0; q < kRec; ++q) {
-      have[q] = (uint32_t)(tid + 256 * q) < gridDim.x;  // no divergence around the asm: a register copy before the wait would read garbage
-      const double* rec = partials + (have[q] ? tid + 256 * q : 0);
+      have[q] = (uint32_t)(tid + 256 * q) < nwg;  // no divergence around the asm: a register copy before the wait would read garbage
+      const double* rec = partials + (have[q] ? tid + 256 * q : 0) * kWord;
 #pragma unroll
       for (int a = 0; a < kNAcc; ++a)
-        asm volatile("global_load_dwordx2 %0, %1, off sc1" : "=v"(r[q][a]) : "v"(rec + a * kPartStride) : "memory");
+        asm volatile("global_load_dwordx2 %0, %1, off sc1" : "=v"(r[q][a]) : "v"(rec + a * kPartStride * kWord) : "memory");
     }
     if (fuse_lm) {  // (coherent loads: cheap insurance, one word per thread)
       if (tid < (int)(sizeof(LmState) / 8))
@@ -2205,7 +2228,7 @@ __device__ __forceinline__ int hand_over_ticketed(int slot, int fuse_lm, double 
     o[kNAcc + (tid - 32)] = (double)h;
   }
   __syncthreads();
-  copy_words(reinterpret_cast<double*>(out), o, (int)(sizeof(LmSums) / 8), tid, 256);
+  if constexpr (!LAST) copy_words(reinterpret_cast<double*>(out), o, (int)(sizeof(LmSums) / 8), tid, 256);
   if (stamp) T.sums = wall_clock64();
   if (!fuse_lm) return kPassSums;  // sharded map: the sums are all-reduced first, lm_step_kernel runs the controller
   if (tid == 0) sh.more = (abl & 32) ? 1 : lm_control(slot, st, sh.S, sh.sums, sh.ctl);  // sh.S / sh.ctl arrived with the partials
@@ -2240,8 +2263,17 @@ struct WgSpan { uint32_t vb0, vb1, V; bool ctl; };
 //         block of the prior table in memory (kBatchPriorStride doubles, solve_kernel_batch_prior); its mode word says whether the
 //         hypothesis carries a prior at all, and the controller's wavefront prepares behind the wait for the records -- the launch is
 //         at the register cap, and a pass of a hypothesis on a few workgroups is long against the 55 loads
+// MATCH : so_icp_match_batch (match_batch_kernel), a per-evaluation pass (not PERSIST) of ONE virtual workgroup, span.vb0 of the
+//         span.V a single registration launches, of one hypothesis among those of the launch: the workgroup's index and grid come from
+//         `span` instead of blockIdx / gridDim, and the hand-over goes to the hypothesis' last arriver (hand_over_ticketed, LAST)
 constexpr int kPriorAtGuess = 2, kPriorBatch = 3;
-template <bool FIT, bool PERSIST = false, bool PROF = false, bool BATCH = false, bool PEER = false, int PRIOR = 0>
+#ifndef SO_MATCH_BATCH_ONE_PER_TRIP
+// The fit loop of a MATCH pass: 0 two queries per trip with their gathers issued together (the single launch's), 1 one per trip (the
+// batched solve's).  Both fit 252 registers without scratch and LDS admits two workgroups per compute unit either way; measured on
+// os1_128_2m at 64 poses the launch takes 406 us with two per trip and 424 us with one (profiles/match_batch).  Same order of accumulation.
+#define SO_MATCH_BATCH_ONE_PER_TRIP 0
+#endif
+template <bool FIT, bool PERSIST = false, bool PROF = false, bool BATCH = false, bool PEER = false, int PRIOR = 0, bool MATCH = false>
 __device__ __forceinline__ int eval_pass(int slot, int fuse_lm, const Pose& pose, const float* __restrict__ spx,
                                          const float* __restrict__ spy, const float* __restrict__ spz,
                                          const CorrBuffers& corr, DevState* __restrict__ st, const EvalParams& ep,
@@ -2267,10 +2299,12 @@ __device__ __forceinline__ int eval_pass(int slot, int fuse_lm, const Pose& pose
   static_assert(!PRIOR || !PEER, "the pose prior belongs to one device");
   static_assert(BATCH == (PRIOR == kPriorBatch) || !PRIOR, "a batch reads its priors from the table in memory, a single registration from the launch's argument");
   static_assert(PRIOR != kPriorAtGuess || PERSIST, "the prior at the guess belongs to the persistent solve");
+  static_assert(!MATCH || (FIT && !PERSIST && !BATCH && !PEER && !PRIOR), "a match is one fit pass without a prior, on one device");
   const int abl = PROF ? ep.ablate : 0;
   const bool stamp = PROF && (abl & 128) != 0;
-  const uint32_t V = BATCH ? span.V : gridDim.x;                    // workgroups of the (virtual) grid
-  const uint32_t vb_begin = BATCH ? span.vb0 : blockIdx.x, vb_end = BATCH ? span.vb1 : blockIdx.x + 1u;
+  constexpr bool kSpan = BATCH || MATCH;                            // the workgroup stands in for virtual workgroups
+  const uint32_t V = kSpan ? span.V : gridDim.x;                    // workgroups of the (virtual) grid
+  const uint32_t vb_begin = kSpan ? span.vb0 : blockIdx.x, vb_end = kSpan ? span.vb1 : blockIdx.x + 1u;
   const bool is_ctl = BATCH ? span.ctl : (blockIdx.x == 0);         // this workgroup collects the records and runs the controller
   PassStamps T;
   if (stamp) T.begin = wall_clock64();
@@ -2383,7 +2417,7 @@ __device__ __forceinline__ int eval_pass(int slot, int fuse_lm, const Pose& pose
     // then the ten neighbour points (one round trip), then the two fits.  With one wavefront per SIMD nothing else
     // hides the latency of the dependent index -> point loads (measured: 3 us of a 12 us pass).
     bool first = true;
-    if (BATCH) {
+    if (BATCH || (MATCH && SO_MATCH_BATCH_ONE_PER_TRIP != 0)) {
       // one query per trip (same order of accumulation): half the live registers, so that two workgroups fit a compute unit
       // and their wavefronts hide each other's gather and fp64 latencies -- a batch has the parallelism the single
       // registration lacks
@@ -2710,6 +2744,8 @@ __device__ __forceinline__ int eval_pass(int slot, int fuse_lm, const Pose& pose
     if (stamp && tid == 0 && (FIT || (slot == 1 && !eg_stamp))) store_stamps<FIT>(sw, T, !FIT || BATCH);
     return sh_more ? kPassMore : kPassDone;
   }
+  if constexpr (MATCH) return hand_over_ticketed<FIT, PROF, false, true>(slot, fuse_lm, mine, st, ep, partials, ticket, hist, out, sh, T, pose, prior, vb_begin, V);
+  else
   return hand_over_ticketed<FIT, PROF, PRIOR != 0>(slot, fuse_lm, mine, st, ep, partials, ticket, hist, out, sh, T, pose, prior);
 }
 
@@ -2751,6 +2787,40 @@ __global__ __launch_bounds__(256, SO_SOLVE_BLOCKS / 256) void eval_kernel_prior(
 #undef SO_BODY_KERNEL
 #undef SO_BODY_PRIOR
 #undef SO_BODY_PRIOR_WORDS
+}
+
+// so_icp_match_batch: eval_kernel<true> -- the plane fit and the evaluation at the guess -- for every hypothesis of a group in ONE launch
+// of n_act * bv.v_grid workgroups.  Workgroup b is virtual workgroup b % v_grid of hypothesis active[b / v_grid] (reg_plan.h:
+// match_batch_slot) and works on that hypothesis' slices of the batch's arrays, exactly as a workgroup of the single launch works on the
+// context's: the same queries in the same order, the same reduction, the same record.  The records of a hypothesis meet in its LAST
+// arriver (hand_over_ticketed, LAST), which adds them in the single launch's order and runs the one-thread controller with the bounds the
+// prologue stored (max_outer 1, lm_max 0: lm_begin ends the solve, and the registration, with the sums of the guess).  No workgroup waits
+// for another, so the grid may be any size: nothing of the batched solve's residency rules applies.
+// An EMPTY scan (ep.n_queries == 0: v_grid is 1) had no binning launch in front, which carries a batch's prologue: it is run here.
+template <bool PROF>
+__global__ __launch_bounds__(256, 2) void match_batch_kernel(const float* __restrict__ spx, const float* __restrict__ spy, const float* __restrict__ spz,
+                                                             CorrBuffers corr, DevState* __restrict__ st, EvalParams ep,
+                                                             double* __restrict__ partials, uint32_t* __restrict__ ticket,
+                                                             int32_t* __restrict__ hist, const float4* __restrict__ mpts,
+                                                             const uint32_t* __restrict__ nbr5, MatchParams mp, BatchView bv) {
+  __shared__ EvalShared sh;
+  const host::MatchBatchSlot w = host::match_batch_slot(blockIdx.x, bv.v_grid);
+  const size_t h = bv.active[w.entry];
+  st += h; corr.nd += h * bv.bs; corr.coeff += h * bv.bs; corr.status += h * bv.bs; nbr5 += h * 5 * bv.bs;
+  partials += host::match_batch_partial_word(h, bv.partial_stride, 0, 0, kPartStride);
+  ticket += host::match_batch_ticket_word(h, bv.sync_stride);
+  hist += h * (kHistReplicas * kHistStride);
+  const RegBeginArgs* begin = bv.begin + h;
+  if (ep.n_queries == 0) {  // (uniform over the launch)
+    hist[threadIdx.x] = 0; hist[256 + threadIdx.x] = 0;
+    reg_begin_state(st, *begin, threadIdx.x);
+    __threadfence_block();  // (the finisher below is this workgroup: one virtual workgroup per hypothesis)
+    __syncthreads();
+  }
+  const Pose pose = pose_from_array(begin->pose);  // (= DevState::T, where the prologue put the guess)
+  const WgSpan span{w.vb, w.vb + 1u, bv.v_grid, false};
+  (void)eval_pass<true, false, PROF, false, false, 0, true>(0, 1, pose, spx, spy, spz, corr, st, ep, partials, ticket, hist, nullptr, mpts, nbr5, mp, sh, nullptr,
+                                                            0, nullptr, nullptr, 0, span);
 }
 
 // The whole solve of one outer iteration in ONE launch (single device): slot 0 = plane fit + first evaluation, then up
@@ -3146,6 +3216,13 @@ void launch_solve_batch(int lm_max, const float* spx, const float* spy, const fl
   auto* k = prof ? solve_kernel<true, true> : solve_kernel<false, true>;
   hipLaunchKernelGGL(k, dim3(n_hyp * bv.wg_per_hyp), dim3(256), 0, s, lm_max, spx, spy, spz, corr, st, ep, partials, ticket, hist, (LmSums*)nullptr, map.pts,
                      nbr5, mp, bv);
+}
+void launch_match_batch(const float* spx, const float* spy, const float* spz, const CorrBuffers& corr, DevState* st, const EvalParams& ep,
+                        double* partials, uint32_t* ticket, int32_t* hist, const DevMapView& map, const uint32_t* nbr5, const MatchParams& mp,
+                        const BatchView& bv, uint32_t n_hyp, hipStream_t s) {
+  if (!n_hyp || !bv.v_grid) return;
+  auto* k = (ep.ablate != 0 || mp.ablate != 0) ? match_batch_kernel<true> : match_batch_kernel<false>;
+  hipLaunchKernelGGL(k, dim3(n_hyp * bv.v_grid), dim3(256), 0, s, spx, spy, spz, corr, st, ep, partials, ticket, hist, map.pts, nbr5, mp, bv);
 }
 void launch_lm_step(int slot, DevState* st, const LmSums* sums, int32_t* hist, const EvalParams& ep, hipStream_t s) {
   hipLaunchKernelGGL(lm_step_kernel, dim3(1), dim3(64), 0, s, slot, st, sums, hist, ep);

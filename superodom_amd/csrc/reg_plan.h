@@ -46,6 +46,22 @@ inline BatchSolveKernelKind batch_solve_kernel(const uint8_t* modes, const uint3
   return kBatchSolvePlain;
 }
 
+// so_icp_match_batch: the one launch that fits and evaluates every (hypothesis, query) of a group (match_batch_kernel) has n_act * V
+// workgroups, V the grid a single registration of the same scan launches for its fit pass.  Workgroup b serves virtual workgroup b % V of
+// the hypothesis active[b / V] -- the workgroups of a hypothesis are consecutive, so they are dispatched together.  constexpr: the
+// kernel calls these too
+struct MatchBatchSlot { uint32_t entry, vb; };  // entry: index into the launch's active list
+constexpr MatchBatchSlot match_batch_slot(uint32_t b, uint32_t V) { return MatchBatchSlot{b / V, b - (b / V) * V}; }
+// Where hypothesis h keeps the workgroup records of that launch and counts their arrivals: inside ITS share of the batch's record table
+// (partial_stride doubles per hypothesis, BatchView) and of the hand-off block (sync_stride words per hypothesis).  The record table is
+// the batched solve's, 16-byte chunks {value, pass tag | counter}: the match writes value a of virtual workgroup vb into the VALUE half of
+// chunk a * max_grid + vb and never a tag, so a solve launch behind it on the same context finds no chunk that claims to be of its pass.
+// The arrival counter is word 0 of the hypothesis' hand-off block (the first arrival counter; the batched solve uses none of them).
+constexpr size_t match_batch_partial_word(size_t h, uint32_t partial_stride, uint32_t a, uint32_t vb, uint32_t max_grid) {
+  return h * partial_stride + 2u * ((size_t)a * max_grid + vb);
+}
+constexpr size_t match_batch_ticket_word(size_t h, uint32_t sync_stride) { return h * sync_stride; }
+
 // so_icp_batch_correspondences: the layout of one export over a selection of the last batch's hypotheses.
 // Entry k of the selection is hypothesis hyp[k] (hyp == nullptr: k).  -> the first entry whose index lies outside [0, n_hyp), -1: none
 inline int batch_selection_first_bad(const int32_t* hyp, int n_sel, int n_hyp) {
