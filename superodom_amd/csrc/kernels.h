@@ -24,6 +24,12 @@
 #ifndef SO_PTOL_AT_PROPOSAL
 #define SO_PTOL_AT_PROPOSAL 1
 #endif
+// A/B switch of the k-NN sweep's second passes (profiles/knn_second_pass; knn_plane_kernel):
+//   SO_KNN_BOUNDED_FULL     a lane that reaches the FULL pass behind a near pass with five exact neighbours in hand searches the ball of
+//                           its exact 5th distance instead of the gate ball: cell range, filter radius and certified radius (0: gate radius)
+#ifndef SO_KNN_BOUNDED_FULL
+#define SO_KNN_BOUNDED_FULL 1
+#endif
 
 namespace soicp {
 

@@ -425,7 +425,10 @@ __device__ __forceinline__ uint32_t knn27(const DevMapView& m, const CellRef& c,
 // bound); exact 5th distance below R2 => the list is the exact 5-NN.
 // Two passes: NEAR (radius = half a cell => 2x2x2 cells for an octant chunk, a third of the candidates) and, only for
 // lanes it could not certify, FULL (the reference's gate radius sqrt(3*planeRes), where "not inside the gate ball" is a
-// certain TOO_FAR).  What is still uncertified (8 near-equidistant candidates, or a block with more than 2048
+// certain TOO_FAR).  A lane that reaches the FULL pass with five exact neighbours from the near pass in hand searches only the
+// ball of its exact 5th distance (full_pass_radius, SO_KNN_BOUNDED_FULL): no member of the true 5-NN is farther, so cell range,
+// filter radius (the group's largest) and certified radius shrink from the gate's 0.775 m to ~0.45 m at planeRes 0.2.
+// What is still uncertified (8 near-equidistant candidates, or a block with more than 2048
 // candidates) falls back to the per-lane exact scan knn27().  Result: bit-identical neighbour lists to the oracle.
 // LIGHT chunks (<= 16 queries: 44 % of the chunks of a 128-beam sweep) are PACKED four to a wavefront, one per row of 16
 // lanes (round 4, SO_KNN_PACK / MatchParams::pack_light): the same two passes with the block bounds, the row table and the
@@ -587,6 +590,13 @@ __device__ __forceinline__ void survivors_to_canon(const Net8& net, const uint32
     canon[t] = (ks[t] == kKeyEmpty || jl >= n_valid) ? 0xFFFFFFFFu : tile_canon[jl < tile_cap ? jl : 0u];
   }
 }
+// Radius of a lane's FULL pass behind a near pass (SO_KNN_BOUNDED_FULL).  `b4` is the lane's 5th key after the near pass's exact re-rank:
+// five real points of the lane's cube with reference-arithmetic distances, so no member of the true 5-NN is farther than its d2 (ties
+// at exactly that d2 included).  The ball of sqrt(d2), widened the way r_gate is derived from the gate, is all the full pass has to
+// search; a lane with fewer than five neighbours in hand (b4 = none), or a 5th beyond the gate, keeps the gate radius.
+__device__ __forceinline__ float full_pass_radius(float r_gate, unsigned long long b4) {
+  return b4 != ~0ull ? fminf(r_gate, sqrtf(__uint_as_float((uint32_t)(b4 >> 32))) * 1.0005f + 1e-4f) : r_gate;
+}
 #ifndef SO_KNN_PACK
 #define SO_KNN_PACK 1  // four light chunks (<= 16 queries each) per wavefront, one per row of 16 lanes (see knn_plane_kernel)
 #endif
@@ -685,7 +695,7 @@ __global__ __launch_bounds__(256, 4) void knn_plane_kernel(const float4* __restr
   uint32_t* rowbeg = rowtab[wv][1];
   const int abl = PROF ? mp.ablate : 0;  // profiling / test switches exist only in the PROF instantiation (launched when SOICP_ABLATE is set)
   const bool stamp = PROF && (abl & 128) != 0 && mp.kdbg != nullptr;
-  unsigned long long ts[4] = {0, 0, 0, 0}, acc[5] = {0, 0, 0, 0, 0}, t_first = 0, n_mine = 0, t_maxchunk = 0;
+  unsigned long long ts[4] = {0, 0, 0, 0}, acc[5] = {0, 0, 0, 0, 0}, pacc[5] = {0, 0, 0, 0, 0}, tp[2] = {0, 0}, t_first = 0, n_mine = 0, t_maxchunk = 0;
   unsigned long long n_cand_total = 0, n_q_total = 0, n_groups_total = 0, n_pass2 = 0, max_info = 0, n_fb_total = 0;
   unsigned long long c_first = 0, t_item0 = 0;
   if (stamp) { t_first = wall_clock64(); c_first = clock64(); }
@@ -819,15 +829,17 @@ __global__ __launch_bounds__(256, 4) void knn_plane_kernel(const float4* __restr
   //      and a lane in another cube than its row's first, is left to the group passes below; so is every lane the near pass
   //      cannot certify (full pass) -- the results are the same exact lists either way.
   if constexpr (packed) if (first_pass == 0 && !(abl & 2))
-  for (int ppass = 0; ppass < 2; ++ppass) {  // near pass, then -- for the rows that still have uncertified lanes -- the full pass (gate radius)
+  for (int ppass = 0; ppass < 2; ++ppass) {  // near pass, then -- for the rows that still have uncertified lanes -- the full pass (each lane's full_pass_radius)
     const bool pend = !resolved && !need_exact;
     if (ppass == 1 && __ballot(pend) == 0ull) break;
     if (ppass == 1) __builtin_amdgcn_s_setprio(3);  // (a wavefront with a second pass ahead is one of the sweep's stragglers: issue priority from here on)
     if (PROF) ++n_groups;
+    if (stamp) tp[0] = wall_clock64();  // (packed wavefronts: row set-up -> acc[1], staging + scan -> acc[2], certification -> acc[3]; pacc[] below)
     const int myslot = (int)(ckey >> 18);
     const int gslot = row_min_i32(pend ? myslot : 0x7FFFFFFF);
     const bool mine = pend && myslot == gslot;
-    const float r_cover = ppass == 0 ? r_near : r_gate;
+    // (full pass: per lane, the ball of the near pass's exact 5th distance -- full_pass_radius)
+    const float r_cover = ppass == 0 ? r_near : (SO_KNN_BOUNDED_FULL ? full_pass_radius(r_gate, top.b4) : r_gate);
     const int lo_x = max(0, (int)floorf((ux - r_cover) * inv_cellf)), hi_x = min(nc - 1, (int)floorf((ux + r_cover) * inv_cellf));
     const int lo_y = max(0, (int)floorf((uy - r_cover) * inv_cellf)), hi_y = min(nc - 1, (int)floorf((uy + r_cover) * inv_cellf));
     const int lo_z = max(0, (int)floorf((uz - r_cover) * inv_cellf)), hi_z = min(nc - 1, (int)floorf((uz + r_cover) * inv_cellf));
@@ -839,8 +851,8 @@ __global__ __launch_bounds__(256, 4) void knn_plane_kernel(const float4* __restr
     // squared distance from the query to the faces of the block (a face on the cube's boundary has nothing of the cube behind
     // it), capped by the filter radius: formed here, while the bounds are at hand (six registers less across the scan)
     float cv = block_cover_distance(bx0, bx1, by0, by1, bz0, bz1, nc, cell, ux, uy, uz);
-    if (ppass == 1) cv = 1e15f;   // (the full pass's block contains the lane's whole gate ball by construction)
-    const float cov2p = fminf(cv * cv, r_cover * r_cover);  // (candidates beyond r_cover of every lane of the group are not staged)
+    if (ppass == 1) cv = 1e15f;   // (the full pass's block contains the whole ball of the lane's radius by construction)
+    const float cov2p = fminf(cv * cv, r_cover * r_cover);  // (candidates beyond r_cover of every lane of the group are not staged; the lane's own radius)
     // row table of the part's block: lane r of the row fetches the bounds of x-run r, inclusive scan over the row
     uint32_t vb = 0, vl = 0;
     if (part_ok && (int)lane16 < nrows) {
@@ -870,7 +882,8 @@ __global__ __launch_bounds__(256, 4) void knn_plane_kernel(const float4* __restr
     const float pinf = __int_as_float(0x7F800000);
     const float bl0 = row_min_f32(mine ? lqx : pinf), bl1 = row_min_f32(mine ? lqy : pinf), bl2 = row_min_f32(mine ? lqz : pinf);
     const float bh0 = -row_min_f32(mine ? -lqx : pinf), bh1 = -row_min_f32(mine ? -lqy : pinf), bh2 = -row_min_f32(mine ? -lqz : pinf);
-    const float dk = r_cover + 2e-4f, dk2 = dk * dk;
+    // filter radius: the largest radius among the row's lanes (the near pass's is the same for all of them)
+    const float dk = ((SO_KNN_BOUNDED_FULL && ppass == 1) ? -row_min_f32(mine ? -r_cover : pinf) : r_cover) + 2e-4f, dk2 = dk * dk;
     const uint32_t tbase = part * kPartTile;
     const uint32_t tot_eff = part_ok ? total : 0u;
     const uint32_t tmax = max_over_rows(tot_eff);
@@ -884,7 +897,7 @@ __global__ __launch_bounds__(256, 4) void knn_plane_kernel(const float4* __restr
     // filtered against the row's box and compacted into the row's quarter of the tile in enumeration order.
     auto stage = [&](const uint32_t tot, const uint32_t tend, const uint32_t gl /*lane in the group*/, const uint32_t width, const uint32_t shift,
                      const uint32_t* poff, const uint32_t* pbeg, const uint32_t tb, const double sx, const double sy, const double sz,
-                     const float l0, const float l1, const float l2, const float h0, const float h1, const float h2) -> uint32_t {
+                     const float l0, const float l1, const float l2, const float h0, const float h1, const float h2, const float dk2s /*the row's dk2*/) -> uint32_t {
       uint32_t kept = 0;
       const unsigned long long gmask = width == 64u ? ~0ull : 0xFFFFull;
       for (uint32_t t0 = 0; t0 < tend; t0 += 4u * width) {
@@ -912,7 +925,7 @@ __global__ __launch_bounds__(256, 4) void knn_plane_kernel(const float4* __restr
             lx = (float)((double)px_[u] - sx); ly = (float)((double)py_[u] - sy); lz = (float)((double)pz_[u] - sz);
             lc = __builtin_fmaf(lz, lz, __builtin_fmaf(ly, ly, lx * lx));
             const float ex = fmaxf(fmaxf(l0 - lx, lx - h0), 0.f), ey = fmaxf(fmaxf(l1 - ly, ly - h1), 0.f), ez = fmaxf(fmaxf(l2 - lz, lz - h2), 0.f);
-            kp = __builtin_fmaf(ez, ez, __builtin_fmaf(ey, ey, ex * ex)) <= dk2;
+            kp = __builtin_fmaf(ez, ez, __builtin_fmaf(ey, ey, ex * ex)) <= dk2s;
           }
           const unsigned long long mg = (__ballot(kp) >> shift) & gmask;
           const uint32_t pos = kept + (uint32_t)__popcll(mg & ((1ull << gl) - 1ull));
@@ -922,8 +935,9 @@ __global__ __launch_bounds__(256, 4) void knn_plane_kernel(const float4* __restr
       }
       return kept;
     };
+    if (stamp) { tp[1] = wall_clock64(); acc[1] += tp[1] - tp[0]; }
     if (ppass == 0) {
-      w = stage(tot_eff, tmax, lane16, 16u, part * 16u, prowoff, prowbeg, tbase, rox, roy, roz, bl0, bl1, bl2, bh0, bh1, bh2);
+      w = stage(tot_eff, tmax, lane16, 16u, part * 16u, prowoff, prowbeg, tbase, rox, roy, roz, bl0, bl1, bl2, bh0, bh1, bh2, dk2);
     } else {
       for (int rr = 0; rr < 4; ++rr) {  // one row after the other, all 64 lanes on it (row-uniform values from the row's first lane)
         const int src = rr * 16;
@@ -932,12 +946,13 @@ __global__ __launch_bounds__(256, 4) void knn_plane_kernel(const float4* __restr
 #define SO_RL_F(v) __int_as_float(__builtin_amdgcn_readlane(__float_as_int(v), src))
 #define SO_RL_D(v) __hiloint2double(__builtin_amdgcn_readlane(__double2hiint(v), src), __builtin_amdgcn_readlane(__double2loint(v), src))
         const uint32_t wr = stage(tot_r, tot_r, (uint32_t)lane, 64u, 0u, rowoff + rr * 17, rowbeg + rr * 16, (uint32_t)rr * kPartTile,
-                                  SO_RL_D(rox), SO_RL_D(roy), SO_RL_D(roz), SO_RL_F(bl0), SO_RL_F(bl1), SO_RL_F(bl2), SO_RL_F(bh0), SO_RL_F(bh1), SO_RL_F(bh2));
+                                  SO_RL_D(rox), SO_RL_D(roy), SO_RL_D(roz), SO_RL_F(bl0), SO_RL_F(bl1), SO_RL_F(bl2), SO_RL_F(bh0), SO_RL_F(bh1), SO_RL_F(bh2), SO_KNN_BOUNDED_FULL ? SO_RL_F(dk2) : dk2);
 #undef SO_RL_F
 #undef SO_RL_D
         if ((int)part == rr) w = wr;
       }
     }
+    if (stamp) { tp[0] = wall_clock64(); pacc[ppass] += tp[0] - tp[1]; }
     if (PROF && lane16 == 0 && gslot != 0x7FFFFFFF) {  // statistics: rows with work / left to the group passes (x-runs, kept candidates) / kept candidates
       atomicAdd(&lh[20], 1);
       if (!(part_ok && w <= kPartTile)) atomicAdd(&lh[nrows > 16 || nrows < 1 ? 21 : 22], 1);
@@ -966,6 +981,7 @@ __global__ __launch_bounds__(256, 4) void knn_plane_kernel(const float4* __restr
       net.push(make_key(d23.x, jl + 2u, keep));
       net.push(make_key(d23.y, jl + 3u, keep));
     }
+    if (stamp) { const unsigned long long t = wall_clock64(); pacc[2] += t - tp[0]; acc[2] += t - tp[1]; tp[1] = t; }
     uint32_t gs[8];
     survivors_to_canon(net, ti + tbase, wk, kPartTile, gs);
     if (mine && part_ok) {
@@ -976,6 +992,7 @@ __global__ __launch_bounds__(256, 4) void knn_plane_kernel(const float4* __restr
     } else if (mine && ppass == 1) {
       need_exact = true;  // (a row whose full-pass block has too many x-runs or keeps more than its quarter of the tile)
     }
+    if (stamp) { const unsigned long long t = wall_clock64(); pacc[3] += t - tp[1]; acc[3] += t - tp[1]; }
   }
   // One query (lane L's) at a time, the WHOLE wavefront on it: the (clamped) 3 x 3 x 3 cells around the query -- every map point
   // inside the gate ball lies there (one cell >= the gate radius) -- as <= 9 x-runs, their points dealt to the 64 lanes with
@@ -1043,21 +1060,26 @@ __global__ __launch_bounds__(256, 4) void knn_plane_kernel(const float4* __restr
     if (left) __builtin_amdgcn_s_setprio(3);
     if (left && lane == 0 && mp.packed_leftover) atomicAdd(leftover_ctr, (uint32_t)__popcll(left));
     if (PROF) n_left_stat = (uint32_t)__popcll(left);
+    if (stamp) tp[0] = wall_clock64();
     while (left) {
       const int L = __ffsll((long long)left) - 1;
       left &= left - 1ull;
       coop_exact_scan(L);
     }
+    if (stamp) pacc[4] += wall_clock64() - tp[0];
   }
   if constexpr (!packed)
   for (int pass = first_pass; pass < 2; ++pass) {
   bool pending = !resolved && !need_exact;
   unsigned long long todo = __ballot(pending);
   if (abl & 2) todo = 0;
-  if (!todo) continue;  // (a packed wavefront may have nothing left for the near pass and still lanes for the full pass)
+  if (!todo) continue;  // (nothing pending in this pass)
   if (pass == 1 && first_pass == 0) __builtin_amdgcn_s_setprio(3);  // (a second pass: one of the sweep's stragglers -- issue priority from here on)
   if (stamp && pass == 1) ++n_pass2;
-  const float r_cover = pass == 0 ? r_near : r_gate;
+  // (a full pass behind a near pass: per lane, the ball of the near pass's exact 5th distance -- full_pass_radius.  Formed from top.b4
+  //  where it is needed, not carried across the group loop: the kernel has no register to spare)
+  const bool bounded = SO_KNN_BOUNDED_FULL && pass == 1 && first_pass == 0;
+  const float r_cover = pass == 0 ? r_near : (bounded ? full_pass_radius(r_gate, top.b4) : r_gate);
   // per-lane cell range that contains the lane's search ball (clamped to the cube: nothing of the cube lies beyond it)
   const int lo_x = max(0, (int)floorf((ux - r_cover) * inv_cellf)), hi_x = min(nc - 1, (int)floorf((ux + r_cover) * inv_cellf));
   const int lo_y = max(0, (int)floorf((uy - r_cover) * inv_cellf)), hi_y = min(nc - 1, (int)floorf((uy + r_cover) * inv_cellf));
@@ -1155,7 +1177,8 @@ __global__ __launch_bounds__(256, 4) void knn_plane_kernel(const float4* __restr
       bl0 = wave_min_f32(mine ? lqx : pinf); bl1 = wave_min_f32(mine ? lqy : pinf); bl2 = wave_min_f32(mine ? lqz : pinf);
       bh0 = -wave_min_f32(mine ? -lqx : pinf); bh1 = -wave_min_f32(mine ? -lqy : pinf); bh2 = -wave_min_f32(mine ? -lqz : pinf);
     }
-    const float dk = r_cover + 2e-4f, dk2 = dk * dk;  // (block-local fp32 coordinates: errors ~1e-6 m, the margin covers them a hundredfold)
+    // (block-local fp32 coordinates: errors ~1e-6 m, the margin covers them a hundredfold; bounded full pass: the group's largest radius)
+    const float dk = ((bounded && filt) ? -wave_min_f32(mine ? -full_pass_radius(r_gate, top.b4) : __int_as_float(0x7F800000)) : r_cover) + 2e-4f, dk2 = dk * dk;
     uint32_t total_eff = total;
     if (filt) {
       // the WHOLE enumeration is filtered into the one tile; a group whose kept candidates do not fit it (dense cells in the
@@ -1285,13 +1308,14 @@ __global__ __launch_bounds__(256, 4) void knn_plane_kernel(const float4* __restr
       k6 = net.a5; k8 = net.a7;
       scanned = true;
       if (pass == 1) {
-        cov2 = 1e30f;  // the block contains the lane's whole gate ball by construction
+        cov2 = 1e30f;  // the block contains the whole ball of the lane's radius by construction: the gate ball, or ...
+        if (bounded) { const float rl = full_pass_radius(r_gate, top.b4); cov2 = rl * rl; }  // (... the ball of the lane's radius: nothing is known beyond it)
       } else {
         // distance to the faces of the scanned block; a face on the cube's boundary has nothing of the cube behind it
         const float cv = block_cover_distance(bx0, bx1, by0, by1, bz0, bz1, nc, cell, ux, uy, uz);
         cov2 = cv * cv;
       }
-      if (filt) cov2 = fminf(cov2, r_cover * r_cover);  // (candidates beyond r_cover of every lane of the group were not staged)
+      if (filt && !bounded) cov2 = fminf(cov2, r_cover * r_cover);  // (candidates beyond r_cover of every lane of the group were not staged)
     }
     if (stamp) { ts[1] = wall_clock64(); acc[3] += ts[1] - ts[3]; }
   }
@@ -1355,7 +1379,7 @@ __global__ __launch_bounds__(256, 4) void knn_plane_kernel(const float4* __restr
   if (stamp && lane_k == 0) {  // one record per wavefront, no atomics (they would perturb the measurement)
     unsigned long long* d = mp.kdbg + ((size_t)(begin ? 0 : (st->outer_iter & 1)) * gridDim.x * 4 + blockIdx.x * 4 + wv) * 16;
     d[0] = t_first; d[1] = wall_clock64();
-    for (int i = 0; i < 5; ++i) d[2 + i] = acc[i];
+    for (int i = 0; i < 5; ++i) d[2 + i] = (acc[i] & 0xFFFFFFFFull) | (pacc[i] << 32);  // (upper words: packed wavefronts -- staging of the near / full pass, scan, certification, leftover scans)
     d[15] = clock64() - c_first;  // shader-clock ticks over the wavefront's life (d[1] - d[0] = the same span at 100 MHz)
     d[7] = n_mine; d[8] = t_maxchunk; d[9] = n_cand_total; d[10] = n_q_total; d[11] = n_groups_total; d[13] = max_info;
     d[12] = n_pass2 | ((t_item0 ? t_item0 - t_entry : 0ull) << 32);  // + kernel entry -> first item begins (ticks), wavefronts with work

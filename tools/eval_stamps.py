@@ -75,6 +75,10 @@ def main():
         entry_all = (rec[..., 12].astype(np.uint64) >> np.uint64(32)).astype(np.float64) * 0.01  # kernel entry -> first item begins (us), wavefronts with work
         steals_all = np.zeros(rec.shape[:-1], np.int64)  # (the hand-over ring that used these bits is gone)
         rec = rec.copy(); rec[..., 12] = rec[..., 12].astype(np.uint64) & np.uint64(0xFFFFFFFF)
+        # upper halves of words 2..6: the phases of PACKED wavefronts (four light chunks, one per row of 16 lanes) -- staging of the near
+        # pass, staging of the full pass, scan, certification, leftover exact scans; lower halves: the five phases of every item
+        packed_all = (rec[..., 2:7].astype(np.uint64) >> np.uint64(32)).astype(np.float64) * 0.01
+        rec[..., 2:7] = rec[..., 2:7].astype(np.uint64) & np.uint64(0xFFFFFFFF)
         rec = rec.astype(np.float64)
         for o in range(2):
             r = rec[o]
@@ -132,6 +136,22 @@ def main():
                 for q in so:
                     w = single[q]
                     print("      %.1f us | %s | queries %d cand %d start %.1f" % (w[8] * 0.01, " ".join("%.1f" % (x * 0.01) for x in w[2:7]), int(w[10]), int(w[9]), (w[0] - t0) * 0.01))
+            pk = packed_all[o][rec[o][:, 0] > 0][r[:, 7] > 0]
+            isp = pk.sum(axis=1) > 0
+            if isp.any():  # packed wavefronts: set-up, staging + scan and certification are also in the five columns above
+                pw, pp = busy[isp], pk[isp]
+                print("   packed wavefronts %d: per wavefront (us): prologue %.2f  row set-up %.2f  staging near %.2f  staging full %.2f  scan %.2f  "
+                      "certification %.2f  leftover scans %.2f | life p50 %.1f max %.1f" % (
+                          (len(pw), pw[:, 2].mean() * 0.01, pw[:, 3].mean() * 0.01) + tuple(pp.mean(axis=0)) +
+                          (np.percentile((pw[:, 1] - pw[:, 0]) * 0.01, 50), ((pw[:, 1] - pw[:, 0]) * 0.01).max())))
+                print("   slowest packed wavefronts (total | prologue, row set-up | staging near, staging full, scan, certification, leftover | items, queries, candidates):")
+                for q in np.argsort(-pw[:, 8])[:6]:
+                    print("      %.1f us | %.1f %.1f | %s | items %d queries %d cand %d" % (pw[q, 8] * 0.01, pw[q, 2] * 0.01, pw[q, 3] * 0.01,
+                          " ".join("%.1f" % x for x in pp[q]), int(pw[q, 7]), int(pw[q, 10]), int(pw[q, 9])))
+            two = busy[(busy[:, 12] > 0) & (busy[:, 7] == 1) & ~isp]
+            if len(two):  # ordinary chunks that ran a full pass behind the near pass
+                print("   single-chunk wavefronts with a full pass %d: mean (us) total %.1f | prologue %.1f set-up %.1f stage+scan %.1f merge %.1f epilogue %.1f" % (
+                    (len(two), two[:, 8].mean() * 0.01) + tuple(two[:, 2:7].mean(axis=0) * 0.01)))
             idle = r[r[:, 7] == 0]
             if len(idle):
                 print("   idle workgroups: start offset p50 %.1f max %.1f us" % (np.percentile((idle[:, 0] - t0) * 0.01, 50), ((idle[:, 0] - t0) * 0.01).max()))
